@@ -25,6 +25,7 @@ FLOP_PER_SAMPLE = 1963.97e9      # conv fwd + dgrad + wgrad, 2*MAC, BASELINE.md 
 ENCODER_FLOP_PER_SAMPLE = 934.9e9   # the Xception encoder's share, forward + backward
 PEAK = {"bf16": 2.5e15, "fp32": 157.3e12}
 CLASS_FREQ = (0.986267818390377, 0.0004578708870701058, 0.01327431072255291)
+DUMP_SAMPLE = 1 << 22            # positions of the parameter and gradient arenas that --dump-outputs writes (16 MB each in fp32)
 
 
 def synthetic_batch(B, H, W, seed, device):
@@ -131,6 +132,26 @@ def torch_gpu_baseline(H, W, local_batch, dev, mode="nhwc", timed_steps=5):
     del params, sd, opt
     torch.cuda.empty_cache()
     return out
+
+
+def dump_outputs(path, step):
+    """--dump-outputs: what a caller of the timed step holds after its last step, one .npy file per array (float32 / float64), so that two
+    builds run with the same arguments can be compared output for output.  The master weights and the gradients (56 M fp32 each) are
+    written at the same fixed, seeded sample of DUMP_SAMPLE positions; the rest is written whole (about 33 MB in all)."""
+    import numpy as np
+    eng = step.eng
+    n = eng.params.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    sel = torch.from_numpy(idx).to(eng.params.device)
+    arrays = {"loss": np.array([step.loss()], dtype=np.float64),
+              "params_sample": eng.params[sel].cpu().numpy(),
+              "grads_sample": eng.grads[sel].cpu().numpy(),
+              "bn_buffers": eng.buffers.cpu().numpy(),
+              "bn_num_batches_tracked": eng.nbt.cpu().numpy().astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 class KernelTimer:
@@ -292,6 +313,8 @@ def main():
     ap.add_argument("--program", action="store_true", help="replay the step from the C-side launch list (TrainStep.enable_program: dc_program_run, "
                     "one call per step, no Python between launches).  The GPU work is the same list of launches.  With more than one rank it "
                     "needs the library's own collective (DC_GRAD_COLLECTIVE=lib: dc_grad_allreduce_enqueue / _wait over RCCL)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them left the caller "
+                    "(loss, a fixed sample of the master weights and gradients, BatchNorm buffers) as DIR/<name>.npy; rank 0 only")
     a = ap.parse_args()
 
     # timing-experiment switches that make backward skip work must never produce a bench line
@@ -398,6 +421,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss = step.loss()
+    dumped = dump_outputs(a.dump_outputs, step) if a.dump_outputs and rank == 0 else None
     sps = a.steps * B * world / dt
     comm = None
     if reducer is not None:
@@ -515,6 +539,8 @@ def main():
                "loss_last_step": round(loss, 6), "roofline": roof}
         if comm is not None:
             out["comm"] = comm
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "files": [f + ".npy" for f in dumped]}
         if world == 1:
             del step, net, opt, eng       # the engine's arenas go back to the allocator before the other configurations / baselines
             gc.collect()

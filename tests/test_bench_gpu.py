@@ -42,3 +42,32 @@ def test_default_line_carries_the_other_single_gpu_configurations():
     r = subprocess.run(cmd + ["--no_also"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "also" not in json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_dump_outputs_writes_the_last_timed_step_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: after the K timed steps the arrays the last one left (loss, the sampled master weights and gradients, BatchNorm
+    buffers) land in DIR as float32 / float64 .npy files, 64 MB at most; the same arguments give the same inputs, so two runs give the same bits."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--local_batch_size", "2", "--height", "64",
+               "--width", "96", "--no_cpu_baseline", "--no_also", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and abs(out["ms_per_step"] * out["value"] - 2e3) < 1.0
+        files = sorted(os.listdir(d))
+        assert files == sorted(out["dump_outputs"]["files"]) and "loss.npy" in files and "params_sample.npy" in files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 2 ** 20
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert abs(float(arrays["loss.npy"][0]) - out["loss_last_step"]) < 1e-6
+        assert arrays["params_sample.npy"].size == 1 << 22 and np.isfinite(arrays["grads_sample.npy"]).all()
+        assert (arrays["bn_num_batches_tracked.npy"] == 4).all()          # one warm-up + three timed steps, nothing after them
+        runs.append(arrays)
+    for f in runs[0]:
+        if f == "loss.npy":      # a double-precision atomic sum (1e-16 jitter), as in test_model_gpu.py::test_train_step_is_bit_reproducible
+            np.testing.assert_allclose(runs[0][f], runs[1][f], rtol=1e-12, atol=0)
+        else:
+            np.testing.assert_array_equal(runs[0][f], runs[1][f], err_msg=f)
