@@ -356,6 +356,18 @@ int dc_bn_bwd_apply_fin(int dtype, long M, int C, long count, const void* dout, 
                         const float* save_invstd, const float* slab, int rows, float* dgamma, float* dbeta, void* dy, int lddy,
                         void* g_out, int ldg, const float* mscale, const float* mshift, void* stream);
 
+/* Backward of o = [relu](bn(y) [+ residual]) for a BatchNorm in EVAL mode (frozen statistics), in one pass: nn.BatchNorm2d after .eval(),
+ * i.e. F.batch_norm(training=False) with running_mean / running_var, whose backward is the affine map of those statistics (torch's
+ * batch_norm_backward with train=false; deeplab_xception.py BatchNorms, autograd through a trained model).  g = dout * mask (relu 0: no
+ * mask, 1: out > 0, 2: y * mscale + mshift > 0 with the eval scale / shift of dc_bn_eval_coeffs; `out` is read for relu 1 only),
+ * dx = g * gamma * rsqrt(running_var + eps), g is also stored when g_out != NULL (the residual's gradient), and the partial sums
+ * (sum g, sum g * (y - running_mean) * rsqrt(running_var + eps)) go to slab[2][rows][C], rows = dc_bn_stat_rows(M), the layout
+ * dc_bn_bwd_reduce leaves: dc_bn_bwd_finalize(C, slab, rows, dgamma, dbeta) completes the parameter gradients.  The running statistics
+ * are read, never written. */
+int dc_bn_bwd_frozen(int dtype, long M, int C, const void* dout, int lddo, const void* y, int ldy, const void* out, int ldout, int relu,
+                     const float* gamma, const float* running_mean, const float* running_var, float eps, void* dx, int lddx,
+                     void* g_out, int ldg, float* slab, const float* mscale, const float* mshift, void* stream);
+
 /* SeparableConv2d_same.forward as ONE operator (deeplab_xception.py:62-66: depthwise 3x3 "same", then pointwise 1x1) for the entry flow's thin
  * layers: d [N,H,W,Cin] = depthwise(act(x)) -- act = the producer's BatchNorm(+ReLU), applied on load when pscale / pshift are given, as in
  * dc_dwconv_fwd, whose bits d has -- and y [N,H,W,Cout] = pointwise(d), with the BatchNorm partial sums of the stored y in slab
@@ -392,6 +404,10 @@ int dc_stem_fwd(int dtype, int N, int Cin, int H, int W, const float* x_nchw, co
 size_t dc_stem_wgrad_workspace(int N, int Cin, int H, int W);
 int dc_stem_wgrad(int dtype, int N, int Cin, int H, int W, const float* x_nchw, const void* dy, int lddy,
                   void* workspace, float* grad_w, void* stream);
+/* data gradient of the stem conv (conv2d(x, w, stride 2, padding 1) w.r.t. x, torch's convolution_backward input gradient) for any
+ * Cin <= 16: dy NHWC [N][Ho][Wo][32] `dtype` (leading dimension lddy), w the fp32 master weight [32][Cin][3][3], dx the caller's NCHW fp32
+ * [N][Cin][H][W] (8-byte aligned), OVERWRITTEN.  A gather: every element of dx is written exactly once, no atomics (deterministic). */
+int dc_stem_dgrad(int dtype, int N, int Cin, int H, int W, const void* dy, int lddy, const float* w, float* dx_nchw, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Classifier head: ConvTranspose2d(256->n_classes=3, k3, s2, p1, op1), deeplab_xception.py:374,382.

@@ -149,6 +149,109 @@ __global__ __launch_bounds__(256) void colred_kernel(long M, int C, int RED_ROWS
   }
 }
 
+// Backward of o = [relu](bn_eval(y) [+ residual]) with the RUNNING statistics (frozen BatchNorm: the batch does not enter mean and var, so
+// the backward is an affine map and needs no second pass): g = dout masked by the ReLU, dx = g * gamma * invstd_run, g itself to gout when
+// given (the residual's gradient), and the partial sums (sum g, sum g * xhat_run) of every RED_ROWS rows to slab[2][rows][C] as
+// dc_bn_bwd_reduce leaves them -- dc_bn_bwd_finalize turns them into dbeta / dgamma.  Thread layout of colred_kernel.
+template <typename T, int RED_CG>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(long M, int C, int RED_ROWS, const T* __restrict__ dout, int lddo,
+                                                            const T* __restrict__ y, int ldy, const T* __restrict__ out, int ldout, int relu,
+                                                            const float* __restrict__ gamma, const float* __restrict__ rmean,
+                                                            const float* __restrict__ rvar, float eps, T* __restrict__ dx, int lddx,
+                                                            T* __restrict__ gout, int ldg, float* __restrict__ slab,
+                                                            const float* __restrict__ mscale, const float* __restrict__ mshift) {
+  constexpr int KPV = Elem<T>::kPerVec;
+  constexpr int RED_RL = 256 / RED_CG;
+  constexpr int CW = RED_CG * KPV;
+  __shared__ __attribute__((aligned(16))) float red[2][RED_RL][CW];   // first the per-channel vectors, then the partial sums
+  const int cgl = threadIdx.x % RED_CG, rl = threadIdx.x / RED_CG;
+  const int c0 = (blockIdx.x * RED_CG + cgl) * KPV;
+  const bool cok = c0 < C;
+  float* vecs = &red[0][0][0];   // [5][CW] <= 2*RED_RL*CW floats
+  for (int i = threadIdx.x; i < CW; i += 256) {
+    const int c = blockIdx.x * CW + i;
+    const bool ok = c < C;
+    const float is = ok ? 1.f / sqrtf(rvar[c] + eps) : 0.f;
+    vecs[0 * CW + i] = ok ? rmean[c] : 0.f;
+    vecs[1 * CW + i] = is;
+    vecs[2 * CW + i] = ok ? gamma[c] * is : 0.f;
+    vecs[3 * CW + i] = (ok && relu == 2) ? mscale[c] : 0.f;
+    vecs[4 * CW + i] = (ok && relu == 2) ? mshift[c] : 0.f;
+  }
+  __syncthreads();
+  float a[KPV], b[KPV], mu[KPV], is[KPV], ca[KPV], ms[KPV], mh[KPV];
+#pragma unroll
+  for (int e = 0; e < KPV; ++e) {
+    const int i = cgl * KPV + e;
+    a[e] = b[e] = 0.f;
+    mu[e] = vecs[0 * CW + i]; is[e] = vecs[1 * CW + i]; ca[e] = vecs[2 * CW + i]; ms[e] = vecs[3 * CW + i]; mh[e] = vecs[4 * CW + i];
+  }
+  __syncthreads();   // the same LDS holds the partial sums below
+  const long rbeg = (long)blockIdx.y * RED_ROWS;
+  const long rend = rbeg + RED_ROWS < M ? rbeg + RED_ROWS : M;
+  constexpr int UR = 4;
+  if (cok) {
+    for (long r0 = rbeg + rl; r0 < rend; r0 += RED_RL * UR) {
+      vec16 vg[UR], vy[UR], vo[UR];
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const long r = r0 + RED_RL * u;
+        const long rr = r < rend ? r : rbeg;   // in range; not used below
+        vg[u] = ldg16(dout + (size_t)rr * lddo + c0);
+        vy[u] = ldg16(y + (size_t)rr * ldy + c0);
+        if (relu == 1) vo[u] = ldg16(out + (size_t)rr * ldout + c0);
+      }
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const long r = r0 + RED_RL * u;
+        if (r >= rend) break;
+        float g[KPV], x[KPV];
+        unpack(vg[u], g, T());
+        unpack(vy[u], x, T());
+        if (relu == 2) {
+#pragma unroll
+          for (int e = 0; e < KPV; ++e) g[e] = fmaf(x[e], ms[e], mh[e]) > 0.f ? g[e] : 0.f;
+        } else if (relu) {
+          float o[KPV];
+          unpack(vo[u], o, T());
+#pragma unroll
+          for (int e = 0; e < KPV; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f;
+        }
+        vec16 v;
+        if (gout != nullptr) {
+          pack(v, g, T());
+          stg16(gout + (size_t)r * ldg + c0, v);
+        }
+        float d[KPV];
+#pragma unroll
+        for (int e = 0; e < KPV; ++e) {
+          a[e] += g[e];
+          b[e] = fmaf(g[e], (x[e] - mu[e]) * is[e], b[e]);
+          d[e] = g[e] * ca[e];
+        }
+        pack(v, d, T());
+        stg16(dx + (size_t)r * lddx + c0, v);
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < KPV; ++e) {
+    red[0][rl][cgl * KPV + e] = a[e];
+    red[1][rl][cgl * KPV + e] = b[e];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * CW; i += 256) {
+    const int which = i / CW, cl = i % CW;
+    const int c = blockIdx.x * CW + cl;
+    if (c < C) {
+      float s = 0.f;
+#pragma unroll
+      for (int r = 0; r < RED_RL; ++r) s += red[which][r][cl];
+      slab[((size_t)which * gridDim.y + blockIdx.y) * C + c] = s;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void slab_fold_kernel(float* slab, int rows, int C) {
   __shared__ double red[2][FIN_RL][FIN_CH];
   slab_fold_block(slab, rows, C, red);
@@ -652,6 +755,32 @@ extern "C" int dc_bn_bwd_apply(int dtype, long M, int C, long count, const void*
                                void* g_out, int ldg, const float* mscale, const float* mshift, void* stream) {
   return bn_bwd_apply_impl(dtype, M, C, count, dout, lddo, y, ldy, out, ldout, relu, gamma, save_mean, save_invstd, dgamma, dbeta, dy, lddy, g_out, ldg,
                            mscale, mshift, stream, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int dc_bn_bwd_frozen(int dtype, long M, int C, const void* dout, int lddo, const void* y, int ldy, const void* out, int ldout,
+                                int relu, const float* gamma, const float* running_mean, const float* running_var, float eps, void* dx,
+                                int lddx, void* g_out, int ldg, float* slab, const float* mscale, const float* mshift, void* stream) {
+  if (int e = dc_check_view(dout, lddo, C, dtype, "dc_bn_bwd_frozen dout")) return e;
+  if (int e = dc_check_view(y, ldy, C, dtype, "dc_bn_bwd_frozen y")) return e;
+  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_bn_bwd_frozen dx")) return e;
+  if (relu == 1)
+    if (int e = dc_check_view(out, ldout, C, dtype, "dc_bn_bwd_frozen out")) return e;
+  if (g_out)
+    if (int e = dc_check_view(g_out, ldg, C, dtype, "dc_bn_bwd_frozen g_out")) return e;
+  DC_REQUIRE(relu >= 0 && relu <= 2, "dc_bn_bwd_frozen: relu is 0, 1 (mask from out) or 2 (mask from y * mscale + mshift)");
+  DC_REQUIRE(relu != 2 || (mscale && mshift), "dc_bn_bwd_frozen: relu == 2 needs the forward scale / shift vectors");
+  DC_REQUIRE(gamma && running_mean && running_var && slab && M > 0, "dc_bn_bwd_frozen: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int RED_ROWS = red_rows(M);        // the rows of dc_bn_stat_rows(M)
+  const int kpv = dtype == DC_BF16 ? 8 : 4;
+  const int ngroups = C / kpv, cg = narrow_cg(ngroups, RED_CG_MAX);
+  const dim3 grid(cdiv(ngroups, cg), cdiv(M, RED_ROWS));
+#define BN_FZ(TT, W) hipLaunchKernelGGL((bn_bwd_frozen_kernel<TT, W>), grid, dim3(256), 0, st, M, C, RED_ROWS, (const TT*)dout, lddo, (const TT*)y, ldy, (const TT*)out, ldout, relu, gamma, running_mean, running_var, eps, (TT*)dx, lddx, (TT*)g_out, ldg, slab, mscale, mshift)
+  if (dtype == DC_BF16) { if (cg == 32) BN_FZ(bf16, 32); else if (cg == 16) BN_FZ(bf16, 16); else if (cg == 8) BN_FZ(bf16, 8); else BN_FZ(bf16, 4); }
+  else                  { if (cg == 32) BN_FZ(float, 32); else if (cg == 16) BN_FZ(float, 16); else if (cg == 8) BN_FZ(float, 8); else BN_FZ(float, 4); }
+#undef BN_FZ
+  DC_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int dc_bn_bwd_apply_fin_max_rows(void) { return FIN_RL; }

@@ -543,6 +543,98 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------------- stem data gradient
+// dx[n][ci][h][w] = sum over the taps with h = 2*oy-1+ky, w = 2*ox-1+kx of sum_co dy[n][oy][ox][co] * w[co][ci][ky][kx], as a gather: an even
+// row takes ky = 1 (oy = h/2), an odd one ky = 0 (oy = (h+1)/2) and ky = 2 (oy = (h-1)/2); the same along W.  Every element of dx is
+// written exactly once (no atomics, deterministic).  A lane owns the pixel pair (2j, 2j+1) of one input row: the even pixel takes kx = 1 at
+// ox = j, the odd one kx = 2 at ox = j and kx = 0 at ox = j+1.  A wave works on 64 pairs of ONE row, so all its lanes read the same weights
+// (LDS broadcast); weights [ky][kx][co][CP] (CP = Cin rounded up to 4, zero-padded: 18 KiB at Cin 16).  dy is read as 16-byte vectors, dx
+// is written NCHW fp32, coalesced along W (8 bytes per lane and channel plane).
+constexpr int SDG_WAVES = 4;
+template <typename T, int CP>
+__global__ __launch_bounds__(64 * SDG_WAVES) void stem_dgrad_kernel(const T* __restrict__ dy, int lddy, const float* __restrict__ w,
+                                                                   float* __restrict__ dx, int N, int Cin, int H, int W, int Ho, int Wo,
+                                                                   int chunks) {
+  __shared__ __attribute__((aligned(16))) float sw[9 * STEM_CO * CP];
+  for (int i = threadIdx.x; i < 9 * STEM_CO * CP; i += 64 * SDG_WAVES) {
+    const int ci = i % CP, co = (i / CP) % STEM_CO, t = i / (CP * STEM_CO);
+    sw[i] = ci < Cin ? w[((size_t)co * Cin + ci) * 9 + t] : 0.f;
+  }
+  __syncthreads();
+  constexpr int KPV = Elem<T>::kPerVec;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int npairs = (W + 1) / 2;
+  const long items = (long)N * H * chunks;      // (row, 64-pair chunk): one per wave at a time
+  for (long item = (long)blockIdx.x * SDG_WAVES + wave; item < items; item += (long)gridDim.x * SDG_WAVES) {
+    const long row = item / chunks;
+    const int j = (int)(item % chunks) * 64 + lane;
+    const int h = (int)(row % H), n = (int)(row / H);
+    if (j >= npairs) continue;
+    float a0[CP], a1[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) a0[c] = a1[c] = 0.f;
+    const bool ok1 = j + 1 < Wo;
+#pragma unroll 1
+    for (int r = 0; r < 2; ++r) {
+      int ky, oy;
+      if (h & 1) {
+        ky = r == 0 ? 0 : 2;
+        oy = r == 0 ? (h + 1) / 2 : (h - 1) / 2;
+      } else {
+        if (r == 1) break;
+        ky = 1;
+        oy = h / 2;
+      }
+      if (oy >= Ho) continue;
+      const T* d0p = dy + ((size_t)((long)n * Ho + oy) * Wo + j) * lddy;
+      const float* wr = sw + ky * 3 * STEM_CO * CP;     // [kx][co][CP]
+      // (the loops over the 16-byte vectors and their channels stay rolled: fully unrolled, the compiler hoisted all 384 weight loads of a
+      // row tap ahead of the FMAs and spilled)
+#pragma unroll 1
+      for (int q = 0; q < STEM_CO / KPV; ++q) {
+        const vec16 v0 = ldg16(d0p + q * KPV);
+        const vec16 v1 = ok1 ? ldg16(d0p + lddy + q * KPV) : zero16();
+        float d0[KPV], d1[KPV];
+        unpack(v0, d0, T());
+        unpack(v1, d1, T());
+#pragma unroll 2
+        for (int e = 0; e < KPV; ++e) {
+          const int co = q * KPV + e;
+          const float4* w0 = reinterpret_cast<const float4*>(wr + (0 * STEM_CO + co) * CP);
+          const float4* w1 = reinterpret_cast<const float4*>(wr + (1 * STEM_CO + co) * CP);
+          const float4* w2 = reinterpret_cast<const float4*>(wr + (2 * STEM_CO + co) * CP);
+#pragma unroll
+          for (int c4 = 0; c4 < CP / 4; ++c4) {
+            const float4 k0 = w0[c4], k1 = w1[c4], k2 = w2[c4];
+            a0[4 * c4 + 0] = fmaf(d0[e], k1.x, a0[4 * c4 + 0]);
+            a0[4 * c4 + 1] = fmaf(d0[e], k1.y, a0[4 * c4 + 1]);
+            a0[4 * c4 + 2] = fmaf(d0[e], k1.z, a0[4 * c4 + 2]);
+            a0[4 * c4 + 3] = fmaf(d0[e], k1.w, a0[4 * c4 + 3]);
+            a1[4 * c4 + 0] = fmaf(d1[e], k0.x, fmaf(d0[e], k2.x, a1[4 * c4 + 0]));
+            a1[4 * c4 + 1] = fmaf(d1[e], k0.y, fmaf(d0[e], k2.y, a1[4 * c4 + 1]));
+            a1[4 * c4 + 2] = fmaf(d1[e], k0.z, fmaf(d0[e], k2.z, a1[4 * c4 + 2]));
+            a1[4 * c4 + 3] = fmaf(d1[e], k0.w, fmaf(d0[e], k2.w, a1[4 * c4 + 3]));
+          }
+        }
+      }
+    }
+    const size_t plane = (size_t)H * W;
+    float* dst = dx + (size_t)n * Cin * plane + (size_t)h * W + 2 * j;
+    const bool odd_ok = 2 * j + 1 < W;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      if (c >= Cin) break;
+      float* p = dst + (size_t)c * plane;
+      if ((W & 1) == 0) {
+        *reinterpret_cast<f32x2*>(p) = f32x2{a0[c], a1[c]};     // (W even: every pair starts on an 8-byte boundary)
+      } else {
+        p[0] = a0[c];
+        if (odd_ok) p[1] = a1[c];
+      }
+    }
+  }
+}
+
 static int stem_ppb(long P) {
   long ppb = (P + 1023) / 1024;
   ppb = (ppb + 63) / 64 * 64;
@@ -595,6 +687,27 @@ extern "C" int dc_stem_wgrad(int dtype, int N, int Cin, int H, int W, const floa
   DC_CHECK_LAUNCH();
   const long n = 32L * K;
   hipLaunchKernelGGL(slab_rows_reduce_kernel, dim3(cdiv(n, 8)), dim3(256), 0, st, (const float*)workspace, grad_w, rows, n);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_stem_dgrad(int dtype, int N, int Cin, int H, int W, const void* dy, int lddy, const float* w, float* dx_nchw,
+                             void* stream) {
+  DC_REQUIRE(w && dx_nchw && N > 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 16, "dc_stem_dgrad: bad argument (Cin must be <= 16)");
+  DC_REQUIRE(((uintptr_t)dx_nchw & 7) == 0, "dc_stem_dgrad: dx must be 8-byte aligned");
+  if (int e = dc_check_view(dy, lddy, STEM_CO, dtype, "dc_stem_dgrad dy")) return e;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int chunks = cdiv((W + 1) / 2, 64);
+  const long items = (long)N * H * chunks;
+  // a persistent grid: every block stages the (up to 18 KiB) weights once, so blocks walk many rows instead of one each
+  const int blocks = items > 2048L * SDG_WAVES ? 2048 : cdiv(items, SDG_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  const int cp = (Cin + 3) / 4 * 4;
+#define SDG(TT, CPV) hipLaunchKernelGGL((stem_dgrad_kernel<TT, CPV>), dim3(blocks), dim3(64 * SDG_WAVES), 0, st, (const TT*)dy, lddy, w, dx_nchw, N, Cin, H, W, Ho, Wo, chunks)
+#define SDG_CP(TT) do { if (cp == 4) SDG(TT, 4); else if (cp == 8) SDG(TT, 8); else if (cp == 12) SDG(TT, 12); else SDG(TT, 16); } while (0)
+  if (dtype == DC_BF16) SDG_CP(bf16); else SDG_CP(float);
+#undef SDG_CP
+#undef SDG
   DC_CHECK_LAUNCH();
   return 0;
 }

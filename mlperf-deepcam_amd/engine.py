@@ -29,6 +29,7 @@ from . import spec as S
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+S_STEM_W = "xception_features.conv1.weight"
 
 
 class Act:
@@ -122,9 +123,11 @@ class LazyAct:
 class Engine:
     def __init__(self, batch: int, height: int, width: int, dtype=torch.bfloat16, device=None, n_input: int = 16,
                  n_classes: int = 3, seed: Optional[int] = 333, share_from: "Engine" = None, layout: "S.Layout" = None,
-                 builder: Callable[["Engine"], None] = None):
+                 builder: Callable[["Engine"], None] = None, frozen_bn: bool = False):
         """layout + builder: a sub-network as an engine of its own (tests build ONE Xception Block from the op builders below
-        and run it against the reference's Block vectors); the default is the whole DeepLabV3+ network."""
+        and run it against the reference's Block vectors); the default is the whole DeepLabV3+ network.
+        frozen_bn: every BatchNorm runs in eval mode, forward AND backward -- the running statistics normalise, nothing updates them, and
+        the backward differentiates that affine map (autograd through ``net.eval()``: saliency, fine-tuning with frozen statistics)."""
         if not torch.cuda.is_available():
             raise L.DeepcamHipError("mlperf_deepcam_amd.Engine needs a HIP device: there is no CPU path")
         L.load()
@@ -238,6 +241,14 @@ class Engine:
         self._fold_seq: List[tuple] = []
         self._final_fold = None                       # (FoldEntry array, count, names): rows produced after the last dense launch
         self.aspp_group = os.environ.get("DC_ASPP_GROUP", "1") != "0"      # atrous ASPP branches in one forward launch
+        self.frozen_bn = frozen_bn
+        if frozen_bn:
+            # every fusion below takes batch statistics, or the backward sums of a train-mode BatchNorm, inside another kernel; their unfused
+            # forms (the DC_FUSE_*=0 paths) serve this engine, whose BatchNorm backward is dc_bn_bwd_frozen + dc_bn_bwd_finalize (_bn).  Set on
+            # this engine only: the environment and the library's options stay as they are for every other engine
+            self.fuse_bn_reduce = self.fuse_bn_into_dw = self.fuse_bn_conv = self.fuse_bn_head = self.fuse_bn_into_head = False
+            self.fuse_head_apply = self.fuse_bn_res = self.fuse_bn_src_dw = self.fuse_pw_bn_bwd = False
+            self.fuse_bn_bwd_fin = self.fuse_bn_fwd_fin = self.bn_sum_rows = False
         self._deferred_names: List[str] = []
         self._ready_now: List[str] = []
 
@@ -763,6 +774,18 @@ class Engine:
             mrelu = (2 if relu else 0) if from_y else relu_i
             optr = (lambda: None) if from_y else (lambda: o.ptr)
             old_ = 0 if from_y else o.ld
+            if self.frozen_bn:
+                # eval-mode BatchNorm: dx, the residual's gradient and the slab of (sum g, sum g*xhat) in ONE pass over the running statistics
+                # (no mean / variance of the batch to differentiate), then the parameter gradients from that slab
+                assert not lazy and getattr(y, "pw_fuse", None) is None and getattr(o, "fused_bwd", None) is None
+                dyf = y.grad
+
+                def bwd_frozen():
+                    L.call("dc_bn_bwd_frozen", bdt, M, Cc, do.ptr, do.ld, y.ptr, y.ld, optr(), old_, mrelu, gam, rm, rv, BN_EPS, dyf.ptr, dyf.ld,
+                           g_out.ptr if g_out is not None else None, g_out.ld if g_out is not None else 0, L.dptr(bslab), L.dptr(scale),
+                           L.dptr(shift), self._st())
+                    L.call("dc_bn_bwd_finalize", Cc, L.dptr(bslab), brows, dgam, dbet, self._st())
+                return bwd_frozen, [bname + ".weight", bname + ".bias"]
             # the producing pointwise conv applies this BatchNorm's backward itself, in one pass with its own two gradients (_conv: bn_fuse)
             pwf = getattr(y, "pw_fuse", None) if (apply_by is None and residual is None and mrelu in (0, 2)) else None
             if pwf is not None:
@@ -885,7 +908,7 @@ class Engine:
         # ---- stem.  16 input channels: one layout pass (NCHW fp32 -> NHWC T) and the 3x3/s2 conv runs on the MFMA kernels
         #      (forward and weight gradient; the input needs no data gradient).  Other channel counts (--channels subsets)
         #      use the dedicated direct-convolution kernels that read NCHW in place.
-        w1 = X + "conv1.weight"
+        w1 = S_STEM_W
         kpv = 8 if self.dtype == torch.bfloat16 else 4
         if self.n_input % kpv == 0:
             x0 = Act(self, "x_nhwc", B, H, W, self.n_input)
@@ -927,6 +950,7 @@ class Engine:
                 return bwd, [w1]
 
             self.bwd.append(stem_bwd_make)
+        self._stem_out = c1          # its gradient is the input of input_grad()
         x = self._bn(c1, sslab, srows, X + "bn1", True)
         y, slab, rows = self._conv(x, X + "conv2.weight", 64, k=3, pad=1)
         x = self._bn(y, slab, rows, X + "bn2", True)
@@ -1212,6 +1236,7 @@ class Engine:
         """logits[B,3,H,W] (fp32, NCHW) = net(x); returns the engine-owned logits buffer.
         x is the reference's NCHW fp32 batch [B,16,H,W], or -- from the input pipeline (data.py) -- an NHWC batch
         [B,H,W,16] already in the activation dtype, which is then used in place (no layout pass)."""
+        train = train and not self.frozen_bn          # (a frozen-BatchNorm engine has the eval forward only)
         if (self.x0 is not None and x_nchw.dim() == 4 and tuple(x_nchw.shape) == (self.B, self.H, self.W, self.n_input)
                 and x_nchw.dtype == self.dtype and x_nchw.is_contiguous() and x_nchw.device == self.device):
             self.x0.buf = x_nchw
@@ -1230,6 +1255,23 @@ class Engine:
             x_nchw = x_nchw.to(device=self.device, dtype=torch.float32).contiguous()
         self.x_in = x_nchw
         return self._run_forward(train)
+
+    def input_grad(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dL/dx of the last backward(): the caller's NCHW fp32 layout [B, n_input, H, W] (out: a buffer of that shape to write, else a new
+        one).  One dc_stem_dgrad launch on the current stream over the stem output's gradient and the fp32 master weight.  It is not part of
+        backward()'s launch list (the train step never needs it): backward() has joined the weight-gradient stream before it returns, nothing
+        writes the stem output's gradient (its own buffer) until the next backward(), and no weight update may come in between."""
+        c1 = getattr(self, "_stem_out", None)
+        if c1 is None:
+            raise L.DeepcamHipError("input_grad: this engine has no network stem (a custom layout)")
+        shape = (self.B, self.n_input, self.H, self.W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise L.DeepcamHipError(f"input_grad: out must be a contiguous fp32 tensor {shape} on {self.device}")
+        dy = c1.grad
+        L.call("dc_stem_dgrad", self.dt, self.B, self.n_input, self.H, self.W, dy.ptr, dy.ld, self.pptr(S_STEM_W), L.dptr(out), self._st())
+        return out
 
     def _run_forward(self, train: bool) -> torch.Tensor:
         if train and self.B < 2:

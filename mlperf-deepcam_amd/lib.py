@@ -115,6 +115,7 @@ _SIGS = {
     "dc_bn_bwd_finalize": (I, [I, P, I, P, P, P]),
     "dc_bn_bwd_apply": (I, [I, L, I, L, P, I, P, I, P, I, I, P, P, P, P, P, P, I, P, I, P, P, P]),
     "dc_bn_bwd_apply_fin_max_rows": (I, []),
+    "dc_bn_bwd_frozen": (I, [I, L, I, P, I, P, I, P, I, I, P, P, P, F, P, I, P, I, P, P, P, P]),
     "dc_sepconv_fwd_rows": (I, [I, I, I, I, I, I, I, I]),
     "dc_sepconv_fwd": (I, [I, I, I, I, I, I, P, I, P, P, I, P, P, I, P, P, I, P, I, P]),
     "dc_pw_bn_bwd_rows": (I, [I, I, I, L]),
@@ -124,6 +125,7 @@ _SIGS = {
     "dc_stem_fwd": (I, [I, I, I, I, I, P, P, P, I, P, P]),
     "dc_stem_wgrad_workspace": (SZ, [I, I, I, I]),
     "dc_stem_wgrad": (I, [I, I, I, I, I, P, P, I, P, P, P]),
+    "dc_stem_dgrad": (I, [I, I, I, I, I, P, I, P, P, P]),
     "dc_head_workspace": (SZ, [I, I, I, I, I]),
     "dc_head_fwd": (I, [I, I, I, I, I, P, I, P, P, P, P]),
     "dc_head_fwd_loss": (I, [I, I, I, I, I, P, I, P, P, P, P, I, P, F, P, P, P, P, P]),

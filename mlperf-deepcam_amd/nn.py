@@ -121,20 +121,28 @@ def compute_score(prediction, gt, num_classes=3, device_id=None, type="iou", wei
 # model
 # ------------------------------------------------------------------------------------------------------------------
 class _NetFn(torch.autograd.Function):
+    """Train mode: the primary engines (batch statistics).  Eval mode with autograd on: the frozen-BatchNorm engines (running statistics in
+    forward and backward), so that ``net.eval(); loss.backward()`` differentiates what the eval forward computed."""
+
     @staticmethod
     def forward(ctx, x, anchor, module):
-        eng = module.engine_for(x)
-        ctx.eng, ctx.module = eng, module
+        frozen = not module.training
+        eng = module.engine_for(x, frozen=frozen)
+        ctx.eng, ctx.module, ctx.frozen = eng, module, frozen
+        ctx.x_meta = (tuple(x.shape), x.dtype, x.device)
         out = _ops.OPS.net_forward(x, _ops.engine_handle(eng), module.training)
-        if module.training:
-            if len(_dlogits_for) > 64:           # engines come and go with input shapes: drop entries of freed buffers
-                _dlogits_for.clear()
-            _dlogits_for[out.data_ptr()] = eng.dlogits
+        if len(_dlogits_for) > 64:               # engines come and go with input shapes: drop entries of freed buffers
+            _dlogits_for.clear()
+        _dlogits_for[out.data_ptr()] = eng.dlogits
         return out
 
     @staticmethod
     def backward(ctx, dlogits):
         eng = ctx.eng
+        if ctx.frozen and ctx.module._ddp_reducer is not None:
+            raise NotImplementedError("backward through the model in eval mode (frozen BatchNorm) is not supported under DistributedDataParallel: "
+                                      "the gradient reducer is wired to the train-mode engines; call net.train(), or run the eval-mode backward "
+                                      "on the unwrapped module of one process")
         # torch semantics: a backward() that arrives without an optimizer.zero_grad() / step() since the previous one ACCUMULATES into p.grad.
         # The engine's backward program writes every parameter's gradient exactly once (it overwrites), so the gradients of the earlier
         # backward calls are set aside first and added back behind this one -- a 226 MB copy and add on the micro-batch path only; the
@@ -154,10 +162,20 @@ class _NetFn(torch.autograd.Function):
             # has taken over averages inside the optimizer kernel: finish(average=True) refuses (the gradients would otherwise be
             # scaled twice, or -- had the reference been dropped -- the buckets launched by this backward would never be waited for)
             red.finish(average=True)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # dL/dx: the stem's data gradient over the stem output's gradient this backward has just left (Engine.input_grad); the parameter
+            # gradients above do not depend on it
+            shape, dtype, device = ctx.x_meta
+            if shape != (eng.B, eng.n_input, eng.H, eng.W):
+                raise L.DeepcamHipError(f"input gradient: the input must be the NCHW batch {(eng.B, eng.n_input, eng.H, eng.W)}, got {shape}")
+            dx = eng.input_grad()
+            if dx.dtype != dtype or dx.device != device:
+                dx = dx.to(device=device, dtype=dtype)
         if stash is not None:
             eng.grads.add_(stash)
         ctx.module._attach_grads()
-        return None, None, None
+        return dx, None, None
 
 
 class DeepLabv3_plus(torch.nn.Module):
@@ -179,16 +197,28 @@ class DeepLabv3_plus(torch.nn.Module):
         self.n_input, self.n_classes, self.act_dtype = n_input, n_classes, dtype
         self._seed = seed
         self._engines: Dict[tuple, Engine] = {}
+        self._frozen_engines: Dict[tuple, Engine] = {}      # eval mode with autograd on (frozen BatchNorm), built on first use
         self._primary: Optional[Engine] = None
         self._anchor = None
         self._ddp_reducer = None      # set by dist.DistributedDataParallel
         self._init_seed_state = torch.random.get_rng_state() if seed is None else None
 
     # -- engines are shape-specialised and built lazily; all of them share one parameter store
-    def engine_for(self, x: torch.Tensor = None, shape: tuple = None) -> Engine:
+    def engine_for(self, x: torch.Tensor = None, shape: tuple = None, frozen: bool = False) -> Engine:
         shp = tuple(x.shape) if x is not None else tuple(shape)
         B, Cin, H, W = shp
         key = (B, H, W)
+        if frozen:
+            # the frozen-BatchNorm engine of this shape: shares the parameter, gradient and buffer arenas with the primary engine; it is not
+            # handed to a gradient reducer (an eval-mode backward under DistributedDataParallel raises in _NetFn.backward)
+            feng = self._frozen_engines.get(key)
+            if feng is None:
+                if self._primary is None:
+                    self.engine_for(shape=shp)
+                feng = Engine(B, H, W, self.act_dtype, n_input=self.n_input, n_classes=self.n_classes, share_from=self._primary,
+                              frozen_bn=True)
+                self._frozen_engines[key] = feng
+            return feng
         eng = self._engines.get(key)
         if eng is None:
             if self._primary is None:
@@ -259,6 +289,10 @@ class DeepLabv3_plus(torch.nn.Module):
             self.engine_for(input)
             return _NetFn.apply(input, self._anchor, self)
         eng = self.engine_for(input)
+        if torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # eval mode with autograd on (saliency, fine-tuning with frozen statistics): BatchNorm on its running statistics, differentiated
+            # as the affine map it then is -- the frozen-BatchNorm engine.  Under no_grad / inference_mode the plain eval forward below runs
+            return _NetFn.apply(input, self._anchor, self)
         return _ops.OPS.net_forward(input, _ops.engine_handle(eng), self.training)
 
     def load_state_dict(self, state_dict, strict: bool = True):
