@@ -32,10 +32,10 @@ enum { DC_ADAM = 0, DC_ADAMW = 1, DC_LAMB = 2 };
 
 const char* dc_last_error(void);
 int dc_version(void);
-/* Tuning switches (A/B measurements inside one process).  "igemm_mode": 2 = LDS-DMA, 3-stage ring, counted waits (default);
- * 1 = LDS-DMA, 2 stages; 0 = register staging.  "igemm256": 0 = 128 x 128 tiles only, 1 = planner picks per layer (default),
- * 2 = 256 x 256 eight-wave kernel wherever eligible.  "wgrad_target_blocks": workgroups aimed at by the split-K planner.
- * "dw_tile" 0/1, "dw_wgrad_tpb", "bn_cgw", "bn_rows": depthwise / BatchNorm kernel variants (see the .hip files). */
+/* Kernel switches (tests and A/B measurements inside one process): they force a kernel at shapes its planner would not give it, or keep
+ * it off.  "igemm256": 0 = 128 x 128 tiles only, 1 = planner picks per layer (default), 2 = 256 x 256 eight-wave kernel wherever
+ * eligible.  "pw384", "pw224", "pw192", "igemm256p", "wgrad384", "thin_tile", "head_*_fused", "dw_tile", "dw_pipe", "bn_apply_rows"
+ * and their like: see the table in README.md and the .hip files.  An unknown name is an error. */
 int dc_set_option(const char* name, int value);
 /* Every dc_set_option switch back to its default (the library's own table; also what a freshly loaded library holds). */
 int dc_reset_options(void);

@@ -417,8 +417,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(int C, const float
 // reductions (16 channel groups x 16 row lanes, APPLY_ROWS rows per block): a thread's channels never change, so its per-channel
 // coefficients are computed once and live in registers -- the earlier grid-stride version re-loaded five vectors per element
 // and ran at 3.2 TB/s where a copy reaches 4.9.
-static int g_bn_cgw = 32, g_bn_rows = 32;
-static int g_bn_fin_mul_f = 2, g_bn_fin_mul_b = 2;   // rows per block of the kernels that run a finalize themselves, in units of bn_rows ("bn_fin_mul_fwd" / "_bwd")
+constexpr int BN_CGW = 32;       // widest channel group of a block (16-byte vectors)
+constexpr int BN_ROWS = 32;      // rows per block at that width
+constexpr int BN_FIN_MUL_FWD = 2, BN_FIN_MUL_BWD = 2;   // rows per block of the kernels that run a finalize themselves, in units of BN_ROWS
 static int g_bn_apply_rows = 1;     // dc_bn_apply on bn_apply_rows_kernel (0: the grid-stride kernel; "bn_apply_rows")
 template <typename T, int CGW>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, int APPLY_ROWS, float inv_count, const T* __restrict__ dout,
@@ -432,7 +433,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, int AP
                                                            const float* __restrict__ fin_slab, int fin_rows, float* dgamma_out, float* dbeta_out) {
   constexpr int KPV = Elem<T>::kPerVec;
   constexpr int RL = 256 / CGW;   // row lanes
-  constexpr int CW = CGW * KPV;   // channels per block: 128..512
+  constexpr int CW = CGW * KPV;   // channels per block: up to 256
   const int cgl = threadIdx.x % CGW, rl = threadIdx.x / CGW;
   const int c0 = (blockIdx.x * CGW + cgl) * KPV;
   // dy = ca*g + cb*(x - mean) + cd.  The block's coefficients are computed once, by one thread per channel, and handed out
@@ -561,11 +562,7 @@ static int fold_large_slab(float* slab, int rows, int C, hipStream_t st) {
 using namespace dc;
 
 extern "C" int dc_bn_set_option(const char* name, int value) {
-  if (strcmp(name, "bn_cgw") == 0 && (value == 16 || value == 32 || value == 64)) { g_bn_cgw = value; return 0; }
-  if (strcmp(name, "bn_rows") == 0 && value >= 16 && value % 16 == 0) { g_bn_rows = value; return 0; }
   if (strcmp(name, "bn_apply_rows") == 0) { g_bn_apply_rows = value != 0; return 0; }
-  if (strcmp(name, "bn_fin_mul_fwd") == 0 && value >= 1 && value <= 16) { g_bn_fin_mul_f = value; return 0; }
-  if (strcmp(name, "bn_fin_mul_bwd") == 0 && value >= 1 && value <= 16) { g_bn_fin_mul_b = value; return 0; }
   return -1;
 }
 
@@ -633,15 +630,15 @@ static int bn_apply_impl(int dtype, long M, int C, const void* y, int ldy, const
   const int kpv = dtype == DC_BF16 ? 8 : 4;
   if (g_bn_apply_rows) {
     // bn_bwd_apply's block shape (a block as narrow as the tensor, rows per block growing with the row lanes)
-    const int cgw = narrow_cg(C / kpv, g_bn_cgw);
-    int APPLY_ROWS = (rows_per_block > 0 ? rows_per_block : g_bn_rows) * (g_bn_cgw > cgw ? g_bn_cgw / cgw : 1);
+    const int cgw = narrow_cg(C / kpv, BN_CGW);
+    int APPLY_ROWS = (rows_per_block > 0 ? rows_per_block : BN_ROWS) * (BN_CGW / cgw);
     while (cdiv(M, APPLY_ROWS) > 65535) APPLY_ROWS *= 2;      // (a block walks its rows in a loop: any row count per block is served)
     {
       const dim3 blocks2(cdiv(C / kpv, cgw), cdiv(M, APPLY_ROWS));
 #define BN_AR(TT, W) do { if (finp != nullptr) hipLaunchKernelGGL((bn_apply_rows_kernel<TT, W, true>), blocks2, dim3(256), 0, st, M, C, APPLY_ROWS, (const TT*)y, ldy, scale, shift, (const TT*)residual, ldr, relu, (TT*)out, ldo, fin); \
                           else hipLaunchKernelGGL((bn_apply_rows_kernel<TT, W, false>), blocks2, dim3(256), 0, st, M, C, APPLY_ROWS, (const TT*)y, ldy, scale, shift, (const TT*)residual, ldr, relu, (TT*)out, ldo, fin); } while (0)
-      if (dtype == DC_BF16) { if (cgw == 64) BN_AR(bf16, 64); else if (cgw == 32) BN_AR(bf16, 32); else if (cgw == 16) BN_AR(bf16, 16); else if (cgw == 8) BN_AR(bf16, 8); else BN_AR(bf16, 4); }
-      else                  { if (cgw == 64) BN_AR(float, 64); else if (cgw == 32) BN_AR(float, 32); else if (cgw == 16) BN_AR(float, 16); else if (cgw == 8) BN_AR(float, 8); else BN_AR(float, 4); }
+      if (dtype == DC_BF16) { if (cgw == 32) BN_AR(bf16, 32); else if (cgw == 16) BN_AR(bf16, 16); else if (cgw == 8) BN_AR(bf16, 8); else BN_AR(bf16, 4); }
+      else                  { if (cgw == 32) BN_AR(float, 32); else if (cgw == 16) BN_AR(float, 16); else if (cgw == 8) BN_AR(float, 8); else BN_AR(float, 4); }
 #undef BN_AR
       DC_CHECK_LAUNCH();
       return 0;
@@ -680,7 +677,7 @@ extern "C" int dc_bn_apply_fin(int dtype, long M, int C, long count, const void*
   if (count <= 1) return dc_fail("Expected more than 1 value per channel when training", __FILE__, __LINE__);
   const BnFinArgs a = bn_fin_args(C, count, slab, rows, 0, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
                                   shift, save_mean, save_invstd);
-  return bn_apply_impl(dtype, M, C, y, ldy, scale, shift, residual, ldr, relu, out, ldo, stream, &a, (rows == SUM_ROW ? 1 : g_bn_fin_mul_f) * g_bn_rows);
+  return bn_apply_impl(dtype, M, C, y, ldy, scale, shift, residual, ldr, relu, out, ldo, stream, &a, (rows == SUM_ROW ? 1 : BN_FIN_MUL_FWD) * BN_ROWS);
 }
 
 static int bn_bwd_reduce_impl(int dtype, long M, int C, const void* dout, int lddo, const void* y, int ldy,
@@ -736,14 +733,14 @@ static int bn_bwd_apply_impl(int dtype, long M, int C, long count, const void* d
   hipStream_t st = (hipStream_t)stream;
   const int kpv = dtype == DC_BF16 ? 8 : 4;
   // a block as narrow as the tensor (see narrow_cg); the rows per block grow with the row lanes so that every thread has its four rows
-  const int cgw = narrow_cg(C / kpv, g_bn_cgw);
-  int APPLY_ROWS = g_bn_rows * (fin_slab != nullptr && fin_rows != SUM_ROW ? g_bn_fin_mul_b : 1) * (g_bn_cgw > cgw ? g_bn_cgw / cgw : 1);
+  const int cgw = narrow_cg(C / kpv, BN_CGW);
+  int APPLY_ROWS = BN_ROWS * (fin_slab != nullptr && fin_rows != SUM_ROW ? BN_FIN_MUL_BWD : 1) * (BN_CGW / cgw);
   while (cdiv(M, APPLY_ROWS) > 65535) APPLY_ROWS *= 2;      // (a block walks its rows in a loop: any row count per block is served)
   const dim3 blocks(cdiv(C / kpv, cgw), cdiv(M, APPLY_ROWS));
   const float inv = 1.0f / (float)count;
 #define BN_BA(TT, W) hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, W>), blocks, dim3(256), 0, st, M, C, APPLY_ROWS, inv, (const TT*)dout, lddo, (const TT*)y, ldy, (const TT*)out, ldout, relu, gamma, save_mean, save_invstd, dgamma, dbeta, (TT*)dy, lddy, (TT*)g_out, ldg, mscale, mshift, fin_slab, fin_rows, dgamma_out, dbeta_out)
-  if (dtype == DC_BF16) { if (cgw == 64) BN_BA(bf16, 64); else if (cgw == 32) BN_BA(bf16, 32); else if (cgw == 16) BN_BA(bf16, 16); else if (cgw == 8) BN_BA(bf16, 8); else BN_BA(bf16, 4); }
-  else                  { if (cgw == 64) BN_BA(float, 64); else if (cgw == 32) BN_BA(float, 32); else if (cgw == 16) BN_BA(float, 16); else if (cgw == 8) BN_BA(float, 8); else BN_BA(float, 4); }
+  if (dtype == DC_BF16) { if (cgw == 32) BN_BA(bf16, 32); else if (cgw == 16) BN_BA(bf16, 16); else if (cgw == 8) BN_BA(bf16, 8); else BN_BA(bf16, 4); }
+  else                  { if (cgw == 32) BN_BA(float, 32); else if (cgw == 16) BN_BA(float, 16); else if (cgw == 8) BN_BA(float, 8); else BN_BA(float, 4); }
 #undef BN_BA
   DC_CHECK_LAUNCH();
   return 0;

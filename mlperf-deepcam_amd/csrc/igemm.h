@@ -38,21 +38,20 @@ struct IgemmParams {
   GatherGeom g;
   int N, ldx, ldy;
   int ldw;     // K stride of a packed weight row: weight_ld(Cin)
-  const void* w_kn;   // the layer's OTHER packing, [k][n] rows of weight_ld(Cout) elements (pointwise layers: wb for the forward pass, wf for the
-  int ldw_kn;         // data gradient); null when the caller passes one image only.  The 224 x 384 kernel (igemm224.hip) takes its weights from it.
+  const void* w_kn = nullptr;   // the layer's OTHER packing, [k][n] rows of weight_ld(Cout) elements (pointwise layers: wb for the forward pass, wf for the
+  int ldw_kn = 0;               // data gradient); null when the caller passes one image only.  The 224 x 384 kernel (igemm224.hip) takes its weights from it.
   int M;       // END of this launch's pixel range (per phase); N*Qh*Qw when the launch covers the layer
-  int m_beg;   // first pixel of this launch's range (a multiple of 256): the mixed plan of run_gather cuts a layer into a
-               // 256-tile launch over [0, m_beg') and a 128-tile launch over [m_beg', M)
+  int m_beg = 0;   // first pixel of this launch's range (a multiple of 256): the mixed plan of run_gather cuts a layer into a
+                   // 256-tile launch over [0, m_beg') and a 128-tile launch over [m_beg', M)
   int mtiles;  // 128-pixel tiles per phase of the WHOLE layer (= rows per phase of the statistics slab)
-  int accumulate;
-  const void* zero_page;   // 256 zero bytes in device memory (set by the 256-tile launcher)
-  int phase_fast;          // 256-tile kernel: consecutive tiles walk the sub-pixel phases of one pixel tile (set by its launcher)
+  int accumulate = 0;
+  const void* zero_page = nullptr;   // 256 zero bytes in device memory (set by the 256-tile launcher)
   // 256-tile kernel, grouped launch (dc_conv_fwd_dilated_group): `ngroup` "same" dilated 3x3 convolutions of ONE input share the
   // launch.  g holds the unit-dilation tap table (dy, dx in {-1,0,1}); member b gathers at dy*gdil[b], dx*gdil[b], multiplies
   // by gw[b] and writes gy[b] / gslab[b].  Member 0 is (w, y, slab) above with gdil[0].  ngroup <= 1: plain launch.
   static constexpr int MAXGROUP = 4;
-  BnBwdEpi bst;            // 128- and 256-tile kernels (LDS epilogue): slab receives BatchNorm-backward sums instead of (sum, sum of squares)
-  int ngroup;
+  BnBwdEpi bst{};          // 128- and 256-tile kernels (LDS epilogue): slab receives BatchNorm-backward sums instead of (sum, sum of squares)
+  int ngroup = 0;
   int gdil[MAXGROUP];
   const void* gw[MAXGROUP - 1];
   void* gy[MAXGROUP - 1];
@@ -60,19 +59,17 @@ struct IgemmParams {
   // 256-tile kernel, split-K launch (few pixels, long K: the atrous ASPP branches at local batch 2 are 81 tiles of 576 K steps): `ksplit` > 1
   // workgroups share a tile, each walks a contiguous range of the K loop's channel-chunk groups and leaves its fp32 accumulators in
   // kslab[split][tile][256 px][256 ch]; igemm256_splitk_fold sums the splits in a fixed order, stores y and takes the BatchNorm sums.
-  int ksplit;
-  float* kslab;
+  int ksplit = 0;
+  float* kslab = nullptr;
   // 128-tile kernel: a 1 x 1 stride-2 data gradient written first-hand (the shortcut convs of the entry flow): only phase (0, 0) has a tap, and a
   // launch over that phase alone also stores the zeros of the other three beside its values -- contiguous output rows instead of every other
   // 128-byte line of every other image row (which wrote 56 MB in 165 us)
-  int zfill;
+  int zfill = 0;
 };
 // OUT32: the epilogue stores fp32 regardless of T (used by the classifier head, whose logits must not be rounded to bf16)
 
 // 256 x 256 tile kernel (bf16 only).  Returns 0 after launching.
 int launch_igemm256(const IgemmParams& p, hipStream_t st);
-void igemm256_set_phase_fast(int v);
-int igemm256_phase_fast_enabled();
 // igemm256p.hip: persistent form (one workgroup per CU walks its tiles; the ring never drains between tiles)
 bool igemm256p_eligible(const IgemmParams& p);
 int launch_igemm256p(const IgemmParams& p, int workgroups, hipStream_t st);

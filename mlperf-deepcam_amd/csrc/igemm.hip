@@ -1,9 +1,9 @@
 // Gather-form implicit GEMM on MFMA for every dense convolution of DeepLabV3+/Xception (see conv_geom.h).
 //
 //   tile      128 output pixels x 128 output channels per 256-thread workgroup (4 waves, 2x2, 64x64 each)
-//   K loop    taps (outer) x input-channel chunks of 128 bytes (64 bf16 / 32 f32), register-staged and
-//             double-buffered in LDS, one barrier per step
-//   LDS       rows of 128 B, 16-B slots XOR-swizzled by (row>>1)&7 -> conflict-free ds_read_b128 fragments
+//   K loop    taps (outer) x input-channel chunks of 64 bytes (32 bf16 / 16 f32), staged by LDS-DMA into a 3-stage ring,
+//             counted vmcnt waits, one barrier per step
+//   LDS       rows of 64 B, 16-B slots XOR-swizzled by (row>>1)&3 -> conflict-free ds_read_b128 fragments
 //   MFMA      A operand = weight rows (output channel), B operand = pixel rows, so each lane ends up with
 //             4 consecutive output channels of one pixel -> 8/16-byte LDS writes in the epilogue
 //   epilogue  accumulators -> LDS C tile -> fully coalesced 16-B NHWC stores; optional bias, optional
@@ -19,18 +19,12 @@
 namespace dc {
 
 constexpr int BM = 128, BN = 128;
-// staging modes (runtime switch "igemm_mode", A/B-able in one process):
-//   0  register staging, 128-byte K rows, 2 LDS stages              (first working version)
-//   1  LDS-DMA,          128-byte K rows, 2 stages, vmcnt(0)+barrier per step
-//   2  LDS-DMA,           64-byte K rows, 3 stages, counted vmcnt: two stages stay in flight across the barrier; 48 KiB of
-//      LDS and 146 registers -> 3 workgroups per CU, which also lets one workgroup's epilogue overlap another's K loop
-//   3/4  as 2 with a 4- / 5-stage ring (64 / 80 KiB, 2 workgroups per CU): deeper prefetch.  PMC on the 728-channel GEMM shows a 90 %
-//      L2 hit rate, i.e. practically every 16 KiB stage contains a few lines that come from the Infinity Cache / HBM, and the
-//      stage is only usable when its slowest line has landed: prefetch distance, not bandwidth, bounds the K loop.
-template <int MODE> struct StageCfg { static constexpr int ROWB = 128, NSTAGE = 2; };
-template <> struct StageCfg<2> { static constexpr int ROWB = 64, NSTAGE = 3; };
-template <> struct StageCfg<3> { static constexpr int ROWB = 64, NSTAGE = 4; };
-template <> struct StageCfg<4> { static constexpr int ROWB = 64, NSTAGE = 5; };
+// Operand staging: LDS-DMA, 64-byte K rows, 3 stages, counted vmcnt: two stages stay in flight across the barrier; 48 KiB of LDS and
+// 146 registers -> 3 workgroups per CU, which also lets one workgroup's epilogue overlap another's K loop.  (Measured against register
+// staging with 128-byte rows in 2 stages, LDS-DMA with 128-byte rows in 2 stages, and 4- / 5-stage rings of 64-byte rows at 2 workgroups
+// per CU: PMC on the 728-channel GEMM shows a 90 % L2 hit rate, i.e. practically every 16 KiB stage contains a few lines that come from
+// the Infinity Cache / HBM, and a stage is only usable when its slowest line has landed.)
+constexpr int ROWB = 64, NSTAGE = 3;
 
 template <typename T>
 struct Mma;
@@ -64,11 +58,7 @@ __device__ unsigned long long* dc_stamp_buf = nullptr;
 #define DC_STAMP(k)
 #endif
 
-template <int ROWB>
-__device__ inline int swz(int row, int slot) {
-  if constexpr (ROWB == 128) return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);   // 8 slots per row
-  else return row * 64 + ((slot ^ ((row >> 1) & 3)) << 4);                          // 4 slots per row
-}
+__device__ inline int swz(int row, int slot) { return row * ROWB + ((slot ^ ((row >> 1) & 3)) << 4); }   // 4 slots per row
 
 // 16 zero bytes in global memory: the source of every predicated-off LDS-DMA lane (zero fill of halos, K and M tails)
 static __device__ __attribute__((aligned(256))) unsigned char dc_zero_page[256];   // (each translation unit has its own copy)
@@ -76,25 +66,22 @@ static __device__ __attribute__((aligned(256))) unsigned char dc_zero_page[256];
 typedef __attribute__((address_space(1))) const void* gas_ptr;
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
-// GLDS: stage operand tiles with the gfx950 LDS-DMA (global_load_lds_dwordx4: global -> LDS without passing through
-// VGPRs and without ds_write instructions, which at ~79 B/clk/CU were the bottleneck of the register-staged loop).
+// Operand tiles are staged with the gfx950 LDS-DMA (global_load_lds_dwordx4: global -> LDS without passing through
+// VGPRs and without ds_write instructions, which at ~79 B/clk/CU were the bottleneck of a register-staged loop).
 // The LDS image is lane-linear per wave instruction, so the XOR swizzle is applied to the per-lane SOURCE address.
-template <typename T, bool OUT32, int MODE>
+template <typename T, bool OUT32>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
-  constexpr bool GLDS = MODE != 0;
-  constexpr int ROWB = StageCfg<MODE>::ROWB, NSTAGE = StageCfg<MODE>::NSTAGE;
   constexpr int OPER_BYTES = BM * ROWB;
   constexpr int SPR = ROWB / 16;          // 16-byte slots per row
   constexpr int KSUB = ROWB / 64;         // MFMA K sub-steps per stage (64 bytes of K each)
   constexpr int LROWS = 256 / SPR;        // rows covered by one pass of the 256 threads
-  constexpr int LPASS = BM / LROWS;       // passes (= LDS-DMA instructions per operand per wave): 4 or 2
+  constexpr int LPASS = BM / LROWS;       // passes (= LDS-DMA instructions per operand per wave): 2
   typedef typename std::conditional<OUT32, float, T>::type TO;   // stored output type
   constexpr int KPV = Elem<T>::kPerVec;      // elements per 16 B
   constexpr int KPVO = Elem<TO>::kPerVec;
   constexpr int BK = ROWB / (int)sizeof(T);  // K elements per step
   constexpr int CROW = BN * (int)sizeof(TO) + 16;  // padded C-tile row
   // all LDS lives in the one dynamic array (keeps its base 16-byte aligned); the tap list sits behind the tiles
-  static_assert(!OUT32 || true, "");
   constexpr int MAIN_BYTES = (2 * NSTAGE * OPER_BYTES) > (BM * CROW) ? (2 * NSTAGE * OPER_BYTES) : (BM * CROW);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* s_tap = reinterpret_cast<int*>(smem + MAIN_BYTES);
@@ -135,7 +122,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   const int steps = ntap * kchunks;
   if (steps == 0 && p.accumulate) return;  // a phase without taps contributes zeros
 
-  // ---- per-thread load bookkeeping: 4 rows of each operand, one 16-byte slot -------------------------
+  // ---- per-thread load bookkeeping: 2 rows of each operand, one 16-byte slot -------------------------
   const int slot = tid % SPR;
   const int trow = tid / SPR;
   int rowbase[LPASS];   // ((n*Hin + iy0)*Win + ix0) is not enough (taps move iy/ix): keep n, iy0, ix0
@@ -175,9 +162,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ra_ = wn * 64 + i * 16 + fr;
-        fa[i] = *reinterpret_cast<const vec16*>(wa + swz<ROWB>(ra_, kk * 4 + fg));
+        fa[i] = *reinterpret_cast<const vec16*>(wa + swz(ra_, kk * 4 + fg));
         const int rb_ = wm * 64 + i * 16 + fr;
-        fb[i] = *reinterpret_cast<const vec16*>(xb + swz<ROWB>(rb_, kk * 4 + fg));
+        fb[i] = *reinterpret_cast<const vec16*>(xb + swz(rb_, kk * 4 + fg));
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -192,126 +179,73 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   };
 
-  if constexpr (GLDS) {
-    // this thread fills PHYSICAL slot `slot` of rows trow + LROWS*i; that slot holds logical slot slot ^ f(row), and f(row)
-    // is the same for all of the thread's rows (LROWS/2 is a multiple of the swizzle period)
-    const int lslot = ROWB == 128 ? (slot ^ ((trow >> 1) & 7)) : (slot ^ ((trow >> 1) & 3));
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    // Source addresses are strength-reduced: PMC showed the first LDS-DMA version VALU-bound on 64-bit address arithmetic
-    // (36 % of wave cycles issuing, MFMA pipe ~20 % busy).  Per tap each row's base pointer and validity are computed
-    // once; per K step only a channel offset is added.
-    const T* xrow[LPASS];
-    const T* wrow[LPASS];
-    bool xok[LPASS], wok[LPASS];
-    int cur_tap = -1;
-    auto issue = [&](int tapi, int kc, int buf) {
-      if (tapi != cur_tap) {
-        cur_tap = tapi;
-        const int dy = s_tap[3 * tapi], dx = s_tap[3 * tapi + 1], widx = s_tap[3 * tapi + 2];
-#pragma unroll
-        for (int i = 0; i < LPASS; ++i) {
-          const int iy = riy[i] + dy, ix = rix[i] + dx;
-          xok[i] = rok[i] && (unsigned)iy < (unsigned)g.Hin && (unsigned)ix < (unsigned)g.Win;
-          xrow[i] = xg + (((size_t)(rowbase[i] + (xok[i] ? iy : 0)) * g.Win + (xok[i] ? ix : 0)) * p.ldx + lslot * KPV);
-          const int ch = n0 + trow + LROWS * i;
-          wok[i] = ch < g.Cout;
-          wrow[i] = wg + (((size_t)widx * g.Cout + (wok[i] ? ch : 0)) * p.ldw + lslot * KPV);
-        }
-      }
-      const int kofs = kc * BK;
-      const bool kok = kofs + lslot * KPV < g.Cin;
-      char* wa = smem + buf * (2 * OPER_BYTES);
-      char* xb = wa + OPER_BYTES;
-#pragma unroll
-      for (int i = 0; i < LPASS; ++i) {
-        const void* srcx = (kok && xok[i]) ? (const void*)(xrow[i] + kofs) : (const void*)dc_zero_page;
-        const void* srcw = (kok && wok[i]) ? (const void*)(wrow[i] + kofs) : (const void*)dc_zero_page;
-        const int rowoff = (LROWS * i + (64 / SPR) * wv) * ROWB;   // wave-uniform: one instruction fills 1 KiB of rows
-        __builtin_amdgcn_global_load_lds((gas_ptr)srcw, (lds_ptr)(wa + rowoff), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gas_ptr)srcx, (lds_ptr)(xb + rowoff), 16, 0, 0);
-      }
-    };
-    int tapi = 0, kc = 0;
-    DC_STAMP(2);
-    if constexpr (NSTAGE == 2) {
-      if (steps > 0) issue(0, 0, 0);
-      __syncthreads();   // (waits vmcnt(0): stage 0 has landed for every wave)
-      for (int s = 0; s < steps; ++s) {
-        next_step(tapi, kc);
-        if (s + 1 < steps) issue(tapi, kc, (s + 1) & 1);
-        compute(s & 1);
-        __syncthreads();   // drains this wave's LDS-DMA (vmcnt(0)) and orders it before the next iteration's reads
-      }
-    } else {
-      // 3-stage ring, counted waits.  Each issue() is 2*LPASS = 4 LDS-DMA instructions per wave, retired in order.
-      // Iteration s: wait until stage s has landed (leave the younger stage in flight), barrier (everybody's stage s is
-      // visible AND everybody has finished reading the buffer of stage s-1, which is the one stage s+2 will overwrite),
-      // issue stage s+2, compute stage s.  Raw s_barrier: __syncthreads() would drain vmcnt to 0.
-      // prologue: NSTAGE-1 stages in flight
-#pragma unroll
-      for (int q = 0; q < NSTAGE - 1; ++q) {
-        if (q < steps) issue(tapi, kc, q);
-        next_step(tapi, kc);
-      }
-      for (int s = 0; s < steps; ++s) {
-        // stage s must have landed; up to NSTAGE-2 younger stages (4 LDS-DMA instructions each) may stay in flight
-        const int younger = min(NSTAGE - 2, steps - 1 - s);
-        if (younger >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-#ifdef DC_STAMPS
-        if (s == 0) DC_STAMP(3);
-#endif
-        if (s + NSTAGE - 1 < steps) issue(tapi, kc, (s + NSTAGE - 1) % NSTAGE);
-        next_step(tapi, kc);
-        compute(s % NSTAGE);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();   // all waves done with the operand ring before the epilogue reuses it as the C tile
-    }
-  } else {
-    vec16 ra[LPASS], rb[LPASS];
-    auto load_step = [&](int tapi, int kc) {
+  // this thread fills PHYSICAL slot `slot` of rows trow + LROWS*i; that slot holds logical slot slot ^ f(row), and f(row)
+  // is the same for all of the thread's rows (LROWS/2 is a multiple of the swizzle period)
+  const int lslot = slot ^ ((trow >> 1) & 3);
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  // Source addresses are strength-reduced: PMC showed the first LDS-DMA version VALU-bound on 64-bit address arithmetic
+  // (36 % of wave cycles issuing, MFMA pipe ~20 % busy).  Per tap each row's base pointer and validity are computed
+  // once; per K step only a channel offset is added.
+  const T* xrow[LPASS];
+  const T* wrow[LPASS];
+  bool xok[LPASS], wok[LPASS];
+  int cur_tap = -1;
+  auto issue = [&](int tapi, int kc, int buf) {
+    if (tapi != cur_tap) {
+      cur_tap = tapi;
       const int dy = s_tap[3 * tapi], dx = s_tap[3 * tapi + 1], widx = s_tap[3 * tapi + 2];
-      const int kofs = kc * BK + slot * KPV;
-      const bool kok = kofs < g.Cin;
 #pragma unroll
       for (int i = 0; i < LPASS; ++i) {
         const int iy = riy[i] + dy, ix = rix[i] + dx;
-        const bool ok = kok && rok[i] && (unsigned)iy < (unsigned)g.Hin && (unsigned)ix < (unsigned)g.Win;
-        rb[i] = ok ? ldg16(xg + (((size_t)(rowbase[i] + iy) * g.Win + ix) * p.ldx + kofs)) : zero16();
+        xok[i] = rok[i] && (unsigned)iy < (unsigned)g.Hin && (unsigned)ix < (unsigned)g.Win;
+        xrow[i] = xg + (((size_t)(rowbase[i] + (xok[i] ? iy : 0)) * g.Win + (xok[i] ? ix : 0)) * p.ldx + lslot * KPV);
         const int ch = n0 + trow + LROWS * i;
-        ra[i] = (kok && ch < g.Cout) ? ldg16(wg + (((size_t)widx * g.Cout + ch) * p.ldw + kofs)) : zero16();
+        wok[i] = ch < g.Cout;
+        wrow[i] = wg + (((size_t)widx * g.Cout + (wok[i] ? ch : 0)) * p.ldw + lslot * KPV);
       }
-    };
-    auto store_step = [&](int buf) {
-      char* wa = smem + buf * (2 * OPER_BYTES);
-      char* xb = wa + OPER_BYTES;
+    }
+    const int kofs = kc * BK;
+    const bool kok = kofs + lslot * KPV < g.Cin;
+    char* wa = smem + buf * (2 * OPER_BYTES);
+    char* xb = wa + OPER_BYTES;
 #pragma unroll
-      for (int i = 0; i < LPASS; ++i) {
-        const int r = trow + LROWS * i;
-        const int o = swz<ROWB>(r, slot);
-        *reinterpret_cast<vec16*>(wa + o) = ra[i];
-        *reinterpret_cast<vec16*>(xb + o) = rb[i];
-      }
-    };
-    if (steps > 0) {
-      load_step(0, 0);
-      store_step(0);
+    for (int i = 0; i < LPASS; ++i) {
+      const void* srcx = (kok && xok[i]) ? (const void*)(xrow[i] + kofs) : (const void*)dc_zero_page;
+      const void* srcw = (kok && wok[i]) ? (const void*)(wrow[i] + kofs) : (const void*)dc_zero_page;
+      const int rowoff = (LROWS * i + (64 / SPR) * wv) * ROWB;   // wave-uniform: one instruction fills 1 KiB of rows
+      __builtin_amdgcn_global_load_lds((gas_ptr)srcw, (lds_ptr)(wa + rowoff), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gas_ptr)srcx, (lds_ptr)(xb + rowoff), 16, 0, 0);
     }
-    __syncthreads();
-    int tapi = 0, kc = 0;
-    for (int s = 0; s < steps; ++s) {
-      next_step(tapi, kc);
-      const bool more = (s + 1) < steps;
-      if (more) load_step(tapi, kc);
-      compute(s & 1);
-      if (more) store_step((s + 1) & 1);
-      __syncthreads();
-    }
+  };
+  int tapi = 0, kc = 0;
+  DC_STAMP(2);
+  // NSTAGE-stage ring, counted waits.  Each issue() is 2*LPASS = 4 LDS-DMA instructions per wave, retired in order.
+  // Iteration s: wait until stage s has landed (leave the younger stage in flight), barrier (everybody's stage s is
+  // visible AND everybody has finished reading the buffer of stage s-1, which is the one stage s+2 will overwrite),
+  // issue stage s+2, compute stage s.  Raw s_barrier: __syncthreads() would drain vmcnt to 0.
+  // prologue: NSTAGE-1 stages in flight
+#pragma unroll
+  for (int q = 0; q < NSTAGE - 1; ++q) {
+    if (q < steps) issue(tapi, kc, q);
+    next_step(tapi, kc);
   }
+  for (int s = 0; s < steps; ++s) {
+    // stage s must have landed; up to NSTAGE-2 younger stages (4 LDS-DMA instructions each) may stay in flight
+    const int younger = min(NSTAGE - 2, steps - 1 - s);
+    if (younger >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    else if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#ifdef DC_STAMPS
+    if (s == 0) DC_STAMP(3);
+#endif
+    if (s + NSTAGE - 1 < steps) issue(tapi, kc, (s + NSTAGE - 1) % NSTAGE);
+    next_step(tapi, kc);
+    compute(s % NSTAGE);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();   // all waves done with the operand ring before the epilogue reuses it as the C tile
 
   // ---- epilogue ------------------------------------------------------------------------------------
   DC_STAMP(4);
@@ -508,28 +442,18 @@ __global__ __launch_bounds__(256) void tiny_gemm_kernel(const IgemmParams p) {
   }
 }
 
-static int g_igemm_mode = 2;
-static int g_thin_fwd = 1;    // dedicated kernel for the thin 3x3 stem convolutions (thinconv.hip)
 static int g_igemm256 = 1;   // 0: never, 1: where the planner expects it to win, 2: whenever eligible (bf16, bf16 output)
 
-template <typename T, bool OUT32, int MODE>
-static int launch_igemm2(const IgemmParams& p, hipStream_t st) {
-  constexpr int CROW = BN * (int)(OUT32 ? 4 : sizeof(T)) + 16;
-  constexpr size_t RING = (size_t)2 * StageCfg<MODE>::NSTAGE * BM * StageCfg<MODE>::ROWB;
-  const size_t lds = (RING > (size_t)BM * CROW ? RING : (size_t)BM * CROW) + 128;
-  DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, OUT32, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  dim3 grid(cdiv(p.g.Cout, BN) * cdiv(p.M - p.m_beg, BM) * (p.zfill ? 1 : p.g.os * p.g.os));
-  hipLaunchKernelGGL((igemm_kernel<T, OUT32, MODE>), grid, dim3(256), lds, st, p);
-  DC_CHECK_LAUNCH();
-  return 0;
-}
 template <typename T, bool OUT32>
 static int launch_igemm(const IgemmParams& p, hipStream_t st) {
-  if (g_igemm_mode == 4) return launch_igemm2<T, OUT32, 4>(p, st);
-  if (g_igemm_mode == 3) return launch_igemm2<T, OUT32, 3>(p, st);
-  if (g_igemm_mode == 2) return launch_igemm2<T, OUT32, 2>(p, st);
-  if (g_igemm_mode == 1) return launch_igemm2<T, OUT32, 1>(p, st);
-  return launch_igemm2<T, OUT32, 0>(p, st);
+  constexpr int CROW = BN * (int)(OUT32 ? 4 : sizeof(T)) + 16;
+  constexpr size_t RING = (size_t)2 * NSTAGE * BM * ROWB;
+  const size_t lds = (RING > (size_t)BM * CROW ? RING : (size_t)BM * CROW) + 128;
+  DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, OUT32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  dim3 grid(cdiv(p.g.Cout, BN) * cdiv(p.M - p.m_beg, BM) * (p.zfill ? 1 : p.g.os * p.g.os));
+  hipLaunchKernelGGL((igemm_kernel<T, OUT32>), grid, dim3(256), lds, st, p);
+  DC_CHECK_LAUNCH();
+  return 0;
 }
 
 // Planner for the tile shape.  The 128-tile kernel keeps 3 workgroups per CU (768 slots), the 256-tile kernel one (256 slots).
@@ -537,7 +461,6 @@ static int launch_igemm(const IgemmParams& p, hipStream_t st) {
 // (>= 64 steps of 32), about the same at 20-60 steps (the 728-channel layers) and 1.1-1.2 when it is short (its prologue and
 // 132 KiB epilogue are not hidden by a co-resident workgroup) -- for 4/3 of the work per round.  When both fit one round the
 // small tile (finer tail, three workgroups hiding each other's latencies) keeps the layer unless the K loop is long.
-static int g_rel256 = 0;   // 0: model below; otherwise cost of a 256-tile round in percent of a 128-tile round (tuning switch)
 // Pointwise layers on the one-wave-per-SIMD kernel (igemm384.hip).  0: never, 1: where the round model below expects it to win,
 // 2 / 3: whenever eligible with 256- / 128-pixel tiles (tests and A/B runs).  Costs are in rounds of 256 x 256 tiles: a
 // 256 x 384 tile is 1.5 of them, a 128 x 384 tile 0.8 (its weight fill is not halved), a round of the 128-tile kernel about 1 at
@@ -547,8 +470,6 @@ static int g_igemm256p_wgs = 0;      // its workgroups ("igemm256p_wgs"); 0: few
 static int g_igemm256p_min = 257;    // fewest tiles it is used for ("igemm256p_min")
 static int g_pw384 = 1;
 static int g_pw192 = 1;             // 128 x 192 tiles for one-round launches of few pixels ("pw192")
-static int g_zfill = 1;             // 1 x 1 stride-2 data gradients written first-hand: one launch over phase (0, 0) stores all four phases ("igemm_zfill")
-static int g_pw384_k64 = 1;         // 256 x 384 tiles with 128-byte K rows where the planner picks that tile ("pw384_k64")
 static int g_pw224 = 1;             // 224 x 384 tiles with weights from the [k][n] packing where the caller passes it ("pw224"; 2: whenever eligible)
 static int pw384_plan(const IgemmParams& p) {
   if (g_pw224 == 2 && pw224_eligible(p)) return 224;
@@ -564,7 +485,7 @@ static int pw384_plan(const IgemmParams& p) {
   const long t8 = pw384_tiles(p, 8), t4 = pw384_tiles(p, 4);
   // 256-pixel tiles run with 64-deep stages of 128-byte K rows (whole L2 lines per LDS-DMA row piece): 4 - 15 % faster than 32-deep stages
   // of 64-byte rows on every shape (profiles/r03_pw384_bench.txt, second table), so a round of them is priced at 1.3 instead of 1.5
-  const bool k64 = g_pw384_k64 && p.g.Cin >= 128;
+  const bool k64 = p.g.Cin >= 128;
   const double c8 = t8 >= 160 ? cdiv(t8, 256) * (k64 ? 1.3 : 1.5) : 1e9, c4 = t4 >= 160 ? cdiv(t4, 256) * 0.8 : 1e9;
   const double best = c8 < c4 ? c8 : c4;
   // few pixels (local batch 2): 128 x 192 tiles when they are ONE round of one workgroup per CU and neither 384-wide tile fills the chip
@@ -589,7 +510,7 @@ static bool igemm256_wins(const IgemmParams& p) {
   const long r128 = cdiv(t128, 768), r256 = cdiv(t256, 256);
   const int steps = cdiv(p.g.Cin, 32) * (p.g.ntaps / (p.g.os * p.g.os) > 0 ? p.g.ntaps / (p.g.os * p.g.os) : 1);   // average over phases
   if (r128 == 1 && r256 == 1 && steps < 64) return false;
-  const int rel = g_rel256 > 0 ? g_rel256 : steps >= 64 ? 90 : steps >= 20 ? 97 : 115;
+  const int rel = steps >= 64 ? 90 : steps >= 20 ? 97 : 115;   // cost of a 256-tile round in percent of a 128-tile round
   return r256 * rel < r128 * 100;
 }
 
@@ -619,13 +540,6 @@ static int run_gather(const dc_conv_desc* d, GatherMode mode, int N, int Hi, int
   const long M = (long)N * p.g.Qh * p.g.Qw;
   DC_REQUIRE(M < (1L << 31) - BM, "dc_conv: too many pixels for 32-bit indexing");
   p.M = (int)M;
-  p.m_beg = 0;
-  p.phase_fast = 0;
-  p.zero_page = nullptr;
-  p.ngroup = 0;
-  p.ksplit = 0; p.kslab = nullptr;
-  p.zfill = 0;
-  p.bst = BnBwdEpi{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
   if (bst != nullptr) {
     DC_REQUIRE(slab != nullptr && !accumulate && !out32 && bias == nullptr, "dc_conv_dgrad_bnstats: needs a slab, no bias, no accumulate");
     if (int e = check_view(bst->y, bst->ldy, p.g.Cout, d->dtype, "dc_conv_dgrad_bnstats y")) return e;
@@ -642,7 +556,7 @@ static int run_gather(const dc_conv_desc* d, GatherMode mode, int N, int Hi, int
     DC_CHECK_LAUNCH();
     return 0;
   }
-  if (!sum_row && bst == nullptr && g_thin_fwd && thin_fwd_eligible(p.g, d->dtype, bias != nullptr, accumulate, out32))
+  if (!sum_row && bst == nullptr && thin_fwd_eligible(p.g, d->dtype, bias != nullptr, accumulate, out32))
     return launch_thin_fwd(p.g, N, in, ldin, w, p.ldw, out, ldout, slab, p.mtiles * p.g.os * p.g.os, st);
   if (d->dtype == DC_BF16 && !out32 && bst == nullptr) {      // (the BatchNorm-backward epilogue lives in the LDS-epilogue kernels)
     if (const int npb = pw384_plan(p)) {
@@ -679,7 +593,7 @@ static int run_gather(const dc_conv_desc* d, GatherMode mode, int N, int Hi, int
     }
   }
   // every tap in phase (0, 0) of a 2 x 2 phase grid, written first-hand, nothing riding along: one launch over that phase stores all four
-  if (g_zfill && p.g.os == 2 && p.g.ntaps > 0 && p.g.phase_beg[1] == p.g.ntaps && !accumulate && slab == nullptr && bias == nullptr && bst == nullptr && !out32)
+  if (p.g.os == 2 && p.g.ntaps > 0 && p.g.phase_beg[1] == p.g.ntaps && !accumulate && slab == nullptr && bias == nullptr && bst == nullptr && !out32)
     p.zfill = 1;
   if (d->dtype == DC_BF16) return out32 ? launch_igemm<bf16, true>(p, st) : launch_igemm<bf16, false>(p, st);
   return launch_igemm<float, false>(p, st);
@@ -936,26 +850,21 @@ extern "C" int dc_debug_stamp_buf(void* buf) {
 }
 #endif
 
-static int g_pack_blocks = 2048;   // workgroups of the flat dc_pack_all grid (tuning switch "pack_blocks")
+constexpr int PACK_BLOCKS = 2048;   // workgroups of the flat dc_pack_all grid
 extern "C" int dc_pack_all(int dtype, const void* table_dev, int nentries, void* stream) {
   DC_REQUIRE(table_dev != nullptr && nentries > 0, "dc_pack_all: bad argument");
   DC_REQUIRE(sizeof(PackEntry) == 40, "dc_pack_all: entry layout changed");
   DC_REQUIRE(nentries <= PACK_MAX_ENTRIES, "dc_pack_all: too many entries for one launch");
-  dim3 grid(g_pack_blocks);
+  dim3 grid(PACK_BLOCKS);
   if (dtype == DC_BF16) hipLaunchKernelGGL(pack_all_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const PackEntry*)table_dev, nentries);
   else hipLaunchKernelGGL(pack_all_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const PackEntry*)table_dev, nentries);
   DC_CHECK_LAUNCH();
   return 0;
 }
 
-// Tuning switches for A/B measurements in one process: "igemm_mode" (0/1/2, see StageCfg), "wgrad_target_blocks".
-extern "C" int dc_wgrad_set_target_blocks(int n);
-extern "C" int dc_wgrad_set_mode(int m);
-extern "C" int dc_wgrad_set_min_steps(int n);
-extern "C" int dc_wgrad_set_thin(int m);
+// Switches that force a kernel at shapes the planners would not give it (tests, A/B runs in one process).
 extern "C" int dc_wgrad_set_384(int m);
 extern "C" int dc_wgrad_set_384_slots(int n);
-extern "C" int dc_wgrad_set_384_fill(int pct);
 extern "C" int dc_wgrad_set_384_min_stages(int n);
 extern "C" int dc_head_set_fused(int v);
 extern "C" int dc_head_set_dgrad_fused(int v);
@@ -963,33 +872,17 @@ extern "C" int dc_head_set_wgrad_fused(int v);
 extern "C" int dc_dw_set_option(const char* name, int value);
 extern "C" int dc_bn_set_option(const char* name, int value);
 extern "C" int dc_set_option(const char* name, int value) {
-  if (name != nullptr && strcmp(name, "igemm_mode") == 0) {
-    if (value < 0 || value > 4) return dc_fail("dc_set_option: igemm_mode must be 0..4", __FILE__, __LINE__);
-    g_igemm_mode = value;
-    return 0;
-  }
   if (name != nullptr && strcmp(name, "igemm256") == 0) { g_igemm256 = value; return 0; }
   if (name != nullptr && strcmp(name, "pw384") == 0) { g_pw384 = value; return 0; }
   if (name != nullptr && strcmp(name, "igemm256p") == 0) { g_igemm256p = value; return 0; }
   if (name != nullptr && strcmp(name, "igemm256p_wgs") == 0) { g_igemm256p_wgs = value; return 0; }
   if (name != nullptr && strcmp(name, "igemm256p_min") == 0) { g_igemm256p_min = value; return 0; }
-  if (name != nullptr && strcmp(name, "pw384_k64") == 0) { g_pw384_k64 = value; return 0; }
   if (name != nullptr && strcmp(name, "pw224") == 0) { g_pw224 = value; return 0; }
   if (name != nullptr && strcmp(name, "pw192") == 0) { g_pw192 = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm_zfill") == 0) { g_zfill = value; return 0; }
   if (name != nullptr && strcmp(name, "igemm256_splitk") == 0) { igemm256_set_splitk(value); return 0; }
-  if (name != nullptr && strcmp(name, "thin_fwd") == 0) { g_thin_fwd = value != 0; return 0; }
   if (name != nullptr && strcmp(name, "thin_tile") == 0) { thin_set_tile(value); return 0; }
-  if (name != nullptr && strcmp(name, "igemm256_rel") == 0) { g_rel256 = value; return 0; }
-  if (name != nullptr && strcmp(name, "pack_blocks") == 0 && value > 0) { g_pack_blocks = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm256_phase_fast") == 0) { igemm256_set_phase_fast(value); return 0; }
-  if (name != nullptr && strcmp(name, "wgrad_target_blocks") == 0) return dc_wgrad_set_target_blocks(value);
-  if (name != nullptr && strcmp(name, "wgrad_mode") == 0) return dc_wgrad_set_mode(value);
-  if (name != nullptr && strcmp(name, "wgrad_min_steps") == 0) return dc_wgrad_set_min_steps(value);
-  if (name != nullptr && strcmp(name, "thin_wgrad") == 0) return dc_wgrad_set_thin(value);
   if (name != nullptr && strcmp(name, "wgrad384") == 0) return dc_wgrad_set_384(value);
   if (name != nullptr && strcmp(name, "wgrad384_slots") == 0) return dc_wgrad_set_384_slots(value);
-  if (name != nullptr && strcmp(name, "wgrad384_fill") == 0) return dc_wgrad_set_384_fill(value);
   if (name != nullptr && strcmp(name, "wgrad384_min_stages") == 0) return dc_wgrad_set_384_min_stages(value);
   if (name != nullptr && strcmp(name, "head_fused") == 0) return dc_head_set_fused(value);
   if (name != nullptr && strcmp(name, "head_dgrad_fused") == 0) return dc_head_set_dgrad_fused(value);
@@ -1003,12 +896,9 @@ extern "C" int dc_set_option(const char* name, int value) {
 // so that a switch one test leaves behind cannot change what the next one measures -- a stale "restore" of this kind once ran the model
 // tests on an experimental kernel), and the library applies the same table when it is loaded, so the table IS the default.
 static const struct { const char* name; int value; } kOptionDefaults[] = {
-    {"igemm_mode", 2}, {"igemm256", 1}, {"pw384", 1}, {"pw384_k64", 1}, {"pw224", 1}, {"pw192", 1}, {"igemm256p", 1}, {"igemm256p_wgs", 0}, {"igemm256p_min", 257},
-    {"thin_fwd", 1}, {"thin_tile", 1}, {"igemm256_rel", 0}, {"pack_blocks", 2048},
-    {"igemm256_phase_fast", 1}, {"wgrad_target_blocks", 768},
-    {"wgrad_mode", 1}, {"wgrad_min_steps", 16}, {"thin_wgrad", 1}, 
-    {"wgrad384", 1}, {"wgrad384_slots", 192}, {"wgrad384_fill", 66}, {"wgrad384_min_stages", 96}, {"head_fused", 1},
-    {"head_dgrad_fused", 1}, {"head_wgrad_fused", 1}, {"igemm256_splitk", 1}, {"igemm_zfill", 1}, {"pw_bn_bwd", 3}, {"sep_fwd", 1}, {"dw_tile", 1}, {"dw_wgrad_tpb", 0}, {"dw_cg", 0}, {"dw_pipe", 1}, {"bn_cgw", 32}, {"bn_rows", 32}, {"bn_apply_rows", 1}, {"bn_fin_mul_fwd", 2}, {"bn_fin_mul_bwd", 2},
+    {"igemm256", 1}, {"pw384", 1}, {"pw224", 1}, {"pw192", 1}, {"igemm256p", 1}, {"igemm256p_wgs", 0}, {"igemm256p_min", 257}, {"thin_tile", 1},
+    {"wgrad384", 1}, {"wgrad384_slots", 192}, {"wgrad384_min_stages", 96}, {"head_fused", 1}, {"head_dgrad_fused", 1}, {"head_wgrad_fused", 1},
+    {"igemm256_splitk", 1}, {"dw_tile", 1}, {"dw_wgrad_tpb", 0}, {"dw_pipe", 1}, {"bn_apply_rows", 1},
 };
 
 extern "C" int dc_reset_options(void) {
@@ -1061,15 +951,14 @@ static int kn_forward_plan(const dc_conv_desc* d, int N, int Hi, int Wi, long* M
   if (!build_geom(*d, Hi, Wi, kFwd, &p.g)) return 0;
   const long M = (long)N * p.g.Qh * p.g.Qw;
   if (M >= (1L << 31) - BM) return 0;
-  if (M <= TINY_M || (g_thin_fwd && thin_fwd_eligible(p.g, d->dtype, false, 0, false))) return 0;      // (run_gather asks these first)
+  if (M <= TINY_M || thin_fwd_eligible(p.g, d->dtype, false, 0, false)) return 0;      // (run_gather asks these first)
   p.x = nullptr; p.w = nullptr; p.y = nullptr; p.bias = nullptr; p.slab = nullptr;
   p.N = N; p.ldx = weight_ld(p.g.Cin); p.ldy = weight_ld(p.g.Cout); p.ldw = weight_ld(p.g.Cin);
   alignas(16) static const char some_image[16] = {0};
   p.w_kn = some_image;                       // (any 16-byte aligned non-null pointer: eligibility only looks at it)
   p.ldw_kn = weight_ld(p.g.Cout);
-  p.M = (int)M; p.m_beg = 0; p.phase_fast = 0; p.zero_page = nullptr; p.ngroup = 0; p.ksplit = 0; p.kslab = nullptr; p.zfill = 0;
-  p.bst = BnBwdEpi{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
-  p.mtiles = cdiv(M, BM); p.accumulate = 0;
+  p.M = (int)M;
+  p.mtiles = cdiv(M, BM);
   *Mout = M;
   return pw384_plan(p);
 }
@@ -1133,14 +1022,10 @@ static int dilated_group_impl(const dc_conv_desc* d, int N, int Hi, int Wi, int 
   const long M = (long)N * p.g.Qh * p.g.Qw;
   DC_REQUIRE(N > 0 && M < (1L << 31) - BM, "dc_conv_fwd_dilated_group: bad pixel count");
   p.x = x; p.w = wfs ? wfs[0] : nullptr; p.y = ys ? ys[0] : nullptr; p.bias = nullptr; p.slab = stat_slabs ? stat_slabs[0] : nullptr;
-  p.ksplit = 0; p.kslab = nullptr; p.zfill = 0;
-  p.bst = BnBwdEpi{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
   p.N = N; p.ldx = ldx; p.ldy = ldy;
   p.ldw = weight_ld(p.g.Cin);
-  p.w_kn = nullptr; p.ldw_kn = 0;
-  p.M = (int)M; p.m_beg = 0; p.phase_fast = 0; p.zero_page = nullptr;
+  p.M = (int)M;
   p.mtiles = cdiv(M, BM);
-  p.accumulate = 0;
   p.ngroup = count;
   size_t need = 0;
   const int splits = igemm256_splitk_plan(p, &need);

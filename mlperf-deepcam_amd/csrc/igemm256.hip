@@ -79,7 +79,6 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
 
   // XCD-aware tile order (see igemm.hip): consecutive tiles of an XCD walk the channel tiles of one pixel tile first
   const int ntn = (g.Cout + TN - 1) / TN;
-  const int mt256 = (p.M - p.m_beg + TM - 1) / TM;
   const int nwg = gridDim.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, xslot = blockIdx.x >> 3;
   int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + xslot;
@@ -113,8 +112,8 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
   // workgroups finish at different times (their write bursts interleave with the others' K loops), and the four phases of one
   // pixel tile read the same input rows through one XCD's L2
   const int nph = g.os * g.os;
-  const int phase = p.phase_fast ? rest % nph : rest / mt256;
-  const int mtile = p.phase_fast ? rest / nph : rest % mt256;
+  const int phase = rest % nph;
+  const int mtile = rest / nph;
   const int n0 = ntile_n * TN, m0 = p.m_beg + mtile * TM;
   const int py = phase / g.os, px = phase % g.os;
 
@@ -512,10 +511,6 @@ extern "C" int dc_debug_stamp_buf256(void* buf) {
 }
 #endif
 
-static int g_phase_fast = 1;     // tile order of multi-phase (transposed / strided) launches: phase fastest (A/B switch "igemm256_phase_fast")
-void igemm256_set_phase_fast(int v) { g_phase_fast = v ? 1 : 0; }
-int igemm256_phase_fast_enabled() { return g_phase_fast; }
-
 
 // Sum of the split-K partial tiles of one 128-pixel half of one tile, in the order of the splits: y (bf16) and the BatchNorm partial sums of
 // the STORED values, one slab row per half as the kernel's own epilogue leaves them.  256 threads = 64 channel groups of 4 x 4 row lanes.
@@ -627,7 +622,6 @@ int launch_igemm256(const IgemmParams& p_in, hipStream_t st) {
   if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
   IgemmParams p = p_in;
   p.zero_page = zero_dev;
-  p.phase_fast = g_phase_fast;
   hipLaunchKernelGGL(igemm256_kernel, dim3((unsigned)(igemm256_tiles(p) * (p.ksplit > 1 ? p.ksplit : 1))), dim3(512), lds, st, p);
   DC_CHECK_LAUNCH();
   return 0;

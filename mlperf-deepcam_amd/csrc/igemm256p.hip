@@ -67,7 +67,7 @@ struct Igemm256pArgs {
   int hwS;
   unsigned wM;
   int wS;
-  int os, is, ldx, ldy, ldw, M, mtiles, phase_fast, ntiles;
+  int os, is, ldx, ldy, ldw, M, mtiles, ntiles;
   int phase_beg[5];
   int taps[9 * 3];   // dy, dx, widx, sorted by phase
 };
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(512) void igemm256p_kernel(const Igemm256pArgs a) {
   };
 
   // Tile order as igemm256_kernel (XCD-aware: XCD x owns a contiguous share of the tiles, consecutive tiles walk the channel tiles,
-  // then -- phase_fast -- the sub-pixel phases of one pixel tile).  gridDim.x is a multiple of 8; workgroup i of W = gridDim.x / 8
+  // then the sub-pixel phases of one pixel tile).  gridDim.x is a multiple of 8; workgroup i of W = gridDim.x / 8
   // on XCD x takes, in round r, slot r * W + (i + r) % W of its XCD's share (W even; r * W + i for odd W).  The rotation by r matters: with a plain stride of W a
   // workgroup would meet the same channel tile and the same phase in every round whenever W is a multiple of their counts, and the
   // phases of a transposed convolution cost 1 : 2 : 2 : 4.
@@ -113,7 +113,6 @@ __global__ __launch_bounds__(512) void igemm256p_kernel(const Igemm256pArgs a) {
     const KArgs k = args();
     const int ntiles = k->ntiles;
     const int ntn = (k->Cout + TN - 1) / TN;
-    const int mt256 = (k->M + TM - 1) / TM;
     const int nph = k->os * k->os;
     const int q8 = ntiles >> 3, r8 = ntiles & 7;
     const int xcd = blockIdx.x & 7, xslot = slot_of(r);
@@ -121,8 +120,8 @@ __global__ __launch_bounds__(512) void igemm256p_kernel(const Igemm256pArgs a) {
     const int ntile_n = tile % ntn;
     const int rest = tile / ntn;
     TileInfo t;
-    t.phase = k->phase_fast ? rest % nph : rest / mt256;
-    const int mtile = k->phase_fast ? rest / nph : rest % mt256;
+    t.phase = rest % nph;
+    const int mtile = rest / nph;
     t.n0 = ntile_n * TN;
     t.m0 = mtile * TM;
     t.tap_beg = k->phase_beg[t.phase];
@@ -483,7 +482,6 @@ int launch_igemm256p(const IgemmParams& p_in, int workgroups, hipStream_t st) {
   a.os = g.os; a.is = g.is;
   a.ldx = p_in.ldx; a.ldy = p_in.ldy; a.ldw = p_in.ldw;
   a.M = p_in.M; a.mtiles = p_in.mtiles;
-  a.phase_fast = igemm256_phase_fast_enabled();
   const long ntiles = igemm256_tiles(p_in);
   a.ntiles = (int)ntiles;
   for (int i = 0; i < 5; ++i) a.phase_beg[i] = g.phase_beg[i];

@@ -406,8 +406,6 @@ __global__ __launch_bounds__(512) void pw_bn_bwd256_kernel(const PwBwdArgs a) {
   }
 }
 
-static int g_pw_bn_bwd = 3;       // tuning switch "pw_bn_bwd": 0 = the three separate passes, bit 0 = layers with 128 output channels, bit 1 = with 256
-
 // workgroups = slab rows: every CU full once (the kernel is persistent; a partial second round would cost a whole one)
 // 256 output channels: pairs of 512-thread workgroups, one workgroup per CU; the rows are the pairs, a multiple of 8 (pairs sit 8 ids apart)
 int pwbwd256_pairs(long M) {
@@ -446,17 +444,15 @@ int pwbwd_grid(int Cin, long M) {
 
 }  // namespace
 
-void pw_bn_bwd_set(int v) { g_pw_bn_bwd = v; }
-
 }  // namespace dc
 
 using namespace dc;
 
 // Slab rows (= workgroups) of dc_pw_bn_bwd for this shape; 0: not served (the caller runs dc_bn_bwd_apply, dc_conv_dgrad and the weight gradient)
 extern "C" int dc_pw_bn_bwd_rows(int dtype, int Cin, int Cout, long M) {
-  if (!g_pw_bn_bwd || dtype != DC_BF16 || M < 65536 || M >= (1L << 31)) return 0;
-  if (Cout == 256 && (Cin == 128 || Cin == 256)) return (g_pw_bn_bwd & 2) ? pwbwd256_pairs(M) : 0;
-  if (Cout != PB_CO || (Cin != 64 && Cin != 128) || !(g_pw_bn_bwd & 1)) return 0;
+  if (dtype != DC_BF16 || M < 65536 || M >= (1L << 31)) return 0;
+  if (Cout == 256 && (Cin == 128 || Cin == 256)) return pwbwd256_pairs(M);
+  if (Cout != PB_CO || (Cin != 64 && Cin != 128)) return 0;
   return pwbwd_grid(Cin, M);
 }
 

@@ -204,8 +204,6 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(const SepFwdArgs a) {
   }
 }
 
-static int g_sep_fwd = 1;        // tuning switch "sep_fwd": 0 = depthwise and pointwise forward as two operators
-
 int sepfwd_grid(int Cin, int N, int H, int W) {
   const long tiles = (long)N * (H / 8) * (W / (Cin == 128 ? 16 : 32));
   long g = 512;                  // two workgroups per CU
@@ -215,15 +213,13 @@ int sepfwd_grid(int Cin, int N, int H, int W) {
 
 }  // namespace
 
-void sep_fwd_set(int v) { g_sep_fwd = v; }
-
 }  // namespace dc
 
 using namespace dc;
 
 // Workgroups (= statistics rows the kernel fills; it zeroes the caller's other rows) of dc_sepconv_fwd; 0: the pair is not served
 extern "C" int dc_sepconv_fwd_rows(int dtype, int Cin, int Cout, int stride, int dil, int N, int H, int W) {
-  if (!g_sep_fwd || dtype != DC_BF16 || Cout != SF_CO || (Cin != 64 && Cin != 128) || stride != 1 || dil != 1) return 0;
+  if (dtype != DC_BF16 || Cout != SF_CO || (Cin != 64 && Cin != 128) || stride != 1 || dil != 1) return 0;
   if (N <= 0 || (H % 8) || (W % (Cin == 128 ? 16 : 32)) || (long)N * H * W < 65536 || (long)N * H * W >= (1L << 31)) return 0;
   return sepfwd_grid(Cin, N, H, W);
 }

@@ -12,25 +12,17 @@
 
 namespace dc {
 
-template <typename T>
-struct WgTraits;
-template <>
-struct WgTraits<bf16> {
-  static constexpr int BP = 64;            // pixels per step
-  static constexpr int ROW = 128 * 2 + 32; // padded LDS row bytes (conflict-free transposed reads)
-};
-template <>
-struct WgTraits<float> {
-  static constexpr int BP = 32;
-  static constexpr int ROW = 128 * 4 + 64;
-};
+// Register-staged kernel: serves the layers whose x operand is formed on the way in (WgradParams::xscale), which the LDS-DMA kernel
+// below cannot do, since its loads bypass the registers.  bf16 only.
+constexpr int WG_REG_BP = 64;              // pixels per step
+constexpr int WG_REG_ROW = 128 * 2 + 32;   // padded LDS row bytes (conflict-free transposed reads)
 
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
-  using TR = WgTraits<T>;
+  static_assert(sizeof(T) == 2, "bf16 only");
   constexpr int KPV = Elem<T>::kPerVec;
-  constexpr int BP = TR::BP, ROW = TR::ROW;
-  constexpr int VPR = 128 * (int)sizeof(T) / 16;   // 16-byte vectors per tile row: 16 / 32
+  constexpr int BP = WG_REG_BP, ROW = WG_REG_ROW;
+  constexpr int VPR = 128 * (int)sizeof(T) / 16;   // 16-byte vectors per tile row: 16
   constexpr int TILE = BP * ROW;                   // bytes per operand tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -59,11 +51,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 
   // each thread moves 4 vectors per operand per step: vector v = tid + 256*i -> (row = v / VPR, col = v % VPR)
   vec16 rq[4], rp[4];
-  // x = act(y * xscale + xshift) formed here (bf16 only): a thread's column, i.e. its KPV channels, is the same for its four vectors
+  // x = act(y * xscale + xshift) formed here: a thread's column, i.e. its KPV channels, is the same for its four vectors
   // (256 is a multiple of VPR); vectors that were not loaded (padding, halo) stay zero
   [[maybe_unused]] unsigned xvalid = 0;
   [[maybe_unused]] float xsc[KPV], xsh[KPV];
-  const bool xform = sizeof(T) == 2 && p.xscale != nullptr;
+  const bool xform = p.xscale != nullptr;
   if (xform) {
     const int ci = ci0 + (tid % VPR) * KPV;
 #pragma unroll
@@ -106,17 +98,15 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
     for (int i = 0; i < 4; ++i) {
       const int v = tid + 256 * i;
       const int row = v / VPR, col = v % VPR;
-      if constexpr (sizeof(T) == 2) {
-        if (xform && (xvalid >> i & 1)) {
-          float f[KPV];
-          unpack(rp[i], f, T());
+      if (xform && (xvalid >> i & 1)) {
+        float f[KPV];
+        unpack(rp[i], f, T());
 #pragma unroll
-          for (int e = 0; e < KPV; ++e) {
-            f[e] = fmaf(f[e], xsc[e], xsh[e]);
-            if (p.xrelu) f[e] = fmaxf(f[e], 0.f);
-          }
-          pack(rp[i], f, T());
+        for (int e = 0; e < KPV; ++e) {
+          f[e] = fmaf(f[e], xsc[e], xsh[e]);
+          if (p.xrelu) f[e] = fmaxf(f[e], 0.f);
         }
+        pack(rp[i], f, T());
       }
       *reinterpret_cast<vec16*>(q + row * ROW + col * 16) = rq[i];
       *reinterpret_cast<vec16*>(pp + row * ROW + col * 16) = rp[i];
@@ -141,49 +131,31 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
     if (more) load_step(s + 1);
     const char* q = smem + (s & 1) * (2 * TILE);
     const char* pp = q + TILE;
-    if constexpr (sizeof(T) == 2) {
-      // two K=32 sub-steps; lane group fg owns pixels 8*fg .. 8*fg+7 of the sub-step
-      const int tq = (lane & 15) >> 2, tp = lane & 3;
+    // two K=32 sub-steps; lane group fg owns pixels 8*fg .. 8*fg+7 of the sub-step
+    const int tq = (lane & 15) >> 2, tp = lane & 3;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int prow = ks * 32 + 8 * fg + tq;
-        vec16 fa[4], fb[4];
+    for (int ks = 0; ks < 2; ++ks) {
+      const int prow = ks * 32 + 8 * fg + tq;
+      vec16 fa[4], fb[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int cq = (wq * 64 + i * 16 + 4 * tp) * 2;
-          const int cp = (wp * 64 + i * 16 + 4 * tp) * 2;
-          typedef __attribute__((address_space(3))) short4v lds_s4;
-          const short4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(q + prow * ROW + cq));
-          const short4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(q + (prow + 4) * ROW + cq));
-          const short4v b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(pp + prow * ROW + cp));
-          const short4v b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(pp + (prow + 4) * ROW + cp));
-          uint2 t0 = __builtin_bit_cast(uint2, a0), t1 = __builtin_bit_cast(uint2, a1);
-          fa[i].w[0] = t0.x; fa[i].w[1] = t0.y; fa[i].w[2] = t1.x; fa[i].w[3] = t1.y;
-          t0 = __builtin_bit_cast(uint2, b0); t1 = __builtin_bit_cast(uint2, b1);
-          fb[i].w[0] = t0.x; fb[i].w[1] = t0.y; fb[i].w[2] = t1.x; fb[i].w[3] = t1.y;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+      for (int i = 0; i < 4; ++i) {
+        const int cq = (wq * 64 + i * 16 + 4 * tp) * 2;
+        const int cp = (wp * 64 + i * 16 + 4 * tp) * 2;
+        typedef __attribute__((address_space(3))) short4v lds_s4;
+        const short4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(q + prow * ROW + cq));
+        const short4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(q + (prow + 4) * ROW + cq));
+        const short4v b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(pp + prow * ROW + cp));
+        const short4v b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(pp + (prow + 4) * ROW + cp));
+        uint2 t0 = __builtin_bit_cast(uint2, a0), t1 = __builtin_bit_cast(uint2, a1);
+        fa[i].w[0] = t0.x; fa[i].w[1] = t0.y; fa[i].w[2] = t1.x; fa[i].w[3] = t1.y;
+        t0 = __builtin_bit_cast(uint2, b0); t1 = __builtin_bit_cast(uint2, b1);
+        fb[i].w[0] = t0.x; fb[i].w[1] = t0.y; fb[i].w[2] = t1.x; fb[i].w[3] = t1.y;
       }
-    } else {
-      // 8 sub-steps of 4 pixels: lane group fg owns pixel 4*ks + fg
 #pragma unroll
-      for (int ks = 0; ks < BP / 4; ++ks) {
-        const int prow = ks * 4 + fg;
-        float fa[4], fb[4];
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          fa[i] = *reinterpret_cast<const float*>(q + prow * ROW + (wq * 64 + i * 16 + fr) * 4);
-          fb[i] = *reinterpret_cast<const float*>(pp + prow * ROW + (wp * 64 + i * 16 + fr) * 4);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
     }
     if (more) store_step((s + 1) & 1);
     __syncthreads();
@@ -206,7 +178,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// LDS-DMA version (default): operands go global -> LDS with global_load_lds_dwordx4 into a 3-stage ring (16 KiB per stage:
+// LDS-DMA version (every layer without the operand transform): operands go global -> LDS with global_load_lds_dwordx4 into a 3-stage ring (16 KiB per stage:
 // 32 pixels x 128 channels bf16, or 16 pixels fp32), counted vmcnt so that two stages stay in flight across the raw
 // s_barrier, 48 KiB of LDS -> 3 workgroups per CU.  LDS-DMA writes are lane-linear, so rows cannot be padded; the
 // transposed reads are kept conflict-free by an XOR swizzle of 32-byte chunks (64-byte chunks for fp32) applied to the
@@ -453,21 +425,19 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-static int g_wgrad_mode = 1;               // 1 = LDS-DMA 3-stage kernel, 0 = register-staged kernel
-static int g_thin_wgrad = 1;               // one-pass kernel for the two thin stem convolutions (thinconv.hip)
-static int g_wgrad384_fill = 66;           // fewest percent of a 384-wide tile row a pointwise layer's input channels must fill ("wgrad384_fill")
+constexpr int WGRAD384_FILL = 66;          // fewest percent of a 384-wide tile row a pointwise layer's input channels must fill
 static int g_wgrad384 = 1;                 // 256 x 384 pointwise kernel: 0 never, 1 planner, 2 wherever eligible (tests)
-static int g_wgrad_target_blocks = 768;    // resident capacity: 256 CUs x 3 workgroups (48 KiB LDS, 146 registers)
+constexpr int WGRAD_TARGET_BLOCKS = 768;   // resident capacity: 256 CUs x 3 workgroups (48 KiB LDS, 146 registers)
 
-// Fewest K steps (of BP pixels) a pixel split may have (tuning switch "wgrad_min_steps").  Every split costs a 64 KiB fp32 slab
+// Fewest K steps (of BP pixels) a pixel split may have.  Every split costs a 64 KiB fp32 slab
 // tile written and read back: with two steps as the floor, the 128 -> 128 layer at 384 x 576 and local batch 2 was cut into 768
 // splits of 9 steps (50 MB of slabs for a 64 KiB result).  Whole-step A/B at 2 / 8 / 16 / 32 / 64 steps: local batch 2 14.71 /
 // 14.54 / 14.43 / 14.45 / 14.86 ms, batch 4 23.26 / 23.20 / 23.08 / 23.18 / 23.32, batch 8 unchanged (40.9-41.0).
-static int g_wgrad_min_steps = 16;
+constexpr int WGRAD_MIN_STEPS = 16;
 static void plan_splits(const GatherGeom& g, long M, int BP, int* splits, int* chunk) {
   const long tiles = (long)cdiv(g.Cin, 128) * cdiv(g.Cout, 128) * g.ntaps;
-  long want = g_wgrad_target_blocks / tiles;   // FLOOR: all workgroups must be co-resident (3 per CU), a second partial wave costs more than it buys
-  const long maxs = (M + (long)g_wgrad_min_steps * BP - 1) / ((long)g_wgrad_min_steps * BP);   // at least that many steps per split
+  long want = WGRAD_TARGET_BLOCKS / tiles;   // FLOOR: all workgroups must be co-resident (3 per CU), a second partial wave costs more than it buys
+  const long maxs = (M + (long)WGRAD_MIN_STEPS * BP - 1) / ((long)WGRAD_MIN_STEPS * BP);   // at least that many steps per split
   if (want > maxs) want = maxs;
   if (want < 1) want = 1;
   if (want > 1024) want = 1024;
@@ -481,24 +451,8 @@ static void plan_splits(const GatherGeom& g, long M, int BP, int* splits, int* c
 
 using namespace dc;
 
-extern "C" int dc_wgrad_set_min_steps(int n) {
-  if (n < 1) return dc_fail("dc_set_option: wgrad_min_steps must be positive", __FILE__, __LINE__);
-  g_wgrad_min_steps = n;
-  return 0;
-}
-
-extern "C" int dc_wgrad_set_mode(int m) {
-  g_wgrad_mode = m ? 1 : 0;
-  return 0;
-}
-
-
 extern "C" int dc_wgrad_set_384(int m) {
   g_wgrad384 = m;
-  return 0;
-}
-extern "C" int dc_wgrad_set_384_fill(int pct) {
-  g_wgrad384_fill = pct;
   return 0;
 }
 extern "C" int dc_wgrad_set_384_slots(int n) {
@@ -509,11 +463,6 @@ extern "C" int dc_wgrad_set_384_slots(int n) {
 extern "C" int dc_wgrad_set_384_min_stages(int n) {
   if (n < 1) return dc_fail("dc_set_option: wgrad384_min_stages must be positive", __FILE__, __LINE__);
   wgrad384_set_min_stages(n);
-  return 0;
-}
-
-extern "C" int dc_wgrad_set_thin(int m) {
-  g_thin_wgrad = m ? 1 : 0;
   return 0;
 }
 
@@ -530,10 +479,10 @@ static bool wgrad384_wins(const GatherGeom& g) {
     // half a tile (304 -> 256: 45 quads = 7.5 tiles); the layer must fill the 256 output channels of a tile to three quarters
     return g_wgrad384 != 3 && g.Cin >= 64 && (long)cdiv(g.Cout, 256) * 256 * 3 <= (long)g.Cout * 4;
   }
-  // pointwise: the x axis in quads of 64 channels must fill its 384-wide tiles to g_wgrad384_fill percent (256 channels: 4 of 6 quads = 67 %),
+  // pointwise: the x axis in quads of 64 channels must fill its 384-wide tiles to WGRAD384_FILL percent (256 channels: 4 of 6 quads = 67 %),
   // the output channels their 256-wide tiles to three quarters
   const long nq = cdiv(g.Cin, 64), nxt = cdiv(nq, 6);
-  return nq * 100 >= nxt * 6 * g_wgrad384_fill && (long)cdiv(g.Cout, 256) * 256 * 3 <= (long)g.Cout * 4;
+  return nq * 100 >= nxt * 6 * WGRAD384_FILL && (long)cdiv(g.Cout, 256) * 256 * 3 <= (long)g.Cout * 4;
 }
 // the "big tile" plan and launch of a layer the 256 x 384 planner accepts
 static void wgrad_big_plan(const GatherGeom& g, long M, int* splits, int* chunk, int group = 1) { wgrad384_plan(g, M, splits, chunk, group); }
@@ -548,11 +497,6 @@ static int launch_wgrad_reduce(const float* slab, float* grad_w, int splits, con
   const int blocks = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, grad_w, splits, g.ntaps, g.Cout, g.Cin, transposed);
   DC_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int dc_wgrad_set_target_blocks(int n) {
-  if (n > 0) g_wgrad_target_blocks = n;
   return 0;
 }
 
@@ -582,7 +526,7 @@ static int plan_wgrad(const dc_conv_desc* d, int N, int Hi, int Wi, bool transfo
   DC_REQUIRE(M < (1L << 31) - 256, "dc_conv_wgrad: too many pixels for 32-bit indexing");
   p->N = N; p->M = (int)M;
   if (count > 1) {
-    DC_REQUIRE(!transform && d->dtype == DC_BF16 && !(g_thin_wgrad && thin_wgrad_eligible(*d, Hi, Wi)) && wgrad384_wins(p->g) &&
+    DC_REQUIRE(!transform && d->dtype == DC_BF16 && !thin_wgrad_eligible(*d, Hi, Wi) && wgrad384_wins(p->g) &&
                    count <= WG384_MAXL,
                "dc_conv_wgrad: this layer is not served by the grouped launch");
     *kind = WK_256;
@@ -590,11 +534,11 @@ static int plan_wgrad(const dc_conv_desc* d, int N, int Hi, int Wi, bool transfo
     return 0;
   }
   const int BP = d->dtype == DC_BF16 ? 64 : 32;    // chunk granularity (a multiple of both kernels' pixels per stage)
-  const bool thin = !transform && g_thin_wgrad && thin_wgrad_eligible(*d, Hi, Wi);
+  const bool thin = !transform && thin_wgrad_eligible(*d, Hi, Wi);
   const bool big = !transform && !thin && d->dtype == DC_BF16 && wgrad384_wins(p->g);
   if (thin) { p->splits = thin_wgrad_splits(*d, N, Hi, Wi); p->chunk = 0; *kind = WK_THIN; }
   else if (big) { wgrad_big_plan(p->g, M, &p->splits, &p->chunk); *kind = WK_256; }
-  else { plan_splits(p->g, M, BP, &p->splits, &p->chunk); *kind = (g_wgrad_mode == 1 && !transform) ? WK_DMA : WK_REG; }
+  else { plan_splits(p->g, M, BP, &p->splits, &p->chunk); *kind = transform ? WK_REG : WK_DMA; }
   return 0;
 }
 
@@ -615,14 +559,10 @@ static int launch_wgrad_partial(const dc_conv_desc* d, const WgradParams& p, Wgr
       DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(wgrad_dma_kernel<float>, grid, dim3(256), lds, st, p);
     }
-  } else if (d->dtype == DC_BF16) {
-    const size_t lds = 4 * (size_t)WgTraits<bf16>::BP * WgTraits<bf16>::ROW;
+  } else {      // WK_REG: the operand transform, bf16 only (conv_wgrad_impl)
+    const size_t lds = 4 * (size_t)WG_REG_BP * WG_REG_ROW;
     DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), lds, st, p);
-  } else {
-    const size_t lds = 4 * (size_t)WgTraits<float>::BP * WgTraits<float>::ROW;
-    DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), lds, st, p);
   }
   DC_CHECK_LAUNCH();
   return 0;
@@ -665,7 +605,7 @@ int conv_wgrad_bnin(const dc_conv_desc* d, int N, int Hi, int Wi, const void* y,
 // Grouped form: `count` layers of ONE geometry (same descriptor, extents and row strides) in one launch of the 256-tile
 // kernel and one reduction per layer.  Layers the 256-tile kernel does not serve fall back to `count` plain calls.
 static bool wgrad_group_eligible(const dc_conv_desc& d, const GatherGeom& g, int Hi, int Wi) {
-  return d.dtype == DC_BF16 && !(g_thin_wgrad && thin_wgrad_eligible(d, Hi, Wi)) && wgrad384_wins(g);
+  return d.dtype == DC_BF16 && !thin_wgrad_eligible(d, Hi, Wi) && wgrad384_wins(g);
 }
 
 extern "C" size_t dc_conv_wgrad_group_workspace(const dc_conv_desc* d, int N, int Hi, int Wi, int count) {

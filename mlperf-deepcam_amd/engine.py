@@ -30,6 +30,10 @@ from . import spec as S
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 S_STEM_W = "xception_features.conv1.weight"
+# pixel stride of the activation tensors with 64 and more channels, rounded up to this many elements (Act)
+ACT_ALIGN = 64
+# most pixels of a tensor whose short statistics slab the consumer of the BatchNorm coefficients sums itself (every workgroup repeats the sum)
+BN_FIN_MAX_M = 16384
 
 
 class Act:
@@ -43,9 +47,8 @@ class Act:
             # pixel stride rounded up to 64 elements: every pixel row of a bf16 tensor then starts on a 128-byte boundary (728 -> 768), so a
             # 128-byte K piece of a row is ONE L2 line for the LDS-DMA loaders of the GEMM kernels (scripts/fill_bench.hip: 15.3 TB/s from
             # line-aligned rows, 12.6 from 64-byte boundaries (736, the stride up to round 4), 10.9 from 728); the pad channels are never
-            # read or written.  DC_ACT_ALIGN=32: the previous stride
-            al = eng.act_align
-            self.ld = Cc if Cc < 64 else (Cc + al - 1) // al * al
+            # read or written
+            self.ld = Cc if Cc < 64 else (Cc + ACT_ALIGN - 1) // ACT_ALIGN * ACT_ALIGN
             self.buf = torch.empty((N, H, W, self.ld), dtype=dtype or eng.dtype, device=eng.device)
             eng.act_bytes += self.buf.numel() * self.buf.element_size()
             eng.saved[name] = self.buf
@@ -141,8 +144,6 @@ class Engine:
         self._builder = builder
         lay = self.layout
         self.act_bytes = 0
-        self.act_align = int(os.environ.get("DC_ACT_ALIGN", "64"))      # pixel stride of the activation tensors in elements (Act)
-        assert self.act_align in (32, 64, 128), "DC_ACT_ALIGN: 32, 64 or 128"
         # name -> tensor of everything forward leaves behind for backward (activations, BatchNorm coefficient vectors): lets a
         # test put two engines on ONE linearisation point (tests/test_model_gpu.py::test_backward_parity_at_shared_activations)
         self.saved: Dict[str, torch.Tensor] = {}
@@ -174,11 +175,9 @@ class Engine:
             self.grads_live = [False]
         self.packed_version = -1
         self._keep: List[torch.Tensor] = []
-        # Fusing the BatchNorm(+ReLU) into the consuming depthwise conv is implemented and tested, but measured slower at B=8
-        # (55.0 vs 53.8 ms/step: the 9-tap stencil becomes VALU-heavy), so it is off by default.
+        # BatchNorm fusions into the depthwise kernels (on by default; the frozen-BatchNorm engine below switches them off)
         self.fuse_bn_reduce = os.environ.get("DC_FUSE_BN_REDUCE", "1") != "0"   # BN backward sums taken in the consumer dw data-gradient kernel
         self.fuse_bn_into_dw = os.environ.get("DC_FUSE_BN_DW", "1") != "0"   # BN(+ReLU) applied in the consumer depthwise kernel's LDS tile
-        self.mask_from_y = os.environ.get("DC_MASK_FROM_Y", "1") != "0"
         # BatchNorm backward sums taken in the epilogue of the consuming dense conv's data gradient (dc_conv_dgrad_bnstats /
         # dc_head_bwd_bnstats) instead of a dc_bn_bwd_reduce pass over the gradient and the BatchNorm input
         # (time-neutral at local batch 8 and 4, where it saves 2.8 GB of reads per step; round 4, one job at local batch 2: 13.99 -> 13.95 ms)
@@ -195,25 +194,17 @@ class Engine:
         self.pack_side = os.environ.get("DC_PACK_SIDE", "1") != "0"       # the batch's layout pass beside the weight repack
         self._layout_forked = False
         self.aspp_side = os.environ.get("DC_ASPP_SIDE", "1") != "0"       # forward: the small ASPP branches beside the grouped atrous launch
-        # depthwise weight gradient taken inside the depthwise data gradient (dc_dwconv_dgrad_bnstats_wgrad) where the layer's input is a
-        # never-stored BatchNorm output: the separate dc_dwconv_wgrad launch (and its second read of dy and y) disappears.  On the tiled
-        # kernel the fusion held 232 registers (two workgroups per CU instead of three) and paid from local batch 8 only; on the persistent
-        # pipelined kernel (csrc/dwpipe.hip, one workgroup per CU by design) it pays everywhere: one job in round 4, local batch 2
-        # 14.36 -> 13.99 ms, batch 4 21.92 -> 21.42 ms
-        self.fuse_dw_wgrad = os.environ.get("DC_FUSE_DW_WGRAD", "1") != "0"
         # the backward sums of a block-output BatchNorm (relu(bn(y) + residual)) taken by the next block's first depthwise data gradient,
         # the last writer of that output's gradient (dc_dwconv_dgrad_wgrad_bnres) instead of a dc_bn_bwd_reduce pass over three tensors
         self.fuse_bn_res = os.environ.get("DC_FUSE_BN_RES", "1") != "0"
         self.fuse_bn_bwd_fin = os.environ.get("DC_FUSE_BN_BWD_FIN", "1") != "0"    # dc_bn_bwd_finalize inside dc_bn_bwd_apply for short slabs
         # dc_bn_finalize inside the kernel that consumes the coefficients (dc_dwconv_fwd_fin, dc_bn_apply_fin) for short slabs of small tensors
         self.fuse_bn_fwd_fin = os.environ.get("DC_FUSE_BN_FWD_FIN", "1") != "0"
-        self.bn_fin_max_m = int(os.environ.get("DC_BN_FIN_MAX_M", "16384"))          # ... up to this many pixels (each workgroup repeats the sum)
         # timing experiments only: "fwd" / "bwd" / "both" leave out the BatchNorm finalize launches (results are then garbage): what the
         # 77 + 78 tiny kernels and the dispatch gaps around them cost the chain
         self._debug_skip_finalize = os.environ.get("DC_DEBUG_SKIP_BN_FINALIZE", "")
         # BatchNorm backward apply + pointwise data gradient + pointwise weight gradient of the entry flow's thin layers in one pass (dc_pw_bn_bwd)
         self.fuse_pw_bn_bwd = os.environ.get("DC_FUSE_PW_BN_BWD", "1") != "0"
-        self.fuse_head_wgrad = os.environ.get("DC_FUSE_HEAD_WGRAD", "1") != "0"
         self.fuse_bn_src_dw = os.environ.get("DC_FUSE_BN_SRC_DW", "1") != "0"       # a stored BatchNorm output's last depthwise reader takes its backward sums
         # BatchNorm sums as ONE fp64 row per layer that the producing launch adds to (dc_conv_sum_row_kn; include/deepcam_hip.h) instead of a row
         # per workgroup: the consumer of the coefficients reads two numbers per channel and runs the finalize itself at any tensor size, so the
@@ -221,8 +212,6 @@ class Engine:
         self.bn_sum_rows = os.environ.get("DC_BN_SUM_ROWS", "1") != "0"
         self._sum_arena = None
         self._sum_used = 0
-        self.conv_kn = os.environ.get("DC_CONV_KN", "1") != "0"                    # pointwise layers pass both packed weight images (dc_conv_fwd_kn / dc_conv_dgrad_kn)
-        self.fuse_sep_fwd = os.environ.get("DC_FUSE_SEP_FWD", "1") != "0"           # depthwise + pointwise forward of the thin layers in one kernel
         # layers per grouped weight-gradient launch (dc_conv_wgrad_group).  Measured with both streams (scripts/ab_step.py): local
         # batch 2: 16.07 -> 15.42 ms/step with groups of 3, batch 4: 24.50 -> 24.11, batch 8: 40.31 -> 40.10 (round 3; 1 / 2 / 3 / 4 layers:
         # 40.31 / 40.28 / 40.10 / 40.18) -- the fp32 split slabs (256 KiB per workgroup whatever the batch) are a third of a 728-channel
@@ -240,7 +229,6 @@ class Engine:
         # static per-launch tables once the backward program is resolved.
         self._fold_seq: List[tuple] = []
         self._final_fold = None                       # (FoldEntry array, count, names): rows produced after the last dense launch
-        self.aspp_group = os.environ.get("DC_ASPP_GROUP", "1") != "0"      # atrous ASPP branches in one forward launch
         self.frozen_bn = frozen_bn
         if frozen_bn:
             # every fusion below takes batch statistics, or the backward sums of a train-mode BatchNorm, inside another kernel; their unfused
@@ -277,24 +265,16 @@ class Engine:
         # Weight gradients are off the critical path of backward (nothing downstream reads them until the optimizer) and
         # are MFMA-bound, while the chain they branch off (BN backward, depthwise data gradient) is HBM-bound: they run
         # on a side HIP stream with a private workspace and overlap it.  backward() joins the streams at the end.
-        # DC_SIDE_PRIORITY=low puts the weight gradients on a lowest-priority HIP stream (dc_stream_create); measured the same
-        # step time as a plain stream (41.3-41.6 ms): workgroups are not preempted, so priority only orders the dispatch.
-        self._side_raw = None
-        if os.environ.get("DC_SIDE_PRIORITY", "normal") == "low":
-            raw = C.c_void_p()
-            with torch.cuda.device(self.device):
-                L.call("dc_stream_create", -1, C.byref(raw))
-            self._side_raw = raw
-            self.side = torch.cuda.ExternalStream(raw.value, device=self.device)
-        else:
-            self.side = torch.cuda.Stream(device=self.device)
+        # (A lowest-priority HIP stream, dc_stream_create, measured the same step time as a plain stream, 41.3-41.6 ms: workgroups are not
+        # preempted, so priority only orders the dispatch.)
+        self.side = torch.cuda.Stream(device=self.device)
         self.workspace2 = torch.empty(max(self.ws_bytes, 256), dtype=torch.uint8, device=self.device)
         self.use_side_stream = os.environ.get("DC_SIDE_STREAM", "1") != "0"
         self.on_grad_ready: Optional[Callable[[List[str]], None]] = None
         self._debug_skip_side = os.environ.get("DC_DEBUG_SKIP_SIDE", "0") == "1"
         self._debug_skip_kind = os.environ.get("DC_DEBUG_SKIP_KIND", "")     # "_conv" / "_dw": skip that kind of weight gradient (timing only)
         self.region_marks: Optional[list] = None      # bench.py sets a list to collect (name, event) at the encoder boundaries
-        self.loss_args: Optional[dict] = None         # set per call by nn.TrainStep (DC_FUSE_HEAD_LOSS): loss inside the classifier's kernel
+        self.loss_args: Optional[dict] = None         # set per call by nn.TrainStep (bf16): loss inside the classifier's kernel
 
     # ------------------------------------------------------------------------------------------------ helpers
     def pptr(self, name: str) -> C.c_void_p:
@@ -385,7 +365,7 @@ class Engine:
         wb = torch.empty(nwb.value, dtype=tdtype, device=self.device) if need_dx else None
         # (a pointwise layer that hands the library both weight images gets the 224-pixel tiles' compact slab: one row per tile, no zero rows --
         # at local batch 4 that is 62 rows, short enough for the kernels that run the BatchNorm finalize themselves)
-        both = self.conv_kn and k == 1 and stride == 1 and not transposed and not f32 and need_dx and dt == L.DC_BF16
+        both = k == 1 and stride == 1 and not transposed and not f32 and need_dx and dt == L.DC_BF16
         rows = (lib.dc_conv_stat_rows_kn if both else lib.dc_conv_stat_rows)(C.byref(d), x.N, x.H, x.W) if stats else 0
         slab = self._f32(2 * rows * cout) if stats else None
         if (stats and both and sum_row and self.bn_sum_rows and fwd_group is None and bias is None and out is None
@@ -411,7 +391,7 @@ class Engine:
 
         # a pointwise layer hands the library BOTH packed images: the 224 x 384 tile kernel streams its weight stages from the [k][n] one
         # (csrc/igemm224.hip; dc_conv_fwd_kn / dc_conv_dgrad_kn fall back to the plain path for every shape it does not serve)
-        assert both == (self.conv_kn and k == 1 and stride == 1 and not transposed and not f32 and wb is not None and dt == L.DC_BF16)
+        assert both == (k == 1 and stride == 1 and not transposed and not f32 and wb is not None and dt == L.DC_BF16)
 
         def fwd(train: bool):
             if both:
@@ -599,15 +579,18 @@ class Engine:
             # sums (sum g, sum g*xhat) on the way out of the data-gradient kernel instead of re-reading dx and y for them
             srows = lib.dc_dwconv_dgrad_bnstats_rows(self.dt, Cc, stride, dil, N, H, W) if (lazy and self.fuse_bn_reduce and mode == 0) else 0
             wrows = 0
-            if srows == 0 and self.fuse_dw_wgrad:
+            if srows == 0:
                 # stored input (or a lazy one whose statistics are taken elsewhere): data gradient + weight-gradient rows in one kernel
                 wrows = lib.dc_dwconv_dgrad_wgrad_rows(self.dt, Cc, stride, dil, N, H, W)
             # BatchNorm sums into ONE fp64 row (the persistent kernel's workgroups add to it): the BatchNorm's apply then runs the finalize itself
             sum_ok = self.bn_sum_rows and lib.dc_dwconv_dgrad_sum_row_ok(self.dt, Cc, stride, dil, N, H, W) == 1
             stats_sum = False
             if srows > 0:
-                if self.fuse_dw_wgrad:
-                    wrows = lib.dc_dwconv_dgrad_wgrad_rows(self.dt, Cc, stride, dil, N, H, W)
+                # the depthwise weight gradient rides along as well: the separate dc_dwconv_wgrad launch (and its second read of dy and y)
+                # disappears.  On the tiled kernel this held 232 registers (two workgroups per CU instead of three) and paid from local batch 8
+                # only; on the persistent pipelined kernel (csrc/dwpipe.hip, one workgroup per CU by design) it pays everywhere: one job in
+                # round 4, local batch 2 14.36 -> 13.99 ms, batch 4 21.92 -> 21.42 ms
+                wrows = lib.dc_dwconv_dgrad_wgrad_rows(self.dt, Cc, stride, dil, N, H, W)
                 stats_sum = sum_ok and wrows > 0
                 sslab = self._sum_row(Cc) if stats_sum else self._f32(2 * srows * Cc)
                 x.fused_bwd = (sslab, -1 if stats_sum else srows)
@@ -704,7 +687,7 @@ class Engine:
         # BatchNorm.  Lazy: the depthwise layer that reads through this BatchNorm takes it (_dw sets fin["taken"])
         fin = None
         if (self.fuse_bn_fwd_fin and not self._debug_skip_finalize and
-                (rows == -1 or (rows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= self.bn_fin_max_m))):      # (a sum row: at any size)
+                (rows == -1 or (rows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M))):      # (a sum row: at any size)
             fin = {"taken": False, "args": (M, L.dptr(slab), rows, gam, bet, rm, rv, nbt, BN_MOMENTUM, BN_EPS, L.dptr(scale), L.dptr(shift),
                                             L.dptr(mean), L.dptr(invstd))}
 
@@ -736,7 +719,7 @@ class Engine:
         if lz is not None:
             lz.mean, lz.invstd, lz.fused_bwd = mean, invstd, None
             lz.fin = fin
-        elif residual is None and out is None and (self.mask_from_y or not relu):
+        elif residual is None and out is None:
             # a stored BatchNorm(+ReLU) output whose ReLU mask is recomputed from y: a sole dense-conv consumer may take this
             # BatchNorm's backward sums in its data-gradient epilogue (_conv(..., sole_consumer=True), the classifier head)
             o.bn_src = {"y": y, "scale": scale, "shift": shift, "mean": mean, "invstd": invstd, "relu": relu_i}
@@ -770,7 +753,7 @@ class Engine:
             dgam, dbet = self.gptr(bname + ".weight"), self.gptr(bname + ".bias")
             # ReLU mask: recomputed from y with the forward scale / shift whenever there is no residual (one tensor read less
             # in both backward kernels, which run at the HBM roofline); from the stored output when a residual was added
-            from_y = lazy or (relu and residual is None and self.mask_from_y)
+            from_y = lazy or (relu and residual is None)
             mrelu = (2 if relu else 0) if from_y else relu_i
             optr = (lambda: None) if from_y else (lambda: o.ptr)
             old_ = 0 if from_y else o.ld
@@ -808,9 +791,9 @@ class Engine:
             # kernel sums it itself (dc_bn_bwd_apply_fin, same bits): one launch and one dependent boundary less per BatchNorm of the middle
             # flow.  Every 32-row block repeats the sum for its channels, so it pays only while the grid is small: local batch 2 12.47 ->
             # 12.38 ms, batch 4 19.80 -> 19.83, batch 8 33.47 -> 33.88 (2 592 blocks re-reading 86 KB each).  With 64 rows per block in this form
-            # (option bn_fin_mul_bwd = 2) batch 4 gains too (19.02 -> 18.93) and batch 8 is level at best: on up to 16 384 pixels (DC_BN_FIN_MAX_M)
+            # (BN_FIN_MUL_BWD = 2 in csrc/bn.hip) batch 4 gains too (19.02 -> 18.93) and batch 8 is level at best: on up to BN_FIN_MAX_M pixels
             fin_in_apply = (self.fuse_bn_bwd_fin and apply_by is None and pwf is None
-                            and (rrows == -1 or (rrows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= self.bn_fin_max_m))      # (a sum row: at any size)
+                            and (rrows == -1 or (rrows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M))      # (a sum row: at any size)
                             and os.environ.get("DC_DEBUG_SKIP_BN_FINALIZE", "") not in ("bwd", "both"))     # (the timing switch is read later)
 
             def bwd():
@@ -842,13 +825,13 @@ class Engine:
         depthwise conv and is fused into it instead of being stored."""
         d = self._dw(x, s.prefix + ".conv1.weight", s.stride, s.dil, s.prefix + ".dw")
         # (where dc_sepconv_fwd may take the pair below, the statistics stay a row slab: that operator writes rows)
-        sep_cand = self.fuse_sep_fwd and L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, s.stride, s.dil, d.N, d.H, d.W) > 0
+        sep_cand = L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, s.stride, s.dil, d.N, d.H, d.W) > 0
         y, slab, rows = self._conv(d, s.prefix + ".pointwise.weight", s.cout, stats=bool(s.bn), name=s.prefix + ".pw",
                                    bn_fuse=bool(s.bn) and residual is None, sum_row=not sep_cand)
         # the entry flow's thin layers: depthwise + pointwise forward as ONE operator (dc_sepconv_fwd: d is written once and not read back);
         # the two forward entries the builders above appended are replaced, everything backward stays as it is
         dwf, cvf = getattr(d, "dw_fwd", None), getattr(y, "conv_fwd", None)
-        if (self.fuse_sep_fwd and dwf is not None and not dwf["fin"] and cvf is not None and cvf["plain"] and d.parent is None and
+        if (dwf is not None and not dwf["fin"] and cvf is not None and cvf["plain"] and d.parent is None and
                 L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, dwf["stride"], dwf["dil"], d.N, d.H, d.W) > 0 and
                 (slab is None or L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, 1, 1, d.N, d.H, d.W) <= rows)):
             src, wf_t = dwf["src"], cvf["wf"]
@@ -857,14 +840,14 @@ class Engine:
                 # pixels is simply longer than needed), and its finalize needs no two-stage fold of 13 824 rows that are mostly zeros
                 rows = L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, 1, 1, d.N, d.H, d.W)
 
-            def sep_fwd(train: bool):
+            def sepconv_fwd(train: bool):
                 L.call("dc_sepconv_fwd", self.dt, d.C, s.cout, d.N, d.H, d.W, src.ptr, src.ld, dwf["ps"], dwf["psh"], dwf["prelu"], dwf["taps"],
                        d.ptr, d.ld, L.dptr(wf_t), y.ptr, y.ld, L.dptr(slab) if (train and slab is not None) else None, rows if slab is not None else 0,
                        self._st())
             del self.fwd_train[-2:]
             del self.fwd_eval[-2:]
-            self.fwd_train.append(lambda: sep_fwd(True))
-            self.fwd_eval.append(lambda: sep_fwd(False))
+            self.fwd_train.append(lambda: sepconv_fwd(True))
+            self.fwd_eval.append(lambda: sepconv_fwd(False))
         if not s.bn:
             return y
         relu = s.relu_after if relu_override is None else relu_override
@@ -1015,18 +998,18 @@ class Engine:
 
         self.bwd.append(bc_bwd_make)
         # The atrous branches share ONE forward launch (dc_conv_fwd_dilated_group): each is 108 tiles of the 256-tile kernel at local
-        # batch 8 and 27 at batch 2, on 256 CUs.  (DC_ASPP_GROUP=0: one launch per branch.)
-        group = [] if self.aspp_group else None
+        # batch 8 and 27 at batch 2, on 256 CUs.
+        group = []
         pending = []
         for i, rate in enumerate(S.ASPP_RATES, start=1):
             k, pad = (1, 0) if rate == 1 else (3, rate)
             y, slab, rows = self._conv(e, f"aspp{i}.atrous_convolution.weight", 256, k=k, pad=pad, dil=rate, name=f"aspp{i}.conv",
                                        fwd_group=group if rate != 1 else None)
-            if group is not None and rate != 1:
+            if rate != 1:
                 pending.append((y, slab, rows, i))
             else:
                 self._bn(y, slab, rows, f"aspp{i}.bn", True, out=cat1.slice(f"aspp{i}", 256 * (i - 1), 256))
-            if rate == 1 and group is not None and self.aspp_side:
+            if rate == 1 and self.aspp_side:
                 # The image-pool branch (five launches on B x 2048 values), the 1 x 1 branch and the decoder's low-level projection (it reads
                 # block1's output, ready long before) are ~200 us of small kernels; the grouped atrous launch behind them is 324 tiles on
                 # 256 CUs, i.e. a second round with 188 CUs idle.  Forward only: the small branches go to the (otherwise idle) side stream
@@ -1130,7 +1113,7 @@ class Engine:
                                L.dptr(self.dlogits), self.pptr(wl), da.ptr if da is not None else None, da.ld if da is not None else 0,
                                self.gptr(wl), hptr, L.dptr(a.mean), L.dptr(a.invstd),
                                L.dptr(sslab) if sslab is not None else None, parts, self._st())
-                    if two_pass and self.fuse_head_wgrad:
+                    if two_pass:
                         # the statistics pass (dx is not stored) has dP and y of every pixel in registers: the weight gradient rides on it
                         # instead of re-reading the 906 MB BatchNorm input in a pass of its own
                         call(3)

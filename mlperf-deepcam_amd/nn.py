@@ -542,10 +542,9 @@ class TrainStep:
         self.npix = batch * height * width
         self.after_backward = None      # set by attach_reducer
         self._eng_handle = _ops.engine_handle(self.eng)
-        # loss inside the classifier's kernel (bf16 engine; DC_FUSE_HEAD_LOSS=0: the separate dc_wce_fused pass over stored logits);
+        # loss inside the classifier's kernel (bf16 engine; fp32: the separate dc_wce_fused pass over stored logits);
         # store_logits: also write the fp32 NCHW logits (nobody reads them in the fused step)
-        import os as _os
-        self.fuse_head_loss = net.act_dtype == torch.bfloat16 and _os.environ.get("DC_FUSE_HEAD_LOSS", "1") != "0"
+        self.fuse_head_loss = net.act_dtype == torch.bfloat16
         self.store_logits = False
 
     def attach_reducer(self, reducer) -> None:

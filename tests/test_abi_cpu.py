@@ -95,3 +95,24 @@ def test_option_defaults_table_is_accepted():
     from mlperf_deepcam_amd import lib as L
     assert L.load().dc_reset_options() == 0, L.last_error()
     assert L.load().dc_set_option(b"no_such_switch", 1) != 0
+
+
+# Switches whose A/B rounds are over: the default was hard-wired and the other side deleted
+RETIRED_OPTIONS = ["igemm_mode", "igemm256_phase_fast", "igemm256_rel", "pack_blocks", "pw384_k64", "igemm_zfill", "thin_fwd", "thin_wgrad",
+                   "wgrad_mode", "wgrad_target_blocks", "wgrad_min_steps", "wgrad384_fill", "pw_bn_bwd", "sep_fwd", "dw_cg", "bn_cgw", "bn_rows",
+                   "bn_fin_mul_fwd", "bn_fin_mul_bwd"]
+# Switches the tests use to force a kernel at a shape its planner would not give it, with their defaults
+KEPT_OPTIONS = {"igemm256": 1, "pw384": 1, "pw224": 1, "pw192": 1, "igemm256p": 1, "igemm256p_wgs": 0, "igemm256p_min": 257, "igemm256_splitk": 1,
+                "thin_tile": 1, "wgrad384": 1, "wgrad384_slots": 192, "wgrad384_min_stages": 96, "head_fused": 1, "head_dgrad_fused": 1,
+                "head_wgrad_fused": 1, "dw_tile": 1, "dw_wgrad_tpb": 0, "dw_pipe": 1, "bn_apply_rows": 1}
+
+
+def test_retired_options_are_refused_and_kept_ones_accepted():
+    lib = L.load()
+    try:
+        for name in RETIRED_OPTIONS:
+            assert lib.dc_set_option(name.encode(), 1) != 0, f"retired switch {name} is still accepted"
+        for name, default in KEPT_OPTIONS.items():
+            assert lib.dc_set_option(name.encode(), default) == 0, f"{name}: {L.last_error()}"
+    finally:
+        assert lib.dc_reset_options() == 0, L.last_error()
