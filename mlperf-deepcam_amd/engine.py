@@ -19,7 +19,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -34,6 +33,15 @@ S_STEM_W = "xception_features.conv1.weight"
 ACT_ALIGN = 64
 # most pixels of a tensor whose short statistics slab the consumer of the BatchNorm coefficients sums itself (every workgroup repeats the sum)
 BN_FIN_MAX_M = 16384
+# layers per grouped weight-gradient launch (dc_conv_wgrad_group).  Measured with both streams (scripts/ab_step.py): local
+# batch 2: 16.07 -> 15.42 ms/step with groups of 3, batch 4: 24.50 -> 24.11, batch 8: 40.31 -> 40.10 (round 3; 1 / 2 / 3 / 4 layers:
+# 40.31 / 40.28 / 40.10 / 40.18) -- the fp32 split slabs (256 KiB per workgroup whatever the batch) are a third of a 728-channel
+# weight gradient's time at batch 2, and a group of three writes and re-reads a third of them.
+# Round 5: the pointwise layers run on 256 x 384 tiles (csrc/wgrad384.hip), which take up to 16 layers per launch; groups of 3 / 4 / 6 / 12:
+# local batch 8 35.35 / 35.20 / 35.02 / 34.95 ms, batch 2 13.27 / - / 13.09 / 13.14, batch 4 20.51 / - / 20.40 / 20.34 (one job each,
+# profiles/r05_ab_wgrad384.txt); the 256 x 256 kernel keeps at most four.  Twelve: equal in time to six, and the 728-channel layers are cut
+# into 2 splits instead of 5 (4.7 MB of fp32 slab per layer written and read back by the fold instead of 11.8 MB)
+WGRAD_GROUP = 12
 
 
 class Act:
@@ -60,6 +68,14 @@ class Act:
         self._grad: Optional[Act] = None
         self.grad_init = False      # set while the backward program is built: has some op written the gradient yet?
         self.grad_takes = 0         # consumers that have registered their contribution to the gradient so far (execution order)
+        # hand-off between the builder of this tensor's producer and those of its consumers (None: nothing offered / taken)
+        self.bn_src: Optional[dict] = None      # _bn: a stored BatchNorm(+ReLU) output; a consumer may take its backward sums
+        self.bn_res: Optional[dict] = None      # _bn: a block output relu(bn(y) + residual); likewise
+        self.fused_bwd: Optional[tuple] = None  # set by the consumer that takes them: (slab, rows[, grad_takes at that point])
+        self.fused_bwd_cancel: Optional[Callable[[], None]] = None     # ... and how that consumer backs out (_bn.make_bwd)
+        self.pw_fuse: Optional[dict] = None     # _conv(bn_fuse=True): the BatchNorm behind this output may leave its backward to it
+        self.conv_fwd: Optional[dict] = None    # _conv / _dw: their forward launch, which _sep may replace by one fused operator
+        self.dw_fwd: Optional[dict] = None
 
     @property
     def M(self) -> int:
@@ -101,11 +117,16 @@ class LazyAct:
     """A BatchNorm(+ReLU) output that is never stored: its only consumer is a depthwise conv, which applies
     act(y*scale + shift) while loading the raw conv output y.  Only the GRADIENT w.r.t. this activation is a real buffer."""
 
-    def __init__(self, y: Act, scale: torch.Tensor, shift: torch.Tensor, relu: bool, name: str):
-        self.y, self.scale, self.shift, self.relu, self.name = y, scale, shift, relu, name
+    def __init__(self, y: Act, scale: torch.Tensor, shift: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, relu: bool,
+                 fin: Optional[dict], name: str):
+        self.y, self.scale, self.shift, self.mean, self.invstd, self.relu, self.name = y, scale, shift, mean, invstd, relu, name
         self.N, self.H, self.W, self.C = y.N, y.H, y.W, y.C
         self._grad: Optional[Act] = None
         self.grad_init = False
+        # hand-off between the BatchNorm's builder (_bn) and its consumer's (_dw, the head)
+        self.fin = fin                          # the forward finalize, if a consumer may run it itself (_bn)
+        self.fused_bwd: Optional[tuple] = None  # (slab, rows): the consumer takes the backward sums
+        self.apply_by: Optional[Callable] = None    # the consumer writes the BatchNorm input's gradient itself (the head, two passes)
 
     @property
     def M(self) -> int:
@@ -126,11 +147,12 @@ class LazyAct:
 class Engine:
     def __init__(self, batch: int, height: int, width: int, dtype=torch.bfloat16, device=None, n_input: int = 16,
                  n_classes: int = 3, seed: Optional[int] = 333, share_from: "Engine" = None, layout: "S.Layout" = None,
-                 builder: Callable[["Engine"], None] = None, frozen_bn: bool = False):
+                 builder: Callable[["Engine"], None] = None, frozen_bn: bool = False, fuse_bn_into_head: bool = True):
         """layout + builder: a sub-network as an engine of its own (tests build ONE Xception Block from the op builders below
         and run it against the reference's Block vectors); the default is the whole DeepLabV3+ network.
         frozen_bn: every BatchNorm runs in eval mode, forward AND backward -- the running statistics normalise, nothing updates them, and
-        the backward differentiates that affine map (autograd through ``net.eval()``: saliency, fine-tuning with frozen statistics)."""
+        the backward differentiates that affine map (autograd through ``net.eval()``: saliency, fine-tuning with frozen statistics).
+        fuse_bn_into_head=False: a bf16 engine stores the head's input as the fp32 one does (tests copy every activation between the two)."""
         if not torch.cuda.is_available():
             raise L.DeepcamHipError("mlperf_deepcam_amd.Engine needs a HIP device: there is no CPU path")
         L.load()
@@ -145,7 +167,7 @@ class Engine:
         lay = self.layout
         self.act_bytes = 0
         # name -> tensor of everything forward leaves behind for backward (activations, BatchNorm coefficient vectors): lets a
-        # test put two engines on ONE linearisation point (tests/test_model_gpu.py::test_backward_parity_at_shared_activations)
+        # test put two engines on ONE linearisation point (tests/test_model_gpu.py::test_backward_parity_at_shared_activations_unfused_head)
         self.saved: Dict[str, torch.Tensor] = {}
         self.saved_channels: Dict[str, int] = {}
 
@@ -175,53 +197,18 @@ class Engine:
             self.grads_live = [False]
         self.packed_version = -1
         self._keep: List[torch.Tensor] = []
-        # BatchNorm fusions into the depthwise kernels (on by default; the frozen-BatchNorm engine below switches them off)
-        self.fuse_bn_reduce = os.environ.get("DC_FUSE_BN_REDUCE", "1") != "0"   # BN backward sums taken in the consumer dw data-gradient kernel
-        self.fuse_bn_into_dw = os.environ.get("DC_FUSE_BN_DW", "1") != "0"   # BN(+ReLU) applied in the consumer depthwise kernel's LDS tile
-        # BatchNorm backward sums taken in the epilogue of the consuming dense conv's data gradient (dc_conv_dgrad_bnstats /
-        # dc_head_bwd_bnstats) instead of a dc_bn_bwd_reduce pass over the gradient and the BatchNorm input
-        # (time-neutral at local batch 8 and 4, where it saves 2.8 GB of reads per step; round 4, one job at local batch 2: 13.99 -> 13.95 ms)
-        self.fuse_bn_conv = os.environ.get("DC_FUSE_BN_CONV", "1") != "0"
-        self.fuse_bn_head = os.environ.get("DC_FUSE_BN_HEAD", "1") != "0"
+        # BatchNorm fusions: the batch statistics or backward sums of a train-mode BatchNorm taken inside a neighbouring kernel (the producing
+        # conv, a consuming depthwise / dense conv or the head), its finalize run by the kernel that consumes the coefficients, its backward
+        # apply folded into the producing pointwise conv's backward (_conv, _dw, _bn, the head).  The frozen-BatchNorm engine has none of them:
+        # its BatchNorm backward is dc_bn_bwd_frozen + dc_bn_bwd_finalize (_bn)
+        self.frozen_bn = frozen_bn
+        self.fuse_bn = not frozen_bn
         # the BatchNorm + ReLU in front of the classifier head (upsample.deconv3.1/.2) is applied by the head itself while it loads
         # (dc_head_fwd_loss_bnin / dc_head_bwd_bnin): the 256-channel 384 x 576 activation is never stored (at local batch 8: a 0.35 ms
         # dc_bn_apply pass and 1.8 GB of traffic less per step).  bf16 only (the fused head kernel).
-        self.fuse_bn_into_head = dtype == torch.bfloat16 and os.environ.get("DC_FUSE_BN_INTO_HEAD", "1") != "0"
-        # the head's data gradient (906 MB at local batch 8, read once) is not stored: the head's kernel takes the BatchNorm sums in a first
-        # pass and writes the BatchNorm input's gradient itself in a second one (dc_head_bwd_bnin_apply)
-        self.fuse_head_apply = os.environ.get("DC_FUSE_HEAD_APPLY", "1") != "0"
-        self.inline_last_wgrad = os.environ.get("DC_INLINE_LAST_WGRAD", "1") != "0"
-        self.pack_side = os.environ.get("DC_PACK_SIDE", "1") != "0"       # the batch's layout pass beside the weight repack
-        self._layout_forked = False
-        self.aspp_side = os.environ.get("DC_ASPP_SIDE", "1") != "0"       # forward: the small ASPP branches beside the grouped atrous launch
-        # the backward sums of a block-output BatchNorm (relu(bn(y) + residual)) taken by the next block's first depthwise data gradient,
-        # the last writer of that output's gradient (dc_dwconv_dgrad_wgrad_bnres) instead of a dc_bn_bwd_reduce pass over three tensors
-        self.fuse_bn_res = os.environ.get("DC_FUSE_BN_RES", "1") != "0"
-        self.fuse_bn_bwd_fin = os.environ.get("DC_FUSE_BN_BWD_FIN", "1") != "0"    # dc_bn_bwd_finalize inside dc_bn_bwd_apply for short slabs
-        # dc_bn_finalize inside the kernel that consumes the coefficients (dc_dwconv_fwd_fin, dc_bn_apply_fin) for short slabs of small tensors
-        self.fuse_bn_fwd_fin = os.environ.get("DC_FUSE_BN_FWD_FIN", "1") != "0"
-        # timing experiments only: "fwd" / "bwd" / "both" leave out the BatchNorm finalize launches (results are then garbage): what the
-        # 77 + 78 tiny kernels and the dispatch gaps around them cost the chain
-        self._debug_skip_finalize = os.environ.get("DC_DEBUG_SKIP_BN_FINALIZE", "")
-        # BatchNorm backward apply + pointwise data gradient + pointwise weight gradient of the entry flow's thin layers in one pass (dc_pw_bn_bwd)
-        self.fuse_pw_bn_bwd = os.environ.get("DC_FUSE_PW_BN_BWD", "1") != "0"
-        self.fuse_bn_src_dw = os.environ.get("DC_FUSE_BN_SRC_DW", "1") != "0"       # a stored BatchNorm output's last depthwise reader takes its backward sums
-        # BatchNorm sums as ONE fp64 row per layer that the producing launch adds to (dc_conv_sum_row_kn; include/deepcam_hip.h) instead of a row
-        # per workgroup: the consumer of the coefficients reads two numbers per channel and runs the finalize itself at any tensor size, so the
-        # 6 us finalize launch leaves the dependent chain.  The rows live in one arena that a single memset zeroes at the start of a train step.
-        self.bn_sum_rows = os.environ.get("DC_BN_SUM_ROWS", "1") != "0"
+        self.fuse_bn_into_head = fuse_bn_into_head and self.fuse_bn and dtype == torch.bfloat16
         self._sum_arena = None
         self._sum_used = 0
-        # layers per grouped weight-gradient launch (dc_conv_wgrad_group).  Measured with both streams (scripts/ab_step.py): local
-        # batch 2: 16.07 -> 15.42 ms/step with groups of 3, batch 4: 24.50 -> 24.11, batch 8: 40.31 -> 40.10 (round 3; 1 / 2 / 3 / 4 layers:
-        # 40.31 / 40.28 / 40.10 / 40.18) -- the fp32 split slabs (256 KiB per workgroup whatever the batch) are a third of a 728-channel
-        # weight gradient's time at batch 2, and a group of three writes and re-reads a third of them.
-        wg = os.environ.get("DC_WGRAD_GROUP", "auto")
-        # Round 5: the pointwise layers run on 256 x 384 tiles (csrc/wgrad384.hip), which take up to 16 layers per launch; groups of 3 / 4 / 6 / 12:
-        # local batch 8 35.35 / 35.20 / 35.02 / 34.95 ms, batch 2 13.27 / - / 13.09 / 13.14, batch 4 20.51 / - / 20.40 / 20.34 (one job each,
-        # profiles/r05_ab_wgrad384.txt); the 256 x 256 kernel keeps at most four.  Twelve: equal in time to six, and the 728-channel layers are cut
-        # into 2 splits instead of 5 (4.7 MB of fp32 slab per layer written and read back by the fold instead of 11.8 MB)
-        self.wgrad_group = 12 if wg == "auto" else max(1, min(16, int(wg)))
         self._wg_recs: List[dict] = []
         # Weight-gradient partial sums stay in per-layer slabs and are folded by dc_fold_slabs (csrc/fold.hip): one fold per dense
         # weight-gradient launch, which also takes the rows that the depthwise data-gradient kernels since the previous fold have left.
@@ -229,16 +216,11 @@ class Engine:
         # static per-launch tables once the backward program is resolved.
         self._fold_seq: List[tuple] = []
         self._final_fold = None                       # (FoldEntry array, count, names): rows produced after the last dense launch
-        self.frozen_bn = frozen_bn
-        if frozen_bn:
-            # every fusion below takes batch statistics, or the backward sums of a train-mode BatchNorm, inside another kernel; their unfused
-            # forms (the DC_FUSE_*=0 paths) serve this engine, whose BatchNorm backward is dc_bn_bwd_frozen + dc_bn_bwd_finalize (_bn).  Set on
-            # this engine only: the environment and the library's options stay as they are for every other engine
-            self.fuse_bn_reduce = self.fuse_bn_into_dw = self.fuse_bn_conv = self.fuse_bn_head = self.fuse_bn_into_head = False
-            self.fuse_head_apply = self.fuse_bn_res = self.fuse_bn_src_dw = self.fuse_pw_bn_bwd = False
-            self.fuse_bn_bwd_fin = self.fuse_bn_fwd_fin = self.bn_sum_rows = False
         self._deferred_names: List[str] = []
         self._ready_now: List[str] = []
+        self._stem_out: Optional[Act] = None          # the network stem's output (its gradient is the input of input_grad())
+        self._layout_op: Optional[Callable[[], None]] = None     # the batch's layout pass, when the stem runs on the MFMA kernels
+        self._layout_forked = False                   # _run_forward has issued it on the side stream this step
 
         # ---- program containers -----------------------------------------------------------------------------
         self.fwd_train: List[Callable[[], None]] = []
@@ -269,10 +251,8 @@ class Engine:
         # preempted, so priority only orders the dispatch.)
         self.side = torch.cuda.Stream(device=self.device)
         self.workspace2 = torch.empty(max(self.ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        self.use_side_stream = os.environ.get("DC_SIDE_STREAM", "1") != "0"
+        self.use_side_stream = True           # False: every launch on the current stream (bench.py's one-stream pass switches it at run time)
         self.on_grad_ready: Optional[Callable[[List[str]], None]] = None
-        self._debug_skip_side = os.environ.get("DC_DEBUG_SKIP_SIDE", "0") == "1"
-        self._debug_skip_kind = os.environ.get("DC_DEBUG_SKIP_KIND", "")     # "_conv" / "_dw": skip that kind of weight gradient (timing only)
         self.region_marks: Optional[list] = None      # bench.py sets a list to collect (name, event) at the encoder boundaries
         self.loss_args: Optional[dict] = None         # set per call by nn.TrainStep (bf16): loss inside the classifier's kernel
 
@@ -308,10 +288,6 @@ class Engine:
 
     def _on_side(self, fn: Callable[[C.c_void_p], None]) -> None:
         """Run fn(workspace_ptr) on the side stream, ordered after everything enqueued so far on the current stream."""
-        if self._debug_skip_side:      # timing experiments only (DC_DEBUG_SKIP_SIDE=1): the weight gradients are NOT computed
-            return
-        if self._debug_skip_kind and self._debug_skip_kind in getattr(fn, "__qualname__", ""):
-            return
         if not self.use_side_stream:
             fn(self._wsptr())
             return
@@ -327,6 +303,10 @@ class Engine:
     def _f32(self, n: int) -> torch.Tensor:
         return torch.empty(n, dtype=torch.float32, device=self.device)
 
+    # BatchNorm sums as ONE fp64 row per layer that the producing launch adds to (dc_conv_sum_row_kn; include/deepcam_hip.h) instead of a row per
+    # workgroup: the consumer of the coefficients reads two numbers per channel and runs the finalize itself at any tensor size, so the 6 us
+    # finalize launch leaves the dependent chain (662 -> 543 launches per step at local batch 8).  The rows live in one arena that a single
+    # memset zeroes at the start of a train step.
     SUM_ARENA_FLOATS = 1 << 21      # 8 MiB: a sum row is double[2][C] = 4 * C floats; the network has some 150 BatchNorms of at most 2048 channels
 
     def _sum_row(self, channels: int) -> torch.Tensor:
@@ -368,12 +348,11 @@ class Engine:
         both = k == 1 and stride == 1 and not transposed and not f32 and need_dx and dt == L.DC_BF16
         rows = (lib.dc_conv_stat_rows_kn if both else lib.dc_conv_stat_rows)(C.byref(d), x.N, x.H, x.W) if stats else 0
         slab = self._f32(2 * rows * cout) if stats else None
-        if (stats and both and sum_row and self.bn_sum_rows and fwd_group is None and bias is None and out is None
+        if (stats and both and sum_row and self.fuse_bn and fwd_group is None and bias is None and out is None
                 and lib.dc_conv_sum_row_kn(C.byref(d), x.N, x.H, x.W) == 1):
             # the 224-pixel tile kernel adds its sums to ONE fp64 row (rows = -1 from here on: _bn hands it to the consumer of the coefficients)
             rows, slab = -1, self._sum_row(cout)
-        y.pw_fuse = None
-        if (bn_fuse and self.fuse_pw_bn_bwd and k == 1 and stride == 1 and not transposed and bias is None and not f32 and need_dx
+        if (bn_fuse and self.fuse_bn and k == 1 and stride == 1 and not transposed and bias is None and not f32 and need_dx
                 and out is None and x.parent is None):
             frows = lib.dc_pw_bn_bwd_rows(dt, x.C, cout, x.M)
             if frows > 0:
@@ -437,7 +416,10 @@ class Engine:
 
             # Weight gradients of consecutive layers of ONE geometry (the 728 -> 728 pointwise convs of the middle flow) are
             # deferred and launched together (one dc_conv_wgrad_partial call): _plan_folds() fixes the roles once the program is resolved.
-            bsrc = getattr(x, "bn_src", None) if (sole_consumer and need_dx and self.fuse_bn_conv) else None
+            # a sole consumer takes its BatchNorm's backward sums in the data-gradient epilogue instead of a dc_bn_bwd_reduce pass over the
+            # gradient and the BatchNorm input (time-neutral at local batch 8 and 4, where it saves 2.8 GB of reads per step; round 4, one job
+            # at local batch 2: 13.99 -> 13.95 ms)
+            bsrc = x.bn_src if (sole_consumer and need_dx) else None
             srows = lib.dc_conv_dgrad_bnstats_rows(C.byref(d), N, H, W) if (bsrc is not None and mode == 0 and x.parent is None) else 0
             if srows > 0:
                 sslab = self._f32(2 * srows * x.C)
@@ -462,7 +444,7 @@ class Engine:
                 def side(ws):
                     L.call("dc_conv_wgrad_partial", C.byref(d), N, H, W, cnt, xs, x.ld, dys, dy.ld, slabs, splits, self._st())
                     L.call("dc_fold_slabs", ents, nent, self._st())
-                if not need_dx and self.inline_last_wgrad:
+                if not need_dx:
                     # a layer without a data gradient (the stem) ends the backward chain: nothing is left for the main stream to run beside
                     # this weight gradient, and on the side stream it would queue behind the previous layer's
                     side(self._wsptr())
@@ -503,7 +485,6 @@ class Engine:
                     for op in ops:
                         op()
             lst.append(forked)
-        self._forked = True
 
     def _dilated_group_fwd(self, members: list) -> None:
         """One launch for the forward of several "same" dilated 3x3 convolutions of one input (the atrous ASPP branches,
@@ -559,7 +540,7 @@ class Engine:
             L.call("dc_dwconv_fwd", self.dt, Cc, stride, dil, N, H, W, src.ptr, src.ld, pw, y.ptr, y.ld, ps, psh, prelu, self._st())
 
         fwd_train = fwd
-        fin = getattr(x, "fin", None) if lazy else None
+        fin = x.fin if lazy else None
         if fin is not None and not fin["taken"] and lib.dc_dwconv_fwd_fin_ok(self.dt, Cc, stride, dil, N, H, W):
             fin["taken"] = True           # this layer runs the BatchNorm's finalize itself (dc_dwconv_fwd_fin)
 
@@ -577,13 +558,13 @@ class Engine:
             dx = x.grad
             # the producer is a never-stored BatchNorm output and this is its only consumer: take that BatchNorm's backward
             # sums (sum g, sum g*xhat) on the way out of the data-gradient kernel instead of re-reading dx and y for them
-            srows = lib.dc_dwconv_dgrad_bnstats_rows(self.dt, Cc, stride, dil, N, H, W) if (lazy and self.fuse_bn_reduce and mode == 0) else 0
+            srows = lib.dc_dwconv_dgrad_bnstats_rows(self.dt, Cc, stride, dil, N, H, W) if (lazy and mode == 0) else 0
             wrows = 0
             if srows == 0:
                 # stored input (or a lazy one whose statistics are taken elsewhere): data gradient + weight-gradient rows in one kernel
                 wrows = lib.dc_dwconv_dgrad_wgrad_rows(self.dt, Cc, stride, dil, N, H, W)
             # BatchNorm sums into ONE fp64 row (the persistent kernel's workgroups add to it): the BatchNorm's apply then runs the finalize itself
-            sum_ok = self.bn_sum_rows and lib.dc_dwconv_dgrad_sum_row_ok(self.dt, Cc, stride, dil, N, H, W) == 1
+            sum_ok = lib.dc_dwconv_dgrad_sum_row_ok(self.dt, Cc, stride, dil, N, H, W) == 1
             stats_sum = False
             if srows > 0:
                 # the depthwise weight gradient rides along as well: the separate dc_dwconv_wgrad launch (and its second read of dy and y)
@@ -596,8 +577,8 @@ class Engine:
                 x.fused_bwd = (sslab, -1 if stats_sum else srows)
                 mean_p, invstd_p = L.dptr(x.mean), L.dptr(x.invstd)
             # the stored input is a block output relu(bn(y) + residual) and this data gradient completes d(x): that BatchNorm's sums ride along
-            res = getattr(x, "bn_res", None) if (not lazy and wrows > 0 and srows == 0 and self.fuse_bn_res) else None
-            if res is not None and getattr(x, "fused_bwd", 1) is None and x.parent is None and \
+            res = x.bn_res if (not lazy and wrows > 0 and srows == 0) else None
+            if res is not None and x.fused_bwd is None and x.parent is None and \
                     lib.dc_dwconv_dgrad_wgrad_bnres_rows(self.dt, Cc, stride, dil, N, H, W) == wrows:
                 rslab2 = self._sum_row(Cc) if sum_ok else self._f32(2 * wrows * Cc)
                 x.fused_bwd = (rslab2, -1 if sum_ok else wrows, x.grad_takes)       # (this layer's take_grad_mode call above was the last one so far)
@@ -608,8 +589,8 @@ class Engine:
             # the stored input is a BatchNorm(+ReLU) output whose mask is recomputed from the BatchNorm's input (bn_src) and that several layers read
             # (bn2: block 1's first depthwise layer and its shortcut conv): the depthwise layer, writing the gradient LAST, takes that BatchNorm's
             # backward sums on the way (dc_dwconv_dgrad_bnstats_wgrad_add) instead of a dc_bn_bwd_reduce pass over the 226 MB gradient and input
-            bsrc = getattr(x, "bn_src", None) if (not lazy and res is None and wrows > 0 and srows == 0 and stride == 1 and self.fuse_bn_src_dw) else None
-            if bsrc is not None and getattr(x, "fused_bwd", 1) is None and x.parent is None:
+            bsrc = x.bn_src if (not lazy and res is None and wrows > 0 and srows == 0 and stride == 1) else None
+            if bsrc is not None and x.fused_bwd is None and x.parent is None:
                 bslab2 = self._f32(2 * wrows * Cc)
                 x.fused_bwd = (bslab2, wrows, x.grad_takes)
             else:
@@ -686,8 +667,7 @@ class Engine:
         # coefficients sums it itself, every workgroup for its own channels (same bits): one launch and one dependent boundary less per
         # BatchNorm.  Lazy: the depthwise layer that reads through this BatchNorm takes it (_dw sets fin["taken"])
         fin = None
-        if (self.fuse_bn_fwd_fin and not self._debug_skip_finalize and
-                (rows == -1 or (rows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M))):      # (a sum row: at any size)
+        if self.fuse_bn and (rows == -1 or (rows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M)):      # (a sum row: at any size)
             fin = {"taken": False, "args": (M, L.dptr(slab), rows, gam, bet, rm, rv, nbt, BN_MOMENTUM, BN_EPS, L.dptr(scale), L.dptr(shift),
                                             L.dptr(mean), L.dptr(invstd))}
 
@@ -696,17 +676,8 @@ class Engine:
                 if not lazy:
                     L.call("dc_bn_apply_fin", bdt, M, Cc, M, y.ptr, y.ld, *fin["args"][1:], rptr(), rld, relu_i, o.ptr, o.ld, self._st())
                 return
-            if self._debug_skip_finalize == "async":
-                # (timing experiment with realistic data: the finalize runs unordered on a stream of its own, the chain uses the previous
-                # step's coefficients)
-                if not hasattr(self, "_dbg_stream"):
-                    self._dbg_stream = torch.cuda.Stream(device=self.device)
-                with torch.cuda.stream(self._dbg_stream):
-                    L.call("dc_bn_finalize", Cc, M, L.dptr(slab), rows, gam, bet, rm, rv, nbt, BN_MOMENTUM, BN_EPS, L.dptr(scale),
-                           L.dptr(shift), L.dptr(mean), L.dptr(invstd), self._st())
-            elif self._debug_skip_finalize not in ("fwd", "both"):
-                L.call("dc_bn_finalize", Cc, M, L.dptr(slab), rows, gam, bet, rm, rv, nbt, BN_MOMENTUM, BN_EPS, L.dptr(scale),
-                       L.dptr(shift), L.dptr(mean), L.dptr(invstd), self._st())
+            L.call("dc_bn_finalize", Cc, M, L.dptr(slab), rows, gam, bet, rm, rv, nbt, BN_MOMENTUM, BN_EPS, L.dptr(scale),
+                   L.dptr(shift), L.dptr(mean), L.dptr(invstd), self._st())
             if not lazy:
                 L.call("dc_bn_apply", bdt, M, Cc, y.ptr, y.ld, L.dptr(scale), L.dptr(shift), rptr(), rld, relu_i, o.ptr, o.ld, self._st())
 
@@ -715,20 +686,16 @@ class Engine:
             if not lazy:
                 L.call("dc_bn_apply", bdt, M, Cc, y.ptr, y.ld, L.dptr(scale), L.dptr(shift), rptr(), rld, relu_i, o.ptr, o.ld, self._st())
 
-        lz = LazyAct(y, scale, shift, relu, (name or bname) + ".lazy") if lazy else None
-        if lz is not None:
-            lz.mean, lz.invstd, lz.fused_bwd = mean, invstd, None
-            lz.fin = fin
-        elif residual is None and out is None:
-            # a stored BatchNorm(+ReLU) output whose ReLU mask is recomputed from y: a sole dense-conv consumer may take this
-            # BatchNorm's backward sums in its data-gradient epilogue (_conv(..., sole_consumer=True), the classifier head)
-            o.bn_src = {"y": y, "scale": scale, "shift": shift, "mean": mean, "invstd": invstd, "relu": relu_i}
-            o.fused_bwd = None
-        elif not lazy and residual is not None and out is None:
-            # a block output relu(bn(y) + residual): the depthwise conv that reads it first (the next block's) is the last writer of its
-            # gradient and may take this BatchNorm's backward sums on the way (_dw: dc_dwconv_dgrad_wgrad_bnres)
-            o.bn_res = {"y": y, "mean": mean, "invstd": invstd, "relu": relu_i}
-            o.fused_bwd = None
+        lz = LazyAct(y, scale, shift, mean, invstd, relu, fin, (name or bname) + ".lazy") if lazy else None
+        if self.fuse_bn and not lazy and out is None:
+            if residual is None:
+                # a stored BatchNorm(+ReLU) output whose ReLU mask is recomputed from y: a sole dense-conv consumer may take this
+                # BatchNorm's backward sums in its data-gradient epilogue (_conv(..., sole_consumer=True), the classifier head)
+                o.bn_src = {"y": y, "scale": scale, "shift": shift, "mean": mean, "invstd": invstd, "relu": relu_i}
+            else:
+                # a block output relu(bn(y) + residual): the depthwise conv that reads it first (the next block's) is the last writer of its
+                # gradient and may take this BatchNorm's backward sums on the way (_dw: dc_dwconv_dgrad_wgrad_bnres)
+                o.bn_res = {"y": y, "mean": mean, "invstd": invstd, "relu": relu_i}
 
         self.fwd_train.append(fwd_train)
         self.fwd_eval.append(fwd_eval)
@@ -736,14 +703,14 @@ class Engine:
         # the reduce pass (where no producer takes the sums on its way) adds to a sum row as well -- on tensors of 256 channels and more: same-address
         # atomics go at one per 17 ns, so the pass is cut into 256 row blocks in that form, too few workgroups for a narrow tensor to stream at rate
         # (128 channels x 1.77 M pixels: 151 -> 175 us, more than the fold and the finalize launch it saves; scripts/sum_row_contention.py)
-        bsum = self.bn_sum_rows and Cc >= 256
+        bsum = self.fuse_bn and Cc >= 256
         if bsum:
             brows, bslab = -1, self._sum_row(Cc)
         else:
             bslab = self._f32(2 * brows * Cc)
 
         def make_bwd():
-            apply_by = getattr(lz, "apply_by", None) if lazy else None      # the consumer writes dy itself (the head, two passes)
+            apply_by = lz.apply_by if lazy else None      # the consumer writes dy itself (the head, two passes)
             do = None if apply_by is not None else (lz.grad if lazy else o.grad)
             assert y.take_grad_mode() == 0, "a conv output feeds exactly one BatchNorm"
             g_out = None
@@ -760,7 +727,7 @@ class Engine:
             if self.frozen_bn:
                 # eval-mode BatchNorm: dx, the residual's gradient and the slab of (sum g, sum g*xhat) in ONE pass over the running statistics
                 # (no mean / variance of the batch to differentiate), then the parameter gradients from that slab
-                assert not lazy and getattr(y, "pw_fuse", None) is None and getattr(o, "fused_bwd", None) is None
+                assert not lazy and y.pw_fuse is None and o.fused_bwd is None
                 dyf = y.grad
 
                 def bwd_frozen():
@@ -770,21 +737,20 @@ class Engine:
                     L.call("dc_bn_bwd_finalize", Cc, L.dptr(bslab), brows, dgam, dbet, self._st())
                 return bwd_frozen, [bname + ".weight", bname + ".bias"]
             # the producing pointwise conv applies this BatchNorm's backward itself, in one pass with its own two gradients (_conv: bn_fuse)
-            pwf = getattr(y, "pw_fuse", None) if (apply_by is None and residual is None and mrelu in (0, 2)) else None
+            pwf = y.pw_fuse if (apply_by is None and residual is None and mrelu in (0, 2)) else None
             if pwf is not None:
                 pwf.update(taken=True, do=do, gam=gam, mean=mean, invstd=invstd, dgam=dgam, dbet=dbet, scale=scale, shift=shift, relu=mrelu,
                            names=[bname + ".weight", bname + ".bias"])
             dy = None if pwf is not None else y.grad
 
             # set by the consumer (a depthwise conv for a lazy output, a dense conv / the head for a stored one): its make_bwd ran first
-            fused = lz.fused_bwd if lazy else getattr(o, "fused_bwd", None)
+            fused = (lz if lazy else o).fused_bwd
             if fused is not None and len(fused) > 2 and o.grad_takes != fused[2]:
                 # the consumer that was to take the sums is not the last writer of this gradient (its sums would miss the later addends):
                 # no fusion for this BatchNorm -- the consumer runs its plain kernel, the sums come from dc_bn_bwd_reduce below
-                cancel = getattr(o, "fused_bwd_cancel", None)
-                if cancel is None:
+                if o.fused_bwd_cancel is None:
                     raise L.DeepcamHipError(f"{bname}: a consumer took this BatchNorm's backward sums but is not the last writer of the gradient")
-                cancel()
+                o.fused_bwd_cancel()
                 fused = None
             rslab, rrows = (fused[0], fused[1]) if fused is not None else (bslab, brows)
             # a short slab (the 42 rows the persistent depthwise data gradient leaves on the 728-channel layers) of a SMALL tensor: the apply
@@ -792,9 +758,8 @@ class Engine:
             # flow.  Every 32-row block repeats the sum for its channels, so it pays only while the grid is small: local batch 2 12.47 ->
             # 12.38 ms, batch 4 19.80 -> 19.83, batch 8 33.47 -> 33.88 (2 592 blocks re-reading 86 KB each).  With 64 rows per block in this form
             # (BN_FIN_MUL_BWD = 2 in csrc/bn.hip) batch 4 gains too (19.02 -> 18.93) and batch 8 is level at best: on up to BN_FIN_MAX_M pixels
-            fin_in_apply = (self.fuse_bn_bwd_fin and apply_by is None and pwf is None
-                            and (rrows == -1 or (rrows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M))      # (a sum row: at any size)
-                            and os.environ.get("DC_DEBUG_SKIP_BN_FINALIZE", "") not in ("bwd", "both"))     # (the timing switch is read later)
+            fin_in_apply = (apply_by is None and pwf is None
+                            and (rrows == -1 or (rrows <= lib.dc_bn_bwd_apply_fin_max_rows() and M <= BN_FIN_MAX_M)))      # (a sum row: at any size)
 
             def bwd():
                 if fused is None:
@@ -805,8 +770,7 @@ class Engine:
                            L.dptr(invstd), L.dptr(rslab), rrows, dgam, dbet, dy.ptr, dy.ld, g_out.ptr if g_out is not None else None,
                            g_out.ld if g_out is not None else 0, L.dptr(scale), L.dptr(shift), self._st())
                     return
-                if self._debug_skip_finalize not in ("bwd", "both"):
-                    L.call("dc_bn_bwd_finalize", Cc, L.dptr(rslab), rrows, dgam, dbet, self._st())
+                L.call("dc_bn_bwd_finalize", Cc, L.dptr(rslab), rrows, dgam, dbet, self._st())
                 if pwf is not None:
                     return
                 if apply_by is not None:
@@ -830,8 +794,8 @@ class Engine:
                                    bn_fuse=bool(s.bn) and residual is None, sum_row=not sep_cand)
         # the entry flow's thin layers: depthwise + pointwise forward as ONE operator (dc_sepconv_fwd: d is written once and not read back);
         # the two forward entries the builders above appended are replaced, everything backward stays as it is
-        dwf, cvf = getattr(d, "dw_fwd", None), getattr(y, "conv_fwd", None)
-        if (dwf is not None and not dwf["fin"] and cvf is not None and cvf["plain"] and d.parent is None and
+        dwf, cvf = d.dw_fwd, y.conv_fwd
+        if (not dwf["fin"] and cvf["plain"] and d.parent is None and
                 L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, dwf["stride"], dwf["dil"], d.N, d.H, d.W) > 0 and
                 (slab is None or L.load().dc_sepconv_fwd_rows(self.dt, d.C, s.cout, 1, 1, d.N, d.H, d.W) <= rows)):
             src, wf_t = dwf["src"], cvf["wf"]
@@ -851,7 +815,7 @@ class Engine:
         if not s.bn:
             return y
         relu = s.relu_after if relu_override is None else relu_override
-        return self._bn(y, slab, rows, s.bn, relu, residual=residual, name=s.bn + ".out", lazy=lazy and self.fuse_bn_into_dw)
+        return self._bn(y, slab, rows, s.bn, relu, residual=residual, name=s.bn + ".out", lazy=lazy and self.fuse_bn)
 
     def _xblock(self, blk: S.BlockSpec, z: Act, relu_out: Optional[bool] = None) -> Act:
         """One Xception Block (deeplab_xception.py:69-122) on an input that is already ReLU'd (the reference's in-place leading
@@ -933,7 +897,7 @@ class Engine:
                 return bwd, [w1]
 
             self.bwd.append(stem_bwd_make)
-        self._stem_out = c1          # its gradient is the input of input_grad()
+        self._stem_out = c1
         x = self._bn(c1, sslab, srows, X + "bn1", True)
         y, slab, rows = self._conv(x, X + "conv2.weight", 64, k=3, pad=1)
         x = self._bn(y, slab, rows, X + "bn2", True)
@@ -1007,33 +971,27 @@ class Engine:
                                        fwd_group=group if rate != 1 else None)
             if rate != 1:
                 pending.append((y, slab, rows, i))
-            else:
-                self._bn(y, slab, rows, f"aspp{i}.bn", True, out=cat1.slice(f"aspp{i}", 256 * (i - 1), 256))
-            if rate == 1 and self.aspp_side:
-                # The image-pool branch (five launches on B x 2048 values), the 1 x 1 branch and the decoder's low-level projection (it reads
-                # block1's output, ready long before) are ~200 us of small kernels; the grouped atrous launch behind them is 324 tiles on
-                # 256 CUs, i.e. a second round with 188 CUs idle.  Forward only: the small branches go to the (otherwise idle) side stream
-                # and run in that shadow; the projection conv joins them.
-                cat2 = Act(self, "dec_cat", B, H // 4, W // 4, 304)
-                yl, slab, rows = self._conv(low, "conv2.weight", 48, name="lowproj")
-                self._bn(yl, slab, rows, "bn2", True, out=cat2.slice("low48", 256, 48))
-                self._fork_forward(small_begin)
+                continue
+            self._bn(y, slab, rows, f"aspp{i}.bn", True, out=cat1.slice(f"aspp{i}", 256 * (i - 1), 256))
+            # The image-pool branch (five launches on B x 2048 values), the 1 x 1 branch and the decoder's low-level projection (it reads
+            # block1's output, ready long before) are ~200 us of small kernels; the grouped atrous launch behind them is 324 tiles on
+            # 256 CUs, i.e. a second round with 188 CUs idle.  Forward only: the small branches go to the (otherwise idle) side stream
+            # and run in that shadow; the projection conv joins them.
+            cat2 = Act(self, "dec_cat", B, H // 4, W // 4, 304)
+            yl, slab, rows = self._conv(low, "conv2.weight", 48, name="lowproj")
+            self._bn(yl, slab, rows, "bn2", True, out=cat2.slice("low48", 256, 48))
+            self._fork_forward(small_begin)
         if group:
             self._dilated_group_fwd(group)
             for y, slab, rows, i in pending:
                 self._bn(y, slab, rows, f"aspp{i}.bn", True, out=cat1.slice(f"aspp{i}", 256 * (i - 1), 256))
-        if getattr(self, "_forked", False):
-            join = lambda: L.call("dc_stream_fence", C.c_void_p(self.side.cuda_stream), L.stream_ptr())   # noqa: E731
-            self.fwd_train.append(join)
-            self.fwd_eval.append(join)
+        join = lambda: L.call("dc_stream_fence", C.c_void_p(self.side.cuda_stream), L.stream_ptr())   # noqa: E731
+        self.fwd_train.append(join)
+        self.fwd_eval.append(join)
         y, slab, rows = self._conv(cat1, "conv1.weight", 256, name="proj")
         p = self._bn(y, slab, rows, "bn1", True)
 
-        # ---- decoder
-        if not getattr(self, "_forked", False):
-            cat2 = Act(self, "dec_cat", B, H // 4, W // 4, 304)
-            yl, slab, rows = self._conv(low, "conv2.weight", 48, name="lowproj")
-            self._bn(yl, slab, rows, "bn2", True, out=cat2.slice("low48", 256, 48))
+        # ---- decoder (its low-level projection cat2[..., 256:] was built beside the ASPP branches above)
         U = "upsample."
         y, slab, rows = self._conv(p, U + "deconv1.0.weight", 256, transposed=True, name="deconv1", sole_consumer=True)
         a = self._bn(y, slab, rows, U + "deconv1.1", True)
@@ -1083,44 +1041,33 @@ class Engine:
 
         def head_bwd_make():
             assert a.take_grad_mode() == 0
-            bsrc = getattr(a, "bn_src", None) if self.fuse_bn_head else None
-            two_pass = lazy_in and self.fuse_bn_head and self.fuse_head_apply and self.dt == L.DC_BF16
-            da = None if two_pass else a.grad
+            srows = (a.M + 127) // 128
             if lazy_in:
-                bsrc = None
-                sslab = None
-                if self.fuse_bn_head:
-                    srows = (a.M + 127) // 128
-                    sslab = self._f32(2 * srows * 256)
-                    a.fused_bwd = (sslab, srows)
-                if two_pass:
-                    def head_apply(gam, dgam, dbet, dy):       # called by the BatchNorm's backward behind its dc_bn_bwd_finalize
-                        L.call("dc_head_bwd_bnin_apply", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
-                               gam, L.dptr(a.mean), L.dptr(a.invstd), dgam, dbet, a.M, dy.ptr, dy.ld, hptr, self._st())
-                    a.apply_by = head_apply
-            elif bsrc is not None:
-                srows = (a.M + 127) // 128
+                # the head's data gradient (906 MB at local batch 8, read once) is not stored: the head's kernel takes the BatchNorm's sums in a
+                # first pass and writes the BatchNorm input's gradient itself in a second one, behind the BatchNorm's dc_bn_bwd_finalize
+                sslab = self._f32(2 * srows * 256)
+                a.fused_bwd = (sslab, srows)
+
+                def head_apply(gam, dgam, dbet, dy):
+                    L.call("dc_head_bwd_bnin_apply", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
+                           gam, L.dptr(a.mean), L.dptr(a.invstd), dgam, dbet, a.M, dy.ptr, dy.ld, hptr, self._st())
+                a.apply_by = head_apply
+
+                def bwd_lazy():
+                    # gathered gradient image + the BatchNorm's sums (dx = NULL); this statistics pass has dP and y of every pixel in registers:
+                    # the weight gradient rides on it (parts = 3) instead of re-reading the 906 MB BatchNorm input in a pass of its own
+                    L.call("dc_head_bwd_bnin", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
+                           L.dptr(self.dlogits), self.pptr(wl), None, 0, self.gptr(wl), hptr, L.dptr(a.mean), L.dptr(a.invstd), L.dptr(sslab), 3,
+                           self._st())
+                return bwd_lazy, [wl]
+            da = a.grad
+            bsrc = a.bn_src
+            if bsrc is not None:
                 sslab = self._f32(2 * srows * 256)
                 a.fused_bwd = (sslab, srows)
                 by = bsrc["y"]
 
             def bwd():
-                if lazy_in:
-                    # gathered gradient image + data gradient (+ the BatchNorm's sums) on the chain, the weight gradient (0.35 ms at local
-                    # batch 8) behind it on the weight-gradient stream like every other one
-                    def call(parts):
-                        L.call("dc_head_bwd_bnin", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
-                               L.dptr(self.dlogits), self.pptr(wl), da.ptr if da is not None else None, da.ld if da is not None else 0,
-                               self.gptr(wl), hptr, L.dptr(a.mean), L.dptr(a.invstd),
-                               L.dptr(sslab) if sslab is not None else None, parts, self._st())
-                    if two_pass:
-                        # the statistics pass (dx is not stored) has dP and y of every pixel in registers: the weight gradient rides on it
-                        # instead of re-reading the 906 MB BatchNorm input in a pass of its own
-                        call(3)
-                        return
-                    call(1)
-                    self._on_side(lambda ws_: call(2))
-                    return
                 if bsrc is not None:
                     L.call("dc_head_bwd_bnstats", self.dt, B, 256, a.H, a.W, a.ptr, a.ld, L.dptr(self.dlogits), self.pptr(wl), da.ptr, da.ld,
                            self.gptr(wl), hptr, by.ptr, by.ld, L.dptr(bsrc["mean"]), L.dptr(bsrc["invstd"]), L.dptr(bsrc["scale"]),
@@ -1148,19 +1095,18 @@ class Engine:
     def _plan_folds(self) -> None:
         """Fixes how every dense weight gradient is launched and folded (the backward program is static, so this runs once).
         Runs of consecutive dense layers with one geometry (in backward order: the three 728 -> 728 pointwise convs of a middle-flow
-        Block) become groups of up to `wgrad_group` layers: all but the last member defer, the last one launches the group
+        Block) become groups of up to WGRAD_GROUP layers: all but the last member defer, the last one launches the group
         (dc_conv_wgrad_partial) and reports every member's gradient as ready.  Every launch is followed, on the same stream, by one
         dc_fold_slabs over its own slabs plus the rows left by the depthwise layers whose data-gradient kernels were enqueued since the
         previous fold (their names move to this op's ready list: on_grad_ready feeds the all-reduce buckets)."""
         lib = L.load()
-        G = self.wgrad_group
         recs = self._wg_recs            # make_bwd ran in backward order, so this list is in execution order
         i = 0
         while i < len(recs):
             j = i
             r0 = recs[i]
-            groupable = G > 1 and not r0["bias"] and self.dt == L.DC_BF16 and r0["key"][0] == L.DC_BF16
-            while groupable and j + 1 < len(recs) and j + 1 - i < G and recs[j + 1]["key"] == r0["key"] and not recs[j + 1]["bias"]:
+            groupable = not r0["bias"] and self.dt == L.DC_BF16 and r0["key"][0] == L.DC_BF16
+            while groupable and j + 1 < len(recs) and j + 1 - i < WGRAD_GROUP and recs[j + 1]["key"] == r0["key"] and not recs[j + 1]["bias"]:
                 j += 1
             d, x = r0["d"], r0["x"]
             splits, sbytes = C.c_int(), C.c_size_t()
@@ -1244,7 +1190,7 @@ class Engine:
         one).  One dc_stem_dgrad launch on the current stream over the stem output's gradient and the fp32 master weight.  It is not part of
         backward()'s launch list (the train step never needs it): backward() has joined the weight-gradient stream before it returns, nothing
         writes the stem output's gradient (its own buffer) until the next backward(), and no weight update may come in between."""
-        c1 = getattr(self, "_stem_out", None)
+        c1 = self._stem_out
         if c1 is None:
             raise L.DeepcamHipError("input_grad: this engine has no network stem (a custom layout)")
         shape = (self.B, self.n_input, self.H, self.W)
@@ -1260,7 +1206,7 @@ class Engine:
         if train and self.B < 2:
             raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, 256, 1, 1])")
         if self.packed_version != self.version[0]:
-            if (self.pack_side and self.use_side_stream and self.x_in is not None and getattr(self, "_layout_op", None) is not None):
+            if self.use_side_stream and self.x_in is not None and self._layout_op is not None:
                 # the layout pass of the batch (NCHW fp32 -> NHWC) does not need the weights: it runs on the side stream beside the repack
                 # (both are short memory-bound kernels that leave the other room); layout_fwd joins
                 L.call("dc_stream_fence", L.stream_ptr(), C.c_void_p(self.side.cuda_stream))

@@ -1,4 +1,4 @@
-"""Per-kernel ranking of a `rocprofv3 --kernel-trace --stats` run of scripts/run_steps.py (DC_SIDE_STREAM=0: every kernel alone):
+"""Per-kernel ranking of a `rocprofv3 --kernel-trace --stats` run of scripts/run_steps.py --one-stream (every kernel alone):
     python scripts/serial_rank.py <dir with *kernel_stats.csv> <steps incl. warm-up> [rows]"""
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One steady-state step, every kernel ALONE on the GPU (DC_SIDE_STREAM=0) beside the same kernels in the two-stream step: two tables of
+"""One steady-state step, every kernel ALONE on the GPU (run_steps.py --one-stream) beside the same kernels in the two-stream step: two tables of
 scripts/step_dump.py (collect_profiles.sh writes step_serial.tsv / step_both.tsv) reduced to one line per kernel.
 
     python scripts/serial_table.py <step_serial.tsv> <step_both.tsv>"""

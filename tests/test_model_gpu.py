@@ -52,7 +52,7 @@ def oracle_small():
 # randomly initialised network amplifies bf16's 4e-3 rounding of the activations beyond the radius in which the gradient is
 # constant.  What IS checked for bf16: the loss (north_star's quantity); backward kernel by kernel (test_kernels_gpu.py, incl. the
 # full layer shapes); the whole backward program against the fp32 engine at ONE shared linearisation point
-# (test_backward_parity_at_shared_activations); and directional derivatives where the problem is well conditioned
+# (test_backward_parity_at_shared_activations_unfused_head); and directional derivatives where the problem is well conditioned
 # (test_directional_derivatives_full_size).
 @pytest.mark.parametrize("dtype,ltol", [(torch.float32, 2e-5), (torch.bfloat16, 5e-3)], ids=["f32", "bf16"])
 def test_forward_backward_vs_oracle(oracle_small, dtype, ltol):
@@ -218,7 +218,7 @@ def test_golden_full_size_step0(golden_dir, dtype, tol):
     for k, d in ref["grad_digest"].items():
         got = float(eng.grad_view(k).double().abs().sum())
         # abs-sums: fp32 measured within 2.3e-3 of the reference, bf16 within 0.11 (profiles/r02_grad_check.txt); an all-zero or
-        # mis-scaled tensor fails either bound (a sign flip does not: see test_backward_parity_at_shared_activations for that)
+        # mis-scaled tensor fails either bound (a sign flip does not: see test_backward_parity_at_shared_activations_unfused_head for that)
         assert got == pytest.approx(d["abs"], rel=5e-3 if dtype == torch.float32 else 0.2), k
     assert torch.isfinite(eng.grads).all()
 
@@ -605,15 +605,7 @@ def _shared_point_engines(B, H, W):
     d(loss)/d(logits).  Backward is then the same LINEAR map in both, evaluated in bf16 and in fp32 arithmetic."""
     x, y = make_inputs(B, H, W)
     # (the bf16 engine stores the head's input here as the fp32 engine does, so that every activation of the point can be copied)
-    old = os.environ.get("DC_FUSE_BN_INTO_HEAD")
-    os.environ["DC_FUSE_BN_INTO_HEAD"] = "0"
-    try:
-        e16 = Engine(B, H, W, torch.bfloat16, seed=333)
-    finally:
-        if old is None:
-            del os.environ["DC_FUSE_BN_INTO_HEAD"]
-        else:
-            os.environ["DC_FUSE_BN_INTO_HEAD"] = old
+    e16 = Engine(B, H, W, torch.bfloat16, seed=333, fuse_bn_into_head=False)
     e32 = Engine(B, H, W, torch.float32, seed=333)
     for e in (e16, e32):
         e.params.copy_(e.params.to(torch.bfloat16).float())
@@ -697,7 +689,7 @@ def test_forward_activations_by_stage_bf16_vs_fp32_full_size():
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 64, 96), (2, 768, 1152)], ids=["small", "full"])
-def test_backward_parity_at_shared_activations(B, H, W):
+def test_backward_parity_at_shared_activations_unfused_head(B, H, W):
     """Model-level check of the bf16 BACKWARD kernels (data gradients, weight gradients, depthwise, BatchNorm backward, head) that
     does not suffer from the network's ill-conditioning: both engines differentiate at the same stored activations, so the only
     difference is bf16 rounding of the gradient activations along the way.  Per tensor and over the whole arena."""
