@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """DeepCAM train-step benchmark on MI355X: samples/s of forward + weighted CE + backward + gradient all-reduce + optimizer
-on synthetic 768x1152x16 batches resident in HBM, plus the MFMA-roofline fraction of the dominant kernel and a CPU
-baseline (the oracle restatement of the reference step on the node's host cores).
+on synthetic 768x1152x16 batches resident in HBM.  With --full, after the headline: the MFMA-roofline fraction of the
+dominant kernel, the other single-GPU configurations (`also`) and a CPU baseline (the oracle restatement of the reference
+step on the node's host cores).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One process per GPU; weak scaling (local batch fixed).  Rank 0 prints ONE JSON line.
@@ -303,9 +305,12 @@ def main():
     ap.add_argument("--optimizer", choices=["Adam", "AdamW", "LAMB"], default="LAMB")
     ap.add_argument("--height", type=int, default=768)
     ap.add_argument("--width", type=int, default=1152)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_also", action="store_true", help="skip the two other single-GPU configurations of BASELINE.json (local batch 2 fp32 Adam, "
-                    "local batch 4 bf16) that a default N=1 run times after the headline and attaches as `also`")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run what it does not need: the roofline passes (`roofline`), "
+                    "the other single-GPU configurations (`also`) and the CPU baseline (`cpu_baseline`).  Without it the run sets up, warms up, "
+                    "times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no_also", action="store_true", help="with --full: skip the other single-GPU configurations of BASELINE.json (local batch 2 "
+                    "fp32 Adam, local batch 4 bf16, local batch 2 bf16) that a --full run at N=1 times after the headline and attaches as `also`")
     ap.add_argument("--torch_gpu_baseline", choices=["nchw", "nchw_tuned", "nhwc", "nhwc_tuned"], default=None, help="also time the oracle's step through PyTorch's own operators on this GPU "
                     "(eager, bf16 autocast, MIOpen / rocBLAS): the reference's stack on the same hardware, reported as `torch_rocm_baseline`")
     ap.add_argument("--graph", action="store_true", help="replay the step as one captured hipGraph (default: eager launches, which "
@@ -435,97 +440,98 @@ def main():
                 "what": "exposed_wait_ms = rank 0's compute stream stalled in reducer.finish() (bucket all-reduces still running when "
                         "backward had finished), HIP events around the wait, per timed step"}
 
-    # ---- roofline of the dominant kernel family, timed per launch with HIP events on the launch stream ----------------
+    # ---- --full: roofline of the dominant kernel family, timed per launch with HIP events on the launch stream ---------
     roof = None
-    # every rank runs these extra steps (they contain the gradient collectives); only rank 0 brackets its launches with events
-    step.graphed = False                         # per-launch events need eager launches (same kernels, same streams)
-    step.programmed = False
-    nroof = min(a.steps, 3)
-    def timed_pass():
+    eng = net.engine
+    if a.full:
+        # every rank runs these extra steps (they contain the gradient collectives); only rank 0 brackets its launches with events
+        step.graphed = False                         # per-launch events need eager launches (same kernels, same streams)
+        step.programmed = False
+        nroof = min(a.steps, 3)
+        def timed_pass():
+            if rank == 0:
+                with KernelTimer(L) as kt:
+                    for _ in range(nroof):
+                        step(x, y)
+                    return kt.result()
+            for _ in range(nroof):
+                step(x, y)
+            return None
+
+        fams = timed_pass()                          # as in the timed region: weight gradients overlap on the side stream
+        barrier()
+        side = eng.use_side_stream
+        eng.use_side_stream = False                  # second pass: every kernel alone on the GPU (standalone kernel efficiency)
+        fams_alone = timed_pass()
+        # third pass, same serial mode: the Xception encoder region on its own (forward up to the ASPP, backward from the point where
+        # the gradient re-enters the encoder), ALL its kernels: convs, depthwise, BatchNorm.  north_star quotes its roofline target
+        # (40 % of the bf16 MFMA peak) on this region.
+        enc = None
         if rank == 0:
-            with KernelTimer(L) as kt:
-                for _ in range(nroof):
-                    step(x, y)
-                return kt.result()
+            eng.region_marks = []
         for _ in range(nroof):
             step(x, y)
-        return None
-
-    fams = timed_pass()                          # as in the timed region: weight gradients overlap on the side stream
-    barrier()
-    eng = net.engine
-    side = eng.use_side_stream
-    eng.use_side_stream = False                  # second pass: every kernel alone on the GPU (standalone kernel efficiency)
-    fams_alone = timed_pass()
-    # third pass, same serial mode: the Xception encoder region on its own (forward up to the ASPP, backward from the point where
-    # the gradient re-enters the encoder), ALL its kernels: convs, depthwise, BatchNorm.  north_star quotes its roofline target
-    # (40 % of the bf16 MFMA peak) on this region.
-    enc = None
-    if rank == 0:
-        eng.region_marks = []
-    for _ in range(nroof):
-        step(x, y)
-    if rank == 0:
-        torch.cuda.synchronize()
-        ev = eng.region_marks
-        eng.region_marks = None
-        per = [dict(ev[i:i + 4]) for i in range(0, len(ev) - len(ev) % 4, 4)]
-        t_fwd = sum(m["fwd_begin"].elapsed_time(m["fwd_enc_end"]) for m in per) / len(per)
-        t_bwd = sum(m["bwd_enc_begin"].elapsed_time(m["bwd_end"]) for m in per) / len(per)
-        enc = (t_fwd, t_bwd)
-    eng.use_side_stream = side
-    step.graphed = graphed
-    step.programmed = programmed
-    barrier()
-    if rank == 0:
-        peak = PEAK[a.dtype]
-        names = {"igemm": f"dc::igemm256_kernel + dc::igemm256p_kernel + dc::pw224_kernel + dc::pw384_kernel + dc::pw192_kernel + dc::igemm_kernel<{a.dtype}> (dense conv "
-                          "forward + data gradient: gather-form implicit GEMM; 256x256 (one tile per workgroup or persistent) / 224x384 / 256x384 / 128x192 "
-                          "eight-wave or 128x128 four-wave tile per layer)",
-                 "wgrad": f"dc::wgrad384_kernel + dc::wgrad_dma_kernel<{a.dtype}> + dc::fold_kernel (dense conv weight gradient: "
-                          "split-K partial sums on 256x384 tiles of the [tap][ci] axis (pointwise and stride-1 3x3 layers), 128x128 tiles (the rest), "
-                          "then the fixed-order fold of the slabs)"}
-        dom = max(fams, key=lambda f: fams[f][1])
-        def entry(f, src=None):
-            fl, secs, n, nbytes = (src or fams)[f]
-            ach = fl / secs if secs > 0 else 0.0
-            return {"kernel": names[f], "achieved": round(ach / 1e12, 2), "frac": round(ach / peak, 4), "launches_timed": n,
-                    "avg_launch_us": round(secs / max(n, 1) * 1e6, 2), "ms_per_step": round(secs / min(a.steps, 3) * 1e3, 3),
-                    "algorithmic_gflop_per_launch": round(fl / max(n, 1) / 1e9, 2), "algorithmic_bytes_per_launch": round(nbytes / max(n, 1))}
-        e = entry(dom)
-        # HBM bytes per launch come from PMC passes (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 runs of this very command) that
-        # cannot be taken from inside the process; the newest committed measurement of this configuration is attached and named.
-        traffic, traffic_source = None, None
-        try:
-            import glob
-            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
-                with open(path) as f:
-                    rec = json.load(f)
-                cfg = rec.get("config", {"local_batch": 8, "dtype": "bf16", "height": 768, "width": 1152})
-                if (cfg.get("local_batch"), cfg.get("dtype"), cfg.get("height"), cfg.get("width")) == (B, a.dtype, H, W):
-                    traffic = round(rec["kernels"][dom]["hbm_bytes_per_launch"])
-                    traffic_source = (f"profiles/{os.path.basename(path)}: committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                      "this command (FETCH doubled per the gfx950 guide); not measured inside this run")
-                    break
-        except Exception:
+        if rank == 0:
+            torch.cuda.synchronize()
+            ev = eng.region_marks
+            eng.region_marks = None
+            per = [dict(ev[i:i + 4]) for i in range(0, len(ev) - len(ev) % 4, 4)]
+            t_fwd = sum(m["fwd_begin"].elapsed_time(m["fwd_enc_end"]) for m in per) / len(per)
+            t_bwd = sum(m["bwd_enc_begin"].elapsed_time(m["bwd_end"]) for m in per) / len(per)
+            enc = (t_fwd, t_bwd)
+        eng.use_side_stream = side
+        step.graphed = graphed
+        step.programmed = programmed
+        barrier()
+        if rank == 0:
+            peak = PEAK[a.dtype]
+            names = {"igemm": f"dc::igemm256_kernel + dc::igemm256p_kernel + dc::pw224_kernel + dc::pw384_kernel + dc::pw192_kernel + dc::igemm_kernel<{a.dtype}> (dense conv "
+                              "forward + data gradient: gather-form implicit GEMM; 256x256 (one tile per workgroup or persistent) / 224x384 / 256x384 / 128x192 "
+                              "eight-wave or 128x128 four-wave tile per layer)",
+                     "wgrad": f"dc::wgrad384_kernel + dc::wgrad_dma_kernel<{a.dtype}> + dc::fold_kernel (dense conv weight gradient: "
+                              "split-K partial sums on 256x384 tiles of the [tap][ci] axis (pointwise and stride-1 3x3 layers), 128x128 tiles (the rest), "
+                              "then the fixed-order fold of the slabs)"}
+            dom = max(fams, key=lambda f: fams[f][1])
+            def entry(f, src=None):
+                fl, secs, n, nbytes = (src or fams)[f]
+                ach = fl / secs if secs > 0 else 0.0
+                return {"kernel": names[f], "achieved": round(ach / 1e12, 2), "frac": round(ach / peak, 4), "launches_timed": n,
+                        "avg_launch_us": round(secs / max(n, 1) * 1e6, 2), "ms_per_step": round(secs / min(a.steps, 3) * 1e3, 3),
+                        "algorithmic_gflop_per_launch": round(fl / max(n, 1) / 1e9, 2), "algorithmic_bytes_per_launch": round(nbytes / max(n, 1))}
+            e = entry(dom)
+            # HBM bytes per launch come from PMC passes (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 runs of this very command) that
+            # cannot be taken from inside the process; the newest committed measurement of this configuration is attached and named.
             traffic, traffic_source = None, None
-        roof = {"bound": "mfma", "achieved": e["achieved"], "peak": peak / 1e12, "unit": "TFLOP/s", "frac": e["frac"], "traffic": traffic,
-                "traffic_source": traffic_source,
-                "kernel": e["kernel"], "launches_timed": e["launches_timed"], "avg_launch_us": e["avg_launch_us"],
-                "ms_per_step": e["ms_per_step"], "algorithmic_gflop_per_launch": e["algorithmic_gflop_per_launch"],
-                "algorithmic_bytes_per_launch": e["algorithmic_bytes_per_launch"], "other_mfma_kernel": entry([f for f in fams if f != dom][0]),
-                "note": "achieved/frac are measured as in the timed region, i.e. while weight-gradient kernels run concurrently on the "
-                        "side stream; 'standalone' repeats the measurement with one kernel on the GPU at a time",
-                "standalone": {f: {k: v for k, v in entry(f, fams_alone).items() if k != "kernel"} for f in fams_alone},
-                "whole_step_frac": round(sps / world * FLOP_PER_SAMPLE * (H * W) / (768 * 1152) / peak, 4)}
-        if enc is not None:
-            enc_flop = ENCODER_FLOP_PER_SAMPLE * B * (H * W) / (768 * 1152)
-            roof["encoder_region"] = {
-                "what": "Xception encoder forward + backward, every kernel of the region (convs, depthwise, BatchNorm), one stream",
-                "fwd_ms": round(enc[0], 3), "bwd_ms": round(enc[1], 3), "gflop_per_sample": ENCODER_FLOP_PER_SAMPLE / 1e9,
-                "achieved": round(enc_flop / ((enc[0] + enc[1]) * 1e-3) / 1e12, 2), "frac": round(enc_flop / ((enc[0] + enc[1]) * 1e-3) / peak, 4)}
-    if world > 1:
-        dist.barrier()
+            try:
+                import glob
+                for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
+                    with open(path) as f:
+                        rec = json.load(f)
+                    cfg = rec.get("config", {"local_batch": 8, "dtype": "bf16", "height": 768, "width": 1152})
+                    if (cfg.get("local_batch"), cfg.get("dtype"), cfg.get("height"), cfg.get("width")) == (B, a.dtype, H, W):
+                        traffic = round(rec["kernels"][dom]["hbm_bytes_per_launch"])
+                        traffic_source = (f"profiles/{os.path.basename(path)}: committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                          "this command (FETCH doubled per the gfx950 guide); not measured inside this run")
+                        break
+            except Exception:
+                traffic, traffic_source = None, None
+            roof = {"bound": "mfma", "achieved": e["achieved"], "peak": peak / 1e12, "unit": "TFLOP/s", "frac": e["frac"], "traffic": traffic,
+                    "traffic_source": traffic_source,
+                    "kernel": e["kernel"], "launches_timed": e["launches_timed"], "avg_launch_us": e["avg_launch_us"],
+                    "ms_per_step": e["ms_per_step"], "algorithmic_gflop_per_launch": e["algorithmic_gflop_per_launch"],
+                    "algorithmic_bytes_per_launch": e["algorithmic_bytes_per_launch"], "other_mfma_kernel": entry([f for f in fams if f != dom][0]),
+                    "note": "achieved/frac are measured as in the timed region, i.e. while weight-gradient kernels run concurrently on the "
+                            "side stream; 'standalone' repeats the measurement with one kernel on the GPU at a time",
+                    "standalone": {f: {k: v for k, v in entry(f, fams_alone).items() if k != "kernel"} for f in fams_alone},
+                    "whole_step_frac": round(sps / world * FLOP_PER_SAMPLE * (H * W) / (768 * 1152) / peak, 4)}
+            if enc is not None:
+                enc_flop = ENCODER_FLOP_PER_SAMPLE * B * (H * W) / (768 * 1152)
+                roof["encoder_region"] = {
+                    "what": "Xception encoder forward + backward, every kernel of the region (convs, depthwise, BatchNorm), one stream",
+                    "fwd_ms": round(enc[0], 3), "bwd_ms": round(enc[1], 3), "gflop_per_sample": ENCODER_FLOP_PER_SAMPLE / 1e9,
+                    "achieved": round(enc_flop / ((enc[0] + enc[1]) * 1e-3) / 1e12, 2), "frac": round(enc_flop / ((enc[0] + enc[1]) * 1e-3) / peak, 4)}
+        if world > 1:
+            dist.barrier()
 
     if rank == 0:
         out = {"metric": "samples/sec (768x1152x16) train step", "value": round(sps, 3), "unit": "samples/s", "n_gpus": world,
@@ -545,7 +551,7 @@ def main():
             del step, net, opt, eng       # the engine's arenas go back to the allocator before the other configurations / baselines
             gc.collect()
             torch.cuda.empty_cache()
-        if world == 1 and not a.no_also and (B, a.dtype) == (8, "bf16"):
+        if world == 1 and a.full and not a.no_also and (B, a.dtype) == (8, "bf16"):
             # BASELINE.json configs[1] and configs[2]: the other two single-GPU configurations, timed the same way in this process
             out["also"] = []
             # ... and the per-rank shape of configs[3] (8 x MI355X, global batch 16, bf16): local batch 2 in bf16
@@ -560,7 +566,7 @@ def main():
                 out["torch_rocm_baseline"]["this_repository_over_it"] = round(sps / out["torch_rocm_baseline"]["value"], 2)
             except Exception as e:  # a baseline must never take the GPU number down with it
                 out["torch_rocm_baseline"] = {"value": None, "unit": "samples/s", "kind": "port", "sample": f"failed: {type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(H, W)
             except Exception as e:  # the baseline must never take the GPU number down with it

@@ -1,4 +1,5 @@
-"""bench.py's optional baseline leg on the GPU (the default line and the N > 1 paths are covered in test_dist_gpu.py / test_profile_gpu.py)."""
+"""bench.py on the GPU: the plain line, what --full adds, the optional baseline leg and --dump-outputs (the N > 1 paths are covered in
+test_dist_gpu.py)."""
 import json, os, subprocess, sys
 import pytest
 
@@ -21,15 +22,28 @@ def test_bench_reports_the_torch_operator_baseline_when_asked():
     assert abs(base["this_repository_over_it"] - out["value"] / base["value"]) < 0.01 * base["this_repository_over_it"] + 0.01
 
 
-def test_default_line_carries_the_other_single_gpu_configurations():
-    """BASELINE.json configs[1] (local batch 2, fp32, Adam), configs[2] (local batch 4, bf16) and the per-rank shape of configs[3] (local batch 2,
-    bf16) ride on the default line as `also`: each timed in the
+def test_plain_line_carries_the_headline_only():
+    """Without --full the run is set-up, warm-up, the K timed steps and the line: no roofline passes, no `also`, no CPU baseline."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--height", "128", "--width", "192"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["config"]["local_batch"] == 8 and out["dtype"] == "bf16" and out["value"] > 0 and out["higher_is_better"] is True
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "samples/s"
+    assert out["roofline"] is None and "also" not in out and "cpu_baseline" not in out
+
+
+def test_full_line_carries_the_other_single_gpu_configurations():
+    """With --full, BASELINE.json configs[1] (local batch 2, fp32, Adam), configs[2] (local batch 4, bf16) and the per-rank shape of configs[3]
+    (local batch 2, bf16) ride on the line as `also`: each timed in the
     same process the same way, with its whole-step and encoder-region fraction.  Small images here; the keys are what is asserted."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--height", "128", "--width", "192", "--no_cpu_baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--height", "128", "--width", "192", "--no_cpu_baseline",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["config"]["local_batch"] == 8 and out["dtype"] == "bf16" and out["value"] > 0
+    assert out["roofline"]["achieved"] > 0 and "encoder_region" in out["roofline"]
     also = out["also"]
     assert [(e["config"]["local_batch"], e["dtype"], e["config"]["optimizer"]) for e in also] == [(2, "fp32", "Adam"), (4, "bf16", "LAMB"), (2, "bf16", "LAMB")]
     for e in also:

@@ -25,12 +25,13 @@ def test_reduced_gradients_equal_sum_of_rank_gradients():
 def test_bench_two_ranks_prints_one_json_line():
     import json
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--local_batch_size", "2",
-                   "--height", "128", "--width", "192"], 29622)
+                   "--height", "128", "--width", "192", "--full"], 29622)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["global_batch"] == 4 and out["value"] > 0
+    assert out["roofline"]["achieved"] > 0          # --full: every rank runs the roofline passes (they hold the gradient collectives)
 
 
 def test_bench_four_ranks_on_one_gpu():
@@ -156,7 +157,7 @@ def test_bench_two_ranks_replayed_from_the_launch_list():
     fences and the wait in front of the optimizer, so the multi-GPU step is ONE C call per step (callback transport here: gloo on one GPU)."""
     import json
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--local_batch_size", "2", "--program",
-                   "--height", "64", "--width", "96", "--no_cpu_baseline"], 29631,
+                   "--height", "64", "--width", "96", "--no_cpu_baseline", "--full"], 29631,
                   extra_env={"DC_GRAD_COLLECTIVE": "lib", "DC_GRAD_COLLECTIVE_TRANSPORT": "callback"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
