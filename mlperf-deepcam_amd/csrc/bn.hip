@@ -420,7 +420,6 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(int C, const float
 constexpr int BN_CGW = 32;       // widest channel group of a block (16-byte vectors)
 constexpr int BN_ROWS = 32;      // rows per block at that width
 constexpr int BN_FIN_MUL_FWD = 2, BN_FIN_MUL_BWD = 2;   // rows per block of the kernels that run a finalize themselves, in units of BN_ROWS
-static int g_bn_apply_rows = 1;     // dc_bn_apply on bn_apply_rows_kernel (0: the grid-stride kernel; "bn_apply_rows")
 template <typename T, int CGW>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, int APPLY_ROWS, float inv_count, const T* __restrict__ dout,
                                                            int lddo, const T* __restrict__ y, int ldy,
@@ -561,11 +560,6 @@ static int fold_large_slab(float* slab, int rows, int C, hipStream_t st) {
 
 using namespace dc;
 
-extern "C" int dc_bn_set_option(const char* name, int value) {
-  if (strcmp(name, "bn_apply_rows") == 0) { g_bn_apply_rows = value != 0; return 0; }
-  return -1;
-}
-
 extern "C" int dc_bn_stat_rows(long M) { return cdiv(M, red_rows(M)); }
 
 extern "C" int dc_bn_stats(int dtype, long M, int C, const void* x, int ldx, float* slab, void* stream) {
@@ -628,7 +622,7 @@ static int bn_apply_impl(int dtype, long M, int C, const void* y, int ldy, const
   DC_REQUIRE(scale && shift && M > 0, "dc_bn_apply: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const int kpv = dtype == DC_BF16 ? 8 : 4;
-  if (g_bn_apply_rows) {
+  if (g_options.bn_apply_rows) {
     // bn_bwd_apply's block shape (a block as narrow as the tensor, rows per block growing with the row lanes)
     const int cgw = narrow_cg(C / kpv, BN_CGW);
     int APPLY_ROWS = (rows_per_block > 0 ? rows_per_block : BN_ROWS) * (BN_CGW / cgw);

@@ -89,6 +89,31 @@ __device__ inline double wave_sum(double v) {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The tuning switches of dc_set_option (igemm.hip): they force a kernel at a shape its planner would not give it (tests, A/B runs in one
+// process).  The member initialisers are the defaults; dc_reset_options restores them.  Host state, read by the launchers.
+struct Options {
+  int igemm256 = 1;              // 256 x 256 tiles: 0 never, 1 where the planner expects them to win, 2 whenever eligible (bf16, bf16 output)
+  int igemm256p = 1;             // persistent 256-tile kernel for multi-round launches
+  int igemm256p_wgs = 0;         // its workgroups; 0: the fewest that keep the number of rounds
+  int igemm256p_min = 257;       // fewest tiles it is used for
+  int igemm256_splitk = 1;       // split the K loop of one-round 256-tile launches (0: never; > 1: thin multi-round launches too)
+  int pw384 = 1;                 // pointwise tile kernels (igemm384.hip; the values: pw384_plan)
+  int pw224 = 1;                 // 224 x 384 tiles where the caller passes the [k][n] packing (2: whenever eligible, 3: 224 x 192 tiles)
+  int pw192 = 1;                 // 128 x 192 tiles for one-round launches of few pixels
+  int thin_tile = 1;             // flag; 0: the gather-form kernel for the stride-1 stem convolutions too
+  int wgrad384 = 1;              // 256 x 384 weight-gradient kernel: 0 never, 1 planner, 2 wherever eligible
+  int wgrad384_slots = 192;      // its split plan: workgroups to aim for ...
+  int wgrad384_min_stages = 96;  // ... and the fewest K stages per split
+  int head_fused = 1;            // flag: the bf16 head forward's products and combination in one kernel (0: GEMM + combine kernels)
+  int head_dgrad_fused = 1;      // flag; 0: the head's data gradient on the tiled GEMM kernels
+  int head_wgrad_fused = 1;      // flag: the head's weight gradient rides on the statistics pass of the two-pass backward
+  int dw_tile = 1;               // flag: LDS-tiled depthwise kernels (dwtile.hip); 0: the register-window kernels of dwconv.hip
+  int dw_wgrad_tpb = 0;          // tiles per workgroup of the depthwise weight gradient (>= 0); 0: planner
+  int dw_pipe = 1;               // 0, 1 or 2: dwpipe.hip's kernel for no depthwise layer, the data gradients, the forward pass too
+  int bn_apply_rows = 1;         // flag: dc_bn_apply on bn_apply_rows_kernel (0: the grid-stride kernel)
+};
+extern Options g_options;
+
 }  // namespace dc
 
 // One-time, thread-safe set-up at a call site (the dynamic-LDS attribute of a kernel, a symbol address): the C ABI may be called from

@@ -11,8 +11,6 @@
 
 namespace dc {
 
-static int g_dw_tile = 1;   // 1: LDS-tiled stride-1 kernels (dwtile.hip); 0: the register-window kernels below
-
 constexpr int DW_PX = 4;  // output pixels per thread (along W)
 
 // weights arrive packed as [9][C] fp32 (dc_dwconv_pack_weights): one thread's 8 (4) channels of a tap are 1-2 vector loads
@@ -441,7 +439,7 @@ static int launch_dw(const void* in, int ldin, const float* w, const void* adden
 static int launch_dw_s1(int dtype, int dil, bool flip, const void* in, int ldin, const float* wp, const void* addend, int ldadd,
                         void* out, int ldout, int N, int H, int W, int C, hipStream_t st, const float* pscale = nullptr,
                         const float* pshift = nullptr, int prelu = 0) {
-  if (g_dw_tile) return launch_dw_tile(dtype, dil, flip, in, ldin, wp, addend, ldadd, out, ldout, N, H, W, C, st, pscale, pshift, prelu, nullptr);
+  if (g_options.dw_tile) return launch_dw_tile(dtype, dil, flip, in, ldin, wp, addend, ldadd, out, ldout, N, H, W, C, st, pscale, pshift, prelu, nullptr);
   const int kpv = dtype == DC_BF16 ? 8 : 4;
   const long total = (long)N * H * ((W + DW_PX - 1) / DW_PX) * (C / kpv);
   DC_REQUIRE(total < (1L << 31), "dc_dwconv: tensor too large for the stride-1 fast path");
@@ -466,13 +464,6 @@ static int dw_check(int dtype, int C, int stride, int dil, int N, int Hi, int Wi
   return 0;
 }
 
-extern "C" int dc_dw_set_option(const char* name, int value) {
-  if (strcmp(name, "dw_tile") == 0) { g_dw_tile = value != 0; return 0; }
-  if (strcmp(name, "dw_wgrad_tpb") == 0) { dw_tile_set_tpb(value); return 0; }
-  if (strcmp(name, "dw_pipe") == 0) { dw_pipe_set(value); return 0; }
-  return -1;
-}
-
 extern "C" int dc_dwconv_pack_weights(int C, const float* master, float* packed, void* stream) {
   DC_REQUIRE(C > 0 && C % 4 == 0 && master && packed, "dc_dwconv_pack_weights: bad argument");
   DC_REQUIRE(((uintptr_t)packed & 15) == 0, "dc_dwconv_pack_weights: packed buffer must be 16-byte aligned");
@@ -492,7 +483,7 @@ extern "C" int dc_dwconv_fwd(int dtype, int C, int stride, int dil, int N, int H
   hipStream_t st = (hipStream_t)stream;
   DC_REQUIRE((pscale == nullptr) == (pshift == nullptr), "dc_dwconv_fwd: pscale and pshift go together");
   if (stride == 1 && (dil == 1 || dil == 2)) return launch_dw_s1(dtype, dil, false, x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, C, st, pscale, pshift, prelu);
-  if (stride == 2 && dil == 1 && g_dw_tile)
+  if (stride == 2 && dil == 1 && g_options.dw_tile)
     return launch_dw_tile_s2(dtype, 0, N, Hi, Wi, C, x, ldx, w, nullptr, 0, y, ldy, nullptr, nullptr, st, pscale, pshift, prelu);
   return dtype == DC_BF16 ? launch_dw<bf16, 0>(x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, Ho, Wo, C, stride, dil, st, pscale, pshift, prelu)
                           : launch_dw<float, 0>(x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, Ho, Wo, C, stride, dil, st, pscale, pshift, prelu);
@@ -502,7 +493,7 @@ extern "C" int dc_dwconv_fwd(int dtype, int C, int stride, int dil, int N, int H
 // (rows <= dc_bn_bwd_apply_fin_max_rows()), every workgroup sums it for its own channels while its halo tile travels (same order, same bits as
 // dc_bn_finalize), the workgroups of pixel tile 0 store scale / shift / save_mean / save_invstd and the running statistics.
 extern "C" int dc_dwconv_fwd_fin_ok(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  return g_dw_tile && !dw_pipe_forward() && stride == 1 && (dil == 1 || dil == 2) && (dtype == DC_BF16 || dtype == DC_F32) &&
+  return g_options.dw_tile && !dw_pipe_forward() && stride == 1 && (dil == 1 || dil == 2) && (dtype == DC_BF16 || dtype == DC_F32) &&
          C % (dtype == DC_BF16 ? 8 : 4) == 0;
 }
 extern "C" int dc_dwconv_fwd_fin(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* x, int ldx, const float* w,
@@ -532,7 +523,7 @@ extern "C" int dc_dwconv_dgrad(int dtype, int C, int stride, int dil, int N, int
   const int Ho = dw_out(Hi, stride, dil), Wo = dw_out(Wi, stride, dil);
   hipStream_t st = (hipStream_t)stream;
   if (stride == 1 && (dil == 1 || dil == 2)) return launch_dw_s1(dtype, dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, st);
-  if (stride == 2 && dil == 1 && g_dw_tile)
+  if (stride == 2 && dil == 1 && g_options.dw_tile)
     return launch_dw_tile_s2(dtype, 1, N, Hi, Wi, C, dy, lddy, w, addend, ldadd, dx, lddx, nullptr, nullptr, st);
   // gather from dy [Ho,Wo] into dx [Hi,Wi]
   return dtype == DC_BF16 ? launch_dw<bf16, 1>(dy, lddy, w, addend, ldadd, dx, lddx, N, Ho, Wo, Hi, Wi, C, stride, dil, st)
@@ -540,7 +531,7 @@ extern "C" int dc_dwconv_dgrad(int dtype, int C, int stride, int dil, int N, int
 }
 
 extern "C" int dc_dwconv_dgrad_bnstats_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_dw_tile || (dtype != DC_BF16 && dtype != DC_F32) || C <= 0 || N <= 0) return 0;
+  if (!g_options.dw_tile || (dtype != DC_BF16 && dtype != DC_F32) || C <= 0 || N <= 0) return 0;
   if (stride == 1 && (dil == 1 || dil == 2)) {
     const int pr = dw_pipe_rows(dtype, C, dil, N, Hi, Wi);    // persistent kernel (dwpipe.hip): one slab row per workgroup
     return pr > 0 ? pr : dw_tile_rows(dtype, C, N, Hi, Wi);
@@ -573,7 +564,7 @@ extern "C" int dc_dwconv_dgrad_bnstats(int dtype, int C, int stride, int dil, in
 // layer's forward input is act(ybn*mscale + mshift) (the never-stored BatchNorm output), so nothing is read that the data gradient
 // with statistics does not read already.
 extern "C" int dc_dwconv_dgrad_wgrad_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_dw_tile) return 0;
+  if (!g_options.dw_tile) return 0;
   if (stride == 2 && dil == 1) {          // the stride-2 data-gradient kernel walks its tiles: one row per workgroup
     const int rows = dc_dwconv_dgrad_bnstats_rows(dtype, C, stride, dil, N, Hi, Wi);
     return rows > 0 && rows <= DWT_MAX_ROWS ? rows : 0;
@@ -589,7 +580,7 @@ extern "C" int dc_dwconv_dgrad_wgrad_rows(int dtype, int C, int stride, int dil,
 // 1: the data gradients that take BatchNorm sums (dc_dwconv_dgrad_bnstats_wgrad_sum, dc_dwconv_dgrad_wgrad_bnres_sum) serve this shape: the
 // persistent pipelined kernel (dwpipe.hip), whose workgroups add their sums to ONE fp64 row (bn_fin.h: SUM_ROW)
 extern "C" int dc_dwconv_dgrad_sum_row_ok(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_dw_tile || stride != 1 || (dil != 1 && dil != 2) || C <= 0 || N <= 0 || (long)N * Hi * Wi >= (1L << 31)) return 0;
+  if (!g_options.dw_tile || stride != 1 || (dil != 1 && dil != 2) || C <= 0 || N <= 0 || (long)N * Hi * Wi >= (1L << 31)) return 0;
   return dw_pipe_rows(dtype, C, dil, N, Hi, Wi) > 0 && dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0 ? 1 : 0;
 }
 
@@ -677,7 +668,7 @@ extern "C" int dc_dwconv_dgrad_wgrad(int dtype, int C, int stride, int dil, int 
 // takes that BatchNorm's backward sums (g = dx masked by x > 0 when relu; slab[2][rows][C]), so dc_bn_bwd_reduce's pass over dx, ybn and x
 // disappears.  Served by the persistent kernel only (rows = 0: use dc_dwconv_dgrad_wgrad + dc_bn_bwd_reduce).
 extern "C" int dc_dwconv_dgrad_wgrad_bnres_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (stride != 1 || dil != 1 || !g_dw_tile) return 0;
+  if (stride != 1 || dil != 1 || !g_options.dw_tile) return 0;
   return dw_pipe_rows(dtype, C, dil, N, Hi, Wi);
 }
 
@@ -756,9 +747,9 @@ extern "C" int dc_dwconv_wgrad(int dtype, int C, int stride, int dil, int N, int
   hipStream_t st = (hipStream_t)stream;
   const int kpv = dtype == DC_BF16 ? 8 : 4;
   const int cgw = dw_pick_cgw(C / kpv);
-  if (stride == 1 && (dil == 1 || dil == 2) && g_dw_tile)
+  if (stride == 1 && (dil == 1 || dil == 2) && g_options.dw_tile)
     return launch_dw_tile_wgrad(dtype, dil, x, ldx, dy, lddy, (float*)workspace, grad_w, N, Hi, Wi, C, st, pscale, pshift, prelu);
-  if (stride == 2 && dil == 1 && g_dw_tile) {
+  if (stride == 2 && dil == 1 && g_options.dw_tile) {
     int trows = 0;
     if (int e = launch_dw_tile_s2(dtype, 2, N, Hi, Wi, C, x, ldx, nullptr, dy, lddy, nullptr, 0, (float*)workspace, &trows, st, pscale, pshift, prelu)) return e;
     return dw_tile_reduce((const float*)workspace, grad_w, trows, C, st);

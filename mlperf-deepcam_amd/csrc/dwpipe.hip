@@ -80,9 +80,6 @@ struct DwpArgs {
   int sum_row, sum_row2; // the BatchNorm sums (st.slab / slab2) go to a SUM ROW, double[2][C] (bn_fin.h), by fp64 atomics instead of a row per workgroup
 };
 
-#ifdef DWP_STAMPS
-static __device__ unsigned long long dwp_stamp_buf[256 * 8 * 4];
-#endif
 typedef __attribute__((address_space(1))) const void* gas_ptr;
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -235,15 +232,6 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(xsc[e]), "+v"(xsh[e]));
   }
-
-
-
-#ifdef DWP_STAMPS
-  unsigned long long tw = 0, ti = 0, tx_ = 0, tc = 0, tprev = __builtin_amdgcn_s_memtime();
-#define STAMP(acc) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - tprev; tprev = now_; } while (0)
-#else
-#define STAMP(acc) do {} while (0)
-#endif
   auto decode = [&](int t, int& n, int& y0, int& x0) {
     const int tx = t % a.ntx;
     const int r = t / a.ntx;
@@ -385,17 +373,13 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
         else if (i == 1) wait_vm<S::STORES + (NS - 2) * (S::DMAS - 1)>();
         else wait_vm<2 * S::STORES + (NS - 2) * (S::DMAS - 1)>();
       }
-      STAMP(tx_);                       // (stamp builds, non-XFORM modes: the vmcnt wait alone goes to the "transform" column)
       __builtin_amdgcn_s_barrier();     // everybody's pieces of tile i have landed; everybody is done with the stage tile i-1 used
-      STAMP(tw);
       {
         int ns = stage + NS - 1;
         if (ns >= NS) ns -= NS;
         issue(t0 + i + NS - 1, ns);     // into the stage tile i-1 has just left
       }
-      STAMP(ti);
       compute_tile(t0 + i, stage);
-      STAMP(tc);
       if (++stage == NS) stage = 0;
     }
   } else {
@@ -420,30 +404,20 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this thread's transform stores of tile i
       __builtin_amdgcn_s_barrier();     // tile i is transformed, tile i+1 has landed, everybody is done with the stage tile i-1 used
-      STAMP(tw);
       {
         int ns = stage + NS - 1;
         if (ns >= NS) ns -= NS;
         issue(t0 + i + NS - 1, ns);
       }
-      STAMP(ti);
       if (i + 1 < nt) {
         int s1 = stage + 1;
         if (s1 == NS) s1 = 0;
         xform_tile(t0 + i + 1, s1);
       }
-      STAMP(tx_);
       compute_tile(t0 + i, stage);
-      STAMP(tc);
       if (++stage == NS) stage = 0;
     }
   }
-#ifdef DWP_STAMPS
-  if ((tid & 63) == 0 && blockIdx.x < 256) {
-    unsigned long long* o = dwp_stamp_buf + ((size_t)blockIdx.x * 8 + wv) * 4;
-    o[0] = tw; o[1] = ti; o[2] = tx_; o[3] = tc;
-  }
-#endif
   // the ring drains (dummy requests past the last tile included) before its memory becomes the fold's scratch
   wait_vm<0>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -512,8 +486,6 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
   }
 }
 
-int g_dw_pipe = 1;   // tuning switch "dw_pipe": 0 = dwtile.hip's kernels everywhere, 1 = data gradients here, 2 = the forward pass too
-
 template <int DIL, int MODE>
 int launch1(const DwpArgs& a, int grid, hipStream_t st) {
   constexpr int LDS = PStage<DIL, MODE>::NS * PStage<DIL, MODE>::BYTES;
@@ -527,21 +499,13 @@ int launch1(const DwpArgs& a, int grid, hipStream_t st) {
 
 }  // namespace
 
-void dw_pipe_set(int v) { g_dw_pipe = v < 0 ? 0 : v > 2 ? 2 : v; }
-bool dw_pipe_forward() { return g_dw_pipe == 2; }
-
-#ifdef DWP_STAMPS
-// diagnostic builds only (make dwstamps; scripts/dw_stamps.py): the phase cycle sums the last launch left, [256 workgroups][8 waves][4]
-extern "C" int dc_debug_dwp_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dwp_stamp_buf), sizeof(unsigned long long) * 256 * 8 * 4);
-}
-#endif
+bool dw_pipe_forward() { return g_options.dw_pipe == 2; }
 
 // workgroups per channel block (= slab rows of the sums that ride along), 0: the shape is not served
 int dw_pipe_rows(int dtype, int C, int dil, int N, int H, int W) {
   // (64 channels -- block 1's first depthwise layer, 226 MB of gradient at local batch 8 -- fill half of a 128-channel block: the idle lanes
   // cost nothing beside one pass over dy that also takes the BatchNorm sums and the weight gradient)
-  if (!g_dw_pipe || dtype != DC_BF16 || C < P_CH / 2 || (C & 7) || (H % P_TH) || (W % P_TW) || (dil != 1 && dil != 2)) return 0;
+  if (!g_options.dw_pipe || dtype != DC_BF16 || C < P_CH / 2 || (C & 7) || (H % P_TH) || (W % P_TW) || (dil != 1 && dil != 2)) return 0;
   if ((long)H * W * ((C + 63) / 64 * 64 + 64) * 2 >= (1L << 30)) return 0;      // an image per buffer resource: offsets and marker below 2 GiB
   const int ncb = cdiv(C / 8, P_CG);
   const long ptiles = (long)N * (H / P_TH) * (W / P_TW);

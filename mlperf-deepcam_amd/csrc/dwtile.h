@@ -28,7 +28,6 @@ int dw_tile_rows(int dtype, int C, int N, int H, int W);   // pixel tiles of the
 int launch_dw_tile_wgrad(int dtype, int dil, const void* x, int ldx, const void* dy, int lddy, float* slab, float* grad_w, int N,
                          int H, int W, int C, hipStream_t st, const float* pscale = nullptr, const float* pshift = nullptr, int prelu = 0);
 size_t dw_tile_wgrad_workspace(int C, int N, int H, int W);
-void dw_tile_set_tpb(int v);
 int dw_tile_reduce(const float* slab, float* grad_w, int rows, int C, hipStream_t st);   // grad[c][t] = sum of slab rows (fp64, fixed order)
 
 // persistent pipelined kernel (dwpipe.hip): bf16, >= 128 channels, image extents multiples of 8.  dw_pipe_rows: workgroups per channel
@@ -37,7 +36,6 @@ int dw_pipe_rows(int dtype, int C, int dil, int N, int H, int W);
 int launch_dw_pipe(int dil, bool flip, const void* in, int ldin, const float* wp, const void* addend, int ldadd, void* out, int ldout, int N,
                    int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu, const DwBnStats* bnstats,
                    const DwResStats* res = nullptr);
-void dw_pipe_set(int v);
 bool dw_pipe_forward();
 
 // stride-2 kernels (dwtile_s2.hip).  mode 0 forward, 1 data gradient (p1 = addend or null), 2 weight-gradient rows into the slab

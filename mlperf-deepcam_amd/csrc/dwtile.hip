@@ -19,13 +19,7 @@
 
 namespace dc {
 
-#ifndef DT_TH_VALUE
-#define DT_TH_VALUE 8
-#endif
-constexpr int DT_TH = DT_TH_VALUE;   // tile rows
-#ifndef DT_PROBE_KY
-#define DT_PROBE_KY 3                // diagnostic builds only: stencil rows the forward / data-gradient loop executes (arithmetic share)
-#endif
+constexpr int DT_TH = 8;   // tile rows
 
 template <int DIL, int CG>
 struct TileCfg {
@@ -227,7 +221,7 @@ __global__ __launch_bounds__(256) void dwt_kernel(const T* __restrict__ in, int 
       }
     }
 #pragma unroll
-    for (int ky = 0; ky < DT_PROBE_KY; ++ky) {
+    for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
       for (int c = 0; c < WC; ++c) {
         float f[KH];
@@ -440,9 +434,6 @@ int dw_tile_reduce(const float* slab, float* grad_w, int rows, int C, hipStream_
   return 0;
 }
 
-static int g_dw_tpb = 0;   // tiles per workgroup of the weight gradient; 0 = planner
-void dw_tile_set_tpb(int v) { g_dw_tpb = v < 0 ? 0 : v; }
-
 static int pick_cg(int ngroups) { return ngroups <= 8 ? 8 : ngroups <= 16 ? 16 : 32; }   // channel-group width of a workgroup
 
 struct TileGrid {
@@ -460,7 +451,7 @@ static TileGrid tile_grid(int ngroups, int N, int H, int W) {
 }
 
 static int wgrad_tpb(const TileGrid& t) {
-  if (g_dw_tpb > 0) return g_dw_tpb;
+  if (g_options.dw_wgrad_tpb > 0) return g_options.dw_wgrad_tpb;
   // about 512 workgroups (2 per CU) of about 3 tiles each measured best on the 728-, 256- and 128-channel layers: fewer,
   // longer workgroups amortise the fold and keep the slab (written once, read once by the reduction) small
   long tpb = ((long)t.ntiles * t.ncgb + 256) / 512;

@@ -6,12 +6,10 @@ namespace dc {
 
 // K stride (elements) of a packed weight row: rows of 64 and more elements start on a 128-byte boundary (728 -> 768), so that a 128-byte K piece of a
 // row is ONE L2 line (scripts/fill_bench.hip: the LDS-DMA fill of a tile reads 15.3 TB/s from line-aligned rows, 12.6 from rows on 64-byte
-// boundaries, 10.9 from rows on 16-byte boundaries); shorter rows keep 64-byte boundaries.  The pad is never read.  DC_WLD_ALIGN=32: the stride up to round 4.
-#ifndef DC_WLD_ALIGN
-#define DC_WLD_ALIGN 64
-#endif
+// boundaries, 10.9 from rows on 16-byte boundaries); shorter rows keep 64-byte boundaries.  The pad is never read.
+constexpr int WLD_ALIGN = 64;   // elements
 __host__ __device__ inline int weight_ld(int c) {
-  const int a = c < 64 ? 32 : DC_WLD_ALIGN;
+  const int a = c < 64 ? 32 : WLD_ALIGN;
   return (c + a - 1) / a * a;
 }
 
@@ -80,7 +78,6 @@ inline long igemm256_tiles(const IgemmParams& p) {
 // split-K plan of a 256-tile launch: splits (1 = none) and the bytes of the partial-sum slab; launch + fold of a planned launch
 int igemm256_splitk_plan(const IgemmParams& p, size_t* slab_bytes);
 int launch_igemm256_splitk(const IgemmParams& p, int splits, void* ws, hipStream_t st);
-void igemm256_set_splitk(int v);
 
 // igemm384.hip: pointwise layers on a (32*npb) x 384 tile, one wave per SIMD (npb = 8 or 4 pixel blocks per wave)
 bool pw384_eligible(const IgemmParams& p);
@@ -98,7 +95,6 @@ int launch_pw192(const IgemmParams& p, hipStream_t st);
 
 // thinconv.hip: the thin 3x3 stem convolutions (forward and data gradient) without LDS staging of the pixel operand
 bool thin_fwd_eligible(const GatherGeom& g, int dtype, int bias, int accumulate, int out32);
-void thin_set_tile(int v);
 int launch_thin_fwd(const GatherGeom& g, int N, const void* in, int ldin, const void* w, int ldw, void* out, int ldout, float* slab,
                     int slab_rows, hipStream_t st);
 

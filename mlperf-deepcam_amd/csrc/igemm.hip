@@ -9,6 +9,7 @@
 //   epilogue  accumulators -> LDS C tile -> fully coalesced 16-B NHWC stores; optional bias, optional
 //             read-modify-write accumulate, optional per-channel sum / sum-of-squares partials of the STORED
 //             values for the following train-mode BatchNorm (deterministic slab, no atomics)
+#include <stdio.h>
 #include <string.h>
 
 #include <type_traits>
@@ -45,19 +46,6 @@ struct Mma<float> {
   }
 };
 
-// Diagnostic build only (-DDC_STAMPS, scripts/igemm_stamps.py): per-workgroup s_memtime stamps at the phase boundaries of the
-// kernel, written to a buffer no other code reads.  The product build contains none of this.
-#ifdef DC_STAMPS
-__device__ unsigned long long* dc_stamp_buf = nullptr;
-#define DC_STAMP(k)                                                                                   \
-  do {                                                                                                \
-    if (threadIdx.x == 0 && dc_stamp_buf != nullptr)                                                  \
-      dc_stamp_buf[(size_t)blockIdx.x * 8 + (k)] = ((k) == 0 || (k) == 7) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define DC_STAMP(k)
-#endif
-
 __device__ inline int swz(int row, int slot) { return row * ROWB + ((slot ^ ((row >> 1) & 3)) << 4); }   // 4 slots per row
 
 // 16 zero bytes in global memory: the source of every predicated-off LDS-DMA lane (zero fill of halos, K and M tails)
@@ -88,8 +76,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
 
   const GatherGeom& g = p.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  DC_STAMP(0);
-  DC_STAMP(1);
   // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with a private L2), so the ones that
   // share an XCD (equal id mod 8) are given CONSECUTIVE tiles, and consecutive tiles walk the output-channel tiles of one
   // pixel tile first: the 128-pixel A panel is then fetched into that XCD's L2 once instead of once per channel tile.
@@ -218,7 +204,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   };
   int tapi = 0, kc = 0;
-  DC_STAMP(2);
   // NSTAGE-stage ring, counted waits.  Each issue() is 2*LPASS = 4 LDS-DMA instructions per wave, retired in order.
   // Iteration s: wait until stage s has landed (leave the younger stage in flight), barrier (everybody's stage s is
   // visible AND everybody has finished reading the buffer of stage s-1, which is the one stage s+2 will overwrite),
@@ -237,9 +222,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifdef DC_STAMPS
-    if (s == 0) DC_STAMP(3);
-#endif
     if (s + NSTAGE - 1 < steps) issue(tapi, kc, (s + NSTAGE - 1) % NSTAGE);
     next_step(tapi, kc);
     compute(s % NSTAGE);
@@ -248,7 +230,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   __builtin_amdgcn_s_barrier();   // all waves done with the operand ring before the epilogue reuses it as the C tile
 
   // ---- epilogue ------------------------------------------------------------------------------------
-  DC_STAMP(4);
   char* ct = smem;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -276,7 +257,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     }
   }
   __syncthreads();
-  DC_STAMP(5);
 
   constexpr int GPR = BN * (int)sizeof(TO) / 16;  // 16-byte groups per C row: 16 (bf16) / 32 (f32)
   constexpr int RPP = 256 / GPR;                  // rows covered per pass: 16 / 8
@@ -385,8 +365,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
       p.slab[((size_t)which * rows + srow) * g.Cout + n0 + c] = a;
     }
   }
-  DC_STAMP(6);
-  DC_STAMP(7);
 }
 
 // Pointwise convolution on at most 16 pixels (the image-pool branch: 2048 -> 256 on the 1x1 pooled map, M = batch).  The tiled
@@ -442,8 +420,6 @@ __global__ __launch_bounds__(256) void tiny_gemm_kernel(const IgemmParams p) {
   }
 }
 
-static int g_igemm256 = 1;   // 0: never, 1: where the planner expects it to win, 2: whenever eligible (bf16, bf16 output)
-
 template <typename T, bool OUT32>
 static int launch_igemm(const IgemmParams& p, hipStream_t st) {
   constexpr int CROW = BN * (int)(OUT32 ? 4 : sizeof(T)) + 16;
@@ -461,24 +437,18 @@ static int launch_igemm(const IgemmParams& p, hipStream_t st) {
 // (>= 64 steps of 32), about the same at 20-60 steps (the 728-channel layers) and 1.1-1.2 when it is short (its prologue and
 // 132 KiB epilogue are not hidden by a co-resident workgroup) -- for 4/3 of the work per round.  When both fit one round the
 // small tile (finer tail, three workgroups hiding each other's latencies) keeps the layer unless the K loop is long.
-// Pointwise layers on the one-wave-per-SIMD kernel (igemm384.hip).  0: never, 1: where the round model below expects it to win,
+// Pointwise layers on the one-wave-per-SIMD kernel (igemm384.hip), switch pw384.  0: never, 1: where the round model below expects it to win,
 // 2 / 3: whenever eligible with 256- / 128-pixel tiles (tests and A/B runs).  Costs are in rounds of 256 x 256 tiles: a
 // 256 x 384 tile is 1.5 of them, a 128 x 384 tile 0.8 (its weight fill is not halved), a round of the 128-tile kernel about 1 at
 // the K depths in question (see igemm256_wins).  The layer must also fill most of the chip with its one workgroup per CU.
-static int g_igemm256p = 1;          // persistent 256-tile kernel for multi-round launches (A/B switch "igemm256p")
-static int g_igemm256p_wgs = 0;      // its workgroups ("igemm256p_wgs"); 0: fewest that keep the number of rounds
-static int g_igemm256p_min = 257;    // fewest tiles it is used for ("igemm256p_min")
-static int g_pw384 = 1;
-static int g_pw192 = 1;             // 128 x 192 tiles for one-round launches of few pixels ("pw192")
-static int g_pw224 = 1;             // 224 x 384 tiles with weights from the [k][n] packing where the caller passes it ("pw224"; 2: whenever eligible)
 static int pw384_plan(const IgemmParams& p) {
-  if (g_pw224 == 2 && pw224_eligible(p)) return 224;
-  if (g_pw224 == 3 && pw224_eligible(p)) return 226;      // 224 x 192 tiles wherever eligible (tests)
-  if (g_pw384 == 0 || !pw384_eligible(p)) return 0;
-  if (g_pw384 == 2) return 8;
-  if (g_pw384 == 3) return 4;
-  if (g_pw384 == 4) return 64;      // 256 x 384 tiles, 64-deep stages of 128-byte rows
-  if (g_pw384 == 5) return 192;     // 128 x 192 tiles (igemm192.hip)
+  if (g_options.pw224 == 2 && pw224_eligible(p)) return 224;
+  if (g_options.pw224 == 3 && pw224_eligible(p)) return 226;      // 224 x 192 tiles wherever eligible (tests)
+  if (g_options.pw384 == 0 || !pw384_eligible(p)) return 0;
+  if (g_options.pw384 == 2) return 8;
+  if (g_options.pw384 == 3) return 4;
+  if (g_options.pw384 == 4) return 64;      // 256 x 384 tiles, 64-deep stages of 128-byte rows
+  if (g_options.pw384 == 5) return 192;     // 128 x 192 tiles (igemm192.hip)
   const long t128 = (long)cdiv(p.g.Cout, BN) * p.mtiles, t256 = igemm256_tiles(p);
   const double c_old = (double)(cdiv(t256, 256) < cdiv(t128, 768) ? cdiv(t256, 256) : cdiv(t128, 768));
   if (p.g.Cout * 10 < (long)cdiv(p.g.Cout, 384) * 384 * 9) return 0;      // a 384-wide tile that is more than a tenth empty loses
@@ -491,14 +461,14 @@ static int pw384_plan(const IgemmParams& p) {
   // few pixels (local batch 2): 128 x 192 tiles when they are ONE round of one workgroup per CU and neither 384-wide tile fills the chip
   // (728 -> 728 at M = 6 912: 216 tiles; 24.6 -> 14 us against the 128 x 128 kernel's 324 tiles, scripts/pw384_bench.py)
   const long t192 = pw192_tiles(p);
-  if (g_pw192 && best >= 1e9 && t192 >= 160 && t192 <= 256 && p.g.Cin >= 128 && p.g.Cout * 10 >= (long)cdiv(p.g.Cout, 192) * 192 * 9) return 192;
+  if (g_options.pw192 && best >= 1e9 && t192 >= 160 && t192 <= 256 && p.g.Cin >= 128 && p.g.Cout * 10 >= (long)cdiv(p.g.Cout, 192) * 192 * 9) return 192;
   if (best >= 0.9 * c_old) return 0;
   // where the 256-pixel tile with 64-deep stages would run: the 224-pixel tile when it is ONE round too (728 -> 728 at M = 27 648: 248 tiles)
   // (multi-round launches too: 728 -> 728 at M = 110 592 137 against 156 us, 256 -> 728 there 81 against 92: profiles/r06_pw224_bench.txt)
-  if (c8 < c4 && k64 && g_pw224 && pw224_eligible(p) && cdiv(pw224_tiles(p), 256) <= cdiv(t8, 256)) return 224;
+  if (c8 < c4 && k64 && g_options.pw224 && pw224_eligible(p) && cdiv(pw224_tiles(p), 256) <= cdiv(t8, 256)) return 224;
   // where 128-pixel tiles would run (half as many pixels: local batch 4): 224 x 192 tiles when they are one round of nearly the whole chip
   // (13 824 pixels x 728 channels: 62 x 4 = 248 tiles, 26 KiB of operands per 32-deep step instead of 32)
-  if (!(c8 < c4) && g_pw224 && pw224_eligible(p) && pw224_tiles(p, 192) > 192 && pw224_tiles(p, 192) <= 256 &&
+  if (!(c8 < c4) && g_options.pw224 && pw224_eligible(p) && pw224_tiles(p, 192) > 192 && pw224_tiles(p, 192) <= 256 &&
       p.g.Cout * 10 >= (long)cdiv(p.g.Cout, 192) * 192 * 9)
     return 226;
   return c8 < c4 ? (k64 ? 64 : 8) : 4;
@@ -585,10 +555,10 @@ static int run_gather(const dc_conv_desc* d, GatherMode mode, int N, int Hi, int
   }
   DC_REQUIRE(slab == nullptr || slab_rows != -1, "dc_conv_fwd_kn: this launch does not add to a sum row (dc_conv_sum_row_kn)");
   DC_REQUIRE(slab == nullptr || slab_rows <= 0 || slab_rows == p.mtiles * p.g.os * p.g.os, "dc_conv_fwd_kn: slab_rows is not what this launch writes now (dc_conv_stat_rows_kn)");
-  if (d->dtype == DC_BF16 && !out32 && g_igemm256 != 0) {
-    if (g_igemm256 == 2 || igemm256_wins(p)) {
+  if (d->dtype == DC_BF16 && !out32 && g_options.igemm256 != 0) {
+    if (g_options.igemm256 == 2 || igemm256_wins(p)) {
       // several rounds of tiles: the persistent form keeps the operand ring full across tiles (igemm256p.hip)
-      if (g_igemm256p && bst == nullptr && igemm256p_eligible(p) && igemm256_tiles(p) >= (long)g_igemm256p_min) return launch_igemm256p(p, g_igemm256p_wgs, st);
+      if (g_options.igemm256p && bst == nullptr && igemm256p_eligible(p) && igemm256_tiles(p) >= (long)g_options.igemm256p_min) return launch_igemm256p(p, g_options.igemm256p_wgs, st);
       return launch_igemm256(p, st);
     }
   }
@@ -843,13 +813,6 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const PackEntry* __restri
 
 using namespace dc;
 
-#ifdef DC_STAMPS
-extern "C" int dc_debug_stamp_buf(void* buf) {
-  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(dc_stamp_buf), &buf, sizeof(buf));
-  return e == hipSuccess ? 0 : dc_set_error(e, __FILE__, __LINE__);
-}
-#endif
-
 constexpr int PACK_BLOCKS = 2048;   // workgroups of the flat dc_pack_all grid
 extern "C" int dc_pack_all(int dtype, const void* table_dev, int nentries, void* stream) {
   DC_REQUIRE(table_dev != nullptr && nentries > 0, "dc_pack_all: bad argument");
@@ -862,56 +825,69 @@ extern "C" int dc_pack_all(int dtype, const void* table_dev, int nentries, void*
   return 0;
 }
 
-// Switches that force a kernel at shapes the planners would not give it (tests, A/B runs in one process).
-extern "C" int dc_wgrad_set_384(int m);
-extern "C" int dc_wgrad_set_384_slots(int n);
-extern "C" int dc_wgrad_set_384_min_stages(int n);
-extern "C" int dc_head_set_fused(int v);
-extern "C" int dc_head_set_dgrad_fused(int v);
-extern "C" int dc_head_set_wgrad_fused(int v);
-extern "C" int dc_dw_set_option(const char* name, int value);
-extern "C" int dc_bn_set_option(const char* name, int value);
+Options dc::g_options;
+
+// dc_set_option's names for the members of dc::Options (common.h), and how each stores a value: as given, as a flag (v != 0), clamped, or
+// refused below 1 (kStages: then at least 4).  dc_reset_options puts the member initialisers back (the test suite calls it after every test,
+// so that a switch one test leaves behind cannot change what the next one measures -- a stale "restore" of this kind once ran the model
+// tests on an experimental kernel).
+namespace {
+enum class Norm { kValue, kFlag, kZeroToTwo, kNonNegative, kPositive, kStages };
+const struct {
+  const char* name;
+  int Options::*field;
+  Norm norm;
+} kOptions[] = {
+    {"igemm256", &Options::igemm256, Norm::kValue},
+    {"igemm256p", &Options::igemm256p, Norm::kValue},
+    {"igemm256p_wgs", &Options::igemm256p_wgs, Norm::kValue},
+    {"igemm256p_min", &Options::igemm256p_min, Norm::kValue},
+    {"igemm256_splitk", &Options::igemm256_splitk, Norm::kValue},
+    {"pw384", &Options::pw384, Norm::kValue},
+    {"pw224", &Options::pw224, Norm::kValue},
+    {"pw192", &Options::pw192, Norm::kValue},
+    {"thin_tile", &Options::thin_tile, Norm::kFlag},
+    {"wgrad384", &Options::wgrad384, Norm::kValue},
+    {"wgrad384_slots", &Options::wgrad384_slots, Norm::kPositive},
+    {"wgrad384_min_stages", &Options::wgrad384_min_stages, Norm::kStages},
+    {"head_fused", &Options::head_fused, Norm::kFlag},
+    {"head_dgrad_fused", &Options::head_dgrad_fused, Norm::kFlag},
+    {"head_wgrad_fused", &Options::head_wgrad_fused, Norm::kFlag},
+    {"dw_tile", &Options::dw_tile, Norm::kFlag},
+    {"dw_wgrad_tpb", &Options::dw_wgrad_tpb, Norm::kNonNegative},
+    {"dw_pipe", &Options::dw_pipe, Norm::kZeroToTwo},
+    {"bn_apply_rows", &Options::bn_apply_rows, Norm::kFlag},
+};
+}  // namespace
+
 extern "C" int dc_set_option(const char* name, int value) {
-  if (name != nullptr && strcmp(name, "igemm256") == 0) { g_igemm256 = value; return 0; }
-  if (name != nullptr && strcmp(name, "pw384") == 0) { g_pw384 = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm256p") == 0) { g_igemm256p = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm256p_wgs") == 0) { g_igemm256p_wgs = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm256p_min") == 0) { g_igemm256p_min = value; return 0; }
-  if (name != nullptr && strcmp(name, "pw224") == 0) { g_pw224 = value; return 0; }
-  if (name != nullptr && strcmp(name, "pw192") == 0) { g_pw192 = value; return 0; }
-  if (name != nullptr && strcmp(name, "igemm256_splitk") == 0) { igemm256_set_splitk(value); return 0; }
-  if (name != nullptr && strcmp(name, "thin_tile") == 0) { thin_set_tile(value); return 0; }
-  if (name != nullptr && strcmp(name, "wgrad384") == 0) return dc_wgrad_set_384(value);
-  if (name != nullptr && strcmp(name, "wgrad384_slots") == 0) return dc_wgrad_set_384_slots(value);
-  if (name != nullptr && strcmp(name, "wgrad384_min_stages") == 0) return dc_wgrad_set_384_min_stages(value);
-  if (name != nullptr && strcmp(name, "head_fused") == 0) return dc_head_set_fused(value);
-  if (name != nullptr && strcmp(name, "head_dgrad_fused") == 0) return dc_head_set_dgrad_fused(value);
-  if (name != nullptr && strcmp(name, "head_wgrad_fused") == 0) return dc_head_set_wgrad_fused(value);
-  if (name != nullptr && dc_dw_set_option(name, value) == 0) return 0;
-  if (name != nullptr && dc_bn_set_option(name, value) == 0) return 0;
+  for (const auto& o : kOptions) {
+    if (name == nullptr || strcmp(name, o.name) != 0) continue;
+    switch (o.norm) {
+      case Norm::kValue: break;
+      case Norm::kFlag: value = value != 0; break;
+      case Norm::kZeroToTwo: value = value < 0 ? 0 : value > 2 ? 2 : value; break;
+      case Norm::kNonNegative: value = value < 0 ? 0 : value; break;
+      case Norm::kPositive:
+      case Norm::kStages:
+        if (value < 1) {
+          char msg[96];
+          snprintf(msg, sizeof(msg), "dc_set_option: %s must be positive", o.name);
+          return dc_fail(msg, __FILE__, __LINE__);
+        }
+        if (o.norm == Norm::kStages && value < 4) value = 4;
+        break;
+    }
+    g_options.*o.field = value;
+    return 0;
+  }
   return dc_fail("dc_set_option: unknown option", __FILE__, __LINE__);
 }
 
-// Every tuning switch with its default, in ONE place: dc_reset_options() puts the whole set back (the test suite calls it after every test,
-// so that a switch one test leaves behind cannot change what the next one measures -- a stale "restore" of this kind once ran the model
-// tests on an experimental kernel), and the library applies the same table when it is loaded, so the table IS the default.
-static const struct { const char* name; int value; } kOptionDefaults[] = {
-    {"igemm256", 1}, {"pw384", 1}, {"pw224", 1}, {"pw192", 1}, {"igemm256p", 1}, {"igemm256p_wgs", 0}, {"igemm256p_min", 257}, {"thin_tile", 1},
-    {"wgrad384", 1}, {"wgrad384_slots", 192}, {"wgrad384_min_stages", 96}, {"head_fused", 1}, {"head_dgrad_fused", 1}, {"head_wgrad_fused", 1},
-    {"igemm256_splitk", 1}, {"dw_tile", 1}, {"dw_wgrad_tpb", 0}, {"dw_pipe", 1}, {"bn_apply_rows", 1},
-};
-
 extern "C" int dc_reset_options(void) {
-  for (const auto& o : kOptionDefaults)
-    if (int e = dc_set_option(o.name, o.value)) return e;
+  g_options = Options{};
   return 0;
 }
-
-namespace {
-struct OptionDefaultsAtLoad {
-  OptionDefaultsAtLoad() { (void)dc_reset_options(); }
-} g_option_defaults_at_load;
-}  // namespace
 
 extern "C" int dc_conv_out_hw(const dc_conv_desc* d, int Hi, int Wi, int* Ho, int* Wo) {
   DC_REQUIRE(d != nullptr, "dc_conv_out_hw: null descriptor");
@@ -998,7 +974,7 @@ static int dilated_group_impl(const dc_conv_desc* d, int N, int Hi, int Wi, int 
   DC_REQUIRE(!d->transposed && d->k == 3 && d->stride == 1, "dc_conv_fwd_dilated_group: 3x3, stride 1 convolutions only");
   if (want_bytes != nullptr) *want_bytes = 0;
   for (int b = 0; b < count; ++b) DC_REQUIRE(dils[b] >= 1 && (want_bytes != nullptr || (wfs[b] != nullptr && ys[b] != nullptr)), "dc_conv_fwd_dilated_group: bad member");
-  const bool fused = count > 1 && d->dtype == DC_BF16 && g_igemm256 != 0;
+  const bool fused = count > 1 && d->dtype == DC_BF16 && g_options.igemm256 != 0;
   if (!fused) {
     if (want_bytes != nullptr) return 0;
     for (int b = 0; b < count; ++b) {

@@ -34,10 +34,7 @@ constexpr int NCB = TN / 16 / GC;      // channel blocks per wave: 6
 constexpr int STAGE = (TN + TM) * RB;  // 40 KiB
 constexpr int NI = STAGE / 1024;       // 40
 constexpr int IPW = NI / 8;            // 5
-#ifndef DC_PW192_STAGES
-#define DC_PW192_STAGES 4
-#endif
-constexpr int NSTG = DC_PW192_STAGES;
+constexpr int NSTG = 4;                // ring stages (4 x 40 KiB = the CU's whole LDS)
 constexpr int RING = NSTG * STAGE;
 constexpr int BLK = 16 * RB;           // bytes between the fragments of consecutive 16-row blocks
 static_assert(NI % 8 == 0 && IPW <= NCB && RING <= 160 * 1024 && NSTG >= 3 && NCB % 3 == 0 && NCB % 2 == 0, "configuration");
@@ -117,10 +114,8 @@ __global__ __launch_bounds__(512) void pw192_kernel(const IgemmParams p) {
     __builtin_amdgcn_global_load_lds((gas_ptr)a, (lds_ptr)(smem + slot * STAGE + (8 * i + wave) * 1024), 16, 0, 0);
   };
 
-#ifndef DC_LATE_PRIO
-#define DC_LATE_PRIO 1      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
-#endif
-  if (DC_LATE_PRIO && late) __builtin_amdgcn_s_setprio(DC_LATE_PRIO);
+  constexpr int LATE_PRIO = 1;      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
+  if (late) __builtin_amdgcn_s_setprio(LATE_PRIO);
   f32x4 acc[NCB][NPB];   // [channel block][pixel block]
 #pragma unroll
   for (int i = 0; i < NCB; ++i)

@@ -40,6 +40,7 @@ namespace {
 
 constexpr int NWS = 3, NPS = 3;              // ring depths
 constexpr int NPB = 7;                       // pixel blocks of 16 per wave
+constexpr int PW224_AUXP = 0;                // cache-policy bits of the pixel LDS-DMA (nt: 2 101 cycles per step against 1 924)
 
 typedef __attribute__((address_space(1))) const void* gas_ptr;
 typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -90,16 +91,6 @@ __device__ inline void static_for(F&& f) {
   }
 }
 
-// diagnostic build (make stamps224; scripts/pw224_stamps.py): wave 0 of every workgroup leaves the 100 MHz real-time counter at kernel entry,
-// behind the prologue's barrier, behind the K loop and behind the drained stores, and the shader clock around the loop
-#ifdef DC_PW224_STAMPS
-__device__ unsigned long long pw224_stamp_buf[1024][8];
-#define PW224_STAMP(i) do { if (threadIdx.x == 0) { pw224_stamp_buf[blockIdx.x & 1023][i] = __builtin_amdgcn_s_memrealtime(); \
-                                                   pw224_stamp_buf[blockIdx.x & 1023][4 + (i)] = __builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define PW224_STAMP(i)
-#endif
-
 // TN: channels per workgroup, 384 (six quads of 64; a wave owns 96 = six blocks of 16) or 192 (three quads; a wave owns 48 = three blocks):
 // 224 x 192 is the tile for HALF as many pixels (local batch 4: 13 824 pixels x 728 channels = 62 x 4 = 248 tiles), 26 KiB of operands per
 // 32-deep step instead of the 32 KiB of 128 x 384.
@@ -131,7 +122,6 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const GatherGeom& g = p.g;
   const int tid = threadIdx.x, lane = tid & 63;
-  PW224_STAMP(0);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave / GC;   // pixel group (112 pixels)
   const int wc = wave % GC;    // channel group.  TN 384: chunk pair wc & 1 of the quads (wc >> 1) + 2 u; TN 192: the chunks 3 wc .. 3 wc + 2
@@ -193,23 +183,13 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
     const unsigned kb = (unsigned)S * 128u;
     const unsigned vk = (last ? kb : 0u) + (S > last_S ? OOB : 0u);     // (scalar) a stage past the K extent: every lane out of range
     const unsigned vt = S == last_S ? ptail : 0u;
-#ifndef DC_PW224_AUXP
-#define DC_PW224_AUXP 0
-#endif
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr)(smem + pdst + (wave + 8 * i) * 1024), 16, srcp[i] + vk + vt, last ? 0u : kb, 0, DC_PW224_AUXP);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr)(smem + pdst + (wave + 8 * i) * 1024), 16, srcp[i] + vk + vt, last ? 0u : kb, 0, PW224_AUXP);
   };
 #else
   auto issue_w = [&](int, int, uint32_t) {};
   auto issue_p = [&](int, int, uint32_t) {};
 #endif
 
-#ifdef DC_PW224_PROBE
-  // diagnostic builds (make probes224), one library per COMPILE-TIME mask: bit 0 drops the K loop's LDS-DMA issues, bit 1 its LDS fragment reads,
-  // bit 2 its MFMAs -- what each costs in the loop.  Results are garbage by construction.
-  constexpr int probe = DC_PW224_PROBE;
-#else
-  constexpr int probe = 0;
-#endif
   f32x4 acc[NCB][NPB];   // [channel block][pixel block]
 #pragma unroll
   for (int i = 0; i < NCB; ++i)
@@ -252,26 +232,23 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
       constexpr int k = decltype(kc)::value;
       if constexpr (k < HP) {
         constexpr int slot = HP * H + k;
-        if constexpr (!(probe & 16)) { if (slot < K::PSLOTS - 1 || has_last) issue_p(slot, S + 2, pdst); }
+        if (slot < K::PSLOTS - 1 || has_last) issue_p(slot, S + 2, pdst);
       } else {
         constexpr int wi = k - HP;
-        if constexpr (!(probe & 8)) { if (wi < K::WSLOTS - K::WDEF || has_last) issue_w(wi, s + 2, wdst); }
+        if (wi < K::WSLOTS - K::WDEF || has_last) issue_w(wi, s + 2, wdst);
       }
     };
     constexpr int ND = HP + K::WSLOTS;                 // 5 / 4
     // blocks in which the early waves (0..3) and the late waves (4..7) issue instruction k
-#ifndef DC_PW224_PLAN
-#define DC_PW224_PLAN 0
-#endif
     constexpr int EB[5] = {0, 0, 1, 1, NCB == 6 ? 2 : 1}, LB[5] = {NCB == 6 ? 2 : 1, NCB == 6 ? 3 : 1, NCB == 6 ? 3 : 2, NCB == 6 ? 4 : 2, NCB == 6 ? 4 : 2};
     static_assert(ND <= 5, "issue plan");
     static_for<0, NCB>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr (i + 2 < NCB && !(probe & 2)) {      // two blocks ahead
+      if constexpr (i + 2 < NCB) {      // two blocks ahead
         if constexpr (TN == 384) lds_read_tr<((i + 2) >> 1) * 8192>(fa[(i + 2) % 3], wcur + a_base[(i + 2) & 1] - lds0);
         else lds_read_tr<0>(fa[(i + 2) % 3], wcur + a_base[i + 2] - lds0);
       }
-      if (dma && !(probe & 1)) {
+      if (dma) {
         static_for<0, ND>([&](auto kc) {
           constexpr int k = decltype(kc)::value;
           if constexpr (EB[k] == i) { if (!late) dma_k(kc); }
@@ -280,19 +257,16 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
       }
       if constexpr (i == NCB - 1) {
         // stage end: W[s+1] (and with it everything older) has landed for this wave; this step's own instructions stay in flight
-        if (dma && !(probe & 1)) {
-          // (all but this step's own instructions: pixel slots + weight slots, one fewer of each kind where waves 4..7 own no last slot)
-          constexpr int NW = (probe & 8) ? 0 : K::WSLOTS, NP = (probe & 16) ? 0 : HP;      // (probe builds that drop one operand's LDS-DMAs)
-          constexpr int DW = (probe & 8) ? 0 : K::WDEF, DP = (probe & 16) || H == 0 ? 0 : 1;
-          if (has_last) vm_lgkm0_wait<NW + NP>(); else vm_lgkm0_wait<NW + NP - DW - DP>();
+        if (dma) {
+          // (all but this step's own instructions: pixel slots + weight slots, one fewer of each kind where waves 4..7 own no last slot; the
+          // last pixel slot is issued in the H = 1 step)
+          if (has_last) vm_lgkm0_wait<K::WSLOTS + HP>(); else vm_lgkm0_wait<K::WSLOTS + HP - K::WDEF - H>();
         } else {
           vm_lgkm0_wait<0>();
         }
         __builtin_amdgcn_s_barrier();
-        if constexpr (!(probe & 2)) {
-          lds_read_tr<0>(fa[0], wnxt + a_base[0] - lds0);                              // next step's first two weight fragments
-          lds_read_tr<0>(fa[1], wnxt + a_base[1] - lds0);
-        }
+        lds_read_tr<0>(fa[0], wnxt + a_base[0] - lds0);                              // next step's first two weight fragments
+        lds_read_tr<0>(fa[1], wnxt + a_base[1] - lds0);
       }
       static_for<0, NPB>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -302,16 +276,14 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
         if constexpr (i == 0) lgkm_wait<NPB - 1 - j + 2>();
         else if constexpr (j == 0 && i < NCB - 2) lgkm_wait<4>();
         else if constexpr (j == 0 && i == NCB - 2) lgkm_wait<2>();
-        if constexpr (!(probe & 4)) mfma_v(acc[i][j], __builtin_bit_cast(bf16x8, fa[i % 3]), fb[j]);
-        if constexpr (i == NCB - 1 && !(probe & 2)) lds_read16<j * 2048>(fb[j], bnxt);   // re-read in place for the next step
+        mfma_v(acc[i][j], __builtin_bit_cast(bf16x8, fa[i % 3]), fb[j]);
+        if constexpr (i == NCB - 1) lds_read16<j * 2048>(fb[j], bnxt);   // re-read in place for the next step
       });
     });
   };
 
-#ifndef DC_PW224_PRIO
-#define DC_PW224_PRIO 1      // the second-dispatched wave of every SIMD loses each arbitration at equal priority: 1 965 -> 1 924 cycles per step
-#endif
-  if (late) __builtin_amdgcn_s_setprio(DC_PW224_PRIO);
+  constexpr int LATE_PRIO = 1;      // the second-dispatched wave of every SIMD loses each arbitration at equal priority: 1 965 -> 1 924 cycles per step
+  if (late) __builtin_amdgcn_s_setprio(LATE_PRIO);
   // ---- prologue: P[0] (the operand from beyond the L2 first), W[0], P[1], W[1] in flight (W[1] last: see "hazards"), P[0] and W[0] landed,
   // first fragments requested
 #pragma unroll
@@ -326,7 +298,6 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
   if (has_last) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::WSLOTS + K::PSLOTS) : "memory");
   else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::WSLOTS - K::WDEF + K::PSLOTS - 1) : "memory");
   __builtin_amdgcn_s_barrier();
-  PW224_STAMP(1);
   lds_read_tr<0>(fa[0], a_base[0]);
   lds_read_tr<0>(fa[1], a_base[1]);
   static_for<0, NPB>([&](auto jc) { lds_read16<decltype(jc)::value * 2048>(fb[decltype(jc)::value], lds0 + b_off); });
@@ -349,7 +320,6 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (the ring is reused below)
 
   __builtin_amdgcn_s_barrier();
-  PW224_STAMP(2);
 
   // ---- epilogue from the accumulator registers (igemm384.hip's) -------------------------------------------------------------------
   // A lane holds, per MFMA tile (i, j), channels fg*4 .. +3 of channel block i for pixel fr of pixel block j.  Blocks 2 pr and 2 pr + 1 are the
@@ -515,11 +485,6 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
       }
     }
   }
-#ifdef DC_PW224_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  PW224_STAMP(3);
-#endif
 }
 
 }  // namespace
@@ -546,9 +511,3 @@ int launch_pw224(const IgemmParams& p, int tn, hipStream_t st) {
 }
 
 }  // namespace dc
-
-#ifdef DC_PW224_STAMPS
-extern "C" int dc_debug_pw224_stamps(void* host_out, int blocks) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dc::pw224_stamp_buf), (size_t)blocks * 8 * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-}
-#endif

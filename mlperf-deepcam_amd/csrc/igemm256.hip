@@ -1,6 +1,6 @@
 // Gather-form implicit GEMM, 256 output pixels x 256 output channels per 512-thread workgroup (bf16).
 //
-// Why a second tile shape: in-kernel stamps on the 128 x 128 kernel (scripts/igemm_stamps.py) show its K loop advancing at
+// Why a second tile shape: in-kernel stamps on the 128 x 128 kernel (profiles/r01_igemm_stamps.txt) show its K loop advancing at
 // ~1480 cycles per 32-deep step with three workgroups per CU, i.e. the CU takes in 16 KiB of operands per ~490 cycles
 // (~33 B/clk) while its MFMA pipes are busy half of that time: the loop is bound by the global->LDS fill, and the bytes to
 // fill per MFMA fall with the tile edge.  A 256 x 256 tile needs half the operand bytes per flop.
@@ -43,16 +43,6 @@ __device__ inline const void* zero_page256_ptr(const IgemmParams& p) { return p.
 typedef __attribute__((address_space(1))) const void* gas_ptr;
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
-// Diagnostic build only (-DDC_STAMPS): per-segment cycle sums of the K loop for one wave of each group (scripts/igemm_stamps.py).
-#ifdef DC_STAMPS
-__device__ unsigned long long* dc_stamp_buf256 = nullptr;
-#define SEG_T() __builtin_amdgcn_s_memtime()
-#define SEG_ADD(k, t0, t1) seg[k] += (t1) - (t0)
-#else
-#define SEG_T() 0ull
-#define SEG_ADD(k, t0, t1)
-#endif
-
 __device__ inline int swz64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 1) & 3)) << 4); }
 
 // ---- helpers of the register epilogue ---------------------------------------------------------------------------------------
@@ -73,7 +63,6 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
   const GatherGeom& g = p.g;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  [[maybe_unused]] const unsigned long long t_start = SEG_T();
   const int grp = wave >> 2;   // pixel half; also the stagger group
   const int wc = wave & 3;     // channel quarter
 
@@ -253,17 +242,12 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const vec16*>(xb + swz64(grp * 128 + j * 16 + fr, fg));
   }
-#ifdef DC_STAMPS
-  unsigned long long seg[6] = {0, 0, 0, 0, 0, 0};
-  const unsigned long long t_loop0 = SEG_T();
-#endif
   // The two waves of a SIMD (w and w+4, i.e. the two pixel halves) run the halves of every segment in opposite order: while
   // one issues its reads and LDS-DMAs (which hold a wave's issue for 60-185 cycles apiece) the other issues MFMAs.  The
   // whole loop is instantiated twice (a branch inside the loop body made the register allocator spill).
   auto k_loop = [&](auto loads_first_tag) {
     constexpr bool LOADS_FIRST = decltype(loads_first_tag)::value;
     for (int s = 0; s < steps; ++s) {
-      [[maybe_unused]] const unsigned long long t0 = SEG_T();
       const char* xb = smem + (s & (NSTAGE - 1)) * STAGE + OPER;
       const char* wa1 = smem + ((s + 1) & (NSTAGE - 1)) * STAGE;
       const char* xb1 = wa1 + OPER;
@@ -289,13 +273,10 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
         for (int j = 0; j < 4; ++j) fb2[j] = *reinterpret_cast<const vec16*>(xb + swz64(grp * 128 + (4 + j) * 16 + fr, fg));
         issue_A(itap, ikc, nslot, live);
       }
-      [[maybe_unused]] const unsigned long long t1 = SEG_T();
       asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-      [[maybe_unused]] const unsigned long long t2 = SEG_T();
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      [[maybe_unused]] const unsigned long long t3 = SEG_T();
       // ---- M1
       if constexpr (LOADS_FIRST) {
 #pragma unroll
@@ -320,21 +301,10 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
         issue_B(itap, ikc, nslot, live);
         advance();
       }
-      [[maybe_unused]] const unsigned long long t4 = SEG_T();
-      SEG_ADD(0, t0, t1); SEG_ADD(1, t1, t2); SEG_ADD(2, t2, t3); SEG_ADD(3, t3, t4);
     }
   };
   if (grp == 0) k_loop(std::true_type{});
   else k_loop(std::false_type{});
-#ifdef DC_STAMPS
-  if (dc_stamp_buf256 != nullptr && lane == 0 && wc == 0) {
-    unsigned long long* o = dc_stamp_buf256 + ((size_t)blockIdx.x * 2 + grp) * 8;
-    for (int k = 0; k < 4; ++k) o[k] = seg[k];
-    o[4] = t_loop0 - t_start;      // prologue: tap table, row bookkeeping, three stages issued, stage 0 landed
-    o[6] = SEG_T() - t_loop0;
-    o[7] = (unsigned long long)steps;
-  }
-#endif
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the zero-page fills of the last three slots
   __builtin_amdgcn_s_barrier();
 
@@ -494,23 +464,9 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
       }
     }
   }
-#ifdef DC_STAMPS
-  if (dc_stamp_buf256 != nullptr && lane == 0 && wc == 0) {
-    unsigned long long* o = dc_stamp_buf256 + ((size_t)blockIdx.x * 2 + grp) * 8;
-    o[5] = SEG_T() - t_start;      // whole kernel
-  }
-#endif
 }
 
 }  // namespace
-
-#ifdef DC_STAMPS
-extern "C" int dc_debug_stamp_buf256(void* buf) {
-  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(dc_stamp_buf256), &buf, sizeof(buf));
-  return e == hipSuccess ? 0 : dc_set_error(e, __FILE__, __LINE__);
-}
-#endif
-
 
 // Sum of the split-K partial tiles of one 128-pixel half of one tile, in the order of the splits: y (bf16) and the BatchNorm partial sums of
 // the STORED values, one slab row per half as the kernel's own epilogue leaves them.  256 threads = 64 channel groups of 4 x 4 row lanes.
@@ -576,15 +532,12 @@ __global__ __launch_bounds__(256) void igemm256_splitk_fold_kernel(const SplitKF
   }
 }
 
-static int g_splitk = 1;         // tuning switch "igemm256_splitk": 0 = never split the K loop of a 256-tile launch
-void igemm256_set_splitk(int v) { g_splitk = v; }
-
 // A launch that leaves more than half of the chip idle and has a long K loop is cut along K: as many splits as fit one round, at least two
 // channel-chunk groups (2 x 4 chunks x taps K steps) each, at most eight.  Plain stride-1 launches only (no sub-pixel phases, no bias, no
 // accumulation, no BatchNorm-backward epilogue: the fold kernel does the plain epilogue).
 int igemm256_splitk_plan(const IgemmParams& p, size_t* slab_bytes) {
   if (slab_bytes) *slab_bytes = 0;
-  if (!g_splitk || p.g.os != 1 || p.m_beg != 0 || p.bias != nullptr || p.accumulate || p.bst.y != nullptr || (p.g.Cout & 7)) return 1;
+  if (!g_options.igemm256_splitk || p.g.os != 1 || p.m_beg != 0 || p.bias != nullptr || p.accumulate || p.bst.y != nullptr || (p.g.Cout & 7)) return 1;
   const long tiles = igemm256_tiles(p);
   if (tiles < 1) return 1;
   const int ngk = ((p.g.Cin + BK - 1) / BK + 3) / 4;
@@ -593,7 +546,7 @@ int igemm256_splitk_plan(const IgemmParams& p, size_t* slab_bytes) {
     s = (int)(256 / tiles);
     if (s > ngk / 2) s = ngk / 2;
     if (s > 8) s = 8;
-  } else if (g_splitk > 1) {
+  } else if (g_options.igemm256_splitk > 1) {
     // more than one round with a thin last one (the grouped atrous launch at local batch 8: 324 tiles of 576 K steps, the second round a
     // quarter full): the split count of 2 - 4 that fills the rounds best, if it fills them at least a tenth better than the plain launch
     auto fill = [](long n) { return (double)n / (double)(((n + 255) / 256) * 256); };

@@ -95,10 +95,7 @@ struct Cfg {
   static constexpr int NCB = TN / 16 / GC;                // channel blocks per wave: 12 / 6
   static constexpr int TM = GP * NPB * 16;                // pixels per workgroup: 256 / 128
   static constexpr int RB = K64 ? 128 : 64;               // bytes of K per row and stage
-#ifndef DC_PW384_GP2_STAGES
-#define DC_PW384_GP2_STAGES 3
-#endif
-  static constexpr int NSTG = K64 ? 2 : (GP == 2 ? DC_PW384_GP2_STAGES : NST);   // ring stages (128 x 384: 32 KiB each, four fit)
+  static constexpr int NSTG = K64 ? 2 : NST;              // ring stages (128 x 384: 32 KiB each, four would fit)
   static constexpr int STAGE = (TN + TM) * RB;            // 40 / 32 KiB (80 KiB: K64)
   static constexpr int NI = STAGE / 1024;                 // LDS-DMA instructions per stage
   static constexpr int IPW = NI / 8;                      // per wave: 5 / 4 (10: K64)
@@ -122,13 +119,6 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
   const int grp = wave / GC;   // pixel group (64 pixels)
   const int wc = wave % GC;    // channel group (NCB blocks of 16)
   const bool late = wave >= 4; // the second wave of its SIMD: issues its LDS-DMAs in the second half of a step
-#ifdef DC_PW384_PROBE
-  // diagnostic builds (make probes; scripts/pw384_probe.py), one library per COMPILE-TIME mask: bit 0 drops the LDS-DMA issues, bit 1
-  // the LDS fragment reads, bit 3 the epilogue stores -- what each costs in the K loop.  Results are garbage by construction.
-  constexpr int probe = DC_PW384_PROBE;
-#else
-  constexpr int probe = 0;
-#endif
 
   // XCD-aware tile order: consecutive tiles of an XCD are the channel tiles of one pixel tile (they share its pixel rows in L2)
   const int ntn = (g.Cout + TN - 1) / TN;
@@ -171,13 +161,11 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
     const bool ok = (src[i] != ~0u) & (kofs + lslot * 8 < g.Cin);          // stage >= kchunks fails the K test: zero page
     const uintptr_t base = (8 * i + wave) * RPI < TN ? wbase : xbase;      // (scalar)
     const uintptr_t a = ok ? base + (src[i] + (unsigned)kofs * 2u) : zp;
-    if constexpr (!(probe & 1)) __builtin_amdgcn_global_load_lds((gas_ptr)a, (lds_ptr)(smem + (stage % K::NSTG) * K::STAGE + (8 * i + wave) * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gas_ptr)a, (lds_ptr)(smem + (stage % K::NSTG) * K::STAGE + (8 * i + wave) * 1024), 16, 0, 0);
   };
 
-#ifndef DC_LATE_PRIO
-#define DC_LATE_PRIO 1      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
-#endif
-  if (DC_LATE_PRIO && late) __builtin_amdgcn_s_setprio(DC_LATE_PRIO);
+  constexpr int LATE_PRIO = 1;      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
+  if (late) __builtin_amdgcn_s_setprio(LATE_PRIO);
   f32x4 acc[NCB][NPB];   // [channel block][pixel block]
 #pragma unroll
   for (int i = 0; i < NCB; ++i)
@@ -202,7 +190,7 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
     constexpr int VMW = decltype(vmw_tag)::value;
     static_for<0, NCB>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr (i + 2 < NCB && !(probe & 2)) lds_read16<(i + 2) * BLK>(fa[(i + 2) % 3], cur_a);      // weight fragment two blocks ahead
+      if constexpr (i + 2 < NCB) lds_read16<(i + 2) * BLK>(fa[(i + 2) % 3], cur_a);      // weight fragment two blocks ahead
       // this step's LDS-DMAs: waves 0..3 in blocks 0 .. IPW-1, waves 4..7 in blocks LATE .. LATE+IPW-1
       if constexpr (i < K::IPW) {
         if (!late && dma >= 0) issue(i, dma);
@@ -217,10 +205,8 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
         } else {
           lgkm_wait<0>();
         }
-        if constexpr (!(probe & 2)) {
-          lds_read16<0>(fa[0], nxt_a);                                                    // next step's first two weight fragments
-          lds_read16<BLK>(fa[1], nxt_a);
-        }
+        lds_read16<0>(fa[0], nxt_a);                                                    // next step's first two weight fragments
+        lds_read16<BLK>(fa[1], nxt_a);
       }
       static_for<0, NPB>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
         if constexpr (i == 0) lgkm_wait<NPB - j>();
         else if constexpr (j == 0 && i < NCB - 1) lgkm_wait<(NCB - 1 - i < 2 ? NCB - 1 - i : 2)>();
         mfma_v(acc[i][j], fa[i % 3], fb[j]);
-        if constexpr (i == NCB - 1 && !(probe & 2)) lds_read16<j * BLK>(fb[j], nxt_b);    // re-read in place for the next step
+        if constexpr (i == NCB - 1) lds_read16<j * BLK>(fb[j], nxt_b);    // re-read in place for the next step
       });
     });
   };
@@ -308,7 +294,7 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
       v.w[1] = odd ? r1 : a1;
       v.w[2] = odd ? b0 : r0;
       v.w[3] = odd ? b1 : r1;
-      if (m < p.M && chok && !(probe & 8)) {
+      if (m < p.M && chok) {
         bf16* dst = yg + (size_t)m * p.ldy + ch0;
         float f[8];
         unpack(v, f, bf16());

@@ -755,8 +755,6 @@ __global__ __launch_bounds__(256) void input_normalize_nchw_kernel(int N, long H
   }
 }
 
-static int g_head_fused = 1;   // bf16 forward: products + combination in one kernel (0: GEMM + combine kernels)
-extern "C" int dc_head_set_fused(int v) { g_head_fused = v ? 1 : 0; return 0; }
 
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -799,7 +797,7 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   if (dtype == DC_BF16) hipLaunchKernelGGL(head_pack_kernel<bf16>, dim3(cdiv(np, 256)), dim3(256), 0, st, w, (bf16*)ws.wf, (bf16*)ws.wb, Cin);
   else hipLaunchKernelGGL(head_pack_kernel<float>, dim3(cdiv(np, 256)), dim3(256), 0, st, w, (float*)ws.wf, (float*)ws.wb, Cin);
   DC_CHECK_LAUNCH();
-  if (dtype == DC_BF16 && g_head_fused && Cin == 256) {
+  if (dtype == DC_BF16 && g_options.head_fused && Cin == 256) {
     const int ntx = cdiv(Wi, HF_TX), nty = cdiv(Hi, HF_TY), strips = cdiv(ntx, HF_TILES);
     const size_t lds = (size_t)HF_MB * 16 * HEAD_NP * 4 + (size_t)HEAD_NP * Cin * 2 + (size_t)2 * Cin * 4;
     auto k0 = &head_fused_fwd_kernel<false>;
@@ -861,7 +859,7 @@ extern "C" int dc_head_fwd_loss(int dtype, int N, int Cin, int Hi, int Wi, const
 extern "C" int dc_head_fwd_bnin(int dtype, int N, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale, const float* shift,
                                 int relu, const float* w, float* logits_nchw, void* workspace, void* stream) {
   DC_REQUIRE(logits_nchw != nullptr && scale != nullptr && shift != nullptr, "dc_head_fwd_bnin: null argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_head_fused, "dc_head_fwd_bnin: bf16, 256 channels, fused head kernel only");
+  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_bnin: bf16, 256 channels, fused head kernel only");
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, nullptr, &bi);
 }
@@ -871,7 +869,7 @@ extern "C" int dc_head_fwd_loss_bnin(int dtype, int N, int Cin, int Hi, int Wi, 
                                      const float* class_weights, float grad_scale, double* loss_sum, float* dlogits, int64_t* pred,
                                      int64_t* counts, void* stream) {
   DC_REQUIRE(labels && class_weights && scale && shift, "dc_head_fwd_loss_bnin: bad argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_head_fused, "dc_head_fwd_loss_bnin: bf16, 256 channels, fused head kernel only");
+  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_loss_bnin: bf16, 256 channels, fused head kernel only");
   DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_loss_bnin: labels must be uint8, int32 or int64");
   HeadLoss hl{labels, label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts};
   const HeadBnIn bi{scale, shift, relu};
@@ -1112,10 +1110,6 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const bf16* __restrict_
   }
 }
 
-static int g_head_dgrad_fused = 1;   // "head_dgrad_fused": 0 = the head's data gradient on the tiled GEMM kernels (A/B, tests)
-extern "C" int dc_head_set_dgrad_fused(int v) { g_head_dgrad_fused = v ? 1 : 0; return 0; }
-static int g_head_wgrad_fused = 1;   // "head_wgrad_fused": the head's weight gradient rides on the statistics pass of the two-pass backward (parts = 3)
-extern "C" int dc_head_set_wgrad_fused(int v) { g_head_wgrad_fused = v ? 1 : 0; return 0; }
 
 // bn_y != nullptr: x is act(bn(bn_y)) and the data gradient also leaves that BatchNorm's backward sums in bn_slab
 static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* x, int ldx, const float* dlogits_nchw,
@@ -1131,7 +1125,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     DC_REQUIRE(bn_y != nullptr && bn_mscale != nullptr && bn_mshift != nullptr && dtype == DC_BF16, "dc_head_bwd_bnin: needs the BatchNorm input and its forward scale / shift (bf16)");
     if (int e = dc_check_view(bn_y, bn_ldy, Cin, dtype, "dc_head_bwd_bnin y")) return e;
   }
-  const bool streaming = dtype == DC_BF16 && Cin == 256 && g_head_dgrad_fused && bn_y != nullptr && bn_slab != nullptr;
+  const bool streaming = dtype == DC_BF16 && Cin == 256 && g_options.head_dgrad_fused && bn_y != nullptr && bn_slab != nullptr;
   if (dx != nullptr) {
     if (int e = dc_check_view(dx, lddx, Cin, dtype, "dc_head_bwd dx")) return e;
   } else {
@@ -1157,7 +1151,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     DC_CHECK_LAUNCH();
   }
   // the statistics pass without a stored dx (dc_head_bwd_bnin, two-pass form) asked for both parts at once: the weight gradient rides on it
-  const bool wg_rides = streaming && g_head_wgrad_fused && x == nullptr && dx == nullptr && parts == 3 && bn_relu >= 0 && P >= 256;
+  const bool wg_rides = streaming && g_options.head_wgrad_fused && x == nullptr && dx == nullptr && parts == 3 && bn_relu >= 0 && P >= 256;
   if ((parts & 2) && !wg_rides) {
     if (x != nullptr) {
       if (int e = dc_conv_wgrad(&d, N, Hi, Wi, x, ldx, ws.dP, HEAD_NP, ws.slabs, ws.slab_bytes, ws.tmp, stream)) return e;
@@ -1236,7 +1230,7 @@ extern "C" int dc_head_bwd_bnin(int dtype, int N, int Cin, int Hi, int Wi, const
 extern "C" int dc_head_bwd_bnin_apply(int dtype, int N, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale, const float* shift,
                                       int relu, const float* gamma, const float* bn_mean, const float* bn_invstd, const float* dgamma,
                                       const float* dbeta, long count, void* dy, int lddy, void* workspace, void* stream) {
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_head_dgrad_fused, "dc_head_bwd_bnin_apply: served by the streaming data-gradient kernel only (bf16, 256 channels)");
+  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_dgrad_fused, "dc_head_bwd_bnin_apply: served by the streaming data-gradient kernel only (bf16, 256 channels)");
   DC_REQUIRE(y && gamma && bn_mean && bn_invstd && dgamma && dbeta && workspace && N > 0 && count > 0 && (!relu || (scale && shift)),
              "dc_head_bwd_bnin_apply: bad argument");
   DC_REQUIRE(((uintptr_t)workspace & 255) == 0, "dc_head_bwd_bnin_apply: workspace must be 256-byte aligned");

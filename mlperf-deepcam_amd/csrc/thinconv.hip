@@ -558,9 +558,6 @@ int launch_thin_wgrad(const dc_conv_desc& d, int N, int Hi, int Wi, const void* 
 
 // Gather-form forward / data gradient of a thin 3x3 convolution (see thin_fwd_kernel).  `slab_rows` is the row count the caller's
 // statistics slab was sized for (dc_conv_stat_rows); rows this kernel does not write are zeroed.
-static int g_thin_tile = 1;      // tuning switch "thin_tile": 0 = the gather-form kernel for the stride-1 layers too
-void thin_set_tile(int v) { g_thin_tile = v ? 1 : 0; }
-
 bool thin_fwd_eligible(const GatherGeom& g, int dtype, int bias, int accumulate, int out32) {
   if (dtype != DC_BF16 || bias || accumulate || out32 || g.os != 1 || g.ntaps != 9) return false;
   return (g.Cin == 16 && g.Cout == 32) || (g.Cin == 32 && g.Cout == 64) || (g.Cin == 64 && g.Cout == 32);
@@ -577,7 +574,7 @@ int launch_thin_fwd(const GatherGeom& g, int N, const void* in, int ldin, const 
   a.div_hw = make_fastdiv(g.Hout * g.Wout);
   a.div_w = make_fastdiv(g.Wout);
   // stride 1 with every tap one pixel away at most (the 3 x 3 "same" convolution and its data gradient): the LDS-tiled kernel
-  bool tiled = g_thin_tile && g.is == 1 && g.Cin != 16;
+  bool tiled = g_options.thin_tile && g.is == 1 && g.Cin != 16;
   for (int t = 0; t < 9; ++t) tiled = tiled && a.tdy[t] >= -1 && a.tdy[t] <= 1 && a.tdx[t] >= -1 && a.tdx[t] <= 1;
   const int chunks = tiled ? N * cdiv(g.Hout, 2) * cdiv(g.Wout, 64) : cdiv(a.M, 256);
   const int wgs = !tiled ? 1024 : 256 * (g.Cin == 32 ? ThinTile<32, 64>::WGS_PER_CU : ThinTile<64, 32>::WGS_PER_CU);

@@ -31,8 +31,6 @@ constexpr int WG384_MAXL = 16;
 bool wgrad384_eligible(const GatherGeom& g, int ldx, int lddy, long M);
 bool wgrad384_is_tconv(const GatherGeom& g);
 void wgrad384_plan(const GatherGeom& g, long M, int* splits, int* chunk, int group = 1);
-void wgrad384_set_slots(int n);
-void wgrad384_set_min_stages(int n);
 int launch_wgrad384(const WgradParams& p, hipStream_t st, int group = 1, const void* const* xs = nullptr, const void* const* dys = nullptr,
                     float* const* outs = nullptr);
 

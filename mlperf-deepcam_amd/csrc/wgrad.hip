@@ -426,7 +426,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 constexpr int WGRAD384_FILL = 66;          // fewest percent of a 384-wide tile row a pointwise layer's input channels must fill
-static int g_wgrad384 = 1;                 // 256 x 384 pointwise kernel: 0 never, 1 planner, 2 wherever eligible (tests)
 constexpr int WGRAD_TARGET_BLOCKS = 768;   // resident capacity: 256 CUs x 3 workgroups (48 KiB LDS, 146 registers)
 
 // Fewest K steps (of BP pixels) a pixel split may have.  Every split costs a 64 KiB fp32 slab
@@ -451,33 +450,18 @@ static void plan_splits(const GatherGeom& g, long M, int BP, int* splits, int* c
 
 using namespace dc;
 
-extern "C" int dc_wgrad_set_384(int m) {
-  g_wgrad384 = m;
-  return 0;
-}
-extern "C" int dc_wgrad_set_384_slots(int n) {
-  if (n < 1) return dc_fail("dc_set_option: wgrad384_slots must be positive", __FILE__, __LINE__);
-  wgrad384_set_slots(n);
-  return 0;
-}
-extern "C" int dc_wgrad_set_384_min_stages(int n) {
-  if (n < 1) return dc_fail("dc_set_option: wgrad384_min_stages must be positive", __FILE__, __LINE__);
-  wgrad384_set_min_stages(n);
-  return 0;
-}
-
 // (Round 6: the 256 x 256 weight-gradient kernel of rounds 2 - 4, wgrad256.hip, served one launch per step after wgrad384.hip took the pointwise,
 // 3 x 3 and transposed layers; with that launch on the 128-tile kernel the step is the same -- 31.14 against 31.17 ms -- and the file is gone.)
 // Pointwise layers whose input-channel extent pads no more on 384-wide tiles than on 256-wide ones go to the 256 x 384 kernel (wgrad384.hip)
 static bool wgrad384_wins(const GatherGeom& g) {
-  if (g_wgrad384 == 0 || !wgrad384_eligible(g, 0, 0, 0)) return false;
-  if (g_wgrad384 == 2) return true;
+  if (g_options.wgrad384 == 0 || !wgrad384_eligible(g, 0, 0, 0)) return false;
+  if (g_options.wgrad384 == 2) return true;
   if (wgrad384_is_tconv(g))      // ConvTranspose2d: x is the 256-wide linear operand, [tap][dy channel] the gathered axis; "wgrad384" = 4: off
-    return g_wgrad384 != 3 && g_wgrad384 != 4 && g.Cout >= 64 && (long)cdiv(g.Cin, 256) * 256 * 3 <= (long)g.Cin * 4;
+    return g_options.wgrad384 != 3 && g_options.wgrad384 != 4 && g.Cout >= 64 && (long)cdiv(g.Cin, 256) * 256 * 3 <= (long)g.Cin * 4;
   if (g.ntaps > 1) {
     // 3 x 3 "same" convolutions: the x axis is [tap][ci] in quads of 64 channels, so any input width fills the 384-wide tiles to within
     // half a tile (304 -> 256: 45 quads = 7.5 tiles); the layer must fill the 256 output channels of a tile to three quarters
-    return g_wgrad384 != 3 && g.Cin >= 64 && (long)cdiv(g.Cout, 256) * 256 * 3 <= (long)g.Cout * 4;
+    return g_options.wgrad384 != 3 && g.Cin >= 64 && (long)cdiv(g.Cout, 256) * 256 * 3 <= (long)g.Cout * 4;
   }
   // pointwise: the x axis in quads of 64 channels must fill its 384-wide tiles to WGRAD384_FILL percent (256 channels: 4 of 6 quads = 67 %),
   // the output channels their 256-wide tiles to three quarters

@@ -43,13 +43,8 @@ constexpr int IPW = NI / 8;               // per wave: 5 (instructions 0, 1: dy 
 constexpr int NCB = 12;                   // ci blocks of 16 per wave
 constexpr int NPB = 4;                    // co blocks of 16 per wave
 constexpr int LATE = NCB - 1 - IPW;       // first block in which waves 4..7 issue their LDS-DMAs
-#ifndef DC_WG384_STAGES
-#define DC_WG384_STAGES 4                 // ring stages (4 x 40 KiB = the CU's whole LDS: three stages in flight)
-#endif
-constexpr int NST = DC_WG384_STAGES;
-#ifndef DC_WG384_AUX
-#define DC_WG384_AUX 0                    // cache policy bits of the LDS-DMA (experiments: 2 = nt)
-#endif
+constexpr int NST = 4;                    // ring stages (4 x 40 KiB = the CU's whole LDS: three stages in flight)
+constexpr int DMA_AUX = 0;                // cache policy bits of the LDS-DMA (experiments: 2 = nt)
 static_assert(NI % 8 == 0 && NST * STAGE <= 160 * 1024 && NST >= 3, "ring");
 
 static __device__ __attribute__((aligned(256))) unsigned char wg384_zero_page[256];
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(512) void wgrad384_kernel(const Wg384Params p) {
       if constexpr (MODE == 2) ok &= ((unsigned)(2 * oy + tdy[k]) < (unsigned)gh) & ((unsigned)(2 * ox + tdx[k]) < (unsigned)gw);
       a = xcur + xoff[k] + lsrc_x;
     }
-    __builtin_amdgcn_global_load_lds((gas_ptr)(ok ? a : zp), (lds_ptr)(smem + slot * STAGE + (8 * i + wave) * 1024), 16, 0, DC_WG384_AUX);
+    __builtin_amdgcn_global_load_lds((gas_ptr)(ok ? a : zp), (lds_ptr)(smem + slot * STAGE + (8 * i + wave) * 1024), 16, 0, DMA_AUX);
   };
   auto advance = [&]() {
     dcur += dstep;
@@ -211,10 +206,8 @@ __global__ __launch_bounds__(512) void wgrad384_kernel(const Wg384Params p) {
     }
   };
 
-#ifndef DC_LATE_PRIO
-#define DC_LATE_PRIO 1      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
-#endif
-  if (DC_LATE_PRIO && late) __builtin_amdgcn_s_setprio(DC_LATE_PRIO);
+  constexpr int LATE_PRIO = 1;      // the second-dispatched wave of every SIMD loses each arbitration at equal priority (igemm224.hip: 1 965 -> 1 924 cycles per step)
+  if (late) __builtin_amdgcn_s_setprio(LATE_PRIO);
   f32x4 acc[NCB][NPB];   // [ci block][co block]
 #pragma unroll
   for (int i = 0; i < NCB; ++i)
@@ -349,18 +342,14 @@ bool wgrad384_eligible(const GatherGeom& g, int ldx, int lddy, long M) {
   return true;
 }
 
-static int g_wgrad384_slots = 192;
-static int g_wgrad384_min_stages = 96;
-void wgrad384_set_slots(int n) { g_wgrad384_slots = n < 1 ? 1 : n; }
-void wgrad384_set_min_stages(int n) { g_wgrad384_min_stages = n < 4 ? 4 : n; }
 static long wgrad384_tiles(const GatherGeom& g) {
   if (wgrad384_is_tconv(g)) return (long)cdiv((long)g.ntaps * cdiv(g.Cout, 64), 6) * cdiv(g.Cin, TCO);     // gathered axis: [tap][dy channel]
   return (long)cdiv((long)g.ntaps * cdiv(g.Cin, 64), 6) * cdiv(g.Cout, TCO);
 }
 void wgrad384_plan(const GatherGeom& g, long M, int* splits, int* chunk, int group) {
   const long tiles = wgrad384_tiles(g) * group;
-  long want = g_wgrad384_slots / tiles;
-  const long per = (long)g_wgrad384_min_stages * BP;
+  long want = g_options.wgrad384_slots / tiles;
+  const long per = (long)g_options.wgrad384_min_stages * BP;
   const long maxs = (M + per - 1) / per;
   if (want > maxs) want = maxs;
   if (want < 1) want = 1;

@@ -90,11 +90,13 @@ def test_torch_custom_ops_are_registered():
 
 
 def test_option_defaults_table_is_accepted():
-    """dc_reset_options applies the library's table of switch defaults through dc_set_option itself: every name in it must be a switch the
-    library knows (no GPU needed: the switches are host-side state)."""
+    """dc_reset_options puts every switch back to its default, and dc_set_option refuses unknown names and out-of-range values (no GPU
+    needed: the switches are host-side state)."""
     from mlperf_deepcam_amd import lib as L
     assert L.load().dc_reset_options() == 0, L.last_error()
     assert L.load().dc_set_option(b"no_such_switch", 1) != 0
+    assert L.load().dc_set_option(b"wgrad384_slots", 0) != 0
+    assert "wgrad384_slots must be positive" in L.last_error()
 
 
 # Switches whose A/B rounds are over: the default was hard-wired and the other side deleted
