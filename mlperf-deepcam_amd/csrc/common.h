@@ -114,6 +114,10 @@ struct Options {
 };
 extern Options g_options;
 
+// 256 zero bytes in device memory, one page for every launcher that passes the address as a kernel argument (igemm.hip); *err: hipSuccess or
+// why the address could not be resolved.  Host function, callable from any thread.
+const void* zero_page(hipError_t* err);
+
 }  // namespace dc
 
 // One-time, thread-safe set-up at a call site (the dynamic-LDS attribute of a kernel, a symbol address): the C ABI may be called from

@@ -22,6 +22,7 @@
 #include "dwtile.h"
 #include "dwtile_common.h"
 #include "bn_fin.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -79,9 +80,6 @@ struct DwpArgs {
   float* slab2;         // [2][st.rows][C]
   int sum_row, sum_row2; // the BatchNorm sums (st.slab / slab2) go to a SUM ROW, double[2][C] (bn_fin.h), by fp64 atomics instead of a row per workgroup
 };
-
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 template <int N>
 __device__ inline void wait_vm() {

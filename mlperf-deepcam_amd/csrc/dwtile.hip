@@ -16,6 +16,7 @@
 #include "dwtile.h"
 #include "dwtile_common.h"
 #include "bn_fin.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -34,8 +35,6 @@ struct TileCfg {
 };
 
 static __device__ __attribute__((aligned(256))) unsigned char dwt_zero_page[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 template <typename T, int DIL, int CG>
 __device__ inline void stage_halo(char* smem, const T* __restrict__ in, int ldin, int n, int y0, int x0, int cg0, int ngroups, int H,

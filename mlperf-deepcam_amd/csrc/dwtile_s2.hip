@@ -9,14 +9,13 @@
 // same tensors (the weight gradient of the 128-channel layer: 516 us against ~115 us of traffic).
 #include "dwtile.h"
 #include "dwtile_common.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
 namespace {
 
 static __device__ __attribute__((aligned(256))) unsigned char dws2_zero_page[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 template <int CG, int TH_>
 struct S2Cfg {

@@ -43,7 +43,7 @@ struct IgemmParams {
                    // 256-tile launch over [0, m_beg') and a 128-tile launch over [m_beg', M)
   int mtiles;  // 128-pixel tiles per phase of the WHOLE layer (= rows per phase of the statistics slab)
   int accumulate = 0;
-  const void* zero_page = nullptr;   // 256 zero bytes in device memory (set by the 256-tile launcher)
+  const void* zero_page = nullptr;   // 256 zero bytes in device memory: dc::zero_page(), set by the launcher
   // 256-tile kernel, grouped launch (dc_conv_fwd_dilated_group): `ngroup` "same" dilated 3x3 convolutions of ONE input share the
   // launch.  g holds the unit-dilation tap table (dy, dx in {-1,0,1}); member b gathers at dy*gdil[b], dx*gdil[b], multiplies
   // by gw[b] and writes gy[b] / gslab[b].  Member 0 is (w, y, slab) above with gdil[0].  ngroup <= 1: plain launch.

@@ -16,6 +16,7 @@
 
 #include "conv_geom.h"
 #include "igemm.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -49,10 +50,7 @@ struct Mma<float> {
 __device__ inline int swz(int row, int slot) { return row * ROWB + ((slot ^ ((row >> 1) & 3)) << 4); }   // 4 slots per row
 
 // 16 zero bytes in global memory: the source of every predicated-off LDS-DMA lane (zero fill of halos, K and M tails)
-static __device__ __attribute__((aligned(256))) unsigned char dc_zero_page[256];   // (each translation unit has its own copy)
-
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
+static __device__ __attribute__((aligned(256))) unsigned char dc_zero_page[256];   // (the kernels that name their page as a symbol each have their own)
 
 // Operand tiles are staged with the gfx950 LDS-DMA (global_load_lds_dwordx4: global -> LDS without passing through
 // VGPRs and without ds_write instructions, which at ~79 B/clk/CU were the bottleneck of a register-staged loop).
@@ -826,6 +824,17 @@ extern "C" int dc_pack_all(int dtype, const void* table_dev, int nentries, void*
 }
 
 Options dc::g_options;
+
+// The zero page of the launchers that hand its address to their kernel in the argument struct (the source of every predicated-off LDS-DMA lane).
+static __device__ __attribute__((aligned(256))) unsigned char dc_arg_zero_page[256];
+
+const void* dc::zero_page(hipError_t* err) {
+  static void* dev = nullptr;
+  static hipError_t init_err = hipSuccess;
+  DC_ONCE({ init_err = hipGetSymbolAddress(&dev, HIP_SYMBOL(dc_arg_zero_page)); });
+  *err = init_err;
+  return dev;
+}
 
 // dc_set_option's names for the members of dc::Options (common.h), and how each stores a value: as given, as a flag (v != 0), clamped, or
 // refused below 1 (kStages: then at least 4).  dc_reset_options puts the member initialisers back (the test suite calls it after every test,

@@ -13,12 +13,10 @@
 //             (waves 0..3 issue theirs in the first 32-deep half of a stage, waves 4..7 in the second); XOR swizzle as igemm384.hip
 //   loop      per half: per channel block the weight fragment two blocks ahead (ds_read_b128), one LDS-DMA, two MFMAs; counted
 //             lgkmcnt / vmcnt, ONE barrier per stage
-//   epilogue  igemm384.hip's register epilogue (lane-pair exchange, 16-byte stores, BatchNorm sums by DPP folded through LDS into the
+//   epilogue  the register epilogue of pw_epilogue.h (lane-pair exchange, 16-byte stores, BatchNorm sums by DPP folded through LDS into the
 //             one 128-pixel slab row of the workgroup)
 // Outputs are bit-identical to the other tile shapes (same MFMA, same K order); BatchNorm sums differ in summation order only.
-#include <type_traits>
-
-#include "igemm.h"
+#include "pw_epilogue.h"
 
 namespace dc {
 
@@ -38,38 +36,6 @@ constexpr int NSTG = 4;                // ring stages (4 x 40 KiB = the CU's who
 constexpr int RING = NSTG * STAGE;
 constexpr int BLK = 16 * RB;           // bytes between the fragments of consecutive 16-row blocks
 static_assert(NI % 8 == 0 && IPW <= NCB && RING <= 160 * 1024 && NSTG >= 3 && NCB % 3 == 0 && NCB % 2 == 0, "configuration");
-
-static __device__ __attribute__((aligned(256))) unsigned char zero_page192[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ inline uint32_t swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-__device__ inline float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-__device__ inline void mfma_v(f32x4& c, const bf16x8& av, const bf16x8& bv) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-}
-template <int OFF>
-__device__ inline void lds_read16(bf16x8& dst, uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ inline void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int I, int N, typename F>
-__device__ inline void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 __global__ __launch_bounds__(512) void pw192_kernel(const IgemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -183,77 +149,12 @@ __global__ __launch_bounds__(512) void pw192_kernel(const IgemmParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");   // the zero-page fills of the last slots; the ring is reused below
   __builtin_amdgcn_s_barrier();
 
-  // ---- epilogue from the accumulator registers (igemm384.hip) --------------------------------------------------------------------
-  const bool odd = fg & 1;
-  bf16* __restrict__ yg = reinterpret_cast<bf16*>(p.y);
+  // ---- epilogue from the accumulator registers (pw_epilogue.h): channel blocks 2 pr and 2 pr + 1 of the wave trade halves --------------
   const bool do_stats = p.slab != nullptr;
   float* red = reinterpret_cast<float*>(smem);      // [pixel group][sum, sum of squares][192]
 #pragma unroll
-  for (int pr = 0; pr < NCB / 2; ++pr) {
-    const int i0 = 2 * pr;
-    const int chl = wc * (NCB * 16) + (i0 + (odd ? 1 : 0)) * 16 + (fg >> 1) * 8;   // first of this lane's 8 channels after the trade
-    const int ch0 = n0 + chl;
-    const bool chok = ch0 < g.Cout;                                               // Cout is a multiple of 8: all or nothing
-    float ba[4] = {0.f, 0.f, 0.f, 0.f}, bb[4] = {0.f, 0.f, 0.f, 0.f};             // bias of the channels this lane COMPUTED
-    if (p.bias != nullptr) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ca = n0 + wc * (NCB * 16) + i0 * 16 + fg * 4 + r, cb = ca + 16;
-        if (ca < g.Cout) ba[r] = p.bias[ca];
-        if (cb < g.Cout) bb[r] = p.bias[cb];
-      }
-    }
-    float st[2][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) st[0][e] = st[1][e] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPB; ++j) {
-      const int m = m0 + grp * (NPB * 16) + j * 16 + fr;
-      const uint32_t a0 = pack2_bf16(acc[i0][j][0] + ba[0], acc[i0][j][1] + ba[1]);
-      const uint32_t a1 = pack2_bf16(acc[i0][j][2] + ba[2], acc[i0][j][3] + ba[3]);
-      const uint32_t b0 = pack2_bf16(acc[i0 + 1][j][0] + bb[0], acc[i0 + 1][j][1] + bb[1]);
-      const uint32_t b1 = pack2_bf16(acc[i0 + 1][j][2] + bb[2], acc[i0 + 1][j][3] + bb[3]);
-      const uint32_t r0 = swap_rows16(odd ? a0 : b0), r1 = swap_rows16(odd ? a1 : b1);
-      vec16 v;
-      v.w[0] = odd ? r0 : a0;
-      v.w[1] = odd ? r1 : a1;
-      v.w[2] = odd ? b0 : r0;
-      v.w[3] = odd ? b1 : r1;
-      if (m < p.M && chok) {
-        bf16* dst = yg + (size_t)m * p.ldy + ch0;
-        float f[8];
-        unpack(v, f, bf16());
-        if (p.accumulate) {
-          float o[8];
-          unpack(ldg16(dst), o, bf16());
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] += o[e];
-          pack(v, f, bf16());
-          unpack(v, f, bf16());
-        }
-        stg16(dst, v);
-        if (do_stats) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            st[0][e] += f[e];
-            st[1][e] = fmaf(f[e], f[e], st[1][e]);
-          }
-        }
-      }
-    }
-    if (do_stats) {
-      // sums over the 16 pixel lanes of a DPP row; lane fr of the row keeps value fr (which = fr >> 3, channel e = fr & 7)
-      float mine = 0.f;
-#pragma unroll
-      for (int w = 0; w < 2; ++w)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float t = row_sum16(st[w][e]);
-          if (fr == w * 8 + e) mine = t;
-        }
-      red[(grp * 2 + (fr >> 3)) * TN + chl + (fr & 7)] = mine;
-    }
-  }
+  for (int pr = 0; pr < NCB / 2; ++pr)
+    pw_epilogue_pair<TN>(p, acc, 2 * pr, n0, wc * (NCB * 16) + pr * 32, m0 + grp * (NPB * 16), grp, fr, fg, red);
   if (do_stats) {
     __syncthreads();
     // the workgroup's 128 pixels are ONE slab row: the four pixel groups folded in a fixed order
@@ -273,17 +174,11 @@ __global__ __launch_bounds__(512) void pw192_kernel(const IgemmParams p) {
 long pw192_tiles(const IgemmParams& p) { return (long)((p.g.Cout + TN - 1) / TN) * ((p.M + TM - 1) / TM); }
 
 int launch_pw192(const IgemmParams& p_in, hipStream_t st) {
-  static const void* zero_dev = nullptr;
-  static hipError_t init_err = hipSuccess;
-  DC_ONCE({
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw192_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RING);
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(zero_page192));
-    zero_dev = zp;
-  });
-  if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
+  DC_ONCE({ (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw192_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RING); });
   IgemmParams p = p_in;
-  p.zero_page = zero_dev;
+  hipError_t zerr;
+  p.zero_page = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   hipLaunchKernelGGL(pw192_kernel, dim3((unsigned)pw192_tiles(p)), dim3(512), RING, st, p);
   DC_CHECK_LAUNCH();
   return 0;

@@ -30,9 +30,8 @@
 //             The last two steps issue nothing and wait vmcnt(0); pixel stages past the K extent are filled with zeros (every lane out of range).
 //   slab      BatchNorm partial sums: ONE row per tile (row = the tile's pixel-tile index) in the layer's usual slab of cdiv(M, 128) rows; the
 //             rows no tile owns are written as zeros by the first tiles, so the finalize kernels need not know the tile shape.
-#include <type_traits>
-
 #include "igemm.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -42,29 +41,10 @@ constexpr int NWS = 3, NPS = 3;              // ring depths
 constexpr int NPB = 7;                       // pixel blocks of 16 per wave
 constexpr int PW224_AUXP = 0;                // cache-policy bits of the pixel LDS-DMA (nt: 2 101 cycles per step against 1 924)
 
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-__device__ inline uint32_t swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-__device__ inline float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
-// MFMA, LDS fragment reads and their waits as (volatile) statements in one hand-placed order (igemm384.hip explains why)
-__device__ inline void mfma_v(f32x4& c, const bf16x8& av, const bf16x8& bv) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-}
-template <int OFF>
-__device__ inline void lds_read16(bf16x8& dst, uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
+// MFMA, LDS fragment reads and their waits are (volatile) statements in one hand-placed order (mfma_tile.h explains why)
 // one A fragment (16 channels x 32 k, channel per lane) = two transposing reads: k rows 8 fg .. + 3 and 8 fg + 4 .. + 7 (512 B apart)
 template <int OFF>
 __device__ inline void lds_read_tr(u32x4& dst, uint32_t addr) {
@@ -75,20 +55,8 @@ __device__ inline void lds_read_tr(u32x4& dst, uint32_t addr) {
   dst[0] = lo[0]; dst[1] = lo[1]; dst[2] = hi[0]; dst[3] = hi[1];
 }
 template <int N>
-__device__ inline void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
 __device__ inline void vm_lgkm0_wait() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-template <int I, int N, typename F>
-__device__ inline void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
 }
 
 // TN: channels per workgroup, 384 (six quads of 64; a wave owns 96 = six blocks of 16) or 192 (three quads; a wave owns 48 = three blocks):
@@ -321,7 +289,8 @@ __global__ __launch_bounds__(512) void pw224_kernel(const IgemmParams p) {
 
   __builtin_amdgcn_s_barrier();
 
-  // ---- epilogue from the accumulator registers (igemm384.hip's) -------------------------------------------------------------------
+  // ---- epilogue from the accumulator registers: the steps of pw_epilogue.h, written out here (on the shared function the 224 x 384 tile
+  // measured 1.5 - 3 % slower per call, profiles/r07_ab_pw_epilogue.txt) -------------------------------------------------------------
   // A lane holds, per MFMA tile (i, j), channels fg*4 .. +3 of channel block i for pixel fr of pixel block j.  Blocks 2 pr and 2 pr + 1 are the
   // two halves of one 32-channel chunk pair: lanes l and l ^ 16 trade halves so that the even-fg lane keeps 8 consecutive channels of block
   // 2 pr and the odd-fg lane 8 of block 2 pr + 1 (64 contiguous bytes per pixel and store instruction).

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "igemm.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -36,26 +37,6 @@ constexpr int RING = NSTAGE * STAGE;   // 128 KiB
 constexpr int CROW = TN * 2 + 16;      // padded C-tile row (bytes)
 constexpr int CTILE = TM * CROW;       // 132 KiB
 constexpr int MAIN_BYTES = RING > CTILE ? RING : CTILE;
-
-static __device__ __attribute__((aligned(256))) unsigned char zero_page256[256];
-// the address travels in the kernel arguments (an SGPR pair): reading the symbol in the loop costs a GOT load + s_waitcnt per use
-__device__ inline const void* zero_page256_ptr(const IgemmParams& p) { return p.zero_page; }
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ inline int swz64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 1) & 3)) << 4); }
-
-// ---- helpers of the register epilogue ---------------------------------------------------------------------------------------
-// lane ^ 16 exchange (the two 16-lane rows of a 32-lane half swap): ds_swizzle in bit-mask mode, no LDS memory involved
-__device__ inline uint32_t swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-// sum over the 16 lanes of a DPP row (xor 1, xor 2, half mirror, mirror): every lane ends with the same bits
-__device__ inline float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
 
 __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -147,7 +128,8 @@ __global__ __launch_bounds__(512) void igemm256_kernel(const IgemmParams p) {
   int tapA = -1, tapB = -1;
   // Every lane's source is either its operand row or the zero page (K tail, image border, rows past M / Cout, and the dummy
   // fills past the last stage); the choice is a select on the address, never a branch: the L segments must stay short.
-  const uintptr_t zp = (uintptr_t)zero_page256_ptr(p);
+  // (the zero page's address travels in the kernel arguments, an SGPR pair: reading a symbol in the loop costs a GOT load + s_waitcnt per use)
+  const uintptr_t zp = (uintptr_t)p.zero_page;
   auto pick = [&](bool ok, const bf16* a) { return (gas_ptr)(ok ? (uintptr_t)a : zp); };
   // weight half of a stage: 2 LDS-DMA instructions per wave
   auto issue_A = [&](int tapi, int kc, int slot, bool live) {
@@ -564,17 +546,11 @@ int igemm256_splitk_plan(const IgemmParams& p, size_t* slab_bytes) {
 
 int launch_igemm256(const IgemmParams& p_in, hipStream_t st) {
   const size_t lds = (size_t)MAIN_BYTES + 128;
-  static const void* zero_dev = nullptr;
-  static hipError_t init_err = hipSuccess;
-  DC_ONCE({
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(zero_page256));
-    zero_dev = zp;
-  });
-  if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
+  DC_ONCE({ (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
   IgemmParams p = p_in;
-  p.zero_page = zero_dev;
+  hipError_t zerr;
+  p.zero_page = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   hipLaunchKernelGGL(igemm256_kernel, dim3((unsigned)(igemm256_tiles(p) * (p.ksplit > 1 ? p.ksplit : 1))), dim3(512), lds, st, p);
   DC_CHECK_LAUNCH();
   return 0;

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "igemm.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -30,20 +31,7 @@ constexpr int STAGE = 2 * OPER;
 constexpr int RING = NSTAGE * STAGE;   // 128 KiB
 constexpr int KG = 4;                  // channel chunks per tap sweep (igemm256.hip)
 
-static __device__ __attribute__((aligned(256))) unsigned char zero_page256p[256];
 static __device__ __attribute__((aligned(256))) unsigned char dump_page256p[256 * 64];   // inactive epilogue lanes store here (per lane 256 B)
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ inline int swz64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 1) & 3)) << 4); }
-__device__ inline uint32_t swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-__device__ inline float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
 
 struct TileInfo {
   int n0, m0, phase, tap_beg, ntap;
@@ -449,7 +437,6 @@ bool igemm256p_eligible(const IgemmParams& p) {
 
 int launch_igemm256p(const IgemmParams& p_in, int workgroups, hipStream_t st) {
   const size_t lds = (size_t)RING + 256;
-  static const void* zero_dev = nullptr;
   static const void* dump_dev = nullptr;
   static hipError_t init_err = hipSuccess;
   auto k0 = &igemm256p_kernel<false>;
@@ -457,15 +444,14 @@ int launch_igemm256p(const IgemmParams& p_in, int workgroups, hipStream_t st) {
   DC_ONCE({
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(zero_page256p));
-    zero_dev = zp;
-    if (init_err == hipSuccess) {
-      init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(dump_page256p));
-      dump_dev = zp;
-    }
+    void* dp = nullptr;
+    init_err = hipGetSymbolAddress(&dp, HIP_SYMBOL(dump_page256p));
+    dump_dev = dp;
   });
   if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
+  hipError_t zerr;
+  const void* zero_dev = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   const GatherGeom& g = p_in.g;
   Igemm256pArgs a;
   a.x = p_in.x;

@@ -20,21 +20,18 @@
 //             ahead, four MFMAs; the pixel fragments of the next step are re-read in place right after their last use (last block).
 //             The two waves of a SIMD issue their LDS-DMAs in different halves of the step, so one multiplies while the other is
 //             held at an LDS-DMA.  ONE barrier per step, in front of the last channel block: behind it stage s+1 is visible to every wave.
-//             LDS reads, MFMAs and their waits are inline assembly: the compiler's s_waitcnt placement waits lgkmcnt(0) in front of
-//             every block of MFMAs, i.e. also for the fragment just requested for the NEXT block (one exposed LDS latency per block).
+//             LDS reads, MFMAs and their waits are inline assembly (mfma_tile.h explains why).
 //   hazards   RAW: a wave waits vmcnt(IPW) (its own LDS-DMAs of stage s+1 have landed; the IPW issued during this step stay in
 //             flight) before the barrier; stage s+1 is first read behind it.  WAR: slot (s+2) % 3 held stage s-1, whose last reads
 //             (the last weight fragment, requested one block before the barrier of step s-1) every wave retired (lgkmcnt(0)) before
 //             that barrier; the first DMA into the slot is issued in step s.  Past the last stage the DMA slots are filled from the
 //             zero page, so the vmcnt arithmetic is the same in every step.
-//   epilogue  from the accumulator registers (the lane-pair exchange of igemm256.hip's register epilogue: 16-byte stores, 64
-//             contiguous bytes per pixel and instruction), optional bias / accumulate; BatchNorm partial sums of the STORED values
-//             by DPP over the 16 pixel lanes, folded through LDS into the same slab rows (one per 128 pixels) as the other kernels.
+//   epilogue  from the accumulator registers (pw_epilogue.h: lane-pair exchange, 16-byte stores, 64 contiguous bytes per pixel and
+//             instruction, optional bias / accumulate; BatchNorm partial sums of the STORED values by DPP over the 16 pixel lanes),
+//             folded through LDS into the same slab rows (one per 128 pixels) as the other kernels.
 // Outputs are bit-identical to the 256 x 256 and 128 x 128 kernels (same MFMA, same K order); the BatchNorm partial sums differ
 // in summation order only (scripts/pw384_bench.py).
-#include <type_traits>
-
-#include "igemm.h"
+#include "pw_epilogue.h"
 
 namespace dc {
 
@@ -45,47 +42,6 @@ constexpr int ROWB = 64;               // bytes of K per row and stage (32 bf16)
 constexpr int BK = 32;
 constexpr int NST = 3;                 // ring stages (a fourth, i.e. the CU's whole 160 KiB, measured 4 % slower on 256 x 384: 42.3 vs 40.7 us)
 constexpr int NPB = 4;                 // pixel blocks of 16 per wave
-
-static __device__ __attribute__((aligned(256))) unsigned char zero_page384[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ inline int swz64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 1) & 3)) << 4); }
-__device__ inline uint32_t swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-__device__ inline float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
-// MFMA as a (volatile) statement: keeps its place between the hand-placed LDS reads and waits below.
-__device__ inline void mfma_v(f32x4& c, const bf16x8& av, const bf16x8& bv) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-}
-
-// LDS fragment reads and their waits are written out: the compiler's own s_waitcnt placement waits lgkmcnt(0) in front of every
-// block of MFMAs, i.e. also for the fragment it has just requested for the NEXT block (one exposed LDS latency per block on a
-// SIMD that has no second wave to hide it).  Reads issued here are invisible to that pass; every consumer is one of the (volatile)
-// MFMA statements above, placed behind a counted wait.
-template <int OFF>
-__device__ inline void lds_read16(bf16x8& dst, uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ inline void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int I, int N, typename F>
-__device__ inline void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 // GP: pixel groups, 4 (256 x 384 tile) or 2 (128 x 384).  K64: 128-byte K rows (whole L2 lines per LDS-DMA row piece, 8 rows per
 // wave-instruction) in a ring of TWO 64-deep stages, against 64-byte rows in a ring of three 32-deep stages.
@@ -256,79 +212,12 @@ __global__ __launch_bounds__(512) void pw384_kernel(const IgemmParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the zero-page fills of the last slots; the ring is reused below
   __builtin_amdgcn_s_barrier();
 
-  // ---- epilogue from the accumulator registers --------------------------------------------------------------------------------
-  // A lane holds, per MFMA tile (i, j), channels fg*4 .. +3 of channel block i for pixel fr of pixel block j: 8 bytes.  Lanes l and
-  // l ^ 16 trade halves so that the even-fg lane keeps 8 consecutive channels of block i and the odd-fg lane 8 of block i + 1.
-  const bool odd = fg & 1;
-  bf16* __restrict__ yg = reinterpret_cast<bf16*>(p.y);
+  // ---- epilogue from the accumulator registers (pw_epilogue.h): channel blocks 2 pr and 2 pr + 1 of the wave trade halves --------------
   const bool do_stats = p.slab != nullptr;
   float* red = reinterpret_cast<float*>(smem);      // [pixel group][sum, sum of squares][384]
 #pragma unroll
-  for (int pr = 0; pr < NCB / 2; ++pr) {
-    const int i0 = 2 * pr;
-    const int chl = wc * (NCB * 16) + (i0 + (odd ? 1 : 0)) * 16 + (fg >> 1) * 8;   // first of this lane's 8 channels after the trade
-    const int ch0 = n0 + chl;
-    const bool chok = ch0 < g.Cout;                                               // Cout is a multiple of 8: all or nothing
-    float ba[4] = {0.f, 0.f, 0.f, 0.f}, bb[4] = {0.f, 0.f, 0.f, 0.f};             // bias of the channels this lane COMPUTED
-    if (p.bias != nullptr) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ca = n0 + wc * (NCB * 16) + i0 * 16 + fg * 4 + r, cb = ca + 16;
-        if (ca < g.Cout) ba[r] = p.bias[ca];
-        if (cb < g.Cout) bb[r] = p.bias[cb];
-      }
-    }
-    float st[2][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) st[0][e] = st[1][e] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPB; ++j) {
-      const int m = m0 + grp * (NPB * 16) + j * 16 + fr;
-      const uint32_t a0 = pack2_bf16(acc[i0][j][0] + ba[0], acc[i0][j][1] + ba[1]);
-      const uint32_t a1 = pack2_bf16(acc[i0][j][2] + ba[2], acc[i0][j][3] + ba[3]);
-      const uint32_t b0 = pack2_bf16(acc[i0 + 1][j][0] + bb[0], acc[i0 + 1][j][1] + bb[1]);
-      const uint32_t b1 = pack2_bf16(acc[i0 + 1][j][2] + bb[2], acc[i0 + 1][j][3] + bb[3]);
-      const uint32_t r0 = swap_rows16(odd ? a0 : b0), r1 = swap_rows16(odd ? a1 : b1);
-      vec16 v;
-      v.w[0] = odd ? r0 : a0;
-      v.w[1] = odd ? r1 : a1;
-      v.w[2] = odd ? b0 : r0;
-      v.w[3] = odd ? b1 : r1;
-      if (m < p.M && chok) {
-        bf16* dst = yg + (size_t)m * p.ldy + ch0;
-        float f[8];
-        unpack(v, f, bf16());
-        if (p.accumulate) {
-          float o[8];
-          unpack(ldg16(dst), o, bf16());
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] += o[e];
-          pack(v, f, bf16());
-          unpack(v, f, bf16());
-        }
-        stg16(dst, v);
-        if (do_stats) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            st[0][e] += f[e];
-            st[1][e] = fmaf(f[e], f[e], st[1][e]);
-          }
-        }
-      }
-    }
-    if (do_stats) {
-      // sums over the 16 pixel lanes of a DPP row; lane fr of the row keeps value fr (which = fr >> 3, channel e = fr & 7)
-      float mine = 0.f;
-#pragma unroll
-      for (int w = 0; w < 2; ++w)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float t = row_sum16(st[w][e]);
-          if (fr == w * 8 + e) mine = t;
-        }
-      red[(grp * 2 + (fr >> 3)) * TN + chl + (fr & 7)] = mine;
-    }
-  }
+  for (int pr = 0; pr < NCB / 2; ++pr)
+    pw_epilogue_pair<TN>(p, acc, 2 * pr, n0, wc * (NCB * 16) + pr * 32, m0 + grp * (NPB * 16), grp, fr, fg, red);
   if (do_stats) {
     __syncthreads();
     // one slab row per 128 pixels = two pixel groups, folded in a fixed order
@@ -355,8 +244,6 @@ bool pw384_eligible(const IgemmParams& p) {
 // npb: 8 (256-pixel tiles) or 4 (128-pixel tiles): pixel blocks of 16 per 128-pixel half, the unit pw384_tiles() counts in;
 // 64: 256-pixel tiles with 64-deep stages of 128-byte rows
 int launch_pw384(const IgemmParams& p_in, int npb, hipStream_t st) {
-  static const void* zero_dev = nullptr;
-  static hipError_t init_err = hipSuccess;
   typedef Cfg<4, false> C8;
   typedef Cfg<2, false> C4;
   typedef Cfg<4, true> C64;
@@ -367,13 +254,11 @@ int launch_pw384(const IgemmParams& p_in, int npb, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, C8::RING);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, C4::RING);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k64), hipFuncAttributeMaxDynamicSharedMemorySize, C64::RING);
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(zero_page384));
-    zero_dev = zp;
   });
-  if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
   IgemmParams p = p_in;
-  p.zero_page = zero_dev;
+  hipError_t zerr;
+  p.zero_page = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   const long tiles = pw384_tiles(p, npb == 64 ? 8 : npb);
   if (npb == 64) hipLaunchKernelGGL(k64, dim3((unsigned)tiles), dim3(512), C64::RING, st, p);
   else if (npb == 8) hipLaunchKernelGGL(k8, dim3((unsigned)tiles), dim3(512), C8::RING, st, p);

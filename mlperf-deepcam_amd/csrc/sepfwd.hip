@@ -22,6 +22,7 @@
 #include "common.h"
 #include "dwtile_common.h"
 #include "igemm.h"
+#include "mfma_tile.h"
 
 namespace dc {
 
@@ -56,18 +57,6 @@ struct SepFwdArgs {
   int N, H, W, ntx, nty, ntiles;
   const void* zero_page;
 };
-
-static __device__ __attribute__((aligned(256))) unsigned char sf_zero_page[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-__device__ inline float sf_row_sum16(float v) {      // sum over the 16 lanes of a DPP row
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));
-  return v;
-}
 
 template <int CI>
 __global__ __launch_bounds__(256) void sepconv_fwd_kernel(const SepFwdArgs a) {
@@ -189,7 +178,7 @@ __global__ __launch_bounds__(256) void sepconv_fwd_kernel(const SepFwdArgs a) {
   if (a.slab != nullptr) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float s0 = sf_row_sum16(ssum[e]), s1 = sf_row_sum16(ssq[e]);
+      const float s0 = row_sum16(ssum[e]), s1 = row_sum16(ssq[e]);
       if (fr == 0) {
         const int co = 32 * wave + 8 * fg + e;
         a.slab[((size_t)0 * a.slab_rows + blockIdx.x) * SF_CO + co] = s0;
@@ -235,16 +224,15 @@ extern "C" int dc_sepconv_fwd(int dtype, int Cin, int Cout, int N, int H, int W,
   if (int e = dc_check_view(x, ldx, Cin, dtype, "dc_sepconv_fwd x")) return e;
   if (int e = dc_check_view(d, ldd, Cin, dtype, "dc_sepconv_fwd d")) return e;
   if (int e = dc_check_view(y, ldy, Cout, dtype, "dc_sepconv_fwd y")) return e;
-  static const void* zero_dev = nullptr;
   static hipError_t init_err = hipSuccess;
   DC_ONCE({
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(sf_zero_page));
-    zero_dev = zp;
-    if (init_err == hipSuccess) init_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&sepconv_fwd_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, SfCfg<128>::LDS);
+    init_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&sepconv_fwd_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, SfCfg<128>::LDS);
     if (init_err == hipSuccess) init_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&sepconv_fwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, SfCfg<64>::LDS);
   });
   if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
+  hipError_t zerr;
+  const void* zero_dev = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   SepFwdArgs a;
   a.x = (const bf16*)x; a.ldx = ldx; a.pscale = pscale; a.pshift = pshift; a.prelu = prelu; a.wdw = wdw; a.d = (bf16*)d; a.ldd = ldd;
   a.wf = (const bf16*)wf; a.ldw = weight_ld(Cin); a.y = (bf16*)y; a.ldy = ldy; a.slab = slab; a.slab_rows = slab_rows;

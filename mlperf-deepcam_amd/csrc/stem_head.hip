@@ -3,6 +3,7 @@
 //   head  ConvTranspose2d(256->3, k3, s2, p1, op1) that reads NHWC and writes the NCHW fp32 logits of the reference API
 #include "common.h"
 #include "lds_tr_image.h"
+#include "mfma_tile.h"
 #include "wgrad.h"
 
 namespace dc {
@@ -912,16 +913,6 @@ struct HeadDgradBst {
   float* wslab;
 };
 
-__device__ inline float head_row_sum16(float v) {      // sum over the 16 lanes of a DPP row (the 16 pixels of a group)
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
-__device__ inline uint32_t head_swap_rows16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }   // lane ^ 16
-
 template <int MODE>
 __global__ __launch_bounds__(256) void head_dgrad_kernel(const bf16* __restrict__ dP, const bf16* __restrict__ wb, bf16* __restrict__ dx,
                                                          int lddx, long M, const HeadDgradBst b) {
@@ -1042,7 +1033,7 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const bf16* __restrict_
           accB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[2 * p + 1]), __builtin_bit_cast(bf16x8, fb[u]), accB, 0, 0, 0);
           const uint32_t a0 = pack2_bf16(accA[0], accA[1]), a1 = pack2_bf16(accA[2], accA[3]);
           const uint32_t b0 = pack2_bf16(accB[0], accB[1]), b1 = pack2_bf16(accB[2], accB[3]);
-          const uint32_t r0 = head_swap_rows16(odd ? a0 : b0), r1 = head_swap_rows16(odd ? a1 : b1);
+          const uint32_t r0 = swap_rows16(odd ? a0 : b0), r1 = swap_rows16(odd ? a1 : b1);
           vec16 o;
           o.w[0] = odd ? r0 : a0;
           o.w[1] = odd ? r1 : a1;
@@ -1089,7 +1080,7 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const bf16* __restrict_
       for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float t0 = head_row_sum16(s0[p][e]), t1 = head_row_sum16(s1[p][e]);
+          const float t0 = row_sum16(s0[p][e]), t1 = row_sum16(s1[p][e]);
           if (fr == 0) {
             const int c = cpair(p) + e;
             b.slab[((size_t)0 * b.rows + chunk) * CIN + c] = t0;

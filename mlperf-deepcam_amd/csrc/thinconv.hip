@@ -14,6 +14,7 @@
 //   * one partial [9][Co][Ci] per workgroup goes to the fp32 slab of wgrad.hip ([split][tap][Co][Ci]) and its fixed-order
 //     reduction kernel finishes the job (deterministic).
 #include "igemm.h"
+#include "mfma_tile.h"
 #include "wgrad.h"
 
 namespace dc {
@@ -21,8 +22,6 @@ namespace dc {
 namespace {
 
 static __device__ __attribute__((aligned(256))) unsigned char thin_zero_page[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef __attribute__((address_space(3))) short4v lds_s4;
 
 struct ThinArgs {

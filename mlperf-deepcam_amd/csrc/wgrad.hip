@@ -8,6 +8,7 @@
 // go to a slab with plain stores and a second kernel reduces them in a fixed order straight into the PyTorch
 // master layout of the gradient -- deterministic, no float atomics.
 #include "conv_geom.h"
+#include "mfma_tile.h"
 #include "wgrad.h"
 
 namespace dc {
@@ -184,8 +185,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 // transposed reads are kept conflict-free by an XOR swizzle of 32-byte chunks (64-byte chunks for fp32) applied to the
 // per-lane SOURCE address and mirrored in the fragment reads.
 static __device__ __attribute__((aligned(256))) unsigned char dc_wg_zero_page[256];
-typedef __attribute__((address_space(1))) const void* wg_gas_ptr;
-typedef __attribute__((address_space(3))) void* wg_lds_ptr;
 
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WgradParams p) {
@@ -269,8 +268,8 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WgradParams p) {
       const bool pok = mok && cp_ok[i] && (unsigned)iy < (unsigned)g.Hin && (unsigned)ix < (unsigned)g.Win;
       const void* srcq = (mok && cq_ok[i]) ? (const void*)(dg + offq[i]) : (const void*)dc_wg_zero_page;
       const void* srcp = pok ? (const void*)(xg + offp[i]) : (const void*)dc_wg_zero_page;
-      __builtin_amdgcn_global_load_lds((wg_gas_ptr)srcq, (wg_lds_ptr)(q + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((wg_gas_ptr)srcp, (wg_lds_ptr)(pp + j * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gas_ptr)srcq, (lds_ptr)(q + j * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gas_ptr)srcp, (lds_ptr)(pp + j * 1024), 16, 0, 0);
       // advance this row by BP pixels
       rqx[i] += BP;
       if (rqx[i] < g.Qw) {

@@ -24,8 +24,7 @@
 //              or -- splits == 1 -- the gradient tensor itself (no slab, no fold).
 //   grouping   up to WG384_MAXL layers of one geometry per launch (pointer table in the kernel-argument segment, read with scalar
 //              loads): the pixel axis of each is cut into fewer, longer splits or not at all.
-#include <type_traits>
-
+#include "mfma_tile.h"
 #include "wgrad.h"
 
 namespace dc {
@@ -47,9 +46,6 @@ constexpr int NST = 4;                    // ring stages (4 x 40 KiB = the CU's 
 constexpr int DMA_AUX = 0;                // cache policy bits of the LDS-DMA (experiments: 2 = nt)
 static_assert(NI % 8 == 0 && NST * STAGE <= 160 * 1024 && NST >= 3, "ring");
 
-static __device__ __attribute__((aligned(256))) unsigned char wg384_zero_page[256];
-typedef __attribute__((address_space(1))) const void* gas_ptr;
-typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
@@ -67,9 +63,6 @@ struct Wg384Params {
   float* out[WG384_MAXL];       // [split][tap][Co][Ci] per layer
 };
 
-__device__ inline void mfma_v(f32x4& c, const bf16x8& av, const bf16x8& bv) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-}
 // one MFMA operand fragment = two transposing reads (pixels 4 fg .. and 16 + 4 fg ..), 2 KiB apart
 template <int OFF>
 __device__ inline void lds_read_frag(bf16x8& dst, uint32_t addr) {
@@ -80,17 +73,6 @@ __device__ inline void lds_read_frag(bf16x8& dst, uint32_t addr) {
   u32x4 f;
   f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
   dst = __builtin_bit_cast(bf16x8, f);
-}
-template <int N>
-__device__ inline void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int I, int N, typename F>
-__device__ inline void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
 }
 // a word of the kernel-argument segment at a wave-uniform (run-time) index: a scalar load (indexing the by-value struct would move it to
 // scratch memory)
@@ -361,17 +343,14 @@ void wgrad384_plan(const GatherGeom& g, long M, int* splits, int* chunk, int gro
 
 int launch_wgrad384(const WgradParams& w, hipStream_t st, int group, const void* const* xs, const void* const* dys, float* const* outs) {
   const size_t lds = (size_t)NST * STAGE;
-  static const void* zero_dev = nullptr;
-  static hipError_t init_err = hipSuccess;
   DC_ONCE({
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad384_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad384_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad384_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    void* zp = nullptr;
-    init_err = hipGetSymbolAddress(&zp, HIP_SYMBOL(wg384_zero_page));
-    zero_dev = zp;
   });
-  if (init_err != hipSuccess) return dc_set_error(init_err, __FILE__, __LINE__);
+  hipError_t zerr;
+  const void* zero_dev = zero_page(&zerr);
+  if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   if (group < 1 || group > WG384_MAXL) return dc_fail("launch_wgrad384: group size out of range", __FILE__, __LINE__);
   const GatherGeom& g = w.g;
   // (the planner decides eligibility before the row strides are known: the kernel's 32-bit lane offsets hold for these)
