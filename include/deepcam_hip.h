@@ -316,6 +316,20 @@ int dc_bn_finalize(int C, long count, float* slab, int rows, const float* gamma,
 /* eval mode: scale/shift from the running statistics */
 int dc_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, float eps, float* scale, float* shift, void* stream);
+/* Every BatchNorm of a network in one launch (net.eval(), train_hdf5_ddp.py:425: the coefficients change only when the weights or the
+ * running statistics do).  table_dev: device array of n records (56 bytes, natural alignment); per channel the arithmetic of
+ * dc_bn_eval_coeffs with the caller's eps, so the coefficients are bit-equal to n calls of it. */
+typedef struct dc_bn_eval_entry {
+  const float* gamma;
+  const float* beta;
+  const float* running_mean;
+  const float* running_var;
+  float* scale;
+  float* shift;
+  int C;
+  float eps;
+} dc_bn_eval_entry;
+int dc_bn_eval_coeffs_all(const dc_bn_eval_entry* table_dev, int n, void* stream);
 /* out = act(y*scale + shift [+ residual]),  act = ReLU when relu != 0 */
 int dc_bn_apply(int dtype, long M, int C, const void* y, int ldy, const float* scale, const float* shift,
                 const void* residual, int ldr, int relu, void* out, int ldo, void* stream);
@@ -446,6 +460,17 @@ int dc_head_fwd_loss_bnin(int dtype, int N, int Cin, int Hi, int Wi, const void*
                           int relu, const float* w, float* logits_nchw, void* workspace, const void* labels, int label_dtype_bytes,
                           const float* class_weights, float grad_scale, double* loss_sum, float* dlogits, int64_t* pred,
                           int64_t* counts, void* stream);
+/* dc_head_fwd / dc_head_fwd_bnin with dc_wce_score's per-sample epilogue on the logits while they are in registers (the validation
+ * forward, train_hdf5_ddp.py:452-460: net.eval() forward, fp_loss, compute_score): no gradient, no prediction store.  Only the first
+ * n_valid samples are computed.  Same logits bit for bit as the siblings, so the same counts as dc_head_fwd[_bnin] + dc_wce_score.
+ * logits_nchw may be null (bf16, Cin = 256: a workgroup of the fused kernel works on ONE sample, so its sums are that sample's);
+ * every other configuration stores the logits and runs dc_wce_score on them. */
+int dc_head_fwd_score(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
+                      float* logits_nchw, void* workspace, const void* labels, int label_dtype_bytes, const float* class_weights,
+                      double* loss_sum /*[N]*/, int64_t* counts /*[N][9]*/, void* stream);
+int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale,
+                           const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, const void* labels,
+                           int label_dtype_bytes, const float* class_weights, double* loss_sum, int64_t* counts, void* stream);
 /* dc_head_bwd for that case: the weight gradient forms the head's input from y itself (register-staged 128-tile kernel); bn_slab != NULL
  * also leaves the BatchNorm's backward sums there as dc_head_bwd_bnstats does (bn_mean / bn_invstd then required).
  * parts: 3 = everything; 1 = the gathered gradient image + the data gradient (+ sums); 2 = the weight gradient alone, which reads the
@@ -493,6 +518,21 @@ int dc_wce_fused(int B, int H, int W, const float* logits_nchw, const void* labe
 /* compute_score on existing prediction / label maps (int64), counts int64[9] += */
 int dc_confusion_counts(long n, const int64_t* pred, const void* labels, int label_dtype_bytes, int64_t* counts,
                         void* stream);
+
+/* The validation pass's metric (train_hdf5_ddp.py:423-512: batch-1 fp_loss and compute_score, then the mean over SAMPLES) on a batch:
+ * dc_wce_fused's loss and count arithmetic statement for statement, without gradient and prediction store, accumulated PER SAMPLE.
+ *   loss_sum   double[B]     [b] += sum over sample b's pixels of w[y]*(lse - logit[y])   (caller zeroes)
+ *   counts     int64[B][9]   [b] += tp[3], fp[3], fn[3] of sample b                       (caller zeroes)
+ * A workgroup belongs to one sample (blockIdx.y), so no partial sum mixes two.  Samples >= n_valid (the padding of a ragged last
+ * batch) are not read and their entries not written.  A label outside [0,3) makes THAT sample's loss_sum NaN. */
+int dc_wce_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_dtype_bytes,
+                 const float* class_weights /*device float[3]*/, double* loss_sum, int64_t* counts, void* stream);
+/* One launch, one thread, samples in order: for b < n_valid  loss = loss_sum[b] / HW,  iou = compute_score's value from counts[b]
+ * (utils/utils.py:53-60: fp32 tp / (tp + fp + fn) per class, 1 where the union is 0, mean of the three), then
+ * acc[0] += 1, acc[1] += loss, acc[2] += iou  (the three running sums of train_hdf5_ddp.py:470-480; the result does not depend on
+ * scheduling).  per_sample (double[B][2], may be NULL) receives (loss, iou) of every valid sample. */
+int dc_val_accumulate(int B, int n_valid, long HW, const double* loss_sum, const int64_t* counts, double* acc /*[3]*/,
+                      double* per_sample, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -262,13 +262,33 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const BnFinArgs a) {
   bn_finalize_block(a, blockIdx.x, red);
 }
 
+// one channel's eval-mode coefficients (shared by the per-layer and the whole-network launch: the same statement, the same bits)
+__device__ __forceinline__ void bn_eval_coeff(int c, const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                              float* scale, float* shift) {
+  const float sc = gamma[c] / sqrtf(rv[c] + eps);
+  scale[c] = sc;
+  shift[c] = beta[c] - rm[c] * sc;
+}
+
 __global__ void bn_eval_coeffs_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv,
                                       float eps, float* scale, float* shift) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float sc = gamma[c] / sqrtf(rv[c] + eps);
-  scale[c] = sc;
-  shift[c] = beta[c] - rm[c] * sc;
+  bn_eval_coeff(c, gamma, beta, rm, rv, eps, scale, shift);
+}
+
+// dc_bn_eval_coeffs_all: blockIdx.y is the table entry (one BatchNorm), the x blocks stride over its channels
+struct BnEvalEntry {
+  const float *gamma, *beta, *rm, *rv;
+  float *scale, *shift;
+  int C;
+  float eps;
+};
+
+__global__ __launch_bounds__(128) void bn_eval_coeffs_all_kernel(const BnEvalEntry* __restrict__ table) {
+  const BnEvalEntry e = table[blockIdx.y];
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < e.C; c += gridDim.x * blockDim.x)
+    bn_eval_coeff(c, e.gamma, e.beta, e.rm, e.rv, e.eps, e.scale, e.shift);
 }
 
 template <typename T>
@@ -607,6 +627,14 @@ extern "C" int dc_bn_eval_coeffs(int C, const float* gamma, const float* beta, c
   DC_REQUIRE(C > 0 && gamma && beta && running_mean && running_var && scale && shift, "dc_bn_eval_coeffs: bad argument");
   hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(cdiv(C, 128)), dim3(128), 0, (hipStream_t)stream, C, gamma, beta,
                      running_mean, running_var, eps, scale, shift);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_bn_eval_coeffs_all(const dc_bn_eval_entry* table_dev, int n, void* stream) {
+  DC_REQUIRE(table_dev != nullptr && n > 0, "dc_bn_eval_coeffs_all: bad argument");
+  DC_REQUIRE(sizeof(BnEvalEntry) == 56 && sizeof(dc_bn_eval_entry) == 56, "dc_bn_eval_coeffs_all: entry layout changed");
+  hipLaunchKernelGGL(bn_eval_coeffs_all_kernel, dim3(4, n), dim3(128), 0, (hipStream_t)stream, (const BnEvalEntry*)table_dev);
   DC_CHECK_LAUNCH();
   return 0;
 }

@@ -104,6 +104,98 @@ __global__ __launch_bounds__(256) void wce_kernel(int B, long HW, const float* _
   }
 }
 
+// wce_kernel's loss and count arithmetic for the validation pass: no gradient, no prediction store, and blockIdx.y is the sample, so a
+// workgroup's partial sums belong to one sample and land in that sample's entries.
+__global__ __launch_bounds__(256) void wce_score_kernel(long HW, const float* __restrict__ logits, const void* __restrict__ labels,
+                                                        int lbytes, const float* __restrict__ cw, double* loss_sum,
+                                                        unsigned long long* counts) {
+  __shared__ double s_loss[4];
+  __shared__ unsigned long long s_cnt[4][9];
+  const int b = blockIdx.y;
+  const float w0 = cw[0], w1 = cw[1], w2 = cw[2];
+  const float* lb = logits + (size_t)b * NC * HW;
+  double lsum = 0.0;
+  unsigned long long cnt[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cnt[k] = 0ull;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the trip count is wave-uniform so that the ballots below see all 64 lanes
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long iters = (HW + stride - 1) / stride;
+  for (long it = 0; it < iters; ++it) {
+    const long p = first + it * stride;
+    const bool ok = p < HW;
+    int y = 0, am = 0;
+    if (ok) {
+      const float l0 = lb[p], l1 = lb[HW + p], l2 = lb[2 * HW + p];
+      y = load_label(labels, lbytes, (long)b * HW + p);
+      float best = l0;
+      if (l1 > best) { best = l1; am = 1; }
+      if (l2 > best) { best = l2; am = 2; }
+      const float e0 = expf(l0 - best), e1 = expf(l1 - best), e2 = expf(l2 - best);
+      const float se = e0 + e1 + e2;
+      const float lse = best + logf(se);
+      if ((unsigned)y < (unsigned)NC) {
+        const float wy = y == 0 ? w0 : (y == 1 ? w1 : w2);
+        const float ly = y == 0 ? l0 : (y == 1 ? l1 : l2);
+        lsum += (double)(wy * (lse - ly));
+      } else {
+        lsum += (double)__builtin_nanf("");          // as wce_kernel: the sample's loss is poisoned, nothing is dropped silently
+      }
+    }
+    const bool eq = ok && (am == y);
+    const bool ne = ok && (am != y);
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      cnt[j] += wave_count(eq && y == j);
+      cnt[3 + j] += wave_count(ne && am == j);
+      cnt[6 + j] += wave_count(ne && y == j);
+    }
+  }
+  lsum = wave_sum(lsum);
+  if (lane == 0) {
+    s_loss[wave] = lsum;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s_cnt[wave][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(loss_sum + b, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
+  if (threadIdx.x < 9) {
+    const int k = threadIdx.x;
+    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
+    if (c) atomicAdd(&counts[(size_t)b * 9 + k], c);
+  }
+}
+
+// One thread walks the samples in order: the three running sums do not depend on how anything was scheduled.
+__global__ void val_accumulate_kernel(int n_valid, long HW, const double* __restrict__ loss_sum, const long long* __restrict__ counts,
+                                      double* acc, double* per_sample) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double a0 = acc[0], a1 = acc[1], a2 = acc[2];
+  for (int b = 0; b < n_valid; ++b) {
+    const double loss = loss_sum[b] / (double)HW;
+    float s = 0.f;
+    for (int j = 0; j < NC; ++j) {
+      const long long tp = counts[b * 9 + j], fp = counts[b * 9 + 3 + j], fn = counts[b * 9 + 6 + j];
+      const long long un = tp + fp + fn;
+      // utils.py:55-58: float tensors, tp / union (1 where the union is empty), summed in class order
+      s += un == 0 ? 1.0f : (float)tp / (float)un;
+    }
+    const double iou = (double)(s / 3.0f);
+    a0 += 1.0;
+    a1 += loss;
+    a2 += iou;
+    if (per_sample != nullptr) {
+      per_sample[2 * b] = loss;
+      per_sample[2 * b + 1] = iou;
+    }
+  }
+  acc[0] = a0;
+  acc[1] = a1;
+  acc[2] = a2;
+}
+
 __global__ __launch_bounds__(256) void confusion_kernel(long n, const int64_t* __restrict__ pred,
                                                         const void* __restrict__ labels, int lbytes,
                                                         unsigned long long* counts) {
@@ -153,6 +245,33 @@ extern "C" int dc_wce_fused(int B, int H, int W, const float* logits_nchw, const
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(wce_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, B, (long)H * W, logits_nchw, labels,
                      label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_wce_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_dtype_bytes,
+                            const float* class_weights, double* loss_sum, int64_t* counts, void* stream) {
+  DC_REQUIRE(logits_nchw && labels && class_weights && loss_sum && counts && B > 0 && H > 0 && W > 0, "dc_wce_score: bad argument");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_wce_score: n_valid must lie in [0, B]");
+  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_wce_score: labels must be uint8, int32 or int64");
+  if (n_valid == 0) return 0;
+  const long HW = (long)H * W;
+  long blocks = (HW + 255) / 256;
+  const long cap = (2048 + n_valid - 1) / n_valid;      // dc_wce_fused's 2048 workgroups, shared between the samples
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(wce_score_kernel, dim3((int)blocks, n_valid), dim3(256), 0, (hipStream_t)stream, HW, logits_nchw, labels,
+                     label_dtype_bytes, class_weights, loss_sum, (unsigned long long*)counts);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_val_accumulate(int B, int n_valid, long HW, const double* loss_sum, const int64_t* counts, double* acc,
+                                 double* per_sample, void* stream) {
+  DC_REQUIRE(loss_sum && counts && acc && B > 0 && HW > 0, "dc_val_accumulate: bad argument");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_val_accumulate: n_valid must lie in [0, B]");
+  if (n_valid == 0) return 0;
+  hipLaunchKernelGGL(val_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, n_valid, HW, loss_sum, (const long long*)counts,
+                     acc, per_sample);
   DC_CHECK_LAUNCH();
   return 0;
 }

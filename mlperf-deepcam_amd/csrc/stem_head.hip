@@ -265,7 +265,9 @@ __device__ inline int head_load_label(const void* labels, int bytes, size_t i) {
   return (v >= 0 && v < HEAD_NC) ? (int)v : -1;
 }
 
-template <bool LOSS, bool BNIN = false>
+// SCORE (with LOSS): the validation pass's per-sample sums (dc_head_fwd_score): a workgroup works on ONE sample n (blockIdx.x -> strip, row
+// of tiles, n), so its partial loss and counts are that sample's and go to loss_sum[n] / counts[n][9]; the grid covers the valid samples only.
+template <bool LOSS, bool BNIN = false, bool SCORE = false>
 __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ wf,
                                                              float* __restrict__ out, int N, int Hi, int Wi, int Cin, int ntx, const HeadLoss hl,
                                                              const HeadBnIn bi) {
@@ -456,10 +458,12 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
       for (int k = 0; k < 9; ++k) s_cnt[wave * 9 + k] = cnt[k];
     }
     __syncthreads();
-    if (tid == 0 && hl.loss_sum != nullptr) atomicAdd(hl.loss_sum, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
+    size_t so = 0;
+    if constexpr (SCORE) so = (size_t)n;
+    if (tid == 0 && hl.loss_sum != nullptr) atomicAdd(hl.loss_sum + so, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
     if (tid < 9 && hl.counts != nullptr) {
       const unsigned long long c = s_cnt[tid] + s_cnt[9 + tid] + s_cnt[18 + tid] + s_cnt[27 + tid];
-      if (c) atomicAdd(&hl.counts[tid], c);
+      if (c) atomicAdd(&hl.counts[so * 9 + tid], c);
     }
   }
 }
@@ -786,9 +790,12 @@ extern "C" size_t dc_head_workspace(int dtype, int N, int Cin, int Hi, int Wi) {
 extern "C" int dc_wce_fused(int B, int H, int W, const float* logits_nchw, const void* labels, int label_dtype_bytes,
                             const float* class_weights, float grad_scale, double* loss_sum, float* dlogits, int64_t* pred,
                             int64_t* counts, void* stream);
+extern "C" int dc_wce_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_dtype_bytes,
+                            const float* class_weights, double* loss_sum, int64_t* counts, void* stream);
 
+// n_score >= 0: the per-sample epilogue of dc_head_fwd_score over the first n_score samples (hl's loss_sum / counts are then per sample)
 static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w, float* logits_nchw,
-                         void* workspace, void* stream, const HeadLoss* hl, const HeadBnIn* bi = nullptr) {
+                         void* workspace, void* stream, const HeadLoss* hl, const HeadBnIn* bi = nullptr, int n_score = -1) {
   if (int e = dc_check_view(x, ldx, Cin, dtype, "dc_head_fwd x")) return e;
   DC_REQUIRE(w && workspace && N > 0, "dc_head_fwd: bad argument");
   DC_REQUIRE(((uintptr_t)logits_nchw & 7) == 0 && ((uintptr_t)workspace & 255) == 0, "dc_head_fwd: logits / workspace alignment");
@@ -805,12 +812,26 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     auto k1 = &head_fused_fwd_kernel<true>;
     auto k2 = &head_fused_fwd_kernel<false, true>;
     auto k3 = &head_fused_fwd_kernel<true, true>;
+    auto k4 = &head_fused_fwd_kernel<true, false, true>;
+    auto k5 = &head_fused_fwd_kernel<true, true, true>;
     DC_ONCE({
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
+    if (n_score >= 0) {
+      // the grid is strips x tile rows x samples with the sample slowest: the first n_score samples are simply the shorter grid
+      if (n_score == 0) return 0;
+      if (bi != nullptr)
+        hipLaunchKernelGGL(k5, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi);
+      else
+        hipLaunchKernelGGL(k4, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{});
+      DC_CHECK_LAUNCH();
+      return 0;
+    }
     if (bi != nullptr) {
       if (hl != nullptr)
         hipLaunchKernelGGL(k3, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi);
@@ -833,6 +854,8 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   const long P = (long)N * Hi * Wi;
   hipLaunchKernelGGL(head_combine_kernel, dim3(cdiv(P, 256)), dim3(256), 0, st, (const float*)ws.P, logits_nchw, N, Hi, Wi);
   DC_CHECK_LAUNCH();
+  if (n_score >= 0)      // (the whole batch's logits exist here; the score reads the valid samples)
+    return dc_wce_score(N, n_score, 2 * Hi, 2 * Wi, logits_nchw, hl->labels, hl->lbytes, hl->cw, hl->loss_sum, (int64_t*)hl->counts, stream);
   if (hl != nullptr)     // not the fused kernel: the separate pass over the logits
     return dc_wce_fused(N, 2 * Hi, 2 * Wi, logits_nchw, hl->labels, hl->lbytes, hl->cw, hl->grad_scale, hl->loss_sum, hl->dlogits, hl->pred,
                         (int64_t*)hl->counts, stream);
@@ -852,6 +875,16 @@ extern "C" int dc_head_fwd_loss(int dtype, int N, int Cin, int Hi, int Wi, const
   DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_loss: labels must be uint8, int32 or int64");
   HeadLoss hl{labels, label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, &hl);
+}
+
+extern "C" int dc_head_fwd_score(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
+                                 float* logits_nchw, void* workspace, const void* labels, int label_dtype_bytes, const float* class_weights,
+                                 double* loss_sum, int64_t* counts, void* stream) {
+  DC_REQUIRE(labels && class_weights && loss_sum && counts, "dc_head_fwd_score: bad argument");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_score: n_valid must lie in [0, N]");
+  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_score: labels must be uint8, int32 or int64");
+  HeadLoss hl{labels, label_dtype_bytes, class_weights, 0.f, loss_sum, nullptr, nullptr, (unsigned long long*)counts};
+  return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, &hl, nullptr, n_valid);
 }
 
 // The head on a BatchNorm output that is never stored: y is the raw output of the convolution in front of the BatchNorm, the head's
@@ -875,6 +908,18 @@ extern "C" int dc_head_fwd_loss_bnin(int dtype, int N, int Cin, int Hi, int Wi, 
   HeadLoss hl{labels, label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts};
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, &hl, &bi);
+}
+
+extern "C" int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale,
+                                      const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, const void* labels,
+                                      int label_dtype_bytes, const float* class_weights, double* loss_sum, int64_t* counts, void* stream) {
+  DC_REQUIRE(labels && class_weights && scale && shift && loss_sum && counts, "dc_head_fwd_score_bnin: bad argument");
+  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_score_bnin: bf16, 256 channels, fused head kernel only");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_score_bnin: n_valid must lie in [0, N]");
+  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_score_bnin: labels must be uint8, int32 or int64");
+  HeadLoss hl{labels, label_dtype_bytes, class_weights, 0.f, loss_sum, nullptr, nullptr, (unsigned long long*)counts};
+  const HeadBnIn bi{scale, shift, relu};
+  return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, &hl, &bi, n_valid);
 }
 
 extern "C" int dc_conv_dgrad_bnstats(const dc_conv_desc* d, int N, int Hi, int Wi, const void* dy, int lddy, const void* wb,

@@ -228,10 +228,14 @@ class InputPipeline:
                     return
                 slot.consumed.synchronize()                       # host wait: the GPU is done with this slot's tensors
                 dn, ln = slot.data_host.numpy(), slot.label_host.numpy()
+                # drop_last=False: the last batch may hold fewer samples than slots; the remaining slots repeat its last sample (the batch
+                # keeps its shape) and `names` lists the valid samples only -- len(names) is the batch's n_valid
+                nv = min(self.B, len(self.ds) - b * self.B)
                 if pool is None:
-                    slot.names = [self.ds.read_into(b * self.B + j, dn[j], ln[j]) for j in range(self.B)]
+                    names = [self.ds.read_into(b * self.B + min(j, nv - 1), dn[j], ln[j]) for j in range(self.B)]
                 else:
-                    slot.names = list(pool.map(lambda j: self.ds.read_into(b * self.B + j, dn[j], ln[j]), range(self.B)))
+                    names = list(pool.map(lambda j: self.ds.read_into(b * self.B + min(j, nv - 1), dn[j], ln[j]), range(self.B)))
+                slot.names = names[:nv]
                 full_q.put(slot)
             full_q.put(None)
         except BaseException as e:  # surface reader failures in the consumer

@@ -44,6 +44,28 @@ BN_FIN_MAX_M = 16384
 WGRAD_GROUP = 12
 
 
+class PoolSlot:
+    """Stands where an activation's tensor will be while a forward-only engine is built: the buffers of such an engine are placed in ONE
+    arena once the program is complete (Engine._plan_pool), two of them on the same bytes where the last launch that touches the one
+    has been issued before the first launch that touches the other.  Every launch closure asks an activation for its pointer when it
+    runs (Act.ptr), so a dry pass over the program, in which data_ptr() below notes the asking step, gives every buffer's life."""
+
+    def __init__(self, eng: "Engine", name: str, shape: tuple, dtype):
+        self.eng, self.name, self.shape, self.dtype = eng, name, shape, dtype
+        self.nbytes = math.prod(shape) * self.element_size()
+        self.first = self.last = None           # program steps of the first and the last launch that touches the buffer
+
+    def element_size(self) -> int:
+        return 2 if self.dtype == torch.bfloat16 else 4
+
+    def data_ptr(self) -> int:
+        i = self.eng._trace_step
+        if self.first is None:
+            self.first = i
+        self.last = i
+        return 0
+
+
 class Act:
     """NHWC activation view: element (n,h,w,c) at base[((n*H+h)*W+w)*ld + off + c]."""
 
@@ -57,14 +79,19 @@ class Act:
             # line-aligned rows, 12.6 from 64-byte boundaries (736, the stride up to round 4), 10.9 from 728); the pad channels are never
             # read or written
             self.ld = Cc if Cc < 64 else (Cc + ACT_ALIGN - 1) // ACT_ALIGN * ACT_ALIGN
-            self.buf = torch.empty((N, H, W, self.ld), dtype=dtype or eng.dtype, device=eng.device)
-            eng.act_bytes += self.buf.numel() * self.buf.element_size()
-            eng.saved[name] = self.buf
-            eng.saved_channels[name] = Cc      # (the buffer's last dimension is ld >= Cc; the pad channels hold whatever the allocator left)
+            if eng.forward_only:
+                self.buf = PoolSlot(eng, name, (N, H, W, self.ld), dtype or eng.dtype)      # Engine._plan_pool puts the tensor here
+            else:
+                self.buf = torch.empty((N, H, W, self.ld), dtype=dtype or eng.dtype, device=eng.device)
+                eng.act_bytes += self.buf.numel() * self.buf.element_size()
+                eng.saved[name] = self.buf
+                eng.saved_channels[name] = Cc      # (the buffer's last dimension is ld >= Cc; the pad channels hold whatever the allocator left)
         else:
             assert (parent.N, parent.H, parent.W) == (N, H, W) and off + Cc <= parent.C
             self.buf, self.ld = parent.buf, parent.ld
             self.off = parent.off + off
+        if eng.forward_only:
+            eng._acts.append(self)
         self._grad: Optional[Act] = None
         self.grad_init = False      # set while the backward program is built: has some op written the gradient yet?
         self.grad_takes = 0         # consumers that have registered their contribution to the gradient so far (execution order)
@@ -147,12 +174,18 @@ class LazyAct:
 class Engine:
     def __init__(self, batch: int, height: int, width: int, dtype=torch.bfloat16, device=None, n_input: int = 16,
                  n_classes: int = 3, seed: Optional[int] = 333, share_from: "Engine" = None, layout: "S.Layout" = None,
-                 builder: Callable[["Engine"], None] = None, frozen_bn: bool = False, fuse_bn_into_head: bool = True):
+                 builder: Callable[["Engine"], None] = None, frozen_bn: bool = False, fuse_bn_into_head: bool = True,
+                 forward_only: bool = False):
         """layout + builder: a sub-network as an engine of its own (tests build ONE Xception Block from the op builders below
         and run it against the reference's Block vectors); the default is the whole DeepLabV3+ network.
         frozen_bn: every BatchNorm runs in eval mode, forward AND backward -- the running statistics normalise, nothing updates them, and
         the backward differentiates that affine map (autograd through ``net.eval()``: saliency, fine-tuning with frozen statistics).
-        fuse_bn_into_head=False: a bf16 engine stores the head's input as the fp32 one does (tests copy every activation between the two)."""
+        fuse_bn_into_head=False: a bf16 engine stores the head's input as the fp32 one does (tests copy every activation between the two).
+        forward_only (with share_from): the eval forward alone, for the validation pass (train_hdf5_ddp.py:423-512, nn.ValStep): no backward
+        program, gradient buffers, statistics slabs or second stream; the activations share one arena by their lives (_plan_pool); every
+        BatchNorm's eval coefficients come from ONE launch beside the weight repack (dc_bn_eval_coeffs_all), i.e. whenever the shared version
+        counter says that weights or running statistics have changed; and with score_args set the classifier's kernel leaves the per-sample
+        loss sums and IoU counts (dc_head_fwd_score).  forward(train=True) and backward() raise."""
         if not torch.cuda.is_available():
             raise L.DeepcamHipError("mlperf_deepcam_amd.Engine needs a HIP device: there is no CPU path")
         L.load()
@@ -164,6 +197,16 @@ class Engine:
         self.n_input, self.n_classes = n_input, n_classes
         self.layout = layout if layout is not None else S.Layout(n_input, n_classes)
         self._builder = builder
+        self.forward_only = forward_only
+        if forward_only and (share_from is None or frozen_bn or builder is not None):
+            raise L.DeepcamHipError("a forward-only engine runs the whole network on another engine's parameters: pass share_from, and neither "
+                                    "frozen_bn nor a builder")
+        self._acts: List[Act] = []                    # forward-only: every activation view, for _plan_pool and close()
+        self._trace_step = 0
+        self._bn_eval_entries: List[L.BnEvalEntry] = []
+        self._arena: Optional[torch.Tensor] = None
+        self.score_args: Optional[dict] = None        # set per call by nn.ValStep: per-sample loss sums and counts behind the classifier
+        self.closed = False
         lay = self.layout
         self.act_bytes = 0
         # name -> tensor of everything forward leaves behind for backward (activations, BatchNorm coefficient vectors): lets a
@@ -233,17 +276,21 @@ class Engine:
         self._ws_users: List[Callable[[], int]] = []
         self.x_in: Optional[torch.Tensor] = None     # caller's NCHW fp32 batch (set per call)
         self.x0: Optional[Act] = None                # NHWC stem input (when the stem runs on the MFMA kernels)
-        self.x_static = torch.empty((batch, n_input, height, width), dtype=torch.float32, device=self.device)
         self.logits = torch.empty((batch, n_classes, height, width), dtype=torch.float32, device=self.device)
+        self.on_grad_ready: Optional[Callable[[List[str]], None]] = None
+        self.region_marks: Optional[list] = None      # bench.py sets a list to collect (name, event) at the encoder boundaries
+        self.loss_args: Optional[dict] = None         # set per call by nn.TrainStep (bf16): loss inside the classifier's kernel
+        if forward_only:
+            self.side, self.use_side_stream = None, False
+            self.x_static = self.dlogits = self.workspace = self.workspace2 = None
+            self._build()
+            self._finish_pack_table()
+            return
+        self.x_static = torch.empty((batch, n_input, height, width), dtype=torch.float32, device=self.device)
         self.dlogits = torch.empty_like(self.logits)
         self._build()
         self.workspace = torch.empty(max(self.ws_bytes, 256), dtype=torch.uint8, device=self.device)
-        # one device table -> one launch repacks every layer's weights (dc_pack_all)
-        arr = (L.PackEntry * len(self._pack_entries))(*self._pack_entries)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-        self._pack_table = raw.to(self.device)
-        npk = len(self._pack_entries)
-        self.pack_ops.append(lambda: L.call("dc_pack_all", self.dt, L.dptr(self._pack_table), npk, self._st()))
+        self._finish_pack_table()
         # Weight gradients are off the critical path of backward (nothing downstream reads them until the optimizer) and
         # are MFMA-bound, while the chain they branch off (BN backward, depthwise data gradient) is HBM-bound: they run
         # on a side HIP stream with a private workspace and overlap it.  backward() joins the streams at the end.
@@ -252,9 +299,22 @@ class Engine:
         self.side = torch.cuda.Stream(device=self.device)
         self.workspace2 = torch.empty(max(self.ws_bytes, 256), dtype=torch.uint8, device=self.device)
         self.use_side_stream = True           # False: every launch on the current stream (bench.py's one-stream pass switches it at run time)
-        self.on_grad_ready: Optional[Callable[[List[str]], None]] = None
-        self.region_marks: Optional[list] = None      # bench.py sets a list to collect (name, event) at the encoder boundaries
-        self.loss_args: Optional[dict] = None         # set per call by nn.TrainStep (bf16): loss inside the classifier's kernel
+
+    def _device_table(self, entries: list, ctype) -> torch.Tensor:
+        arr = (ctype * len(entries))(*entries)
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(self.device)
+
+    def _finish_pack_table(self) -> None:
+        # one device table -> one launch repacks every layer's weights (dc_pack_all)
+        self._pack_table = self._device_table(self._pack_entries, L.PackEntry)
+        npk = len(self._pack_entries)
+        self.pack_ops.append(lambda: L.call("dc_pack_all", self.dt, L.dptr(self._pack_table), npk, self._st()))
+        if self.forward_only:
+            # ... and one more makes every BatchNorm's eval coefficients (they change when the weights or the running statistics do, which is
+            # when the version counter moves: optimizer step, load_state_dict)
+            self._bn_table = self._device_table(self._bn_eval_entries, L.BnEvalEntry)
+            nbn = len(self._bn_eval_entries)
+            self.pack_ops.append(lambda: L.call("dc_bn_eval_coeffs_all", L.dptr(self._bn_table), nbn, self._st()))
 
     # ------------------------------------------------------------------------------------------------ helpers
     def pptr(self, name: str) -> C.c_void_p:
@@ -342,6 +402,10 @@ class Engine:
         nwf, nwb = C.c_size_t(), C.c_size_t()
         L.call("dc_conv_packed_elems", C.byref(d), C.byref(nwf), C.byref(nwb))
         wf = torch.empty(nwf.value, dtype=tdtype, device=self.device)
+        if self.forward_only:
+            # no statistics, and the data-gradient image of the weights only where the forward kernel streams from it (dc_conv_fwd_kn, below)
+            stats = False
+            need_dx = need_dx and k == 1 and stride == 1 and not transposed and not f32 and dt == L.DC_BF16
         wb = torch.empty(nwb.value, dtype=tdtype, device=self.device) if need_dx else None
         # (a pointwise layer that hands the library both weight images gets the 224-pixel tiles' compact slab: one row per tile, no zero rows --
         # at local batch 4 that is 62 rows, short enough for the kernels that run the BatchNorm finalize themselves)
@@ -495,7 +559,7 @@ class Engine:
         assert all(m[5] is x and m[2].ld == y0.ld and (m[2].H, m[2].W, m[2].C) == (y0.H, y0.W, y0.C) for m in members)
         dils = (C.c_int * cnt)(*[m[0] for m in members])
         wfs = (C.c_void_p * cnt)(*[m[1].data_ptr() for m in members])
-        slabs = (C.c_void_p * cnt)(*[m[3].data_ptr() for m in members])
+        slabs = (C.c_void_p * cnt)(*[m[3].data_ptr() if m[3] is not None else None for m in members])
         N, H, W = x.N, x.H, x.W
         # few pixels under a long K loop (local batch 2: 81 tiles of 576 K steps on 256 CUs): the library cuts the launch along K when it is
         # given room for the partial tiles (dc_conv_fwd_dilated_group_ws)
@@ -653,6 +717,19 @@ class Engine:
         else:
             o = out or Act(self, name or bname, y.N, y.H, y.W, Cc, dtype=y.buf.dtype)
             assert o.buf.dtype == y.buf.dtype
+        if self.forward_only:
+            # the scale / shift map of the running statistics, whose coefficients dc_bn_eval_coeffs_all refreshes beside the weight repack
+            scale, shift = self._f32(Cc), self._f32(Cc)
+            self._keep += [scale, shift]
+            self._bn_eval_entries.append(L.BnEvalEntry(self.pptr(bname + ".weight").value, self.pptr(bname + ".bias").value,
+                                                       self.bptr(bname + ".running_mean").value, self.bptr(bname + ".running_var").value,
+                                                       scale.data_ptr(), shift.data_ptr(), Cc, BN_EPS))
+            if lazy:
+                return LazyAct(y, scale, shift, None, None, relu, None, (name or bname) + ".lazy")
+            rp = (lambda: residual.ptr) if residual is not None else (lambda: None)
+            self.fwd_eval.append(lambda: L.call("dc_bn_apply", bdt, M, Cc, y.ptr, y.ld, L.dptr(scale), L.dptr(shift), rp(),
+                                                residual.ld if residual is not None else 0, 1 if relu else 0, o.ptr, o.ld, self._st()))
+            return o
         scale, shift, mean, invstd = (self._f32(Cc) for _ in range(4))
         for suffix, t in ((".scale", scale), (".shift", shift), (".save_mean", mean), (".save_invstd", invstd)):
             self.saved[bname + suffix] = t
@@ -846,7 +923,66 @@ class Engine:
             self._resolve_backward()
             return
         self._build_network()
+        if self.forward_only:
+            self.bwd, self.fwd_train, self.grad_ready = [], [], []      # (the builders' backward makers are never resolved: nothing of theirs exists)
+            self._plan_pool()
+            return
         self._resolve_backward()
+
+    def _plan_pool(self) -> None:
+        """Places the activation buffers of a forward-only engine in one arena.  The program is static: a dry pass over it (no launch is issued,
+        lib.dry_run) has every launch closure ask its activations for their pointers, which gives each buffer the first and the last step that
+        touches it; all launches go to one stream in program order, so two buffers whose step ranges do not meet may share bytes.  Largest
+        buffer first, each at the lowest offset free over its whole life."""
+        slots: List[PoolSlot] = []
+        for a in self._acts:
+            if isinstance(a.buf, PoolSlot) and all(a.buf is not t for t in slots):
+                slots.append(a.buf)
+        self.x_in = self.logits               # (any tensor: the layout pass of an NCHW batch touches the stem's input)
+        with L.dry_run():
+            for i, op in enumerate(self.fwd_eval):
+                self._trace_step = i
+                op()
+        self.x_in = None
+        nsteps = len(self.fwd_eval)
+        placed: List[tuple] = []              # (offset, end, first, last)
+        total = 0
+        offs = {}
+        for t in sorted(slots, key=lambda t: -t.nbytes):
+            if t.first is None:               # never asked for: keep it clear of everything
+                t.first, t.last = 0, nsteps
+            size = (t.nbytes + 511) // 512 * 512
+            off = 0
+            for o, e, f, l in sorted(p for p in placed if not (p[3] < t.first or t.last < p[2])):
+                if off + size <= o:
+                    break
+                off = max(off, e)
+            placed.append((off, off + size, t.first, t.last))
+            offs[id(t)] = off
+            total = max(total, off + size)
+        self._arena = torch.empty(max(total, 512), dtype=torch.uint8, device=self.device)
+        self.act_bytes = total
+        self.act_bytes_unpooled = sum((t.nbytes + 511) // 512 * 512 for t in slots)
+        views = {id(t): self._arena[offs[id(t)]:offs[id(t)] + t.nbytes].view(t.dtype).view(t.shape) for t in slots}
+        for a in self._acts:
+            a.buf = views[id(a.buf)]
+        if self.x0 is not None:
+            self._x0_own = self.x0.buf
+
+    def close(self) -> None:
+        """Drops the launch closures and every buffer this engine owns (activations, packed weights, slabs, workspaces, logits); the
+        parameter, gradient and buffer arenas stay with whoever shares them.  The engine cannot run afterwards."""
+        self.closed = True
+        self.fwd_train, self.fwd_eval, self.bwd, self.pack_ops, self.grad_ready = [], [], [], [], []
+        self._wg_recs, self._fold_seq, self._final_fold = [], [], None
+        for a in self._acts:
+            a.buf = None
+        self._acts = []
+        self.saved, self.saved_channels, self._keep = {}, {}, []
+        self.x0 = self._x0_own = self._stem_out = self._layout_op = self.x_in = None
+        self._arena = self._sum_arena = self._pack_table = self._bn_table = None
+        self.logits = self.dlogits = self.x_static = self.workspace = self.workspace2 = self.side = None
+        self.on_grad_ready = self.loss_args = self.score_args = None
 
     def _build_network(self) -> None:
         lib = L.load()
@@ -987,7 +1123,8 @@ class Engine:
                 self._bn(y, slab, rows, f"aspp{i}.bn", True, out=cat1.slice(f"aspp{i}", 256 * (i - 1), 256))
         join = lambda: L.call("dc_stream_fence", C.c_void_p(self.side.cuda_stream), L.stream_ptr())   # noqa: E731
         self.fwd_train.append(join)
-        self.fwd_eval.append(join)
+        if not self.forward_only:             # (a forward-only engine has one stream: its small branches run in line, _fork_forward)
+            self.fwd_eval.append(join)
         y, slab, rows = self._conv(cat1, "conv1.weight", 256, name="proj")
         p = self._bn(y, slab, rows, "bn1", True)
 
@@ -1036,8 +1173,27 @@ class Engine:
                    hptr, L.dptr(la["labels"]), la["labels"].element_size(), L.dptr(la["weight"]), la["grad_scale"], L.dptr(la["loss_sum"]),
                    L.dptr(self.dlogits), L.dptr(la["pred"]), L.dptr(la["counts"]), self._st())
 
+        def head_fwd_score():
+            # the validation step (nn.ValStep) hands the score arguments over: per-sample loss sums and IoU counts of the first n_valid samples,
+            # in the classifier's kernel on the logits it has in registers (bf16: dc_head_fwd_score), or by dc_wce_score on the stored ones (fp32)
+            sa = self.score_args
+            if sa is None:
+                return head_fwd()
+            lab, nv = sa["labels"], sa["n_valid"]
+            tail = (L.dptr(lab), lab.element_size(), L.dptr(sa["weight"]), L.dptr(sa["loss_sum"]), L.dptr(sa["counts"]), self._st())
+            if self.dt != L.DC_BF16:
+                head_fwd()
+                L.call("dc_wce_score", B, nv, H, W, L.dptr(self.logits), *tail)
+                return
+            lg = L.dptr(self.logits) if sa["store_logits"] else None
+            if lazy_in:
+                L.call("dc_head_fwd_score_bnin", self.dt, B, nv, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
+                       self.pptr(wl), lg, hptr, *tail)
+                return
+            L.call("dc_head_fwd_score", self.dt, B, nv, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), lg, hptr, *tail)
+
         self.fwd_train.append(head_fwd_train)
-        self.fwd_eval.append(head_fwd)
+        self.fwd_eval.append(head_fwd_score if self.forward_only else head_fwd)
 
         def head_bwd_make():
             assert a.take_grad_mode() == 0
@@ -1165,6 +1321,10 @@ class Engine:
         """logits[B,3,H,W] (fp32, NCHW) = net(x); returns the engine-owned logits buffer.
         x is the reference's NCHW fp32 batch [B,16,H,W], or -- from the input pipeline (data.py) -- an NHWC batch
         [B,H,W,16] already in the activation dtype, which is then used in place (no layout pass)."""
+        if self.closed:
+            raise L.DeepcamHipError("this engine has been closed (Engine.close)")
+        if self.forward_only and train:
+            raise L.DeepcamHipError("a forward-only engine has the eval forward only: forward(train=True) needs a training engine")
         train = train and not self.frozen_bn          # (a frozen-BatchNorm engine has the eval forward only)
         if (self.x0 is not None and x_nchw.dim() == 4 and tuple(x_nchw.shape) == (self.B, self.H, self.W, self.n_input)
                 and x_nchw.dtype == self.dtype and x_nchw.is_contiguous() and x_nchw.device == self.device):
@@ -1227,6 +1387,8 @@ class Engine:
 
     def backward(self) -> None:
         """Consumes self.dlogits (NCHW fp32); leaves every parameter gradient in self.grads."""
+        if self.forward_only or self.closed:
+            raise L.DeepcamHipError("backward(): a forward-only (or closed) engine has no backward program")
         cb = self.on_grad_ready
         marks = self.region_marks
         enc_begin = len(self.bwd) - self._enc_bwd_makers      # the backward program is the reversed maker list

@@ -38,6 +38,12 @@ class FoldEntry(C.Structure):
 DC_FOLD_CONV, DC_FOLD_CONVT, DC_FOLD_DW = 0, 1, 2
 
 
+class BnEvalEntry(C.Structure):
+    """dc_bn_eval_entry (include/deepcam_hip.h): one BatchNorm of dc_bn_eval_coeffs_all's device table."""
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("C", C.c_int), ("eps", C.c_float)]
+
+
 P, I, L, F, SZ = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 CD = C.POINTER(ConvDesc)
 
@@ -108,6 +114,7 @@ _SIGS = {
     "dc_bn_stats": (I, [I, L, I, P, I, P, P]),
     "dc_bn_finalize": (I, [I, L, P, I, P, P, P, P, P, F, F, P, P, P, P, P]),
     "dc_bn_eval_coeffs": (I, [I, P, P, P, P, F, P, P, P]),
+    "dc_bn_eval_coeffs_all": (I, [P, I, P]),
     "dc_bn_apply": (I, [I, L, I, P, I, P, P, P, I, I, P, I, P]),
     "dc_bn_apply_fin": (I, [I, L, I, L, P, I, P, I, P, P, P, P, P, F, F, P, P, P, P, P, I, I, P, I, P]),
     "dc_bn_bwd_reduce": (I, [I, L, I, P, I, P, I, P, I, I, P, P, P, P, P, P]),
@@ -133,6 +140,8 @@ _SIGS = {
     "dc_head_bwd_bnstats": (I, [I, I, I, I, I, P, I, P, P, P, I, P, P, P, I, P, P, P, P, I, P, P]),
     "dc_head_fwd_bnin": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, P]),
     "dc_head_fwd_loss_bnin": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, P, I, P, F, P, P, P, P, P]),
+    "dc_head_fwd_score": (I, [I, I, I, I, I, I, P, I, P, P, P, P, I, P, P, P, P]),
+    "dc_head_fwd_score_bnin": (I, [I, I, I, I, I, I, P, I, P, P, I, P, P, P, P, I, P, P, P, P]),
     "dc_head_bwd_bnin": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, I, P, P, P, P, P, I, P]),
     "dc_head_bwd_bnin_apply": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, P, P, L, P, I, P, P]),
     "dc_nchw_to_nhwc": (I, [I, I, I, I, I, P, P, I, P]),
@@ -140,6 +149,8 @@ _SIGS = {
     "dc_input_normalize_hwc_to_nchw": (I, [I, L, I, I, P, P, P, P, P, P]),
     "dc_wce_fused": (I, [I, I, I, P, P, I, P, F, P, P, P, P, P]),
     "dc_confusion_counts": (I, [L, P, P, I, P, P]),
+    "dc_wce_score": (I, [I, I, I, I, P, P, I, P, P, P, P]),
+    "dc_val_accumulate": (I, [I, I, L, P, P, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),
@@ -218,8 +229,27 @@ _recorder: Optional["Program"] = None     # set by Program.recording(): every ca
 _recorder_thread = 0                       # (an input pipeline's reader threads issue library calls of their own: not part of the step's list)
 
 
+_dry = False                               # dry_run(): call() issues nothing (a forward-only engine walks its program once to plan its buffers)
+
+
+def dry_run():
+    import contextlib
+
+    @contextlib.contextmanager
+    def ctx():
+        global _dry
+        _dry = True
+        try:
+            yield
+        finally:
+            _dry = False
+    return ctx()
+
+
 def call(name: str, *args):
     """Call an int-returning entry point and raise on failure."""
+    if _dry:
+        return
     if _recorder is not None and threading.get_ident() == _recorder_thread:
         _recorder.append(name, *args)
     rc = getattr(load(), name)(*args)

@@ -673,3 +673,72 @@ class TrainStep:
 
     def iou(self) -> float:
         return iou_from_counts(self.counts.cpu().tolist())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# batched validation step
+# ------------------------------------------------------------------------------------------------------------------
+class ValStep:
+    """The reference's validation pass (train_hdf5_ddp.py:423-512: net.eval(), forward, fp_loss, compute_score at batch 1, mean over the
+    samples) on batches: eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running statistics, pooled
+    activations), per-sample loss sums and IoU counts behind the classifier (dc_head_fwd_score; fp32: dc_head_fwd + dc_wce_score) and their
+    reduction to the three running sums (count, sum of per-sample losses, sum of per-sample IoUs) on the device (dc_val_accumulate).
+    Nothing here synchronises; result() is the one device-to-host read."""
+
+    def __init__(self, net: DeepLabv3_plus, weight: Sequence[float], batch: int, height: int, width: int):
+        if net.engine is None:
+            raise L.DeepcamHipError("ValStep: materialize the model first (its parameters live in the primary engine's arena)")
+        self.net, self.B, self.H, self.W = net, batch, height, width
+        self.eng = Engine(batch, height, width, net.act_dtype, n_input=net.n_input, n_classes=net.n_classes, share_from=net.engine,
+                          forward_only=True)
+        dev = self.eng.device
+        # per-sample loss sums (B doubles) and counts (B x 9 int64) in ONE buffer: one memset per call clears both
+        self._score = torch.zeros(10 * batch, dtype=torch.int64, device=dev)
+        self.loss_sum = self._score[:batch].view(torch.float64)
+        self.counts = self._score[batch:].view(batch, 9)
+        self.acc = torch.zeros(3, dtype=torch.float64, device=dev)            # count, sum of losses, sum of IoUs
+        self._per = torch.zeros((batch, 2), dtype=torch.float64, device=dev)
+        self._weight = _cw_tensor(weight, dev)
+        self._last_valid = 0
+        self.store_logits = False       # bf16: also write the fp32 NCHW logits (the score needs them in registers only)
+        self._eng_handle = _ops.engine_handle(self.eng)
+
+    def __call__(self, x: torch.Tensor, labels: torch.Tensor, n_valid: Optional[int] = None) -> None:
+        """x: the NCHW fp32 batch or the input pipeline's NHWC batch (Engine.forward); the samples from n_valid on are padding: they are
+        computed by the network's body, but neither scored nor counted."""
+        eng, B = self.eng, self.B
+        nv = B if n_valid is None else int(n_valid)
+        if not 0 < nv <= B:
+            raise L.DeepcamHipError(f"ValStep: n_valid must lie in [1, {B}], got {n_valid}")
+        t = labels.squeeze(1) if labels.dim() == 4 else labels
+        if t.dtype not in (torch.uint8, torch.int32, torch.int64):
+            t = t.long()
+        if not t.is_contiguous():
+            t = t.contiguous()
+        if tuple(t.shape) != (B, self.H, self.W) or t.device != eng.device:
+            raise L.DeepcamHipError(f"ValStep: labels must be {(B, self.H, self.W)} on {eng.device}, got {tuple(t.shape)} on {t.device}")
+        L.call("dc_memset_async", L.dptr(self._score), 0, 80 * B, L.stream_ptr())
+        eng.score_args = {"labels": t, "weight": self._weight, "n_valid": nv, "loss_sum": self.loss_sum, "counts": self.counts,
+                          "store_logits": self.store_logits}
+        try:
+            _ops.OPS.net_forward(x, self._eng_handle, False)
+        finally:
+            eng.score_args = None
+        L.call("dc_val_accumulate", B, nv, self.H * self.W, L.dptr(self.loss_sum), L.dptr(self.counts), L.dptr(self.acc), L.dptr(self._per),
+               L.stream_ptr())
+        self._last_valid = nv
+
+    def reset(self) -> None:
+        L.call("dc_memset_async", L.dptr(self.acc), 0, 24, L.stream_ptr())
+
+    def result(self) -> tuple:
+        """(count, sum of per-sample losses, sum of per-sample IoUs) since reset(): one device-to-host read."""
+        c, ls, iou = self.acc.cpu().tolist()
+        return c, ls, iou
+
+    def per_sample(self) -> List[tuple]:
+        """(loss, IoU) of every valid sample of the last call."""
+        return [tuple(r) for r in self._per[:self._last_valid].cpu().tolist()]
+
+    def close(self) -> None:
+        self.eng.close()

@@ -8,7 +8,8 @@ Input: data.InputPipeline over the HDF5 files (decoded with h5py, or through the
 h5lite), or over synthetic HWC fields with ``--synthetic_samples N``.
 
 Extra flags (not in the reference): --wireup_method env|single, --dtype, --synthetic_samples, --synthetic_learnable,
---height/--width, --max_steps.
+--height/--width, --max_steps, --validation_batch_size (above 1: nn.ValStep, the validation pass in batches with its three sums kept on
+the device).
 """
 from __future__ import annotations
 
@@ -139,6 +140,8 @@ def build_parser():
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_steps", type=int, default=None)
+    AP.add_argument("--validation_batch_size", type=int, default=1,
+                    help="samples per validation batch; 1: the reference's loop, above 1: the batched validation step (same per-sample metric)")
     return AP
 
 
@@ -219,7 +222,11 @@ def main(pargs):
     # channel counts the MFMA stem does not take go through the direct stem kernel, which reads the reference's NCHW fp32 batch
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     train_loader = ddata.InputPipeline(train_set, B, dtype=dtype, device=device, layout=layout)
-    validation_loader = ddata.InputPipeline(validation_set, 1, dtype=dtype, device=device, layout=layout)
+    VB = pargs.validation_batch_size
+    if VB < 1:
+        raise ValueError("--validation_batch_size must be at least 1")
+    # (above 1 the last batch may be ragged: the pipeline pads it with its last sample and names the valid ones only)
+    validation_loader = ddata.InputPipeline(validation_set, VB, dtype=dtype, device=device, layout=layout, drop_last=VB == 1)
     logger.log_event(key="train_samples", value=train_set.global_size)
     val_size = validation_set.global_size if pargs.max_validation_steps is None else \
         min([validation_set.global_size, pargs.max_validation_steps * B * size])
@@ -228,6 +235,7 @@ def main(pargs):
         logger.log_event(key="invalid_submission")
 
     train_step = dnn.TrainStep(net, optimizer, class_weights, B, H, W, with_metrics=True)
+    val_step = dnn.ValStep(net, class_weights, VB, H, W) if VB > 1 else None
     if ddp.reducer is not None:
         train_step.attach_reducer(ddp.reducer)
     step, epoch = start_step, start_epoch
@@ -266,9 +274,20 @@ def main(pargs):
                 logger.log_start(key="eval_start", metadata={"epoch_num": epoch + 1})
                 net.eval()
                 sums = torch.zeros(3, dtype=torch.float64, device=device)            # count, loss, iou
+                if val_step is not None:
+                    # batches of VB samples: per-sample loss and IoU and their sums stay on the device (nn.ValStep); the ragged last batch
+                    # arrives padded and is scored up to the samples it names
+                    val_step.reset()
+                    step_val = 0
+                    for inputs_val, label_val, names_val in validation_loader:
+                        val_step(inputs_val, label_val, n_valid=len(names_val))
+                        step_val += 1
+                        if pargs.max_validation_steps is not None and step_val > pargs.max_validation_steps:
+                            break
+                    sums = val_step.acc.clone()
                 with torch.no_grad():
                     step_val = 0
-                    for inputs_val, label_val, _ in validation_loader:
+                    for inputs_val, label_val, _ in (validation_loader if val_step is None else ()):
                         outputs_val = net.engine_for(shape=(1, len(pargs.channels), H, W)).forward(inputs_val, train=False)
                         counts = torch.zeros(9, dtype=torch.int64, device=device)
                         ls = dnn.wce_fused(outputs_val, label_val, class_weights, counts=counts)
