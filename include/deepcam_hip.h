@@ -50,6 +50,10 @@ int dc_stream_priority_range(int* least, int* greatest);
  * same order, train_hdf5_ddp.py:358-364: backward, all-reduce, optimizer). */
 int dc_stream_fence(void* from_stream, void* to_stream);
 int dc_memset_async(void* dst, int byte, size_t bytes, void* stream);
+/* dst[0 .. bytes) = src[0 .. bytes), both in device memory, in stream order.  A word-argument call, so that the two copies that keep virtual
+ * rank 0's BatchNorm running buffers across the micro-batches of one step (the buffers a checkpoint of rank 0 holds, train_hdf5_ddp.py:515-527)
+ * are part of a recorded launch list. */
+int dc_memcpy_async(void* dst, const void* src, size_t bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The launch list of a train step as a C object.  The reference's step is the Python loop body train_hdf5_ddp.py:345-371, a chain of
@@ -575,6 +579,18 @@ int dc_lamb_step(int ntensors, const int64_t* offsets_dev, long n, float* p, con
  * ------------------------------------------------------------------------------------------------ */
 int dc_grad_pack_bf16(long n, const float* g, void* out_bf16, void* stream);
 int dc_grad_unpack_bf16(long n, const void* in_bf16, float* g, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gradient accumulation over virtual ranks: K micro-batches on one device stand for K data-parallel ranks, whose gradients apex /
+ * torch DDP sum and divide by the world size before the one optimizer update (train_hdf5_ddp.py:227,359-363).  Called on a bucket
+ * range of the gradient arena (g) and the same range of the accumulation arena (acc) as the bucket becomes ready during backward:
+ *   first != 0:  acc[i] = g[i]      (overwrites: acc may hold anything, NaN included; nothing clears the arena)
+ *   first == 0:  acc[i] += g[i]     (fp32)
+ * Any n >= 0.  g and acc need not be 16-byte aligned, but must sit at the SAME offset from a 16-byte boundary (the same range of two
+ * arenas does); the elements in front of the first boundary and behind the last whole vector take a scalar path.  One thread owns one
+ * element and there are no atomics: the sum is bit-identical from run to run, and in the order of the calls.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_grad_accumulate(long n, const float* g, float* acc, int first, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The gradient all-reduce itself, inside the library (csrc/comm.cpp; SURVEY section 8b: grad_allreduce_{enqueue,wait} over a raw RCCL

@@ -433,6 +433,32 @@ extern "C" int dc_copy_view(int dtype, long M, int C, const void* src, int lds, 
   return 0;
 }
 
+// ---- gradient accumulation over virtual ranks (nn.TrainStep(virtual_ranks=K): K micro-batches stand for K data-parallel ranks) ----
+// acc = g (first) or acc += g, one thread per element, no atomics: the sum over the micro-batches is the fixed fp32 expression
+// ((g0 + g1) + g2) ...  `head` elements in front of the first 16-byte boundary and the `n - head - 4 * nv` behind the last whole vector go
+// through block 0's scalar path; g and acc share their misalignment (the host checks), so one head serves both.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(long n, int head, const float* __restrict__ g, float* __restrict__ acc, int first) {
+  const float* gb = g + head;
+  float* ab = acc + head;
+  const long nv = (n - head) >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+    vec16 a = ldg16(gb + i * 4);
+    if (!first) {
+      const vec16 b = ldg16(ab + i * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a.w[e] = __float_as_uint(__uint_as_float(b.w[e]) + __uint_as_float(a.w[e]));
+    }
+    stg16(ab + i * 4, a);
+  }
+  if (blockIdx.x == 0) {
+    // threads 0 .. head-1: the head; threads 64 .. 64+tail-1: the tail (both shorter than 4 elements)
+    long t = -1;
+    if ((int)threadIdx.x < head) t = threadIdx.x;
+    else if (threadIdx.x >= 64 && head + nv * 4 + (threadIdx.x - 64) < n) t = head + nv * 4 + (threadIdx.x - 64);
+    if (t >= 0) acc[t] = first ? g[t] : acc[t] + g[t];
+  }
+}
+
 extern "C" int dc_grad_pack_bf16(long n, const float* g, void* out_bf16, void* stream) {
   DC_REQUIRE(g && out_bf16 && n > 0, "dc_grad_pack_bf16: bad argument");
   DC_REQUIRE((((uintptr_t)g | (uintptr_t)out_bf16) & 15) == 0, "dc_grad_pack_bf16: buffers must be 16-byte aligned");
@@ -445,6 +471,21 @@ extern "C" int dc_grad_unpack_bf16(long n, const void* in_bf16, float* g, void* 
   DC_REQUIRE(g && in_bf16 && n > 0, "dc_grad_unpack_bf16: bad argument");
   DC_REQUIRE((((uintptr_t)g | (uintptr_t)in_bf16) & 15) == 0, "dc_grad_unpack_bf16: buffers must be 16-byte aligned");
   hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(ew_blocks2(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, n, (const bf16*)in_bf16, g);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_grad_accumulate(long n, const float* g, float* acc, int first, void* stream) {
+  DC_REQUIRE(n >= 0, "dc_grad_accumulate: n must not be negative");
+  if (n == 0) return 0;
+  DC_REQUIRE(g && acc, "dc_grad_accumulate: null argument");
+  DC_REQUIRE((((uintptr_t)g | (uintptr_t)acc) & 3) == 0, "dc_grad_accumulate: both ranges must be 4-byte aligned");
+  DC_REQUIRE((((uintptr_t)g ^ (uintptr_t)acc) & 15) == 0,
+             "dc_grad_accumulate: g and acc must sit at the same offset from a 16-byte boundary (the same range of two arenas)");
+  long head = (long)((16 - ((uintptr_t)acc & 15)) & 15) / 4;      // floats in front of the first 16-byte boundary
+  if (head > n) head = n;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3(ew_blocks2((n - head) / 4 + 1)), dim3(256), 0, (hipStream_t)stream, n, (int)head, g, acc,
+                     first != 0 ? 1 : 0);
   DC_CHECK_LAUNCH();
   return 0;
 }

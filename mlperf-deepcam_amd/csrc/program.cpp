@@ -162,3 +162,11 @@ extern "C" int dc_memset_async(void* dst, int byte, size_t bytes, void* stream) 
   hipError_t e = hipMemsetAsync(dst, byte, bytes, (hipStream_t)stream);
   return e == hipSuccess ? 0 : dc_set_error(e, __FILE__, __LINE__);
 }
+
+// device-to-device copy on a stream (the BatchNorm running buffers set aside and put back around the micro-batches of a virtual-rank step)
+extern "C" int dc_memcpy_async(void* dst, const void* src, size_t bytes, void* stream) {
+  if ((dst == nullptr || src == nullptr) && bytes != 0) return dc_fail("dc_memcpy_async: null argument", __FILE__, __LINE__);
+  if (bytes == 0) return 0;
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : dc_set_error(e, __FILE__, __LINE__);
+}

@@ -51,6 +51,28 @@ def shard_files(all_files: Sequence[str], comm_size: int, comm_rank: int, allow_
     return list(mine), global_size
 
 
+def shard_files_virtual(all_files: Sequence[str], comm_size: int, comm_rank: int, virtual_ranks: int, batch_size: int,
+                        allow_uneven_distribution: bool, shuffle: bool, seed: int = 12345) -> Tuple[List[str], int]:
+    """(this process's files, global_size) when the process stands for `virtual_ranks` consecutive ranks of a job of
+    comm_size * virtual_ranks ranks (nn.TrainStep(virtual_ranks=K)): the shards shard_files gives global ranks
+    comm_rank * K + v, v = 0 .. K-1, interleaved in pieces of batch_size, so that the s-th run of K * batch_size files is
+    [rank 0's s-th batch, rank 1's s-th batch, ...] -- micro-batch v of step s holds exactly the samples global rank
+    comm_rank * K + v reads in step s of the larger job.  Samples behind a shard's last whole batch are dropped, as that job's
+    loader drops them.  virtual_ranks = 1 is shard_files."""
+    K = int(virtual_ranks)
+    if K < 1 or batch_size < 1:
+        raise ValueError("virtual_ranks and batch_size must be at least 1")
+    shards, global_size = [], 0
+    for v in range(K):
+        mine, global_size = shard_files(all_files, comm_size * K, comm_rank * K + v, allow_uneven_distribution, shuffle, seed)
+        shards.append(mine)
+    if K == 1:
+        return shards[0], global_size
+    steps = min(len(sh) for sh in shards) // batch_size
+    files = [f for s in range(steps) for sh in shards for f in sh[s * batch_size:(s + 1) * batch_size]]
+    return files, global_size
+
+
 def _h5_backend():
     """h5py when it is installed, else the ctypes binding of libhdf5 (h5lite); RuntimeError when neither is usable."""
     try:
@@ -69,11 +91,14 @@ class CamDataset:
     stored and label int64 [H, W]; channel selection and normalisation happen on the device."""
 
     def __init__(self, source: str, statsfile: str, channels: Sequence[int], allow_uneven_distribution: bool = False,
-                 shuffle: bool = False, preprocess: bool = True, comm_size: int = 1, comm_rank: int = 0, seed: int = 12345):
+                 shuffle: bool = False, preprocess: bool = True, comm_size: int = 1, comm_rank: int = 0, seed: int = 12345,
+                 virtual_ranks: int = 1, batch_size: int = 1):
+        """virtual_ranks / batch_size: see shard_files_virtual (the training set of a process that stands for several ranks)"""
         self.backend, self._h5 = _h5_backend()
         self.channels = list(channels)
         all_files = [os.path.join(source, x) for x in os.listdir(source) if x.endswith(".h5")]
-        self.files, self.global_size = shard_files(all_files, comm_size, comm_rank, allow_uneven_distribution, shuffle, seed)
+        self.files, self.global_size = shard_files_virtual(all_files, comm_size, comm_rank, virtual_ranks, batch_size,
+                                                           allow_uneven_distribution, shuffle, seed)
         self.local_size = len(self.files)
         if self.backend == "h5py":
             with self._h5.File(self.files[0], "r") as f:
@@ -122,13 +147,14 @@ class SyntheticHWC:
 
     def __init__(self, global_size: int, H: int, W: int, cfile: int = 16, channels: Sequence[int] = tuple(range(16)),
                  allow_uneven_distribution: bool = False, shuffle: bool = False, comm_size: int = 1, comm_rank: int = 0,
-                 seed: int = 12345, learnable: bool = False):
+                 seed: int = 12345, learnable: bool = False, virtual_ranks: int = 1, batch_size: int = 1):
         # learnable: the labels are a function of the fields (block-constant structures in channels 0 and 1 decide the class), so
         # a run has something to converge on: used for the time-to-target demonstration of the driver's stop rule
         # (train_hdf5_ddp.py:505-507).  Otherwise labels are independent draws with the reference's class frequencies.
         self.learnable = learnable
         names = [f"data-synthetic-{i:06d}.h5" for i in range(global_size)]
-        self.files, self.global_size = shard_files(names, comm_size, comm_rank, allow_uneven_distribution, shuffle, seed)
+        self.files, self.global_size = shard_files_virtual(names, comm_size, comm_rank, virtual_ranks, batch_size,
+                                                           allow_uneven_distribution, shuffle, seed)
         self.local_size = len(self.files)
         self.H, self.W, self.cfile = H, W, cfile
         self.channels = list(channels)

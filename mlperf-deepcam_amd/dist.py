@@ -11,6 +11,10 @@ collectives and re-arms the buckets for the next backward.  The 1/world averagin
 (``loss.backward(); optimizer.step()``), applied to the arena by ``finish(average=True)`` at the end of backward, so that
 ``p.grad`` is the averaged gradient exactly as under apex / torch DDP.  BatchNorm statistics stay per rank, as in the
 reference (no SyncBN).
+
+Virtual ranks (``nn.TrainStep(virtual_ranks=K)``): the same bucket plan also hands every ready bucket to ``dc_grad_accumulate``, which
+sums the K micro-batches' gradients into a second arena on the reducer's stream (``GradReducer.accumulate_into``); with a real world
+behind it, the collective then runs once per K micro-batches, on the accumulation arena, during the last one's backward.
 """
 from __future__ import annotations
 
@@ -213,6 +217,10 @@ class GradReducer:
         self.hook(engine)
         self.launched = 0
         self.averaging_in_optimizer = False     # set by TrainStep.attach_reducer: the 1/world then rides in the optimizer kernel
+        # virtual ranks (accumulate_into): the arena the ready buckets are summed into, whether the micro-batch that is running is the
+        # first of its step (its buckets overwrite) and whether it is the last (its buckets go on to the collective, from that arena)
+        self.acc: Optional[torch.Tensor] = None
+        self.acc_first, self.acc_send = True, True
         self._owns_comm = False
         if self.collective == "library" and (self.comm is None or isinstance(self.comm, str)):
             self._owns_comm = True
@@ -237,9 +245,37 @@ class GradReducer:
         except Exception:
             pass
 
+    def accumulate_into(self, acc: Optional[torch.Tensor]) -> None:
+        """Sum the gradients of several backward passes into `acc` (an fp32 arena of the gradient arena's size) bucket by bucket:
+        every bucket that becomes ready is handed to dc_grad_accumulate on the stream its collective would use, behind the compute
+        stream's position, so the add overlaps the rest of backward as the all-reduce does.  The caller (nn.TrainStep) says per
+        micro-batch whether it is the first (acc_first: overwrite) and the last (acc_send: the bucket, now complete in `acc`, goes to
+        the collective), and calls finish() after each backward.  None: back to reducing the gradient arena itself."""
+        if acc is not None and (acc.numel() != self.eng.grads.numel() or acc.dtype != torch.float32 or acc.device != self.eng.grads.device):
+            raise ValueError("the accumulation arena must be an fp32 tensor of the gradient arena's size on its device")
+        self.acc = acc
+        self.acc_first, self.acc_send = True, True
+
+    def _source(self) -> torch.Tensor:
+        """the arena the collective reduces: the accumulation arena when there is one, else the gradient arena"""
+        return self.acc if self.acc is not None else self.eng.grads
+
+    def _accumulate(self, b: Bucket) -> None:
+        from . import lib as L
+        L.call("dc_grad_accumulate", b.hi - b.lo, L.dptr(self.eng.grads[b.lo:b.hi]), L.dptr(self.acc[b.lo:b.hi]), 1 if self.acc_first else 0,
+               L.stream_ptr())
+
+    def _hand_off(self, b: Bucket) -> None:
+        """what happens to a ready bucket on the reducer's stream: [accumulate], then the collective (of the last micro-batch only)"""
+        if self.acc is not None:
+            self._accumulate(b)
+            if not self.acc_send:
+                return
+        b.work = self._reduce(b)
+
     def _resolve(self, ptr: int, count: int, dtype_code: int):
         """callback transport: the arena view an address handed to dc_grad_allreduce_enqueue refers to"""
-        arena = self._send if dtype_code == 1 else self.eng.grads
+        arena = self._send if dtype_code == 1 else self._source()
         off = (ptr - arena.data_ptr()) // arena.element_size()
         assert 0 <= off and off + count <= arena.numel(), "address outside the gradient arena"
         return arena[off:off + count]
@@ -262,7 +298,7 @@ class GradReducer:
     def _reduce(self, b: Bucket):
         if self.world <= 1:
             return None                          # a single rank has nothing to reduce
-        g = self.eng.grads[b.lo:b.hi]
+        g = self._source()[b.lo:b.hi]
         lib_path = self.collective == "library"
         if lib_path:
             import ctypes as C
@@ -285,7 +321,7 @@ class GradReducer:
         return dist.all_reduce(s, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def _unpack(self, b: Bucket) -> None:
-        g, s = self.eng.grads[b.lo:b.hi], self._send[b.lo:b.hi]
+        g, s = self._source()[b.lo:b.hi], self._send[b.lo:b.hi]
         if g.is_cuda:
             from . import lib as L
             L.call("dc_grad_unpack_bf16", b.hi - b.lo, L.dptr(s), L.dptr(g), L.stream_ptr())
@@ -304,16 +340,16 @@ class GradReducer:
                 # so it covers both without stalling backward.
                 side = getattr(self.eng, "side", None) if getattr(self.eng, "use_side_stream", False) else None
                 if side is not None:
-                    if self.collective == "library":       # a C call, so that a recorded launch list holds the fence too
+                    if self.collective == "library" or self.acc is not None:       # a C call, so that a recorded launch list holds the fence too
                         import ctypes as C
                         from . import lib as L
                         L.call("dc_stream_fence", L.stream_ptr(), C.c_void_p(side.cuda_stream))
                     else:
                         side.wait_event(torch.cuda.current_stream().record_event())
                     with torch.cuda.stream(side):
-                        b.work = self._reduce(b)
+                        self._hand_off(b)
                 else:
-                    b.work = self._reduce(b)
+                    self._hand_off(b)
                 self.launched += 1
 
     def finish(self, average: bool = False) -> None:
@@ -340,7 +376,7 @@ class GradReducer:
             raise RuntimeError(f"gradient bucket [{b.lo},{b.hi}) never completed: {b.remaining} gradients missing "
                                f"({len(missing)} of {len(self.buckets)} buckets incomplete)")
         if average and self.world > 1:
-            self.eng.grads.mul_(1.0 / self.world)
+            self._source().mul_(1.0 / self.world)
 
     def broadcast_parameters(self, src: int = 0) -> None:
         """DDP construction semantics (train_hdf5_ddp.py:227): every rank starts from rank 0's weights and BN buffers."""

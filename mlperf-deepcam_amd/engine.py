@@ -239,6 +239,9 @@ class Engine:
             # window OVERWRITES the gradients (the engine never accumulates), which nn._NetFn.backward then says out loud
             self.grads_live = [False]
         self.packed_version = -1
+        # the accumulation arena of a virtual-rank step (nn.TrainStep(virtual_ranks=K)): allocated by enable_grad_accumulation() only
+        self.grad_acc: Optional[torch.Tensor] = None
+        self._buffers_aside: Optional[torch.Tensor] = None
         self._keep: List[torch.Tensor] = []
         # BatchNorm fusions: the batch statistics or backward sums of a train-mode BatchNorm taken inside a neighbouring kernel (the producing
         # conv, a consuming depthwise / dense conv or the head), its finalize run by the kernel that consumes the coefficients, its backward
@@ -339,6 +342,27 @@ class Engine:
             return self.nbt[self.layout.nbt[name]]
         off, c = self.layout.buffers[name]
         return self.buffers[off:off + c]
+
+    def enable_grad_accumulation(self) -> torch.Tensor:
+        """The second fp32 arena of the gradient arena's size, into which the gradient buckets of K micro-batches are summed
+        (dc_grad_accumulate, handed off by dist.GradReducer as the buckets become ready), and the few kilobytes in which virtual rank 0's
+        BatchNorm running buffers wait while the other micro-batches run.  Nothing clears the arena: the first micro-batch overwrites it."""
+        if self.forward_only or self.closed:
+            raise L.DeepcamHipError("enable_grad_accumulation(): a forward-only (or closed) engine has no gradients")
+        if self.grad_acc is None:
+            self.grad_acc = torch.empty_like(self.grads)
+            # running_mean / running_var (fp32) and behind them num_batches_tracked (int64), as bytes
+            self._buffers_aside = torch.empty(self.buffers.numel() * 4 + self.nbt.numel() * 8, dtype=torch.uint8, device=self.device)
+        return self.grad_acc
+
+    def _copy_buffers(self, aside: bool) -> None:
+        """aside=True: BatchNorm running buffers -> the side copy; False: back.  Two C calls on the current stream (they record)."""
+        nb, nn_ = self.buffers.numel() * 4, self.nbt.numel() * 8
+        side = self._buffers_aside.data_ptr()
+        pairs = ((side, self.buffers.data_ptr(), nb), (side + nb, self.nbt.data_ptr(), nn_))
+        for s_ptr, b_ptr, n in pairs:
+            dst, src = (s_ptr, b_ptr) if aside else (b_ptr, s_ptr)
+            L.call("dc_memcpy_async", C.c_void_p(dst), C.c_void_p(src), n, self._st())
 
     def _need_ws(self, nbytes: int) -> None:
         self.ws_bytes = max(self.ws_bytes, int(nbytes))

@@ -58,6 +58,7 @@ _SIGS = {
     "dc_stream_priority_range": (I, [P, P]),
     "dc_stream_fence": (I, [P, P]),
     "dc_memset_async": (I, [P, I, SZ, P]),
+    "dc_memcpy_async": (I, [P, P, SZ, P]),
     "dc_program_create": (I, [P]),
     "dc_program_destroy": (I, [P]),
     "dc_program_append": (I, [P, C.c_char_p, I, P, P]),
@@ -161,6 +162,7 @@ _SIGS = {
     "dc_lamb_step": (I, [I, P, L, P, P, P, P, P, F, F, F, F, P, F, F, P, P]),
     "dc_grad_pack_bf16": (I, [L, P, P, P]),
     "dc_grad_unpack_bf16": (I, [L, P, P, P]),
+    "dc_grad_accumulate": (I, [L, P, P, I, P]),
     "dc_comm_unique_id": (I, [P]),
     "dc_comm_create": (I, [P, I, I, C.POINTER(P)]),
     "dc_comm_adopt": (I, [P, I, I, C.POINTER(P)]),

@@ -333,6 +333,7 @@ class ArenaOptimizer:
         self.step_count = 0
         self.max_grad_norm = max_grad_norm
         self.grad_scale = 1.0
+        self.grad_arena: Optional[torch.Tensor] = None     # use_gradients(): read the gradient from here instead of engine.grads
         # learning rate (float32) and step count (int32) side by side: ONE 8-byte host-to-device copy per step
         self._scal_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         self._lr_host = self._scal_host[:1].view(torch.float32)
@@ -353,6 +354,14 @@ class ArenaOptimizer:
         # (_NetFn.backward)
         self.engine.grads_live[0] = False
         return None
+
+    def use_gradients(self, arena: Optional[torch.Tensor]) -> None:
+        """Point the update at another fp32 arena of the gradient arena's size and layout (the accumulation arena of a virtual-rank step,
+        Engine.grad_acc); None: the engine's own gradient arena again.  Not part of state_dict(): it names a buffer, not optimizer state."""
+        if arena is not None and (arena.numel() != self.engine.grads.numel() or arena.dtype != torch.float32
+                                  or arena.device != self.engine.grads.device):
+            raise L.DeepcamHipError("use_gradients: the arena must be an fp32 tensor of the gradient arena's size on its device")
+        self.grad_arena = arena
 
     def sync_scalars(self) -> None:
         """Push lr / step count to the device scalars the kernels read (keeps a captured hipGraph in step).
@@ -376,12 +385,13 @@ class ArenaOptimizer:
         eng = self.engine
         n = eng.layout.n_params
         b1, b2 = g["betas"]
+        grads = eng.grads if self.grad_arena is None else self.grad_arena
         if self.kind == L.DC_LAMB:
-            L.call("dc_lamb_step", len(eng.layout.params), L.dptr(self._offsets), n, L.dptr(eng.params), L.dptr(eng.grads),
+            L.call("dc_lamb_step", len(eng.layout.params), L.dptr(self._offsets), n, L.dptr(eng.params), L.dptr(grads),
                    L.dptr(self.m), L.dptr(self.v), L.dptr(self.lr_dev), b1, b2, g["eps"], g["weight_decay"], L.dptr(self.step_dev),
                    self.max_grad_norm, self.grad_scale, L.dptr(self._lamb_ws), L.stream_ptr())
         else:
-            L.call("dc_adam_step", self.kind, n, L.dptr(eng.params), L.dptr(eng.grads), L.dptr(self.m), L.dptr(self.v),
+            L.call("dc_adam_step", self.kind, n, L.dptr(eng.params), L.dptr(grads), L.dptr(self.m), L.dptr(self.v),
                    L.dptr(self.lr_dev), b1, b2, g["eps"], g["weight_decay"], L.dptr(self.step_dev), self.grad_scale, L.stream_ptr())
         eng.mark_weights_changed()
 
@@ -525,22 +535,45 @@ class GradualWarmupScheduler:
 # ------------------------------------------------------------------------------------------------------------------
 class TrainStep:
     """inputs -> forward -> weighted CE (+argmax, IoU counts) -> backward -> [gradient hook] -> optimizer, as one flat
-    launch sequence on the current stream.  Equivalent to train_hdf5_ddp.py:348-364."""
+    launch sequence on the current stream.  Equivalent to train_hdf5_ddp.py:348-364.
+
+    virtual_ranks=K > 1: one call is the step of K data-parallel ranks (train_hdf5_ddp.py:227,345-364) on this device.  It takes K * batch
+    samples; micro-batch v (samples v * batch ... (v + 1) * batch - 1) is what rank v would have seen: forward with its own BatchNorm batch
+    statistics, its own mean loss (gradient scale 1 / (batch * H * W)), backward.  As the gradient buckets of a micro-batch become ready they
+    are summed into a second arena (dc_grad_accumulate through dist.GradReducer.accumulate_into: ascending v, ((g0 + g1) + g2) ... in fp32),
+    and ONE optimizer update reads that arena with grad_scale 1 / K (1 / (K * world) with a reducer attached, whose collective then runs
+    once per K micro-batches, during the last one's backward).  The BatchNorm running buffers and num_batches_tracked are virtual rank 0's
+    after the step, as a checkpoint written by rank 0 holds them.  loss() and iou() are the means over the ranks (rank_losses(), rank_ious()
+    give every rank's own).  K = 1 is the plain step, launch for launch, and allocates nothing more."""
 
     def __init__(self, net: DeepLabv3_plus, optimizer: ArenaOptimizer, weight: Sequence[float], batch: int, height: int,
-                 width: int, with_metrics: bool = False):
+                 width: int, with_metrics: bool = False, virtual_ranks: int = 1):
         self.net, self.opt = net, optimizer
+        self.K = int(virtual_ranks)
+        if self.K < 1:
+            raise L.DeepcamHipError(f"TrainStep: virtual_ranks must be at least 1, got {virtual_ranks}")
         self.eng = net.engine_for(shape=(batch, net.n_input, height, width))
         self.weight = list(weight)
         dev = self.eng.device
         # loss sum (one double) and the nine confusion counts behind it in ONE 80-byte buffer: one memset per step clears both
-        self._acc = torch.zeros(10, dtype=torch.int64, device=dev)
+        # (K virtual ranks: one such slot per micro-batch, still one memset, so that every rank's own loss and IoU can be read back)
+        self._acc = torch.zeros(10 * self.K, dtype=torch.int64, device=dev)
         self.loss_sum = self._acc[:1].view(torch.float64)
         self.with_metrics = with_metrics
-        self.pred = torch.empty((batch, height, width), dtype=torch.int64, device=dev) if with_metrics else None
+        self.pred = torch.empty((self.K * batch, height, width), dtype=torch.int64, device=dev) if with_metrics else None
         self.counts = self._acc[1:] if with_metrics else None
-        self.npix = batch * height * width
+        self.npix = batch * height * width          # of ONE micro-batch: the loss gradient is a rank's own mean
         self.after_backward = None      # set by attach_reducer
+        self._own_reducer = False
+        if self.K > 1:
+            # the bucket plan and the hand-off on the reducer's stream are dist.GradReducer's; at world size 1 it has nothing to send
+            from .dist import GradReducer
+            acc = self.eng.enable_grad_accumulation()
+            self._reducer = GradReducer(self.eng, 1)
+            self._reducer.accumulate_into(acc)
+            self._own_reducer = True
+            self.opt.use_gradients(acc)
+            self.opt.grad_scale = 1.0 / self.K
         self._eng_handle = _ops.engine_handle(self.eng)
         # loss inside the classifier's kernel (bf16 engine; fp32: the separate dc_wce_fused pass over stored logits);
         # store_logits: also write the fp32 NCHW logits (nobody reads them in the fused step)
@@ -552,16 +585,44 @@ class TrainStep:
         waits for them before the optimizer and the 1/world averaging rides in the optimizer kernel (no extra pass)."""
         self.after_backward = reducer.finish
         self._reducer = reducer
-        self.opt.grad_scale = 1.0 / reducer.world
+        self._own_reducer = False
+        self.opt.grad_scale = 1.0 / (self.K * reducer.world)
         # one averaging mechanism per module: the autograd path (DistributedDataParallel -> finish(average=True)) is switched off
         reducer.averaging_in_optimizer = True
         reducer.hook(self.eng)
+        if self.K > 1:
+            # the buckets of every micro-batch are summed into the accumulation arena; the last micro-batch's go on to the collective from there
+            reducer.accumulate_into(self.eng.grad_acc)
+            self.eng.on_grad_ready = reducer.ready       # (in place of the world-1 reducer this step was built with)
         # (net._ddp_reducer stays set: a loss.backward() through the wrapped module after this point reaches finish(average=True), which
         # raises on a reducer whose averaging lives in the optimizer, instead of silently leaving launched buckets un-waited)
 
     def launch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
+        L.call("dc_memset_async", L.dptr(self._acc), 0, 80 * self.K if self.counts is not None or self.K > 1 else 8, L.stream_ptr())
+        if self.K == 1:
+            self._micro_batch(x, labels, self.pred, self.loss_sum, self.counts)
+            if self.after_backward is not None:
+                self.after_backward()
+        else:
+            eng, B, red = self.eng, self.eng.B, self._reducer
+            if x.size(0) != self.K * B or labels.size(0) != self.K * B:
+                raise L.DeepcamHipError(f"TrainStep: {self.K} virtual ranks of batch {B} take {self.K * B} samples, got {x.size(0)} "
+                                        f"(labels: {labels.size(0)})")
+            for v in range(self.K):
+                red.acc_first, red.acc_send = v == 0, v == self.K - 1
+                slot = self._acc[10 * v:10 * v + 10]
+                self._micro_batch(x[v * B:(v + 1) * B], labels[v * B:(v + 1) * B], None if self.pred is None else self.pred[v * B:(v + 1) * B],
+                                  slot[:1].view(torch.float64), slot[1:] if self.with_metrics else None)
+                if v == 0:
+                    eng._copy_buffers(aside=True)       # virtual rank 0's running statistics (a train-mode forward never reads them)
+                red.finish()                            # re-arms the buckets; behind the last micro-batch: the wait for the collectives
+            eng._copy_buffers(aside=False)
+        self.opt.launch()
+
+    def _micro_batch(self, x: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], loss_sum: torch.Tensor,
+                     counts: Optional[torch.Tensor]) -> None:
+        """forward, loss and backward of one (micro-)batch; its loss sum and IoU counts go to the slot it is given"""
         eng = self.eng
-        L.call("dc_memset_async", L.dptr(self._acc), 0, 80 if self.counts is not None else 8, L.stream_ptr())
         if self.fuse_head_loss:
             # the loss pass rides inside the classifier's forward kernel (dc_head_fwd_loss): the logits are neither stored nor re-read
             t = labels.squeeze(1) if labels.dim() == 4 else labels
@@ -572,27 +633,23 @@ class TrainStep:
             if tuple(t.shape) != (eng.B, eng.H, eng.W):
                 raise L.DeepcamHipError(f"TrainStep: target shape {tuple(t.shape)} does not match the engine {(eng.B, eng.H, eng.W)}")
             eng.loss_args = {"labels": t, "weight": _cw_tensor(self.weight, eng.device), "grad_scale": 1.0 / float(self.npix),
-                             "loss_sum": self.loss_sum, "pred": self.pred, "counts": self.counts, "store_logits": self.store_logits}
+                             "loss_sum": loss_sum, "pred": pred, "counts": counts, "store_logits": self.store_logits}
             try:
                 _ops.OPS.net_forward(x, self._eng_handle, True)
             finally:
                 eng.loss_args = None
         else:
             logits = _ops.OPS.net_forward(x, self._eng_handle, True)
-            wce_fused(logits, labels, self.weight, dlogits=eng.dlogits, pred=self.pred, counts=self.counts, loss_sum=self.loss_sum)
+            wce_fused(logits, labels, self.weight, dlogits=eng.dlogits, pred=pred, counts=counts, loss_sum=loss_sum)
         _ops.OPS.net_backward(eng.dlogits, self._eng_handle)
-        if self.after_backward is not None:
-            self.after_backward()
-        self.opt.launch()
 
     def enable_graph(self) -> None:
         """Capture the whole step (about 1000 launches) into one hipGraph; later calls copy the batch into static
         buffers and replay.  Single-process only: the RCCL hand-off of the gradient reducer stays eager."""
-        if self.after_backward is not None or self.eng.on_grad_ready is not None:
+        if self.after_backward is not None or (self.eng.on_grad_ready is not None and not self._own_reducer):
             raise L.DeepcamHipError("hipGraph capture is for the single-GPU step (the all-reduce path launches eagerly)")
         eng = self.eng
-        self._gx = eng.x_static
-        self._gy = torch.zeros((eng.B, eng.H, eng.W), dtype=torch.int64, device=eng.device)
+        self._static_batch()
         if eng.packed_version != eng.version[0]:
             eng.pack_weights()
         # weights change every step: repacking is part of the captured sequence
@@ -611,6 +668,13 @@ class TrainStep:
         # callers enable the graph before training starts (bench) or accept one extra step on stale data
         self.graphed = True
 
+    def _static_batch(self) -> None:
+        """the buffers a captured or recorded step reads its batch from: K * batch samples, micro-batch v a view of them"""
+        eng = self.eng
+        self._gx = eng.x_static if self.K == 1 else torch.zeros((self.K * eng.B, eng.n_input, eng.H, eng.W), dtype=torch.float32,
+                                                                device=eng.device)
+        self._gy = torch.zeros((self.K * eng.B, eng.H, eng.W), dtype=torch.int64, device=eng.device)
+
     def enable_program(self) -> None:
         """Record the whole step as a C-side launch list (lib.Program, dc_program_*: every library call of one step with its arguments,
         stream fences included) and replay it with ONE call per step: later calls copy the batch into static buffers, push the
@@ -619,12 +683,15 @@ class TrainStep:
         is the library's own (GradReducer(collective="library"): dc_grad_allreduce_enqueue / _wait and the stream fences are C calls and
         land in the list); torch.distributed's collectives are Python objects and cannot."""
         red = getattr(self, "_reducer", None)
-        if (self.after_backward is not None or self.eng.on_grad_ready is not None) and getattr(red, "collective", None) != "library":
+        if self.K > 1 and not self._own_reducer:
+            raise L.DeepcamHipError(f"enable_program(): a step of {self.K} virtual ranks with a gradient reducer attached runs eagerly only "
+                                    "(record it without a reducer, or attach the reducer to a plain step)")
+        if ((self.after_backward is not None or self.eng.on_grad_ready is not None) and not self._own_reducer
+                and getattr(red, "collective", None) != "library"):
             raise L.DeepcamHipError("the recorded launch list needs the library's own collective (GradReducer(collective='library')): "
                                     "torch.distributed's all-reduce hooks run in Python")
         eng = self.eng
-        self._gx = eng.x_static
-        self._gy = torch.zeros((eng.B, eng.H, eng.W), dtype=torch.int64, device=eng.device)
+        self._static_batch()
         eng.packed_version = -1           # weights change every step: repacking is part of the recorded sequence
         self.opt.step_count += 1
         self.opt.sync_scalars()
@@ -668,11 +735,26 @@ class TrainStep:
             return
         self.launch(x, labels)
 
+    def rank_losses(self) -> List[float]:
+        """the mean loss of every virtual rank's micro-batch of the last step (one device-to-host read)"""
+        acc = self._acc.cpu()
+        return [float(acc[10 * v:10 * v + 1].view(torch.float64).item()) / self.npix for v in range(self.K)]
+
+    def rank_ious(self) -> List[float]:
+        acc = self._acc.cpu().tolist()
+        return [iou_from_counts(acc[10 * v + 1:10 * v + 10]) for v in range(self.K)]
+
     def loss(self) -> float:
-        return float(self.loss_sum.item()) / self.npix
+        """K = 1: the batch's mean loss; K virtual ranks: the mean of the ranks' losses (what train_hdf5_ddp.py:400-410 logs), which is
+        the loss sum over K * batch * H * W"""
+        if self.K == 1:
+            return float(self.loss_sum.item()) / self.npix
+        return sum(self.rank_losses()) / self.K
 
     def iou(self) -> float:
-        return iou_from_counts(self.counts.cpu().tolist())
+        if self.K == 1:
+            return iou_from_counts(self.counts.cpu().tolist())
+        return sum(self.rank_ious()) / self.K
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@ h5lite), or over synthetic HWC fields with ``--synthetic_samples N``.
 
 Extra flags (not in the reference): --wireup_method env|single, --dtype, --synthetic_samples, --synthetic_learnable,
 --height/--width, --max_steps, --validation_batch_size (above 1: nn.ValStep, the validation pass in batches with its three sums kept on
-the device).
+the device), --virtual_ranks K (process r of R acts as global ranks r*K .. r*K+K-1 of an R*K-rank job: same sample assignment, K
+micro-batches per step with their gradients summed on the device, one optimizer update; nn.TrainStep(virtual_ranks=K)).
 """
 from __future__ import annotations
 
@@ -142,6 +143,8 @@ def build_parser():
     AP.add_argument("--max_steps", type=int, default=None)
     AP.add_argument("--validation_batch_size", type=int, default=1,
                     help="samples per validation batch; 1: the reference's loop, above 1: the batched validation step (same per-sample metric)")
+    AP.add_argument("--virtual_ranks", type=int, default=1,
+                    help="data-parallel ranks this process stands for: K micro-batches of --local_batch_size per step, one optimizer update")
     return AP
 
 
@@ -164,7 +167,10 @@ def main(pargs):
     if rank == 0:
         os.makedirs(pargs.output_dir, exist_ok=True)
 
-    logger.log_event(key="global_batch_size", value=pargs.local_batch_size * size)
+    K = pargs.virtual_ranks
+    if K < 1:
+        raise ValueError("--virtual_ranks must be at least 1")
+    logger.log_event(key="global_batch_size", value=pargs.local_batch_size * size * K)
     logger.log_event(key="opt_name", value=pargs.optimizer)
     logger.log_event(key="opt_base_learning_rate", value=pargs.start_lr * pargs.lr_warmup_factor)
     logger.log_event(key="opt_learning_rate_warmup_steps", value=pargs.lr_warmup_steps)
@@ -207,21 +213,24 @@ def main(pargs):
     root_dir = os.path.join(pargs.data_dir_prefix)
     if pargs.synthetic_samples > 0:
         train_set = ddata.SyntheticHWC(pargs.synthetic_samples, H, W, channels=pargs.channels, allow_uneven_distribution=False,
-                                       shuffle=True, comm_size=size, comm_rank=rank, learnable=pargs.synthetic_learnable)
+                                       shuffle=True, comm_size=size, comm_rank=rank, learnable=pargs.synthetic_learnable,
+                                       virtual_ranks=K, batch_size=B)
         n_val = max(size, pargs.synthetic_samples // 8)
         validation_set = ddata.SyntheticHWC(n_val, H, W, channels=pargs.channels, allow_uneven_distribution=True,
                                             shuffle=(pargs.max_validation_steps is not None), comm_size=size, comm_rank=rank, seed=54321,
                                             learnable=pargs.synthetic_learnable)
     else:
         train_set = ddata.CamDataset(os.path.join(root_dir, "train"), os.path.join(root_dir, "stats.h5"), pargs.channels,
-                                     allow_uneven_distribution=False, shuffle=True, preprocess=True, comm_size=size, comm_rank=rank)
+                                     allow_uneven_distribution=False, shuffle=True, preprocess=True, comm_size=size, comm_rank=rank,
+                                     virtual_ranks=K, batch_size=B)
         validation_set = ddata.CamDataset(os.path.join(root_dir, "validation"), os.path.join(root_dir, "stats.h5"), pargs.channels,
                                           allow_uneven_distribution=True, shuffle=(pargs.max_validation_steps is not None),
                                           preprocess=True, comm_size=size, comm_rank=rank)
         assert tuple(train_set.data_shape[:2]) == (H, W), "pass --height/--width matching the files"
     # channel counts the MFMA stem does not take go through the direct stem kernel, which reads the reference's NCHW fp32 batch
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
-    train_loader = ddata.InputPipeline(train_set, B, dtype=dtype, device=device, layout=layout)
+    # (with virtual ranks a batch holds the K micro-batches of one step, rank after rank: data.shard_files_virtual)
+    train_loader = ddata.InputPipeline(train_set, K * B, dtype=dtype, device=device, layout=layout)
     VB = pargs.validation_batch_size
     if VB < 1:
         raise ValueError("--validation_batch_size must be at least 1")
@@ -234,7 +243,7 @@ def main(pargs):
     if pargs.max_validation_steps is not None:
         logger.log_event(key="invalid_submission")
 
-    train_step = dnn.TrainStep(net, optimizer, class_weights, B, H, W, with_metrics=True)
+    train_step = dnn.TrainStep(net, optimizer, class_weights, B, H, W, with_metrics=True, virtual_ranks=K)
     val_step = dnn.ValStep(net, class_weights, VB, H, W) if VB > 1 else None
     if ddp.reducer is not None:
         train_step.attach_reducer(ddp.reducer)
@@ -260,12 +269,17 @@ def main(pargs):
                 # collective: only the rank that saw the corrupt label has a NaN at this step, and a rank that raised alone would leave
                 # the others blocked in the reduction below.
                 vals = torch.tensor([loss_now, train_step.iou(), 0.0 if math.isfinite(loss_now) else 1.0], dtype=torch.float32, device=device)
+                if K > 1:
+                    # every virtual rank contributes its own float32 triple, as the ranks of the larger job do in the reduction below
+                    vals = torch.zeros(3, dtype=torch.float32, device=device)
+                    for lv, iv in zip(train_step.rank_losses(), train_step.rank_ious()):
+                        vals += torch.tensor([lv, iv, 0.0 if math.isfinite(lv) else 1.0], dtype=torch.float32, device=device)
                 if size > 1:
                     dist.all_reduce(vals, op=dist.ReduceOp.SUM)
                 if float(vals[2]) > 0 or not bool(torch.isfinite(vals[0])):
                     raise RuntimeError(f"non-finite training loss at step {step} on {int(vals[2])} rank(s) (local value {loss_now}): "
                                        "corrupt label or diverged run")
-                loss_avg_train, iou_avg_train = (vals[:2] / float(size)).tolist()
+                loss_avg_train, iou_avg_train = (vals[:2] / float(size * K)).tolist()
                 md = {"epoch_num": epoch + 1, "step_num": step}
                 logger.log_event(key="learning_rate", value=current_lr, metadata=md)
                 logger.log_event(key="train_accuracy", value=iou_avg_train, metadata=md)
