@@ -475,6 +475,19 @@ int dc_head_fwd_score(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, co
 int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale,
                            const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, const void* labels,
                            int label_dtype_bytes, const float* class_weights, double* loss_sum, int64_t* counts, void* stream);
+/* dc_head_fwd / dc_head_fwd_bnin for inference on unlabelled data (nn.Predictor, predict.py; reference: the net.eval() forward and
+ * torch.max(outputs, 1)[1] of train_hdf5_ddp.py:452-458, on a batch that has no labels): the epilogue of dc_logits_predict on the logits
+ * while they are in registers.  Only the first n_valid samples are computed; the bytes of the others stay as they were.
+ *   mask          uint8 [N][2Hi][2Wi]   first-max class (strict >, classes ascending: dc_wce_fused's pred)
+ *   conf          fp32  [N][2Hi][2Wi]   its softmax probability 1 / sum_k exp(l_k - max)                    (NULL to skip)
+ *   class_counts  int64 [N][3]          [n][j] += pixels of sample n with class j; the caller zeroes         (NULL to skip)
+ * Same logits bit for bit as the siblings, so the same outputs as dc_head_fwd[_bnin] + dc_logits_predict.  logits_nchw may be null
+ * (bf16, Cin = 256: the fused kernel); every other configuration stores the logits and runs dc_logits_predict on them. */
+int dc_head_fwd_predict(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
+                        float* logits_nchw, void* workspace, uint8_t* mask, float* conf, int64_t* class_counts, void* stream);
+int dc_head_fwd_predict_bnin(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale,
+                             const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, uint8_t* mask,
+                             float* conf, int64_t* class_counts, void* stream);
 /* dc_head_bwd for that case: the weight gradient forms the head's input from y itself (register-staged 128-tile kernel); bn_slab != NULL
  * also leaves the BatchNorm's backward sums there as dc_head_bwd_bnstats does (bn_mean / bn_invstd then required).
  * parts: 3 = everything; 1 = the gathered gradient image + the data gradient (+ sums); 2 = the weight gradient alone, which reads the
@@ -537,6 +550,12 @@ int dc_wce_score(int B, int n_valid, int H, int W, const float* logits_nchw, con
  * scheduling).  per_sample (double[B][2], may be NULL) receives (loss, iou) of every valid sample. */
 int dc_val_accumulate(int B, int n_valid, long HW, const double* loss_sum, const int64_t* counts, double* acc /*[3]*/,
                       double* per_sample, void* stream);
+
+/* Inference on stored logits (nn.predict_from_logits; the fp32 engine of nn.Predictor; reference: torch.max(outputs, 1)[1],
+ * train_hdf5_ddp.py:458): mask / conf / class_counts of dc_head_fwd_predict from fp32 NCHW logits [B][3][H][W], statement for statement
+ * the fused kernel's arithmetic.  A workgroup belongs to one sample; samples >= n_valid are neither read nor written. */
+int dc_logits_predict(int B, int n_valid, int H, int W, const float* logits_nchw, uint8_t* mask, float* conf /*may be NULL*/,
+                      int64_t* class_counts /*[B][3], may be NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

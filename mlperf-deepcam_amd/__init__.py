@@ -8,5 +8,6 @@ Import as ``mlperf_deepcam_amd``.  Layout:
   nn.py            reference-compatible call surface: DeepLabv3_plus, fp_loss, compute_score, optimizers, schedules
   dist.py          comm wire-up + RCCL gradient all-reduce overlapped with backward
   train.py         train_hdf5_ddp.py-compatible driver (CLI, checkpoints, MLLOG lines)
+  predict.py       inference driver: checkpoint + unlabelled files -> one mask file per input file
 """
 __version__ = "0.1.0"

@@ -168,6 +168,54 @@ __global__ __launch_bounds__(256) void wce_score_kernel(long HW, const float* __
   }
 }
 
+// Inference on stored logits (dc_logits_predict): the first-max class as one byte, optionally its softmax probability, and the pixel count
+// per class of each sample.  The statements are those of head_fused_fwd_kernel<PREDICT> (stem_head.hip), so equal logits give equal bits;
+// blockIdx.y is the sample as in wce_score_kernel.
+__global__ __launch_bounds__(256) void logits_predict_kernel(long HW, const float* __restrict__ logits, uint8_t* __restrict__ mask,
+                                                             float* __restrict__ conf, unsigned long long* counts) {
+  __shared__ unsigned long long s_cnt[4][NC];
+  const int b = blockIdx.y;
+  const float* lb = logits + (size_t)b * NC * HW;
+  unsigned long long cnt[NC] = {0ull, 0ull, 0ull};
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the trip count is wave-uniform so that the ballots below see all 64 lanes
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long iters = (HW + stride - 1) / stride;
+  for (long it = 0; it < iters; ++it) {
+    const long p = first + it * stride;
+    const bool ok = p < HW;
+    int am = 0;
+    if (ok) {
+      const float l0 = lb[p], l1 = lb[HW + p], l2 = lb[2 * HW + p];
+      const size_t gi = (size_t)b * HW + p;
+      float best = l0;
+      if (l1 > best) { best = l1; am = 1; }
+      if (l2 > best) { best = l2; am = 2; }
+      mask[gi] = (uint8_t)am;
+      if (conf != nullptr) {
+        const float e0 = expf(l0 - best), e1 = expf(l1 - best), e2 = expf(l2 - best);
+        conf[gi] = 1.0f / (e0 + e1 + e2);
+      }
+    }
+    if (counts != nullptr) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j) cnt[j] += wave_count(ok && am == j);
+    }
+  }
+  if (counts == nullptr) return;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) s_cnt[wave][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    const int k = threadIdx.x;
+    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
+    if (c) atomicAdd(&counts[(size_t)b * NC + k], c);
+  }
+}
+
 // One thread walks the samples in order: the three running sums do not depend on how anything was scheduled.
 __global__ void val_accumulate_kernel(int n_valid, long HW, const double* __restrict__ loss_sum, const long long* __restrict__ counts,
                                       double* acc, double* per_sample) {
@@ -261,6 +309,21 @@ extern "C" int dc_wce_score(int B, int n_valid, int H, int W, const float* logit
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(wce_score_kernel, dim3((int)blocks, n_valid), dim3(256), 0, (hipStream_t)stream, HW, logits_nchw, labels,
                      label_dtype_bytes, class_weights, loss_sum, (unsigned long long*)counts);
+  DC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dc_logits_predict(int B, int n_valid, int H, int W, const float* logits_nchw, uint8_t* mask, float* conf, int64_t* class_counts,
+                                 void* stream) {
+  DC_REQUIRE(logits_nchw && mask && B > 0 && H > 0 && W > 0, "dc_logits_predict: bad argument");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_logits_predict: n_valid must lie in [0, B]");
+  if (n_valid == 0) return 0;
+  const long HW = (long)H * W;
+  long blocks = (HW + 255) / 256;
+  const long cap = (2048 + n_valid - 1) / n_valid;      // dc_wce_score's share of workgroups per sample
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(logits_predict_kernel, dim3((int)blocks, n_valid), dim3(256), 0, (hipStream_t)stream, HW, logits_nchw, mask, conf,
+                     (unsigned long long*)class_counts);
   DC_CHECK_LAUNCH();
   return 0;
 }

@@ -265,12 +265,23 @@ __device__ inline int head_load_label(const void* labels, int bytes, size_t i) {
   return (v >= 0 && v < HEAD_NC) ? (int)v : -1;
 }
 
+// What dc_head_fwd_predict leaves behind the classifier: the class map, its confidence and the per-sample class pixel counts
+struct HeadPredict {
+  uint8_t* mask;
+  float* conf;
+  unsigned long long* counts;
+};
+
 // SCORE (with LOSS): the validation pass's per-sample sums (dc_head_fwd_score): a workgroup works on ONE sample n (blockIdx.x -> strip, row
 // of tiles, n), so its partial loss and counts are that sample's and go to loss_sum[n] / counts[n][9]; the grid covers the valid samples only.
-template <bool LOSS, bool BNIN = false, bool SCORE = false>
+// PREDICT (without LOSS): inference on unlabelled data (dc_head_fwd_predict): the grid of SCORE, and per pixel the first-max class (the `am` of
+// the LOSS path) as one byte, optionally its softmax probability, and the sample's pixel count per class in hp.counts[n][3]
+// (reference: torch.max(outputs, 1)[1], train_hdf5_ddp.py:458, on a batch that has no labels).
+template <bool LOSS, bool BNIN = false, bool SCORE = false, bool PREDICT = false>
 __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ wf,
                                                              float* __restrict__ out, int N, int Hi, int Wi, int Cin, int ntx, const HeadLoss hl,
-                                                             const HeadBnIn bi) {
+                                                             const HeadBnIn bi, const HeadPredict hp) {
+  static_assert(!(PREDICT && (LOSS || SCORE)), "PREDICT has no labels: neither loss nor score");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* P = reinterpret_cast<float*>(smem);                       // [HF_MB*16][HEAD_NP]
   char* wl = smem + HF_MB * 16 * HEAD_NP * 4;                      // weight image [32][Cin] bf16, 64-byte K rows swizzled per 16-B slot
@@ -362,7 +373,51 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
       cur_ok = nxt_ok;
     }
     __syncthreads();
-    if constexpr (!LOSS) {
+    if constexpr (PREDICT) {
+      // one output PIXEL per thread and pass as in the LOSS branch below (same addition order, same `am`); a wave covers one output row of
+      // the tile, so its 64 mask bytes are consecutive
+      constexpr int NPIX = 2 * HF_TY * 2 * HF_TX;
+#pragma unroll
+      for (int it = 0; it < NPIX / 256; ++it) {
+        const int i = tid + it * 256;
+        const int ox_l = i % (2 * HF_TX), oy_l = i / (2 * HF_TX);
+        const int qy_l = oy_l >> 1, py = oy_l & 1, qx_l = ox_l >> 1, px = ox_l & 1;
+        const int qy = y0 + qy_l, qx = x0 + qx_l;
+        const bool ok = qy < Hi && qx < Wi;
+        float l[HEAD_NC] = {0.f, 0.f, 0.f};
+        int am = 0;
+        if (ok) {
+#pragma unroll
+          for (int co = 0; co < HEAD_NC; ++co) {
+            const float* p00 = P + (qy_l * (HF_TX + 1) + qx_l) * HEAD_NP + co * 9;
+            const float* p01 = p00 + HEAD_NP;
+            const float* p10 = p00 + (HF_TX + 1) * HEAD_NP;
+            const float* p11 = p10 + HEAD_NP;
+            if (py == 0) l[co] = px == 0 ? p00[4] : p00[5] + p01[3];
+            else l[co] = px == 0 ? p00[7] + p10[1] : ((p00[8] + p01[6]) + p10[2]) + p11[0];
+          }
+          const size_t HWo = (size_t)Ho * Wo;
+          const size_t pix = (size_t)(2 * qy + py) * Wo + 2 * qx + px;
+          if (out != nullptr) {
+#pragma unroll
+            for (int co = 0; co < HEAD_NC; ++co) out[((size_t)n * HEAD_NC + co) * HWo + pix] = l[co];
+          }
+          const size_t gi = (size_t)n * HWo + pix;
+          float best = l[0];
+          if (l[1] > best) { best = l[1]; am = 1; }
+          if (l[2] > best) { best = l[2]; am = 2; }
+          hp.mask[gi] = (uint8_t)am;
+          if (hp.conf != nullptr) {
+            const float e0 = expf(l[0] - best), e1 = expf(l[1] - best), e2 = expf(l[2] - best);
+            hp.conf[gi] = 1.0f / (e0 + e1 + e2);
+          }
+        }
+        if (hp.counts != nullptr) {
+#pragma unroll
+          for (int j = 0; j < HEAD_NC; ++j) cnt[j] += __popcll(__ballot(ok && am == j));
+        }
+      }
+    } else if constexpr (!LOSS) {
       // combine: 2*HF_TY x 2*HF_TX outputs per class, consecutive lanes along x
       for (int i = tid; i < HEAD_NC * 2 * HF_TY * 2 * HF_TX; i += 256) {
         const int ox_l = i % (2 * HF_TX);
@@ -444,6 +499,21 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
             cnt[6 + j] += __popcll(__ballot(ne && y == j));
           }
         }
+      }
+    }
+  }
+  if constexpr (PREDICT) {
+    if (hp.counts != nullptr) {                       // (a kernel argument: uniform over the workgroup)
+      __syncthreads();                                // P is dead: reuse its first bytes for the block's partial counts
+      unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < HEAD_NC; ++k) s_cnt[wave * HEAD_NC + k] = cnt[k];
+      }
+      __syncthreads();
+      if (tid < HEAD_NC) {
+        const unsigned long long c = s_cnt[tid] + s_cnt[HEAD_NC + tid] + s_cnt[2 * HEAD_NC + tid] + s_cnt[3 * HEAD_NC + tid];
+        if (c) atomicAdd(&hp.counts[(size_t)n * HEAD_NC + tid], c);
       }
     }
   }
@@ -792,10 +862,14 @@ extern "C" int dc_wce_fused(int B, int H, int W, const float* logits_nchw, const
                             int64_t* counts, void* stream);
 extern "C" int dc_wce_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_dtype_bytes,
                             const float* class_weights, double* loss_sum, int64_t* counts, void* stream);
+extern "C" int dc_logits_predict(int B, int n_valid, int H, int W, const float* logits_nchw, uint8_t* mask, float* conf, int64_t* class_counts,
+                                 void* stream);
 
-// n_score >= 0: the per-sample epilogue of dc_head_fwd_score over the first n_score samples (hl's loss_sum / counts are then per sample)
+// n_score >= 0: the per-sample epilogue of dc_head_fwd_score over the first n_score samples (hl's loss_sum / counts are then per sample);
+// with hp: dc_head_fwd_predict's epilogue over them instead (no labels, hl is null)
 static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w, float* logits_nchw,
-                         void* workspace, void* stream, const HeadLoss* hl, const HeadBnIn* bi = nullptr, int n_score = -1) {
+                         void* workspace, void* stream, const HeadLoss* hl, const HeadBnIn* bi = nullptr, int n_score = -1,
+                         const HeadPredict* hp = nullptr) {
   if (int e = dc_check_view(x, ldx, Cin, dtype, "dc_head_fwd x")) return e;
   DC_REQUIRE(w && workspace && N > 0, "dc_head_fwd: bad argument");
   DC_REQUIRE(((uintptr_t)logits_nchw & 7) == 0 && ((uintptr_t)workspace & 255) == 0, "dc_head_fwd: logits / workspace alignment");
@@ -814,6 +888,8 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     auto k3 = &head_fused_fwd_kernel<true, true>;
     auto k4 = &head_fused_fwd_kernel<true, false, true>;
     auto k5 = &head_fused_fwd_kernel<true, true, true>;
+    auto k6 = &head_fused_fwd_kernel<false, false, false, true>;
+    auto k7 = &head_fused_fwd_kernel<false, true, false, true>;
     DC_ONCE({
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -821,29 +897,41 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k6), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k7), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
+    if (hp != nullptr) {
+      // the shorter grid of the score variant below: the first n_score samples
+      if (n_score == 0) return 0;
+      if (bi != nullptr)
+        hipLaunchKernelGGL(k7, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, *hp);
+      else
+        hipLaunchKernelGGL(k6, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, *hp);
+      DC_CHECK_LAUNCH();
+      return 0;
+    }
     if (n_score >= 0) {
       // the grid is strips x tile rows x samples with the sample slowest: the first n_score samples are simply the shorter grid
       if (n_score == 0) return 0;
       if (bi != nullptr)
-        hipLaunchKernelGGL(k5, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi);
+        hipLaunchKernelGGL(k5, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
       else
-        hipLaunchKernelGGL(k4, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{});
+        hipLaunchKernelGGL(k4, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
       DC_CHECK_LAUNCH();
       return 0;
     }
     if (bi != nullptr) {
       if (hl != nullptr)
-        hipLaunchKernelGGL(k3, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi);
+        hipLaunchKernelGGL(k3, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
       else
-        hipLaunchKernelGGL(k2, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi);
+        hipLaunchKernelGGL(k2, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, HeadPredict{});
       DC_CHECK_LAUNCH();
       return 0;
     }
     if (hl != nullptr)
-      hipLaunchKernelGGL(k1, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{});
+      hipLaunchKernelGGL(k1, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
     else
-      hipLaunchKernelGGL(k0, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{});
+      hipLaunchKernelGGL(k0, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, HeadPredict{});
     DC_CHECK_LAUNCH();
     return 0;
   }
@@ -854,6 +942,8 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   const long P = (long)N * Hi * Wi;
   hipLaunchKernelGGL(head_combine_kernel, dim3(cdiv(P, 256)), dim3(256), 0, st, (const float*)ws.P, logits_nchw, N, Hi, Wi);
   DC_CHECK_LAUNCH();
+  if (hp != nullptr)     // (the whole batch's logits exist here; the prediction reads the valid samples)
+    return dc_logits_predict(N, n_score, 2 * Hi, 2 * Wi, logits_nchw, hp->mask, hp->conf, (int64_t*)hp->counts, stream);
   if (n_score >= 0)      // (the whole batch's logits exist here; the score reads the valid samples)
     return dc_wce_score(N, n_score, 2 * Hi, 2 * Wi, logits_nchw, hl->labels, hl->lbytes, hl->cw, hl->loss_sum, (int64_t*)hl->counts, stream);
   if (hl != nullptr)     // not the fused kernel: the separate pass over the logits
@@ -920,6 +1010,29 @@ extern "C" int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, in
   HeadLoss hl{labels, label_dtype_bytes, class_weights, 0.f, loss_sum, nullptr, nullptr, (unsigned long long*)counts};
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, &hl, &bi, n_valid);
+}
+
+// Inference on unlabelled data: the classifier leaves the class map (first maximum, one byte per pixel), optionally its softmax probability
+// and the per-sample class pixel counts of the first n_valid samples (reference: torch.max(outputs, 1)[1], train_hdf5_ddp.py:458).
+extern "C" int dc_head_fwd_predict(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
+                                   float* logits_nchw, void* workspace, uint8_t* mask, float* conf, int64_t* class_counts, void* stream) {
+  DC_REQUIRE(mask != nullptr, "dc_head_fwd_predict: null mask");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_predict: n_valid must lie in [0, N]");
+  DC_REQUIRE(((uintptr_t)conf & 3) == 0 && ((uintptr_t)class_counts & 7) == 0, "dc_head_fwd_predict: conf / class_counts alignment");
+  const HeadPredict hp{mask, conf, (unsigned long long*)class_counts};
+  return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, nullptr, nullptr, n_valid, &hp);
+}
+
+extern "C" int dc_head_fwd_predict_bnin(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale,
+                                        const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, uint8_t* mask,
+                                        float* conf, int64_t* class_counts, void* stream) {
+  DC_REQUIRE(mask != nullptr && scale != nullptr && shift != nullptr, "dc_head_fwd_predict_bnin: null argument");
+  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_predict_bnin: bf16, 256 channels, fused head kernel only");
+  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_predict_bnin: n_valid must lie in [0, N]");
+  DC_REQUIRE(((uintptr_t)conf & 3) == 0 && ((uintptr_t)class_counts & 7) == 0, "dc_head_fwd_predict_bnin: conf / class_counts alignment");
+  const HeadPredict hp{mask, conf, (unsigned long long*)class_counts};
+  const HeadBnIn bi{scale, shift, relu};
+  return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, nullptr, &bi, n_valid, &hp);
 }
 
 extern "C" int dc_conv_dgrad_bnstats(const dc_conv_desc* d, int N, int Hi, int Wi, const void* dy, int lddy, const void* wb,

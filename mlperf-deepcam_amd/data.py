@@ -88,13 +88,15 @@ def _h5_backend():
 
 class CamDataset:
     """HDF5-backed source (cam_hdf5_dataset.py:36-131).  read_into(i, data, label) fills data float32 [H, W, Cfile] exactly as
-    stored and label int64 [H, W]; channel selection and normalisation happen on the device."""
+    stored and label int64 [H, W]; channel selection and normalisation happen on the device.
+    labels=False: unlabelled files (inference, predict.py): climate/labels_0 is neither required nor read, read_into takes label_out=None."""
 
     def __init__(self, source: str, statsfile: str, channels: Sequence[int], allow_uneven_distribution: bool = False,
                  shuffle: bool = False, preprocess: bool = True, comm_size: int = 1, comm_rank: int = 0, seed: int = 12345,
-                 virtual_ranks: int = 1, batch_size: int = 1):
+                 virtual_ranks: int = 1, batch_size: int = 1, labels: bool = True):
         """virtual_ranks / batch_size: see shard_files_virtual (the training set of a process that stands for several ranks)"""
         self.backend, self._h5 = _h5_backend()
+        self.labels = bool(labels)
         self.channels = list(channels)
         all_files = [os.path.join(source, x) for x in os.listdir(source) if x.endswith(".h5")]
         self.files, self.global_size = shard_files_virtual(all_files, comm_size, comm_rank, virtual_ranks, batch_size,
@@ -103,13 +105,14 @@ class CamDataset:
         if self.backend == "h5py":
             with self._h5.File(self.files[0], "r") as f:
                 self.data_shape = tuple(f["climate"]["data"].shape)
-                self.label_shape = tuple(f["climate"]["labels_0"].shape)
+                self.label_shape = tuple(f["climate"]["labels_0"].shape) if self.labels else self.data_shape[:2]
             with self._h5.File(statsfile, "r") as f:
                 minval, maxval = f["climate"]["minval"][...], f["climate"]["maxval"][...]
         else:
             with self._h5.File(self.files[0]) as f:
-                self.data_shape, self.label_shape = f.shape("climate/data"), f.shape("climate/labels_0")
-                self._label_dtype = f.dtype("climate/labels_0").newbyteorder("=")
+                self.data_shape = f.shape("climate/data")
+                self.label_shape = f.shape("climate/labels_0") if self.labels else tuple(self.data_shape[:2])
+                self._label_dtype = f.dtype("climate/labels_0").newbyteorder("=") if self.labels else None
             with self._h5.File(statsfile) as f:
                 minval, maxval = f.read("climate/minval"), f.read("climate/maxval")
         shift = np.asarray(minval)[self.channels]                                   # :96-98
@@ -124,15 +127,20 @@ class CamDataset:
     def __len__(self):
         return self.local_size
 
-    def read_into(self, i: int, data_out: np.ndarray, label_out: np.ndarray) -> str:
+    def read_into(self, i: int, data_out: np.ndarray, label_out: Optional[np.ndarray]) -> str:
+        if self.labels == (label_out is None):
+            raise ValueError("CamDataset.read_into: label_out is given exactly when the dataset was opened with labels=True")
         if self.backend == "h5py":
             with self._h5.File(self.files[i], "r") as f:
                 f["climate/data"].read_direct(data_out)
-                label_out[...] = f["climate/labels_0"][...]
+                if label_out is not None:
+                    label_out[...] = f["climate/labels_0"][...]
         else:
             with self._h5.File(self.files[i]) as f:
                 f.read_direct("climate/data", data_out)               # contiguous fp32: pread straight into the pinned buffer
-                if self._label_dtype == label_out.dtype:
+                if label_out is None:
+                    pass
+                elif self._label_dtype == label_out.dtype:
                     f.read_direct("climate/labels_0", label_out)
                 else:
                     label_out[...] = f.read("climate/labels_0")
@@ -192,14 +200,14 @@ class SyntheticHWC:
 # device half
 # ---------------------------------------------------------------------------------------------------------------------
 class _Slot:
-    def __init__(self, B, H, W, cfile, C_, dtype, device, nchw=False):
+    def __init__(self, B, H, W, cfile, C_, dtype, device, nchw=False, labels=True):
         self.data_host = torch.empty((B, H, W, cfile), dtype=torch.float32).pin_memory()
-        self.label_host = torch.empty((B, H, W), dtype=torch.int64).pin_memory()
+        self.label_host = torch.empty((B, H, W), dtype=torch.int64).pin_memory() if labels else None
         self.data_dev = torch.empty((B, H, W, cfile), dtype=torch.float32, device=device)
         # NHWC activations, consumed in place by the MFMA stem; or the reference's NCHW fp32 batch for the direct stem kernel
         self.x = torch.empty((B, C_, H, W), dtype=torch.float32, device=device) if nchw else \
             torch.empty((B, H, W, C_), dtype=dtype, device=device)
-        self.label = torch.empty((B, H, W), dtype=torch.int64, device=device)
+        self.label = torch.empty((B, H, W), dtype=torch.int64, device=device) if labels else None
         self.ready = torch.cuda.Event()
         self.consumed = torch.cuda.Event()
         self.names: List[str] = []
@@ -211,7 +219,11 @@ class InputPipeline:
     A reader thread fills pinned staging buffers (numpy/h5py release the GIL while copying); the main thread enqueues, on a
     dedicated copy stream, the H2D DMA and the normalise kernel of batch i+1 while the compute stream trains on batch i.
     `depth` slots (>= 2) bound the memory; a slot is recycled only after the compute stream has passed the point where its
-    tensors were last used (the consumer calls release(), or simply asks for the next batch)."""
+    tensors were last used (the consumer calls release(), or simply asks for the next batch).
+
+    Over an unlabelled dataset (CamDataset(labels=False)) there are no label slots and the batches are (x, None, filenames).
+    drop_last=False: the last batch may be ragged; its padding repeats the last sample, `filenames` lists the valid samples only and
+    `n_valid` holds the fill count of the batch handed out last."""
 
     def __init__(self, dataset, batch_size: int, dtype=torch.bfloat16, device=None, depth: int = 3, drop_last: bool = True,
                  workers: int = 4, layout: str = "nhwc"):
@@ -229,7 +241,9 @@ class InputPipeline:
         if layout not in ("nhwc", "nchw"):
             raise ValueError(f"layout must be 'nhwc' or 'nchw', got {layout!r}")
         self.nchw = layout == "nchw"
-        self.slots = [_Slot(batch_size, H, W, cfile, self.C, dtype, self.device, self.nchw) for _ in range(max(2, depth))]
+        self.labels = bool(getattr(dataset, "labels", True))
+        self.slots = [_Slot(batch_size, H, W, cfile, self.C, dtype, self.device, self.nchw, self.labels) for _ in range(max(2, depth))]
+        self.n_valid = 0
         self.shift = torch.from_numpy(np.asarray(dataset.data_shift, np.float32)).to(self.device)
         self.scale = torch.from_numpy(np.asarray(dataset.data_scale, np.float32)).to(self.device)
         ident = list(dataset.channels) == list(range(cfile))
@@ -253,7 +267,8 @@ class InputPipeline:
                 if slot is None or stop.is_set():
                     return
                 slot.consumed.synchronize()                       # host wait: the GPU is done with this slot's tensors
-                dn, ln = slot.data_host.numpy(), slot.label_host.numpy()
+                dn = slot.data_host.numpy()
+                ln = slot.label_host.numpy() if self.labels else [None] * self.B
                 # drop_last=False: the last batch may hold fewer samples than slots; the remaining slots repeat its last sample (the batch
                 # keeps its shape) and `names` lists the valid samples only -- len(names) is the batch's n_valid
                 nv = min(self.B, len(self.ds) - b * self.B)
@@ -303,7 +318,8 @@ class InputPipeline:
                 raise item
             with torch.cuda.stream(self.copy_stream):
                 item.data_dev.copy_(item.data_host, non_blocking=True)
-                item.label.copy_(item.label_host, non_blocking=True)
+                if self.labels:
+                    item.label.copy_(item.label_host, non_blocking=True)
                 if self.nchw:
                     L.call("dc_input_normalize_hwc_to_nchw", self.B, self.H * self.W, self.cfile, self.C, L.dptr(self.channels),
                            L.dptr(item.data_dev), L.dptr(self.shift), L.dptr(self.scale), L.dptr(item.x),
@@ -329,6 +345,7 @@ class InputPipeline:
                     more = stage_next()                                  # batch i+1 is in flight while batch i trains
                 torch.cuda.current_stream().wait_event(cur.ready)
                 self._prev = cur
+                self.n_valid = len(cur.names)
                 yield cur.x, cur.label, cur.names
             if self._prev is not None:
                 self._release(self._prev, free_q)

@@ -185,7 +185,8 @@ class Engine:
         program, gradient buffers, statistics slabs or second stream; the activations share one arena by their lives (_plan_pool); every
         BatchNorm's eval coefficients come from ONE launch beside the weight repack (dc_bn_eval_coeffs_all), i.e. whenever the shared version
         counter says that weights or running statistics have changed; and with score_args set the classifier's kernel leaves the per-sample
-        loss sums and IoU counts (dc_head_fwd_score).  forward(train=True) and backward() raise."""
+        loss sums and IoU counts (dc_head_fwd_score), with predict_args set the class map, its confidence and the per-sample class counts
+        (dc_head_fwd_predict); the two together raise.  forward(train=True) and backward() raise."""
         if not torch.cuda.is_available():
             raise L.DeepcamHipError("mlperf_deepcam_amd.Engine needs a HIP device: there is no CPU path")
         L.load()
@@ -206,6 +207,7 @@ class Engine:
         self._bn_eval_entries: List[L.BnEvalEntry] = []
         self._arena: Optional[torch.Tensor] = None
         self.score_args: Optional[dict] = None        # set per call by nn.ValStep: per-sample loss sums and counts behind the classifier
+        self.predict_args: Optional[dict] = None      # set per call by nn.Predictor: class map, confidence and class counts behind the classifier
         self.closed = False
         lay = self.layout
         self.act_bytes = 0
@@ -1006,7 +1008,7 @@ class Engine:
         self.x0 = self._x0_own = self._stem_out = self._layout_op = self.x_in = None
         self._arena = self._sum_arena = self._pack_table = self._bn_table = None
         self.logits = self.dlogits = self.x_static = self.workspace = self.workspace2 = self.side = None
-        self.on_grad_ready = self.loss_args = self.score_args = None
+        self.on_grad_ready = self.loss_args = self.score_args = self.predict_args = None
 
     def _build_network(self) -> None:
         lib = L.load()
@@ -1201,6 +1203,10 @@ class Engine:
             # the validation step (nn.ValStep) hands the score arguments over: per-sample loss sums and IoU counts of the first n_valid samples,
             # in the classifier's kernel on the logits it has in registers (bf16: dc_head_fwd_score), or by dc_wce_score on the stored ones (fp32)
             sa = self.score_args
+            if self.predict_args is not None:
+                if sa is not None:
+                    raise L.DeepcamHipError("a forward-only engine either scores against labels (score_args) or predicts (predict_args), not both")
+                return head_fwd_predict()
             if sa is None:
                 return head_fwd()
             lab, nv = sa["labels"], sa["n_valid"]
@@ -1215,6 +1221,24 @@ class Engine:
                        self.pptr(wl), lg, hptr, *tail)
                 return
             L.call("dc_head_fwd_score", self.dt, B, nv, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), lg, hptr, *tail)
+
+        def head_fwd_predict():
+            # inference (nn.Predictor) hands the prediction arguments over: the class map, its confidence and the per-sample class counts of the
+            # first n_valid samples, in the classifier's kernel on the logits it has in registers (bf16: dc_head_fwd_predict), or by
+            # dc_logits_predict on the stored ones (fp32; bf16 with the head_fused switch off stores them inside dc_head_fwd_predict)
+            pa = self.predict_args
+            nv = pa["n_valid"]
+            tail = (L.dptr(pa["mask"]), L.dptr(pa["conf"]), L.dptr(pa["class_counts"]), self._st())
+            if self.dt != L.DC_BF16:
+                head_fwd()
+                L.call("dc_logits_predict", B, nv, H, W, L.dptr(self.logits), *tail)
+                return
+            lg = L.dptr(self.logits) if pa["store_logits"] else None
+            if lazy_in:
+                L.call("dc_head_fwd_predict_bnin", self.dt, B, nv, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
+                       self.pptr(wl), lg, hptr, *tail)
+                return
+            L.call("dc_head_fwd_predict", self.dt, B, nv, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), lg, hptr, *tail)
 
         self.fwd_train.append(head_fwd_train)
         self.fwd_eval.append(head_fwd_score if self.forward_only else head_fwd)

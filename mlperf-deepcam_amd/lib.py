@@ -143,6 +143,8 @@ _SIGS = {
     "dc_head_fwd_loss_bnin": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, P, I, P, F, P, P, P, P, P]),
     "dc_head_fwd_score": (I, [I, I, I, I, I, I, P, I, P, P, P, P, I, P, P, P, P]),
     "dc_head_fwd_score_bnin": (I, [I, I, I, I, I, I, P, I, P, P, I, P, P, P, P, I, P, P, P, P]),
+    "dc_head_fwd_predict": (I, [I, I, I, I, I, I, P, I, P, P, P, P, P, P, P]),
+    "dc_head_fwd_predict_bnin": (I, [I, I, I, I, I, I, P, I, P, P, I, P, P, P, P, P, P, P]),
     "dc_head_bwd_bnin": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, I, P, P, P, P, P, I, P]),
     "dc_head_bwd_bnin_apply": (I, [I, I, I, I, I, P, I, P, P, I, P, P, P, P, P, L, P, I, P, P]),
     "dc_nchw_to_nhwc": (I, [I, I, I, I, I, P, P, I, P]),
@@ -152,6 +154,7 @@ _SIGS = {
     "dc_confusion_counts": (I, [L, P, P, I, P, P]),
     "dc_wce_score": (I, [I, I, I, I, P, P, I, P, P, P, P]),
     "dc_val_accumulate": (I, [I, I, L, P, P, P, P, P]),
+    "dc_logits_predict": (I, [I, I, I, I, P, P, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

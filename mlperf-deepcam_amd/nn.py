@@ -824,3 +824,81 @@ class ValStep:
 
     def close(self) -> None:
         self.eng.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# inference on unlabelled data
+# ------------------------------------------------------------------------------------------------------------------
+def predict_from_logits(logits: torch.Tensor, confidence: bool = False, n_valid: Optional[int] = None):
+    """(mask uint8 [B,H,W], confidence fp32 [B,H,W] or None, class_counts int64 [B,3]) of fp32 NCHW logits [B,3,H,W] (dc_logits_predict):
+    the first-max class of torch.max(logits, 1)[1] (train_hdf5_ddp.py:458) as one byte, its softmax probability, the pixels per class and
+    sample.  Samples from n_valid on are not read; their rows of the outputs are zero."""
+    if logits.dim() != 4 or logits.size(1) != 3 or not logits.is_cuda:
+        raise L.DeepcamHipError(f"predict_from_logits: logits must be a device tensor [B, 3, H, W], got {tuple(logits.shape)} on {logits.device}")
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        logits = logits.float().contiguous()
+    B, _, H, W = logits.shape
+    nv = B if n_valid is None else int(n_valid)
+    mask = torch.zeros((B, H, W), dtype=torch.uint8, device=logits.device)
+    conf = torch.zeros((B, H, W), dtype=torch.float32, device=logits.device) if confidence else None
+    counts = torch.zeros((B, 3), dtype=torch.int64, device=logits.device)
+    L.call("dc_logits_predict", B, nv, H, W, L.dptr(logits), L.dptr(mask), L.dptr(conf), L.dptr(counts), L.stream_ptr())
+    return mask, conf, counts
+
+
+class Predictor:
+    """Masks for unlabelled data: the eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running
+    statistics through the shared arena, pooled activations) whose classifier leaves, per pixel, the first-max class as one byte
+    (torch.max(outputs, 1)[1] of train_hdf5_ddp.py:458), optionally its softmax probability, and per sample the pixels of each class
+    (bf16: dc_head_fwd_predict on the logits in registers; fp32: dc_head_fwd + dc_logits_predict).  Nothing here synchronises."""
+
+    def __init__(self, net: DeepLabv3_plus, batch: int, height: int, width: int, confidence: bool = False):
+        if net.engine is None:
+            raise L.DeepcamHipError("Predictor: materialize the model first (its parameters live in the primary engine's arena)")
+        self.net, self.B, self.H, self.W = net, batch, height, width
+        self.eng = Engine(batch, height, width, net.act_dtype, n_input=net.n_input, n_classes=net.n_classes, share_from=net.engine,
+                          forward_only=True)
+        dev = self.eng.device
+        self._mask = torch.zeros((batch, height, width), dtype=torch.uint8, device=dev)
+        self._conf = torch.zeros((batch, height, width), dtype=torch.float32, device=dev) if confidence else None
+        self._counts = torch.zeros((batch, 3), dtype=torch.int64, device=dev)
+        self._last_valid = 0
+        self.store_logits = False       # bf16: also write the fp32 NCHW logits (the prediction needs them in registers only)
+        self._eng_handle = _ops.engine_handle(self.eng)
+
+    def __call__(self, x: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
+        """x: the NCHW fp32 batch or the input pipeline's NHWC batch (Engine.forward); returns the uint8 mask [n_valid, H, W], a view of a
+        buffer this object owns (the next call overwrites it).  The samples from n_valid on are padding: the network's body computes
+        them, the classifier does not, and their bytes in the buffers stay as they were."""
+        eng, B = self.eng, self.B
+        nv = B if n_valid is None else int(n_valid)
+        if not 0 < nv <= B:
+            raise L.DeepcamHipError(f"Predictor: n_valid must lie in [1, {B}], got {n_valid}")
+        L.call("dc_memset_async", L.dptr(self._counts), 0, 24 * nv, L.stream_ptr())
+        eng.predict_args = {"n_valid": nv, "mask": self._mask, "conf": self._conf, "class_counts": self._counts,
+                            "store_logits": self.store_logits}
+        try:
+            _ops.OPS.net_forward(x, self._eng_handle, False)
+        finally:
+            eng.predict_args = None
+        self._last_valid = nv
+        return self._mask[:nv]
+
+    @property
+    def confidence(self) -> Optional[torch.Tensor]:
+        """fp32 [n_valid, H, W] of the last call: the predicted class's softmax probability (None unless built with confidence=True)"""
+        return None if self._conf is None else self._conf[:self._last_valid]
+
+    @property
+    def class_counts(self) -> torch.Tensor:
+        """int64 [n_valid, 3] of the last call: pixels per class and sample"""
+        return self._counts[:self._last_valid]
+
+    @property
+    def logits(self) -> torch.Tensor:
+        """the engine's fp32 NCHW logits of the last call (fp32 engines always; bf16 with store_logits=True), valid samples only"""
+        return self.eng.logits[:self._last_valid]
+
+    def close(self) -> None:
+        self.eng.close()
+        self._mask = self._conf = self._counts = None
