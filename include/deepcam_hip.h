@@ -40,6 +40,41 @@ int dc_set_option(const char* name, int value);
 /* Every dc_set_option switch back to its default (the library's own table; also what a freshly loaded library holds). */
 int dc_reset_options(void);
 
+/* Launch record (tests): which kernel served each call.  Several kernel families stand behind one entry point, chosen on the host by
+ * eligibility predicates, a cost model and the switches above; between dc_launch_log_begin and dc_launch_log_end every launch the CALLING
+ * THREAD issues through this library notes the name of its family.  Host state only, thread-local, off by default; nothing changes on the
+ * device.  A recorded launch list (dc_program_run) replays through the same entry points and is recorded like direct calls; replaying a
+ * captured graph launches nothing from the library and leaves no names.
+ *   dc_launch_log_begin  starts an empty record; an error while one is open on this thread.
+ *   dc_launch_log_end    stops recording and writes the names in launch order, joined by '\n', into buf (NUL-terminated; no launches: "").
+ *                        An error when no record is open, when cap is too small for the names, or when more launches were issued than the
+ *                        fixed-size record holds (4096); the record is closed in every case.
+ * The names, one per family and template variant the dispatcher distinguishes:
+ *   dense forward / data gradient (dc_conv_fwd*, dc_conv_dgrad*):
+ *     tiny_gemm                             at most 16 pixels of a pointwise layer
+ *     thin_fwd, thin_tile                   the thin stem convolutions: gather form, LDS-tiled form
+ *     igemm128_bf16, igemm128_f32           128 x 128 tiles; igemm128_bf16_zfill / igemm128_f32_zfill: one launch over phase (0, 0) that
+ *     igemm128_f32out                       zero-fills the three empty phases; _f32out: bf16 operands, fp32 output
+ *     igemm256, igemm256p                   256 x 256 tiles; the persistent form
+ *     igemm256_splitk, igemm256_splitk_fold 256 x 256 tiles cut along K, and the kernel that sums the cuts
+ *     pw384_256, pw384_128, pw384_256_k64   pointwise, 384 channels wide: 256- / 128-pixel tiles of 32-deep stages, 256-pixel tiles of 64-deep stages
+ *     pw224_384, pw224_192, pw192           pointwise, 224-pixel tiles 384 / 192 channels wide; 128 x 192 tiles
+ *   dense weight gradient (dc_conv_wgrad*):
+ *     thin_wgrad                            the stem layers' one-pass kernel
+ *     wgrad384_pw, wgrad384_3x3, wgrad384_convT   256 x 384 tiles: pointwise, 3 x 3 "same", ConvTranspose2d
+ *     wgrad128_bf16, wgrad128_f32, wgrad128_bnin  the plain split kernels on 128 x 128 tiles; _bnin: operand transformed while staged
+ *     wgrad_reduce, fold                    the sum over the splits of one layer; dc_fold_slabs
+ *   depthwise (dc_dwconv_*), each as _fwd / _dgrad / _wgrad:
+ *     dw_reg_*, dw_win_*                    register kernels: any stride and dilation; the stride-1 window (dw_reg_reduce sums their wgrad rows)
+ *     dw_tile_*, dw_tile_s2_*               LDS-tiled kernels, stride 1 and stride 2 (dw_tile_reduce sums their wgrad rows)
+ *     dwpipe_fwd, dwpipe_dgrad              the persistent pipelined kernel (its data gradient carries the weight-gradient rows)
+ *   head: head_fwd_fused | the GEMM's name then head_combine; head_dgrad_stream, head_dgrad_stream_wgrad (weight gradient riding along),
+ *     head_dgrad_apply | the GEMM's name
+ *   BatchNorm apply: bn_apply_rows, bn_apply
+ *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
+int dc_launch_log_begin(void);
+int dc_launch_log_end(char* buf, size_t cap);
+
 /* Streams for the host runtime.  The reference leaves stream management to PyTorch/apex (its DDP overlaps the all-reduce
  * on a side stream, train_hdf5_ddp.py:227,363); here the weight-gradient kernels run beside the backward chain on a stream
  * of the LOWEST priority (level < 0; 0 = default, > 0 = highest), created non-blocking.  The caller owns the stream. */

@@ -34,6 +34,54 @@ extern "C" int dc_check_view(const void* ptr, int ld, int c, int dtype, const ch
   return -3;
 }
 
+// ---- launch record: which kernel family served each call (tests).  Thread-local like the error string; the launch sites (DC_LAUNCHED,
+// common.h) test g_launch_log_on and call launch_log_note with a string literal, so the record keeps pointers only.
+namespace dc {
+thread_local bool g_launch_log_on = false;
+static constexpr int kLaunchLogCap = 4096;
+static thread_local const char* g_launch_log[kLaunchLogCap];
+static thread_local int g_launch_log_n = 0;            // launches noted since _begin (may exceed the capacity: overflow)
+static thread_local bool g_launch_log_open = false;    // between _begin and _end (stays true when an overflow stopped the notes)
+void launch_log_note(const char* name) {
+  if (g_launch_log_n < kLaunchLogCap) g_launch_log[g_launch_log_n] = name;
+  ++g_launch_log_n;
+}
+}  // namespace dc
+
+extern "C" int dc_launch_log_begin(void) {
+  if (dc::g_launch_log_open) return dc_fail("dc_launch_log_begin: a record is already open on this thread (dc_launch_log_end closes it)", __FILE__, __LINE__);
+  dc::g_launch_log_open = dc::g_launch_log_on = true;
+  dc::g_launch_log_n = 0;
+  return 0;
+}
+
+extern "C" int dc_launch_log_end(char* buf, size_t cap) {
+  if (!dc::g_launch_log_open) return dc_fail("dc_launch_log_end: no record is open on this thread (dc_launch_log_begin opens one)", __FILE__, __LINE__);
+  dc::g_launch_log_open = dc::g_launch_log_on = false;      // whatever follows, the record is closed
+  const int n = dc::g_launch_log_n;
+  if (n > dc::kLaunchLogCap) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "dc_launch_log_end: %d launches overflowed the record of %d", n, dc::kLaunchLogCap);
+    return dc_fail(msg, __FILE__, __LINE__);
+  }
+  size_t need = 1;
+  for (int i = 0; i < n; ++i) need += strlen(dc::g_launch_log[i]) + (i ? 1 : 0);
+  if (buf == nullptr || cap < need) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "dc_launch_log_end: the buffer holds %zu bytes, the record of %d launches needs %zu", buf ? cap : (size_t)0, n, need);
+    return dc_fail(msg, __FILE__, __LINE__);
+  }
+  char* o = buf;
+  for (int i = 0; i < n; ++i) {
+    if (i) *o++ = '\n';
+    const size_t l = strlen(dc::g_launch_log[i]);
+    memcpy(o, dc::g_launch_log[i], l);
+    o += l;
+  }
+  *o = 0;
+  return 0;
+}
+
 // A non-blocking HIP stream at the lowest (level < 0), default (0) or highest (level > 0) priority the device offers.  The
 // engine puts the weight-gradient work on a lowest-priority stream so that it fills the CUs the dependent backward chain
 // leaves idle instead of competing with it workgroup for workgroup.

@@ -662,7 +662,7 @@ static int bn_apply_impl(int dtype, long M, int C, const void* y, int ldy, const
       if (dtype == DC_BF16) { if (cgw == 32) BN_AR(bf16, 32); else if (cgw == 16) BN_AR(bf16, 16); else if (cgw == 8) BN_AR(bf16, 8); else BN_AR(bf16, 4); }
       else                  { if (cgw == 32) BN_AR(float, 32); else if (cgw == 16) BN_AR(float, 16); else if (cgw == 8) BN_AR(float, 8); else BN_AR(float, 4); }
 #undef BN_AR
-      DC_CHECK_LAUNCH();
+      DC_LAUNCHED("bn_apply_rows");
       return 0;
     }
   }
@@ -677,7 +677,7 @@ static int bn_apply_impl(int dtype, long M, int C, const void* y, int ldy, const
     hipLaunchKernelGGL(bn_apply_kernel<bf16>, dim3(blocks), dim3(256), 0, st, M, C, (const bf16*)y, ldy, scale, shift, (const bf16*)residual, ldr, relu, (bf16*)out, ldo);
   else
     hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(blocks), dim3(256), 0, st, M, C, (const float*)y, ldy, scale, shift, (const float*)residual, ldr, relu, (float*)out, ldo);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("bn_apply");
   return 0;
 }
 

@@ -129,11 +129,22 @@ const void* zero_page(hipError_t* err);
     std::call_once(once_flag__, [&] { __VA_ARGS__; }); \
   } while (0)
 
-#define DC_CHECK_LAUNCH()                                  \
+// The launch record (dc_launch_log_begin / dc_launch_log_end, api.cpp): while the calling thread records, every launch site notes the name
+// of the kernel family that serves the call (the vocabulary: include/deepcam_hip.h).  Host state only; switched off it is this one branch.
+namespace dc {
+extern thread_local bool g_launch_log_on;
+void launch_log_note(const char* name);
+}  // namespace dc
+
+// after a launch: fail on a launch error, else note `name` (a string literal) in the launch record
+#define DC_LAUNCHED(name)                                  \
   do {                                                     \
     hipError_t e__ = hipGetLastError();                    \
     if (e__ != hipSuccess) return dc_set_error(e__, __FILE__, __LINE__); \
+    if (dc::g_launch_log_on) dc::launch_log_note(name);    \
   } while (0)
+// a launch site no option or planner chooses: the generic name
+#define DC_CHECK_LAUNCH() DC_LAUNCHED("aux")
 
 extern "C" int dc_set_error(int code, const char* file, int line);
 extern "C" int dc_fail(const char* msg, const char* file, int line);

@@ -432,7 +432,7 @@ static int launch_dw(const void* in, int ldin, const float* w, const void* adden
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipLaunchKernelGGL((dw_kernel<T, MODE>), dim3((int)blocks), dim3(256), 0, st, (const T*)in, ldin, w,
                      (const T*)addend, ldadd, (T*)out, ldout, N, Hin, Win, Hout, Wout, C, stride, dil, pscale, pshift, prelu);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(MODE == 0 ? "dw_reg_fwd" : "dw_reg_dgrad");
   return 0;
 }
 
@@ -453,7 +453,7 @@ static int launch_dw_s1(int dtype, int dil, bool flip, const void* in, int ldin,
     else          { if (flip) DW_S1(float, 2, true); else DW_S1(float, 2, false); }
   }
 #undef DW_S1
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(flip ? "dw_win_dgrad" : "dw_win_fwd");
   return 0;
 }
 
@@ -767,9 +767,9 @@ extern "C" int dc_dwconv_wgrad(int dtype, int C, int stride, int dil, int N, int
     if (dtype == DC_BF16) { if (dil == 1) DW_WS1(bf16, 1); else DW_WS1(bf16, 2); }
     else                  { if (dil == 1) DW_WS1(float, 1); else DW_WS1(float, 2); }
 #undef DW_WS1
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("dw_win_wgrad");
     hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv(9 * C, 8)), dim3(256), 0, st, (const float*)workspace, grad_w, frows, C);
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("dw_reg_reduce");
     return 0;
   }
   dim3 grid(cdiv(C / kpv, cgw), rows);
@@ -780,8 +780,8 @@ extern "C" int dc_dwconv_wgrad(int dtype, int C, int stride, int dil, int N, int
     if (cgw == 64) DW_WG(float, 64); else if (cgw == 32) DW_WG(float, 32); else if (cgw == 16) DW_WG(float, 16); else DW_WG(float, 8);
   }
 #undef DW_WG
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("dw_reg_wgrad");
   hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv(9 * C, 8)), dim3(256), 0, st, (const float*)workspace, grad_w, rows, C);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("dw_reg_reduce");
   return 0;
 }

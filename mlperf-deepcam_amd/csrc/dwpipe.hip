@@ -491,7 +491,7 @@ int launch1(const DwpArgs& a, int grid, hipStream_t st) {
   static_assert(16 * 9 * P_CH * 4 <= LDS, "the fold's scratch lives in the drained ring");
   DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwp_kernel<DIL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
   hipLaunchKernelGGL((dwp_kernel<DIL, MODE>), dim3(grid), dim3(P_THREADS), LDS, st, a);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED((MODE & PM_FLIP) ? "dwpipe_dgrad" : "dwpipe_fwd");
   return 0;
 }
 

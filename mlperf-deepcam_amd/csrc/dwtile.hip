@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void dwt_reduce_kernel(const float* __restrict
 
 int dw_tile_reduce(const float* slab, float* grad_w, int rows, int C, hipStream_t st) {
   hipLaunchKernelGGL(dwt_reduce_kernel, dim3(cdiv(9 * C, 16)), dim3(256), 0, st, slab, grad_w, rows, C);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("dw_tile_reduce");
   return 0;
 }
 
@@ -542,7 +542,7 @@ int launch_dw_tile(int dtype, int dil, bool flip, const void* in, int ldin, cons
     else          { if (flip) DWT(float, 2, true); else DWT(float, 2, false); }
   }
 #undef DWT
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(flip ? "dw_tile_dgrad" : "dw_tile_fwd");
   return 0;
 }
 
@@ -579,9 +579,9 @@ int launch_dw_tile_wgrad(int dtype, int dil, const void* x, int ldx, const void*
     if (dil == 1) launch_wg2<float, 1>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
     else launch_wg2<float, 2>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
   }
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("dw_tile_wgrad");
   hipLaunchKernelGGL(dwt_reduce_kernel, dim3(cdiv(9 * C, 16)), dim3(256), 0, st, (const float*)slab, grad_w, rows, C);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("dw_tile_reduce");
   return 0;
 }
 

@@ -486,7 +486,7 @@ int launch_dw_tile_s2(int dtype, int mode, int N, int Hi, int Wi, int C, const v
   if (dtype == DC_BF16) launch2<bf16>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, &rows, st, bs);
   else launch2<float>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, &rows, st, bs);
   if (rows_out) *rows_out = rows;
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(mode == 0 ? "dw_tile_s2_fwd" : mode == 1 ? "dw_tile_s2_dgrad" : "dw_tile_s2_wgrad");
   return 0;
 }
 

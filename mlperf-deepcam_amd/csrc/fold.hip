@@ -160,7 +160,7 @@ extern "C" int dc_fold_slabs(const dc_fold_entry* entries, int n, void* stream) 
     DC_REQUIRE(blocks < (1L << 31), "dc_fold_slabs: too many blocks");
     if (blocks == 0) continue;
     hipLaunchKernelGGL(fold_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("fold");
   }
   return 0;
 }

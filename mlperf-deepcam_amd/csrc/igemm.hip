@@ -426,7 +426,9 @@ static int launch_igemm(const IgemmParams& p, hipStream_t st) {
   DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, OUT32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid(cdiv(p.g.Cout, BN) * cdiv(p.M - p.m_beg, BM) * (p.zfill ? 1 : p.g.os * p.g.os));
   hipLaunchKernelGGL((igemm_kernel<T, OUT32>), grid, dim3(256), lds, st, p);
-  DC_CHECK_LAUNCH();
+  if (OUT32) DC_LAUNCHED("igemm128_f32out");
+  else if (sizeof(T) == 2) DC_LAUNCHED(p.zfill ? "igemm128_bf16_zfill" : "igemm128_bf16");
+  else DC_LAUNCHED(p.zfill ? "igemm128_f32_zfill" : "igemm128_f32");
   return 0;
 }
 
@@ -521,7 +523,7 @@ static int run_gather(const dc_conv_desc* d, GatherMode mode, int N, int Hi, int
   if (!sum_row && bst == nullptr && !out32 && p.M <= TINY_M && p.g.ntaps == 1 && p.g.os == 1 && p.g.is == 1 && p.g.taps[0].dy == 0 && p.g.taps[0].dx == 0) {
     if (d->dtype == DC_BF16) hipLaunchKernelGGL(tiny_gemm_kernel<bf16>, dim3(cdiv(p.g.Cout, 4)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(tiny_gemm_kernel<float>, dim3(cdiv(p.g.Cout, 4)), dim3(256), 0, st, p);
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("tiny_gemm");
     return 0;
   }
   if (!sum_row && bst == nullptr && thin_fwd_eligible(p.g, d->dtype, bias != nullptr, accumulate, out32))

@@ -180,7 +180,7 @@ int launch_pw192(const IgemmParams& p_in, hipStream_t st) {
   p.zero_page = zero_page(&zerr);
   if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   hipLaunchKernelGGL(pw192_kernel, dim3((unsigned)pw192_tiles(p)), dim3(512), RING, st, p);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("pw192");
   return 0;
 }
 

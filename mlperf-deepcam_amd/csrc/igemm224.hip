@@ -475,7 +475,7 @@ int launch_pw224(const IgemmParams& p, int tn, hipStream_t st) {
   });
   if (tn == 192) hipLaunchKernelGGL(k192, dim3((unsigned)pw224_tiles(p, 192)), dim3(512), Cfg<192>::RING, st, p);
   else hipLaunchKernelGGL(k384, dim3((unsigned)pw224_tiles(p, 384)), dim3(512), Cfg<384>::RING, st, p);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(tn == 192 ? "pw224_192" : "pw224_384");
   return 0;
 }
 

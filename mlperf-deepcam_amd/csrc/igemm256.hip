@@ -552,7 +552,7 @@ int launch_igemm256(const IgemmParams& p_in, hipStream_t st) {
   p.zero_page = zero_page(&zerr);
   if (zerr != hipSuccess) return dc_set_error(zerr, __FILE__, __LINE__);
   hipLaunchKernelGGL(igemm256_kernel, dim3((unsigned)(igemm256_tiles(p) * (p.ksplit > 1 ? p.ksplit : 1))), dim3(512), lds, st, p);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(p.ksplit > 1 ? "igemm256_splitk" : "igemm256");
   return 0;
 }
 
@@ -569,7 +569,7 @@ int launch_igemm256_splitk(const IgemmParams& p_in, int splits, void* ws, hipStr
     a.slab[b] = b == 0 ? p.slab : p.gslab[b - 1];
   }
   hipLaunchKernelGGL(igemm256_splitk_fold_kernel, dim3((unsigned)(2 * a.tiles_per_split)), dim3(256), 0, st, a);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("igemm256_splitk_fold");
   return 0;
 }
 

@@ -488,7 +488,7 @@ int launch_igemm256p(const IgemmParams& p_in, int workgroups, hipStream_t st) {
   if (wgs < 8) wgs = 8;
   if (a.slab != nullptr) hipLaunchKernelGGL(igemm256p_kernel<true>, dim3((unsigned)wgs), dim3(512), lds, st, a);
   else hipLaunchKernelGGL(igemm256p_kernel<false>, dim3((unsigned)wgs), dim3(512), lds, st, a);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("igemm256p");
   return 0;
 }
 

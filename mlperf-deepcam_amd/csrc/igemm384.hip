@@ -263,7 +263,7 @@ int launch_pw384(const IgemmParams& p_in, int npb, hipStream_t st) {
   if (npb == 64) hipLaunchKernelGGL(k64, dim3((unsigned)tiles), dim3(512), C64::RING, st, p);
   else if (npb == 8) hipLaunchKernelGGL(k8, dim3((unsigned)tiles), dim3(512), C8::RING, st, p);
   else hipLaunchKernelGGL(k4, dim3((unsigned)tiles), dim3(512), C4::RING, st, p);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(npb == 64 ? "pw384_256_k64" : npb == 8 ? "pw384_256" : "pw384_128");
   return 0;
 }
 

@@ -907,7 +907,7 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
         hipLaunchKernelGGL(k7, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, *hp);
       else
         hipLaunchKernelGGL(k6, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, *hp);
-      DC_CHECK_LAUNCH();
+      DC_LAUNCHED("head_fwd_fused");
       return 0;
     }
     if (n_score >= 0) {
@@ -917,7 +917,7 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
         hipLaunchKernelGGL(k5, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
       else
         hipLaunchKernelGGL(k4, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
-      DC_CHECK_LAUNCH();
+      DC_LAUNCHED("head_fwd_fused");
       return 0;
     }
     if (bi != nullptr) {
@@ -925,14 +925,14 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
         hipLaunchKernelGGL(k3, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
       else
         hipLaunchKernelGGL(k2, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, HeadPredict{});
-      DC_CHECK_LAUNCH();
+      DC_LAUNCHED("head_fwd_fused");
       return 0;
     }
     if (hl != nullptr)
       hipLaunchKernelGGL(k1, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
     else
       hipLaunchKernelGGL(k0, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, HeadPredict{});
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("head_fwd_fused");
     return 0;
   }
   DC_REQUIRE(bi == nullptr, "dc_head_fwd_bnin: only the fused bf16 head kernel (256 input channels) applies the BatchNorm while loading");
@@ -941,7 +941,7 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   if (int e = dc_conv_fwd_f32out(&d, N, Hi, Wi, x, ldx, ws.wf, ws.P, HEAD_NP, stream)) return e;
   const long P = (long)N * Hi * Wi;
   hipLaunchKernelGGL(head_combine_kernel, dim3(cdiv(P, 256)), dim3(256), 0, st, (const float*)ws.P, logits_nchw, N, Hi, Wi);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("head_combine");
   if (hp != nullptr)     // (the whole batch's logits exist here; the prediction reads the valid samples)
     return dc_logits_predict(N, n_score, 2 * Hi, 2 * Wi, logits_nchw, hp->mask, hp->conf, (int64_t*)hp->counts, stream);
   if (n_score >= 0)      // (the whole batch's logits exist here; the score reads the valid samples)
@@ -1327,7 +1327,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
       static_assert(HEAD_NP == 32, "product image");
       DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_dgrad_kernel<HD_SUMS_WG>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * TRI_QUAD));
       hipLaunchKernelGGL(head_dgrad_kernel<HD_SUMS_WG>, dim3(g2), dim3(256), 4 * 2 * TRI_QUAD, st, (const bf16*)ws.dP, (const bf16*)ws.wb, (bf16*)nullptr, 0, (long)P, b);
-      DC_CHECK_LAUNCH();
+      DC_LAUNCHED("head_dgrad_stream_wgrad");
       const long nw = (long)HEAD_NP * Cin;
       hipLaunchKernelGGL(slab_rows_reduce_kernel, dim3(cdiv(nw, 8)), dim3(256), 0, st, (const float*)ws.P, ws.tmp, g2, nw);
       hipLaunchKernelGGL(head_wfinish_kernel, dim3(cdiv(Cin * HEAD_NC * 9, 256)), dim3(256), 0, st, (const float*)ws.tmp, grad_w, Cin);
@@ -1338,7 +1338,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
       hipLaunchKernelGGL(head_dgrad_kernel<HD_STORE>, dim3(grid), dim3(256), 0, st, (const bf16*)ws.dP, (const bf16*)ws.wb, (bf16*)dx, lddx, (long)P, b);
     else
       hipLaunchKernelGGL(head_dgrad_kernel<HD_SUMS>, dim3(grid), dim3(256), 0, st, (const bf16*)ws.dP, (const bf16*)ws.wb, (bf16*)nullptr, 0, (long)P, b);
-    DC_CHECK_LAUNCH();
+    DC_LAUNCHED("head_dgrad_stream");
     return 0;
   }
   if (bn_y != nullptr && bn_slab != nullptr)
@@ -1392,7 +1392,7 @@ extern "C" int dc_head_bwd_bnin_apply(int dtype, int N, int Cin, int Hi, int Wi,
   const HeadDgradBst b{(const bf16*)y, ldy, bn_mean, bn_invstd, scale, shift, relu, nullptr, chunks, gamma, dgamma, dbeta, 1.0f / (float)count};
   hipLaunchKernelGGL(head_dgrad_kernel<HD_APPLY>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)ws.dP, (const bf16*)ws.wb, (bf16*)dy,
                      lddy, (long)P, b);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("head_dgrad_apply");
   return 0;
 }
 

@@ -551,7 +551,7 @@ int launch_thin_wgrad(const dc_conv_desc& d, int N, int Hi, int Wi, const void* 
     DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_wgrad_kernel<32, 64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
     hipLaunchKernelGGL((thin_wgrad_kernel<32, 64, 1>), dim3(p.blocks), dim3(256), K::LDS, st, a);
   }
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("thin_wgrad");
   return 0;
 }
 
@@ -596,7 +596,7 @@ int launch_thin_fwd(const GatherGeom& g, int N, const void* in, int ldin, const 
   else { if (tiled) THIN_TILE(64, 32); else THIN_FWD(64, 32); }
 #undef THIN_TILE
 #undef THIN_FWD
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(tiled ? "thin_tile" : "thin_fwd");
   return 0;
 }
 

@@ -479,7 +479,7 @@ static int launch_wgrad_reduce(const float* slab, float* grad_w, int splits, con
   const long work = (per >> 2) * g.ntaps;
   const int blocks = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, grad_w, splits, g.ntaps, g.Cout, g.Cin, transposed);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED("wgrad_reduce");
   return 0;
 }
 
@@ -529,11 +529,9 @@ static int plan_wgrad(const dc_conv_desc* d, int N, int Hi, int Wi, bool transfo
 static int launch_wgrad_partial(const dc_conv_desc* d, const WgradParams& p, WgradKernel kind, int N, int Hi, int Wi, hipStream_t st, int group = 1,
                                 const void* const* xs = nullptr, const void* const* dys = nullptr, float* const* slabs = nullptr) {
   dim3 grid(cdiv(p.g.Cin, 128) * cdiv(p.g.Cout, 128) * p.g.ntaps * p.splits);
-  if (kind == WK_THIN) {
-    if (int e = launch_thin_wgrad(*d, N, Hi, Wi, p.x, p.ldx, p.dy, p.lddy, p.slab, st)) return e;
-  } else if (kind == WK_256) {
-    if (int e = launch_wgrad_big(p, st, group, xs, dys, slabs)) return e;
-  } else if (kind == WK_DMA) {
+  if (kind == WK_THIN) return launch_thin_wgrad(*d, N, Hi, Wi, p.x, p.ldx, p.dy, p.lddy, p.slab, st);
+  if (kind == WK_256) return launch_wgrad_big(p, st, group, xs, dys, slabs);
+  if (kind == WK_DMA) {
     const size_t lds = 3 * 2 * 8192;
     if (d->dtype == DC_BF16) {
       DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -542,12 +540,13 @@ static int launch_wgrad_partial(const dc_conv_desc* d, const WgradParams& p, Wgr
       DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(wgrad_dma_kernel<float>, grid, dim3(256), lds, st, p);
     }
+    DC_LAUNCHED(d->dtype == DC_BF16 ? "wgrad128_bf16" : "wgrad128_f32");
   } else {      // WK_REG: the operand transform, bf16 only (conv_wgrad_impl)
     const size_t lds = 4 * (size_t)WG_REG_BP * WG_REG_ROW;
     DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), lds, st, p);
+    DC_LAUNCHED("wgrad128_bnin");
   }
-  DC_CHECK_LAUNCH();
   return 0;
 }
 

@@ -393,7 +393,7 @@ int launch_wgrad384(const WgradParams& w, hipStream_t st, int group, const void*
     hipLaunchKernelGGL(wgrad384_kernel<2>, dim3((unsigned)blocks), dim3(512), lds, st, pp);
   } else if (g.ntaps == 1) hipLaunchKernelGGL(wgrad384_kernel<0>, dim3((unsigned)blocks), dim3(512), lds, st, pp);
   else hipLaunchKernelGGL(wgrad384_kernel<1>, dim3((unsigned)blocks), dim3(512), lds, st, pp);
-  DC_CHECK_LAUNCH();
+  DC_LAUNCHED(wgrad384_is_tconv(g) ? "wgrad384_convT" : g.ntaps == 1 ? "wgrad384_pw" : "wgrad384_3x3");
   return 0;
 }
 

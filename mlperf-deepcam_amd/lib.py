@@ -53,6 +53,8 @@ _SIGS = {
     "dc_version": (I, []),
     "dc_set_option": (I, [C.c_char_p, I]),
     "dc_reset_options": (I, []),
+    "dc_launch_log_begin": (I, []),
+    "dc_launch_log_end": (I, [C.c_char_p, SZ]),
     "dc_stream_create": (I, [I, P]),
     "dc_stream_destroy": (I, [P]),
     "dc_stream_priority_range": (I, [P, P]),

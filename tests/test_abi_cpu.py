@@ -118,3 +118,57 @@ def test_retired_options_are_refused_and_kept_ones_accepted():
             assert lib.dc_set_option(name.encode(), default) == 0, f"{name}: {L.last_error()}"
     finally:
         assert lib.dc_reset_options() == 0, L.last_error()
+
+
+def test_launch_record_protocol():
+    """dc_launch_log_begin / dc_launch_log_end (host state of the calling thread, no GPU needed): an empty record, the three misuses and a
+    buffer that is too small each fail with a message, and every failure of _end still closes the record."""
+    import ctypes as C
+    import threading
+    from util_launch import served, end_record
+    lib = L.load()
+    with served() as names:                              # nothing launched: an empty record
+        pass
+    assert names == []
+    buf = C.create_string_buffer(64)
+    assert lib.dc_launch_log_end(buf, 64) != 0           # no record open
+    assert "no record is open" in L.last_error()
+    with pytest.raises(L.DeepcamHipError, match="no record is open"):
+        end_record()
+    assert lib.dc_launch_log_begin() == 0
+    assert lib.dc_launch_log_begin() != 0                # a second begin
+    assert "already open" in L.last_error()
+    seen = []
+    t = threading.Thread(target=lambda: seen.append((lib.dc_launch_log_end(buf, 64), lib.dc_launch_log_begin(), lib.dc_launch_log_end(buf, 64))))
+    t.start()
+    t.join()
+    assert seen[0][0] != 0 and seen[0][1:] == (0, 0)     # thread-local: another thread neither sees nor disturbs this thread's record
+    assert lib.dc_launch_log_end(buf, 0) != 0            # not even room for the terminator
+    assert "buffer holds 0 bytes" in L.last_error() and "needs 1" in L.last_error()
+    assert lib.dc_launch_log_end(buf, 64) != 0           # ... and that failure closed the record
+    assert lib.dc_launch_log_begin() == 0
+    assert lib.dc_launch_log_end(None, 64) != 0          # a null buffer
+    assert lib.dc_launch_log_begin() == 0
+    buf.value = b"stale"
+    assert lib.dc_launch_log_end(buf, 1) == 0 and buf.value == b""      # an empty record fits one byte
+
+
+def test_launch_record_vocabulary_is_documented():
+    """Every name a launch site notes (DC_LAUNCHED in csrc/) is listed in the header comment of dc_launch_log_begin."""
+    hdr = open(os.path.join(ROOT, "include", "deepcam_hip.h")).read()
+    doc = hdr[hdr.index("Launch record"):hdr.index("int dc_launch_log_begin")]
+    csrc = os.path.join(ROOT, "mlperf-deepcam_amd", "csrc")
+    names = set()
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".cpp", ".h")):
+            for line in open(os.path.join(csrc, fn)):
+                if "DC_LAUNCHED(" in line and "#define DC_LAUNCHED" not in line:
+                    found = re.findall(r'"([A-Za-z0-9_]+)"', line)
+                    assert found, f"{fn}: a launch site without a literal name: {line.strip()}"
+                    names.update(found)
+    assert len(names) >= 40 and "aux" in names
+    words = set(re.findall(r"[A-Za-z0-9_]+", doc))
+    for stem in ("dw_reg", "dw_win", "dw_tile", "dw_tile_s2"):      # the header lists these as dw_reg_* with the three directions
+        if stem + "_" in doc:
+            words.update(f"{stem}_{d}" for d in ("fwd", "dgrad", "wgrad"))
+    assert not (names - words), f"undocumented launch names: {sorted(names - words)}"

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from mlperf_deepcam_amd import lib as L  # noqa: E402
+from util_launch import assert_served, served  # noqa: E402
 
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -95,12 +96,41 @@ CONV_CASES = [
 ]
 
 
+def served_by(fwd=None, dgrad=None, wgrad=None, **other):
+    """The `expect` table of test_conv_fwd_dgrad_wgrad: the forward family (all three forward calls: with statistics, accumulate, bias), the
+    data-gradient family (plain and accumulate) and the weight-gradient launches; single calls by keyword (fwd_acc=, fwd_bias=, dgrad_acc=)."""
+    e = {}
+    if fwd is not None:
+        e.update(fwd=fwd, fwd_acc=fwd, fwd_bias=fwd)
+    if dgrad is not None:
+        e.update(dgrad=dgrad, dgrad_acc=dgrad)
+    if wgrad is not None:
+        e["wgrad"] = wgrad
+    e.update(other)
+    return e
+
+
+# the plain kernels a forced variant is compared with (bf16): whichever tile the default planner picks
+PLAIN_GEMM = ("igemm128_bf16", "igemm256")
+
+# Who serves the calls under igemm256 = 2.  Deliberate fallbacks: at most 16 pixels of a pointwise layer stay on the GEMV bundle (run_gather asks
+# for it first), and the thin stem layers stay on thinconv.hip for the plain forward / data gradient it serves (not with bias or accumulate,
+# not for the phase-split data gradient of the stride-2 stem: those reach the 256-tile kernel).
+IGEMM256_FORCED = {c[0]: served_by("igemm256", "igemm256") for c in CONV_CASES}
+IGEMM256_FORCED["gemm_rows2"] = served_by("tiny_gemm", "tiny_gemm")              # fallback on purpose: M = 2
+IGEMM256_FORCED["gemm_rows16"] = served_by("tiny_gemm", "tiny_gemm")             # fallback on purpose: M = 16
+IGEMM256_FORCED["stem_thin"]["fwd"] = "thin_fwd"                                 # fallback on purpose (the plain forward)
+IGEMM256_FORCED["stem_thin_19_rows"]["fwd"] = "thin_fwd"
+IGEMM256_FORCED["conv2_thin"].update(fwd="thin_tile", dgrad="thin_tile")         # fallback on purpose (the plain forward and data gradient)
+
+
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_256_tile_kernel(case):
-    """The eight-wave 256 x 256 tile kernel (forced on every eligible call) passes the same checks as the 128 x 128 one."""
+    """The eight-wave 256 x 256 tile kernel (forced on every eligible call) passes the same checks as the 128 x 128 one; the launch record
+    proves which calls it served (IGEMM256_FORCED)."""
     L.call("dc_set_option", b"igemm256", 2)
     try:
-        test_conv_fwd_dgrad_wgrad(case, torch.bfloat16)
+        test_conv_fwd_dgrad_wgrad(case, torch.bfloat16, IGEMM256_FORCED[case[0]])
     finally:
         L.call("dc_set_option", b"igemm256", 1)
 
@@ -108,23 +138,38 @@ def test_conv_256_tile_kernel(case):
 PW_CASES = [c for c in CONV_CASES if c[1] == 1 and c[2] == 1 and c[6] >= 64 and c[8] * c[9] * c[10] > 16]
 
 
-@pytest.mark.parametrize("mode", [2, 3, 5], ids=["256x384", "128x384", "128x192"])
+PW384_NAME = {2: "pw384_256", 3: "pw384_128", 4: "pw384_256_k64", 5: "pw192"}      # option pw384 -> the family it forces
+
+
+@pytest.mark.parametrize("mode", [2, 3, 4, 5], ids=["256x384", "128x384", "256x384_k64", "128x192"])
 @pytest.mark.parametrize("case", PW_CASES, ids=[c[0] for c in PW_CASES])
 def test_conv_pointwise_384_tile_kernel(case, mode):
-    """The two-waves-per-SIMD 256 x 384 / 128 x 384 pointwise kernel (csrc/igemm384.hip), forced on every eligible forward and
-    data-gradient call, passes the same checks against F.conv2d + autograd as the other tile shapes."""
+    """The two-waves-per-SIMD 256 x 384 / 128 x 384 pointwise kernel (csrc/igemm384.hip; mode 4: its 64-deep stages of 128-byte rows) and the
+    128 x 192 kernel, forced on every eligible forward and data-gradient call, pass the same checks against F.conv2d + autograd as the other
+    tile shapes.  Fallback on purpose: the data gradient of pw_small_n has 48 input channels, fewer than the two K steps pw384_eligible asks for."""
+    expect = served_by(PW384_NAME[mode], PW384_NAME[mode])
+    if case[0] == "pw_small_n":
+        expect.update(dgrad="igemm128_bf16", dgrad_acc="igemm128_bf16")
     L.call("dc_set_option", b"pw384", mode)
     try:
-        test_conv_fwd_dgrad_wgrad(case, torch.bfloat16)
+        test_conv_fwd_dgrad_wgrad(case, torch.bfloat16, expect)
     finally:
         L.call("dc_set_option", b"pw384", 1)
 
 
-@pytest.mark.parametrize("shape", [(728, 728, 3, 19, 17), (728, 728, 2, 48, 72), (136, 392, 2, 21, 13), (1536, 776, 1, 24, 20)],
-                         ids=["ragged969", "middle_flow_b2", "one_and_a_bit_tiles", "long_k_three_tiles"])
+@pytest.mark.parametrize("shape", [(728, 728, 3, 19, 17), (728, 728, 2, 48, 72), (136, 392, 2, 21, 13), (1536, 776, 1, 24, 20),
+                                   # for the 64-deep stages of mode 4: Cin = 128 is two stages (the prologue meets the tail), 136 and 728 leave a
+                                   # ragged last stage of 8 and 24 channels, 1536 is exact; 255 / 256 / 257 and 969 pixels around the 256-pixel
+                                   # tile; Cout = 8, 376 / 384 / 392 around the 384-wide tile, 728 two tiles.  (The data gradient swaps the roles.)
+                                   (128, 8, 1, 15, 17), (136, 376, 1, 16, 16), (728, 384, 1, 1, 257), (1536, 392, 1, 15, 17), (128, 728, 3, 19, 17)],
+                         ids=["ragged969", "middle_flow_b2", "one_and_a_bit_tiles", "long_k_three_tiles",
+                              "k64_two_stages_m255_c8", "k64_tail8_m256_c376", "k64_tail24_m257_c384", "k64_exact_m255_c392", "k64_two_stages_m969_c728"])
 def test_conv_pointwise_384_tile_kernel_same_bits(shape):
     """Same MFMA instruction and K order as the 256 x 256 / 128 x 128 kernels: outputs bit-equal (forward with bias, accumulate mode,
-    data gradient through padded views), BatchNorm slabs equal up to the order of the additions; pad channels untouched."""
+    data gradient through padded views), BatchNorm slabs equal up to the order of the additions; pad channels untouched.  Every mode of
+    option pw384 that forces a kernel, the 64-deep stages of mode 4 included; the launch record proves that each call ran on the forced
+    family and the baseline on a plain tile kernel.  Fallback on purpose: a data gradient with fewer than 64 input channels (Cout = 8) is
+    refused by pw384_eligible and stays on the 128-tile kernel in every mode."""
     cin, cout, N, H, W = shape
     dtype = torch.bfloat16
     d = desc(dtype, 1, 1, 0, 1, 0, cin, cout)
@@ -142,15 +187,23 @@ def test_conv_pointwise_384_tile_kernel_same_bits(shape):
     rows = L.load().dc_conv_stat_rows(C.byref(d), N, H, W)
     got = []
     try:
-        for mode in (0, 2, 3, 5):
+        for mode in (0, 2, 3, 4, 5):
             L.call("dc_set_option", b"pw384", mode)
             ybuf, yv = empty_nhwc(N, H, W, cout, dtype, ld=cout + 24, off=16)
             slab = torch.full((2, rows, cout), float("nan"), device=dev())
-            L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+            with served(f"pw384={mode} fwd") as n_fwd:
+                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
             y0 = from_nhwc(yv).clone()
-            L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 1, S())
+            with served(f"pw384={mode} fwd_bias_acc") as n_acc:
+                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 1, S())
             _, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-            L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            with served(f"pw384={mode} dgrad") as n_dg:
+                L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            for what, names, k_in in (("fwd", n_fwd, cin), ("fwd_bias_acc", n_acc, cin), ("dgrad", n_dg, cout)):
+                if mode and k_in >= 64:
+                    assert_served(names, PW384_NAME[mode], f"pw384={mode} {what}")
+                else:       # the baseline, and the data gradient pw384_eligible refuses
+                    assert len(names) == 1 and names[0] in PLAIN_GEMM, f"pw384={mode} {what}: served by {names}, expected one of {PLAIN_GEMM}"
             torch.cuda.synchronize()
             assert torch.isnan(ybuf[..., :16].float()).all() and torch.isnan(ybuf[..., 16 + cout:].float()).all()
             got.append((y0, from_nhwc(yv), slab.cpu(), from_nhwc(gxv)))
@@ -204,10 +257,12 @@ def test_conv_pointwise_224_tile_kernel_same_bits(shape, tile):
             slab = torch.full((3 * krows, cout), float("nan"), device=dev())     # [2 * krows ..]: a neighbour's rows, must stay NaN
             _, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
             if kn:
-                L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), None, vptr(yv), cout + 24, vptr(slab), krows, 0, S())
-                y0 = from_nhwc(yv).clone()
-                L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), vptr(bias), vptr(yv), cout + 24, None, 0, 1, S())
-                L.call("dc_conv_dgrad_kn", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(wf), vptr(gxv), cin + 8, 0, S())
+                with served(f"pw224={tile} fwd_kn, fwd_kn bias acc, dgrad_kn") as names:
+                    L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), None, vptr(yv), cout + 24, vptr(slab), krows, 0, S())
+                    y0 = from_nhwc(yv).clone()
+                    L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), vptr(bias), vptr(yv), cout + 24, None, 0, 1, S())
+                    L.call("dc_conv_dgrad_kn", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(wf), vptr(gxv), cin + 8, 0, S())
+                assert_served(names, ["pw224_384" if tile == 2 else "pw224_192"] * 3, f"pw224={tile}")
                 # slab_rows = 0: the dc_conv_stat_rows layout, zero rows behind the tiles' own
                 wide = torch.full((2, rows, cout), float("nan"), device=dev())
                 _, y2 = empty_nhwc(N, H, W, cout, dtype)
@@ -216,10 +271,18 @@ def test_conv_pointwise_224_tile_kernel_same_bits(shape, tile):
                 with pytest.raises(L.DeepcamHipError):
                     L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), None, vptr(y2), cout, vptr(wide), ntm - 1, 0, S()) if ntm > 1 else L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, None, vptr(wb), None, vptr(y2), cout, vptr(wide), 0, 0, S())
             else:
-                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
-                y0 = from_nhwc(yv).clone()
-                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 1, S())
-                L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+                with served("pw384=0 pw224=0 fwd, fwd bias acc, dgrad") as names:
+                    L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+                    y0 = from_nhwc(yv).clone()
+                    L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 1, S())
+                    L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+                if ((M + 255) // 256) * ((cout + 255) // 256) >= 257:
+                    # the default planner hands a launch of at least 257 tiles (option igemm256p_min) to the persistent form of the 256-tile
+                    # kernel, which takes no bias and no accumulate (igemm256p_eligible); test_conv_persistent_tiles_same_bits pins its
+                    # bits to the one-tile-per-workgroup kernel's.  Here: 108 pixel tiles x 3 channel tiles at local batch 8.
+                    assert_served(names, ["igemm256p", "igemm256", "igemm256p"], "baseline")
+                else:
+                    assert len(names) == 3 and all(n in PLAIN_GEMM for n in names), f"baseline served by {names}, expected three of {PLAIN_GEMM}"
             torch.cuda.synchronize()
             assert torch.isnan(ybuf[..., :16].float()).all() and torch.isnan(ybuf[..., 16 + cout:].float()).all()
             assert torch.isnan(slab[2 * krows:]).all() and not torch.isnan(slab[:2 * krows]).any()
@@ -231,6 +294,22 @@ def test_conv_pointwise_224_tile_kernel_same_bits(shape, tile):
     finally:
         L.call("dc_set_option", b"pw384", 1)
         L.call("dc_set_option", b"pw224", 1)
+    if (cin, cout, H, W) == (728, 728, 48, 72) and tile == 2:
+        # The default planner on the middle-flow layer (README, DESIGN.md section 5, pw384_plan's comments): with both weight images the 224-pixel
+        # tiles at local batch 8, the 128 x 192 tiles at local batch 2; with one image (dc_conv_fwd) at local batch 8 the 64-deep 384-wide
+        # variant is pinned by test_conv_full_shapes.  Outputs: the bits of the forced run above (same kernels or same MFMA order).
+        _, yd = empty_nhwc(N, H, W, cout, dtype)
+        with served(f"default planner fwd_kn N={N}") as names:
+            L.call("dc_conv_fwd_kn", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), None, vptr(yd), cout, None, 0, 0, S())
+        assert_served(names, {8: "pw224_384", 2: "pw192"}[N], f"default planner, local batch {N}")
+        torch.cuda.synchronize()
+        assert torch.equal(from_nhwc(yd), got[1][0])
+        if N == 8:      # local batch 4: half of the pixels of the same tensors
+            with served("default planner fwd_kn N=4") as names:
+                L.call("dc_conv_fwd_kn", C.byref(d), 4, H, W, vptr(xv), cin + 16, vptr(wf), vptr(wb), None, vptr(yd), cout, None, 0, 0, S())
+            assert_served(names, "pw224_192", "default planner, local batch 4")
+            torch.cuda.synchronize()
+            assert torch.equal(from_nhwc(yd)[:4], got[1][0][:4])
     assert_close(got[0][0], F.conv2d(x, q(w, dtype)), dtype)
     assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]) and torch.equal(got[0][3], got[1][3])
     slab = got[1][2]
@@ -238,16 +317,26 @@ def test_conv_pointwise_224_tile_kernel_same_bits(shape, tile):
     np.testing.assert_allclose(got[0][2].double().sum(1).numpy(), slab.double().sum(1).numpy(), rtol=2e-5, atol=1e-3)
 
 
+# igemm256p_eligible asks for at least 8 tiles in the direction under test and at least NSTAGE = 4 K steps in EVERY output phase; the last
+# two columns say whether the forward / the data gradient reaches igemm256p.hip ("p") or falls back on purpose to igemm256.hip ("-").
 PERSIST_CASES = [
-    # name, k, stride, pad, dil, transposed, cin, cout, N, H, W, workgroups
-    ("pw_ragged", 1, 1, 0, 1, 0, 728, 728, 2, 40, 52, 8),          # ragged K (728 = 22.75 chunks), ragged channel and pixel tiles
-    ("pw_two_rounds", 1, 1, 0, 1, 0, 256, 512, 2, 48, 64, 16),     # 48 tiles on 16 workgroups: three tiles each
-    ("dense3x3", 3, 1, 1, 1, 0, 72, 264, 2, 32, 48, 8),
-    ("atrous6", 3, 1, 6, 6, 0, 64, 256, 1, 48, 32, 8),
-    ("convT_phases", 3, 2, 1, 1, 1, 256, 256, 2, 16, 32, 8),       # 1/2/2/4 taps per output parity class, tiles of different K
-    ("stride2", 3, 2, 1, 1, 0, 128, 256, 2, 32, 48, 8),
-    ("one_tile_each", 1, 1, 0, 1, 0, 128, 256, 1, 32, 64, 8),      # 8 tiles on 8 workgroups: no tile switch at all
-    ("pw_stride2", 1, 2, 0, 1, 0, 128, 256, 2, 32, 48, 8),         # its data gradient has three sub-pixel phases without a tap (zeros)
+    # name, k, stride, pad, dil, transposed, cin, cout, N, H, W, workgroups, forward, data gradient
+    ("pw_ragged", 1, 1, 0, 1, 0, 728, 728, 2, 40, 52, 8, "p", "p"),          # ragged K (728 = 22.75 chunks), ragged channel and pixel tiles
+    ("pw_two_rounds", 1, 1, 0, 1, 0, 256, 512, 2, 48, 64, 16, "p", "p"),     # 48 tiles on 16 workgroups: three tiles each
+    ("dense3x3", 3, 1, 1, 1, 0, 72, 264, 2, 32, 48, 8, "p", "p"),
+    ("atrous6", 3, 1, 6, 6, 0, 64, 256, 1, 48, 32, 8, "-", "-"),             # fallback on purpose: 1536 pixels are 6 tiles either way
+    ("atrous6_8_tiles", 3, 1, 6, 6, 0, 64, 256, 1, 64, 32, 8, "p", "p"),     # ... 2048 pixels: 8 tiles forward, 8 in the data gradient
+    ("convT_phases", 3, 2, 1, 1, 1, 256, 256, 2, 16, 32, 8, "p", "-"),       # 1/2/2/4 taps per output parity class, tiles of different K;
+                                                                              # its data gradient (a stride-2 conv over 1024 pixels): 4 tiles
+    ("convT_dgrad_8_tiles", 3, 2, 1, 1, 1, 256, 256, 2, 32, 32, 8, "p", "p"),
+    ("stride2", 3, 2, 1, 1, 0, 128, 256, 2, 32, 48, 8, "-", "p"),            # forward: 768 pixels, 3 tiles; data gradient: 3 tiles x 4 phases
+    ("stride2_fwd_8_tiles", 3, 2, 1, 1, 0, 128, 256, 2, 64, 64, 8, "p", "p"),
+    ("one_tile_each", 1, 1, 0, 1, 0, 128, 256, 1, 32, 64, 8, "p", "p"),      # 8 tiles on 8 workgroups: no tile switch at all
+    # Fallback on purpose in both directions.  Forward: 3 tiles.  Data gradient: three of its four sub-pixel phases have no tap, and the
+    # predicate refuses that by design, not by accident: igemm256p_kernel issues the NEXT tile's first three stages in the last three K steps
+    # of the current tile and starts every tile with its operands already in the ring, so a tile without K steps has no slots to carry its
+    # successor's stages (its loop "for s in steps - 3 .. steps" would be empty).  The zeros of the empty phases are igemm256.hip's work.
+    ("pw_stride2", 1, 2, 0, 1, 0, 128, 256, 2, 32, 48, 8, "-", "-"),
 ]
 
 
@@ -255,8 +344,8 @@ PERSIST_CASES = [
 def test_conv_persistent_tiles_same_bits(case):
     """The persistent 256-tile kernel (igemm256p.hip: a workgroup walks several tiles, the operand ring never drains) against the
     one-tile-per-workgroup kernel: outputs and data gradients bit for bit, BatchNorm sums up to the order of the additions, nothing
-    written outside the tensor's own channels."""
-    name, k, stride, pad, dil, tr, cin, cout, N, H, W, wgs = case
+    written outside the tensor's own channels.  The launch record proves which direction of which case the persistent kernel served."""
+    name, k, stride, pad, dil, tr, cin, cout, N, H, W, wgs, fwd_p, dgrad_p = case
     dtype = torch.bfloat16
     d = desc(dtype, k, stride, pad, dil, tr, cin, cout)
     kk = 3 if tr else k
@@ -284,11 +373,15 @@ def test_conv_persistent_tiles_same_bits(case):
             L.call("dc_set_option", b"igemm256p", persistent)
             ybuf, yv = empty_nhwc(N, Ho, Wo, cout, dtype, ld=cout + 24, off=16)
             slab = torch.full((2, rows, cout), float("nan"), device=dev())
-            L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
-            ybuf2, yv2 = empty_nhwc(N, Ho, Wo, cout, dtype, ld=cout + 24, off=16)          # without statistics: the other instantiation
-            L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv2), cout + 24, None, 0, S())
+            with served(f"igemm256p={persistent} fwd, fwd without statistics") as n_fwd:
+                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+                ybuf2, yv2 = empty_nhwc(N, Ho, Wo, cout, dtype, ld=cout + 24, off=16)          # without statistics: the other instantiation
+                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv2), cout + 24, None, 0, S())
             gbuf, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-            L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            with served(f"igemm256p={persistent} dgrad") as n_dg:
+                L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            assert_served(n_fwd, ["igemm256p" if persistent and fwd_p == "p" else "igemm256"] * 2, f"igemm256p={persistent} forward")
+            assert_served(n_dg, "igemm256p" if persistent and dgrad_p == "p" else "igemm256", f"igemm256p={persistent} data gradient")
             torch.cuda.synchronize()
             for b in (ybuf, ybuf2):
                 assert torch.isnan(b[..., :16].float()).all() and torch.isnan(b[..., 16 + cout:].float()).all()
@@ -339,9 +432,11 @@ def test_thin_conv_lds_tiled_kernel_same_bits(case):
             L.call("dc_set_option", b"thin_tile", tiled)
             ybuf, yv = empty_nhwc(N, H, W, cout, dtype, ld=cout + 24, off=16)
             slab = torch.full((2, rows, cout), float("nan"), device=dev())
-            L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
-            gbuf, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-            L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            with served(f"thin_tile={tiled} fwd, dgrad") as names:
+                L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+                gbuf, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
+                L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+            assert_served(names, ["thin_tile" if tiled else "thin_fwd"] * 2, f"thin_tile={tiled}")
             torch.cuda.synchronize()
             assert torch.isnan(ybuf[..., :16].float()).all() and torch.isnan(ybuf[..., 16 + cout:].float()).all()
             assert torch.isnan(gbuf[..., cin:].float()).all()
@@ -397,7 +492,8 @@ def test_conv_dgrad_with_fused_bn_backward_statistics(case, dtype, tile, relu):
     try:
         L.call("dc_set_option", b"igemm256", tile)
         _, dx_ref = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-        L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(dx_ref), cin + 8, 0, S())
+        with served(f"igemm256={tile} dgrad") as n_plain:
+            L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(dx_ref), cin + 8, 0, S())
         rrows = L.load().dc_bn_stat_rows(M)
         rslab = torch.zeros(2, rrows, cin, device=dev())
         L.call("dc_bn_bwd_reduce", L.dtype_code(dtype), M, cin, vptr(dx_ref), cin + 8, vptr(ybv), cin + 16, None, 0, 2 if relu else 0,
@@ -406,8 +502,13 @@ def test_conv_dgrad_with_fused_bn_backward_statistics(case, dtype, tile, relu):
         assert rows > 0
         slab = torch.full((2, rows, cin), float("nan"), device=dev())
         _, dx = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-        L.call("dc_conv_dgrad_bnstats", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(dx), cin + 8, vptr(ybv), cin + 16,
-               vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), relu, vptr(slab), S())
+        with served(f"igemm256={tile} dgrad_bnstats") as n_stats:
+            L.call("dc_conv_dgrad_bnstats", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(dx), cin + 8, vptr(ybv), cin + 16,
+                   vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), relu, vptr(slab), S())
+        # the BatchNorm-backward epilogue lives in the 128- and the 256-tile kernel: both calls on the tile the option names
+        tile_name = "igemm256" if tile == 2 else "igemm128_bf16" if dtype == torch.bfloat16 else "igemm128_f32"
+        assert_served(n_plain, tile_name, f"igemm256={tile} data gradient")
+        assert_served(n_stats, tile_name, f"igemm256={tile} data gradient with statistics")
         torch.cuda.synchronize()
     finally:
         L.call("dc_set_option", b"igemm256", 1)
@@ -429,8 +530,14 @@ def conv_ref(x, w, bias, k, stride, pad, dil, transposed):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
-def test_conv_fwd_dgrad_wgrad(case, dtype):
+def test_conv_fwd_dgrad_wgrad(case, dtype, expect=None):
+    """expect (the tests that force a kernel or pin the planner pass it): which kernel family serves each of the six calls, see served_by()."""
     name, k, stride, pad, dil, tr, cin, cout, N, H, W = case
+    expect = expect or {}
+
+    def check(call, names):
+        if call in expect:
+            assert_served(names, expect[call], f"{name} {call}")
     d = desc(dtype, k, stride, pad, dil, tr, cin, cout)
     kk = 3 if tr else k
     wshape = (cin, cout, kk, kk) if tr else (cout, cin, kk, kk)
@@ -461,7 +568,9 @@ def test_conv_fwd_dgrad_wgrad(case, dtype):
     ybuf, yv = empty_nhwc(N, Ho, Wo, cout, dtype, ld=cout + 24, off=16)
     rows = L.load().dc_conv_stat_rows(C.byref(d), N, H, W)
     slab = torch.full((2, rows, cout), float("nan"), device=dev())
-    L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+    with served("fwd") as names:
+        L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, vptr(slab), 0, S())
+    check("fwd", names)
     torch.cuda.synchronize()
     y = from_nhwc(yv)
     assert_close(y, yref.detach(), dtype)
@@ -473,23 +582,31 @@ def test_conv_fwd_dgrad_wgrad(case, dtype):
     np.testing.assert_allclose(ssq.numpy(), (y * y).sum((0, 2, 3)).numpy(), rtol=2e-3)
 
     # accumulate: y += conv(x)
-    L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, None, 1, S())
+    with served("fwd_acc") as names:
+        L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), None, vptr(yv), cout + 24, None, 1, S())
+    check("fwd_acc", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(yv), 2 * yref.detach(), dtype, bf16=4e-2)
 
     # bias
     bias = rnd(cout, seed=5).to(dev())
-    L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 0, S())
+    with served("fwd_bias") as names:
+        L.call("dc_conv_fwd", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(wf), vptr(bias), vptr(yv), cout + 24, None, 0, S())
+    check("fwd_bias", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(yv), yref.detach() + bias.cpu()[None, :, None, None], dtype)
 
     # data gradient
     _, gyv = to_nhwc(gy, dtype)
     _, gxv = empty_nhwc(N, H, W, cin, dtype, ld=cin + 8, off=0)
-    L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+    with served("dgrad") as names:
+        L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 0, S())
+    check("dgrad", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(gxv), gx_ref, dtype)
-    L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 1, S())
+    with served("dgrad_acc") as names:
+        L.call("dc_conv_dgrad", C.byref(d), N, H, W, vptr(gyv), cout, vptr(wb), vptr(gxv), cin + 8, 1, S())
+    check("dgrad_acc", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(gxv), 2 * gx_ref, dtype, bf16=4e-2)
 
@@ -497,7 +614,9 @@ def test_conv_fwd_dgrad_wgrad(case, dtype):
     wsb = L.load().dc_conv_wgrad_workspace(C.byref(d), N, H, W)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev())
     gw = torch.full(wshape, float("nan"), device=dev())
-    L.call("dc_conv_wgrad", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(gyv), cout, vptr(ws), wsb, vptr(gw), S())
+    with served("wgrad") as names:
+        L.call("dc_conv_wgrad", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(gyv), cout, vptr(ws), wsb, vptr(gw), S())
+    check("wgrad", names)
     torch.cuda.synchronize()
     assert_close(gw.cpu(), gw_ref, dtype, f32=3e-4, bf16=1e-2)
 
@@ -515,11 +634,27 @@ FULL_CASES = [
 ]
 
 
+# What the DEFAULT planner gives these layers, as README.md, DESIGN.md section 5 and the planners' own comments say:
+FULL_SERVED = {
+    # one weight image (dc_conv_fwd / dc_conv_dgrad): the 384-wide tile with 64-deep stages; the weight gradient on the 256 x 384 kernel
+    "full_pw728_b8": served_by("pw384_256_k64", "pw384_256_k64", ["wgrad384_pw", "wgrad_reduce"]),
+    # the ASPP 3 x 3 convolutions over 2048 channels: long K loops, the 256-tile kernel (one round: not the persistent form)
+    "full_aspp_d18": served_by("igemm256", wgrad=["wgrad384_3x3", "wgrad_reduce"]),
+    "full_aspp_d6": served_by("igemm256", wgrad=["wgrad384_3x3", "wgrad_reduce"]),
+    # "every other dense conv ... on 256 x 256 tiles; the p form is persistent": 864 tiles are several rounds, so the plain forward is the
+    # persistent kernel's; with bias or accumulate (which it does not serve) the one-tile-per-workgroup kernel
+    "full_convT256": dict(served_by("igemm256", wgrad=["wgrad384_convT", "wgrad_reduce"]), fwd="igemm256p"),
+    # a thin layer (four K steps): the 128-tile kernel, forward and data gradient
+    "full_pw128_thin": served_by("igemm128_bf16", "igemm128_bf16"),
+}
+
+
 @pytest.mark.parametrize("case", FULL_CASES, ids=[c[0] for c in FULL_CASES])
 def test_conv_full_shapes(case):
     """Forward (+ BatchNorm partial sums, accumulate, bias), data gradient and weight gradient at the benchmark's real layer
-    shapes against F.conv2d / autograd on the CPU, bf16 storage (the benchmarked dtype), default tile planner."""
-    test_conv_fwd_dgrad_wgrad(case, torch.bfloat16)
+    shapes against F.conv2d / autograd on the CPU, bf16 storage (the benchmarked dtype), default tile planner; FULL_SERVED pins the kernel
+    families the planner is documented to pick there."""
+    test_conv_fwd_dgrad_wgrad(case, torch.bfloat16, FULL_SERVED.get(case[0]))
 
 
 def test_conv_full_shape_pw728_fp32():
@@ -559,9 +694,12 @@ def test_dilated_group_is_bit_identical_to_single_launches(shape, dtype):
     rows = singles[0][1].shape[1]
     gslabs = [torch.full((2, rows, cout), float("nan"), device=dev()) for _ in dils]
     ys = [cat[..., b * cout:(b + 1) * cout] for b in range(3)]
-    L.call("dc_conv_fwd_dilated_group", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
-           (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8,
-           (C.c_void_p * 3)(*[t.data_ptr() for t in gslabs]), S())
+    with served("dilated group") as names:
+        L.call("dc_conv_fwd_dilated_group", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
+               (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8,
+               (C.c_void_p * 3)(*[t.data_ptr() for t in gslabs]), S())
+    # one grouped launch of the 256-tile kernel in bf16; fp32: the per-branch fallback inside the entry point
+    assert_served(names, ["igemm256"] if dtype == torch.bfloat16 else ["igemm128_f32"] * 3, "dc_conv_fwd_dilated_group")
     torch.cuda.synchronize()
     for b in range(3):
         assert torch.equal(ys[b], singles[b][0]), f"member {b}: outputs differ"
@@ -602,9 +740,11 @@ def _split_k_checks(d0, N, H, W, cin, cout, dils, xv, wfs, ys, cat, singles, row
     for with_stats in (True, False):
         cat.fill_(float("nan"))
         gs2 = [torch.full((2, rows, cout), float("nan"), device=dev()) for _ in dils]
-        L.call("dc_conv_fwd_dilated_group_ws", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
-               (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8,
-               (C.c_void_p * 3)(*[t.data_ptr() for t in gs2]) if with_stats else None, vptr(ws), wsb, S())
+        with served(f"split-K stats={with_stats}") as names:
+            L.call("dc_conv_fwd_dilated_group_ws", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
+                   (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8,
+                   (C.c_void_p * 3)(*[t.data_ptr() for t in gs2]) if with_stats else None, vptr(ws), wsb, S())
+        assert_served(names, ["igemm256_splitk", "igemm256_splitk_fold"], "grouped launch with a workspace")
         torch.cuda.synchronize()
         assert torch.isnan(cat[..., 3 * cout:].float()).all()
         for b in range(3):
@@ -615,8 +755,10 @@ def _split_k_checks(d0, N, H, W, cin, cout, dils, xv, wfs, ys, cat, singles, row
                 assert torch.allclose(gs2[b], singles[b][1], rtol=2e-3, atol=2e-2), f"member {b}: statistics"
     # too small a workspace: the unsplit launch, bit for bit
     cat.fill_(float("nan"))
-    L.call("dc_conv_fwd_dilated_group_ws", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
-           (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8, None, vptr(ws), wsb - 16, S())
+    with served("split-K workspace too small") as names:
+        L.call("dc_conv_fwd_dilated_group_ws", C.byref(d0), N, H, W, 3, (C.c_int * 3)(*dils), vptr(xv), cin + 32,
+               (C.c_void_p * 3)(*[t.data_ptr() for t in wfs]), (C.c_void_p * 3)(*[t.data_ptr() for t in ys]), 3 * cout + 8, None, vptr(ws), wsb - 16, S())
+    assert_served(names, "igemm256", "grouped launch, workspace too small")      # fallback on purpose: the unsplit grouped launch
     torch.cuda.synchronize()
     assert all(torch.equal(ys[b], singles[b][0]) for b in range(3))
 
@@ -625,7 +767,8 @@ GROUP_CASES = [
     # name, k, stride, pad, dil, transposed, cin, cout, N, H, W, layers
     ("pw728_x3", 1, 1, 0, 1, 0, 728, 728, 2, 24, 20, 3),       # the middle-flow Block: three pointwise convs, one launch
     ("pw728_x4", 1, 1, 0, 1, 0, 728, 728, 3, 17, 13, 4),       # ragged pixel count, the largest group
-    ("dense3x3_x2", 3, 1, 1, 1, 0, 256, 256, 2, 10, 12, 2),
+    ("dense3x3_x2", 3, 1, 1, 1, 0, 256, 256, 2, 10, 12, 2),     # rows of 12 pixels, shorter than a stage of wgrad384.hip (32): plain calls
+    ("dense3x3_x2_rows32", 3, 1, 1, 1, 0, 256, 256, 1, 6, 32, 2),  # ... rows exactly a stage long: the grouped 3 x 3 launch
     ("thin_x2_falls_back", 1, 1, 0, 1, 0, 64, 48, 2, 9, 7, 2),  # not served by the 256-tile kernel: plain calls
 ]
 
@@ -658,7 +801,15 @@ def test_conv_wgrad_group(case, dtype):
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev())
     gws = [torch.full(wshape, float("nan"), device=dev()) for _ in range(layers)]
     pa = lambda ts: (C.c_void_p * layers)(*[t.data_ptr() for t in ts])
-    L.call("dc_conv_wgrad_group", C.byref(d), N, H, W, layers, pa(xs), cin + 16, pa(gys), cout, vptr(ws), wsb, pa(gws), S())
+    with served("wgrad_group") as names:
+        L.call("dc_conv_wgrad_group", C.byref(d), N, H, W, layers, pa(xs), cin + 16, pa(gys), cout, vptr(ws), wsb, pa(gws), S())
+    # bf16: one grouped launch of the 256 x 384 kernel and a reduction per layer; fallbacks on purpose: fp32, and thin_x2_falls_back (64 input
+    # channels fill a sixth of a 384-wide tile: wgrad384_wins says no) and dense3x3_x2 (wgrad384_eligible refuses a multi-tap layer whose rows
+    # are shorter than a stage) run `layers` plain calls on the 128-tile kernel
+    if dtype == torch.bfloat16 and name not in ("thin_x2_falls_back", "dense3x3_x2"):
+        assert_served(names, ["wgrad384_pw" if k == 1 else "wgrad384_3x3"] + ["wgrad_reduce"] * layers, name)
+    else:
+        assert_served(names, ["wgrad128_bf16" if dtype == torch.bfloat16 else "wgrad128_f32", "wgrad_reduce"] * layers, name)
     torch.cuda.synchronize()
     for l in range(layers):
         assert_close(gws[l].cpu(), refs[l], dtype, f32=3e-4, bf16=1e-2)
@@ -717,7 +868,12 @@ def test_conv_wgrad_384_tile_kernel(case):
         wsb = lib.dc_conv_wgrad_group_workspace(C.byref(d), N, H, W, layers)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev())
         gws = [torch.full((cout, cin, k, k), float("nan"), device=dev()) for _ in range(layers)]
-        L.call("dc_conv_wgrad_group", C.byref(d), N, H, W, layers, pa(xs), cin + 16, pa(gys), cout + 8, vptr(ws), wsb, pa(gws), S())
+        with served(f"wgrad384={mode}") as names:
+            L.call("dc_conv_wgrad_group", C.byref(d), N, H, W, layers, pa(xs), cin + 16, pa(gys), cout + 8, vptr(ws), wsb, pa(gws), S())
+        if mode == 2:      # one (grouped) launch of the forced kernel, a reduction per layer
+            assert_served(names, ["wgrad384_pw" if k == 1 else "wgrad384_3x3"] + ["wgrad_reduce"] * layers, f"{name} wgrad384=2")
+        else:              # the baseline: a plain call per layer on the 128-tile kernel
+            assert_served(names, ["wgrad128_bf16", "wgrad_reduce"] * layers, f"{name} wgrad384=0")
         torch.cuda.synchronize()
         outs[mode] = gws
     for l in range(layers):
@@ -755,7 +911,9 @@ def test_conv_transpose_wgrad_384_tile_kernel(case):
         wsb = lib.dc_conv_wgrad_workspace(C.byref(d), N, H, W)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev())
         gw = torch.full((cin, cout, 3, 3), float("nan"), device=dev())
-        L.call("dc_conv_wgrad", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(gyv), cout + 8, vptr(ws), wsb, vptr(gw), S())
+        with served(f"wgrad384={mode}") as names:
+            L.call("dc_conv_wgrad", C.byref(d), N, H, W, vptr(xv), cin + 16, vptr(gyv), cout + 8, vptr(ws), wsb, vptr(gw), S())
+        assert_served(names, ["wgrad384_convT" if mode == 2 else "wgrad128_bf16", "wgrad_reduce"], f"{name} wgrad384={mode}")
         torch.cuda.synchronize()
         outs[mode] = gw
     assert_close(outs[2].cpu(), ref, dtype, f32=3e-4, bf16=1e-2)
@@ -919,8 +1077,18 @@ DW_CASES = [("s1", 728, 1, 1, 2, 12, 10), ("s2", 128, 2, 1, 2, 16, 12), ("d2", 1
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", DW_CASES, ids=[c[0] for c in DW_CASES])
-def test_depthwise(case, dtype):
-    _, Cc, stride, dil, N, H, W = case
+def test_depthwise(case, dtype, expect=None):
+    """expect: call -> the launches that serve it (the tests that force a kernel pass it).  Pinned here for the default planner: the pipe*
+    cases (extents multiples of 8, at least 64 channels) run their bf16 data gradients on dwpipe.hip and their fp32 ones on the tiled kernel."""
+    cname, Cc, stride, dil, N, H, W = case
+    expect = dict(expect or {})
+    if cname.startswith("pipe"):
+        dg = "dwpipe_dgrad" if dtype == torch.bfloat16 else "dw_tile_dgrad"
+        expect.update(dgrad=dg, dgrad_add=dg, dgrad_wgrad=[dg, "dw_tile_reduce"])
+
+    def check(call, names):
+        if call in expect:
+            assert_served(names, expect[call], f"{cname} {call}")
     dt = L.dtype_code(dtype)
     x = q(rnd(N, Cc, H, W, seed=1), dtype)
     w = rnd(Cc, 1, 3, 3, seed=2, scale=1 / 3)
@@ -935,23 +1103,31 @@ def test_depthwise(case, dtype):
     L.call("dc_dwconv_pack_weights", Cc, vptr(wm), vptr(wd), S())
     _, xv = to_nhwc(x, dtype, ld=Cc + 8)
     _, yv = empty_nhwc(N, Ho, Wo, Cc, dtype)
-    L.call("dc_dwconv_fwd", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(wd), vptr(yv), Cc, None, None, 0, S())
+    with served("fwd") as names:
+        L.call("dc_dwconv_fwd", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(wd), vptr(yv), Cc, None, None, 0, S())
+    check("fwd", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(yv), yref.detach(), dtype, bf16=1e-2)
     _, gyv = to_nhwc(gy, dtype)
     add = q(rnd(N, Cc, H, W, seed=4), dtype)
     _, addv = to_nhwc(add, dtype)
     _, gxv = empty_nhwc(N, H, W, Cc, dtype)
-    L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), None, 0, vptr(gxv), Cc, S())
+    with served("dgrad") as names:
+        L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), None, 0, vptr(gxv), Cc, S())
+    check("dgrad", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(gxv), gx_ref, dtype, bf16=1e-2)
-    L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), vptr(addv), Cc, vptr(gxv), Cc, S())
+    with served("dgrad_add") as names:
+        L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), vptr(addv), Cc, vptr(gxv), Cc, S())
+    check("dgrad_add", names)
     torch.cuda.synchronize()
     assert_close(from_nhwc(gxv), gx_ref + add, dtype, bf16=1e-2)
     wsb = L.load().dc_dwconv_wgrad_workspace(Cc, N, H, W, stride)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev())
     gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
-    L.call("dc_dwconv_wgrad", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(gyv), Cc, vptr(ws), vptr(gw), None, None, 0, S())
+    with served("wgrad") as names:
+        L.call("dc_dwconv_wgrad", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(gyv), Cc, vptr(ws), vptr(gw), None, None, 0, S())
+    check("wgrad", names)
     torch.cuda.synchronize()
     assert_close(gw.cpu(), gw_ref, dtype, f32=2e-4, bf16=2e-3)
     # data gradient (onto an addend) and weight gradient in ONE kernel (the tiled stride-1 kernels and the stride-2 data-gradient kernel)
@@ -961,9 +1137,11 @@ def test_depthwise(case, dtype):
         _, gxv2 = empty_nhwc(N, H, W, Cc, dtype)
         wslab = torch.full((rows, 9, Cc), float("nan"), device=dev())
         gw2 = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
-        L.call("dc_dwconv_dgrad_wgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), vptr(addv), Cc, vptr(gxv2), Cc, vptr(xv), Cc + 8,
-               None, None, 0, vptr(wslab), S())
-        L.call("dc_dwconv_wgrad_reduce", Cc, rows, vptr(wslab), vptr(gw2), S())
+        with served("dgrad_wgrad") as names:
+            L.call("dc_dwconv_dgrad_wgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), vptr(addv), Cc, vptr(gxv2), Cc, vptr(xv), Cc + 8,
+                   None, None, 0, vptr(wslab), S())
+            L.call("dc_dwconv_wgrad_reduce", Cc, rows, vptr(wslab), vptr(gw2), S())
+        check("dgrad_wgrad", names)
         torch.cuda.synchronize()
         assert torch.equal(from_nhwc(gxv2), from_nhwc(gxv))
         assert_close(gw2.cpu(), gw_ref, dtype, f32=2e-4, bf16=2e-3)
@@ -1096,7 +1274,9 @@ def test_batchnorm_finalize_inside_its_consumer(case):
     try:
         got = state()
         ob, o_fb = empty_nhwc(N, H, W, Cc, dtype, ld=Cc + 16, off=8)
-        L.call("dc_bn_apply_fin", dt, M, Cc, M, vptr(yv), ld, *fin_args(got), None, Cc, prelu, vptr(o_fb), Cc + 16, S())
+        with served("bn_apply_rows=0 dc_bn_apply_fin") as names:
+            L.call("dc_bn_apply_fin", dt, M, Cc, M, vptr(yv), ld, *fin_args(got), None, Cc, prelu, vptr(o_fb), Cc + 16, S())
+        assert_served(names, ["aux", "bn_apply"], "bn_apply_rows=0")      # the finalize launch, then the grid-stride apply
         torch.cuda.synchronize()
     finally:
         L.call("dc_set_option", b"bn_apply_rows", 1)
@@ -1229,8 +1409,10 @@ def test_depthwise_wgrad_several_tiles_per_workgroup(tpb):
     """The weight-gradient planner gives a workgroup several tiles only on large layers; force it on a small one."""
     L.call("dc_set_option", b"dw_wgrad_tpb", tpb)
     try:
-        test_depthwise(("s1", 728, 1, 1, 2, 12, 10), torch.bfloat16)
-        test_depthwise(("thin64", 64, 1, 1, 2, 9, 40), torch.float32)
+        # the override acts in the stride-1 tiled weight-gradient kernel: both layers must be served by it
+        tiled = {"wgrad": ["dw_tile_wgrad", "dw_tile_reduce"]}
+        test_depthwise(("s1", 728, 1, 1, 2, 12, 10), torch.bfloat16, tiled)
+        test_depthwise(("thin64", 64, 1, 1, 2, 9, 40), torch.float32, tiled)
     finally:
         L.call("dc_set_option", b"dw_wgrad_tpb", 0)
 
@@ -1248,8 +1430,11 @@ def test_depthwise_tiled_matches_register_window_path():
         L.call("dc_set_option", b"dw_tile", mode)
         _, yv = empty_nhwc(N, H, W, Cc, torch.bfloat16)
         _, gv = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-        L.call("dc_dwconv_fwd", L.DC_BF16, Cc, 1, 1, N, H, W, vptr(xv), Cc, vptr(wd), vptr(yv), Cc, None, None, 0, S())
-        L.call("dc_dwconv_dgrad", L.DC_BF16, Cc, 1, 1, N, H, W, vptr(xv), Cc, vptr(wd), None, 0, vptr(gv), Cc, S())
+        with served(f"dw_tile={mode} fwd, dgrad") as names:
+            L.call("dc_dwconv_fwd", L.DC_BF16, Cc, 1, 1, N, H, W, vptr(xv), Cc, vptr(wd), vptr(yv), Cc, None, None, 0, S())
+            L.call("dc_dwconv_dgrad", L.DC_BF16, Cc, 1, 1, N, H, W, vptr(xv), Cc, vptr(wd), None, 0, vptr(gv), Cc, S())
+        # (a width of 19 is not a multiple of dwpipe.hip's 8-pixel tiles: the data gradient is the tiled kernel's)
+        assert_served(names, ["dw_tile_fwd", "dw_tile_dgrad"] if mode else ["dw_win_fwd", "dw_win_dgrad"], f"dw_tile={mode}")
         torch.cuda.synchronize()
         outs.append((yv.clone(), gv.clone()))
     L.call("dc_set_option", b"dw_tile", 1)
@@ -1284,66 +1469,72 @@ def test_depthwise_pipelined_kernel_matches_tiled(case):
     for mode in (2, 0):                                  # 2: the forward pass on the pipelined kernel too (default 1: data gradients only)
         L.call("dc_set_option", b"dw_pipe", mode)
         out = {}
-        for prelu, tag in ((None, "fwd"), (1, "fwd_bn_relu"), (0, "fwd_bn")):
-            _, yv = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-            L.call("dc_dwconv_fwd", dt, Cc, 1, dil, N, H, W, vptr(xv), ld, vptr(wd), vptr(yv), Cc, vptr(sc) if prelu is not None else None,
-                   vptr(sh) if prelu is not None else None, prelu or 0, S())
-            out[tag] = yv
-        _, g1 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-        L.call("dc_dwconv_dgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), None, 0, vptr(g1), Cc, S())
-        _, g2 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-        L.call("dc_dwconv_dgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g2), Cc, S())
-        out["dgrad"], out["dgrad_add"] = g1, g2
-        for relu in (1, 0):
-            rows = lib.dc_dwconv_dgrad_bnstats_rows(dt, Cc, 1, dil, N, H, W)
-            wrows = lib.dc_dwconv_dgrad_wgrad_rows(dt, Cc, 1, dil, N, H, W)
-            assert rows > 0 and wrows > 0
-            _, g3 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-            slab = torch.full((2, rows, Cc), float("nan"), device=dev())
-            L.call("dc_dwconv_dgrad_bnstats", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(g3), Cc, vptr(xv), ld, vptr(mean), vptr(invstd),
-                   vptr(sc), vptr(sh), relu, vptr(slab), S())
-            dgam, dbet = torch.empty(Cc, device=dev()), torch.empty(Cc, device=dev())
-            L.call("dc_bn_bwd_finalize", Cc, vptr(slab), rows, vptr(dgam), vptr(dbet), S())
-            _, g4 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-            slab2 = torch.full((2, rows, Cc), float("nan"), device=dev())
-            wslab = torch.full((wrows, 9, Cc), float("nan"), device=dev())
-            gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
-            L.call("dc_dwconv_dgrad_bnstats_wgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(g4), Cc, vptr(xv), ld, vptr(mean),
-                   vptr(invstd), vptr(sc), vptr(sh), relu, vptr(slab2), vptr(wslab), S())
-            L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab), vptr(gw), S())
-            torch.cuda.synchronize()
-            assert torch.equal(slab, slab2) and torch.equal(g3, g4) and torch.equal(g3, g1)
-            out[f"stats{relu}"] = (dgam, dbet, gw)
-            # the same with an addend (this layer is the LAST of several writers of the gradient): dx = the accumulated gradient, the sums are
-            # those of it (against dc_bn_bwd_reduce over that dx), the weight gradient is unchanged
-            _, g6 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-            slab3 = torch.full((2, rows, Cc), float("nan"), device=dev())
-            wslab3 = torch.full((wrows, 9, Cc), float("nan"), device=dev())
-            gw3 = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
-            L.call("dc_dwconv_dgrad_bnstats_wgrad_add", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g6), Cc, vptr(xv), ld,
-                   vptr(mean), vptr(invstd), vptr(sc), vptr(sh), relu, vptr(slab3), vptr(wslab3), S())
-            L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab3), vptr(gw3), S())
-            M_ = N * H * W
-            rrows = lib.dc_bn_stat_rows(M_)
-            rslab = torch.full((2, rrows, Cc), float("nan"), device=dev())
-            L.call("dc_bn_bwd_reduce", dt, M_, Cc, vptr(g2), Cc, vptr(xv), ld, None, 0, 2 if relu else 0, vptr(mean), vptr(invstd), vptr(rslab), vptr(sc),
-                   vptr(sh), S())
-            torch.cuda.synchronize()
-            assert torch.equal(g6, g2)
-            want, got = rslab.double().sum(1), slab3.double().sum(1)
-            assert torch.allclose(got, want, rtol=1e-4, atol=1e-4 * float(want.abs().max())), (relu, (got - want).abs().max().item())
-            np.testing.assert_allclose(gw3.cpu().numpy(), gw.cpu().numpy(), rtol=3e-5, atol=3e-5 * float(gw.abs().max()))
-        # stored (or lazily affine) layer input, addend, no statistics
-        for aff in (0, 1):
-            _, g5 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
-            wslab = torch.full((wrows, 9, Cc), float("nan"), device=dev())
-            gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
-            L.call("dc_dwconv_dgrad_wgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g5), Cc, vptr(xv), ld,
-                   vptr(sc) if aff else None, vptr(sh) if aff else None, aff, vptr(wslab), S())
-            L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab), vptr(gw), S())
-            torch.cuda.synchronize()
-            assert torch.equal(g5, g2)
-            out[f"wg_add{aff}"] = gw
+        with served(f"dw_pipe={mode} every entry point") as names:
+            for prelu, tag in ((None, "fwd"), (1, "fwd_bn_relu"), (0, "fwd_bn")):
+                _, yv = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+                L.call("dc_dwconv_fwd", dt, Cc, 1, dil, N, H, W, vptr(xv), ld, vptr(wd), vptr(yv), Cc, vptr(sc) if prelu is not None else None,
+                       vptr(sh) if prelu is not None else None, prelu or 0, S())
+                out[tag] = yv
+            _, g1 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+            L.call("dc_dwconv_dgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), None, 0, vptr(g1), Cc, S())
+            _, g2 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+            L.call("dc_dwconv_dgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g2), Cc, S())
+            out["dgrad"], out["dgrad_add"] = g1, g2
+            for relu in (1, 0):
+                rows = lib.dc_dwconv_dgrad_bnstats_rows(dt, Cc, 1, dil, N, H, W)
+                wrows = lib.dc_dwconv_dgrad_wgrad_rows(dt, Cc, 1, dil, N, H, W)
+                assert rows > 0 and wrows > 0
+                _, g3 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+                slab = torch.full((2, rows, Cc), float("nan"), device=dev())
+                L.call("dc_dwconv_dgrad_bnstats", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(g3), Cc, vptr(xv), ld, vptr(mean), vptr(invstd),
+                       vptr(sc), vptr(sh), relu, vptr(slab), S())
+                dgam, dbet = torch.empty(Cc, device=dev()), torch.empty(Cc, device=dev())
+                L.call("dc_bn_bwd_finalize", Cc, vptr(slab), rows, vptr(dgam), vptr(dbet), S())
+                _, g4 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+                slab2 = torch.full((2, rows, Cc), float("nan"), device=dev())
+                wslab = torch.full((wrows, 9, Cc), float("nan"), device=dev())
+                gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
+                L.call("dc_dwconv_dgrad_bnstats_wgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(g4), Cc, vptr(xv), ld, vptr(mean),
+                       vptr(invstd), vptr(sc), vptr(sh), relu, vptr(slab2), vptr(wslab), S())
+                L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab), vptr(gw), S())
+                torch.cuda.synchronize()
+                assert torch.equal(slab, slab2) and torch.equal(g3, g4) and torch.equal(g3, g1)
+                out[f"stats{relu}"] = (dgam, dbet, gw)
+                # the same with an addend (this layer is the LAST of several writers of the gradient): dx = the accumulated gradient, the sums are
+                # those of it (against dc_bn_bwd_reduce over that dx), the weight gradient is unchanged
+                _, g6 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+                slab3 = torch.full((2, rows, Cc), float("nan"), device=dev())
+                wslab3 = torch.full((wrows, 9, Cc), float("nan"), device=dev())
+                gw3 = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
+                L.call("dc_dwconv_dgrad_bnstats_wgrad_add", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g6), Cc, vptr(xv), ld,
+                       vptr(mean), vptr(invstd), vptr(sc), vptr(sh), relu, vptr(slab3), vptr(wslab3), S())
+                L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab3), vptr(gw3), S())
+                M_ = N * H * W
+                rrows = lib.dc_bn_stat_rows(M_)
+                rslab = torch.full((2, rrows, Cc), float("nan"), device=dev())
+                L.call("dc_bn_bwd_reduce", dt, M_, Cc, vptr(g2), Cc, vptr(xv), ld, None, 0, 2 if relu else 0, vptr(mean), vptr(invstd), vptr(rslab), vptr(sc),
+                       vptr(sh), S())
+                torch.cuda.synchronize()
+                assert torch.equal(g6, g2)
+                want, got = rslab.double().sum(1), slab3.double().sum(1)
+                assert torch.allclose(got, want, rtol=1e-4, atol=1e-4 * float(want.abs().max())), (relu, (got - want).abs().max().item())
+                np.testing.assert_allclose(gw3.cpu().numpy(), gw.cpu().numpy(), rtol=3e-5, atol=3e-5 * float(gw.abs().max()))
+            # stored (or lazily affine) layer input, addend, no statistics
+            for aff in (0, 1):
+                _, g5 = empty_nhwc(N, H, W, Cc, torch.bfloat16)
+                wslab = torch.full((wrows, 9, Cc), float("nan"), device=dev())
+                gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
+                L.call("dc_dwconv_dgrad_wgrad", dt, Cc, 1, dil, N, H, W, vptr(gyv), ld, vptr(wd), vptr(addv), Cc, vptr(g5), Cc, vptr(xv), ld,
+                       vptr(sc) if aff else None, vptr(sh) if aff else None, aff, vptr(wslab), S())
+                L.call("dc_dwconv_wgrad_reduce", Cc, wrows, vptr(wslab), vptr(gw), S())
+                torch.cuda.synchronize()
+                assert torch.equal(g5, g2)
+                out[f"wg_add{aff}"] = gw
+        # every depthwise launch of the pass on the family the option names (3 forward calls, 10 data gradients); the BatchNorm finalizes and
+        # reductions between them are generic launches, the weight-gradient rows are summed by dw_tile_reduce either way
+        dw = [n for n in names if n not in ("aux", "dw_tile_reduce")]
+        assert dw[:3] == ["dwpipe_fwd" if mode == 2 else "dw_tile_fwd"] * 3 and dw[3:] == ["dwpipe_dgrad" if mode == 2 else "dw_tile_dgrad"] * 10, \
+            f"dw_pipe={mode}: served by {dw}"
         res.append(out)
     L.call("dc_set_option", b"dw_pipe", 1)
     a, b = res
@@ -1631,14 +1822,18 @@ def test_batchnorm_train_fwd_bwd(shape, dtype, relu, use_res):
            vptr(scale), vptr(shift), vptr(smean), vptr(sinv), S())
     resv = to_nhwc(res, dtype)[1] if use_res else None
     _, ov = empty_nhwc(N, H, W, Cc, dtype, ld=Cc + 16, off=8)
-    L.call("dc_bn_apply", dt, M, Cc, vptr(yv), Cc + 8, vptr(scale), vptr(shift), vptr(resv) if use_res else None, Cc, relu,
-           vptr(ov), Cc + 16, S())
+    with served("bn_apply_rows=1 dc_bn_apply") as names:
+        L.call("dc_bn_apply", dt, M, Cc, vptr(yv), Cc + 8, vptr(scale), vptr(shift), vptr(resv) if use_res else None, Cc, relu,
+               vptr(ov), Cc + 16, S())
+    assert_served(names, "bn_apply_rows", "bn_apply_rows=1")
     # the row-layout kernel (default) and the grid-stride kernel do the same arithmetic: same bits, pad channels untouched
     ob2, ov2 = empty_nhwc(N, H, W, Cc, dtype, ld=Cc + 16, off=8)
     L.call("dc_set_option", b"bn_apply_rows", 0)
-    L.call("dc_bn_apply", dt, M, Cc, vptr(yv), Cc + 8, vptr(scale), vptr(shift), vptr(resv) if use_res else None, Cc, relu,
-           vptr(ov2), Cc + 16, S())
+    with served("bn_apply_rows=0 dc_bn_apply") as names:
+        L.call("dc_bn_apply", dt, M, Cc, vptr(yv), Cc + 8, vptr(scale), vptr(shift), vptr(resv) if use_res else None, Cc, relu,
+               vptr(ov2), Cc + 16, S())
     L.call("dc_set_option", b"bn_apply_rows", 1)
+    assert_served(names, "bn_apply", "bn_apply_rows=0")
     torch.cuda.synchronize()
     assert torch.equal(ov.float(), ov2.float()) and torch.isnan(ob2[..., :8].float()).all() and torch.isnan(ob2[..., 8 + Cc:].float()).all()
     assert int(nbt) == 1
@@ -1803,8 +1998,11 @@ def test_head(dtype):
     slab = torch.full((2, rows, Cin), float("nan"), device=dev())
     _, gxv2 = empty_nhwc(N, H, W, Cin, dtype)
     gw2 = torch.full((Cin, 3, 3, 3), float("nan"), device=dev())
-    L.call("dc_head_bwd_bnstats", dt, N, Cin, H, W, vptr(xv), Cin + 8, vptr(gld), vptr(wd), vptr(gxv2), Cin, vptr(gw2), wsp, vptr(ybv), Cin,
-           vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), 1, vptr(slab), S())
+    with served("head_dgrad_fused=1 dc_head_bwd_bnstats") as names:
+        L.call("dc_head_bwd_bnstats", dt, N, Cin, H, W, vptr(xv), Cin + 8, vptr(gld), vptr(wd), vptr(gxv2), Cin, vptr(gw2), wsp, vptr(ybv), Cin,
+               vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), 1, vptr(slab), S())
+    # the data gradient is the call's last launch: bf16 on the streaming kernel, fp32 on the tiled GEMM with the BatchNorm-backward epilogue
+    assert names[-1] == ("head_dgrad_stream" if dtype == torch.bfloat16 else "igemm128_f32"), names
     rrows = L.load().dc_bn_stat_rows(M)
     rslab = torch.zeros(2, rrows, Cin, device=dev())
     L.call("dc_bn_bwd_reduce", dt, M, Cin, vptr(gxv), Cin, vptr(ybv), Cin, None, 0, 2, vptr(mean), vptr(invstd), vptr(rslab), vptr(mscale),
@@ -1820,8 +2018,10 @@ def test_head(dtype):
             slab3 = torch.full((2, rows, Cin), float("nan"), device=dev())
             _, gxv3 = empty_nhwc(N, H, W, Cin, dtype)
             gw3 = torch.full((Cin, 3, 3, 3), float("nan"), device=dev())
-            L.call("dc_head_bwd_bnstats", dt, N, Cin, H, W, vptr(xv), Cin + 8, vptr(gld), vptr(wd), vptr(gxv3), Cin, vptr(gw3), wsp, vptr(ybv), Cin,
-                   vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), 1, vptr(slab3), S())
+            with served("head_dgrad_fused=0 dc_head_bwd_bnstats") as names:
+                L.call("dc_head_bwd_bnstats", dt, N, Cin, H, W, vptr(xv), Cin + 8, vptr(gld), vptr(wd), vptr(gxv3), Cin, vptr(gw3), wsp, vptr(ybv), Cin,
+                       vptr(mean), vptr(invstd), vptr(mscale), vptr(mshift), 1, vptr(slab3), S())
+            assert names[-1] in PLAIN_GEMM and "head_dgrad_stream" not in names, names
             torch.cuda.synchronize()
         finally:
             L.call("dc_set_option", b"head_dgrad_fused", 1)
@@ -1846,7 +2046,10 @@ def test_head_fused_forward_matches_gemm_plus_combine(shape):
     for mode in (1, 0):
         L.call("dc_set_option", b"head_fused", mode)
         out = torch.full((N, 3, 2 * H, 2 * W), float("nan"), device=dev())
-        L.call("dc_head_fwd", L.DC_BF16, N, Cin, H, W, vptr(xv), Cin, vptr(wd), vptr(out), wsp, S())
+        with served(f"head_fused={mode} dc_head_fwd") as names:
+            L.call("dc_head_fwd", L.DC_BF16, N, Cin, H, W, vptr(xv), Cin, vptr(wd), vptr(out), wsp, S())
+        # behind the weight packing (a generic launch): the fused kernel, or the GEMM with fp32 output and the combination kernel
+        assert_served(names, ["head_fwd_fused"] if mode else ["igemm128_f32out", "head_combine"], f"head_fused={mode}", ignore=("aux",))
         torch.cuda.synchronize()
         outs.append(out.clone())
     L.call("dc_set_option", b"head_fused", 1)
@@ -2016,8 +2219,12 @@ def test_head_on_unstored_batchnorm_output(shape, relu):
         L.call("dc_set_option", b"head_wgrad_fused", switch)
         slab3 = torch.full((2, rows, Cin), float("nan"), device=dev())
         gw3 = torch.full((Cin, 3, 3, 3), float("nan"), device=dev())
-        L.call("dc_head_bwd_bnin", dt, N, Cin, H, W, vptr(yv), Cin + 16, vptr(scale), vptr(shift), relu, vptr(ref_dl), vptr(wd), None, 0,
-               vptr(gw3), wsp, vptr(mean), vptr(invstd), vptr(slab3), 3, S())
+        with served(f"head_wgrad_fused={switch} dc_head_bwd_bnin parts=3") as names:
+            L.call("dc_head_bwd_bnin", dt, N, Cin, H, W, vptr(yv), Cin + 16, vptr(scale), vptr(shift), relu, vptr(ref_dl), vptr(wd), None, 0,
+                   vptr(gw3), wsp, vptr(mean), vptr(invstd), vptr(slab3), 3, S())
+        # (packing, gather, the rows' reduction and the finish kernel are generic launches)
+        assert_served(names, ["head_dgrad_stream_wgrad"] if switch else ["wgrad128_bnin", "wgrad_reduce", "head_dgrad_stream"],
+                      f"head_wgrad_fused={switch}", ignore=("aux",))
         torch.cuda.synchronize()
         assert torch.equal(slab3, ref_slab), switch
         assert not torch.isnan(gw3).any()
