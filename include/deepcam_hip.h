@@ -71,6 +71,8 @@ int dc_reset_options(void);
  *   head: head_fwd_fused | the GEMM's name then head_combine; head_dgrad_stream, head_dgrad_stream_wgrad (weight gradient riding along),
  *     head_dgrad_apply | the GEMM's name
  *   BatchNorm apply: bn_apply_rows, bn_apply
+ *   event catalogue (dc_mask_components, dc_component_stats): cc_tile, cc_merge, cc_flatten (tile labelling in LDS, the unions across
+ *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -591,6 +593,30 @@ int dc_val_accumulate(int B, int n_valid, long HW, const double* loss_sum, const
  * the fused kernel's arithmetic.  A workgroup belongs to one sample; samples >= n_valid are neither read nor written. */
 int dc_logits_predict(int B, int n_valid, int H, int W, const float* logits_nchw, uint8_t* mask, float* conf /*may be NULL*/,
                       int64_t* class_counts /*[B][3], may be NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Event catalogue (nn.EventCatalog; predict.py --events): connected components of a class mask and one row of statistics per component.
+ * Nothing like it exists in the reference, which stops at the mask; its visualiser rolls the fields by W / 2 because they are global
+ * longitude bands, hence `wrap`.  Everything is integer arithmetic: equal inputs give equal bits whatever the scheduling.
+ *   mask    uint8 [B][H][W]   classes 1 and 2 are foreground; 0 and every value >= 3 are background
+ *   A component is a maximal set of pixels of ONE class connected under `connectivity` 4 or 8.  Rows are never periodic; with wrap = 1 the
+ *   columns are (column W-1 touches column 0, under 8-connectivity diagonally too).
+ *   labels  int32 [B][H][W]   0 for background, else 1 + the smallest r * W + c of the pixel's component (its root)
+ *   table   int64 [B][cap][10], zeroed by the call; row k of a sample is the component with the k-th smallest root:
+ *           root, class, pixels, sum wy[r], sum r, sum cx[c], sum sx[c], smallest row, largest row, seam (1: pixels in column 0 AND in column W-1)
+ *   ncomp   int32 [B][3]      components: all, class 1, class 2 -- not capped: with all > cap the table holds the first cap rows by root
+ *   wy [H], cx [W], sx [W]    int32 weights of a row / a column (nn.event_weight_tables: 2^20-scaled cos(lat), cos(lon), sin(lon))
+ * Samples from n_valid on are not read and their slices of labels and ncomp not written (the whole table is zeroed).
+ * dc_mask_components_tile: the tile of the labelling kernel (tests derive their shapes from it); dc_mask_components_workspace: bytes of
+ * the workspace both calls take (256-byte aligned; dc_component_stats keeps ranks and prefix counts there); both are host functions.
+ * connectivity 4 or 8, 0 < n_valid <= B, H * W < 2^31 - 1, cap >= 1.  Neither call synchronises; dc_component_stats reads the labels
+ * dc_mask_components left on the same stream. */
+int dc_mask_components_tile(int* th, int* tw);
+size_t dc_mask_components_workspace(int B, int H, int W);
+int dc_mask_components(int B, int n_valid, int H, int W, const uint8_t* mask, int connectivity, int wrap, int32_t* labels,
+                       void* workspace, void* stream);
+int dc_component_stats(int B, int n_valid, int H, int W, const uint8_t* mask, const int32_t* labels, const int32_t* wy,
+                       const int32_t* cx, const int32_t* sx, int cap, int64_t* table, int32_t* ncomp, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

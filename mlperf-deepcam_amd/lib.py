@@ -157,6 +157,10 @@ _SIGS = {
     "dc_wce_score": (I, [I, I, I, I, P, P, I, P, P, P, P]),
     "dc_val_accumulate": (I, [I, I, L, P, P, P, P, P]),
     "dc_logits_predict": (I, [I, I, I, I, P, P, P, P, P]),
+    "dc_mask_components_tile": (I, [C.POINTER(I), C.POINTER(I)]),
+    "dc_mask_components_workspace": (SZ, [I, I, I]),
+    "dc_mask_components": (I, [I, I, I, I, P, I, I, P, P, P]),
+    "dc_component_stats": (I, [I, I, I, I, P, P, P, P, P, I, P, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

@@ -846,13 +846,114 @@ def predict_from_logits(logits: torch.Tensor, confidence: bool = False, n_valid:
     return mask, conf, counts
 
 
+EVENT_FIELDS = ("root", "class", "pixels", "area", "sum_row", "sum_cx", "sum_sx", "row_min", "row_max", "seam")
+EVENT_SCALE = 1 << 20
+
+
+def event_weight_tables(height: int, width: int):
+    """(wy [H], cx [W], sx [W]) int32 numpy arrays: cos(lat_r), cos(lon_c), sin(lon_c) times 2^20, rounded to nearest (ties to even), with
+    lat = linspace(-90, 90, H) and lon = linspace(-180, 180, W) degrees, evaluated in float64.  Integer weights make every sum of the
+    catalogue exact and independent of the order in which pixels arrive."""
+    lat = np.deg2rad(np.linspace(-90.0, 90.0, height))
+    lon = np.deg2rad(np.linspace(-180.0, 180.0, width))
+    q = lambda v: np.rint(v * EVENT_SCALE).astype(np.int32)  # noqa: E731
+    return q(np.cos(lat)), q(np.cos(lon)), q(np.sin(lon))
+
+
+class EventCatalog:
+    """Connected components of class masks on the device (dc_mask_components + dc_component_stats, csrc/components.hip): what a user of a
+    tropical-cyclone / atmospheric-river detector works with -- how many events a snapshot holds, where they are and how large.
+    Classes 1 and 2 are foreground; a component is a maximal set of pixels of one class under 4- or 8-connectivity, with periodic columns
+    when wrap is set (the fields are global longitude bands).  The object owns the label map (int32, 0 = background, else 1 + the smallest
+    r * W + c of the component), the workspace, the weight tables, the table (int64 [B, cap, 10], EVENT_FIELDS) and the counts (int32
+    [B, 3]: all, class 1, class 2 -- not capped).  A call launches on the current stream and does not synchronise; events() reads back."""
+
+    def __init__(self, batch: int, height: int, width: int, connectivity: int = 8, wrap: bool = True, cap: int = 4096, device=None):
+        if connectivity not in (4, 8):
+            raise L.DeepcamHipError(f"EventCatalog: connectivity must be 4 or 8, got {connectivity}")
+        if batch < 1 or height < 1 or width < 1 or cap < 1:
+            raise L.DeepcamHipError("EventCatalog: batch, height, width and cap must be positive")
+        self.B, self.H, self.W, self.connectivity, self.wrap, self.cap = batch, height, width, connectivity, bool(wrap), cap
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.tables = event_weight_tables(height, width)
+        self._wy, self._cx, self._sx = (torch.from_numpy(t).to(dev) for t in self.tables)
+        self._labels = torch.zeros((batch, height, width), dtype=torch.int32, device=dev)
+        self._table = torch.zeros((batch, cap, len(EVENT_FIELDS)), dtype=torch.int64, device=dev)
+        self._ncomp = torch.zeros((batch, 3), dtype=torch.int32, device=dev)
+        self._ws = torch.empty(max(L.load().dc_mask_components_workspace(batch, height, width), 256), dtype=torch.uint8, device=dev)
+        self._last_valid = 0
+
+    def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventCatalog":
+        """mask: device uint8 [B, H, W].  Samples from n_valid on are padding: not read, their labels and counts stay as they were."""
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (self.B, self.H, self.W) or not mask.is_cuda or not mask.is_contiguous():
+            raise L.DeepcamHipError(f"EventCatalog: mask must be a contiguous device uint8 tensor [{self.B}, {self.H}, {self.W}], got "
+                                    f"{mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        nv = self.B if n_valid is None else int(n_valid)
+        st = L.stream_ptr()
+        L.call("dc_mask_components", self.B, nv, self.H, self.W, L.dptr(mask), self.connectivity, int(self.wrap), L.dptr(self._labels),
+               L.dptr(self._ws), st)
+        L.call("dc_component_stats", self.B, nv, self.H, self.W, L.dptr(mask), L.dptr(self._labels), L.dptr(self._wy), L.dptr(self._cx),
+               L.dptr(self._sx), self.cap, L.dptr(self._table), L.dptr(self._ncomp), L.dptr(self._ws), st)
+        self._last_valid = nv
+        return self
+
+    @property
+    def labels(self) -> torch.Tensor:
+        """int32 [n_valid, H, W] of the last call (a view)"""
+        return self._labels[:self._last_valid]
+
+    @property
+    def table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, 10] of the last call (a view): the raw rows, zero beyond min(count, cap)"""
+        return self._table[:self._last_valid]
+
+    def counts(self) -> torch.Tensor:
+        """int32 [n_valid, 3] of the last call (a view): components of any class, of class 1, of class 2"""
+        return self._ncomp[:self._last_valid]
+
+    def rows(self):
+        """(counts, rows) on the host: the counts first, then only the rows that are filled -- one list entry per valid sample, each an
+        int64 numpy array [min(total, cap), 10]."""
+        nv = self._last_valid
+        if nv == 0:
+            return [], []
+        ncomp = self._ncomp[:nv].cpu().numpy()
+        fill = [min(int(t), self.cap) for t in ncomp[:, 0]]
+        host = self._table[:nv, :max(max(fill), 1)].cpu().numpy()
+        return ncomp, [host[b, :fill[b]].copy() for b in range(nv)]
+
+    def events(self, min_pixels: int = 0):
+        """Per valid sample of the last call a list of dicts (decode), components below min_pixels left out on the host."""
+        _, rows = self.rows()
+        return [self.decode(r, self.H, self.W, min_pixels=min_pixels) for r in rows]
+
+    @staticmethod
+    def decode(rows, height: int, width: int, min_pixels: int = 0):
+        """Raw rows [n, 10] (EVENT_FIELDS) -> dicts: class, pixels, area_fraction (area / sum_r W * wy[r]: the share of the sphere), lat (the
+        mean row through linspace(-90, 90, H)), lon (atan2(sum sx, sum cx) in degrees: the circular mean, right across the seam), row_min,
+        row_max, crosses_seam, root."""
+        wy = event_weight_tables(height, width)[0]
+        whole = float(width) * float(wy.astype("int64").sum())
+        out = []
+        for r in rows:
+            root, cls, n, area, sr, scx, ssx, rmin, rmax, seam = (int(v) for v in r)
+            if n < max(min_pixels, 1):
+                continue
+            lat = -90.0 + 180.0 * (sr / n) / (height - 1) if height > 1 else -90.0
+            out.append({"class": cls, "pixels": n, "area_fraction": area / whole if whole > 0 else 0.0, "lat": lat,
+                        "lon": math.degrees(math.atan2(ssx, scx)), "row_min": rmin, "row_max": rmax, "crosses_seam": bool(seam), "root": root})
+        return out
+
+
 class Predictor:
     """Masks for unlabelled data: the eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running
     statistics through the shared arena, pooled activations) whose classifier leaves, per pixel, the first-max class as one byte
     (torch.max(outputs, 1)[1] of train_hdf5_ddp.py:458), optionally its softmax probability, and per sample the pixels of each class
-    (bf16: dc_head_fwd_predict on the logits in registers; fp32: dc_head_fwd + dc_logits_predict).  Nothing here synchronises."""
+    (bf16: dc_head_fwd_predict on the logits in registers; fp32: dc_head_fwd + dc_logits_predict).  Nothing here synchronises.
+    events=True adds `.catalog`, an EventCatalog that runs on the mask of every call."""
 
-    def __init__(self, net: DeepLabv3_plus, batch: int, height: int, width: int, confidence: bool = False):
+    def __init__(self, net: DeepLabv3_plus, batch: int, height: int, width: int, confidence: bool = False, events: bool = False,
+                 event_connectivity: int = 8, event_cap: int = 4096):
         if net.engine is None:
             raise L.DeepcamHipError("Predictor: materialize the model first (its parameters live in the primary engine's arena)")
         self.net, self.B, self.H, self.W = net, batch, height, width
@@ -865,6 +966,8 @@ class Predictor:
         self._last_valid = 0
         self.store_logits = False       # bf16: also write the fp32 NCHW logits (the prediction needs them in registers only)
         self._eng_handle = _ops.engine_handle(self.eng)
+        # events=True: the event catalogue of every mask (EventCatalog below), run behind the classifier on the same stream
+        self.catalog = EventCatalog(batch, height, width, connectivity=event_connectivity, cap=event_cap, device=dev) if events else None
 
     def __call__(self, x: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
         """x: the NCHW fp32 batch or the input pipeline's NHWC batch (Engine.forward); returns the uint8 mask [n_valid, H, W], a view of a
@@ -882,6 +985,8 @@ class Predictor:
         finally:
             eng.predict_args = None
         self._last_valid = nv
+        if self.catalog is not None:
+            self.catalog(self._mask, n_valid=nv)
         return self._mask[:nv]
 
     @property
@@ -901,4 +1006,4 @@ class Predictor:
 
     def close(self) -> None:
         self.eng.close()
-        self._mask = self._conf = self._counts = None
+        self._mask = self._conf = self._counts = self.catalog = None
