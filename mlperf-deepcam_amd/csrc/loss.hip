@@ -2,37 +2,22 @@
 // NCHW fp32 logits (HBM-bound: 12 B/pixel read, 12 B/pixel gradient write, 8 B/pixel labels).
 //   reference: utils/losses.py:28-52 (plain mean of w[y]*CE; the "false positive" factors are identities),
 //              torch.max(outputs,1)[1] (train_hdf5_ddp.py:406,458), utils/utils.py:32-60.
-#include "common.h"
+#include "pixel_score.h"
 
 namespace dc {
 
-constexpr int NC = 3;
-
-// labels outside [0, NC) come back as -1 (the full 64-bit value is compared, not its low half)
-__device__ inline int load_label(const void* labels, int bytes, long i) {
-  long long v;
-  if (bytes == 8) v = reinterpret_cast<const int64_t*>(labels)[i];
-  else if (bytes == 4) v = reinterpret_cast<const int32_t*>(labels)[i];
-  else v = reinterpret_cast<const uint8_t*>(labels)[i];
-  return (v >= 0 && v < NC) ? (int)v : -1;
-}
-
-__device__ inline unsigned long long wave_count(bool pred) { return __popcll(__ballot(pred)); }
-
+// The per-pixel arithmetic and the workgroup reduction of the four kernels below are pixel_score.h's; a kernel here is its index walk.
 __global__ __launch_bounds__(256) void wce_kernel(int B, long HW, const float* __restrict__ logits,
                                                   const void* __restrict__ labels, int lbytes,
                                                   const float* __restrict__ cw, float grad_scale, double* loss_sum,
                                                   float* __restrict__ dlogits, int64_t* __restrict__ pred,
                                                   unsigned long long* counts) {
   __shared__ double s_loss[4];
-  __shared__ unsigned long long s_cnt[4][9];
+  __shared__ unsigned long long s_cnt[4 * 9];
   const long total = (long)B * HW;
-  const float w0 = cw[0], w1 = cw[1], w2 = cw[2];
+  const ClassWeights w = load_class_weights(cw);
   double lsum = 0.0;
-  unsigned long long cnt[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) cnt[k] = 0ull;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Confusion cf;
   // the trip count is made wave-uniform so that the ballots below see all 64 lanes
   const long stride = (long)gridDim.x * blockDim.x;
   const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -41,84 +26,37 @@ __global__ __launch_bounds__(256) void wce_kernel(int B, long HW, const float* _
     const long i = first + it * stride;
     const bool ok = i < total;
     int y = 0, am = 0;
-    bool valid = false;
     if (ok) {
       const long b = i / HW, p = i - b * HW;
       const float* lp = logits + (size_t)b * NC * HW + p;
       const float l0 = lp[0], l1 = lp[HW], l2 = lp[2 * HW];
       y = load_label(labels, lbytes, i);
-      valid = (unsigned)y < (unsigned)NC;
-      float best = l0;
-      if (l1 > best) { best = l1; am = 1; }
-      if (l2 > best) { best = l2; am = 2; }
-      const float e0 = expf(l0 - best), e1 = expf(l1 - best), e2 = expf(l2 - best);
-      const float se = e0 + e1 + e2;
-      const float lse = best + logf(se);
-      if (valid) {
-        const float wy = y == 0 ? w0 : (y == 1 ? w1 : w2);
-        const float ly = y == 0 ? l0 : (y == 1 ? l1 : l2);
-        lsum += (double)(wy * (lse - ly));
-        if (dlogits != nullptr) {
-          const float inv = 1.0f / se;
-          const float s = wy * grad_scale;
-          float* gp = dlogits + (size_t)b * NC * HW + p;
-          gp[0] = s * (e0 * inv - (y == 0 ? 1.f : 0.f));
-          gp[HW] = s * (e1 * inv - (y == 1 ? 1.f : 0.f));
-          gp[2 * HW] = s * (e2 * inv - (y == 2 ? 1.f : 0.f));
-        }
-      } else {
-        // A label outside [0, 3): nn.CrossEntropyLoss raises for it in the reference (losses.py:36).  A kernel cannot raise and
-        // this ABI never synchronises, so the result is poisoned instead of silently dropping the pixel: the loss and this
-        // pixel's gradient become NaN, which reaches every weight in the same step.
-        lsum += (double)__builtin_nanf("");
-        if (dlogits != nullptr) {
-          float* gp = dlogits + (size_t)b * NC * HW + p;
-          gp[0] = gp[HW] = gp[2 * HW] = __builtin_nanf("");
-        }
-      }
+      const FirstMax m = first_max(l0, l1, l2);
+      am = m.am;
+      lsum += (double)wce_pixel(l0, l1, l2, m.best, y, w, grad_scale, dlogits != nullptr ? dlogits + (size_t)b * NC * HW + p : nullptr, HW);
       if (pred != nullptr) pred[i] = am;
     }
-    if (counts != nullptr) {
-      const bool eq = ok && (am == y);
-      const bool ne = ok && (am != y);
-#pragma unroll
-      for (int j = 0; j < NC; ++j) {
-        cnt[j] += wave_count(eq && y == j);          // tp: agree and gt == j
-        cnt[3 + j] += wave_count(ne && am == j);     // fp: disagree and pred == j
-        cnt[6 + j] += wave_count(ne && y == j);      // fn: disagree and gt == j
-      }
-    }
+    if (counts != nullptr) cf.add(ok, am, y);
   }
-  lsum = wave_sum(lsum);
-  if (lane == 0) {
-    s_loss[wave] = lsum;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s_cnt[wave][k] = cnt[k];  // wave-uniform already
-  }
+  stage_loss(lsum, s_loss);
+  stage_counts(cf.c, s_cnt);
   __syncthreads();
-  if (threadIdx.x == 0 && loss_sum != nullptr) atomicAdd(loss_sum, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
-  if (threadIdx.x < 9 && counts != nullptr) {
-    const int k = threadIdx.x;
-    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
-    if (c) atomicAdd(&counts[k], c);
-  }
+  commit_loss(s_loss, loss_sum, 0);
+  commit_counts<9>(s_cnt, counts, 0);
 }
 
-// wce_kernel's loss and count arithmetic for the validation pass: no gradient, no prediction store, and blockIdx.y is the sample, so a
-// workgroup's partial sums belong to one sample and land in that sample's entries.
+// The validation pass: no gradient, no prediction store, and blockIdx.y is the sample, so a workgroup's partial sums belong to one sample
+// and land in that sample's entries.
 __global__ __launch_bounds__(256) void wce_score_kernel(long HW, const float* __restrict__ logits, const void* __restrict__ labels,
                                                         int lbytes, const float* __restrict__ cw, double* loss_sum,
                                                         unsigned long long* counts) {
   __shared__ double s_loss[4];
-  __shared__ unsigned long long s_cnt[4][9];
+  __shared__ unsigned long long s_cnt[4 * 9];
   const int b = blockIdx.y;
-  const float w0 = cw[0], w1 = cw[1], w2 = cw[2];
+  const ClassWeights w = load_class_weights(cw);
   const float* lb = logits + (size_t)b * NC * HW;
   double lsum = 0.0;
-  unsigned long long cnt[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) cnt[k] = 0ull;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Confusion cf;
   // the trip count is wave-uniform so that the ballots below see all 64 lanes
   const long stride = (long)gridDim.x * blockDim.x;
   const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -129,55 +67,28 @@ __global__ __launch_bounds__(256) void wce_score_kernel(long HW, const float* __
     int y = 0, am = 0;
     if (ok) {
       const float l0 = lb[p], l1 = lb[HW + p], l2 = lb[2 * HW + p];
-      y = load_label(labels, lbytes, (long)b * HW + p);
-      float best = l0;
-      if (l1 > best) { best = l1; am = 1; }
-      if (l2 > best) { best = l2; am = 2; }
-      const float e0 = expf(l0 - best), e1 = expf(l1 - best), e2 = expf(l2 - best);
-      const float se = e0 + e1 + e2;
-      const float lse = best + logf(se);
-      if ((unsigned)y < (unsigned)NC) {
-        const float wy = y == 0 ? w0 : (y == 1 ? w1 : w2);
-        const float ly = y == 0 ? l0 : (y == 1 ? l1 : l2);
-        lsum += (double)(wy * (lse - ly));
-      } else {
-        lsum += (double)__builtin_nanf("");          // as wce_kernel: the sample's loss is poisoned, nothing is dropped silently
-      }
+      y = load_label(labels, lbytes, (size_t)b * HW + p);
+      const FirstMax m = first_max(l0, l1, l2);
+      am = m.am;
+      lsum += (double)wce_pixel(l0, l1, l2, m.best, y, w, 0.f, nullptr, 0);
     }
-    const bool eq = ok && (am == y);
-    const bool ne = ok && (am != y);
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      cnt[j] += wave_count(eq && y == j);
-      cnt[3 + j] += wave_count(ne && am == j);
-      cnt[6 + j] += wave_count(ne && y == j);
-    }
+    cf.add(ok, am, y);
   }
-  lsum = wave_sum(lsum);
-  if (lane == 0) {
-    s_loss[wave] = lsum;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s_cnt[wave][k] = cnt[k];
-  }
+  stage_loss(lsum, s_loss);
+  stage_counts(cf.c, s_cnt);
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss_sum + b, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
-  if (threadIdx.x < 9) {
-    const int k = threadIdx.x;
-    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
-    if (c) atomicAdd(&counts[(size_t)b * 9 + k], c);
-  }
+  commit_loss(s_loss, loss_sum, b);
+  commit_counts<9>(s_cnt, counts, b);
 }
 
 // Inference on stored logits (dc_logits_predict): the first-max class as one byte, optionally its softmax probability, and the pixel count
-// per class of each sample.  The statements are those of head_fused_fwd_kernel<PREDICT> (stem_head.hip), so equal logits give equal bits;
-// blockIdx.y is the sample as in wce_score_kernel.
+// per class of each sample; blockIdx.y is the sample as in wce_score_kernel.
 __global__ __launch_bounds__(256) void logits_predict_kernel(long HW, const float* __restrict__ logits, uint8_t* __restrict__ mask,
                                                              float* __restrict__ conf, unsigned long long* counts) {
-  __shared__ unsigned long long s_cnt[4][NC];
+  __shared__ unsigned long long s_cnt[4 * NC];
   const int b = blockIdx.y;
   const float* lb = logits + (size_t)b * NC * HW;
-  unsigned long long cnt[NC] = {0ull, 0ull, 0ull};
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  ClassCount cc;
   // the trip count is wave-uniform so that the ballots below see all 64 lanes
   const long stride = (long)gridDim.x * blockDim.x;
   const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -189,31 +100,17 @@ __global__ __launch_bounds__(256) void logits_predict_kernel(long HW, const floa
     if (ok) {
       const float l0 = lb[p], l1 = lb[HW + p], l2 = lb[2 * HW + p];
       const size_t gi = (size_t)b * HW + p;
-      float best = l0;
-      if (l1 > best) { best = l1; am = 1; }
-      if (l2 > best) { best = l2; am = 2; }
+      const FirstMax m = first_max(l0, l1, l2);
+      am = m.am;
       mask[gi] = (uint8_t)am;
-      if (conf != nullptr) {
-        const float e0 = expf(l0 - best), e1 = expf(l1 - best), e2 = expf(l2 - best);
-        conf[gi] = 1.0f / (e0 + e1 + e2);
-      }
+      if (conf != nullptr) conf[gi] = 1.0f / softmax_terms(l0, l1, l2, m.best).se;
     }
-    if (counts != nullptr) {
-#pragma unroll
-      for (int j = 0; j < NC; ++j) cnt[j] += wave_count(ok && am == j);
-    }
+    if (counts != nullptr) cc.add(ok, am);
   }
   if (counts == nullptr) return;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) s_cnt[wave][k] = cnt[k];
-  }
+  stage_counts(cc.c, s_cnt);
   __syncthreads();
-  if (threadIdx.x < NC) {
-    const int k = threadIdx.x;
-    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
-    if (c) atomicAdd(&counts[(size_t)b * NC + k], c);
-  }
+  commit_counts<NC>(s_cnt, counts, b);
 }
 
 // One thread walks the samples in order: the three running sums do not depend on how anything was scheduled.
@@ -247,36 +144,19 @@ __global__ void val_accumulate_kernel(int n_valid, long HW, const double* __rest
 __global__ __launch_bounds__(256) void confusion_kernel(long n, const int64_t* __restrict__ pred,
                                                         const void* __restrict__ labels, int lbytes,
                                                         unsigned long long* counts) {
-  __shared__ unsigned long long s_cnt[4][9];
-  unsigned long long cnt[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) cnt[k] = 0ull;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ unsigned long long s_cnt[4 * 9];
+  Confusion cf;
   const long stride = (long)gridDim.x * blockDim.x;
   const long first = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const long iters = (n + stride - 1) / stride;
   for (long it = 0; it < iters; ++it) {
     const long i = first + it * stride;
     const bool ok = i < n;
-    const int am = ok ? (int)pred[i] : -1;
-    const int y = ok ? load_label(labels, lbytes, i) : -2;
-    const bool eq = ok && am == y, ne = ok && am != y;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      cnt[j] += wave_count(eq && y == j);
-      cnt[3 + j] += wave_count(ne && am == j);
-      cnt[6 + j] += wave_count(ne && y == j);
-    }
+    cf.add(ok, ok ? (int)pred[i] : -1, ok ? load_label(labels, lbytes, i) : -2);
   }
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s_cnt[wave][k] = cnt[k];
+  stage_counts(cf.c, s_cnt);
   __syncthreads();
-  if (threadIdx.x < 9) {
-    const int k = threadIdx.x;
-    const unsigned long long c = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
-    if (c) atomicAdd(&counts[k], c);
-  }
+  commit_counts<9>(s_cnt, counts, 0);
 }
 
 }  // namespace dc

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "lds_tr_image.h"
 #include "mfma_tile.h"
+#include "pixel_score.h"
 #include "wgrad.h"
 
 namespace dc {
@@ -179,7 +180,6 @@ __global__ __launch_bounds__(256) void slab_rows_reduce_kernel(const float* __re
 //             logits(2qy+py, 2qx+px) = sum of the 1/2/2/4 taps of P at (qy,qx), (qy,qx+1), (qy+1,qx), (qy+1,qx+1)
 //   backward  dP[pixel][co*9+t] = dlogits[n, co, 2qy-1+ky, 2qx-1+kx]      (gather, zero outside)
 //             dx = dP . W^T (1x1 data-gradient GEMM),   dW = x^T . dP (pixel-reduction GEMM)
-constexpr int HEAD_NC = 3;
 constexpr int HEAD_NP = 32;   // 27 products padded to an MFMA-friendly width
 
 template <typename T>
@@ -187,7 +187,7 @@ __global__ void head_pack_kernel(const float* __restrict__ w, T* __restrict__ wf
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= HEAD_NP * Cin) return;
   const int j = i / Cin, ci = i % Cin;
-  const float v = j < HEAD_NC * 9 ? w[(size_t)ci * (HEAD_NC * 9) + j] : 0.f;   // master [ci][co][ky][kx]
+  const float v = j < NC * 9 ? w[(size_t)ci * (NC * 9) + j] : 0.f;   // master [ci][co][ky][kx]
   Elem<T>::store(wf + (size_t)j * Cin + ci, v);
   Elem<T>::store(wb + (size_t)ci * HEAD_NP + j, v);
 }
@@ -209,14 +209,14 @@ __global__ __launch_bounds__(256) void head_combine_kernel(const float* __restri
   const float* p11 = p10 + HEAD_NP;
   const int Ho = 2 * Hi, Wo = 2 * Wi;
 #pragma unroll
-  for (int co = 0; co < HEAD_NC; ++co) {
+  for (int co = 0; co < NC; ++co) {
     const float* a = p00 + co * 9;
     const float o00 = a[4];
     float o01 = a[5], o10 = a[7], o11 = a[8];
     if (hx) { o01 += p01[co * 9 + 3]; o11 += p01[co * 9 + 6]; }
     if (hy) { o10 += p10[co * 9 + 1]; o11 += p10[co * 9 + 2]; }
     if (hx && hy) o11 += p11[co * 9 + 0];
-    float* base = out + (((size_t)n * HEAD_NC + co) * Ho + 2 * qy) * Wo + 2 * qx;
+    float* base = out + (((size_t)n * NC + co) * Ho + 2 * qy) * Wo + 2 * qx;
     *reinterpret_cast<float2*>(base) = make_float2(o00, o01);
     *reinterpret_cast<float2*>(base + Wo) = make_float2(o10, o11);
   }
@@ -234,7 +234,7 @@ constexpr int HF_PX = (HF_TY + 1) * (HF_TX + 1);        // 165 product pixels pe
 constexpr int HF_MB = (HF_PX + 15) / 16;                // 11 MFMA row blocks
 constexpr int HF_TILES = 6;                             // tiles per workgroup (along x), amortises the weight image
 
-// LOSS: the weighted cross-entropy pass (loss.hip: wce_kernel, same arithmetic statement for statement, so the same bits) runs on the
+// LOSS: the weighted cross-entropy pass (the per-pixel arithmetic of loss.hip's wce_kernel: pixel_score.h) runs on the
 // logits of a tile while they are still in registers: the fp32 NCHW logits are then written only if the caller wants them (`out`
 // may be null) and never read back (reference: upsample.last_deconv, deeplab_xception.py:374,382, followed by utils/losses.py:35-50).
 // BNIN: x is the raw output y of the convolution in front of a BatchNorm(+ReLU) and the head's real input act(y * scale + shift) is formed
@@ -257,14 +257,6 @@ struct HeadLoss {
   unsigned long long* counts;
 };
 
-__device__ inline int head_load_label(const void* labels, int bytes, size_t i) {
-  long long v;
-  if (bytes == 8) v = reinterpret_cast<const int64_t*>(labels)[i];
-  else if (bytes == 4) v = reinterpret_cast<const int32_t*>(labels)[i];
-  else v = reinterpret_cast<const uint8_t*>(labels)[i];
-  return (v >= 0 && v < HEAD_NC) ? (int)v : -1;
-}
-
 // What dc_head_fwd_predict leaves behind the classifier: the class map, its confidence and the per-sample class pixel counts
 struct HeadPredict {
   uint8_t* mask;
@@ -275,8 +267,19 @@ struct HeadPredict {
 // SCORE (with LOSS): the validation pass's per-sample sums (dc_head_fwd_score): a workgroup works on ONE sample n (blockIdx.x -> strip, row
 // of tiles, n), so its partial loss and counts are that sample's and go to loss_sum[n] / counts[n][9]; the grid covers the valid samples only.
 // PREDICT (without LOSS): inference on unlabelled data (dc_head_fwd_predict): the grid of SCORE, and per pixel the first-max class (the `am` of
-// the LOSS path) as one byte, optionally its softmax probability, and the sample's pixel count per class in hp.counts[n][3]
+// the LOSS path, pixel_score.h) as one byte, optionally its softmax probability, and the sample's pixel count per class in hp.counts[n][3]
 // (reference: torch.max(outputs, 1)[1], train_hdf5_ddp.py:458, on a batch that has no labels).
+
+// One logit of the tile: class co at output pixel (2 * qy_l + py, 2 * qx_l + px), from the products P of the tile's 5 x 33 input pixels
+__device__ inline float head_tap_sum(const float* P, int qy_l, int qx_l, int py, int px, int co) {
+  const float* p00 = P + (qy_l * (HF_TX + 1) + qx_l) * HEAD_NP + co * 9;
+  const float* p01 = p00 + HEAD_NP;
+  const float* p10 = p00 + (HF_TX + 1) * HEAD_NP;
+  const float* p11 = p10 + HEAD_NP;
+  if (py == 0) return px == 0 ? p00[4] : p00[5] + p01[3];
+  return px == 0 ? p00[7] + p10[1] : ((p00[8] + p01[6]) + p10[2]) + p11[0];
+}
+
 template <bool LOSS, bool BNIN = false, bool SCORE = false, bool PREDICT = false>
 __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ wf,
                                                              float* __restrict__ out, int N, int Hi, int Wi, int Cin, int ntx, const HeadLoss hl,
@@ -309,7 +312,10 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
   const int y0 = ty * HF_TY;
   const int Ho = 2 * Hi, Wo = 2 * Wi;
   [[maybe_unused]] double lsum = 0.0;
-  [[maybe_unused]] unsigned long long cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  [[maybe_unused]] Confusion cf;     // LOSS
+  [[maybe_unused]] ClassCount cc;    // PREDICT
+  [[maybe_unused]] ClassWeights cw{};
+  if constexpr (LOSS) cw = load_class_weights(hl.cw);
   for (int tt = 0; tt < HF_TILES; ++tt) {
     const int tx = strip * HF_TILES + tt;
     if (tx >= ntx) break;
@@ -373,71 +379,20 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
       cur_ok = nxt_ok;
     }
     __syncthreads();
-    if constexpr (PREDICT) {
-      // one output PIXEL per thread and pass as in the LOSS branch below (same addition order, same `am`); a wave covers one output row of
-      // the tile, so its 64 mask bytes are consecutive
-      constexpr int NPIX = 2 * HF_TY * 2 * HF_TX;
-#pragma unroll
-      for (int it = 0; it < NPIX / 256; ++it) {
-        const int i = tid + it * 256;
-        const int ox_l = i % (2 * HF_TX), oy_l = i / (2 * HF_TX);
-        const int qy_l = oy_l >> 1, py = oy_l & 1, qx_l = ox_l >> 1, px = ox_l & 1;
-        const int qy = y0 + qy_l, qx = x0 + qx_l;
-        const bool ok = qy < Hi && qx < Wi;
-        float l[HEAD_NC] = {0.f, 0.f, 0.f};
-        int am = 0;
-        if (ok) {
-#pragma unroll
-          for (int co = 0; co < HEAD_NC; ++co) {
-            const float* p00 = P + (qy_l * (HF_TX + 1) + qx_l) * HEAD_NP + co * 9;
-            const float* p01 = p00 + HEAD_NP;
-            const float* p10 = p00 + (HF_TX + 1) * HEAD_NP;
-            const float* p11 = p10 + HEAD_NP;
-            if (py == 0) l[co] = px == 0 ? p00[4] : p00[5] + p01[3];
-            else l[co] = px == 0 ? p00[7] + p10[1] : ((p00[8] + p01[6]) + p10[2]) + p11[0];
-          }
-          const size_t HWo = (size_t)Ho * Wo;
-          const size_t pix = (size_t)(2 * qy + py) * Wo + 2 * qx + px;
-          if (out != nullptr) {
-#pragma unroll
-            for (int co = 0; co < HEAD_NC; ++co) out[((size_t)n * HEAD_NC + co) * HWo + pix] = l[co];
-          }
-          const size_t gi = (size_t)n * HWo + pix;
-          float best = l[0];
-          if (l[1] > best) { best = l[1]; am = 1; }
-          if (l[2] > best) { best = l[2]; am = 2; }
-          hp.mask[gi] = (uint8_t)am;
-          if (hp.conf != nullptr) {
-            const float e0 = expf(l[0] - best), e1 = expf(l[1] - best), e2 = expf(l[2] - best);
-            hp.conf[gi] = 1.0f / (e0 + e1 + e2);
-          }
-        }
-        if (hp.counts != nullptr) {
-#pragma unroll
-          for (int j = 0; j < HEAD_NC; ++j) cnt[j] += __popcll(__ballot(ok && am == j));
-        }
-      }
-    } else if constexpr (!LOSS) {
+    if constexpr (!LOSS && !PREDICT) {
       // combine: 2*HF_TY x 2*HF_TX outputs per class, consecutive lanes along x
-      for (int i = tid; i < HEAD_NC * 2 * HF_TY * 2 * HF_TX; i += 256) {
+      for (int i = tid; i < NC * 2 * HF_TY * 2 * HF_TX; i += 256) {
         const int ox_l = i % (2 * HF_TX);
         const int t2 = i / (2 * HF_TX);
         const int oy_l = t2 % (2 * HF_TY), co = t2 / (2 * HF_TY);
         const int qy_l = oy_l >> 1, py = oy_l & 1, qx_l = ox_l >> 1, px = ox_l & 1;
         const int qy = y0 + qy_l, qx = x0 + qx_l;
-        if (qy < Hi && qx < Wi) {
-          const float* p00 = P + (qy_l * (HF_TX + 1) + qx_l) * HEAD_NP + co * 9;
-          const float* p01 = p00 + HEAD_NP;
-          const float* p10 = p00 + (HF_TX + 1) * HEAD_NP;
-          const float* p11 = p10 + HEAD_NP;
-          float o;
-          if (py == 0) o = px == 0 ? p00[4] : p00[5] + p01[3];
-          else o = px == 0 ? p00[7] + p10[1] : ((p00[8] + p01[6]) + p10[2]) + p11[0];
-          out[(((size_t)n * HEAD_NC + co) * Ho + 2 * qy + py) * Wo + 2 * qx + px] = o;
-        }
+        if (qy < Hi && qx < Wi)
+          out[(((size_t)n * NC + co) * Ho + 2 * qy + py) * Wo + 2 * qx + px] = head_tap_sum(P, qy_l, qx_l, py, px, co);
       }
     } else {
-      // combine one output PIXEL per thread and pass (its three logits with the same addition order as above), then the loss on them
+      // one output PIXEL per thread and pass (its three logits with the same addition order as above), then the loss or the prediction on
+      // them (pixel_score.h); a wave covers one output row of the tile, so its 64 mask bytes are consecutive
       constexpr int NPIX = 2 * HF_TY * 2 * HF_TX;   // 512: two wave-uniform passes
 #pragma unroll
       for (int it = 0; it < NPIX / 256; ++it) {
@@ -446,95 +401,57 @@ __global__ __launch_bounds__(256) void head_fused_fwd_kernel(const bf16* __restr
         const int qy_l = oy_l >> 1, py = oy_l & 1, qx_l = ox_l >> 1, px = ox_l & 1;
         const int qy = y0 + qy_l, qx = x0 + qx_l;
         const bool ok = qy < Hi && qx < Wi;
-        float l[HEAD_NC] = {0.f, 0.f, 0.f};
         int y = 0, am = 0;
         if (ok) {
+          float l[NC];
 #pragma unroll
-          for (int co = 0; co < HEAD_NC; ++co) {
-            const float* p00 = P + (qy_l * (HF_TX + 1) + qx_l) * HEAD_NP + co * 9;
-            const float* p01 = p00 + HEAD_NP;
-            const float* p10 = p00 + (HF_TX + 1) * HEAD_NP;
-            const float* p11 = p10 + HEAD_NP;
-            if (py == 0) l[co] = px == 0 ? p00[4] : p00[5] + p01[3];
-            else l[co] = px == 0 ? p00[7] + p10[1] : ((p00[8] + p01[6]) + p10[2]) + p11[0];
-          }
+          for (int co = 0; co < NC; ++co) l[co] = head_tap_sum(P, qy_l, qx_l, py, px, co);
           const size_t HWo = (size_t)Ho * Wo;
           const size_t pix = (size_t)(2 * qy + py) * Wo + 2 * qx + px;
           if (out != nullptr) {
 #pragma unroll
-            for (int co = 0; co < HEAD_NC; ++co) out[((size_t)n * HEAD_NC + co) * HWo + pix] = l[co];
+            for (int co = 0; co < NC; ++co) out[((size_t)n * NC + co) * HWo + pix] = l[co];
           }
           const size_t gi = (size_t)n * HWo + pix;
-          y = head_load_label(hl.labels, hl.lbytes, gi);
-          float best = l[0];
-          if (l[1] > best) { best = l[1]; am = 1; }
-          if (l[2] > best) { best = l[2]; am = 2; }
-          const float e0 = expf(l[0] - best), e1 = expf(l[1] - best), e2 = expf(l[2] - best);
-          const float se = e0 + e1 + e2;
-          const float lse = best + logf(se);
-          float* gp = hl.dlogits != nullptr ? hl.dlogits + (size_t)n * HEAD_NC * HWo + pix : nullptr;
-          if ((unsigned)y < (unsigned)HEAD_NC) {
-            const float wy = hl.cw[y];
-            const float ly = y == 0 ? l[0] : (y == 1 ? l[1] : l[2]);
-            lsum += (double)(wy * (lse - ly));
-            if (gp != nullptr) {
-              const float inv = 1.0f / se;
-              const float sc = wy * hl.grad_scale;
-              gp[0] = sc * (e0 * inv - (y == 0 ? 1.f : 0.f));
-              gp[HWo] = sc * (e1 * inv - (y == 1 ? 1.f : 0.f));
-              gp[2 * HWo] = sc * (e2 * inv - (y == 2 ? 1.f : 0.f));
-            }
-          } else {   // a label outside [0, 3) poisons the loss and this pixel's gradient, as dc_wce_fused does
-            lsum += (double)__builtin_nanf("");
-            if (gp != nullptr) gp[0] = gp[HWo] = gp[2 * HWo] = __builtin_nanf("");
+          const FirstMax m = first_max(l[0], l[1], l[2]);
+          am = m.am;
+          if constexpr (PREDICT) {
+            hp.mask[gi] = (uint8_t)am;
+            if (hp.conf != nullptr) hp.conf[gi] = 1.0f / softmax_terms(l[0], l[1], l[2], m.best).se;
+          } else {
+            y = load_label(hl.labels, hl.lbytes, gi);
+            lsum += (double)wce_pixel(l[0], l[1], l[2], m.best, y, cw, hl.grad_scale,
+                                      hl.dlogits != nullptr ? hl.dlogits + (size_t)n * NC * HWo + pix : nullptr, HWo);
+            if (hl.pred != nullptr) hl.pred[gi] = am;
           }
-          if (hl.pred != nullptr) hl.pred[gi] = am;
         }
-        if (hl.counts != nullptr) {
-          const bool eq = ok && (am == y), ne = ok && (am != y);
-#pragma unroll
-          for (int j = 0; j < HEAD_NC; ++j) {
-            cnt[j] += __popcll(__ballot(eq && y == j));
-            cnt[3 + j] += __popcll(__ballot(ne && am == j));
-            cnt[6 + j] += __popcll(__ballot(ne && y == j));
-          }
+        if constexpr (PREDICT) {
+          if (hp.counts != nullptr) cc.add(ok, am);
+        } else {
+          if (hl.counts != nullptr) cf.add(ok, am, y);
         }
       }
     }
   }
+  // P is dead: its first bytes take the block's partial sums (4 doubles, then the counters 64 bytes in)
+  [[maybe_unused]] unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + 64);
   if constexpr (PREDICT) {
     if (hp.counts != nullptr) {                       // (a kernel argument: uniform over the workgroup)
-      __syncthreads();                                // P is dead: reuse its first bytes for the block's partial counts
-      unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem);
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < HEAD_NC; ++k) s_cnt[wave * HEAD_NC + k] = cnt[k];
-      }
       __syncthreads();
-      if (tid < HEAD_NC) {
-        const unsigned long long c = s_cnt[tid] + s_cnt[HEAD_NC + tid] + s_cnt[2 * HEAD_NC + tid] + s_cnt[3 * HEAD_NC + tid];
-        if (c) atomicAdd(&hp.counts[(size_t)n * HEAD_NC + tid], c);
-      }
+      stage_counts(cc.c, s_cnt);
+      __syncthreads();
+      commit_counts<NC>(s_cnt, hp.counts, n);
     }
   }
   if constexpr (LOSS) {
-    __syncthreads();                                  // P is dead: reuse its first bytes for the block's partial sums
     double* s_loss = reinterpret_cast<double*>(smem);
-    unsigned long long* s_cnt = reinterpret_cast<unsigned long long*>(smem + 64);
-    lsum = wave_sum(lsum);
-    if (lane == 0) {
-      s_loss[wave] = lsum;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) s_cnt[wave * 9 + k] = cnt[k];
-    }
     __syncthreads();
-    size_t so = 0;
-    if constexpr (SCORE) so = (size_t)n;
-    if (tid == 0 && hl.loss_sum != nullptr) atomicAdd(hl.loss_sum + so, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
-    if (tid < 9 && hl.counts != nullptr) {
-      const unsigned long long c = s_cnt[tid] + s_cnt[9 + tid] + s_cnt[18 + tid] + s_cnt[27 + tid];
-      if (c) atomicAdd(&hl.counts[so * 9 + tid], c);
-    }
+    stage_loss(lsum, s_loss);
+    stage_counts(cf.c, s_cnt);
+    __syncthreads();
+    const size_t so = SCORE ? (size_t)n : 0;
+    commit_loss(s_loss, hl.loss_sum, so);
+    commit_counts<9>(s_cnt, hl.counts, so);
   }
 }
 
@@ -552,11 +469,11 @@ __global__ __launch_bounds__(256) void head_gather_kernel(const float* __restric
 #pragma unroll
   for (int j = 0; j < HEAD_NP; ++j) v[j] = 0.f;
 #pragma unroll
-  for (int co = 0; co < HEAD_NC; ++co)
+  for (int co = 0; co < NC; ++co)
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int oy = 2 * qy - 1 + t / 3, ox = 2 * qx - 1 + t % 3;
-      if ((unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo) v[co * 9 + t] = dl[(((size_t)n * HEAD_NC + co) * Ho + oy) * Wo + ox];
+      if ((unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo) v[co * 9 + t] = dl[(((size_t)n * NC + co) * Ho + oy) * Wo + ox];
     }
   constexpr int KPV = Elem<T>::kPerVec;
   T* dst = dP + (size_t)pix * HEAD_NP;
@@ -574,8 +491,8 @@ __global__ __launch_bounds__(256) void head_gather_kernel(const float* __restric
 // grad[ci][co][ky][kx] = tmp[(co*9+t)][ci]
 __global__ void head_wfinish_kernel(const float* __restrict__ tmp, float* __restrict__ grad, int Cin) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Cin * HEAD_NC * 9) return;
-  const int ci = i / (HEAD_NC * 9), j = i % (HEAD_NC * 9);
+  if (i >= Cin * NC * 9) return;
+  const int ci = i / (NC * 9), j = i % (NC * 9);
   grad[i] = tmp[(size_t)j * Cin + ci];
 }
 
@@ -865,6 +782,21 @@ extern "C" int dc_wce_score(int B, int n_valid, int H, int W, const float* logit
 extern "C" int dc_logits_predict(int B, int n_valid, int H, int W, const float* logits_nchw, uint8_t* mask, float* conf, int64_t* class_counts,
                                  void* stream);
 
+// The launch of one (LOSS, SCORE, PREDICT) mode of head_fused_fwd_kernel, on a stored input or (bi) on a BatchNorm's input; the dynamic
+// LDS attribute is set at an instantiation's first launch
+template <bool LOSS, bool SCORE, bool PREDICT>
+static int head_fused_launch(int blocks, size_t lds, hipStream_t st, const bf16* x, int ldx, const bf16* wf, float* out, int N, int Hi, int Wi,
+                             int Cin, int ntx, const HeadLoss* hl, const HeadBnIn* bi, const HeadPredict* hp) {
+  const bool bnin = bi != nullptr;
+  auto k = bnin ? &head_fused_fwd_kernel<LOSS, true, SCORE, PREDICT> : &head_fused_fwd_kernel<LOSS, false, SCORE, PREDICT>;
+  static std::once_flag once[2];
+  std::call_once(once[bnin], [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, x, ldx, wf, out, N, Hi, Wi, Cin, ntx, LOSS ? *hl : HeadLoss{}, bnin ? *bi : HeadBnIn{},
+                     PREDICT ? *hp : HeadPredict{});
+  DC_LAUNCHED("head_fwd_fused");
+  return 0;
+}
+
 // n_score >= 0: the per-sample epilogue of dc_head_fwd_score over the first n_score samples (hl's loss_sum / counts are then per sample);
 // with hp: dc_head_fwd_predict's epilogue over them instead (no labels, hl is null)
 static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w, float* logits_nchw,
@@ -882,58 +814,14 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   if (dtype == DC_BF16 && g_options.head_fused && Cin == 256) {
     const int ntx = cdiv(Wi, HF_TX), nty = cdiv(Hi, HF_TY), strips = cdiv(ntx, HF_TILES);
     const size_t lds = (size_t)HF_MB * 16 * HEAD_NP * 4 + (size_t)HEAD_NP * Cin * 2 + (size_t)2 * Cin * 4;
-    auto k0 = &head_fused_fwd_kernel<false>;
-    auto k1 = &head_fused_fwd_kernel<true>;
-    auto k2 = &head_fused_fwd_kernel<false, true>;
-    auto k3 = &head_fused_fwd_kernel<true, true>;
-    auto k4 = &head_fused_fwd_kernel<true, false, true>;
-    auto k5 = &head_fused_fwd_kernel<true, true, true>;
-    auto k6 = &head_fused_fwd_kernel<false, false, false, true>;
-    auto k7 = &head_fused_fwd_kernel<false, true, false, true>;
-    DC_ONCE({
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k6), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k7), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (hp != nullptr) {
-      // the shorter grid of the score variant below: the first n_score samples
-      if (n_score == 0) return 0;
-      if (bi != nullptr)
-        hipLaunchKernelGGL(k7, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, *hp);
-      else
-        hipLaunchKernelGGL(k6, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, *hp);
-      DC_LAUNCHED("head_fwd_fused");
-      return 0;
-    }
-    if (n_score >= 0) {
-      // the grid is strips x tile rows x samples with the sample slowest: the first n_score samples are simply the shorter grid
-      if (n_score == 0) return 0;
-      if (bi != nullptr)
-        hipLaunchKernelGGL(k5, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
-      else
-        hipLaunchKernelGGL(k4, dim3(strips * nty * n_score), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
-      DC_LAUNCHED("head_fwd_fused");
-      return 0;
-    }
-    if (bi != nullptr) {
-      if (hl != nullptr)
-        hipLaunchKernelGGL(k3, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, *bi, HeadPredict{});
-      else
-        hipLaunchKernelGGL(k2, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, *bi, HeadPredict{});
-      DC_LAUNCHED("head_fwd_fused");
-      return 0;
-    }
-    if (hl != nullptr)
-      hipLaunchKernelGGL(k1, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, *hl, HeadBnIn{}, HeadPredict{});
-    else
-      hipLaunchKernelGGL(k0, dim3(strips * nty * N), dim3(256), lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, HeadLoss{}, HeadBnIn{}, HeadPredict{});
-    DC_LAUNCHED("head_fwd_fused");
-    return 0;
+    // the grid is strips x tile rows x samples with the sample slowest: the first n_score samples are simply the shorter grid
+    const int blocks = strips * nty * (n_score >= 0 ? n_score : N);
+    if (blocks == 0) return 0;
+    auto launch = hp != nullptr ? &head_fused_launch<false, false, true>
+                : n_score >= 0  ? &head_fused_launch<true, true, false>
+                : hl != nullptr ? &head_fused_launch<true, false, false>
+                                : &head_fused_launch<false, false, false>;
+    return launch(blocks, lds, st, (const bf16*)x, ldx, (const bf16*)ws.wf, logits_nchw, N, Hi, Wi, Cin, ntx, hl, bi, hp);
   }
   DC_REQUIRE(bi == nullptr, "dc_head_fwd_bnin: only the fused bf16 head kernel (256 input channels) applies the BatchNorm while loading");
   DC_REQUIRE(logits_nchw != nullptr, "dc_head_fwd: this configuration (fp32, or the unfused path) needs a logits buffer");
@@ -952,6 +840,24 @@ static int head_fwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
   return 0;
 }
 
+// The argument checks the entry points below share: 0, or the error of entry point `fn`, whose name leads the message
+static int head_check(const char* fn, bool ok, const char* what) {
+  if (ok) return 0;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+  return dc_fail(msg, __FILE__, __LINE__);
+}
+static int head_check_labels(const char* fn, int bytes) {
+  return head_check(fn, bytes == 1 || bytes == 4 || bytes == 8, "labels must be uint8, int32 or int64");
+}
+static int head_check_n_valid(const char* fn, int n_valid, int N) { return head_check(fn, n_valid >= 0 && n_valid <= N, "n_valid must lie in [0, N]"); }
+static int head_check_bnin(const char* fn, int dtype, int Cin) {
+  return head_check(fn, dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "bf16, 256 channels, fused head kernel only");
+}
+static int head_check_predict_align(const char* fn, const float* conf, const int64_t* class_counts) {
+  return head_check(fn, ((uintptr_t)conf & 3) == 0 && ((uintptr_t)class_counts & 7) == 0, "conf / class_counts alignment");
+}
+
 extern "C" int dc_head_fwd(int dtype, int N, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
                            float* logits_nchw, void* workspace, void* stream) {
   DC_REQUIRE(logits_nchw != nullptr, "dc_head_fwd: null logits");
@@ -962,7 +868,7 @@ extern "C" int dc_head_fwd_loss(int dtype, int N, int Cin, int Hi, int Wi, const
                                 void* workspace, const void* labels, int label_dtype_bytes, const float* class_weights, float grad_scale,
                                 double* loss_sum, float* dlogits, int64_t* pred, int64_t* counts, void* stream) {
   DC_REQUIRE(labels && class_weights, "dc_head_fwd_loss: bad argument");
-  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_loss: labels must be uint8, int32 or int64");
+  if (int e = head_check_labels("dc_head_fwd_loss", label_dtype_bytes)) return e;
   HeadLoss hl{labels, label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, &hl);
 }
@@ -971,8 +877,8 @@ extern "C" int dc_head_fwd_score(int dtype, int N, int n_valid, int Cin, int Hi,
                                  float* logits_nchw, void* workspace, const void* labels, int label_dtype_bytes, const float* class_weights,
                                  double* loss_sum, int64_t* counts, void* stream) {
   DC_REQUIRE(labels && class_weights && loss_sum && counts, "dc_head_fwd_score: bad argument");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_score: n_valid must lie in [0, N]");
-  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_score: labels must be uint8, int32 or int64");
+  if (int e = head_check_n_valid("dc_head_fwd_score", n_valid, N)) return e;
+  if (int e = head_check_labels("dc_head_fwd_score", label_dtype_bytes)) return e;
   HeadLoss hl{labels, label_dtype_bytes, class_weights, 0.f, loss_sum, nullptr, nullptr, (unsigned long long*)counts};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, &hl, nullptr, n_valid);
 }
@@ -983,7 +889,7 @@ extern "C" int dc_head_fwd_score(int dtype, int N, int n_valid, int Cin, int Hi,
 extern "C" int dc_head_fwd_bnin(int dtype, int N, int Cin, int Hi, int Wi, const void* y, int ldy, const float* scale, const float* shift,
                                 int relu, const float* w, float* logits_nchw, void* workspace, void* stream) {
   DC_REQUIRE(logits_nchw != nullptr && scale != nullptr && shift != nullptr, "dc_head_fwd_bnin: null argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_bnin: bf16, 256 channels, fused head kernel only");
+  if (int e = head_check_bnin("dc_head_fwd_bnin", dtype, Cin)) return e;
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, nullptr, &bi);
 }
@@ -993,8 +899,8 @@ extern "C" int dc_head_fwd_loss_bnin(int dtype, int N, int Cin, int Hi, int Wi, 
                                      const float* class_weights, float grad_scale, double* loss_sum, float* dlogits, int64_t* pred,
                                      int64_t* counts, void* stream) {
   DC_REQUIRE(labels && class_weights && scale && shift, "dc_head_fwd_loss_bnin: bad argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_loss_bnin: bf16, 256 channels, fused head kernel only");
-  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_loss_bnin: labels must be uint8, int32 or int64");
+  if (int e = head_check_bnin("dc_head_fwd_loss_bnin", dtype, Cin)) return e;
+  if (int e = head_check_labels("dc_head_fwd_loss_bnin", label_dtype_bytes)) return e;
   HeadLoss hl{labels, label_dtype_bytes, class_weights, grad_scale, loss_sum, dlogits, pred, (unsigned long long*)counts};
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, &hl, &bi);
@@ -1004,9 +910,9 @@ extern "C" int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, in
                                       const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, const void* labels,
                                       int label_dtype_bytes, const float* class_weights, double* loss_sum, int64_t* counts, void* stream) {
   DC_REQUIRE(labels && class_weights && scale && shift && loss_sum && counts, "dc_head_fwd_score_bnin: bad argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_score_bnin: bf16, 256 channels, fused head kernel only");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_score_bnin: n_valid must lie in [0, N]");
-  DC_REQUIRE(label_dtype_bytes == 1 || label_dtype_bytes == 4 || label_dtype_bytes == 8, "dc_head_fwd_score_bnin: labels must be uint8, int32 or int64");
+  if (int e = head_check_bnin("dc_head_fwd_score_bnin", dtype, Cin)) return e;
+  if (int e = head_check_n_valid("dc_head_fwd_score_bnin", n_valid, N)) return e;
+  if (int e = head_check_labels("dc_head_fwd_score_bnin", label_dtype_bytes)) return e;
   HeadLoss hl{labels, label_dtype_bytes, class_weights, 0.f, loss_sum, nullptr, nullptr, (unsigned long long*)counts};
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, &hl, &bi, n_valid);
@@ -1017,8 +923,8 @@ extern "C" int dc_head_fwd_score_bnin(int dtype, int N, int n_valid, int Cin, in
 extern "C" int dc_head_fwd_predict(int dtype, int N, int n_valid, int Cin, int Hi, int Wi, const void* x, int ldx, const float* w,
                                    float* logits_nchw, void* workspace, uint8_t* mask, float* conf, int64_t* class_counts, void* stream) {
   DC_REQUIRE(mask != nullptr, "dc_head_fwd_predict: null mask");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_predict: n_valid must lie in [0, N]");
-  DC_REQUIRE(((uintptr_t)conf & 3) == 0 && ((uintptr_t)class_counts & 7) == 0, "dc_head_fwd_predict: conf / class_counts alignment");
+  if (int e = head_check_n_valid("dc_head_fwd_predict", n_valid, N)) return e;
+  if (int e = head_check_predict_align("dc_head_fwd_predict", conf, class_counts)) return e;
   const HeadPredict hp{mask, conf, (unsigned long long*)class_counts};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, x, ldx, w, logits_nchw, workspace, stream, nullptr, nullptr, n_valid, &hp);
 }
@@ -1027,9 +933,9 @@ extern "C" int dc_head_fwd_predict_bnin(int dtype, int N, int n_valid, int Cin, 
                                         const float* shift, int relu, const float* w, float* logits_nchw, void* workspace, uint8_t* mask,
                                         float* conf, int64_t* class_counts, void* stream) {
   DC_REQUIRE(mask != nullptr && scale != nullptr && shift != nullptr, "dc_head_fwd_predict_bnin: null argument");
-  DC_REQUIRE(dtype == DC_BF16 && Cin == 256 && g_options.head_fused, "dc_head_fwd_predict_bnin: bf16, 256 channels, fused head kernel only");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= N, "dc_head_fwd_predict_bnin: n_valid must lie in [0, N]");
-  DC_REQUIRE(((uintptr_t)conf & 3) == 0 && ((uintptr_t)class_counts & 7) == 0, "dc_head_fwd_predict_bnin: conf / class_counts alignment");
+  if (int e = head_check_bnin("dc_head_fwd_predict_bnin", dtype, Cin)) return e;
+  if (int e = head_check_n_valid("dc_head_fwd_predict_bnin", n_valid, N)) return e;
+  if (int e = head_check_predict_align("dc_head_fwd_predict_bnin", conf, class_counts)) return e;
   const HeadPredict hp{mask, conf, (unsigned long long*)class_counts};
   const HeadBnIn bi{scale, shift, relu};
   return head_fwd_impl(dtype, N, Cin, Hi, Wi, y, ldy, w, logits_nchw, workspace, stream, nullptr, &bi, n_valid, &hp);
@@ -1307,7 +1213,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     } else {
       if (int e = conv_wgrad_bnin(&d, N, Hi, Wi, bn_y, bn_ldy, bn_mscale, bn_mshift, bn_relu, ws.dP, HEAD_NP, ws.slabs, ws.slab_bytes, ws.tmp, stream)) return e;
     }
-    hipLaunchKernelGGL(head_wfinish_kernel, dim3(cdiv(Cin * HEAD_NC * 9, 256)), dim3(256), 0, st, (const float*)ws.tmp, grad_w, Cin);
+    hipLaunchKernelGGL(head_wfinish_kernel, dim3(cdiv(Cin * NC * 9, 256)), dim3(256), 0, st, (const float*)ws.tmp, grad_w, Cin);
     DC_CHECK_LAUNCH();
   }
   if (!(parts & 1)) return 0;
@@ -1330,7 +1236,7 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
       DC_LAUNCHED("head_dgrad_stream_wgrad");
       const long nw = (long)HEAD_NP * Cin;
       hipLaunchKernelGGL(slab_rows_reduce_kernel, dim3(cdiv(nw, 8)), dim3(256), 0, st, (const float*)ws.P, ws.tmp, g2, nw);
-      hipLaunchKernelGGL(head_wfinish_kernel, dim3(cdiv(Cin * HEAD_NC * 9, 256)), dim3(256), 0, st, (const float*)ws.tmp, grad_w, Cin);
+      hipLaunchKernelGGL(head_wfinish_kernel, dim3(cdiv(Cin * NC * 9, 256)), dim3(256), 0, st, (const float*)ws.tmp, grad_w, Cin);
       DC_CHECK_LAUNCH();
       return 0;
     }

@@ -1176,72 +1176,46 @@ class Engine:
         self._keep.append(hws)
         hptr = C.c_void_p((hws.data_ptr() + 255) // 256 * 256)
 
-        def head_fwd():
-            if lazy_in:
-                L.call("dc_head_fwd_bnin", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu), self.pptr(wl),
-                       L.dptr(self.logits), hptr, self._st())
-                return
-            L.call("dc_head_fwd", self.dt, B, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), L.dptr(self.logits), hptr, self._st())
+        def head_call(mode="", pre=(), logits=True, post=()):
+            # dc_head_fwd<mode>[_bnin](dt, B, *pre, 256, H, W, <input>, weights, logits, workspace, *post, stream).  The input is the stored
+            # activation, or (lazy_in) the BatchNorm's input with its scale / shift, which the kernel applies while it loads
+            inp = (a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu)) if lazy_in else (a.ptr, a.ld)
+            L.call("dc_head_fwd" + mode + ("_bnin" if lazy_in else ""), self.dt, B, *pre, 256, a.H, a.W, *inp, self.pptr(wl),
+                   L.dptr(self.logits) if logits else None, hptr, *post, self._st())
 
         def head_fwd_train():
             # a fused train step (nn.TrainStep) hands the loss arguments over: the classifier's kernel then computes the weighted
             # cross-entropy, its gradient, the argmax and the IoU counts on the logits it has in registers (dc_head_fwd_loss)
             la = self.loss_args
             if la is None:
-                return head_fwd()
-            if lazy_in:
-                L.call("dc_head_fwd_loss_bnin", self.dt, B, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
-                       self.pptr(wl), L.dptr(self.logits) if la["store_logits"] else None, hptr, L.dptr(la["labels"]), la["labels"].element_size(),
-                       L.dptr(la["weight"]), la["grad_scale"], L.dptr(la["loss_sum"]), L.dptr(self.dlogits), L.dptr(la["pred"]),
-                       L.dptr(la["counts"]), self._st())
-                return
-            L.call("dc_head_fwd_loss", self.dt, B, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), L.dptr(self.logits) if la["store_logits"] else None,
-                   hptr, L.dptr(la["labels"]), la["labels"].element_size(), L.dptr(la["weight"]), la["grad_scale"], L.dptr(la["loss_sum"]),
-                   L.dptr(self.dlogits), L.dptr(la["pred"]), L.dptr(la["counts"]), self._st())
+                return head_call()
+            head_call("_loss", (), la["store_logits"], (L.dptr(la["labels"]), la["labels"].element_size(), L.dptr(la["weight"]), la["grad_scale"],
+                                                       L.dptr(la["loss_sum"]), L.dptr(self.dlogits), L.dptr(la["pred"]), L.dptr(la["counts"])))
 
-        def head_fwd_score():
-            # the validation step (nn.ValStep) hands the score arguments over: per-sample loss sums and IoU counts of the first n_valid samples,
-            # in the classifier's kernel on the logits it has in registers (bf16: dc_head_fwd_score), or by dc_wce_score on the stored ones (fp32)
-            sa = self.score_args
-            if self.predict_args is not None:
-                if sa is not None:
-                    raise L.DeepcamHipError("a forward-only engine either scores against labels (score_args) or predicts (predict_args), not both")
-                return head_fwd_predict()
-            if sa is None:
-                return head_fwd()
-            lab, nv = sa["labels"], sa["n_valid"]
-            tail = (L.dptr(lab), lab.element_size(), L.dptr(sa["weight"]), L.dptr(sa["loss_sum"]), L.dptr(sa["counts"]), self._st())
+        def head_fwd_eval():
+            # A forward-only engine is handed either the score arguments (nn.ValStep: per-sample loss sums and IoU counts) or the prediction
+            # arguments (nn.Predictor: class map, confidence, per-sample class counts) of the first n_valid samples.  bf16: the classifier's
+            # kernel takes them on the logits it has in registers (dc_head_fwd_score / dc_head_fwd_predict; with the head_fused switch off
+            # those store the logits themselves); fp32: dc_wce_score / dc_logits_predict on the stored logits
+            sa, pa = self.score_args, self.predict_args
+            if sa is not None and pa is not None:
+                raise L.DeepcamHipError("a forward-only engine either scores against labels (score_args) or predicts (predict_args), not both")
+            if sa is None and pa is None:
+                return head_call()
+            if sa is not None:
+                mode, after, args = "_score", "dc_wce_score", sa
+                post = (L.dptr(sa["labels"]), sa["labels"].element_size(), L.dptr(sa["weight"]), L.dptr(sa["loss_sum"]), L.dptr(sa["counts"]))
+            else:
+                mode, after, args = "_predict", "dc_logits_predict", pa
+                post = (L.dptr(pa["mask"]), L.dptr(pa["conf"]), L.dptr(pa["class_counts"]))
             if self.dt != L.DC_BF16:
-                head_fwd()
-                L.call("dc_wce_score", B, nv, H, W, L.dptr(self.logits), *tail)
+                head_call()
+                L.call(after, B, args["n_valid"], H, W, L.dptr(self.logits), *post, self._st())
                 return
-            lg = L.dptr(self.logits) if sa["store_logits"] else None
-            if lazy_in:
-                L.call("dc_head_fwd_score_bnin", self.dt, B, nv, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
-                       self.pptr(wl), lg, hptr, *tail)
-                return
-            L.call("dc_head_fwd_score", self.dt, B, nv, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), lg, hptr, *tail)
-
-        def head_fwd_predict():
-            # inference (nn.Predictor) hands the prediction arguments over: the class map, its confidence and the per-sample class counts of the
-            # first n_valid samples, in the classifier's kernel on the logits it has in registers (bf16: dc_head_fwd_predict), or by
-            # dc_logits_predict on the stored ones (fp32; bf16 with the head_fused switch off stores them inside dc_head_fwd_predict)
-            pa = self.predict_args
-            nv = pa["n_valid"]
-            tail = (L.dptr(pa["mask"]), L.dptr(pa["conf"]), L.dptr(pa["class_counts"]), self._st())
-            if self.dt != L.DC_BF16:
-                head_fwd()
-                L.call("dc_logits_predict", B, nv, H, W, L.dptr(self.logits), *tail)
-                return
-            lg = L.dptr(self.logits) if pa["store_logits"] else None
-            if lazy_in:
-                L.call("dc_head_fwd_predict_bnin", self.dt, B, nv, 256, a.H, a.W, a.y.ptr, a.y.ld, L.dptr(a.scale), L.dptr(a.shift), int(a.relu),
-                       self.pptr(wl), lg, hptr, *tail)
-                return
-            L.call("dc_head_fwd_predict", self.dt, B, nv, 256, a.H, a.W, a.ptr, a.ld, self.pptr(wl), lg, hptr, *tail)
+            head_call(mode, (args["n_valid"],), args["store_logits"], post)
 
         self.fwd_train.append(head_fwd_train)
-        self.fwd_eval.append(head_fwd_score if self.forward_only else head_fwd)
+        self.fwd_eval.append(head_fwd_eval if self.forward_only else head_call)
 
         def head_bwd_make():
             assert a.take_grad_mode() == 0

@@ -113,6 +113,25 @@ def test_one_pass_kernels_of_the_entry_flow_keep_their_occupancy(tmp_path, src, 
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+def test_fused_head_kernels_keep_their_register_bands(tmp_path):
+    """head_fused_fwd_kernel <LOSS, BNIN, SCORE, PREDICT> (stem_head.hip) shares its epilogue with the loss kernels through pixel_score.h, so an
+    edit there reaches the training step's head launch <LOSS, BNIN>.  The eight instantiations use 104 - 124 registers on a stored input
+    (four waves per SIMD of the 512-register file: at most 128) and 132 - 144 with the BatchNorm applied while loading (three waves: at most
+    168), none with a spill; one register band up costs a wave per SIMD -- with correct results."""
+    asm = _device_asm("stem_head.hip", tmp_path)
+    kernels = _kernels(asm, "head_fused_fwd_kernel")
+    assert len(kernels) == 8, sorted(kernels)
+    bnin = [k for k in kernels if re.search(r"head_fused_fwd_kernelILb[01]ELb1E", k)]
+    assert len(bnin) == 4, sorted(kernels)
+    for kname, lines in kernels.items():
+        assert not any("scratch_" in x for x in lines), f"{kname}: scratch access"
+        m = re.search(r"\.amdhsa_kernel %s\b.*?\.amdhsa_next_free_vgpr (\d+)" % re.escape(kname), asm, re.S)
+        assert m, kname
+        band = 168 if kname in bnin else 128
+        assert int(m.group(1)) <= band, f"{kname}: {m.group(1)} registers, band {band}"
+
+
+@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_forward_depthwise_tile_kernel_keeps_three_workgroups_per_cu(tmp_path):
     """dwt_kernel's 8 x 8 pixel halo tile of 256 channels is 52 KiB of dynamic LDS: three workgroups on a CU's 160 KiB, with 4 KiB to spare.
     The in-kernel BatchNorm finalize needs 18 KiB of static LDS (2 KiB when this was found) and is therefore an instantiation of its own (FIN): in the

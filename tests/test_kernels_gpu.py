@@ -2058,7 +2058,7 @@ def test_head_fused_forward_matches_gemm_plus_combine(shape):
     assert_close(outs[0].cpu(), ref, torch.float32, f32=2e-4)
 
 
-@pytest.mark.parametrize("lab_dtype", [torch.int64, torch.uint8])
+@pytest.mark.parametrize("lab_dtype", [torch.int64, torch.uint8, torch.int32])
 @pytest.mark.parametrize("shape", [(2, 20, 70), (1, 9, 229), (1, 8, 32)], ids=["3x3tiles", "8tiles_wide", "one_exact_tile"])
 def test_head_forward_with_fused_loss(shape, lab_dtype):
     """dc_head_fwd_loss = dc_head_fwd followed by dc_wce_fused: logits, logit gradient, predictions and IoU counts bit for bit, the
