@@ -73,6 +73,7 @@ int dc_reset_options(void);
  *   BatchNorm apply: bn_apply_rows, bn_apply
  *   event catalogue (dc_mask_components, dc_component_stats): cc_tile, cc_merge, cc_flatten (tile labelling in LDS, the unions across
  *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
+ *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -617,6 +618,45 @@ int dc_mask_components(int B, int n_valid, int H, int W, const uint8_t* mask, in
                        void* workspace, void* stream);
 int dc_component_stats(int B, int n_valid, int H, int W, const uint8_t* mask, const int32_t* labels, const int32_t* wy,
                        const int32_t* cx, const int32_t* sx, int cap, int64_t* table, int32_t* ncomp, void* workspace, void* stream);
+
+/* Overlap of two catalogues of the same frames (nn.EventMatcher; predict.py --verify): which component of catalogue a shares pixels with
+ * which of catalogue b, and how much of each component the other mask covers.  a and b are any two catalogues of equal B, H, W -- a
+ * prediction and its labels, or two consecutive time steps; nothing below depends on which is which.  Integer arithmetic throughout.
+ *   mask_x    uint8 [B][H][W]   as above      labels_x  int32 [B][H][W]  as dc_mask_components leaves them
+ *   rank_x    int32 [B][H][W]   the rank map of dc_component_stats: the first B * H * W words of ITS workspace; at a root pixel the row
+ *                               index of that component, undefined elsewhere (only root pixels are read)
+ *   pairs     int64 [B][pair_cap][3], zeroed by the call for all B samples: one row (rank a, rank b, shared pixels) per distinct pair of
+ *             components with at least one pixel in common, whatever their classes.  Pairs with rank a >= cap_a or rank b >= cap_b are
+ *             not listed.  The order of the rows is unspecified (sort on the host); rows from the stored count on are zero.
+ *   npairs    int32 [B][2]: rows stored, overflow flag.  With at most pair_cap listable pairs all are stored and the flag is 0, whatever
+ *             the scheduling (a pair is given up only after the whole table was probed).  Otherwise the flag is 1, pair_cap rows are
+ *             stored (which ones is unspecified), and each of them is a distinct true pair with its full count.  Samples >= n_valid: not written.
+ *   cover_a   int64 [B][cap_a], cover_b int64 [B][cap_b], zeroed by the call for all B samples: per component of rank < cap the number
+ *             of its pixels at which the OTHER mask has the same class.  Accumulated by the pixel pass itself: exact also when the pair
+ *             table overflows, and it counts the other side's components of any rank.
+ *   workspace dc_component_overlap_workspace(B, pair_cap) bytes (a host function; 0 for arguments out of range), 256-byte aligned: the
+ *             open-addressing pair table, int64 [B][slots][2] with slots = the power of two >= max(16, 2 * pair_cap), a counter of
+ *             opened slots per sample and int32 [B][pair_cap] slot indices; the call clears what it needs cleared.
+ * 0 < n_valid <= B, cap_a, cap_b >= 1, 1 <= pair_cap <= 2^24.  Samples from n_valid on are not read.  Does not synchronise; reads what
+ * dc_mask_components and dc_component_stats left for BOTH catalogues on the same stream.
+ * dc_component_overlap_lds_slots: the slots of the per-workgroup pair table in LDS (tests build a tile with more distinct pairs than that
+ * from it, so that the runs which find no slot there and go to the global table directly stay exercised if the table grows). */
+int dc_component_overlap_lds_slots(int* slots);
+size_t dc_component_overlap_workspace(int B, int pair_cap);
+int dc_component_overlap(int B, int n_valid, int H, int W, const uint8_t* mask_a, const int32_t* labels_a, const int32_t* rank_a, int cap_a,
+                         const uint8_t* mask_b, const int32_t* labels_b, const int32_t* rank_b, int cap_b, int pair_cap, int64_t* pairs,
+                         int32_t* npairs, int64_t* cover_a, int64_t* cover_b, void* workspace, void* stream);
+/* Event scores from two tables and their coverage.  A component of class k in {1, 2} is SCORED when its pixels >= max(min_pixels, 1) and
+ * its rank < cap (it has a row); a scored component is MATCHED when cover >= 1 and cover * 1024 >= cover_q * pixels (1 <= cover_q <= 1024).
+ *   table_x, ncomp_x  as dc_component_stats leaves them; cover_x, npairs as dc_component_overlap leaves them
+ *   scores  int64 [B][2][4], per class 1, 2: hits (matched in b), misses (unmatched in b), false alarms (unmatched in a), matched
+ *           detections (matched in a).  Samples >= n_valid: not written.
+ *   acc     int64 [10], NOT zeroed by the call: += the 8 sums over the valid samples, acc[8] += n_valid, acc[9] += the number of valid
+ *           samples with more components than a cap or with the pair overflow flag set (non-zero: something was truncated).
+ * Does not synchronise; the result does not depend on scheduling. */
+int dc_event_scores(int B, int n_valid, int cap_a, const int64_t* table_a, const int32_t* ncomp_a, const int64_t* cover_a, int cap_b,
+                    const int64_t* table_b, const int32_t* ncomp_b, const int64_t* cover_b, const int32_t* npairs, long min_pixels,
+                    int cover_q, int64_t* scores, int64_t* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

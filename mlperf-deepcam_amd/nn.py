@@ -911,6 +911,13 @@ class EventCatalog:
         """int32 [n_valid, 3] of the last call (a view): components of any class, of class 1, of class 2"""
         return self._ncomp[:self._last_valid]
 
+    @property
+    def rank_map(self) -> torch.Tensor:
+        """int32 [n_valid, H, W] of the last call (a view of the workspace's first segment, valid until the next call): at every root pixel
+        (labels == r * W + c + 1) the row index of that component, undefined elsewhere.  What dc_component_overlap reads."""
+        n = self.B * self.H * self.W
+        return self._ws[:4 * n].view(torch.int32).view(self.B, self.H, self.W)[:self._last_valid]
+
     def rows(self):
         """(counts, rows) on the host: the counts first, then only the rows that are filled -- one list entry per valid sample, each an
         int64 numpy array [min(total, cap), 10]."""
@@ -943,6 +950,152 @@ class EventCatalog:
             out.append({"class": cls, "pixels": n, "area_fraction": area / whole if whole > 0 else 0.0, "lat": lat,
                         "lon": math.degrees(math.atan2(ssx, scx)), "row_min": rmin, "row_max": rmax, "crosses_seam": bool(seam), "root": root})
         return out
+
+
+class EventMatcher:
+    """Two event catalogues of the same frames matched on the device (dc_component_overlap + dc_event_scores, csrc/components.hip): which
+    event of mask a overlaps which event of mask b and by how many pixels, how much of every event the other mask covers with the same
+    class, and from that the detection scores per class -- hits and misses among b's events, false alarms and matched detections among
+    a's.  With a = a prediction and b = its labels these are the counts behind POD, FAR and CSI; the same pairs link the events of two
+    time steps.  An event is SCORED when it has at least max(min_pixels, 1) pixels and a row in its table; it is MATCHED when the other
+    mask covers at least min_cover of it with its class (integer: cover * 1024 >= round(min_cover * 1024) * pixels, and cover >= 1).
+    Coverage, not pairwise IoU, decides: a labelled river predicted as two fragments is still found.  The object owns the two catalogues
+    `.a` and `.b`, the pair table (int64 [B, pair_cap, 3]), the coverage counts (int64 [B, cap] per side), the per-sample scores (int64
+    [B, 2, 4]) and the running sums.  A call launches on the current stream and does not synchronise."""
+
+    SCORE_FIELDS = ("hits", "misses", "false_alarms", "matched")
+
+    def __init__(self, batch: int, height: int, width: int, connectivity: int = 8, wrap: bool = True, cap: int = 4096, pair_cap: int = 8192,
+                 min_pixels: int = 0, min_cover: float = 0.5, device=None):
+        if not 0.0 < float(min_cover) <= 1.0:
+            raise L.DeepcamHipError(f"EventMatcher: min_cover must lie in (0, 1], got {min_cover}")
+        if pair_cap < 1 or min_pixels < 0:
+            raise L.DeepcamHipError("EventMatcher: pair_cap must be positive and min_pixels not negative")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.a = EventCatalog(batch, height, width, connectivity=connectivity, wrap=wrap, cap=cap, device=dev)
+        self.b = EventCatalog(batch, height, width, connectivity=connectivity, wrap=wrap, cap=cap, device=dev)
+        self.B, self.H, self.W, self.cap, self.pair_cap, self.min_pixels = batch, height, width, cap, pair_cap, int(min_pixels)
+        self.cover_q = min(max(int(round(float(min_cover) * 1024)), 1), 1024)
+        self._pairs = torch.zeros((batch, pair_cap, 3), dtype=torch.int64, device=dev)
+        self._npairs = torch.zeros((batch, 2), dtype=torch.int32, device=dev)
+        self._cover_a = torch.zeros((batch, cap), dtype=torch.int64, device=dev)
+        self._cover_b = torch.zeros((batch, cap), dtype=torch.int64, device=dev)
+        self._scores = torch.zeros((batch, 2, 4), dtype=torch.int64, device=dev)
+        self.acc = torch.zeros(10, dtype=torch.int64, device=dev)
+        nbytes = L.load().dc_component_overlap_workspace(batch, pair_cap)
+        if nbytes == 0:
+            raise L.DeepcamHipError(f"EventMatcher: pair_cap {pair_cap} is out of range")
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._mask_b = None
+        self._last_valid = 0
+
+    def __call__(self, mask_a: torch.Tensor, mask_b: torch.Tensor, n_valid: Optional[int] = None) -> "EventMatcher":
+        """mask_a: device uint8 [B, H, W]; mask_b: the same, or a label tensor (int64, int32) whose classes become bytes here.  Samples from
+        n_valid on are padding: not read."""
+        if mask_b.dtype in (torch.int64, torch.int32):
+            mask_b = mask_b.to(torch.uint8)
+        nv = self.B if n_valid is None else int(n_valid)
+        a, b, st = self.a, self.b, L.stream_ptr()
+        a(mask_a, n_valid=nv)
+        b(mask_b, n_valid=nv)
+        self._mask_b = mask_b                      # the converted bytes stay alive while the launches below may still read them
+        L.call("dc_component_overlap", self.B, nv, self.H, self.W, L.dptr(mask_a), L.dptr(a._labels), L.dptr(a._ws), a.cap, L.dptr(mask_b),
+               L.dptr(b._labels), L.dptr(b._ws), b.cap, self.pair_cap, L.dptr(self._pairs), L.dptr(self._npairs), L.dptr(self._cover_a),
+               L.dptr(self._cover_b), L.dptr(self._ws), st)
+        L.call("dc_event_scores", self.B, nv, a.cap, L.dptr(a._table), L.dptr(a._ncomp), L.dptr(self._cover_a), b.cap, L.dptr(b._table),
+               L.dptr(b._ncomp), L.dptr(self._cover_b), L.dptr(self._npairs), self.min_pixels, self.cover_q, L.dptr(self._scores),
+               L.dptr(self.acc), st)
+        self._last_valid = nv
+        return self
+
+    @property
+    def pair_table(self) -> torch.Tensor:
+        """int64 [n_valid, pair_cap, 3] of the last call (a view): (rank a, rank b, pixels), device order, zero beyond the stored count"""
+        return self._pairs[:self._last_valid]
+
+    @property
+    def pair_counts(self) -> torch.Tensor:
+        """int32 [n_valid, 2] of the last call (a view): rows stored, overflow flag"""
+        return self._npairs[:self._last_valid]
+
+    @property
+    def score_table(self) -> torch.Tensor:
+        """int64 [n_valid, 2, 4] of the last call (a view): per class 1, 2 the SCORE_FIELDS"""
+        return self._scores[:self._last_valid]
+
+    @staticmethod
+    def sort_pairs(rows: np.ndarray) -> np.ndarray:
+        """the stored rows [n, 3] ordered by (rank a, rank b)"""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+        return np.ascontiguousarray(rows[np.lexsort((rows[:, 1], rows[:, 0]))])
+
+    def pairs(self):
+        """(rows, flags) on the host: per valid sample an int64 numpy array [n, 3] sorted by (rank a, rank b), and the overflow flags"""
+        nv = self._last_valid
+        if nv == 0:
+            return [], []
+        npairs = self._npairs[:nv].cpu().numpy()
+        fill = [int(n) for n in npairs[:, 0]]
+        host = self._pairs[:nv, :max(max(fill), 1)].cpu().numpy()
+        return [self.sort_pairs(host[s, :fill[s]]) for s in range(nv)], [int(f) for f in npairs[:, 1]]
+
+    def cover(self):
+        """(cover_a, cover_b) on the host: int64 numpy arrays [n_valid, cap], per component the pixels the other mask covers with its class"""
+        nv = self._last_valid
+        return self._cover_a[:nv].cpu().numpy(), self._cover_b[:nv].cpu().numpy()
+
+    def scores(self) -> np.ndarray:
+        """int64 numpy array [n_valid, 2, 4]: per sample and class the SCORE_FIELDS"""
+        return self._scores[:self._last_valid].cpu().numpy()
+
+    @staticmethod
+    def join(pairs, rows_a, rows_b, height: int, width: int, min_pixels: int = 0):
+        """Sorted pairs [n, 3] and the two catalogues' raw rows -> a list of dicts: `a`, `b` (EventCatalog.decode of the two rows),
+        `class_a`, `class_b`, `pixels` (shared), `iou` (shared / union).  Pairs with an event below min_pixels are left out."""
+        out = []
+        for ra, rb, n in np.asarray(pairs, dtype=np.int64).reshape(-1, 3).tolist():
+            if min(int(rows_a[ra][2]), int(rows_b[rb][2])) < max(min_pixels, 1):
+                continue
+            ea = EventCatalog.decode(rows_a[ra:ra + 1], height, width)[0]
+            eb = EventCatalog.decode(rows_b[rb:rb + 1], height, width)[0]
+            out.append({"a": ea, "b": eb, "class_a": ea["class"], "class_b": eb["class"], "pixels": n,
+                        "iou": n / (ea["pixels"] + eb["pixels"] - n)})
+        return out
+
+    def matches(self, min_pixels: Optional[int] = None):
+        """Per valid sample of the last call the joined pairs (join); min_pixels defaults to the matcher's."""
+        mp = self.min_pixels if min_pixels is None else int(min_pixels)
+        pairs, _ = self.pairs()
+        _, rows_a = self.a.rows()
+        _, rows_b = self.b.rows()
+        return [self.join(p, ra, rb, self.H, self.W, mp) for p, ra, rb in zip(pairs, rows_a, rows_b)]
+
+    def reset(self) -> None:
+        L.call("dc_memset_async", L.dptr(self.acc), 0, 80, L.stream_ptr())
+
+    @staticmethod
+    def rates(hits: int, misses: int, false_alarms: int, matched: int) -> dict:
+        """pod = hits / (hits + misses): the share of b's events found; far = false_alarms / (false_alarms + matched): the share of a's
+        events that answer to nothing; csi = hits / (hits + misses + false_alarms).  None where the denominator is zero."""
+        div = lambda n, d: n / d if d > 0 else None  # noqa: E731
+        return {"pod": div(hits, hits + misses), "far": div(false_alarms, false_alarms + matched),
+                "csi": div(hits, hits + misses + false_alarms)}
+
+    @staticmethod
+    def summarize(acc) -> dict:
+        """the ten running sums -> {"samples", "truncated", "class_1": {...}, "class_2": {...}}: per class the SCORE_FIELDS and rates();
+        truncated: some sample held more events than a table or more pairs than the pair table, so counts may be short"""
+        acc = [int(v) for v in acc]
+        out = {"samples": acc[8], "truncated": acc[9] != 0}
+        for k in (0, 1):
+            h, m, f, d = acc[4 * k:4 * k + 4]
+            out[f"class_{k + 1}"] = {"hits": h, "misses": m, "false_alarms": f, "matched": d, **EventMatcher.rates(h, m, f, d),
+                                     "truncated": acc[9] != 0}
+        return out
+
+    def result(self) -> dict:
+        """summarize() of the sums since reset(): one device-to-host read"""
+        return self.summarize(self.acc.cpu().tolist())
 
 
 class Predictor:
@@ -988,6 +1141,11 @@ class Predictor:
         if self.catalog is not None:
             self.catalog(self._mask, n_valid=nv)
         return self._mask[:nv]
+
+    @property
+    def mask_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the whole buffer the masks are written to, padding samples included (what EventCatalog / EventMatcher take)"""
+        return self._mask
 
     @property
     def confidence(self) -> Optional[torch.Tensor]:

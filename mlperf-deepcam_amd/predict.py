@@ -12,7 +12,11 @@ of its input file and holds ``prediction`` (uint8 [H, W]: 0 background, 1 tropic
 confidence per file.  With --events every output file also carries ``events`` (int64 [n, 10], the raw rows of nn.EventCatalog: root,
 class, pixels, area, sum of rows, sum of cx, sum of sx, first row, last row, seam flag -- connected components of the mask, found on the
 device; the table, not a label map, is what crosses to the host), and ``summary.json`` the number of class-1 and class-2 events per file
-and in total and the number of files whose table overflowed.  Single process, single device."""
+and in total and the number of files whose table overflowed.  With --verify (which implies --events) the files must be labelled: the
+masks and the labels go through nn.EventMatcher (a = prediction, b = labels), every output file also carries ``truth_events`` (int64
+[m, 10], the label side's rows), ``matches`` (int64 [p, 3]: row of ``events``, row of ``truth_events``, shared pixels; sorted) and
+``event_scores`` (int64 [2, 4], per class: hits, misses, false alarms, matched detections), and ``summary.json`` and the final line
+gain ``event_verification`` (hits, misses, false alarms, POD, FAR and CSI per class over all files).  Single process, single device."""
 from __future__ import annotations
 
 import argparse
@@ -27,6 +31,17 @@ import torch
 
 from . import data as ddata
 from . import nn as dnn
+
+
+class _Verify(argparse.Action):
+    """--verify: implies --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.verify = True
+        namespace.events = True
 
 
 def build_parser():
@@ -44,14 +59,19 @@ def build_parser():
     AP.add_argument("--events", action="store_true", help="also catalogue the connected components of every mask (dataset 'events')")
     AP.add_argument("--min_event_pixels", type=int, default=0, help="with --events: leave out components of fewer pixels")
     AP.add_argument("--event_connectivity", type=int, default=8, choices=[4, 8], help="with --events: pixel connectivity")
+    AP.add_argument("--verify", action=_Verify, help="match the events of every mask to the events of the file's labels (implies --events; "
+                    "the files need climate/labels_0): datasets 'truth_events', 'matches', 'event_scores'; 'event_verification' in the summary")
+    AP.add_argument("--min_event_cover", type=float, default=0.5, help="with --verify: an event is found when the other mask covers at "
+                    "least this share of it with its class, in (0, 1]")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
     return AP
 
 
-def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None) -> None:
-    """`prediction` (and `confidence`, `events`) as datasets of one HDF5 file, through the backend data.CamDataset reads with."""
+def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None, extra=None) -> None:
+    """`prediction` (and `confidence`, `events`, the datasets of `extra`) as datasets of one HDF5 file, through the backend
+    data.CamDataset reads with."""
     backend, h5 = ddata._h5_backend()
     if backend == "h5py":
         with h5.File(path, "w") as f:
@@ -60,6 +80,8 @@ def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None) 
                 f.create_dataset("confidence", data=confidence)
             if events is not None:
                 f.create_dataset("events", data=events)
+            for name, array in (extra or {}).items():
+                f.create_dataset(name, data=array)
         return
     with h5.File(path, "w") as f:
         f.write("prediction", prediction)
@@ -67,10 +89,39 @@ def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None) 
             f.write("confidence", confidence)
         if events is not None:
             f.write("events", events)
+        for name, array in (extra or {}).items():
+            f.write(name, array)
+
+
+def require_labels(data_dir: str) -> None:
+    """--verify: every input file must hold climate/labels_0; the first one that does not is named."""
+    backend, h5 = ddata._h5_backend()
+    for name in sorted(x for x in os.listdir(data_dir) if x.endswith(".h5")):
+        path = os.path.join(data_dir, name)
+        with (h5.File(path, "r") if backend == "h5py" else h5.File(path)) as f:
+            if "climate/labels_0" not in f:
+                raise ValueError(f"--verify needs labelled files: {path} has no climate/labels_0")
+
+
+def filter_matches(rows_a: np.ndarray, rows_b: np.ndarray, pairs: np.ndarray, min_pixels: int):
+    """The rows of both tables with at least min_pixels pixels, and the pairs between them with their ranks renumbered to the rows that
+    are left (so `matches` indexes `events` and `truth_events` as they are stored)."""
+    keep_a, keep_b = rows_a[:, 2] >= min_pixels, rows_b[:, 2] >= min_pixels
+    new_a, new_b = np.cumsum(keep_a) - 1, np.cumsum(keep_b) - 1
+    pairs = pairs.reshape(-1, 3)
+    pairs = pairs[keep_a[pairs[:, 0]] & keep_b[pairs[:, 1]]]
+    out = np.stack([new_a[pairs[:, 0]], new_b[pairs[:, 1]], pairs[:, 2]], axis=1).astype(np.int64).reshape(-1, 3)
+    return np.ascontiguousarray(rows_a[keep_a]), np.ascontiguousarray(rows_b[keep_b]), np.ascontiguousarray(out)
 
 
 class _HostSlot:
-    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0):
+    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0):
+        # --verify: the label side's table and counts, the pair table with its counts, the scores
+        self.truth = torch.empty((B, event_cap, len(dnn.EVENT_FIELDS)), dtype=torch.int64).pin_memory() if pair_cap else None
+        self.ntruth = torch.empty((B, 3), dtype=torch.int32).pin_memory() if pair_cap else None
+        self.pairs = torch.empty((B, pair_cap, 3), dtype=torch.int64).pin_memory() if pair_cap else None
+        self.npairs = torch.empty((B, 2), dtype=torch.int32).pin_memory() if pair_cap else None
+        self.scores = torch.empty((B, 2, 4), dtype=torch.int64).pin_memory() if pair_cap else None
         # --events: the whole table of a batch (cap rows of 80 bytes per sample) and the counts that say how many rows are filled
         self.events = torch.empty((B, event_cap, len(dnn.EVENT_FIELDS)), dtype=torch.int64).pin_memory() if event_cap else None
         self.ncomp = torch.empty((B, 3), dtype=torch.int32).pin_memory() if event_cap else None
@@ -92,17 +143,26 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                 for j, name in enumerate(names):
                     conf = slot.conf[j].numpy() if slot.conf is not None else None
                     base = os.path.basename(name)
-                    rows = None
+                    rows = extra = None
                     if slot.events is not None:
                         total = int(slot.ncomp[j, 0])
                         rows = slot.events[j, :min(total, slot.events.shape[1])].numpy()
-                        rows = np.ascontiguousarray(rows[rows[:, 2] >= min_event_pixels])
-                    write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows)
+                        if slot.pairs is not None:
+                            truth = slot.truth[j, :min(int(slot.ntruth[j, 0]), slot.truth.shape[1])].numpy()
+                            pairs = dnn.EventMatcher.sort_pairs(slot.pairs[j, :int(slot.npairs[j, 0])].numpy())
+                            rows, truth, pairs = filter_matches(rows, truth, pairs, min_event_pixels)
+                            extra = {"truth_events": truth, "matches": pairs, "event_scores": slot.scores[j].numpy()}
+                        else:
+                            rows = np.ascontiguousarray(rows[rows[:, 2] >= min_event_pixels])
+                    write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     rec = {"file": base, "class_counts": [int(v) for v in slot.counts[j].tolist()],
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if rows is not None:
                         rec["events"] = [int((rows[:, 1] == 1).sum()), int((rows[:, 1] == 2).sum())]
                         rec["events_overflowed"] = total > slot.events.shape[1]
+                    if extra is not None:
+                        rec["event_scores"] = extra["event_scores"].tolist()
+                        rec["matches_overflowed"] = bool(slot.npairs[j, 1])
                     records.append(rec)
         except BaseException as e:      # surfaces in the main thread; the slots keep circulating so that it cannot block
             errors.append(e)
@@ -122,8 +182,11 @@ def main(pargs) -> dict:
         (torch.float32 if pargs.amp_opt_level == "O0" else torch.bfloat16)
     os.makedirs(pargs.output_dir, exist_ok=True)
 
+    verify = bool(getattr(pargs, "verify", False))
+    if verify:
+        require_labels(pargs.data_dir)
     dataset = ddata.CamDataset(pargs.data_dir, pargs.stats_file, pargs.channels, allow_uneven_distribution=True, shuffle=False,
-                               preprocess=True, labels=False)
+                               preprocess=True, labels=verify)
     assert tuple(dataset.data_shape[:2]) == (H, W), "pass --height/--width matching the files"
 
     net = dnn.DeepLabv3_plus(n_input=len(pargs.channels), n_classes=3, os=16, pretrained=False, rank=0, dtype=dtype, _print=False)
@@ -133,13 +196,19 @@ def main(pargs) -> dict:
     net.eval()
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     loader = ddata.InputPipeline(dataset, B, dtype=dtype, device=device, layout=layout, drop_last=False, workers=pargs.max_inter_threads)
-    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=pargs.events, event_connectivity=pargs.event_connectivity)
-    event_cap = predictor.catalog.cap if pargs.events else 0
+    events = bool(pargs.events) or verify
+    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify,
+                              event_connectivity=pargs.event_connectivity)
+    # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
+    matcher = dnn.EventMatcher(B, H, W, connectivity=pargs.event_connectivity, min_pixels=pargs.min_event_pixels,
+                               min_cover=pargs.min_event_cover, device=device) if verify else None
+    catalog = matcher.a if verify else predictor.catalog
+    event_cap = catalog.cap if events else 0
 
     free_q: "queue.Queue" = queue.Queue()
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
-        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap))
+        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels),
@@ -147,20 +216,28 @@ def main(pargs) -> dict:
     writer.start()
     t0 = time.perf_counter()
     try:
-        for x, _, names in loader:
+        for x, y, names in loader:
             nv = len(names)
             slot = free_q.get()                    # blocks only while the writer still holds BOTH host buffers
             if errors:
                 free_q.put(slot)
                 break
             mask = predictor(x, n_valid=nv)
+            if verify:
+                matcher(predictor.mask_buffer, y, n_valid=nv)
             slot.mask[:nv].copy_(mask, non_blocking=True)
             if slot.conf is not None:
                 slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
             slot.counts[:nv].copy_(predictor.class_counts, non_blocking=True)
             if slot.events is not None:
-                slot.events[:nv].copy_(predictor.catalog.table, non_blocking=True)
-                slot.ncomp[:nv].copy_(predictor.catalog.counts(), non_blocking=True)
+                slot.events[:nv].copy_(catalog.table, non_blocking=True)
+                slot.ncomp[:nv].copy_(catalog.counts(), non_blocking=True)
+            if slot.pairs is not None:
+                slot.truth[:nv].copy_(matcher.b.table, non_blocking=True)
+                slot.ntruth[:nv].copy_(matcher.b.counts(), non_blocking=True)
+                slot.pairs[:nv].copy_(matcher.pair_table, non_blocking=True)
+                slot.npairs[:nv].copy_(matcher.pair_counts, non_blocking=True)
+                slot.scores[:nv].copy_(matcher.score_table, non_blocking=True)
             slot.done.record(torch.cuda.current_stream())
             work_q.put((slot, names))
     finally:
@@ -169,20 +246,25 @@ def main(pargs) -> dict:
         predictor.close()
     if errors:
         raise errors[0]
+    verification = matcher.result() if verify else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
     totals = [sum(r["class_counts"][j] for r in records) for j in range(3)]
     summary = {"files": records, "class_counts": totals}
-    if pargs.events:
+    if events:
         summary["events"] = [sum(r["events"][j] for r in records) for j in range(2)]
         summary["events_overflowed_files"] = sum(1 for r in records if r["events_overflowed"])
+    if verify:
+        summary["event_verification"] = verification
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     line = {"samples": len(records), "class_counts": totals, "seconds": round(elapsed, 4),
             "samples_per_second": round(len(records) / elapsed, 3) if elapsed > 0 else None}
-    if pargs.events:
+    if events:
         line["events"] = summary["events"]
+    if verify:
+        line["event_verification"] = verification
     if pargs.confidence and records:
         line["mean_confidence"] = float(np.mean([r["mean_confidence"] for r in records]))
     print(json.dumps(line))
