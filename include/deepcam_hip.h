@@ -74,6 +74,7 @@ int dc_reset_options(void);
  *   event catalogue (dc_mask_components, dc_component_stats): cc_tile, cc_merge, cc_flatten (tile labelling in LDS, the unions across
  *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
+ *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -657,6 +658,37 @@ int dc_component_overlap(int B, int n_valid, int H, int W, const uint8_t* mask_a
 int dc_event_scores(int B, int n_valid, int cap_a, const int64_t* table_a, const int32_t* ncomp_a, const int64_t* cover_a, int cap_b,
                     const int64_t* table_b, const int32_t* ncomp_b, const int64_t* cover_b, const int32_t* npairs, long min_pixels,
                     int cover_q, int64_t* scores, int64_t* acc, void* stream);
+
+/* Per-event statistics of the input fields (nn.EventFields; predict.py --event_fields): for every event of a catalogue and every channel
+ * of the raw fields the minimum and its pixel, the maximum and its pixel, a plain sum and an area-weighted sum -- a cyclone's pressure
+ * minimum and where it sits, its maximum wind, a river's mean water vapour.  One pass over the label map; field values are loaded at
+ * foreground pixels only.  Every result is exact and independent of the order in which pixels arrive (minimum, maximum, integer sums).
+ *   labels      int32 [B][H][W]       as dc_mask_components leaves them
+ *   rank_map    int32 [B][H][W]       the rank map of dc_component_stats (the first B * H * W words of its workspace), cap its row capacity
+ *   fields      fp32 [B][H][W][ldc]   channel-last, physical units; channels 0 .. C-1 are used, 1 <= C <= 32, ldc >= C.  16-byte loads
+ *                                     when ldc % 4 == 0 and the base is 16-byte aligned, scalar loads otherwise
+ *   scale_bits  int32 [C], device     the sums' binary scale per channel (nn.event_field_bits: 39 - exponent of the recorded range)
+ *   wy          int32 [H]             the catalogue's cos(lat) * 2^20 table
+ *   ftable      int64 [B][cap][C][6]  16-byte aligned; row (k, ch) belongs to the event of rank k (row k of dc_component_stats):
+ *                                     min, max, sum, wsum, nonfinite, saturated
+ * For every foreground pixel p = r * W + c (labels[p] > 0) with k = rank_map[labels[p] - 1] in [0, cap) and every channel ch, v =
+ * fields[b][r][c][ch]:
+ *   v is NaN or +-Inf:  nonfinite += 1, nothing else.  Otherwise, with key(v) = bits ^ 0xFFFFFFFF if the sign bit is set, else
+ *   bits | 0x80000000 (an order-preserving 32-bit key: -0.0 < +0.0, denormals in their places):
+ *   min  = the unsigned 64-bit minimum of (key(v) << 32) | p                   (empty: all ones, -1 as int64)
+ *   max  = the unsigned 64-bit maximum of (key(v) << 32) | (0xFFFFFFFF - p)    (empty: 0)
+ *          both name the SMALLEST pixel index among equal values
+ *   q = rint(ldexp((double)v, scale_bits[ch])), ties to even.  |q| > 2^40: saturated += 1 and v takes no part in either sum (it does in
+ *   min and max).  Otherwise  sum += (int64)q  and  wsum += (int64)rint(ldexp((double)v, scale_bits[ch]) * ((double)wy[r] * 2^-20))
+ *   (two exact factors, one rounded fp64 product, rint).  A sum of n values is within n * 2^-(scale_bits + 1) of the real one.
+ * H * W <= 2^22 (the pixel shares a word with the key, and 2^40 * H * W stays inside int64).  Rows of valid samples without an event
+ * (from min(ncomp, cap) on) hold the empty row (-1, 0, 0, 0, 0, 0); samples from n_valid on are neither read nor written.  Does not
+ * synchronise; reads what dc_mask_components and dc_component_stats left on the same stream.
+ * dc_component_fields_lds_slots: the roots the per-workgroup table in LDS holds (tests build a tile with more roots than that, so that
+ * the runs which go to the global rows directly stay exercised if the table grows). */
+int dc_component_fields_lds_slots(int* slots);
+int dc_component_fields(int B, int n_valid, int H, int W, const int32_t* labels, const int32_t* rank_map, int cap, const float* fields,
+                        int C, int ldc, const int32_t* scale_bits, const int32_t* wy, int64_t* ftable, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -115,6 +115,7 @@ class CamDataset:
                 self._label_dtype = f.dtype("climate/labels_0").newbyteorder("=") if self.labels else None
             with self._h5.File(statsfile) as f:
                 minval, maxval = f.read("climate/minval"), f.read("climate/maxval")
+        self.minval, self.maxval = np.asarray(minval, np.float32), np.asarray(maxval, np.float32)   # every file channel, as recorded
         shift = np.asarray(minval)[self.channels]                                   # :96-98
         scale = 1.0 / (np.asarray(maxval)[self.channels] - shift)
         if not preprocess:                                                          # :100-102
@@ -257,6 +258,13 @@ class InputPipeline:
 
     def __len__(self):
         return self.nbatches
+
+    @property
+    def raw(self) -> Optional[torch.Tensor]:
+        """fp32 [B, H, W, Cfile] on the device: the fields of the batch handed out last exactly as the files store them (physical units,
+        every file channel, before channel selection and normalisation); None before the first batch.  Valid until the next batch is
+        requested, and ordered on the current stream by the same event as the batch itself."""
+        return self._prev.data_dev if self._prev is not None else None
 
     def _reader(self, free_q: "queue.Queue", full_q: "queue.Queue", stop: "threading.Event"):
         from concurrent.futures import ThreadPoolExecutor

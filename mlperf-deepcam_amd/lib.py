@@ -165,6 +165,8 @@ _SIGS = {
     "dc_component_overlap_workspace": (SZ, [I, I]),
     "dc_component_overlap": (I, [I, I, I, I, P, P, P, I, P, P, P, I, I, P, P, P, P, P, P]),
     "dc_event_scores": (I, [I, I, I, P, P, P, I, P, P, P, P, L, I, P, P, P]),
+    "dc_component_fields_lds_slots": (I, [C.POINTER(I)]),
+    "dc_component_fields": (I, [I, I, I, I, P, P, I, P, I, I, P, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

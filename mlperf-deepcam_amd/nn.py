@@ -1098,6 +1098,151 @@ class EventMatcher:
         return self.summarize(self.acc.cpu().tolist())
 
 
+EVENT_FIELD_STATS = ("min", "max", "sum", "wsum", "nonfinite", "saturated")
+
+
+def event_field_bits(minval, maxval) -> np.ndarray:
+    """int32 [C]: the binary scale of dc_component_fields' sums per channel, from the dataset's recorded range (stats.h5: climate/minval,
+    climate/maxval).  With m = max(|minval|, |maxval|): 39 - frexp(m)[1], and 0 where m is zero or not finite.  A value v inside the range
+    is summed as rint(v * 2^bits) with |v * 2^bits| < 2^39; values up to twice outside the range still fit below the kernel's limit of
+    2^40, larger ones are counted as saturated.  The quantum of the sums is 2^-bits: a sum of n values is within n * 2^-(bits + 1) of the
+    real one (m = 1e5: bits 22, 1.2e-7 per value)."""
+    lo = np.atleast_1d(np.asarray(minval, np.float64))
+    hi = np.atleast_1d(np.asarray(maxval, np.float64))
+    m = np.maximum(np.abs(lo), np.abs(hi))
+    ok = np.isfinite(m) & (m > 0)
+    return np.where(ok, 39 - np.frexp(np.where(ok, m, 1.0))[1], 0).astype(np.int32)
+
+
+def event_field_key(values) -> np.ndarray:
+    """uint32 keys of float32 values whose unsigned order is the values' order (-0.0 below +0.0, denormals in their places): the bits with
+    the sign bit set for non-negative values, all bits flipped for negative ones.  The upper half of the min / max words."""
+    u = np.asarray(values, np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), u ^ np.uint32(0xFFFFFFFF), u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def event_field_value(keys) -> np.ndarray:
+    """float32 values of event_field_key's keys"""
+    k = np.asarray(keys, np.uint32)
+    return np.where(k & np.uint32(0x80000000), k ^ np.uint32(0x80000000), k ^ np.uint32(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+
+
+class EventFields:
+    """Per-event statistics of the raw input fields on the device (dc_component_fields, csrc/components.hip): for every event of a
+    catalogue and every channel the minimum and where it sits (a cyclone's pressure minimum is its centre), the maximum and where it sits
+    (its strongest wind), the sum and the area-weighted sum (a river's mean water vapour).  The object owns the device scale_bits (int32
+    [C], see event_field_bits) and the table (int64 [B, cap, C, 6], EVENT_FIELD_STATS; row k belongs to row k of the catalogue's table).
+    Everything is exact and independent of the order in which pixels arrive.  A call must follow the catalogue's call on the same stream
+    (it reads the catalogue's labels and rank map); it launches and does not synchronise."""
+
+    def __init__(self, catalog: EventCatalog, channels: int, bits: Sequence[int], ldc: Optional[int] = None):
+        ldc = int(channels if ldc is None else ldc)
+        bits = [int(v) for v in np.asarray(bits).reshape(-1)]
+        if not 1 <= int(channels) <= 32 or ldc < channels:
+            raise L.DeepcamHipError(f"EventFields: channels must lie in [1, 32] and ldc must be at least channels, got {channels}, {ldc}")
+        if len(bits) != channels:
+            raise L.DeepcamHipError(f"EventFields: {len(bits)} scale bits for {channels} channels")
+        if catalog.H * catalog.W > 1 << 22:
+            raise L.DeepcamHipError("EventFields: H * W must be at most 2^22")
+        self.catalog, self.C, self.ldc, self.bits = catalog, int(channels), ldc, bits
+        dev = catalog._labels.device
+        self._bits = torch.tensor(bits, dtype=torch.int32, device=dev)
+        self._ftable = torch.zeros((catalog.B, catalog.cap, self.C, len(EVENT_FIELD_STATS)), dtype=torch.int64, device=dev)
+        self._last_valid = 0
+
+    def __call__(self, fields: torch.Tensor, n_valid: Optional[int] = None) -> "EventFields":
+        """fields: contiguous device fp32 [B, H, W, ldc], physical units (InputPipeline.raw).  n_valid defaults to the catalogue's."""
+        cat = self.catalog
+        want = (cat.B, cat.H, cat.W, self.ldc)
+        if fields.dtype != torch.float32 or tuple(fields.shape) != want or not fields.is_cuda or not fields.is_contiguous() \
+                or fields.device != cat._labels.device:
+            raise L.DeepcamHipError(f"EventFields: fields must be a contiguous fp32 tensor {list(want)} on {cat._labels.device}, got "
+                                    f"{fields.dtype} {tuple(fields.shape)} on {fields.device}")
+        nv = cat._last_valid if n_valid is None else int(n_valid)
+        L.call("dc_component_fields", cat.B, nv, cat.H, cat.W, L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, L.dptr(fields), self.C, self.ldc,
+               L.dptr(self._bits), L.dptr(cat._wy), L.dptr(self._ftable), L.stream_ptr())
+        self._last_valid = nv
+        return self
+
+    @property
+    def table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, C, 6] of the last call (a view): rows from min(count, cap) on are empty (-1, 0, 0, 0, 0, 0)"""
+        return self._ftable[:self._last_valid]
+
+    def rows(self):
+        """On the host, per valid sample only the filled rows: int64 numpy arrays [min(total, cap), C, 6] (the catalogue's counts decide)"""
+        nv = self._last_valid
+        if nv == 0:
+            return []
+        fill = [min(int(t), self.catalog.cap) for t in self.catalog._ncomp[:nv, 0].cpu().tolist()]
+        host = self._ftable[:nv, :max(max(fill), 1)].cpu().numpy()
+        return [host[b, :fill[b]].copy() for b in range(nv)]
+
+    def stats(self, min_pixels: int = 0):
+        """Per valid sample a list aligned with catalog.events(min_pixels): per event a list over channels of dicts (decode)."""
+        _, rows = self.catalog.rows()
+        out = []
+        for fr, r in zip(self.rows(), rows):
+            keep = r[:, 2] >= max(min_pixels, 1)
+            out.append(self.decode(fr[keep], r[keep], self.catalog.H, self.catalog.W, self.bits))
+        return out
+
+    FIELD_VALUES = ("min", "min_lat", "min_lon", "max", "max_lat", "max_lon", "mean", "area_mean")
+
+    @staticmethod
+    def values(frows, rows, height: int, width: int, bits) -> np.ndarray:
+        """float64 [n, C, 8] (FIELD_VALUES): decode's numbers for whole arrays at once, NaN where decode gives None -- the same
+        operations on the same operands, so the two agree to the bit (what predict.py stores as event_field_values)."""
+        bits = np.asarray(bits, np.int64).reshape(-1)
+        fr = np.asarray(frows, np.int64).reshape(-1, len(bits), len(EVENT_FIELD_STATS))
+        rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
+        lat, lon = np.linspace(-90.0, 90.0, height), np.linspace(-180.0, 180.0, width)
+        out = np.full(fr.shape[:2] + (8,), np.nan, np.float64)
+        lo, hi = fr[..., 0].view(np.uint64), fr[..., 1].view(np.uint64)
+        for k, (word, some) in enumerate(((lo, fr[..., 0] != -1), (hi, fr[..., 1] != 0))):
+            p = (word & np.uint64(0xFFFFFFFF)).astype(np.int64)
+            p = np.where(some, p if k == 0 else 0xFFFFFFFF - p, 0)
+            val = event_field_value((word >> np.uint64(32)).astype(np.uint32)).astype(np.float64)
+            out[..., 3 * k] = np.where(some, val, np.nan)
+            out[..., 3 * k + 1] = np.where(some, lat[np.minimum(p // width, height - 1)], np.nan)
+            out[..., 3 * k + 2] = np.where(some, lon[p % width], np.nan)
+        n = rows[:, 2, None] - fr[..., 4] - fr[..., 5]
+        area = rows[:, 3, None].astype(np.float64) * 2.0 ** -20
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[..., 6] = np.where(n > 0, np.ldexp(fr[..., 2].astype(np.float64), -bits) / n, np.nan)
+            out[..., 7] = np.where(area > 0, fr[..., 3].astype(np.float64) / (np.ldexp(1.0, bits) * area), np.nan)
+        return out
+
+    @staticmethod
+    def decode(frows, rows, height: int, width: int, bits):
+        """Raw rows [n, C, 6] (EVENT_FIELD_STATS) and the events' own rows [n, 10] (EVENT_FIELDS) -> per event a list over channels of
+        dicts: min, min_row, min_col, min_lat, min_lon, max, max_row, max_col, max_lat, max_lon (lat / lon through the linspaces of
+        event_weight_tables), mean = sum * 2^-bits / (pixels - nonfinite - saturated), area_mean = wsum / (2^bits * area * 2^-20),
+        nonfinite, saturated.  None where the row is empty (no finite value) or a divisor is zero."""
+        frows = np.asarray(frows, np.int64)
+        lat, lon = np.linspace(-90.0, 90.0, height), np.linspace(-180.0, 180.0, width)
+        out = []
+        for fr, r in zip(frows.tolist(), np.asarray(rows, np.int64).tolist()):
+            pixels, area = r[2], r[3]
+            per = []
+            for ch, (lo, hi, s, ws, nonfinite, saturated) in enumerate(fr):
+                d = {"nonfinite": nonfinite, "saturated": saturated}
+                for name, word, empty in (("min", lo, -1), ("max", hi, 0)):
+                    if word == empty:
+                        d.update({name: None, name + "_row": None, name + "_col": None, name + "_lat": None, name + "_lon": None})
+                        continue
+                    word &= 0xFFFFFFFFFFFFFFFF
+                    p = word & 0xFFFFFFFF if name == "min" else 0xFFFFFFFF - (word & 0xFFFFFFFF)
+                    d.update({name: float(event_field_value(np.uint32(word >> 32))), name + "_row": p // width, name + "_col": p % width,
+                              name + "_lat": float(lat[p // width]), name + "_lon": float(lon[p % width])})
+                n = pixels - nonfinite - saturated
+                d["mean"] = math.ldexp(float(s), -int(bits[ch])) / n if n > 0 else None
+                d["area_mean"] = float(ws) / (math.ldexp(1.0, int(bits[ch])) * (area * 2.0 ** -20)) if area > 0 else None
+                per.append(d)
+            out.append(per)
+        return out
+
+
 class Predictor:
     """Masks for unlabelled data: the eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running
     statistics through the shared arena, pooled activations) whose classifier leaves, per pixel, the first-max class as one byte

@@ -16,7 +16,13 @@ and in total and the number of files whose table overflowed.  With --verify (whi
 masks and the labels go through nn.EventMatcher (a = prediction, b = labels), every output file also carries ``truth_events`` (int64
 [m, 10], the label side's rows), ``matches`` (int64 [p, 3]: row of ``events``, row of ``truth_events``, shared pixels; sorted) and
 ``event_scores`` (int64 [2, 4], per class: hits, misses, false alarms, matched detections), and ``summary.json`` and the final line
-gain ``event_verification`` (hits, misses, false alarms, POD, FAR and CSI per class over all files).  Single process, single device."""
+gain ``event_verification`` (hits, misses, false alarms, POD, FAR and CSI per class over all files).  With --event_fields (which
+implies --events) nn.EventFields reduces the raw fields of every batch per event on the device, behind the catalogue: every output file
+also carries ``event_fields`` (int64 [n, C, 6] over all C file channels: min, max, sum, wsum, nonfinite, saturated -- the rows of
+``events``, in their order), ``event_field_values`` (float64 [n, C, 8]: min, its lat and lon, max, its lat and lon, mean, area-weighted
+mean; NaN where there is none) and ``event_field_bits`` (int32 [C], the sums' binary scale from the stats file's range), and
+``summary.json`` gains ``event_fields`` (channels, scale_bits, and the non-finite and saturated values met over all stored events).
+Single process, single device."""
 from __future__ import annotations
 
 import argparse
@@ -44,6 +50,17 @@ class _Verify(argparse.Action):
         namespace.events = True
 
 
+class _EventFields(argparse.Action):
+    """--event_fields: implies --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.event_fields = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -63,6 +80,8 @@ def build_parser():
                     "the files need climate/labels_0): datasets 'truth_events', 'matches', 'event_scores'; 'event_verification' in the summary")
     AP.add_argument("--min_event_cover", type=float, default=0.5, help="with --verify: an event is found when the other mask covers at "
                     "least this share of it with its class, in (0, 1]")
+    AP.add_argument("--event_fields", action=_EventFields, help="per event and file channel the extremes with their positions and the means "
+                    "of the raw fields (implies --events): datasets 'event_fields', 'event_field_values', 'event_field_bits'")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -115,7 +134,10 @@ def filter_matches(rows_a: np.ndarray, rows_b: np.ndarray, pairs: np.ndarray, mi
 
 
 class _HostSlot:
-    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0):
+    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0):
+        # --event_fields: the rows of nn.EventFields (cap * C rows of 48 bytes per sample)
+        self.fields = torch.empty((B, event_cap, field_channels, len(dnn.EVENT_FIELD_STATS)), dtype=torch.int64).pin_memory() \
+            if field_channels else None
         # --verify: the label side's table and counts, the pair table with its counts, the scores
         self.truth = torch.empty((B, event_cap, len(dnn.EVENT_FIELDS)), dtype=torch.int64).pin_memory() if pair_cap else None
         self.ntruth = torch.empty((B, 3), dtype=torch.int32).pin_memory() if pair_cap else None
@@ -131,7 +153,8 @@ class _HostSlot:
         self.done = torch.cuda.Event()
 
 
-def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records: list, errors: list, min_event_pixels: int = 0) -> None:
+def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records: list, errors: list, min_event_pixels: int = 0,
+            field_bits=None) -> None:
     while True:
         item = work_q.get()
         if item is None:
@@ -147,6 +170,9 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if slot.events is not None:
                         total = int(slot.ncomp[j, 0])
                         rows = slot.events[j, :min(total, slot.events.shape[1])].numpy()
+                        frows = None
+                        if slot.fields is not None:          # the filter of `events`, whichever branch below applies it
+                            frows = np.ascontiguousarray(slot.fields[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.pairs is not None:
                             truth = slot.truth[j, :min(int(slot.ntruth[j, 0]), slot.truth.shape[1])].numpy()
                             pairs = dnn.EventMatcher.sort_pairs(slot.pairs[j, :int(slot.npairs[j, 0])].numpy())
@@ -154,13 +180,19 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             extra = {"truth_events": truth, "matches": pairs, "event_scores": slot.scores[j].numpy()}
                         else:
                             rows = np.ascontiguousarray(rows[rows[:, 2] >= min_event_pixels])
+                        if frows is not None:
+                            H, W = slot.mask.shape[1:]
+                            extra = dict(extra or {}, event_fields=frows, event_field_values=dnn.EventFields.values(frows, rows, H, W, field_bits),
+                                         event_field_bits=np.asarray(field_bits, np.int32))
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     rec = {"file": base, "class_counts": [int(v) for v in slot.counts[j].tolist()],
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if rows is not None:
                         rec["events"] = [int((rows[:, 1] == 1).sum()), int((rows[:, 1] == 2).sum())]
                         rec["events_overflowed"] = total > slot.events.shape[1]
-                    if extra is not None:
+                    if extra is not None and "event_fields" in extra:
+                        rec["event_field_counts"] = [int(extra["event_fields"][..., 4].sum()), int(extra["event_fields"][..., 5].sum())]
+                    if extra is not None and "event_scores" in extra:
                         rec["event_scores"] = extra["event_scores"].tolist()
                         rec["matches_overflowed"] = bool(slot.npairs[j, 1])
                     records.append(rec)
@@ -204,14 +236,19 @@ def main(pargs) -> dict:
                                min_cover=pargs.min_event_cover, device=device) if verify else None
     catalog = matcher.a if verify else predictor.catalog
     event_cap = catalog.cap if events else 0
+    # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
+    efields = field_bits = None
+    if getattr(pargs, "event_fields", False):
+        field_bits = dnn.event_field_bits(dataset.minval, dataset.maxval)
+        efields = dnn.EventFields(catalog, loader.cfile, field_bits)
 
     free_q: "queue.Queue" = queue.Queue()
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
-        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0))
+        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0))
     records: list = []
     errors: list = []
-    writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels),
+    writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
                               daemon=True)
     writer.start()
     t0 = time.perf_counter()
@@ -225,6 +262,9 @@ def main(pargs) -> dict:
             mask = predictor(x, n_valid=nv)
             if verify:
                 matcher(predictor.mask_buffer, y, n_valid=nv)
+            if efields is not None:
+                efields(loader.raw, n_valid=nv)     # behind the catalogue's launches, on their stream
+                slot.fields[:nv].copy_(efields.table, non_blocking=True)
             slot.mask[:nv].copy_(mask, non_blocking=True)
             if slot.conf is not None:
                 slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
@@ -255,6 +295,10 @@ def main(pargs) -> dict:
     if events:
         summary["events"] = [sum(r["events"][j] for r in records) for j in range(2)]
         summary["events_overflowed_files"] = sum(1 for r in records if r["events_overflowed"])
+    if efields is not None:
+        summary["event_fields"] = {"channels": efields.C, "scale_bits": [int(v) for v in field_bits],
+                                   "nonfinite": sum(r["event_field_counts"][0] for r in records),
+                                   "saturated": sum(r["event_field_counts"][1] for r in records)}
     if verify:
         summary["event_verification"] = verification
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
