@@ -75,6 +75,8 @@ int dc_reset_options(void);
  *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
+ *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
+ *     (colour table, graticule and outlines into the RGB bytes)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -689,6 +691,46 @@ int dc_event_scores(int B, int n_valid, int cap_a, const int64_t* table_a, const
 int dc_component_fields_lds_slots(int* slots);
 int dc_component_fields(int B, int n_valid, int H, int W, const int32_t* labels, const int32_t* rank_map, int cap, const float* fields,
                         int C, int ldc, const int32_t* scale_bits, const int32_t* wy, int64_t* ftable, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frame renderer (nn.FrameRenderer; predict.py --plots, train.py --plots): the picture the reference's visualiser draws on the host
+ * (utils/visualizer.py, CamVisualizer.plot: the field of one channel through a colour table, the class-1 and class-2 regions of the
+ * prediction outlined above the same field with the labels' regions outlined, rolled so that longitude 0 is in the middle, rows spaced
+ * by the Gall stereographic projection, a graticule), made on the device as 8-bit RGB.  Only the colour index is floating point, two
+ * separately rounded fp32 operations; everything after it is integer arithmetic: equal inputs give equal bytes.
+ *   fields     fp32 [B][H][W][ldc]      channel-last, physical units; channel ch is drawn, 0 <= ch < ldc
+ *   lo, scale  the drawn range: t = (v - lo) * scale, normally scale = 1 / (hi - lo) rounded to fp32
+ *   lut        uint8 [nlut][3], device  the colour table (R, G, B), 1 <= nlut <= 256
+ *   mask_a     [B][H][W] of 1-, 4- or 8-byte integers (a_bytes, as dc_wce_score takes labels): values 1 and 2 are the classes, every
+ *              other value is background.  mask_b likewise (b_bytes); mask_b == NULL: one panel, P = 1, else P = 2 (a above b)
+ *   src_row    int32 [Ho], device       the source row of every output row; ANY values, clamped to [0, H - 1]; need not be monotone
+ *   shift      0 <= shift < W           output column x shows source column (x + shift) mod W
+ *   row_line   uint8 [Ho], col_line uint8 [W], device: non-zero = a graticule line through that output row / column
+ *   missing_rgb 0x00RRGGBB; line_argb, class1_argb, class2_argb 0xAARRGGBB (plain ints)
+ *   width      1, 3, 5 or 7: the outlines' width in source pixels, R = (width - 1) / 2
+ *   out        uint8 [B][P][Ho][W][3]
+ *   workspace  dc_render_workspace(B, P, H, W) bytes, 256-byte aligned: one byte per source pixel and panel.  Every call overwrites
+ *              all of it that it reads.
+ * For every valid sample b, panel p and output pixel (y, x), with r = clamp(src_row[y]), c = (x + shift) mod W, m = the panel's mask:
+ *   1. v = fields[b][r][c][ch].  NaN or +-Inf: the colour is missing_rgb.  Otherwise t = fl32(fl32(v - lo) * scale) (two roundings,
+ *      nothing fused); i = 0 unless t > 0 (so also where t is NaN, which takes a non-finite lo or scale), i = nlut - 1 if t >= 1, else
+ *      i = min(nlut - 1, (int)fl32(t * nlut)); the colour is lut[i].
+ *   2. If row_line[y] or col_line[x] is non-zero, line_argb is blended over the colour.
+ *   3. class1_argb is blended over it where (r, c) lies on the outline of class 1 of m, then class2_argb likewise for class 2.
+ *   blend(fg, a): every channel becomes (fg * a + old * (255 - a) + 127) / 255 in integer arithmetic.
+ *   An EDGE pixel of class k is a pixel of class k with at least one of its four neighbours not of class k; rows r +- 1 count only where
+ *   they exist, columns are periodic (c +- 1 modulo W).  The OUTLINE of class k is every pixel (r, c) with an edge pixel of class k at
+ *   (r + dy, (c + dx) mod W) for some |dy|, |dx| <= R with the row in range.  The outline lives in source space: output rows that show
+ *   the same source row show the same outline.
+ * W >= 8, H >= 1, H * W < 2^31, Ho * W < 2^31, 0 < n_valid <= B (at most 32767).  Samples from n_valid on are neither read nor
+ * written.  Does not synchronise.  dc_render_tile: the source tile of the outline pass (tests derive their shapes from it);
+ * dc_render_workspace: 0 for arguments out of range.  Both are host functions. */
+int dc_render_tile(int* th, int* tw);
+size_t dc_render_workspace(int B, int panels, int H, int W);
+int dc_render_frames(int B, int n_valid, int H, int W, const float* fields, int ch, int ldc, float lo, float scale, const uint8_t* lut,
+                     int nlut, const void* mask_a, int a_bytes, const void* mask_b /*may be NULL*/, int b_bytes, const int32_t* src_row,
+                     int Ho, int shift, const uint8_t* row_line, const uint8_t* col_line, int missing_rgb, int line_argb, int class1_argb,
+                     int class2_argb, int width, uint8_t* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

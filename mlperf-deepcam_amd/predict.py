@@ -22,6 +22,10 @@ also carries ``event_fields`` (int64 [n, C, 6] over all C file channels: min, ma
 ``events``, in their order), ``event_field_values`` (float64 [n, C, 8]: min, its lat and lon, max, its lat and lon, mean, area-weighted
 mean; NaN where there is none) and ``event_field_bits`` (int32 [C], the sums' binary scale from the stats file's range), and
 ``summary.json`` gains ``event_fields`` (channels, scale_bits, and the non-finite and saturated values met over all stored events).
+With --plots nn.FrameRenderer draws, on the device, what the reference's visualiser draws on the host: channel --plot_channel of the raw
+fields through a colour table, the predicted cyclones and rivers outlined, and with --verify a second panel below it with the labelled
+ones; ``<output_dir>/plots/<base>.png`` is written for every --plot_every-th input file (in the order of the file names) and
+``summary.json`` gains ``plots`` (their number).  Only the RGB bytes cross to the host; the writer thread encodes them (png.py).
 Single process, single device."""
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ import torch
 
 from . import data as ddata
 from . import nn as dnn
+from . import png
 
 
 class _Verify(argparse.Action):
@@ -82,6 +87,11 @@ def build_parser():
                     "least this share of it with its class, in (0, 1]")
     AP.add_argument("--event_fields", action=_EventFields, help="per event and file channel the extremes with their positions and the means "
                     "of the raw fields (implies --events): datasets 'event_fields', 'event_field_values', 'event_field_bits'")
+    AP.add_argument("--plots", action="store_true", help="also write <output_dir>/plots/<base>.png: the field with the predicted classes "
+                    "outlined (with --verify: above the same field with the labelled ones).  Encoding one two-panel 768 x 1152 frame takes tens "
+                    "to hundreds of milliseconds of the writer thread, so with --plot_every 1 the writer bounds the rate, not the device: raise --plot_every")
+    AP.add_argument("--plot_every", type=int, default=1, help="with --plots: draw every N-th input file")
+    AP.add_argument("--plot_channel", type=int, default=0, help="with --plots: the file channel that is drawn (0: integrated water vapour)")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -133,8 +143,16 @@ def filter_matches(rows_a: np.ndarray, rows_b: np.ndarray, pairs: np.ndarray, mi
     return np.ascontiguousarray(rows_a[keep_a]), np.ascontiguousarray(rows_b[keep_b]), np.ascontiguousarray(out)
 
 
+def plot_name(base: str) -> str:
+    """the picture's file name for an input file's base name"""
+    return (base[:-3] if base.endswith(".h5") else base) + ".png"
+
+
 class _HostSlot:
-    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0):
+    def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
+                 plot_rows: int = 0):
+        # --plots: the RGB bytes of nn.FrameRenderer, per sample the panels stacked
+        self.rgb = torch.empty((B, plot_rows, W, 3), dtype=torch.uint8).pin_memory() if plot_rows else None
         # --event_fields: the rows of nn.EventFields (cap * C rows of 48 bytes per sample)
         self.fields = torch.empty((B, event_cap, field_channels, len(dnn.EVENT_FIELD_STATS)), dtype=torch.int64).pin_memory() \
             if field_channels else None
@@ -159,7 +177,7 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
         item = work_q.get()
         if item is None:
             return
-        slot, names = item
+        slot, names, plot = item
         try:
             if not errors:
                 slot.done.synchronize()                      # host wait of THIS thread: the copies of the batch have landed
@@ -185,8 +203,12 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             extra = dict(extra or {}, event_fields=frows, event_field_values=dnn.EventFields.values(frows, rows, H, W, field_bits),
                                          event_field_bits=np.asarray(field_bits, np.int32))
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
+                    if plot[j]:
+                        png.write_png(os.path.join(out_dir, "plots", plot_name(base)), slot.rgb[j].numpy())
                     rec = {"file": base, "class_counts": [int(v) for v in slot.counts[j].tolist()],
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
+                    if plot[j]:
+                        rec["plot"] = plot_name(base)
                     if rows is not None:
                         rec["events"] = [int((rows[:, 1] == 1).sum()), int((rows[:, 1] == 2).sum())]
                         rec["events_overflowed"] = total > slot.events.shape[1]
@@ -242,10 +264,23 @@ def main(pargs) -> dict:
         field_bits = dnn.event_field_bits(dataset.minval, dataset.maxval)
         efields = dnn.EventFields(catalog, loader.cfile, field_bits)
 
+    # --plots: one panel (the prediction), with --verify two (the prediction above the labels); the range is the stats file's
+    renderer = None
+    plot_every = max(int(getattr(pargs, "plot_every", 1)), 1)
+    if getattr(pargs, "plots", False):
+        pc = int(pargs.plot_channel)
+        if not 0 <= pc < loader.cfile:
+            raise ValueError(f"--plot_channel must lie in [0, {loader.cfile}), got {pc}")
+        os.makedirs(os.path.join(pargs.output_dir, "plots"), exist_ok=True)
+        renderer = dnn.FrameRenderer(B, H, W, channel=pc, ldc=loader.cfile, lo=float(dataset.minval[pc]), hi=float(dataset.maxval[pc]),
+                                     panels=2 if verify else 1, device=device)
+    seen = 0                                       # input files so far, in the order the batches arrive (sorted names)
+
     free_q: "queue.Queue" = queue.Queue()
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
-        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0))
+        free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
+                             renderer.P * renderer.Ho if renderer else 0))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -278,8 +313,12 @@ def main(pargs) -> dict:
                 slot.pairs[:nv].copy_(matcher.pair_table, non_blocking=True)
                 slot.npairs[:nv].copy_(matcher.pair_counts, non_blocking=True)
                 slot.scores[:nv].copy_(matcher.score_table, non_blocking=True)
+            plot = [renderer is not None and (seen + j) % plot_every == 0 for j in range(nv)]
+            seen += nv
+            if any(plot):
+                slot.rgb[:nv].copy_(renderer(loader.raw, predictor.mask_buffer, y if verify else None, n_valid=nv), non_blocking=True)
             slot.done.record(torch.cuda.current_stream())
-            work_q.put((slot, names))
+            work_q.put((slot, names, plot))
     finally:
         work_q.put(None)
         writer.join()
@@ -301,6 +340,8 @@ def main(pargs) -> dict:
                                    "saturated": sum(r["event_field_counts"][1] for r in records)}
     if verify:
         summary["event_verification"] = verification
+    if renderer is not None:
+        summary["plots"] = sum(1 for r in records if "plot" in r)
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     line = {"samples": len(records), "class_counts": totals, "seconds": round(elapsed, 4),

@@ -3,7 +3,9 @@
 Same command line as the reference (src/deepCam/train_hdf5_ddp.py:548-578, flag for flag), same step order (:345-371),
 same logging-frequency reductions (:398-414), validation averaging (:423-512: mean of per-sample IoUs at batch 1),
 checkpoint dictionary (:515-527: step, epoch, model with 'module.'-prefixed keys, optimizer) and ``:::MLLOG`` event keys
-(utils/mlperf_log_utils.py).  Out of scope by SURVEY section 8: W&B and Basemap plots (flags accepted, ignored).
+(utils/mlperf_log_utils.py).  Out of scope by SURVEY section 8: W&B (flags accepted, ignored).  The visualiser's plots
+(train_hdf5_ddp.py:374-394,463-476) are drawn on the device by nn.FrameRenderer and only with --plots: without it the two visualisation
+frequencies stay accepted and unused and no plots directory is made.
 Input: data.InputPipeline over the HDF5 files (decoded with h5py, or through the HDF5 C library when h5py is not installed:
 h5lite), or over synthetic HWC fields with ``--synthetic_samples N``.
 
@@ -28,6 +30,7 @@ import torch.distributed as dist
 from . import data as ddata
 from . import dist as comm
 from . import nn as dnn
+from . import png
 
 
 class StoreDictKeyPair(ap.Action):
@@ -117,8 +120,9 @@ def build_parser():
     AP.add_argument("--validation_frequency", type=int, default=100, help="Frequency with which the model is validated")
     AP.add_argument("--max_validation_steps", type=int, default=None, help="Number of validation steps to perform (invalidates a submission)")
     AP.add_argument("--logging_frequency", type=int, default=100, help="Frequency with which the training progress is logged")
-    AP.add_argument("--training_visualization_frequency", type=int, default=50, help="accepted; plotting is out of scope (0 = off)")
-    AP.add_argument("--validation_visualization_frequency", type=int, default=50, help="accepted; plotting is out of scope (0 = off)")
+    AP.add_argument("--training_visualization_frequency", type=int, default=50, help="with --plots: one sample is drawn every this many training steps (0 = off); unused without --plots")
+    AP.add_argument("--validation_visualization_frequency", type=int, default=50,
+                    help="with --plots: one sample per validation pass is drawn, at the first batch whose index this divides (0 = off); unused without --plots")
     AP.add_argument("--local_batch_size", type=int, default=1, help="Number of samples per local minibatch")
     AP.add_argument("--channels", type=int, nargs="+", default=list(range(16)), help="Channels used in input")
     AP.add_argument("--optimizer", type=str, default="Adam", choices=["Adam", "AdamW", "LAMB"], help="Optimizer to use")
@@ -145,7 +149,40 @@ def build_parser():
                     help="samples per validation batch; 1: the reference's loop, above 1: the batched validation step (same per-sample metric)")
     AP.add_argument("--virtual_ranks", type=int, default=1,
                     help="data-parallel ranks this process stands for: K micro-batches of --local_batch_size per step, one optimizer update")
+    AP.add_argument("--plots", action="store_true",
+                    help="rank 0 writes <output_dir>/plots/training-*.png and validation-*.png at the two visualisation frequencies: the first "
+                    "input channel with the predicted classes outlined, above the same field with the labelled ones")
     return AP
+
+
+class FramePlotter:
+    """--plots on rank 0 (train_hdf5_ddp.py:374-394,463-476): one sample of a batch as a two-panel PNG, the prediction above the labels.
+    The picture is made on the device (nn.FrameRenderer at batch 1, built at the first plot); the encode runs on the host after the one
+    synchronise the copy of the bytes implies.  The sample index comes from a private RandomState: plotting draws nothing from the global
+    generators, so a run with --plots trains on the same numbers as one without."""
+
+    def __init__(self, output_dir: str, dataset, channels, height: int, width: int, device):
+        self.dir = os.path.join(output_dir, "plots")
+        os.makedirs(self.dir, exist_ok=True)
+        self.channel = int(channels[0])            # the reference draws inputs[:, 0]: the first selected channel, normalised to [0, 1]
+        lo = getattr(dataset, "minval", getattr(dataset, "_lo", None))
+        hi = getattr(dataset, "maxval", getattr(dataset, "_hi", None))
+        self.lo, self.hi = float(lo[self.channel]), float(hi[self.channel])
+        self.H, self.W, self.device = height, width, device
+        self.rs = np.random.RandomState(333)
+        self.renderer = None
+
+    def plot(self, kind: str, raw: torch.Tensor, prediction: torch.Tensor, label: torch.Tensor, names) -> str:
+        """raw: InputPipeline.raw of the batch; prediction, label: integer class maps [B, H, W]; names: the valid samples' files"""
+        if self.renderer is None:
+            self.renderer = dnn.FrameRenderer(1, self.H, self.W, channel=self.channel, ldc=raw.shape[3], lo=self.lo, hi=self.hi, panels=2,
+                                              device=self.device)
+        i = int(self.rs.randint(low=0, high=len(names)))
+        label = label.squeeze(1) if label.dim() == 4 else label
+        frame = self.renderer(raw[i:i + 1], prediction[i:i + 1].contiguous(), label[i:i + 1].contiguous())
+        path = os.path.join(self.dir, os.path.basename(names[i]).replace("data-", kind + "-").replace(".h5", ".png"))
+        png.write_png(path, frame[0].cpu().numpy())
+        return path
 
 
 def main(pargs):
@@ -247,6 +284,8 @@ def main(pargs):
     val_step = dnn.ValStep(net, class_weights, VB, H, W) if VB > 1 else None
     if ddp.reducer is not None:
         train_step.attach_reducer(ddp.reducer)
+    plotter = FramePlotter(pargs.output_dir, train_set, pargs.channels, H, W, device) if pargs.plots and rank == 0 else None
+    tvf, vvf = pargs.training_visualization_frequency, pargs.validation_visualization_frequency
     step, epoch = start_step, start_epoch
     current_lr = pargs.start_lr if scheduler is None else scheduler.get_last_lr()[0]
     stop_training = False
@@ -262,6 +301,8 @@ def main(pargs):
             if scheduler is not None:
                 current_lr = scheduler.get_last_lr()[0]
                 scheduler.step()
+            if plotter is not None and tvf > 0 and step % tvf == 0:
+                plotter.plot("training", train_loader.raw, train_step.pred, label, filename)
             if step % pargs.logging_frequency == 0:
                 loss_now = train_step.loss()
                 # the fused loss kernel turns a label outside [0, 3) into NaN (the reference's CrossEntropyLoss raises on it,
@@ -288,21 +329,31 @@ def main(pargs):
                 logger.log_start(key="eval_start", metadata={"epoch_num": epoch + 1})
                 net.eval()
                 sums = torch.zeros(3, dtype=torch.float64, device=device)            # count, loss, iou
+                visualized = plotter is None or vvf <= 0
                 if val_step is not None:
                     # batches of VB samples: per-sample loss and IoU and their sums stay on the device (nn.ValStep); the ragged last batch
                     # arrives padded and is scored up to the samples it names
                     val_step.reset()
                     step_val = 0
                     for inputs_val, label_val, names_val in validation_loader:
+                        plot_now = not visualized and step_val % vvf == 0
+                        val_step.store_logits = plot_now                  # bf16 keeps the logits in registers unless asked
                         val_step(inputs_val, label_val, n_valid=len(names_val))
+                        if plot_now:
+                            mask_val = dnn.predict_from_logits(val_step.eng.logits, n_valid=len(names_val))[0]
+                            plotter.plot("validation", validation_loader.raw, mask_val, label_val, names_val)
+                            visualized = True
                         step_val += 1
                         if pargs.max_validation_steps is not None and step_val > pargs.max_validation_steps:
                             break
                     sums = val_step.acc.clone()
                 with torch.no_grad():
                     step_val = 0
-                    for inputs_val, label_val, _ in (validation_loader if val_step is None else ()):
+                    for inputs_val, label_val, names_val in (validation_loader if val_step is None else ()):
                         outputs_val = net.engine_for(shape=(1, len(pargs.channels), H, W)).forward(inputs_val, train=False)
+                        if not visualized and step_val % vvf == 0:
+                            plotter.plot("validation", validation_loader.raw, dnn.predict_from_logits(outputs_val)[0], label_val, names_val)
+                            visualized = True
                         counts = torch.zeros(9, dtype=torch.int64, device=device)
                         ls = dnn.wce_fused(outputs_val, label_val, class_weights, counts=counts)
                         sums[0] += 1.0
