@@ -75,6 +75,7 @@ int dc_reset_options(void);
  *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
+ *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
  *     (colour table, graticule and outlines into the RGB bytes)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
@@ -691,6 +692,54 @@ int dc_event_scores(int B, int n_valid, int cap_a, const int64_t* table_a, const
 int dc_component_fields_lds_slots(int* slots);
 int dc_component_fields(int B, int n_valid, int H, int W, const int32_t* labels, const int32_t* rank_map, int cap, const float* fields,
                         int C, int ldc, const int32_t* scale_bits, const int32_t* wy, int64_t* ftable, void* stream);
+
+/* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
+ * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in
+ * device memory from one call to the next, and only small tables ever cross the bus.  Everything is integer arithmetic: equal inputs give
+ * equal bits whatever the scheduling and however the frames were cut into batches.
+ *   Frames are numbered 0, 1, 2, ... in the order they are given.  The EVENTS of a frame are the rows of its catalogue table, rank k <
+ *   min(ncomp all, cap); the event number of (frame f, rank k) is the count of events in the frames before f, plus k.  Events with a
+ *   number >= event_cap are counted, not stored, and take part in nothing.
+ *   Two stored events of consecutive frames are LINKED when they have the same class, at least one pixel (r, c) belongs to both (the two
+ *   masks hold that class there), and each has at least max(min_pixels, 1) pixels.  No dilation, no gap frames, never across classes.
+ *   A TRACK is a connected component of the stored events under these links (merges and splits stay inside one track); its id is the
+ *   smallest event number it holds, and track rows are ordered by id.
+ *   state     int64 [4], device, kept across calls (zero it to start a series): events stored, frames seen, events not stored because
+ *             the store was full, frames whose catalogue was truncated (ncomp all > cap)
+ *   parent    int32 [event_cap]: the forest over event numbers, a root names itself.  Between calls every entry names an event of its own
+ *             track with a number not larger than its own; dc_track_resolve leaves the smallest (the id) in every stored entry.
+ *   store     int64 [event_cap][12]: frame, rank, then the ten columns of the event's catalogue row unchanged
+ * dc_track_append numbers the events of a batch: frames j < n_valid of (table, ncomp) as dc_component_stats left them, frame j being frame
+ * number frame0 + j (the caller counts frames; frame0 + n_valid < 2^31).
+ *   first     int64 [B]: [j] = the event number of rank 0 of frame j, the prefix sum of min(ncomp all, cap) over the frames before it on
+ *             top of state[0] + state[2], read on the device.  Entries from n_valid on are not written.
+ *   For every new stored event e: parent[e] = e and store[e] is filled.  state is advanced.  1 <= cap <= 2^22.
+ * dc_track_link unites the events of n frame pairs in one pass over both masks: pair j is frame j of side a (the EARLIER frame) against
+ * frame j of side b, every array with the per-frame stride H * W (first_x: one entry per frame), so the pairs inside a batch are the
+ * batch's own arrays as a and the same arrays advanced by one frame as b, n = n_valid - 1; one more call with n = 1 links a frame kept
+ * from the call before.  mask_x, labels_x, rank_x as dc_component_overlap takes them; labels and ranks are read only where both masks
+ * hold the same class 1 or 2.  The masks are loaded 4 bytes at a time where W % 4 == 0 and both bases are 4-byte aligned, bytewise
+ * otherwise.  Events of rank >= cap, of number >= event_cap or (min_pixels > 1) of fewer than min_pixels pixels (store column 4) are
+ * skipped.  n = 0 launches nothing.  0 <= n <= 65535, H * W < 2^31 - 1, event_cap * H * W * 2^20 < 2^63 (a track's area sum fits).
+ * dc_track_resolve is called when tracks are read; it may be called at any point of a series and changes no later result.
+ *   track_of  int32 [event_cap]: per stored event the row of its track, -1 where that row is >= track_cap; entries from state[0] on are
+ *             not written
+ *   tracks    int64 [track_cap][8], zeroed by the call: id, class, events, first frame, last frame, pixels (summed over the events),
+ *             peak = the unsigned maximum over the events of (pixels << 32) | (0xFFFFFFFF - frame) (the largest event, the earliest frame
+ *             among equals), area (the sum of the events' column `sum wy[r]`)
+ *   ntracks   int64 [4]: tracks of any class, of class 1, of class 2 -- not capped --, rows stored = min(all, track_cap)
+ *   workspace dc_track_workspace(event_cap) bytes (a host function; 0 for arguments out of range), 256-byte aligned; holds nothing
+ *             between calls
+ * 1 <= event_cap <= 2^30, 1 <= track_cap <= event_cap.  The grids are sized from event_cap; the kernels read the live count from state.
+ * No call synchronises or reads anything on the host; all of them run on the caller's stream, in its order. */
+size_t dc_track_workspace(int event_cap);
+int dc_track_append(int B, int n_valid, int cap, const int64_t* table, const int32_t* ncomp, long frame0, int event_cap, int64_t* state,
+                    int64_t* first, int32_t* parent, int64_t* store, void* stream);
+int dc_track_link(int n, int H, int W, const uint8_t* mask_a, const int32_t* labels_a, const int32_t* rank_a, const int64_t* first_a,
+                  const uint8_t* mask_b, const int32_t* labels_b, const int32_t* rank_b, const int64_t* first_b, int cap, int event_cap,
+                  long min_pixels, const int64_t* store, int32_t* parent, void* stream);
+int dc_track_resolve(int event_cap, int track_cap, const int64_t* state, int32_t* parent, const int64_t* store, int32_t* track_of,
+                     int64_t* tracks, int64_t* ntracks, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frame renderer (nn.FrameRenderer; predict.py --plots, train.py --plots): the picture the reference's visualiser draws on the host

@@ -974,3 +974,348 @@ extern "C" int dc_component_fields(int B, int n_valid, int H, int W, const int32
   DC_LAUNCHED("cc_fields");
   return 0;
 }
+
+// ---- event tracks (dc_track_append, dc_track_link, dc_track_resolve; nn.EventTracker) ------------------------------------------------
+// The events of a time series, numbered in the order frames and ranks arrive, and a second union-find forest over those numbers: two
+// events of consecutive frames that share a pixel of their class are united, a track is a tree.  `parent` is int32 [event_cap] in the
+// plain encoding of the LDS forest above (a root names itself), and the two invariants of this file's header carry over word for word:
+//   (I1) dc_track_append writes parent[e] = e before any launch on the stream can meet e, and afterwards an entry changes by atomicMin
+//        only (tk_union) or, in tk_flatten, to the root a walk from it ended at; both are smaller than the entry's index or equal to
+//        what it held.  A link joins an event with one of the frame before, whose number is smaller (the numbers grow with the frames),
+//        and unites the two ROOTS, the larger below the smaller: every link goes to a smaller number, every walk descends and ends.
+//   (I2) every value parent[e] ever held names an event of e's track: itself, a root it was united with, or the root of a later walk.
+// So it does not matter whether the entries of earlier calls are flattened, partly flattened (a resolve in the middle of the series) or
+// as the unions left them: a union through them still ends at the two current roots.  When an atomicMin replaces a -> old by a -> b the
+// loop goes on with (old, b), as g_union does.  The state survives from call to call in device memory; nothing is read on the host.
+//   tk_first    one workgroup: the prefix sum of min(ncomp, cap) over the batch's frames on top of the events seen so far, the counters
+//   tk_fill     16 threads per new event: its row of the store (frame, rank, the ten catalogue columns) and parent[e] = e
+//   tk_link     one thread per 4 consecutive pixels of a frame pair, both masks as one word each where the layout allows; labels and ranks
+//               are read only where both masks hold the same class 1 or 2.  A thread skips a pixel whose two labels equal those of the
+//               foreground pixel before it (its own, or the last one of its left lane): a run costs one union.  A repeated union that
+//               slips through is two finds and no atomic.
+//   tk_flatten, tk_count, tk_offsets, tk_rank, tk_gather    (resolve) every entry becomes its root, the roots are ranked in order as
+//               cc_count / cc_offsets / cc_rank rank root pixels, and every event adds itself to its track's row with 64-bit integer
+//               atomics (sums and unsigned maxima: no result depends on the order of arrival).  A track's root is its smallest event
+//               number, so its id, its class and its first frame are the root's own and need no atomic.
+namespace dc {
+
+static constexpr int TK_STORE = 12, TK_TRACK = 8;  // store row: frame, rank, the catalogue's CC_FIELDS; track row: id, class, events, first, last, pixels, peak, area
+static constexpr int TK_CHUNK = 256;               // events per workgroup of the root count and rank passes
+static constexpr unsigned long long TK_NONE = ~0ull;
+static_assert(TK_STORE == CC_FIELDS + 2, "tk_fill_kernel: a store row is (frame, rank) and a catalogue row");
+
+__device__ inline int tk_find(const int* P, int x) {
+  for (;;) {
+    const int p = __hip_atomic_load(P + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p >= x || p < 0) return x;      // root (p == x); anything else cannot occur and ends the walk as well
+    x = p;
+  }
+}
+__device__ inline void tk_union(int* P, int a, int b) {
+  for (;;) {
+    a = tk_find(P, a);
+    b = tk_find(P, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(P + a, b);
+    if (old >= a) return;               // a was a root and now hangs below b
+    a = old;                            // a had been linked meanwhile: its former parent and b are still to be united
+  }
+}
+
+__device__ inline int tk_rows(const int* __restrict__ ncomp, int j, int cap) {
+  const int all = ncomp[j * 3];
+  return all < 0 ? 0 : (all > cap ? cap : all);
+}
+
+__global__ __launch_bounds__(256) void tk_first_kernel(int n_valid, int cap, const int* __restrict__ ncomp, long long event_cap, long long* state,
+                                                       long long* __restrict__ first) {
+  __shared__ int s_w[4];
+  __shared__ long long s_base;
+  if (threadIdx.x == 0) s_base = state[0] + state[2];
+  __syncthreads();
+  const long long base = s_base;
+  long long carry = 0, cut = 0;
+  for (int j0 = 0; j0 < n_valid; j0 += 256) {      // uniform trip count: every thread reaches the barriers inside the scans
+    const int j = j0 + threadIdx.x;
+    const int v = j < n_valid ? tk_rows(ncomp, j, cap) : 0, t = j < n_valid && ncomp[j * 3] > cap ? 1 : 0;
+    int tot, tot_t;
+    const int ex = block_excl_scan(v, s_w, &tot);
+    block_excl_scan(t, s_w, &tot_t);
+    if (j < n_valid) first[j] = base + carry + ex;
+    carry += tot;
+    cut += tot_t;
+  }
+  if (threadIdx.x == 0) {                          // the only reader of the state is this workgroup, and it has read it
+    const long long all = base + carry, stored = all < event_cap ? all : event_cap;
+    state[0] = stored;
+    state[1] += n_valid;
+    state[2] = all - stored;
+    state[3] += cut;
+  }
+}
+
+__global__ __launch_bounds__(256) void tk_fill_kernel(int cap, const long long* __restrict__ table, const int* __restrict__ ncomp, long long frame0,
+                                                      long long event_cap, const long long* __restrict__ first, int* __restrict__ parent,
+                                                      long long* __restrict__ store) {
+  const int j = blockIdx.y, k = blockIdx.x * 16 + (threadIdx.x >> 4), f = threadIdx.x & 15;
+  if (k >= tk_rows(ncomp, j, cap) || f >= TK_STORE) return;
+  const long long e = first[j] + k;
+  if (e < 0 || e >= event_cap) return;             // beyond the store: counted in the state only
+  store[e * TK_STORE + f] = f == 0 ? frame0 + j : f == 1 ? (long long)k : table[((size_t)j * cap + k) * CC_FIELDS + (f - 2)];
+  if (f == 0) parent[e] = (int)e;
+}
+
+struct TkPair {                                    // one frame pair's slices and what every lookup needs
+  const int *rank_a, *rank_b;
+  long long first_a, first_b, event_cap, min_pixels;
+  const long long* store;
+  int* parent;
+  long HW;
+  int cap;
+};
+
+__device__ inline void tk_link(const TkPair& S, int root_a, int root_b) {
+  if (root_a < 0 || root_a >= S.HW || root_b < 0 || root_b >= S.HW) return;
+  const int ra = S.rank_a[root_a], rb = S.rank_b[root_b];
+  if (ra < 0 || ra >= S.cap || rb < 0 || rb >= S.cap) return;                   // no row in its frame's table: no event
+  const long long ea = S.first_a + ra, eb = S.first_b + rb;
+  if (ea < 0 || ea >= S.event_cap || eb < 0 || eb >= S.event_cap) return;       // not stored
+  if (S.min_pixels > 1 && (S.store[ea * TK_STORE + 4] < S.min_pixels || S.store[eb * TK_STORE + 4] < S.min_pixels)) return;
+  tk_union(S.parent, (int)ea, (int)eb);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void tk_link_kernel(long HW, const uint8_t* __restrict__ mask_a, const int* __restrict__ labels_a,
+                                                      const int* __restrict__ rank_a, const long long* __restrict__ first_a,
+                                                      const uint8_t* __restrict__ mask_b, const int* __restrict__ labels_b,
+                                                      const int* __restrict__ rank_b, const long long* __restrict__ first_b, int cap,
+                                                      long long event_cap, long long min_pixels, const long long* store, int* parent) {
+  const size_t base = (size_t)blockIdx.y * HW;
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  unsigned wa = 0u, wb = 0u;                       // four mask bytes of each side; zero (background) beyond the frame's end
+  if (p0 < HW) {
+    if (VEC) {                                     // HW % 4 == 0 and 4-byte aligned bases: the word lies inside the frame
+      wa = *(const unsigned*)(mask_a + base + p0);
+      wb = *(const unsigned*)(mask_b + base + p0);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (p0 + i < HW) {
+          wa |= (unsigned)mask_a[base + p0 + i] << (8 * i);
+          wb |= (unsigned)mask_b[base + p0 + i] << (8 * i);
+        }
+    }
+  }
+  unsigned long long key[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned ca = (wa >> (8 * i)) & 255u, cb = (wb >> (8 * i)) & 255u;
+    key[i] = TK_NONE;
+    if (ca == cb && (ca == 1u || ca == 2u)) {
+      const int la = labels_a[base + p0 + i], lb = labels_b[base + p0 + i];
+      if (la > 0 && lb > 0) key[i] = ((unsigned long long)(unsigned)la << 32) | (unsigned)lb;
+    }
+  }
+  // every lane is still here: the last pixel of the left lane (the frame is one flat run of pixels; lane 0 starts afresh)
+  unsigned long long prev = __shfl_up(key[3], 1, 64);
+  if ((threadIdx.x & 63) == 0) prev = TK_NONE;
+  if ((key[0] & key[1] & key[2] & key[3]) == TK_NONE) return;
+  TkPair S;
+  S.rank_a = rank_a + base;
+  S.rank_b = rank_b + base;
+  S.first_a = first_a[blockIdx.y];
+  S.first_b = first_b[blockIdx.y];
+  S.event_cap = event_cap;
+  S.min_pixels = min_pixels;
+  S.store = store;
+  S.parent = parent;
+  S.HW = HW;
+  S.cap = cap;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned long long k = key[i];
+    if (k == TK_NONE || k == prev) continue;
+    prev = k;
+    tk_link(S, (int)(k >> 32) - 1, (int)(k & 0xffffffffull) - 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void tk_flatten_kernel(const long long* __restrict__ state, int* parent) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= state[0]) return;
+  const int v = parent[e];
+  if (v < 0 || v >= (int)e) return;
+  const int root = tk_find(parent, v);             // other threads' stores of this launch replace an entry by its root, an ancestor (I2)
+  if (root != v) parent[e] = root;
+}
+
+// roots (total, class 1) of every chunk of TK_CHUNK consecutive events
+__global__ __launch_bounds__(256) void tk_count_kernel(const long long* __restrict__ state, const int* __restrict__ parent,
+                                                       const long long* __restrict__ store, int* __restrict__ chunk_cnt) {
+  __shared__ int s_w[4];
+  const long long e = (long long)blockIdx.x * TK_CHUNK + threadIdx.x;
+  const bool root = e < state[0] && parent[e] == (int)e;
+  const bool one = root && store[e * TK_STORE + 3] == 1;
+  int tot, tot1;
+  block_excl_scan(root ? 1 : 0, s_w, &tot);
+  block_excl_scan(one ? 1 : 0, s_w, &tot1);
+  if (threadIdx.x == 0) {
+    chunk_cnt[(size_t)blockIdx.x * 2 + 0] = tot;
+    chunk_cnt[(size_t)blockIdx.x * 2 + 1] = tot1;
+  }
+}
+
+// one workgroup: the live chunks' counts become exclusive offsets, the sums go to ntracks
+__global__ __launch_bounds__(256) void tk_offsets_kernel(const long long* __restrict__ state, const int* __restrict__ chunk_cnt,
+                                                         int* __restrict__ chunk_off, long long track_cap, long long* __restrict__ ntracks) {
+  __shared__ int s_w[4];
+  const long long nchunk = (state[0] + TK_CHUNK - 1) / TK_CHUNK;
+  int carry = 0, carry1 = 0;
+  for (long long k0 = 0; k0 < nchunk; k0 += 256) {
+    const long long k = k0 + threadIdx.x;
+    const int v = k < nchunk ? chunk_cnt[2 * k] : 0, v1 = k < nchunk ? chunk_cnt[2 * k + 1] : 0;
+    int tot, tot1;
+    const int ex = block_excl_scan(v, s_w, &tot);
+    block_excl_scan(v1, s_w, &tot1);
+    if (k < nchunk) chunk_off[k] = carry + ex;
+    carry += tot;
+    carry1 += tot1;
+  }
+  if (threadIdx.x == 0) {
+    ntracks[0] = carry;
+    ntracks[1] = carry1;
+    ntracks[2] = carry - carry1;
+    ntracks[3] = carry < track_cap ? (long long)carry : track_cap;
+  }
+}
+
+// every root learns its row (kept in row_of at the root's own index) and opens it: id, class, first frame
+__global__ __launch_bounds__(256) void tk_rank_kernel(const long long* __restrict__ state, const int* __restrict__ parent,
+                                                      const long long* __restrict__ store, const int* __restrict__ chunk_off, int track_cap,
+                                                      int* __restrict__ row_of, long long* __restrict__ tracks) {
+  __shared__ int s_w[4];
+  const long long e = (long long)blockIdx.x * TK_CHUNK + threadIdx.x;
+  const bool root = e < state[0] && parent[e] == (int)e;
+  int tot;
+  const int ex = block_excl_scan(root ? 1 : 0, s_w, &tot);
+  if (!root) return;
+  const int row = chunk_off[blockIdx.x] + ex;
+  row_of[e] = row;
+  if (row < track_cap) {
+    long long* t = tracks + (size_t)row * TK_TRACK;
+    t[0] = e;
+    t[1] = store[e * TK_STORE + 3];
+    t[3] = store[e * TK_STORE + 0];                // the smallest event number of the track lies in its earliest frame
+  }
+}
+
+__global__ __launch_bounds__(256) void tk_gather_kernel(const long long* __restrict__ state, const int* __restrict__ parent,
+                                                        const long long* __restrict__ store, const int* __restrict__ row_of, int track_cap,
+                                                        int* __restrict__ track_of, long long* tracks) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= state[0]) return;
+  const int root = parent[e];
+  const int row = root >= 0 && root <= (int)e ? row_of[root] : -1;
+  if (row < 0 || row >= track_cap) {
+    track_of[e] = -1;
+    return;
+  }
+  track_of[e] = row;
+  const long long* s = store + e * TK_STORE;
+  const unsigned long long frame = (unsigned long long)s[0], pixels = (unsigned long long)s[4];
+  unsigned long long* t = (unsigned long long*)(tracks + (size_t)row * TK_TRACK);
+  atomicAdd(t + 2, 1ull);
+  atomicMax(t + 4, frame);
+  atomicAdd(t + 5, pixels);
+  atomicMax(t + 6, (pixels << 32) | (0xffffffffull - frame));
+  atomicAdd(t + 7, (unsigned long long)s[5]);
+}
+
+static int tk_check_caps(int event_cap) {
+  DC_REQUIRE(event_cap >= 1 && event_cap <= (1 << 30), "tracks: event_cap must lie in [1, 2^30]");
+  return 0;
+}
+
+}  // namespace dc
+
+// the workspace: row_of int32 [event_cap] | chunk_cnt int32 [nchunk][2] | chunk_off int32 [nchunk]
+extern "C" size_t dc_track_workspace(int event_cap) {
+  if (event_cap < 1 || event_cap > (1 << 30)) return 0;
+  const size_t nchunk = ((size_t)event_cap + TK_CHUNK - 1) / TK_CHUNK;
+  return cc_align((size_t)event_cap * 4) + cc_align(nchunk * 8) + cc_align(nchunk * 4);
+}
+
+extern "C" int dc_track_append(int B, int n_valid, int cap, const int64_t* table, const int32_t* ncomp, long frame0, int event_cap,
+                               int64_t* state, int64_t* first, int32_t* parent, int64_t* store, void* stream) {
+  DC_REQUIRE(B > 0 && n_valid > 0 && n_valid <= B, "dc_track_append: n_valid must lie in [1, B]");
+  DC_REQUIRE(n_valid <= 65535, "dc_track_append: at most 65535 frames per call");
+  DC_REQUIRE(cap >= 1 && cap <= (1 << 22), "dc_track_append: cap must lie in [1, 2^22]");
+  if (int rc = tk_check_caps(event_cap)) return rc;
+  DC_REQUIRE(frame0 >= 0 && frame0 + n_valid <= 2147483647L, "dc_track_append: frame numbers must stay below 2^31");
+  DC_REQUIRE(table && ncomp && state && first && parent && store, "dc_track_append: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(tk_first_kernel, dim3(1), dim3(256), 0, st, n_valid, cap, ncomp, (long long)event_cap, (long long*)state, (long long*)first);
+  DC_LAUNCHED("cc_tracks");
+  hipLaunchKernelGGL(tk_fill_kernel, dim3((cap + 15) / 16, n_valid), dim3(256), 0, st, cap, (const long long*)table, ncomp, (long long)frame0,
+                     (long long)event_cap, (const long long*)first, parent, (long long*)store);
+  DC_LAUNCHED("cc_tracks");
+  return 0;
+}
+
+extern "C" int dc_track_link(int n, int H, int W, const uint8_t* mask_a, const int32_t* labels_a, const int32_t* rank_a, const int64_t* first_a,
+                             const uint8_t* mask_b, const int32_t* labels_b, const int32_t* rank_b, const int64_t* first_b, int cap,
+                             int event_cap, long min_pixels, const int64_t* store, int32_t* parent, void* stream) {
+  DC_REQUIRE(n >= 0 && n <= 65535, "dc_track_link: n must lie in [0, 65535]");
+  DC_REQUIRE(H > 0 && W > 0, "dc_track_link: H and W must be positive");
+  DC_REQUIRE((long)H * W < 2147483647L, "dc_track_link: H * W must be below 2^31 - 1 (labels are int32)");
+  DC_REQUIRE(cap >= 1, "dc_track_link: cap must be at least 1");
+  if (int rc = tk_check_caps(event_cap)) return rc;
+  DC_REQUIRE((long)event_cap <= ((1L << 43) - 1) / ((long)H * W), "dc_track_link: event_cap * H * W * 2^20 must stay below 2^63 (a track's area sum)");
+  DC_REQUIRE(min_pixels >= 0, "dc_track_link: min_pixels must not be negative");
+  DC_REQUIRE(mask_a && labels_a && rank_a && first_a && mask_b && labels_b && rank_b && first_b && store && parent, "dc_track_link: null pointer");
+  if (n == 0) return 0;
+  const long HW = (long)H * W;
+  const bool vec = W % 4 == 0 && (((uintptr_t)mask_a | (uintptr_t)mask_b) & 3) == 0;
+  const dim3 grid((unsigned)((HW + 1023) / 1024), n);
+  if (vec)
+    hipLaunchKernelGGL(tk_link_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, HW, mask_a, labels_a, rank_a, (const long long*)first_a,
+                       mask_b, labels_b, rank_b, (const long long*)first_b, cap, (long long)event_cap, (long long)min_pixels,
+                       (const long long*)store, parent);
+  else
+    hipLaunchKernelGGL(tk_link_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, HW, mask_a, labels_a, rank_a, (const long long*)first_a,
+                       mask_b, labels_b, rank_b, (const long long*)first_b, cap, (long long)event_cap, (long long)min_pixels,
+                       (const long long*)store, parent);
+  DC_LAUNCHED("cc_tracks");
+  return 0;
+}
+
+extern "C" int dc_track_resolve(int event_cap, int track_cap, const int64_t* state, int32_t* parent, const int64_t* store, int32_t* track_of,
+                                int64_t* tracks, int64_t* ntracks, void* workspace, void* stream) {
+  if (int rc = tk_check_caps(event_cap)) return rc;
+  DC_REQUIRE(track_cap >= 1 && track_cap <= event_cap, "dc_track_resolve: track_cap must lie in [1, event_cap]");
+  DC_REQUIRE(state && parent && store && track_of && tracks && ntracks && workspace, "dc_track_resolve: null pointer");
+  DC_REQUIRE(((uintptr_t)workspace & 255) == 0, "dc_track_resolve: workspace not 256-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t nchunk = ((size_t)event_cap + TK_CHUNK - 1) / TK_CHUNK;
+  int* row_of = (int*)workspace;
+  int* chunk_cnt = (int*)((char*)workspace + cc_align((size_t)event_cap * 4));
+  int* chunk_off = (int*)((char*)chunk_cnt + cc_align(nchunk * 8));
+  hipError_t e = hipMemsetAsync(tracks, 0, (size_t)track_cap * TK_TRACK * sizeof(int64_t), st);
+  if (e != hipSuccess) return dc_set_error(e, __FILE__, __LINE__);
+  const dim3 grid((unsigned)nchunk);
+  hipLaunchKernelGGL(tk_flatten_kernel, grid, dim3(256), 0, st, (const long long*)state, parent);
+  DC_LAUNCHED("cc_tracks");
+  hipLaunchKernelGGL(tk_count_kernel, grid, dim3(256), 0, st, (const long long*)state, parent, (const long long*)store, chunk_cnt);
+  DC_LAUNCHED("cc_tracks");
+  hipLaunchKernelGGL(tk_offsets_kernel, dim3(1), dim3(256), 0, st, (const long long*)state, chunk_cnt, chunk_off, (long long)track_cap,
+                     (long long*)ntracks);
+  DC_LAUNCHED("cc_tracks");
+  hipLaunchKernelGGL(tk_rank_kernel, grid, dim3(256), 0, st, (const long long*)state, parent, (const long long*)store, chunk_off, track_cap, row_of,
+                     (long long*)tracks);
+  DC_LAUNCHED("cc_tracks");
+  hipLaunchKernelGGL(tk_gather_kernel, grid, dim3(256), 0, st, (const long long*)state, parent, (const long long*)store, row_of, track_cap, track_of,
+                     (long long*)tracks);
+  DC_LAUNCHED("cc_tracks");
+  return 0;
+}

@@ -1243,6 +1243,152 @@ class EventFields:
         return out
 
 
+TRACK_STORE_FIELDS = ("frame", "rank") + EVENT_FIELDS
+TRACK_FIELDS = ("id", "class", "events", "first_frame", "last_frame", "pixels", "peak", "area")
+
+
+class EventTracker:
+    """Events linked across time steps on the device (dc_track_append, dc_track_link, dc_track_resolve, csrc/components.hip): the frames
+    given since reset() are one time series, frame numbers 0, 1, 2, ...; two events of consecutive frames are linked when they have the
+    same class, share at least one pixel and each has at least max(min_pixels, 1) pixels; a track is a connected component of the events
+    under these links (merges and splits stay in one track), its id the smallest event number it holds (include/deepcam_hip.h has the
+    definitions).  Built on an existing EventCatalog, as EventFields is.  The object owns the state that survives from call to call --
+    the four counters, the forest over event numbers, the store (int64 [event_cap, 12], TRACK_STORE_FIELDS) -- and one-frame copies of
+    the last frame's mask, labels, rank map and first event number, because the caller's mask buffer and the catalogue's workspace are
+    overwritten by the next call.  A call must follow the catalogue's call for that mask on the same stream; it launches and neither
+    synchronises nor reads anything back.  tracks() / rows() resolve and read back only the filled parts."""
+
+    def __init__(self, catalog: EventCatalog, event_cap: int = 1 << 19, track_cap: Optional[int] = None, min_pixels: int = 0):
+        event_cap = int(event_cap)
+        track_cap = event_cap if track_cap is None else int(track_cap)
+        if not 1 <= event_cap <= 1 << 30:
+            raise L.DeepcamHipError(f"EventTracker: event_cap must lie in [1, 2^30], got {event_cap}")
+        if not 1 <= track_cap <= event_cap:
+            raise L.DeepcamHipError(f"EventTracker: track_cap must lie in [1, event_cap], got {track_cap}")
+        if int(min_pixels) < 0:
+            raise L.DeepcamHipError("EventTracker: min_pixels must not be negative")
+        if event_cap > ((1 << 43) - 1) // (catalog.H * catalog.W):
+            raise L.DeepcamHipError(f"EventTracker: event_cap * H * W * 2^20 must stay below 2^63, got event_cap {event_cap} at "
+                                    f"{catalog.H} x {catalog.W}")
+        self.catalog, self.event_cap, self.track_cap, self.min_pixels = catalog, event_cap, track_cap, int(min_pixels)
+        dev = catalog._labels.device
+        H, W = catalog.H, catalog.W
+        self._state = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._first = torch.zeros(catalog.B, dtype=torch.int64, device=dev)
+        self._parent = torch.empty(event_cap, dtype=torch.int32, device=dev)
+        self._store = torch.empty((event_cap, len(TRACK_STORE_FIELDS)), dtype=torch.int64, device=dev)
+        self._track_of = torch.empty(event_cap, dtype=torch.int32, device=dev)
+        self._tracks = torch.zeros((track_cap, len(TRACK_FIELDS)), dtype=torch.int64, device=dev)
+        self._ntracks = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._ws = torch.empty(L.load().dc_track_workspace(event_cap), dtype=torch.uint8, device=dev)
+        # the carry: the last valid frame of the call before
+        self._c_mask = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
+        self._c_labels = torch.zeros((1, H, W), dtype=torch.int32, device=dev)
+        self._c_rank = torch.zeros((1, H, W), dtype=torch.int32, device=dev)
+        self._c_first = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._carry = False
+        self._frames = 0                           # frames given since reset(), counted on the host: the next call's frame0
+
+    def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventTracker":
+        """mask: the device uint8 [B, H, W] the catalogue was just called with.  n_valid defaults to the catalogue's and must equal it."""
+        cat = self.catalog
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (cat.B, cat.H, cat.W) or not mask.is_cuda or not mask.is_contiguous() \
+                or mask.device != cat._labels.device:
+            raise L.DeepcamHipError(f"EventTracker: mask must be a contiguous uint8 tensor [{cat.B}, {cat.H}, {cat.W}] on {cat._labels.device}, "
+                                    f"got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        nv = cat._last_valid if n_valid is None else int(n_valid)
+        if nv < 1 or nv != cat._last_valid:
+            raise L.DeepcamHipError(f"EventTracker: call the catalogue on this mask first, with the same n_valid (its last call had "
+                                    f"{cat._last_valid}, this one has {nv})")
+        HW, st = cat.H * cat.W, L.stream_ptr()
+        at = lambda t, k: C.c_void_p(t.data_ptr() + k * t.element_size())  # noqa: E731
+        L.call("dc_track_append", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), self._frames, self.event_cap, L.dptr(self._state),
+               L.dptr(self._first), L.dptr(self._parent), L.dptr(self._store), st)
+        link = lambda n, a, b: L.call("dc_track_link", n, cat.H, cat.W, *a, *b, cat.cap, self.event_cap, self.min_pixels,  # noqa: E731
+                                      L.dptr(self._store), L.dptr(self._parent), st)
+        side = lambda k: (at(mask, k * HW), at(cat._labels, k * HW), at(cat._ws, 4 * k * HW), at(self._first, k))  # noqa: E731
+        if nv > 1:
+            link(nv - 1, side(0), side(1))
+        if self._carry:
+            link(1, (L.dptr(self._c_mask), L.dptr(self._c_labels), L.dptr(self._c_rank), L.dptr(self._c_first)), side(0))
+        for dst, src in zip((self._c_mask, self._c_labels, self._c_rank, self._c_first), side(nv - 1)):
+            L.call("dc_memcpy_async", L.dptr(dst), src, dst.numel() * dst.element_size(), st)
+        self._carry = True
+        self._frames += nv
+        return self
+
+    def cut(self) -> None:
+        """A break in the sequence: the next frame is not linked to the one before it.  Frame numbering goes on."""
+        self._carry = False
+
+    def reset(self) -> None:
+        """Forget every frame: the next one is frame 0."""
+        L.call("dc_memset_async", L.dptr(self._state), 0, 32, L.stream_ptr())
+        self._carry = False
+        self._frames = 0
+
+    def state(self) -> dict:
+        """the four counters (one device-to-host read)"""
+        s = [int(v) for v in self._state.cpu().tolist()]
+        return {"events": s[0], "frames": s[1], "events_dropped": s[2], "frames_truncated": s[3]}
+
+    def resolve(self) -> "EventTracker":
+        """dc_track_resolve on the current stream: track_of, the track rows and the counts for the frames given so far.  Does not
+        synchronise; may be called in the middle of a series."""
+        L.call("dc_track_resolve", self.event_cap, self.track_cap, L.dptr(self._state), L.dptr(self._parent), L.dptr(self._store),
+               L.dptr(self._track_of), L.dptr(self._tracks), L.dptr(self._ntracks), L.dptr(self._ws), L.stream_ptr())
+        return self
+
+    def track_counts(self) -> np.ndarray:
+        """int64 [4] of the last resolve: tracks of any class, of class 1, of class 2 (not capped), rows stored"""
+        return self._ntracks.cpu().numpy()
+
+    def rows(self):
+        """(state int64 [4], store rows int64 [n, 12], track_of int32 [n], track rows int64 [m, 8]) as numpy arrays: resolves, reads the
+        counters, then only the filled parts."""
+        self.resolve()
+        state = self._state.cpu().numpy()
+        n, m = int(state[0]), int(self._ntracks[3].item())
+        return state, self._store[:n].cpu().numpy(), self._track_of[:n].cpu().numpy(), self._tracks[:m].cpu().numpy()
+
+    def tracks(self, min_frames: int = 1):
+        """The tracks of the frames given so far as a list of dicts (decode), those of fewer than min_frames frames left out."""
+        _, store, track_of, tracks = self.rows()
+        return self.decode(store, track_of, tracks, self.catalog.H, self.catalog.W, min_frames=min_frames)
+
+    @staticmethod
+    def decode(store, track_of, tracks, height: int, width: int, min_frames: int = 1):
+        """Store rows [n, 12] (TRACK_STORE_FIELDS), track_of [n] and track rows [m, 8] (TRACK_FIELDS) -> one dict per track with at least
+        min_frames frames, in row order: id, class, first_frame, last_frame, frames (last - first + 1), events, pixels, peak_pixels and
+        peak_frame (the largest single event and its frame, the earliest among equals), area_fraction_sum (the events' area fractions
+        summed) and path: per frame of the track its events' count, their pixels and the centroid lat / lon by EventCatalog.decode's
+        formulas over the SUMMED columns, so two fragments of one frame give their joint centroid.  Needs no GPU."""
+        store = np.asarray(store, np.int64).reshape(-1, len(TRACK_STORE_FIELDS))
+        track_of = np.asarray(track_of, np.int64).reshape(-1)
+        tracks = np.asarray(tracks, np.int64).reshape(-1, len(TRACK_FIELDS))
+        wy = event_weight_tables(height, width)[0]
+        whole = float(width) * float(wy.astype("int64").sum())
+        order = np.argsort(track_of, kind="stable")
+        lo = np.searchsorted(track_of[order], np.arange(len(tracks)), side="left")
+        hi = np.searchsorted(track_of[order], np.arange(len(tracks)), side="right")
+        out = []
+        for t, row in enumerate(tracks.tolist()):
+            tid, cls, nev, f0, f1, px, peak, area = row
+            if f1 - f0 + 1 < min_frames:
+                continue
+            peak &= 0xFFFFFFFFFFFFFFFF
+            ev = store[order[lo[t]:hi[t]]]
+            path = []
+            for f in np.unique(ev[:, 0]).tolist():
+                n, sr, scx, ssx = (int(v) for v in ev[ev[:, 0] == f][:, [4, 6, 7, 8]].sum(axis=0))
+                lat = -90.0 + 180.0 * (sr / n) / (height - 1) if height > 1 and n > 0 else -90.0
+                path.append({"frame": f, "events": int((ev[:, 0] == f).sum()), "pixels": n, "lat": lat, "lon": math.degrees(math.atan2(ssx, scx))})
+            out.append({"id": tid, "class": cls, "first_frame": f0, "last_frame": f1, "frames": f1 - f0 + 1, "events": nev, "pixels": px,
+                        "peak_pixels": peak >> 32, "peak_frame": 0xFFFFFFFF - (peak & 0xFFFFFFFF),
+                        "area_fraction_sum": area / whole if whole > 0 else 0.0, "path": path})
+        return out
+
+
 class Predictor:
     """Masks for unlabelled data: the eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running
     statistics through the shared arena, pooled activations) whose classifier leaves, per pixel, the first-max class as one byte

@@ -26,6 +26,12 @@ With --plots nn.FrameRenderer draws, on the device, what the reference's visuali
 fields through a colour table, the predicted cyclones and rivers outlined, and with --verify a second panel below it with the labelled
 ones; ``<output_dir>/plots/<base>.png`` is written for every --plot_every-th input file (in the order of the file names) and
 ``summary.json`` gains ``plots`` (their number).  Only the RGB bytes cross to the host; the writer thread encodes them (png.py).
+With --tracks (which implies --events) nn.EventTracker links the events of consecutive files on the device, behind the catalogue of every
+batch: the sorted files are taken as ONE gap-free time sequence, file index = frame number (gaps in the dates or interleaved runs are
+not detected from the names).  At the end of the run ``<output_dir>/tracks.h5`` holds ``tracks`` (int64 [n, 8]: id, class, events, first
+frame, last frame, pixels, peak, area), ``track_events`` (int64 [m, 13]: frame, rank, the ten columns of ``events``, the row of
+``tracks`` or -1 -- with --min_event_pixels 0, (frame, rank) is row `rank` of the ``events`` and ``event_fields`` of file `frame`) and
+``track_state`` (int64 [4]: events stored, frames, events dropped, frames with a truncated catalogue); ``summary.json`` gains ``tracks``.
 Single process, single device."""
 from __future__ import annotations
 
@@ -66,6 +72,17 @@ class _EventFields(argparse.Action):
         namespace.events = True
 
 
+class _Tracks(argparse.Action):
+    """--tracks: implies --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.tracks = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -92,6 +109,11 @@ def build_parser():
                     "to hundreds of milliseconds of the writer thread, so with --plot_every 1 the writer bounds the rate, not the device: raise --plot_every")
     AP.add_argument("--plot_every", type=int, default=1, help="with --plots: draw every N-th input file")
     AP.add_argument("--plot_channel", type=int, default=0, help="with --plots: the file channel that is drawn (0: integrated water vapour)")
+    AP.add_argument("--tracks", action=_Tracks, help="link the events of consecutive files into tracks (implies --events): the files, in the "
+                    "order of their sorted names, are taken as one gap-free time sequence (file index = frame number; date gaps or interleaved "
+                    "runs are not detected).  Writes <output_dir>/tracks.h5 ('tracks', 'track_events', 'track_state'); 'tracks' in the summary")
+    AP.add_argument("--min_track_frames", type=int, default=1, help="with --tracks: the summary also counts the tracks of at least N frames")
+    AP.add_argument("--min_track_pixels", type=int, default=0, help="with --tracks: events of fewer pixels link nothing")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -120,6 +142,36 @@ def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None, 
             f.write("events", events)
         for name, array in (extra or {}).items():
             f.write(name, array)
+
+
+def write_datasets(path: str, arrays: dict) -> None:
+    """the arrays as datasets of one HDF5 file, through the backend data.CamDataset reads with"""
+    backend, h5 = ddata._h5_backend()
+    with h5.File(path, "w") as f:
+        for name, array in arrays.items():
+            if backend == "h5py":
+                f.create_dataset(name, data=array)
+            else:
+                f.write(name, array)
+
+
+def track_summary(state, tracks, min_frames: int = 1) -> dict:
+    """the `tracks` entry of summary.json from the four counters and the track rows [n, 8]: per class the number of tracks, of those with
+    at least min_frames frames, and the longest one (the smallest id among equals)"""
+    tracks = np.asarray(tracks, np.int64).reshape(-1, len(dnn.TRACK_FIELDS))
+    out = {"min_frames": int(min_frames), "tracks": len(tracks)}
+    frames = tracks[:, 4] - tracks[:, 3] + 1
+    for cls in (1, 2):
+        sel = tracks[:, 1] == cls
+        longest = None
+        if sel.any():
+            t = tracks[sel][int(np.argmax(frames[sel]))]
+            longest = {"id": int(t[0]), "frames": int(t[4] - t[3] + 1), "first_frame": int(t[3]), "last_frame": int(t[4]), "events": int(t[2]),
+                       "pixels": int(t[5])}
+        out[f"class_{cls}"] = {"tracks": int(sel.sum()), "tracks_min_frames": int((sel & (frames >= min_frames)).sum()), "longest": longest}
+    s = [int(v) for v in state]
+    out["state"] = {"events": s[0], "frames": s[1], "events_dropped": s[2], "frames_truncated": s[3]}
+    return out
 
 
 def require_labels(data_dir: str) -> None:
@@ -250,7 +302,7 @@ def main(pargs) -> dict:
     net.eval()
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     loader = ddata.InputPipeline(dataset, B, dtype=dtype, device=device, layout=layout, drop_last=False, workers=pargs.max_inter_threads)
-    events = bool(pargs.events) or verify
+    events = bool(pargs.events) or verify or bool(getattr(pargs, "tracks", False))
     predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify,
                               event_connectivity=pargs.event_connectivity)
     # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
@@ -263,6 +315,9 @@ def main(pargs) -> dict:
     if getattr(pargs, "event_fields", False):
         field_bits = dnn.event_field_bits(dataset.minval, dataset.maxval)
         efields = dnn.EventFields(catalog, loader.cfile, field_bits)
+
+    # --tracks: behind the catalogue of every batch; the batches arrive in the order of the sorted names, one frame per file
+    tracker = dnn.EventTracker(catalog, min_pixels=pargs.min_track_pixels) if getattr(pargs, "tracks", False) else None
 
     # --plots: one panel (the prediction), with --verify two (the prediction above the labels); the range is the stats file's
     renderer = None
@@ -297,6 +352,8 @@ def main(pargs) -> dict:
             mask = predictor(x, n_valid=nv)
             if verify:
                 matcher(predictor.mask_buffer, y, n_valid=nv)
+            if tracker is not None:
+                tracker(predictor.mask_buffer, n_valid=nv)
             if efields is not None:
                 efields(loader.raw, n_valid=nv)     # behind the catalogue's launches, on their stream
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
@@ -326,6 +383,7 @@ def main(pargs) -> dict:
     if errors:
         raise errors[0]
     verification = matcher.result() if verify else None
+    track_rows = tracker.rows() if tracker is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -340,6 +398,11 @@ def main(pargs) -> dict:
                                    "saturated": sum(r["event_field_counts"][1] for r in records)}
     if verify:
         summary["event_verification"] = verification
+    if track_rows is not None:
+        t_state, t_store, t_of, t_tracks = track_rows
+        write_datasets(os.path.join(pargs.output_dir, "tracks.h5"),
+                       {"tracks": t_tracks, "track_events": np.concatenate([t_store, t_of.astype(np.int64)[:, None]], axis=1), "track_state": t_state})
+        summary["tracks"] = track_summary(t_state, t_tracks, pargs.min_track_frames)
     if renderer is not None:
         summary["plots"] = sum(1 for r in records if "plot" in r)
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
