@@ -34,7 +34,7 @@ const char* dc_last_error(void);
 int dc_version(void);
 /* Kernel switches (tests and A/B measurements inside one process): they force a kernel at shapes its planner would not give it, or keep
  * it off.  "igemm256": 0 = 128 x 128 tiles only, 1 = planner picks per layer (default), 2 = 256 x 256 eight-wave kernel wherever
- * eligible.  "pw384", "pw224", "pw192", "igemm256p", "wgrad384", "thin_tile", "head_*_fused", "dw_tile", "dw_pipe", "bn_apply_rows"
+ * eligible.  "pw384", "pw224", "pw192", "igemm256p", "wgrad384", "thin_tile", "head_*_fused", "dw_tile", "dw_pipe", "dw_res_masked", "bn_apply_rows"
  * and their like: see the table in README.md and the .hip files.  An unknown name is an error. */
 int dc_set_option(const char* name, int value);
 /* Every dc_set_option switch back to its default (the library's own table; also what a freshly loaded library holds). */
@@ -68,6 +68,7 @@ int dc_reset_options(void);
  *     dw_reg_*, dw_win_*                    register kernels: any stride and dilation; the stride-1 window (dw_reg_reduce sums their wgrad rows)
  *     dw_tile_*, dw_tile_s2_*               LDS-tiled kernels, stride 1 and stride 2 (dw_tile_reduce sums their wgrad rows)
  *     dwpipe_fwd, dwpipe_dgrad              the persistent pipelined kernel (its data gradient carries the weight-gradient rows)
+ *     dwpipe_dgrad_masked                   ... its data gradient that stores dx masked by the stored input (dc_dwconv_dgrad_wgrad_bnres, relu = 2)
  *   head: head_fwd_fused | the GEMM's name then head_combine; head_dgrad_stream, head_dgrad_stream_wgrad (weight gradient riding along),
  *     head_dgrad_apply | the GEMM's name
  *   BatchNorm apply: bn_apply_rows, bn_apply
@@ -320,8 +321,14 @@ int dc_dwconv_dgrad_wgrad(int dtype, int C, int stride, int dil, int N, int Hi, 
  * (deeplab_xception.py:99-122: `x += skip`, then the next block's in-place ReLU), and this data gradient is the LAST contribution to d(x):
  * that BatchNorm's backward sums (sum g, sum g*xhat; g = the stored dx masked by x > 0 when relu) are taken on the way out into
  * slab[2][rows][C], so dc_bn_bwd_reduce's pass over dx, ybn and x is not needed.  rows = dc_dwconv_dgrad_wgrad_bnres_rows (also the
- * rows of wslab; 0: not served -- use dc_dwconv_dgrad_wgrad and dc_bn_bwd_reduce). */
+ * rows of wslab; 0: not served -- use dc_dwconv_dgrad_wgrad and dc_bn_bwd_reduce).
+ * relu = 2: the sums are masked as with relu = 1 AND dx is stored masked: dx = 0 wherever x > 0 is false (the bits of masking the rounded
+ * value after the store).  The stored dx then is g itself: dc_bn_bwd_apply[_fin] takes it with relu = 0, without `out` and without `g_out`
+ * (same dy, bit for bit, as relu = 1 with out = x on the unmasked dx), and the shortcut's gradient is that buffer -- two tensor passes fewer
+ * per block end.  Served where dc_dwconv_dgrad_wgrad_bnres_masked says 1 (the shapes of _rows, while option "dw_res_masked" is on);
+ * elsewhere relu = 2 is an error. */
 int dc_dwconv_dgrad_wgrad_bnres_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi);
+int dc_dwconv_dgrad_wgrad_bnres_masked(int dtype, int C, int stride, int dil, int N, int Hi, int Wi);
 int dc_dwconv_dgrad_wgrad_bnres(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                 const float* w_packed, const void* addend, int ldadd, void* dx, int lddx, const void* x, int ldx,
                                 float* wslab, const void* ybn, int ldybn, const float* save_mean, const float* save_invstd, int relu,

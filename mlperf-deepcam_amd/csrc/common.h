@@ -110,6 +110,7 @@ struct Options {
   int dw_tile = 1;               // flag: LDS-tiled depthwise kernels (dwtile.hip); 0: the register-window kernels of dwconv.hip
   int dw_wgrad_tpb = 0;          // tiles per workgroup of the depthwise weight gradient (>= 0); 0: planner
   int dw_pipe = 1;               // 0, 1 or 2: dwpipe.hip's kernel for no depthwise layer, the data gradients, the forward pass too
+  int dw_res_masked = 1;         // flag: dc_dwconv_dgrad_wgrad_bnres offers relu = 2, dx stored masked (0: the block-end BatchNorm backward masks and copies)
   int bn_apply_rows = 1;         // flag: dc_bn_apply on bn_apply_rows_kernel (0: the grid-stride kernel)
 };
 extern Options g_options;

@@ -667,9 +667,14 @@ extern "C" int dc_dwconv_dgrad_wgrad(int dtype, int C, int stride, int dil, int 
 // of an Xception block reading the previous block's output -- and whose data gradient is the LAST contribution to d(x): the kernel also
 // takes that BatchNorm's backward sums (g = dx masked by x > 0 when relu; slab[2][rows][C]), so dc_bn_bwd_reduce's pass over dx, ybn and x
 // disappears.  Served by the persistent kernel only (rows = 0: use dc_dwconv_dgrad_wgrad + dc_bn_bwd_reduce).
+// relu = 2 (where dc_dwconv_dgrad_wgrad_bnres_masked says 1): dx is stored masked by x > 0 as well, i.e. as the g that BatchNorm's apply pass
+// and the shortcut need -- dc_bn_bwd_apply then runs with relu = 0, reads no `out` and writes no `g_out`.
 extern "C" int dc_dwconv_dgrad_wgrad_bnres_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
   if (stride != 1 || dil != 1 || !g_options.dw_tile) return 0;
   return dw_pipe_rows(dtype, C, dil, N, Hi, Wi);
+}
+extern "C" int dc_dwconv_dgrad_wgrad_bnres_masked(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
+  return g_options.dw_res_masked && dc_dwconv_dgrad_wgrad_bnres_rows(dtype, C, stride, dil, N, Hi, Wi) > 0 ? 1 : 0;
 }
 
 static int dgrad_wgrad_bnres_impl(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
@@ -685,12 +690,15 @@ static int dgrad_wgrad_bnres_impl(int dtype, int C, int stride, int dil, int N, 
     if (int e = dc_check_view(addend, ldadd, C, dtype, "dc_dwconv_dgrad_wgrad_bnres addend")) return e;
   DC_REQUIRE(w && wslab && save_mean && save_invstd && slab, "dc_dwconv_dgrad_wgrad_bnres: null argument");
   DC_REQUIRE(dc_dwconv_dgrad_wgrad_bnres_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_wgrad_bnres: shape not served");
+  DC_REQUIRE(relu >= 0 && relu <= 2, "dc_dwconv_dgrad_wgrad_bnres: relu is 0, 1 (mask the sums) or 2 (mask the sums and the stored dx)");
+  DC_REQUIRE(relu != 2 || dc_dwconv_dgrad_wgrad_bnres_masked(dtype, C, stride, dil, N, Hi, Wi),
+             "dc_dwconv_dgrad_wgrad_bnres: relu = 2 is switched off (option dw_res_masked)");
   DwBnStats bs;
   bs.y = x; bs.ldy = ldx; bs.mean = bs.invstd = nullptr; bs.mscale = nullptr; bs.mshift = nullptr; bs.relu = 0;
   bs.slab = nullptr; bs.rows = 0; bs.wslab = wslab;
   DwResStats rs;
   DC_REQUIRE(!sum_row || ((uintptr_t)slab & 7) == 0, "dc_dwconv_dgrad_wgrad_bnres_sum: a sum row is double[2][C]");
-  rs.y = ybn; rs.ldy = ldybn; rs.mean = save_mean; rs.invstd = save_invstd; rs.relu = relu ? 1 : 0; rs.slab = slab; rs.sum_row = sum_row ? 1 : 0;
+  rs.y = ybn; rs.ldy = ldybn; rs.mean = save_mean; rs.invstd = save_invstd; rs.relu = relu; rs.slab = slab; rs.sum_row = sum_row ? 1 : 0;
   return launch_dw_pipe(dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, 0, &bs, &rs);
 }
 extern "C" int dc_dwconv_dgrad_wgrad_bnres(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,

@@ -35,7 +35,9 @@ constexpr int P_CH = P_CG * 8;      // channels of a block
 // PM_RES (with PM_WGRAD): the layer's stored input x is the output relu(bn(y2) + residual) of a BatchNorm whose backward sums (sum g, sum g*xhat
 // with g = dx masked by x > 0) this kernel takes as well -- dx is that BatchNorm's complete output gradient once this kernel, its last
 // writer, has added its share to the addend (the first separable conv of an Xception block, deeplab_xception.py:69-122)
-enum { PM_FLIP = 1, PM_STATS = 2, PM_WGRAD = 4, PM_ADD = 8, PM_XFORM = 16, PM_RES = 32 };
+// PM_MASK (with PM_RES): dx is STORED masked by x > 0 as well (relu = 2 of dc_dwconv_dgrad_wgrad_bnres): it then is the masked gradient g itself,
+// which that BatchNorm's apply pass reads without the stored block output and the shortcut takes as its gradient without a copy
+enum { PM_FLIP = 1, PM_STATS = 2, PM_WGRAD = 4, PM_ADD = 8, PM_XFORM = 16, PM_RES = 32, PM_MASK = 64 };
 
 template <int DIL>
 struct PCfg {
@@ -91,8 +93,9 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
   typedef PCfg<DIL> K;
   typedef PStage<DIL, MODE> S;
   constexpr bool FLIP = (MODE & PM_FLIP) != 0, STATS = (MODE & PM_STATS) != 0, WGRAD = (MODE & PM_WGRAD) != 0, ADD = (MODE & PM_ADD) != 0,
-                 XFORM = (MODE & PM_XFORM) != 0, RES = (MODE & PM_RES) != 0;
+                 XFORM = (MODE & PM_XFORM) != 0, RES = (MODE & PM_RES) != 0, MASK = (MODE & PM_MASK) != 0;
   static_assert(!RES || (WGRAD && !STATS), "PM_RES rides on the weight-gradient form");
+  static_assert(!MASK || RES, "PM_MASK is a form of PM_RES");
   constexpr int WC = DT_PX + 2 * DIL, KH = 4, NS = S::NS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -333,6 +336,12 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
 #pragma unroll
         for (int e = 0; e < KH; ++e) acc[j][e] += av[e];
       }
+      if constexpr (MASK) {
+        // the select the sums below make on the rounded value, made on the sum instead (zero rounds to zero: the same bits as masking the
+        // packed halves); the store count per wave and tile, which the vmcnt immediates rely on, stays as it is
+#pragma unroll
+        for (int e = 0; e < KH; ++e) acc[j][e] = yf[j][e] > 0.f ? acc[j][e] : 0.f;
+      }
       vec8 v;
       pack8(v, acc[j], bf16());
       // (exactly STORES store instructions per wave per tile: the `cok` mask never empties a wave, every wave holds all 32 half-groups)
@@ -349,7 +358,7 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
         unpack8(*reinterpret_cast<const vec8*>(sb + S::OFF_Y2 + (row * P_TW + xs + j) * P_ROWB + h * 8), y2f, bf16());
 #pragma unroll
         for (int e = 0; e < KH; ++e) {
-          const float gm = (!a.relu2 || yf[j][e] > 0.f) ? gs[e] : 0.f;
+          const float gm = (MASK || !a.relu2 || yf[j][e] > 0.f) ? gs[e] : 0.f;
           ra[e] += gm;
           rb[e] = fmaf(gm, (y2f[e] - mu2[e]) * is2[e], rb[e]);
         }
@@ -491,7 +500,7 @@ int launch1(const DwpArgs& a, int grid, hipStream_t st) {
   static_assert(16 * 9 * P_CH * 4 <= LDS, "the fold's scratch lives in the drained ring");
   DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwp_kernel<DIL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
   hipLaunchKernelGGL((dwp_kernel<DIL, MODE>), dim3(grid), dim3(P_THREADS), LDS, st, a);
-  DC_LAUNCHED((MODE & PM_FLIP) ? "dwpipe_dgrad" : "dwpipe_fwd");
+  DC_LAUNCHED((MODE & PM_MASK) ? "dwpipe_dgrad_masked" : (MODE & PM_FLIP) ? "dwpipe_dgrad" : "dwpipe_fwd");
   return 0;
 }
 
@@ -543,6 +552,10 @@ int launch_dw_pipe(int dil, bool flip, const void* in, int ldin, const float* wp
   if (res != nullptr) {
     DC_REQUIRE(wg && !stats && a.y2 && a.mean2 && a.invstd2 && a.slab2, "launch_dw_pipe: the residual BatchNorm's sums ride on the weight-gradient form");
     DC_REQUIRE(dil == 1, "launch_dw_pipe: the residual form is built for dilation 1 (with dilation 2 its ring would hold a single stage)");
+    if (res->relu == 2) {
+      if (add) return launch1<1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES | PM_MASK>(a, grid, st);
+      return launch1<1, PM_FLIP | PM_WGRAD | PM_RES | PM_MASK>(a, grid, st);
+    }
     if (add) return launch1<1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES>(a, grid, st);
     return launch1<1, PM_FLIP | PM_WGRAD | PM_RES>(a, grid, st);
   }

@@ -867,6 +867,7 @@ const struct {
     {"dw_tile", &Options::dw_tile, Norm::kFlag},
     {"dw_wgrad_tpb", &Options::dw_wgrad_tpb, Norm::kNonNegative},
     {"dw_pipe", &Options::dw_pipe, Norm::kZeroToTwo},
+    {"dw_res_masked", &Options::dw_res_masked, Norm::kFlag},
     {"bn_apply_rows", &Options::bn_apply_rows, Norm::kFlag},
 };
 }  // namespace

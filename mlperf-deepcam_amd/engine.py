@@ -100,6 +100,7 @@ class Act:
         self.bn_res: Optional[dict] = None      # _bn: a block output relu(bn(y) + residual); likewise
         self.fused_bwd: Optional[tuple] = None  # set by the consumer that takes them: (slab, rows[, grad_takes at that point])
         self.fused_bwd_cancel: Optional[Callable[[], None]] = None     # ... and how that consumer backs out (_bn.make_bwd)
+        self.fused_bwd_mask: Optional[Callable[[], None]] = None       # ... or is told to store the gradient masked (bn_res, where it can)
         self.pw_fuse: Optional[dict] = None     # _conv(bn_fuse=True): the BatchNorm behind this output may leave its backward to it
         self.conv_fwd: Optional[dict] = None    # _conv / _dw: their forward launch, which _sep may replace by one fused operator
         self.dw_fwd: Optional[dict] = None
@@ -211,6 +212,7 @@ class Engine:
         self.closed = False
         lay = self.layout
         self.act_bytes = 0
+        self.masked_block_ends: List[str] = []        # the block-end BatchNorms whose backward reads a masked gradient (_bn.make_bwd)
         # name -> tensor of everything forward leaves behind for backward (activations, BatchNorm coefficient vectors): lets a
         # test put two engines on ONE linearisation point (tests/test_model_gpu.py::test_backward_parity_at_shared_activations_unfused_head)
         self.saved: Dict[str, torch.Tensor] = {}
@@ -685,9 +687,13 @@ class Engine:
                 x.fused_bwd = (bslab2, wrows, x.grad_takes)
             else:
                 bsrc = None
-            fuse_state = {"res": res, "bsrc": bsrc}
+            fuse_state = {"res": res, "bsrc": bsrc, "masked": False}
             if res is not None or bsrc is not None:
                 x.fused_bwd_cancel = lambda: fuse_state.update(res=None, bsrc=None)
+            if res is not None and lib.dc_dwconv_dgrad_wgrad_bnres_masked(self.dt, Cc, stride, dil, N, H, W) == 1:
+                # the block-end BatchNorm may ask for dx stored MASKED by the block output's sign (relu = 2): dx then is the gradient its apply
+                # pass and the shortcut need, so that pass reads no stored output and writes no copy for the shortcut (_bn.make_bwd)
+                x.fused_bwd_mask = lambda: fuse_state.update(masked=True)
             ready = [wname]
             if wrows > 0:
                 # the rows stay in this layer's own slab until the next dense weight-gradient launch folds them (dc_fold_slabs); the
@@ -703,7 +709,7 @@ class Engine:
                 if res is not None:
                     L.call("dc_dwconv_dgrad_wgrad_bnres_sum" if sum_ok else "dc_dwconv_dgrad_wgrad_bnres", self.dt, Cc, stride, dil, N, H, W, dy.ptr, dy.ld, pw, dx.ptr if mode else None, dx.ld,
                            dx.ptr, dx.ld, src.ptr, src.ld, L.dptr(wslab), res["y"].ptr, res["y"].ld, L.dptr(res["mean"]), L.dptr(res["invstd"]),
-                           res["relu"], L.dptr(rslab2), self._st())
+                           2 if fuse_state["masked"] else res["relu"], L.dptr(rslab2), self._st())
                     return
                 bs = fuse_state["bsrc"]
                 if bs is not None:
@@ -816,10 +822,8 @@ class Engine:
             apply_by = lz.apply_by if lazy else None      # the consumer writes dy itself (the head, two passes)
             do = None if apply_by is not None else (lz.grad if lazy else o.grad)
             assert y.take_grad_mode() == 0, "a conv output feeds exactly one BatchNorm"
-            g_out = None
             if residual is not None:
                 assert residual.take_grad_mode() == 0, f"{bname}: residual gradient must be first written here"
-                g_out = residual.grad
             dgam, dbet = self.gptr(bname + ".weight"), self.gptr(bname + ".bias")
             # ReLU mask: recomputed from y with the forward scale / shift whenever there is no residual (one tensor read less
             # in both backward kernels, which run at the HBM roofline); from the stored output when a residual was added
@@ -832,6 +836,7 @@ class Engine:
                 # (no mean / variance of the batch to differentiate), then the parameter gradients from that slab
                 assert not lazy and y.pw_fuse is None and o.fused_bwd is None
                 dyf = y.grad
+                g_out = residual.grad if residual is not None else None
 
                 def bwd_frozen():
                     L.call("dc_bn_bwd_frozen", bdt, M, Cc, do.ptr, do.ld, y.ptr, y.ld, optr(), old_, mrelu, gam, rm, rv, BN_EPS, dyf.ptr, dyf.ld,
@@ -856,6 +861,22 @@ class Engine:
                 o.fused_bwd_cancel()
                 fused = None
             rslab, rrows = (fused[0], fused[1]) if fused is not None else (bslab, brows)
+            # a block end relu(bn(y) + residual) whose sums the next block's first depthwise data gradient takes: that kernel, the last writer
+            # of `do`, stores it masked by the block output's sign on request.  `do` then is the masked gradient itself: the apply pass below runs
+            # without a mask (no read of the stored output) and the residual's gradient IS that buffer (no copy): three tensor passes instead
+            # of five, same bits.  The consumers of the residual's gradient add onto it in place, so ONE buffer travels down the skip path
+            if (residual is not None and fused is not None and o.bn_res is not None and o.fused_bwd_mask is not None and residual._grad is None
+                    and residual.parent is None and o.parent is None and residual.buf.dtype == o.buf.dtype
+                    and (residual.N, residual.H, residual.W, residual.C, residual.ld) == (o.N, o.H, o.W, o.C, o.ld)):
+                if relu_i:
+                    o.fused_bwd_mask()
+                residual._grad = do
+                self.saved["d" + residual.name] = do.buf      # (found under the residual's name as well: its gradient lives there)
+                self.saved_channels["d" + residual.name] = residual.C
+                g_out, mrelu, optr, old_ = None, 0, (lambda: None), 0
+                self.masked_block_ends.append(bname)
+            else:
+                g_out = residual.grad if residual is not None else None
             # a short slab (the 42 rows the persistent depthwise data gradient leaves on the 728-channel layers) of a SMALL tensor: the apply
             # kernel sums it itself (dc_bn_bwd_apply_fin, same bits): one launch and one dependent boundary less per BatchNorm of the middle
             # flow.  Every 32-row block repeats the sum for its channels, so it pays only while the grid is small: local batch 2 12.47 ->
