@@ -77,6 +77,7 @@ int dc_reset_options(void);
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
+ *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
  *     (colour table, graticule and outlines into the RGB bytes)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
@@ -747,6 +748,56 @@ int dc_track_link(int n, int H, int W, const uint8_t* mask_a, const int32_t* lab
                   long min_pixels, const int64_t* store, int32_t* parent, void* stream);
 int dc_track_resolve(int event_cap, int track_cap, const int64_t* state, int32_t* parent, const int64_t* store, int32_t* track_of,
                      int64_t* tracks, int64_t* ntracks, void* workspace, void* stream);
+
+/* Storm life cycles (nn.TrackFields; predict.py --track_fields): the join of the two sections above on the device -- per track and frame
+ * the field statistics of the track's events in that frame (a cyclone's centre and intensity per time step), per track the lifetime
+ * extremes with the frame and pixel where they occurred.  Integer arithmetic and order-independent 64-bit atomics only: equal inputs
+ * give equal bits whatever the scheduling and however the frames were cut into batches.
+ *   Links join consecutive frames only (no gap frames; a cut links nothing), so the frames of a track form an INTERVAL: every frame from
+ *   its first to its last holds at least one event of it.  A STEP is a (track, frame) pair of that interval; track row t has
+ *   frames[t] = last - first + 1 steps, and step (t, f) is row offsets[t] + f - first[t] of the step tables.
+ *   fstore    int64 [event_cap][C][6], 16-byte aligned, kept across calls next to the tracker's store: the field rows of event e, in the
+ *             format of dc_component_fields (min, max, sum, wsum, nonfinite, saturated).  48 * C bytes per event slot: 403 MB at
+ *             event_cap = 2^19 and C = 16.
+ * dc_track_fields_append files a batch's field rows: row k < min(ncomp all, cap) of frame j < n_valid of ftable ([B][cap][C][6], as
+ * dc_component_fields left it) is copied unchanged to event number e = first[j] + k, first as dc_track_append just wrote it for the same
+ * batch; events with e >= event_cap are skipped.  It runs after dc_track_append and dc_component_fields on the same stream.  16-byte loads
+ * and stores.  1 <= n_valid <= B, n_valid <= 65535, 1 <= cap <= 2^22.
+ * dc_track_cycles is called when life cycles are read, after dc_track_resolve on the same stream; it reads what that call left (state,
+ * store, track_of, tracks, ntracks) and fstore, and changes none of them.  It may be called at any point of a series.
+ *   SELECTED  track row t < ntracks[3] with frames[t] >= max(min_frames, 1) and bit `class` of class_mask set (class_mask in [1, 6]:
+ *             bit 1 is class 1, bit 2 is class 2).  need[t] = the sum of frames over the selected rows before t (the uncapped layout).
+ *   STORED    a selected row with need[t] + frames[t] <= step_cap: it lies wholly inside the first step_cap rows of the uncapped layout.
+ *             The stored rows are a prefix of the selected ones.  Events with track_of < 0 or of a track that is not stored take part in
+ *             nothing.
+ *   offsets   int64 [track_cap]: need[t] for stored rows, -1 for rows not selected, -2 for rows selected but not stored; entries from
+ *             ntracks[3] on are not written
+ *   ncycles   int64 [4]: tracks selected, step rows needed (not capped), step rows stored, tracks selected but not stored
+ *   steps     int64 [step_cap][8], 16-byte aligned; the first ncycles[2] rows are written, the others untouched: track row, frame, the
+ *             number of the track's events in that frame, and the sums over those events of the store columns pixels, area (sum wy[r]),
+ *             sum_row, sum_cx, sum_sx -- so a step of two fragments has their joint centroid
+ *   step_fields  int64 [step_cap][C][6], 16-byte aligned, the same rows: the events' field rows merged -- min = the unsigned 64-bit
+ *             minimum of their min words, max = the unsigned maximum of their max words (both still name the smallest pixel among equal
+ *             values, across fragments as within one event), sum, wsum, nonfinite, saturated = int64 sums (a step covers at most H * W
+ *             pixels: the bound of dc_component_fields holds).  Empty: (-1, 0, 0, 0, 0, 0).
+ *   track_fields  int64 [track_cap][C][4], 16-byte aligned; rows below ntracks[3] are written: the lifetime extremes of a stored track
+ *             over its steps that have a finite value.  Words 0, 1: the lexicographic minimum of (key, frame, pixel) -- the value, the
+ *             EARLIEST frame among equals, then the smallest pixel -- as (key << 32) | frame and the pixel; empty (-1, -1).  Words 2, 3:
+ *             the largest key, then the earliest frame, then the smallest pixel, as (key << 32) | (0xFFFFFFFF - frame) and the pixel;
+ *             empty (0, -1).  Rows of tracks that are not stored hold the empty values.  Lifetime SUMS are not kept: a long track can
+ *             pass int64 in units of the per-pixel quantum; add the step sums on the host.
+ *   workspace dc_track_cycles_workspace(event_cap, track_cap) bytes (a host function; 0 for arguments out of range), 256-byte aligned;
+ *             holds nothing between calls
+ * 1 <= C <= 32, 1 <= step_cap <= 2^31 - 1, min_frames >= 0, event_cap and track_cap as dc_track_resolve takes them, frames < 2^31 (the
+ * tracker's limit) and H * W <= 2^22 (the limit of the field words).  The grids are sized from the capacities; the kernels read the live
+ * counts (state[0], ntracks[3], ncycles[2]) on the device.  No call synchronises or reads anything on the host. */
+size_t dc_track_cycles_workspace(int event_cap, int track_cap);
+int dc_track_fields_append(int B, int n_valid, int cap, const int32_t* ncomp, const int64_t* first, const int64_t* ftable, int C,
+                           int event_cap, int64_t* fstore, void* stream);
+int dc_track_cycles(int event_cap, int track_cap, int step_cap, int C, int min_frames, int class_mask, const int64_t* state,
+                    const int64_t* store, const int32_t* track_of, const int64_t* tracks, const int64_t* ntracks, const int64_t* fstore,
+                    int64_t* offsets, int64_t* steps, int64_t* step_fields, int64_t* track_fields, int64_t* ncycles, void* workspace,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frame renderer (nn.FrameRenderer; predict.py --plots, train.py --plots): the picture the reference's visualiser draws on the host

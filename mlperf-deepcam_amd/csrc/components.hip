@@ -167,20 +167,22 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(long HW, int* labels) {
 
 // ---- statistics ------------------------------------------------------------------------------------------------------------------
 // exclusive prefix sum of v over the 256 threads; *total: the sum.  s_w: four words of LDS, free again when the call returns.
-__device__ inline int block_excl_scan(int v, int* s_w, int* total) {
+// T: int, or long long where the sum can pass 2^31 (the step rows of dc_track_cycles)
+template <typename T>
+__device__ inline T block_excl_scan(T v, T* s_w, T* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
+  T incl = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const int n = __shfl_up(incl, o, 64);
+    const T n = __shfl_up(incl, o, 64);
     if (lane >= o) incl += n;
   }
   if (lane == 63) s_w[wave] = incl;
   __syncthreads();
-  int before = 0, all = 0;
+  T before = 0, all = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int w = s_w[k];
+    const T w = s_w[k];
     if (k < wave) before += w;
     all += w;
   }
@@ -1317,5 +1319,254 @@ extern "C" int dc_track_resolve(int event_cap, int track_cap, const int64_t* sta
   hipLaunchKernelGGL(tk_gather_kernel, grid, dim3(256), 0, st, (const long long*)state, parent, (const long long*)store, row_of, track_cap, track_of,
                      (long long*)tracks);
   DC_LAUNCHED("cc_tracks");
+  return 0;
+}
+
+// ---- storm life cycles (dc_track_fields_append, dc_track_cycles; nn.TrackFields) -------------------------------------------------------
+// The join of the two products above: dc_track_fields_append files every event's field rows (dc_component_fields) under its event number,
+// next to the tracker's store, and dc_track_cycles groups them by (track, frame) when life cycles are read.  Links join consecutive
+// frames only, so the frames of a track form an interval and every one of them holds an event of the track: the step rows of track row t
+// are the frames[t] = last - first + 1 rows from offsets[t] on, offsets a prefix sum over the selected track rows.  No sort, no search.
+// A row is stored iff it ends inside step_cap; the offsets grow with t, so the stored rows are a prefix of the selected ones and the
+// stored step rows are exactly the first ncycles[2].
+//   tf_file     (append) one thread per 16 bytes of a new event's field rows
+//   tf_count, tf_offsets, tf_rank    the prefix sum of the selected rows' frame counts, as tk_count / tk_offsets / tk_rank rank roots, in
+//               int64; tf_rank writes offsets and adds the stored step rows and the rows left out (one atomic each per workgroup)
+//   tf_init     zeros into the stored step rows, the empty row into their field rows and into the lifetime rows of every track row
+//   tf_event    one thread per (stored event, channel): its field row into the step's with the atomics of fs_emit; the channel-0 thread also
+//               adds the event's store columns to the step row and writes the row's track and frame (every event of a step writes the
+//               same two values)
+//   tf_life<0>  one thread per (stored step row, channel): (key, frame) into the track's lifetime words, one atomicMin and one atomicMax
+//   tf_life<1>  the same threads: the step whose (key, frame) won stores its pixel -- (track, frame) names one step row, so one writer
+// Minimum, maximum and integer addition only: no result depends on the order of arrival.
+namespace dc {
+
+static constexpr int TF_STEP = 8, TF_LIFE = 4;     // step row: track, frame, events, pixels, area, sum_row, sum_cx, sum_sx; lifetime row: min, its pixel, max, its pixel
+static constexpr int TF_INIT_BLOCKS = 1 << 16;     // tf_init strides over its pieces with at most this many workgroups
+static_assert(FS_STATS == 6, "tf_file, tf_init, tf_event: a field row is three 16-byte pieces");
+
+__global__ __launch_bounds__(256) void tf_file_kernel(int cap, const int* __restrict__ ncomp, const long long* __restrict__ first, int C,
+                                                      long long event_cap, const ulonglong2* __restrict__ ftable, ulonglong2* __restrict__ fstore) {
+  const int j = blockIdx.y;
+  const long per = (long)C * 3, i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long k = i / per;
+  if (k >= tk_rows(ncomp, j, cap)) return;
+  const long long e = first[j] + k;
+  if (e < 0 || e >= event_cap) return;             // beyond the store: no field row either
+  fstore[(size_t)e * per + (i - k * per)] = ftable[((size_t)j * cap + k) * per + (i - k * per)];
+}
+
+// the frames of track row t if it is selected, else 0 (a track has at least one frame)
+__device__ inline long long tf_frames(const long long* __restrict__ ntracks, const long long* __restrict__ tracks, long long t, int min_frames,
+                                      int class_mask) {
+  if (t >= ntracks[3]) return 0;
+  const long long* r = tracks + (size_t)t * TK_TRACK;
+  const long long n = r[4] - r[3] + 1, cls = r[1];
+  if (n < 1 || n < min_frames || cls < 1 || cls > 2 || !((class_mask >> (int)cls) & 1)) return 0;
+  return n;
+}
+
+__global__ __launch_bounds__(256) void tf_count_kernel(const long long* __restrict__ ntracks, const long long* __restrict__ tracks, int min_frames,
+                                                       int class_mask, long long* __restrict__ chunk_cnt) {
+  __shared__ long long s_w[4];
+  const long long v = tf_frames(ntracks, tracks, (long long)blockIdx.x * TK_CHUNK + threadIdx.x, min_frames, class_mask);
+  long long tot, tot_n;
+  block_excl_scan<long long>(v, s_w, &tot);
+  block_excl_scan<long long>(v > 0 ? 1 : 0, s_w, &tot_n);
+  if (threadIdx.x == 0) {
+    chunk_cnt[(size_t)blockIdx.x * 2 + 0] = tot;
+    chunk_cnt[(size_t)blockIdx.x * 2 + 1] = tot_n;
+  }
+}
+
+__global__ __launch_bounds__(256) void tf_offsets_kernel(const long long* __restrict__ ntracks, const long long* __restrict__ chunk_cnt,
+                                                         long long* __restrict__ chunk_off, long long* __restrict__ ncycles) {
+  __shared__ long long s_w[4];
+  const long long nchunk = (ntracks[3] + TK_CHUNK - 1) / TK_CHUNK;
+  long long carry = 0, carry_n = 0;
+  for (long long k0 = 0; k0 < nchunk; k0 += 256) {
+    const long long k = k0 + threadIdx.x;
+    const long long v = k < nchunk ? chunk_cnt[2 * k] : 0, vn = k < nchunk ? chunk_cnt[2 * k + 1] : 0;
+    long long tot, tot_n;
+    const long long ex = block_excl_scan<long long>(v, s_w, &tot);
+    block_excl_scan<long long>(vn, s_w, &tot_n);
+    if (k < nchunk) chunk_off[k] = carry + ex;
+    carry += tot;
+    carry_n += tot_n;
+  }
+  if (threadIdx.x == 0) {
+    ncycles[0] = carry_n;
+    ncycles[1] = carry;
+    ncycles[2] = 0;                                // tf_rank adds to these two
+    ncycles[3] = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void tf_rank_kernel(const long long* __restrict__ ntracks, const long long* __restrict__ tracks, int min_frames,
+                                                      int class_mask, const long long* __restrict__ chunk_off, long long step_cap,
+                                                      long long* __restrict__ offsets, long long* ncycles) {
+  __shared__ long long s_w[4];
+  const long long t = (long long)blockIdx.x * TK_CHUNK + threadIdx.x;
+  if ((long long)blockIdx.x * TK_CHUNK >= ntracks[3]) return;   // the whole workgroup: tf_offsets wrote no offset for this chunk
+  const long long v = tf_frames(ntracks, tracks, t, min_frames, class_mask);
+  long long tot, rows, left;
+  const long long need = chunk_off[blockIdx.x] + block_excl_scan<long long>(v, s_w, &tot);
+  const bool stored = v > 0 && need + v <= step_cap;
+  block_excl_scan<long long>(stored ? v : 0, s_w, &rows);
+  block_excl_scan<long long>(v > 0 && !stored ? 1 : 0, s_w, &left);
+  if (t < ntracks[3]) offsets[t] = v == 0 ? -1 : stored ? need : -2;
+  if (threadIdx.x == 0) {
+    if (rows != 0) atomicAdd((unsigned long long*)ncycles + 2, (unsigned long long)rows);
+    if (left != 0) atomicAdd((unsigned long long*)ncycles + 3, (unsigned long long)left);
+  }
+}
+
+// pieces of 16 bytes: 4 per stored step row, 3 C per stored step row of the fields, 2 C per track row
+__global__ __launch_bounds__(256) void tf_init_kernel(int C, const long long* __restrict__ ntracks, const long long* __restrict__ ncycles,
+                                                      ulonglong2* __restrict__ steps, ulonglong2* __restrict__ step_fields,
+                                                      ulonglong2* __restrict__ track_fields) {
+  const long long n = ncycles[2], m = ntracks[3];
+  const long long a = n * (TF_STEP / 2), b = a + n * C * 3, all = b + m * C * 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < all; i += (long long)gridDim.x * 256) {
+    if (i < a)
+      steps[i] = make_ulonglong2(0ull, 0ull);
+    else if (i < b)
+      step_fields[i - a] = make_ulonglong2((i - a) % 3 == 0 ? FS_NONE : 0ull, 0ull);
+    else
+      track_fields[i - b] = make_ulonglong2((i - b) % 2 == 0 ? FS_NONE : 0ull, FS_NONE);   // (-1, -1) and (0, -1)
+  }
+}
+
+__global__ __launch_bounds__(256) void tf_event_kernel(int C, long long step_cap, const long long* __restrict__ state,
+                                                       const long long* __restrict__ store, const int* __restrict__ track_of,
+                                                       const long long* __restrict__ tracks, const long long* __restrict__ offsets,
+                                                       const ulonglong2* __restrict__ fstore, long long* steps, unsigned long long* step_fields) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, e = i / C;
+  const int ch = (int)(i - e * C);
+  if (e >= state[0]) return;
+  const int t = track_of[e];
+  if (t < 0) return;                               // its track has no row
+  const long long off = offsets[t];
+  if (off < 0) return;                             // not selected, or not stored
+  const long long* s = store + e * TK_STORE;
+  const long long frames = tracks[(size_t)t * TK_TRACK + 4] - tracks[(size_t)t * TK_TRACK + 3] + 1;
+  const long long d = s[0] - tracks[(size_t)t * TK_TRACK + 3];
+  if (d < 0 || d >= frames || off + d >= step_cap) return;   // cannot occur: the frame lies inside its track's interval, the row inside the table
+  const long long row = off + d;
+  const ulonglong2* src = fstore + ((size_t)e * C + ch) * 3;
+  const ulonglong2 lohi = src[0], sums = src[1], cnts = src[2];
+  unsigned long long* q = step_fields + ((size_t)row * C + ch) * FS_STATS;
+  fs_emit(q, lohi.x, lohi.y, (long long)sums.x, (long long)sums.y, 0, 0);
+  if (cnts.x != 0) atomicAdd(q + 4, cnts.x);
+  if (cnts.y != 0) atomicAdd(q + 5, cnts.y);
+  if (ch != 0) return;
+  long long* r = steps + (size_t)row * TF_STEP;
+  r[0] = t;                                        // every event of the step stores the same two values
+  r[1] = s[0];
+  atomicAdd((unsigned long long*)r + 2, 1ull);
+  atomicAdd((unsigned long long*)r + 3, (unsigned long long)s[4]);
+  atomicAdd((unsigned long long*)r + 4, (unsigned long long)s[5]);
+  atomicAdd((unsigned long long*)r + 5, (unsigned long long)s[6]);
+  atomicAdd((unsigned long long*)r + 6, (unsigned long long)s[7]);
+  atomicAdd((unsigned long long*)r + 7, (unsigned long long)s[8]);
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void tf_life_kernel(int C, long long track_cap, const long long* __restrict__ ncycles,
+                                                      const long long* __restrict__ steps, const unsigned long long* __restrict__ step_fields,
+                                                      unsigned long long* track_fields) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, row = i / C;
+  const int ch = (int)(i - row * C);
+  if (row >= ncycles[2]) return;
+  const long long t = steps[(size_t)row * TF_STEP + 0];
+  const unsigned long long frame = (unsigned long long)steps[(size_t)row * TF_STEP + 1] & 0xffffffffull;
+  if (t < 0 || t >= track_cap) return;             // cannot occur: every stored step row holds an event of a stored track
+  const unsigned long long* q = step_fields + ((size_t)row * C + ch) * FS_STATS;
+  const unsigned long long lo = q[0], hi = q[1];
+  if (lo == FS_NONE) return;                       // no finite value in this step (then hi is empty as well)
+  unsigned long long* life = track_fields + ((size_t)t * C + ch) * TF_LIFE;
+  const unsigned long long wlo = (lo & ~0xffffffffull) | frame, whi = (hi & ~0xffffffffull) | (0xffffffffull - frame);
+  if (PASS == 0) {
+    atomicMin(life + 0, wlo);
+    atomicMax(life + 2, whi);
+  } else {
+    if (life[0] == wlo) life[1] = lo & 0xffffffffull;
+    if (life[2] == whi) life[3] = 0xffffffffull - (hi & 0xffffffffull);
+  }
+}
+
+static int tf_check(int event_cap, int track_cap, int C) {
+  if (int rc = tk_check_caps(event_cap)) return rc;
+  DC_REQUIRE(track_cap >= 1 && track_cap <= event_cap, "track fields: track_cap must lie in [1, event_cap]");
+  DC_REQUIRE(C >= 1 && C <= FS_MAX_C, "track fields: C must lie in [1, 32]");
+  return 0;
+}
+
+}  // namespace dc
+
+// the workspace: chunk_cnt int64 [nchunk][2] | chunk_off int64 [nchunk], nchunk chunks of TK_CHUNK track rows
+extern "C" size_t dc_track_cycles_workspace(int event_cap, int track_cap) {
+  if (event_cap < 1 || event_cap > (1 << 30) || track_cap < 1 || track_cap > event_cap) return 0;
+  const size_t nchunk = ((size_t)track_cap + TK_CHUNK - 1) / TK_CHUNK;
+  return cc_align(nchunk * 16) + cc_align(nchunk * 8);
+}
+
+extern "C" int dc_track_fields_append(int B, int n_valid, int cap, const int32_t* ncomp, const int64_t* first, const int64_t* ftable, int C,
+                                      int event_cap, int64_t* fstore, void* stream) {
+  DC_REQUIRE(B > 0 && n_valid > 0 && n_valid <= B, "dc_track_fields_append: n_valid must lie in [1, B]");
+  DC_REQUIRE(n_valid <= 65535, "dc_track_fields_append: at most 65535 frames per call");
+  DC_REQUIRE(cap >= 1 && cap <= (1 << 22), "dc_track_fields_append: cap must lie in [1, 2^22]");
+  if (int rc = tf_check(event_cap, 1, C)) return rc;
+  DC_REQUIRE(ncomp && first && ftable && fstore, "dc_track_fields_append: null pointer");
+  DC_REQUIRE((((uintptr_t)ftable | (uintptr_t)fstore) & 15) == 0, "dc_track_fields_append: ftable or fstore not 16-byte aligned");
+  const long pieces = (long)cap * C * 3;
+  hipLaunchKernelGGL(tf_file_kernel, dim3((unsigned)((pieces + 255) / 256), n_valid), dim3(256), 0, (hipStream_t)stream, cap, ncomp,
+                     (const long long*)first, C, (long long)event_cap, (const ulonglong2*)ftable, (ulonglong2*)fstore);
+  DC_LAUNCHED("cc_track_fields");
+  return 0;
+}
+
+extern "C" int dc_track_cycles(int event_cap, int track_cap, int step_cap, int C, int min_frames, int class_mask, const int64_t* state,
+                               const int64_t* store, const int32_t* track_of, const int64_t* tracks, const int64_t* ntracks,
+                               const int64_t* fstore, int64_t* offsets, int64_t* steps, int64_t* step_fields, int64_t* track_fields,
+                               int64_t* ncycles, void* workspace, void* stream) {
+  if (int rc = tf_check(event_cap, track_cap, C)) return rc;
+  DC_REQUIRE(step_cap >= 1, "dc_track_cycles: step_cap must lie in [1, 2^31 - 1]");
+  DC_REQUIRE(min_frames >= 0, "dc_track_cycles: min_frames must not be negative");
+  DC_REQUIRE(class_mask >= 1 && class_mask <= 6, "dc_track_cycles: class_mask must lie in [1, 6] (bit 1: class 1, bit 2: class 2)");
+  DC_REQUIRE(state && store && track_of && tracks && ntracks && fstore && offsets && steps && step_fields && track_fields && ncycles && workspace,
+             "dc_track_cycles: null pointer");
+  DC_REQUIRE((((uintptr_t)fstore | (uintptr_t)steps | (uintptr_t)step_fields | (uintptr_t)track_fields) & 15) == 0,
+             "dc_track_cycles: fstore, steps, step_fields or track_fields not 16-byte aligned");
+  DC_REQUIRE(((uintptr_t)workspace & 255) == 0, "dc_track_cycles: workspace not 256-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t nchunk = ((size_t)track_cap + TK_CHUNK - 1) / TK_CHUNK;
+  long long* chunk_cnt = (long long*)workspace;
+  long long* chunk_off = (long long*)((char*)workspace + cc_align(nchunk * 16));
+  const long long *nt = (const long long*)ntracks, *tr = (const long long*)tracks;
+  long long* nc = (long long*)ncycles;
+  hipLaunchKernelGGL(tf_count_kernel, dim3((unsigned)nchunk), dim3(256), 0, st, nt, tr, min_frames, class_mask, chunk_cnt);
+  DC_LAUNCHED("cc_track_fields");
+  hipLaunchKernelGGL(tf_offsets_kernel, dim3(1), dim3(256), 0, st, nt, chunk_cnt, chunk_off, nc);
+  DC_LAUNCHED("cc_track_fields");
+  hipLaunchKernelGGL(tf_rank_kernel, dim3((unsigned)nchunk), dim3(256), 0, st, nt, tr, min_frames, class_mask, chunk_off, (long long)step_cap,
+                     (long long*)offsets, nc);
+  DC_LAUNCHED("cc_track_fields");
+  const size_t pieces = (size_t)step_cap * (TF_STEP / 2 + (size_t)C * 3) + (size_t)track_cap * C * 2;
+  const size_t init_blocks = (pieces + 255) / 256;
+  hipLaunchKernelGGL(tf_init_kernel, dim3((unsigned)(init_blocks < (size_t)TF_INIT_BLOCKS ? init_blocks : (size_t)TF_INIT_BLOCKS)), dim3(256), 0, st,
+                     C, nt, nc, (ulonglong2*)steps, (ulonglong2*)step_fields, (ulonglong2*)track_fields);
+  DC_LAUNCHED("cc_track_fields");
+  hipLaunchKernelGGL(tf_event_kernel, dim3((unsigned)(((size_t)event_cap * C + 255) / 256)), dim3(256), 0, st, C, (long long)step_cap,
+                     (const long long*)state, (const long long*)store, track_of, tr, (const long long*)offsets, (const ulonglong2*)fstore,
+                     (long long*)steps, (unsigned long long*)step_fields);
+  DC_LAUNCHED("cc_track_fields");
+  const dim3 life((unsigned)(((size_t)step_cap * C + 255) / 256));
+  hipLaunchKernelGGL(tf_life_kernel<0>, life, dim3(256), 0, st, C, (long long)track_cap, nc, (const long long*)steps,
+                     (const unsigned long long*)step_fields, (unsigned long long*)track_fields);
+  DC_LAUNCHED("cc_track_fields");
+  hipLaunchKernelGGL(tf_life_kernel<1>, life, dim3(256), 0, st, C, (long long)track_cap, nc, (const long long*)steps,
+                     (const unsigned long long*)step_fields, (unsigned long long*)track_fields);
+  DC_LAUNCHED("cc_track_fields");
   return 0;
 }

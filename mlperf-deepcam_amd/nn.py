@@ -1389,6 +1389,157 @@ class EventTracker:
         return out
 
 
+TRACK_STEP_FIELDS = ("track", "frame", "events", "pixels", "area", "sum_row", "sum_cx", "sum_sx")
+TRACK_FIELD_STATS = ("min", "min_pixel", "max", "max_pixel")
+
+
+class TrackFields:
+    """Storm life cycles on the device (dc_track_fields_append, dc_track_cycles, csrc/components.hip): the join of an EventTracker (which
+    events of which frames form one storm) and an EventFields of the same catalogue (every event's extremes and sums of the raw fields).
+    Per track and frame -- a STEP -- the field rows of the track's events in that frame merged into one (for a cyclone and sea-level
+    pressure the minimum's place is the conventional track position, its value the intensity), per track the lifetime extremes with the
+    frame and place where they occurred (include/deepcam_hip.h has the definitions).  The object owns the field store (int64 [event_cap,
+    C, 6]: 48 * C bytes per event slot next to the tracker's store, 403 MB at the tracker's default event_cap = 2^19 with 16 channels) and
+    the output tables: offsets int64 [track_cap], steps int64 [step_cap, 8] (TRACK_STEP_FIELDS), step_fields int64 [step_cap, C, 6]
+    (EVENT_FIELD_STATS), track_fields int64 [track_cap, C, 4] (TRACK_FIELD_STATS) and the four counters.  A call launches and neither
+    synchronises nor reads anything back; reset() and cut() are the tracker's -- the state follows its counters.  rows() / cycles() resolve
+    and read back only the filled parts."""
+
+    def __init__(self, tracker: "EventTracker", fields: EventFields, step_cap: Optional[int] = None):
+        if not isinstance(tracker, EventTracker) or not isinstance(fields, EventFields):
+            raise L.DeepcamHipError("TrackFields: needs an EventTracker and an EventFields")
+        if tracker.catalog is not fields.catalog:
+            raise L.DeepcamHipError("TrackFields: the tracker and the fields must be built on the same EventCatalog")
+        step_cap = tracker.event_cap if step_cap is None else int(step_cap)
+        if not 1 <= step_cap <= (1 << 31) - 1:
+            raise L.DeepcamHipError(f"TrackFields: step_cap must lie in [1, 2^31 - 1], got {step_cap}")
+        self.tracker, self.fields, self.C, self.step_cap = tracker, fields, fields.C, step_cap
+        dev = tracker._store.device
+        i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)  # noqa: E731
+        self._fstore = torch.empty((tracker.event_cap, self.C, len(EVENT_FIELD_STATS)), dtype=torch.int64, device=dev)
+        self._offsets = i64(tracker.track_cap)
+        self._steps = i64(step_cap, len(TRACK_STEP_FIELDS))
+        self._step_fields = i64(step_cap, self.C, len(EVENT_FIELD_STATS))
+        self._track_fields = i64(tracker.track_cap, self.C, len(TRACK_FIELD_STATS))
+        self._ncycles = i64(4)
+        self._ws = torch.empty(max(L.load().dc_track_cycles_workspace(tracker.event_cap, tracker.track_cap), 256), dtype=torch.uint8, device=dev)
+
+    def __call__(self) -> "TrackFields":
+        """Files the field rows of the batch the tracker and the fields were just called with (both, on this stream, before this)."""
+        trk, fld, cat = self.tracker, self.fields, self.tracker.catalog
+        nv = cat._last_valid
+        if nv < 1 or fld._last_valid != nv:
+            raise L.DeepcamHipError(f"TrackFields: call the tracker and the fields on the same batch first (the catalogue's last call had "
+                                    f"{nv} valid samples, the fields' {fld._last_valid})")
+        L.call("dc_track_fields_append", cat.B, nv, cat.cap, L.dptr(cat._ncomp), L.dptr(trk._first), L.dptr(fld._ftable), self.C, trk.event_cap,
+               L.dptr(self._fstore), L.stream_ptr())
+        return self
+
+    @staticmethod
+    def class_mask(classes) -> int:
+        mask = 0
+        for c in classes:
+            if int(c) not in (1, 2):
+                raise L.DeepcamHipError(f"TrackFields: classes are 1 and 2, got {c}")
+            mask |= 1 << int(c)
+        if mask == 0:
+            raise L.DeepcamHipError("TrackFields: no class selected")
+        return mask
+
+    def launch(self, min_frames: int = 1, classes=(1, 2)) -> "TrackFields":
+        """dc_track_resolve and dc_track_cycles on the current stream, for the frames given so far.  Does not synchronise."""
+        trk = self.tracker
+        trk.resolve()
+        L.call("dc_track_cycles", trk.event_cap, trk.track_cap, self.step_cap, self.C, max(int(min_frames), 0), self.class_mask(classes),
+               L.dptr(trk._state), L.dptr(trk._store), L.dptr(trk._track_of), L.dptr(trk._tracks), L.dptr(trk._ntracks), L.dptr(self._fstore),
+               L.dptr(self._offsets), L.dptr(self._steps), L.dptr(self._step_fields), L.dptr(self._track_fields), L.dptr(self._ncycles),
+               L.dptr(self._ws), L.stream_ptr())
+        return self
+
+    def rows(self, min_frames: int = 1, classes=(1, 2)) -> dict:
+        """launch(), then the counters and only the filled parts as numpy arrays: "counts" int64 [4] (tracks selected, step rows needed, step
+        rows stored, tracks selected but not stored), "tracks" int64 [m, 8], "offsets" int64 [m], "steps" int64 [n, 8], "step_fields" int64
+        [n, C, 6], "track_fields" int64 [m, C, 4], with m the tracker's stored track rows and n the stored step rows."""
+        self.launch(min_frames, classes)
+        counts = self._ncycles.cpu().numpy()
+        m, n = int(self.tracker._ntracks[3].item()), int(counts[2])
+        return {"counts": counts, "tracks": self.tracker._tracks[:m].cpu().numpy(), "offsets": self._offsets[:m].cpu().numpy(),
+                "steps": self._steps[:n].cpu().numpy(), "step_fields": self._step_fields[:n].cpu().numpy(),
+                "track_fields": self._track_fields[:m].cpu().numpy()}
+
+    def cycles(self, min_frames: int = 1, classes=(1, 2), center_channel: Optional[int] = None):
+        """The life cycles of the frames given so far as a list of dicts (decode)."""
+        r = self.rows(min_frames, classes)
+        cat = self.tracker.catalog
+        return self.decode(r["tracks"], r["offsets"], r["steps"], r["step_fields"], r["track_fields"], cat.H, cat.W, self.fields.bits,
+                           center_channel=center_channel)
+
+    @staticmethod
+    def decode(tracks, offsets, steps, step_fields, track_fields, height: int, width: int, bits, center_channel: Optional[int] = None):
+        """Track rows [m, 8] (TRACK_FIELDS), offsets [m], step rows [n, 8] (TRACK_STEP_FIELDS), their field rows [n, C, 6]
+        (EVENT_FIELD_STATS) and the lifetime rows [m, C, 4] (TRACK_FIELD_STATS) -> one dict per STORED track (offsets >= 0), in row order:
+        id, class, first_frame, last_frame, frames, events, pixels, peak_pixels, peak_frame, area_fraction_sum as EventTracker.decode gives
+        them; fields: per channel min, min_frame, min_row, min_col, min_lat, min_lon, the same for max (None where the track has no finite
+        value), mean = the step sums added in Python integers * 2^-bits / the pixels that took part (None without any) and nonfinite,
+        saturated; series: per frame of the track frame, events, pixels, the centroid lat / lon by EventCatalog.decode's formulas over the
+        summed columns, and fields: the EventFields.decode entries of the merged row.  With center_channel = c every series entry also
+        has center_lat / center_lon, the place of channel c's minimum (None where the step has no finite value).  Needs no GPU."""
+        bits = [int(v) for v in np.asarray(bits).reshape(-1)]
+        nch = len(bits)
+        tracks = np.asarray(tracks, np.int64).reshape(-1, len(TRACK_FIELDS))
+        offsets = np.asarray(offsets, np.int64).reshape(-1)
+        steps = np.asarray(steps, np.int64).reshape(-1, len(TRACK_STEP_FIELDS))
+        step_fields = np.asarray(step_fields, np.int64).reshape(-1, nch, len(EVENT_FIELD_STATS))
+        track_fields = np.asarray(track_fields, np.int64).reshape(-1, nch, len(TRACK_FIELD_STATS))
+        if center_channel is not None and not 0 <= int(center_channel) < nch:
+            raise L.DeepcamHipError(f"TrackFields: center_channel must lie in [0, {nch}), got {center_channel}")
+        lat, lon = np.linspace(-90.0, 90.0, height), np.linspace(-180.0, 180.0, width)
+        wy = event_weight_tables(height, width)[0]
+        whole = float(width) * float(wy.astype("int64").sum())
+        out = []
+        for t, row in enumerate(tracks.tolist()):
+            off = int(offsets[t])
+            if off < 0:
+                continue
+            tid, cls, nev, f0, f1, px, peak, area = row
+            peak &= 0xFFFFFFFFFFFFFFFF
+            st = steps[off:off + f1 - f0 + 1]
+            sf = step_fields[off:off + f1 - f0 + 1]
+            if len(st) != f1 - f0 + 1 or (st[:, 0] != t).any() or (st[:, 1] != np.arange(f0, f1 + 1)).any():
+                raise L.DeepcamHipError(f"TrackFields.decode: the step rows of track row {t} are not its frames {f0} .. {f1}")
+            # a step as one event row (EVENT_FIELDS): pixels, area and the centroid sums are the columns the decoders read
+            pseudo = np.zeros((len(st), len(EVENT_FIELDS)), np.int64)
+            pseudo[:, 1], pseudo[:, 2:7] = cls, st[:, 3:8]
+            per_step = EventFields.decode(sf, pseudo, height, width, bits)
+            series = []
+            for (_, f, n_ev, n, _a, sr, scx, ssx), per in zip(st.tolist(), per_step):
+                la = -90.0 + 180.0 * (sr / n) / (height - 1) if height > 1 and n > 0 else -90.0
+                entry = {"frame": f, "events": n_ev, "pixels": n, "lat": la, "lon": math.degrees(math.atan2(ssx, scx)), "fields": per}
+                if center_channel is not None:
+                    entry["center_lat"], entry["center_lon"] = per[int(center_channel)]["min_lat"], per[int(center_channel)]["min_lon"]
+                series.append(entry)
+            life = []
+            for ch, (wlo, plo, whi, phi) in enumerate(track_fields[t].tolist()):
+                total = sum(int(v) for v in sf[:, ch, 2])
+                nonfinite, saturated = int(sf[:, ch, 4].sum()), int(sf[:, ch, 5].sum())
+                n = px - nonfinite - saturated
+                d = {"nonfinite": nonfinite, "saturated": saturated, "mean": math.ldexp(float(total), -bits[ch]) / n if n > 0 else None}
+                for name, word, p, empty in (("min", wlo, plo, -1), ("max", whi, phi, 0)):
+                    if word == empty:
+                        d.update({name: None, name + "_frame": None, name + "_row": None, name + "_col": None, name + "_lat": None,
+                                  name + "_lon": None})
+                        continue
+                    word &= 0xFFFFFFFFFFFFFFFF
+                    frame = word & 0xFFFFFFFF if name == "min" else 0xFFFFFFFF - (word & 0xFFFFFFFF)
+                    d.update({name: float(event_field_value(np.uint32(word >> 32))), name + "_frame": frame, name + "_row": p // width,
+                              name + "_col": p % width, name + "_lat": float(lat[p // width]), name + "_lon": float(lon[p % width])})
+                life.append(d)
+            out.append({"id": tid, "class": cls, "first_frame": f0, "last_frame": f1, "frames": f1 - f0 + 1, "events": nev, "pixels": px,
+                        "peak_pixels": peak >> 32, "peak_frame": 0xFFFFFFFF - (peak & 0xFFFFFFFF),
+                        "area_fraction_sum": area / whole if whole > 0 else 0.0, "fields": life, "series": series})
+        return out
+
+
 class Predictor:
     """Masks for unlabelled data: the eval forward on a forward-only engine (Engine(forward_only=True): the net's weights and running
     statistics through the shared arena, pooled activations) whose classifier leaves, per pixel, the first-max class as one byte

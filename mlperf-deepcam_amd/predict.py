@@ -32,6 +32,15 @@ not detected from the names).  At the end of the run ``<output_dir>/tracks.h5`` 
 frame, last frame, pixels, peak, area), ``track_events`` (int64 [m, 13]: frame, rank, the ten columns of ``events``, the row of
 ``tracks`` or -1 -- with --min_event_pixels 0, (frame, rank) is row `rank` of the ``events`` and ``event_fields`` of file `frame`) and
 ``track_state`` (int64 [4]: events stored, frames, events dropped, frames with a truncated catalogue); ``summary.json`` gains ``tracks``.
+With --track_fields (which implies --tracks and --event_fields) nn.TrackFields files the field rows of every batch next to the tracker's
+store and joins the two on the device at the end of the run -- the storm life cycles: ``tracks.h5`` additionally holds
+``track_step_offsets`` (int64 [n]: per row of ``tracks`` the first of its step rows, -1 not selected by --min_track_frames, -2 beyond the
+step table), ``track_steps`` (int64 [s, 8]: row of ``tracks``, frame, events, and the summed pixels, area, sum of rows, sum of cx, sum of sx
+of the track's events in that frame), ``track_step_fields`` (int64 [s, C, 6]: their ``event_fields`` rows merged), ``track_fields`` (int64
+[n, C, 4]: per channel the lifetime minimum as (key << 32) | frame and its pixel, the maximum as (key << 32) | (0xFFFFFFFF - frame) and its
+pixel) and ``track_cycle_counts`` (int64 [4]: tracks selected, step rows needed, step rows stored, tracks left out); ``summary.json`` gains
+``track_fields`` (the counters, the cycles per class and, with --track_center_channel C, the deepest minimum of channel C over the
+class-1 tracks with its track id, frame, lat and lon -- for sea-level pressure the strongest cyclone of the run).
 Single process, single device."""
 from __future__ import annotations
 
@@ -83,6 +92,19 @@ class _Tracks(argparse.Action):
         namespace.events = True
 
 
+class _TrackFields(argparse.Action):
+    """--track_fields: implies --tracks, --event_fields and --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.track_fields = True
+        namespace.tracks = True
+        namespace.event_fields = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -114,10 +136,37 @@ def build_parser():
                     "runs are not detected).  Writes <output_dir>/tracks.h5 ('tracks', 'track_events', 'track_state'); 'tracks' in the summary")
     AP.add_argument("--min_track_frames", type=int, default=1, help="with --tracks: the summary also counts the tracks of at least N frames")
     AP.add_argument("--min_track_pixels", type=int, default=0, help="with --tracks: events of fewer pixels link nothing")
+    AP.add_argument("--track_fields", action=_TrackFields, help="the storm life cycles: per track and frame the merged field rows of its events, "
+                    "per track the lifetime extremes with frame and place (implies --tracks and --event_fields; --min_track_frames selects the "
+                    "cycles).  tracks.h5 gains 'track_step_offsets', 'track_steps', 'track_step_fields', 'track_fields', 'track_cycle_counts'; "
+                    "'track_fields' in the summary")
+    AP.add_argument("--track_center_channel", type=int, default=None, help="with --track_fields: the file channel whose minimum is a track's "
+                    "centre (sea-level pressure for cyclones); the summary names the deepest minimum over the class-1 tracks")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
     return AP
+
+
+def track_fields_summary(rows: dict, height: int, width: int, center_channel=None) -> dict:
+    """the `track_fields` entry of summary.json from nn.TrackFields.rows(): the four counters, the cycles per class and, with a centre
+    channel, the deepest lifetime minimum of that channel over the stored class-1 tracks (the smallest track row among equals)"""
+    counts = [int(v) for v in rows["counts"]]
+    tracks, stored = rows["tracks"], rows["offsets"] >= 0
+    out = {"tracks_selected": counts[0], "steps_needed": counts[1], "steps_stored": counts[2], "tracks_not_stored": counts[3],
+           "class_1": int((stored & (tracks[:, 1] == 1)).sum()), "class_2": int((stored & (tracks[:, 1] == 2)).sum())}
+    if center_channel is not None:
+        c = int(center_channel)
+        out["center_channel"], out["deepest_class_1"] = c, None
+        life = rows["track_fields"][:, c]
+        pick = np.flatnonzero(stored & (tracks[:, 1] == 1) & (life[:, 0] != -1))
+        if len(pick):
+            t = int(pick[int(np.argmin(life[pick, 0].view(np.uint64)))])
+            word, p = int(life[t, 0]) & 0xFFFFFFFFFFFFFFFF, int(life[t, 1])
+            out["deepest_class_1"] = {"id": int(tracks[t, 0]), "value": float(dnn.event_field_value(np.uint32(word >> 32))),
+                                      "frame": word & 0xFFFFFFFF, "lat": float(np.linspace(-90.0, 90.0, height)[p // width]),
+                                      "lon": float(np.linspace(-180.0, 180.0, width)[p % width])}
+    return out
 
 
 def write_mask_file(path: str, prediction: np.ndarray, confidence, events=None, extra=None) -> None:
@@ -318,6 +367,13 @@ def main(pargs) -> dict:
 
     # --tracks: behind the catalogue of every batch; the batches arrive in the order of the sorted names, one frame per file
     tracker = dnn.EventTracker(catalog, min_pixels=pargs.min_track_pixels) if getattr(pargs, "tracks", False) else None
+    # --track_fields: the field rows of every batch filed next to the tracker's store, joined with the tracks at the end of the run
+    tfields = center = None
+    if getattr(pargs, "track_fields", False):
+        center = getattr(pargs, "track_center_channel", None)
+        if center is not None and not 0 <= int(center) < efields.C:
+            raise ValueError(f"--track_center_channel must lie in [0, {efields.C}), got {center}")
+        tfields = dnn.TrackFields(tracker, efields)
 
     # --plots: one panel (the prediction), with --verify two (the prediction above the labels); the range is the stats file's
     renderer = None
@@ -357,6 +413,8 @@ def main(pargs) -> dict:
             if efields is not None:
                 efields(loader.raw, n_valid=nv)     # behind the catalogue's launches, on their stream
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
+            if tfields is not None:
+                tfields()
             slot.mask[:nv].copy_(mask, non_blocking=True)
             if slot.conf is not None:
                 slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
@@ -384,6 +442,7 @@ def main(pargs) -> dict:
         raise errors[0]
     verification = matcher.result() if verify else None
     track_rows = tracker.rows() if tracker is not None else None
+    cycle_rows = tfields.rows(min_frames=pargs.min_track_frames) if tfields is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -400,9 +459,15 @@ def main(pargs) -> dict:
         summary["event_verification"] = verification
     if track_rows is not None:
         t_state, t_store, t_of, t_tracks = track_rows
-        write_datasets(os.path.join(pargs.output_dir, "tracks.h5"),
-                       {"tracks": t_tracks, "track_events": np.concatenate([t_store, t_of.astype(np.int64)[:, None]], axis=1), "track_state": t_state})
+        arrays = {"tracks": t_tracks, "track_events": np.concatenate([t_store, t_of.astype(np.int64)[:, None]], axis=1), "track_state": t_state}
+        if cycle_rows is not None:
+            arrays.update({"track_step_offsets": cycle_rows["offsets"], "track_steps": cycle_rows["steps"],
+                           "track_step_fields": cycle_rows["step_fields"], "track_fields": cycle_rows["track_fields"],
+                           "track_cycle_counts": cycle_rows["counts"]})
+        write_datasets(os.path.join(pargs.output_dir, "tracks.h5"), arrays)
         summary["tracks"] = track_summary(t_state, t_tracks, pargs.min_track_frames)
+        if cycle_rows is not None:
+            summary["track_fields"] = track_fields_summary(cycle_rows, H, W, center)
     if renderer is not None:
         summary["plots"] = sum(1 for r in records if "plot" in r)
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
