@@ -80,6 +80,8 @@ int dc_reset_options(void);
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
  *     (colour table, graticule and outlines into the RGB bytes)
+ *   climatology (dc_climatology_accumulate, dc_climatology_maps): climatology_accumulate_vec (16-byte loads, four lanes per 16-channel
+ *     pixel), climatology_accumulate_scalar (any channel selection, and none), climatology_maps
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -838,6 +840,58 @@ int dc_render_frames(int B, int n_valid, int H, int W, const float* fields, int 
                      int nlut, const void* mask_a, int a_bytes, const void* mask_b /*may be NULL*/, int b_bytes, const int32_t* src_row,
                      int Ho, int shift, const uint8_t* row_line, const uint8_t* col_line, int missing_rgb, int line_argb, int class1_argb,
                      int class2_argb, int width, uint8_t* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Climatology (nn.Climatology; predict.py --climatology): the maps over time -- how often a grid point lies inside a cyclone or a river,
+ * what the raw fields are there when it does, and what share of a field's total the events account for.  The accumulators live in device
+ * memory from call to call, owned by the caller, who zeroes them to start.  Everything is an integer sum: the state after a sequence of
+ * frames does not depend on how the sequence was cut into batches, nor on the order of arrival.
+ *   G groups (1, 4 seasons, 12 months, ...), frames of H x W pixels, C >= 0 selected channels, bits[c] per selected channel
+ *   (nn.event_field_bits).
+ *   frames  int64 [G]               frames added to group g
+ *   count   int32 [G][2][H][W]      frames in which the pixel was class 1 / class 2
+ *   sum     int64 [G][3][H][W][C]   row 0 "all", row 1 "class 1", row 2 "class 2": the sum of q over the frames of that row
+ *   n       int32 [G][3][H][W][C]   how many values that sum holds
+ * dc_climatology_accumulate, one pass over a batch:
+ *   mask    [B][H][W] of 1-, 4- or 8-byte integers (mask_bytes, as dc_render_frames takes them): 1 and 2 are the classes, every other
+ *           value is background
+ *   fields  fp32 [B][H][W][ldc], channel-last, physical units; NULL exactly when C == 0 (then bits, chan, sum and n are not touched)
+ *   chan    int32 [C], device: the index of every selected channel among the ldc channels of a pixel; NULL: the first C channels in order
+ *   bits    int32 [C], device       group  int32 [B], device
+ * For frame b with g = group[b] in [0, G), pixel p, class k = mask[b][p] and channel value v = fields[b][p][chan[c]]:
+ *   frames[g] += 1, once per frame.  k in {1, 2}: count[g][k - 1][p] += 1.
+ *   q = rint(ldexp((double)v, bits[c])), ties to even (dc_component_fields' rule).  If v is finite and |q| <= 2^40:
+ *   sum[g][0][p][c] += q, n[g][0][p][c] += 1, and for k in {1, 2} the same into row k.  NaN, +-Inf and saturated values add nothing: they
+ *   show up as frames - n and count - n.
+ * A frame with group[b] < 0 is not read at all (padding samples, gaps, n_valid).  An index >= G is the caller's error (the table is on
+ * the device, the host cannot see it): such a frame is skipped as well rather than written out of bounds, and so is a chan entry outside
+ * [0, ldc).
+ * No atomics: one thread owns a pixel's channel (quad), walks the frames in order with its partial sums in registers and adds them to
+ * the accumulators once per run of equal group; every accumulator word has exactly one writer.  The "all" row is read-modified-written
+ * once per pixel and run, a class row only where the pixel had that class in the run.  With chan == NULL, ldc == C, C % 4 == 0 and
+ * fields, sum and n 16-byte aligned the fields are loaded 16 bytes per lane on consecutive addresses (C = 16: four lanes per pixel) and
+ * the accumulators move in 16-byte pieces; every other layout takes scalar loads.  All offsets into sum / n are 64-bit.
+ * 1 <= B <= 65535, H * W < 2^31, 1 <= G <= 65536, 0 <= C <= 32, ldc >= 1 (>= C with chan == NULL).  The caller keeps every group below
+ * 2^31 - 1 frames: then neither int32 count / n nor int64 sum (2^40 * 2^31 < 2^63) can overflow.
+ * dc_climatology_maps, called when maps are read or drawn: K products of the accumulators as fp32 [G][H][W][K] -- with ldc = K exactly
+ * what dc_render_frames takes as `fields` of a batch of G -- and a contour mask uint8 [G][H][W] for it to outline.
+ *   products  int32 [K][3], device: (0, k, -) the frequency of class k; (1, c, r) the mean of selected channel c in row r; (2, c, k) the
+ *             share of class k in selected channel c.  A triple that is none of these gives NaN.
+ *   frequency  (float)((double)count / (double)frames), 0 where frames == 0
+ *   mean       (float)(ldexp((double)sum, -bits[c]) / (double)n), NaN where n == 0
+ *   share      (float)((double)sum_k / (double)sum_all), NaN where sum_all == 0
+ *   The two roundings (the fp64 quotient, then fp32) are part of the definition; NaN is the word 0x7FC00000.
+ *   contour    1 where frequency_1 >= t1, else 2 where frequency_2 >= t2, else 0 (the fp32 frequencies above against fp32 thresholds)
+ *   1 <= K <= 256, G * H * W * K / 256 < 2^31.
+ * dc_climatology_block: the pixels one workgroup of the accumulate kernel covers (a host function; tests derive their shapes from it).
+ * Neither device call synchronises; both run on the caller's stream.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_climatology_block(int* pixels);
+int dc_climatology_accumulate(int B, int H, int W, int G, const void* mask, int mask_bytes, const float* fields /*NULL when C == 0*/, int C,
+                              int ldc, const int32_t* chan /*may be NULL*/, const int32_t* bits, const int32_t* group, int64_t* frames,
+                              int32_t* count, int64_t* sum, int32_t* n, void* stream);
+int dc_climatology_maps(int G, int H, int W, int C, const int64_t* frames, const int32_t* count, const int64_t* sum, const int32_t* n,
+                        const int32_t* bits, int K, const int32_t* products, float t1, float t2, float* out, uint8_t* contour, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

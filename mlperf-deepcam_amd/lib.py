@@ -178,6 +178,9 @@ _SIGS = {
     "dc_render_tile": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_render_workspace": (SZ, [I, I, I, I]),
     "dc_render_frames": (I, [I, I, I, I, P, I, I, F, F, P, I, P, I, P, I, P, I, I, P, P, I, I, I, I, I, P, P, P]),
+    "dc_climatology_block": (I, [C.POINTER(I)]),
+    "dc_climatology_accumulate": (I, [I, I, I, I, P, I, P, I, I, P, P, P, P, P, P, P, P]),
+    "dc_climatology_maps": (I, [I, I, I, I, P, P, P, P, P, I, P, F, F, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

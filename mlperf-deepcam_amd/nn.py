@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import re
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence
 
@@ -1763,3 +1765,204 @@ class FrameRenderer:
                self.shift, L.dptr(self._row_line), L.dptr(self._col_line), _c_int(c["missing"]), _c_int(c["line"]), _c_int(c["class1"]),
                _c_int(c["class2"]), self.outline, L.dptr(self._out), L.dptr(self._ws), L.stream_ptr())
         return self._out[:nv].view(nv, self.P * self.Ho, self.W, 3)
+
+
+# ---------------------------------------------------------------------------------------------- climatology: the maps over time
+CLIMATOLOGY_ROWS = ("all", "class1", "class2")
+CLIMATOLOGY_PRODUCTS = {"frequency": 0, "mean": 1, "share": 2}
+CLIMATOLOGY_MAX_FRAMES = (1 << 31) - 1
+CLIMATOLOGY_GROUPS = {"all": ("all",), "month": tuple(f"{m:02d}" for m in range(1, 13)), "season": ("DJF", "MAM", "JJA", "SON")}
+_SEASON_OF_MONTH = (0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 0)                      # DJF, MAM, JJA, SON
+_DATE = re.compile(r"(\d{4})-(\d{2})-(\d{2})")
+
+
+def climatology_group(name: str, by: str = "all") -> int:
+    """The group of a file from its base name: by = "all": 0; "month": 0 .. 11; "season": DJF, MAM, JJA, SON -> 0 .. 3 (December is season
+    0).  The date is the first YYYY-MM-DD in the name; a name without one (or with a month outside 1 .. 12) is an error unless by is
+    "all"."""
+    if by not in CLIMATOLOGY_GROUPS:
+        raise L.DeepcamHipError(f"climatology_group: by must be 'all', 'month' or 'season', got {by!r}")
+    if by == "all":
+        return 0
+    m = _DATE.search(os.path.basename(str(name)))
+    month = int(m.group(2)) if m else 0
+    if not 1 <= month <= 12:
+        raise L.DeepcamHipError(f"climatology_group: no YYYY-MM-DD date in {name!r}")
+    return month - 1 if by == "month" else _SEASON_OF_MONTH[month - 1]
+
+
+class Climatology:
+    """Occurrence and class-conditional field maps over time, accumulated on the device (dc_climatology_accumulate, dc_climatology_maps,
+    csrc/climatology.hip): per group (1, 4 seasons, 12 months) how many frames a pixel spent inside class 1 / class 2, and per selected
+    channel of the raw fields the sum and number of its values over all frames, over the class-1 frames and over the class-2 frames of the
+    pixel -- the frequency of cyclones and rivers, the mean field inside them, the share of a field's total they account for.
+    channels: indices into the ldc channels of a pixel (ldc defaults to the largest index + 1); bits: the sums' binary scale per SELECTED
+    channel (event_field_bits).  The object owns frames (int64 [G]), count (int32 [G, 2, H, W]), sum (int64 [G, 3, H, W, C]) and n (int32
+    [G, 3, H, W, C]); everything is an integer sum, so the state does not depend on how a sequence was cut into batches or ordered.
+    Memory: G * H * W * (8 + 36 * C) bytes -- 8 for the two counts, 3 * (8 + 4) per selected channel.  768 x 1152 with 16 channels and
+    one group: 884736 * 584 = 516.7 MB (12 months: 6.2 GB; without channels 7.1 MB per group).
+    A call launches on the current stream and does not synchronise; state() and maps() read back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, channels: Sequence[int] = (), bits=None, ldc: Optional[int] = None,
+                 groups: int = 1, device=None):
+        channels = [int(c) for c in channels]
+        C = len(channels)
+        if batch < 1 or batch > 65535 or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError("Climatology: batch must lie in [1, 65535], height and width be positive and height * width below 2^31")
+        if not 1 <= int(groups) <= 65536:
+            raise L.DeepcamHipError(f"Climatology: groups must lie in [1, 65536], got {groups}")
+        if C > 32:
+            raise L.DeepcamHipError(f"Climatology: at most 32 channels, got {C}")
+        ldc = int((max(channels) + 1 if C else 0) if ldc is None else ldc)
+        if C and (min(channels) < 0 or max(channels) >= ldc):
+            raise L.DeepcamHipError(f"Climatology: channels must lie in [0, {ldc}), got {channels}")
+        bits = [] if bits is None else [int(v) for v in np.asarray(bits).reshape(-1)]
+        if len(bits) != C:
+            raise L.DeepcamHipError(f"Climatology: {len(bits)} scale bits for {C} channels")
+        self.B, self.H, self.W, self.C, self.ldc, self.G = batch, height, width, C, ldc, int(groups)
+        self.channels, self.bits = channels, bits
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._frames = torch.zeros((self.G,), dtype=torch.int64, device=dev)
+        dev = self.device = self._frames.device
+        self._count = torch.zeros((self.G, 2, height, width), dtype=torch.int32, device=dev)
+        self._sum = torch.zeros((self.G, 3, height, width, C), dtype=torch.int64, device=dev) if C else None
+        self._n = torch.zeros((self.G, 3, height, width, C), dtype=torch.int32, device=dev) if C else None
+        self._bits = torch.tensor(bits, dtype=torch.int32, device=dev) if C else None
+        # the identity over all ldc channels travels as a null table: the library then knows it on the host and may take its 16-byte loads
+        self._chan = None if channels == list(range(ldc)) else torch.tensor(channels, dtype=torch.int32, device=dev)
+        self._tables = {}                            # group tuple -> device int32 [B]: a time-sorted sequence produces few distinct ones
+        self._products = {}                          # product tuple -> (device int32 [K, 3], out fp32 [G, H, W, K], contour uint8 [G, H, W])
+        self.host_frames = [0] * self.G              # the device's `frames`, counted here too: the overflow bound needs no read-back
+
+    def _group_table(self, groups, n_valid) -> tuple:
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"Climatology: n_valid must lie in [0, {self.B}], got {n_valid}")
+        if groups is None or isinstance(groups, (int, np.integer)):
+            table = [0 if groups is None else int(groups)] * self.B
+        else:
+            table = [int(g) for g in groups]
+            if len(table) != self.B:
+                raise L.DeepcamHipError(f"Climatology: {len(table)} groups for a batch of {self.B}")
+        table = tuple(g if j < nv and g >= 0 else -1 for j, g in enumerate(table))
+        if any(g >= self.G for g in table):
+            raise L.DeepcamHipError(f"Climatology: group indices must be below {self.G}, got {list(table)}")
+        return table
+
+    def __call__(self, mask: torch.Tensor, fields: Optional[torch.Tensor] = None, groups=None, n_valid: Optional[int] = None) -> "Climatology":
+        """mask: contiguous device uint8, int32 or int64 [B, H, W]; fields: contiguous device fp32 [B, H, W, ldc] in physical units
+        (InputPipeline.raw), given exactly when channels were selected; groups: None (every frame to group 0), an int, or B ints, a
+        negative one skipping its frame; frames from n_valid on are skipped."""
+        if mask.dtype not in self._BYTES or tuple(mask.shape) != (self.B, self.H, self.W) or not mask.is_cuda or mask.device != self.device \
+                or not mask.is_contiguous():
+            raise L.DeepcamHipError(f"Climatology: mask must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] on "
+                                    f"{self.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        if (fields is None) != (self.C == 0):
+            raise L.DeepcamHipError(f"Climatology: built for {self.C} channel(s): fields are given exactly when there are some")
+        if fields is not None:
+            want = (self.B, self.H, self.W, self.ldc)
+            if fields.dtype != torch.float32 or tuple(fields.shape) != want or not fields.is_cuda or fields.device != self.device \
+                    or not fields.is_contiguous():
+                raise L.DeepcamHipError(f"Climatology: fields must be a contiguous fp32 tensor {list(want)} on {self.device}, got "
+                                        f"{fields.dtype} {tuple(fields.shape)} on {fields.device}")
+        table = self._group_table(groups, n_valid)
+        added = [0] * self.G
+        for g in table:
+            if g >= 0:
+                added[g] += 1
+        if any(h + a > CLIMATOLOGY_MAX_FRAMES for h, a in zip(self.host_frames, added)):
+            raise L.DeepcamHipError(f"Climatology: a group would pass {CLIMATOLOGY_MAX_FRAMES} frames, the bound of the int32 counts")
+        if not any(added):
+            return self
+        dev_table = self._tables.get(table)
+        if dev_table is None:
+            dev_table = self._tables[table] = torch.tensor(table, dtype=torch.int32, device=self.device)
+        L.call("dc_climatology_accumulate", self.B, self.H, self.W, self.G, L.dptr(mask), self._BYTES[mask.dtype], L.dptr(fields), self.C,
+               max(self.ldc, 1), L.dptr(self._chan), L.dptr(self._bits), L.dptr(dev_table), L.dptr(self._frames), L.dptr(self._count),
+               L.dptr(self._sum), L.dptr(self._n), L.stream_ptr())
+        self.host_frames = [h + a for h, a in zip(self.host_frames, added)]
+        return self
+
+    def reset(self) -> None:
+        """zeroes the accumulators (in stream order)"""
+        for t in (self._frames, self._count, self._sum, self._n):
+            if t is not None:
+                t.zero_()
+        self.host_frames = [0] * self.G
+
+    def state(self) -> dict:
+        """the four accumulators on the host: frames int64 [G], count int32 [G, 2, H, W], sum int64 / n int32 [G, 3, H, W, C]"""
+        empty = (self.G, 3, self.H, self.W, 0)
+        return {"frames": self._frames.cpu().numpy(), "count": self._count.cpu().numpy(),
+                "sum": self._sum.cpu().numpy() if self.C else np.zeros(empty, np.int64),
+                "n": self._n.cpu().numpy() if self.C else np.zeros(empty, np.int32)}
+
+    def product_table(self, products) -> np.ndarray:
+        """int32 [K, 3] of products given as ("frequency", k), ("mean", c, row) or ("share", c, k): k the class 1 or 2, c the POSITION of
+        a selected channel, row 0 / 1 / 2 or a name of CLIMATOLOGY_ROWS"""
+        out = []
+        for prod in products:
+            kind, args = prod[0], list(prod[1:])
+            if kind not in CLIMATOLOGY_PRODUCTS or len(args) != (1 if kind == "frequency" else 2):
+                raise L.DeepcamHipError(f"Climatology: a product is ('frequency', k), ('mean', c, row) or ('share', c, k), got {prod!r}")
+            if kind == "mean" and args[1] in CLIMATOLOGY_ROWS:
+                args[1] = CLIMATOLOGY_ROWS.index(args[1])
+            args = [int(a) for a in args] + [0] * (2 - len(args))
+            ok = args[0] in (1, 2) if kind == "frequency" else 0 <= args[0] < self.C and (0 <= args[1] < 3 if kind == "mean" else args[1] in (1, 2))
+            if not ok:
+                raise L.DeepcamHipError(f"Climatology: product {prod!r} names a class, channel position or row that does not exist")
+            out.append([CLIMATOLOGY_PRODUCTS[kind]] + args)
+        if not 1 <= len(out) <= 256:
+            raise L.DeepcamHipError(f"Climatology: between 1 and 256 products, got {len(out)}")
+        return np.asarray(out, np.int32)
+
+    def fields(self, products, t1: float = 0.1, t2: float = 0.1):
+        """(fp32 [G, H, W, K], uint8 [G, H, W]) on the device, from dc_climatology_maps on the current stream, not synchronised: the
+        products as the channels of a FrameRenderer(batch=G, ldc=K) input, and the contour mask (1 where the class-1 frequency >= t1, else
+        2 where the class-2 frequency >= t2).  Both are buffers of the object, overwritten by the next call with the same products."""
+        key = tuple(tuple(p) for p in products)
+        if key not in self._products:
+            table = self.product_table(products)
+            self._products[key] = (torch.from_numpy(table).to(self.device),
+                                   torch.empty((self.G, self.H, self.W, len(table)), dtype=torch.float32, device=self.device),
+                                   torch.empty((self.G, self.H, self.W), dtype=torch.uint8, device=self.device))
+        table, out, contour = self._products[key]
+        L.call("dc_climatology_maps", self.G, self.H, self.W, self.C, L.dptr(self._frames), L.dptr(self._count), L.dptr(self._sum),
+               L.dptr(self._n), L.dptr(self._bits), len(table), L.dptr(table), float(np.float32(t1)), float(np.float32(t2)), L.dptr(out),
+               L.dptr(contour), L.stream_ptr())
+        return out, contour
+
+    def maps(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(s["frames"], s["count"], s["sum"], s["n"], self.bits, self.H, self.W)
+
+    @staticmethod
+    def occurrence(frames, count, height: int, width: int) -> dict:
+        """decode()'s frequency, zonal_frequency and area_frequency, which need the counts alone"""
+        frames = np.asarray(frames, np.int64).reshape(-1)
+        count = np.asarray(count, np.int64).reshape(len(frames), 2, height, width)
+        fr = frames.astype(np.float64)
+        div = lambda a, b: np.where(b != 0, a / np.where(b != 0, b, 1), np.nan)  # noqa: E731
+        rows = count.sum(axis=3)                                                # int64 [G, 2, H]
+        wy = event_weight_tables(height, width)[0].astype(np.int64)
+        return {"frequency": div(count.astype(np.float64), fr[:, None, None, None]),
+                "zonal_frequency": div(rows.astype(np.float64), fr[:, None, None] * width),
+                "area_frequency": div((rows * wy).sum(axis=2).astype(np.float64), fr[:, None] * (float(width) * float(wy.sum())))}
+
+    @staticmethod
+    def decode(frames, count, sum, n, bits, height: int, width: int) -> dict:
+        """float64 maps from the raw integers, NaN where a divisor is zero: frequency [G, 2, H, W] = count / frames; mean [G, 3, H, W, C]
+        = sum * 2^-bits / n; share [G, 2, H, W, C] = sum of class k / sum of all; zonal_frequency [G, 2, H], the mean frequency of a row;
+        area_frequency [G, 2], the cos(lat)-weighted mean frequency with event_weight_tables' integer wy: sum_r wy[r] * (count summed
+        along the row) / (frames * W * sum_r wy[r]) -- the share of the globe's area and time spent inside the class."""
+        out = Climatology.occurrence(frames, count, height, width)
+        G, C = len(out["area_frequency"]), len(np.asarray(bits).reshape(-1))
+        total = np.asarray(sum, np.int64).reshape(G, 3, height, width, C).astype(np.float64)
+        n = np.asarray(n, np.int64).reshape(G, 3, height, width, C)
+        div = lambda a, b: np.where(b != 0, a / np.where(b != 0, b, 1), np.nan)  # noqa: E731
+        scaled = np.ldexp(total, -np.asarray(bits, np.int32).reshape(-1)) if C else total
+        out.update(mean=div(scaled, n.astype(np.float64)), share=div(total[:, 1:], total[:, :1]))
+        return out

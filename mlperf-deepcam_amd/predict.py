@@ -41,6 +41,15 @@ of the track's events in that frame), ``track_step_fields`` (int64 [s, C, 6]: th
 pixel) and ``track_cycle_counts`` (int64 [4]: tracks selected, step rows needed, step rows stored, tracks left out); ``summary.json`` gains
 ``track_fields`` (the counters, the cycles per class and, with --track_center_channel C, the deepest minimum of channel C over the
 class-1 tracks with its track id, frame, lat and lon -- for sea-level pressure the strongest cyclone of the run).
+With --climatology nn.Climatology accumulates, behind every batch and on the device, the maps over time: per group (--climatology_by all,
+month or season, from the first YYYY-MM-DD in a file's name) how often every pixel was predicted class 1 / class 2 and, per file channel
+of --climatology_channels, the sum and number of its values over all frames, the class-1 frames and the class-2 frames of the pixel.  At
+the end of the run ``<output_dir>/climatology.h5`` holds the raw integers ``frames`` (int64 [G]), ``count`` (int32 [G, 2, H, W]), ``sum``
+(int64 [G, 3, H, W, C]), ``n`` (int32 [G, 3, H, W, C]), ``bits`` and ``channels`` (int32 [C]) -- the datasets of two runs add exactly, and
+nn.Climatology.decode turns them into frequencies, means and shares --, with --verify also ``truth_count``, ``truth_sum``, ``truth_n`` of
+the files' labels; ``summary.json`` gains ``climatology`` (the groups, their frames, the area-weighted frequency per class and group).
+With --plots ``plots/climatology-<group>-class<k>.png`` shows, for every group that received a frame, the frequency of class k across
+[0, 1] with the region of frequency >= --climatology_contour outlined (with --verify above the same picture of the labels).
 Single process, single device."""
 from __future__ import annotations
 
@@ -142,6 +151,15 @@ def build_parser():
                     "'track_fields' in the summary")
     AP.add_argument("--track_center_channel", type=int, default=None, help="with --track_fields: the file channel whose minimum is a track's "
                     "centre (sea-level pressure for cyclones); the summary names the deepest minimum over the class-1 tracks")
+    AP.add_argument("--climatology", action="store_true", help="accumulate the maps over time on the device: how often every pixel is class 1 / "
+                    "class 2, and the sums of the --climatology_channels over all, class-1 and class-2 frames.  Writes <output_dir>/climatology.h5 "
+                    "('frames', 'count', 'sum', 'n', 'bits', 'channels'; with --verify also the labels' 'truth_count', 'truth_sum', 'truth_n'); "
+                    "'climatology' in the summary; with --plots one frequency map per group and class")
+    AP.add_argument("--climatology_by", type=str, default="all", choices=list(dnn.CLIMATOLOGY_GROUPS), help="with --climatology: one set of "
+                    "maps for the whole run, per month or per season (DJF, MAM, JJA, SON), from the first YYYY-MM-DD in every file name")
+    AP.add_argument("--climatology_channels", type=int, nargs="*", default=[], help="with --climatology: the file channels whose sums are "
+                    "kept (36 bytes per pixel, group and channel); none by default: occurrence only")
+    AP.add_argument("--climatology_contour", type=float, default=0.1, help="with --climatology and --plots: the frequency whose region is outlined")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -166,6 +184,37 @@ def track_fields_summary(rows: dict, height: int, width: int, center_channel=Non
             out["deepest_class_1"] = {"id": int(tracks[t, 0]), "value": float(dnn.event_field_value(np.uint32(word >> 32))),
                                       "frame": word & 0xFFFFFFFF, "lat": float(np.linspace(-90.0, 90.0, height)[p // width]),
                                       "lon": float(np.linspace(-180.0, 180.0, width)[p % width])}
+    return out
+
+
+def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
+    """the `climatology` entry of summary.json: the groups' names and frames and, per class, the area-weighted frequency of every group
+    (None for a group without a frame); with --verify the same of the labels"""
+    clean = lambda a: [None if np.isnan(v) else float(v) for v in a]  # noqa: E731
+    out = {"by": by, "groups": list(dnn.CLIMATOLOGY_GROUPS[by]), "frames": [int(v) for v in frames], "channels": [int(c) for c in channels],
+           "area_frequency": {f"class_{k + 1}": clean(maps["area_frequency"][:, k]) for k in range(2)}}
+    if truth_maps is not None:
+        out["truth_area_frequency"] = {f"class_{k + 1}": clean(truth_maps["area_frequency"][:, k]) for k in range(2)}
+    return out
+
+
+def climatology_plot_name(group: str, cls: int) -> str:
+    return f"climatology-{group}-class{cls}.png"
+
+
+def climatology_pictures(clim, truth, contour: float, by: str) -> dict:
+    """file name -> uint8 [rows, W, 3]: per group with a frame and per class the frequency map across [0, 1] through nn.FrameRenderer, the
+    region of frequency >= contour outlined; with `truth` (the labels' climatology) the labels' picture below it"""
+    renderer = dnn.FrameRenderer(clim.G, clim.H, clim.W, channel=0, ldc=1, lo=0.0, hi=1.0, panels=1, device=clim.device)
+    names = dnn.CLIMATOLOGY_GROUPS[by]
+    never = float("inf")
+    out = {}
+    for cls in (1, 2):
+        t = (contour, never) if cls == 1 else (never, contour)
+        panels = [renderer(*c.fields([("frequency", cls)], *t)).cpu().numpy() for c in ([clim] if truth is None else [clim, truth])]
+        for g, name in enumerate(names):
+            if clim.host_frames[g]:
+                out[climatology_plot_name(name, cls)] = np.concatenate([p[g] for p in panels], axis=0)
     return out
 
 
@@ -385,6 +434,18 @@ def main(pargs) -> dict:
         os.makedirs(os.path.join(pargs.output_dir, "plots"), exist_ok=True)
         renderer = dnn.FrameRenderer(B, H, W, channel=pc, ldc=loader.cfile, lo=float(dataset.minval[pc]), hi=float(dataset.maxval[pc]),
                                      panels=2 if verify else 1, device=device)
+    # --climatology: behind every batch; the groups come from the files' names
+    clim = clim_truth = None
+    if getattr(pargs, "climatology", False):
+        clim_by = pargs.climatology_by
+        clim_channels = [int(c) for c in pargs.climatology_channels]
+        if any(not 0 <= c < loader.cfile for c in clim_channels) or len(clim_channels) > 32:
+            raise ValueError(f"--climatology_channels: at most 32 file channels in [0, {loader.cfile}), got {clim_channels}")
+        all_bits = dnn.event_field_bits(dataset.minval, dataset.maxval)
+        clim_bits = [int(all_bits[c]) for c in clim_channels]
+        make = lambda: dnn.Climatology(B, H, W, channels=clim_channels, bits=clim_bits, ldc=loader.cfile,  # noqa: E731
+                                       groups=len(dnn.CLIMATOLOGY_GROUPS[clim_by]), device=device)
+        clim, clim_truth = make(), make() if verify else None
     seen = 0                                       # input files so far, in the order the batches arrive (sorted names)
 
     free_q: "queue.Queue" = queue.Queue()
@@ -415,6 +476,12 @@ def main(pargs) -> dict:
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
             if tfields is not None:
                 tfields()
+            if clim is not None:
+                groups = [dnn.climatology_group(name, clim_by) for name in names] + [-1] * (B - nv)
+                raw = loader.raw if clim.C else None
+                clim(predictor.mask_buffer, raw, groups=groups, n_valid=nv)
+                if clim_truth is not None:
+                    clim_truth(y, raw, groups=groups, n_valid=nv)
             slot.mask[:nv].copy_(mask, non_blocking=True)
             if slot.conf is not None:
                 slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
@@ -443,6 +510,7 @@ def main(pargs) -> dict:
     verification = matcher.result() if verify else None
     track_rows = tracker.rows() if tracker is not None else None
     cycle_rows = tfields.rows(min_frames=pargs.min_track_frames) if tfields is not None else None
+    clim_state = clim.state() if clim is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -470,6 +538,21 @@ def main(pargs) -> dict:
             summary["track_fields"] = track_fields_summary(cycle_rows, H, W, center)
     if renderer is not None:
         summary["plots"] = sum(1 for r in records if "plot" in r)
+    if clim is not None:
+        arrays = dict(clim_state, bits=np.asarray(clim.bits, np.int32), channels=np.asarray(clim.channels, np.int32))
+        truth_maps = None
+        if clim_truth is not None:
+            truth_state = clim_truth.state()
+            arrays.update({"truth_" + k: truth_state[k] for k in ("count", "sum", "n")})
+            truth_maps = dnn.Climatology.occurrence(truth_state["frames"], truth_state["count"], H, W)
+        write_datasets(os.path.join(pargs.output_dir, "climatology.h5"), arrays)
+        maps = dnn.Climatology.occurrence(clim_state["frames"], clim_state["count"], H, W)
+        summary["climatology"] = climatology_summary(clim_by, clim_state["frames"], maps, truth_maps, clim.channels)
+        if getattr(pargs, "plots", False):
+            pictures = climatology_pictures(clim, clim_truth, float(pargs.climatology_contour), clim_by)
+            for name, rgb in pictures.items():
+                png.write_png(os.path.join(pargs.output_dir, "plots", name), rgb)
+            summary["climatology"]["plots"] = sorted(pictures)
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     line = {"samples": len(records), "class_counts": totals, "seconds": round(elapsed, 4),
