@@ -76,6 +76,7 @@ int dc_reset_options(void);
  *     tile borders and the seam, root + 1 into every pixel), cc_stats (every launch of the statistics call)
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
+ *   event shapes and the shape filter (dc_component_shape, dc_event_select, dc_mask_select): cc_shape (every launch of the three calls)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
@@ -702,6 +703,59 @@ int dc_event_scores(int B, int n_valid, int cap_a, const int64_t* table_a, const
 int dc_component_fields_lds_slots(int* slots);
 int dc_component_fields(int B, int n_valid, int H, int W, const int32_t* labels, const int32_t* rank_map, int cap, const float* fields,
                         int C, int ldc, const int32_t* scale_bits, const int32_t* wy, int64_t* ftable, void* stream);
+
+/* Event shapes (nn.EventShape; predict.py --event_shape): one row of geometry per event of a catalogue -- what tells a long narrow
+ * atmospheric river from a compact cyclone -- from exact integer sums in one pass over the label map.
+ *   labels, rank_map, cap   as dc_component_fields takes them; wrap: the catalogue's flag
+ *   row_tables  int32 [6][H]: wy, rc2, rcs, rc3, rc2s, rcs2     col_tables  int32 [5][W]: cx, sx, cxx, cxy, cyy
+ *               (nn.event_shape_tables.  With cl = cos lat, sl = sin lat at the latitudes of nn.event_weight_tables and co = cos lon,
+ *               so = sin lon at lon_c = -180 + 360 c / W degrees, each 2^20-scaled and rounded as wy is:  wy = cl, rc2 = cl^2,
+ *               rcs = cl sl, rc3 = cl^3, rc2s = cl^2 sl, rcs2 = cl sl^2;  cx = co, sx = so, cxx = co^2, cxy = co so, cyy = so^2.
+ *               The columns are a PERIODIC grid, column W-1 one step west of column 0 as `wrap` has it, so a shape rolled across the
+ *               seam keeps its moments; the catalogue's own cx / sx, at linspace(-180, 180, W), hold the seam meridian twice.)
+ *   shape       int64 [B][cap][12], zeroed by the call for the samples below n_valid; row k belongs to the event of rank k (row k of
+ *               dc_component_stats), events of rank >= cap have no row.  With "not of the same component" meaning: a different label
+ *               word (background or another event), or off the grid -- rows are never periodic; columns are with wrap = 1 (column W-1 is
+ *               column 0's left neighbour), otherwise off the grid too.  Only the four edge neighbours make faces, under 8-connectivity too.
+ *     0      boundary pixels: pixels of the event with at least one 4-neighbour that is not of the same component
+ *     1      exposed vertical faces: (pixel, left-or-right neighbour) pairs whose neighbour is not of the same component
+ *     2      exposed horizontal faces, weighted: sum of wy[r] over (pixel, upper-or-lower neighbour) pairs whose neighbour is not of the
+ *            same component
+ *     3-5    S_x = sum rc2[r] cx[c],  S_y = sum rc2[r] sx[c],  S_z = sum rcs[r] 2^20
+ *     6-11   S_xx = sum rc3[r] cxx[c],  S_xy = sum rc3[r] cxy[c],  S_yy = sum rc3[r] cyy[c],  S_xz = sum rc2s[r] cx[c],
+ *            S_yz = sum rc2s[r] sx[c],  S_zz = sum rcs2[r] 2^20
+ *   A pixel is the unit vector u = (cl co, cl so, sl) with weight cl: fields 3-11 are the 2^40-scaled first and second moments
+ *   sum w u and sum w u u^T on the sphere; the 2^40-scaled zeroth moment is field 3 of the catalogue's row times 2^20.  Nothing depends on
+ *   a column anchor, so an event across the seam is no special case.  Every per-pixel term is below 2^40 in magnitude and H * W <= 2^22
+ *   (refused otherwise): every sum fits an int64, is exact and independent of the order of arrival.
+ *   The decode (nn.EventShape.decode; dc_event_select evaluates lambda+- in fp64): with S0 the zeroth moment, m = S1 / S0,
+ *   C = S2 / S0 - m m^T, c = m / |m| ((1, 0, 0) when |m| = 0), lat = asin c_z, lon = atan2(c_y, c_x), e = (-sin lon, cos lon, 0),
+ *   n = (-sin lat cos lon, -sin lat sin lon, cos lat), a = e^T C e, b = e^T C n, d = n^T C n,
+ *   lambda+- = (a + d) / 2 +- sqrt(((a - d) / 2)^2 + b^2), clamped at 0.  sqrt(12 lambda+-) are the sides of the uniform strip with these
+ *   second moments in chord space; nn.EventShape turns 12 lambda+ into the angle of the great-circle arc with that moment
+ *   (6 (1 - sin t / t) = 12 lambda+), and nn.EventFilter.length_units a length in km into min_len2 the same way.
+ * Samples from n_valid on are neither read nor written.  Does not synchronise; reads what dc_mask_components and dc_component_stats left
+ * on the same stream.
+ *
+ * The filter (nn.EventFilter; predict.py --event_filter).  dc_event_select, one thread per event row:
+ *   table, ncomp  as dc_component_stats leaves them; shape as dc_component_shape leaves it
+ *   criteria  device, 8-byte aligned: two rows, class 1 then class 2, each { int64 min_pixels, int64 min_area (units of the catalogue's
+ *             field 3), double min_len2, double min_aspect2 }
+ *   An event of class k in {1, 2} with a row (rank < min(ncomp all, cap)) is KEPT iff  pixels >= min_pixels[k]  and  area >= min_area[k]
+ *   and  12 lambda+ >= min_len2[k]  and  lambda+ >= min_aspect2[k] lambda-.  A criterion of 0 is off; an event whose zeroth moment is 0
+ *   fails every active shape criterion (the last two).
+ *   keep    uint8 [B][cap]: 1 for a kept event, 0 for a dropped one and for rows without an event
+ *   counts  int64 [B][8], zeroed by the call for the samples below n_valid: per class (1, then 2) events kept, events dropped, pixels
+ *           kept, pixels dropped; this call fills the events, dc_mask_select adds the pixels
+ * dc_mask_select, one streaming pass: out_mask[p] = mask[p] where mask[p] is background or >= 3; for a pixel of class 1 or 2 its class
+ * iff its event is kept or has no row (rank >= cap: no criterion was evaluated, ncomp tells the caller), 0 otherwise.  out_mask may not
+ * alias mask.  Samples from n_valid on are neither read nor written, in either call; neither synchronises. */
+int dc_component_shape(int B, int n_valid, int H, int W, const int32_t* labels, const int32_t* rank_map, int cap, int wrap,
+                       const int32_t* row_tables, const int32_t* col_tables, int64_t* shape, void* stream);
+int dc_event_select(int B, int n_valid, int cap, const int64_t* table, const int32_t* ncomp, const int64_t* shape, const void* criteria,
+                    uint8_t* keep, int64_t* counts, void* stream);
+int dc_mask_select(int B, int n_valid, int H, int W, const uint8_t* mask, const int32_t* labels, const int32_t* rank_map, int cap,
+                   const uint8_t* keep, uint8_t* out_mask, int64_t* counts, void* stream);
 
 /* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
  * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in

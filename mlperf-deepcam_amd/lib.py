@@ -168,6 +168,9 @@ _SIGS = {
     "dc_event_scores": (I, [I, I, I, P, P, P, I, P, P, P, P, L, I, P, P, P]),
     "dc_component_fields_lds_slots": (I, [C.POINTER(I)]),
     "dc_component_fields": (I, [I, I, I, I, P, P, I, P, I, I, P, P, P, P]),
+    "dc_component_shape": (I, [I, I, I, I, P, P, I, I, P, P, P, P]),
+    "dc_event_select": (I, [I, I, I, P, P, P, P, P, P, P]),
+    "dc_mask_select": (I, [I, I, I, I, P, P, P, I, P, P, P, P]),
     "dc_track_workspace": (SZ, [I]),
     "dc_track_append": (I, [I, I, I, P, P, L, I, P, P, P, P, P]),
     "dc_track_link": (I, [I, I, I, P, P, P, P, P, P, P, P, I, I, L, P, P, P]),

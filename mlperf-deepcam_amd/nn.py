@@ -1245,6 +1245,286 @@ class EventFields:
         return out
 
 
+EVENT_SHAPE_FIELDS = ("boundary_pixels", "faces_v", "faces_h", "s_x", "s_y", "s_z", "s_xx", "s_xy", "s_yy", "s_xz", "s_yz", "s_zz")
+EVENT_SHAPE_VALUES = ("lat", "lon", "length_km", "width_km", "aspect", "orientation_deg", "perimeter_km", "area_km2", "compactness",
+                      "boundary_pixels")
+EVENT_FILTER_COUNTS = ("events_kept", "events_dropped", "pixels_kept", "pixels_dropped")
+EARTH_RADIUS_KM = 6371.0
+
+
+def event_shape_tables(height: int, width: int):
+    """(rows int32 [6, H]: wy, rc2, rcs, rc3, rc2s, rcs2; cols int32 [5, W]: cx, sx, cxx, cxy, cyy) -- the tables of dc_component_shape.
+    With cl / sl the cosine / sine of a row's latitude and co / so of a column's longitude: cl, cl^2, cl sl, cl^3, cl^2 sl, cl sl^2 and
+    co, so, co^2, co so, so^2, each evaluated in float64, scaled by 2^20 and rounded to nearest (ties to even).  The latitudes are those
+    of event_weight_tables (rows[0] is its wy).  The longitudes are the W columns of a PERIODIC grid, lon_c = -180 + 360 c / W: column
+    W - 1 is one step west of column 0, as `wrap` has it, so a shape rolled across the seam keeps its moments.  event_weight_tables'
+    linspace(-180, 180, W) holds the seam meridian twice (columns 0 and W - 1) and is left as it is for the catalogue."""
+    lat = np.deg2rad(np.linspace(-90.0, 90.0, height))
+    lon = np.deg2rad(-180.0 + 360.0 * np.arange(width) / width)
+    cl, sl, co, so = np.cos(lat), np.sin(lat), np.cos(lon), np.sin(lon)
+    q = lambda v: np.rint(v * EVENT_SCALE).astype(np.int32)  # noqa: E731
+    rows = np.stack([q(cl), q(cl * cl), q(cl * sl), q(cl * cl * cl), q(cl * cl * sl), q(cl * sl * sl)])
+    cols = np.stack([q(co), q(so), q(co * co), q(co * so), q(so * so)])
+    return np.ascontiguousarray(rows), np.ascontiguousarray(cols)
+
+
+class EventShape:
+    """Geometry per event on the device (dc_component_shape, csrc/components.hip): boundary pixels, perimeter faces, and the first and
+    second moments of the event's pixels as area-weighted unit vectors on the sphere, all exact integer sums (EVENT_SHAPE_FIELDS; the
+    header has the definition).  decode turns them into a spherical centroid, the length and width of the uniform strip with the same
+    second moments, aspect, orientation, perimeter and compactness.  Built on an existing EventCatalog, as EventFields is; a call must
+    follow the catalogue's call on the same stream, launches and does not synchronise.  The object owns the tables and the shape rows
+    (int64 [B, cap, 12]: 96 bytes per event slot; row k belongs to row k of the catalogue's table)."""
+
+    def __init__(self, catalog: EventCatalog):
+        if catalog.H * catalog.W > 1 << 22:
+            raise L.DeepcamHipError("EventShape: H * W must be at most 2^22")
+        self.catalog = catalog
+        dev = catalog._labels.device
+        self.tables = event_shape_tables(catalog.H, catalog.W)
+        self._rowt, self._colt = (torch.from_numpy(t).to(dev) for t in self.tables)
+        self._shape = torch.zeros((catalog.B, catalog.cap, len(EVENT_SHAPE_FIELDS)), dtype=torch.int64, device=dev)
+        self._last_valid = 0
+
+    def __call__(self, n_valid: Optional[int] = None) -> "EventShape":
+        """n_valid defaults to the catalogue's."""
+        cat = self.catalog
+        nv = cat._last_valid if n_valid is None else int(n_valid)
+        L.call("dc_component_shape", cat.B, nv, cat.H, cat.W, L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, int(cat.wrap), L.dptr(self._rowt),
+               L.dptr(self._colt), L.dptr(self._shape), L.stream_ptr())
+        self._last_valid = nv
+        return self
+
+    @property
+    def table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, 12] of the last call (a view): zero from min(count, cap) on"""
+        return self._shape[:self._last_valid]
+
+    def rows(self):
+        """On the host, per valid sample only the filled rows: int64 numpy arrays [min(total, cap), 12] (the catalogue's counts decide)"""
+        nv = self._last_valid
+        if nv == 0:
+            return []
+        fill = [min(int(t), self.catalog.cap) for t in self.catalog._ncomp[:nv, 0].cpu().tolist()]
+        host = self._shape[:nv, :max(max(fill), 1)].cpu().numpy()
+        return [host[b, :fill[b]].copy() for b in range(nv)]
+
+    def shapes(self):
+        """Per valid sample of the last call a list of dicts (decode), one per row of the catalogue."""
+        _, rows = self.catalog.rows()
+        return [self.decode(s, r, self.catalog.H, self.catalog.W) for s, r in zip(self.rows(), rows)]
+
+    @staticmethod
+    def steps(height: int, width: int):
+        """(dlat, dlon) in radians: the spacing of the rows and columns of event_shape_tables (rows pole to pole, columns periodic)"""
+        return math.pi / max(height - 1, 1), 2.0 * math.pi / width
+
+    ARC_MAX = 4.4934                               # radians: 1 - sin(t) / t grows up to here (tan t = t), well beyond half the globe
+
+    @staticmethod
+    def chord_moment(theta):
+        """12 lambda+ of a uniform great-circle arc of angle theta (radians, numpy): 6 (1 - sin(theta) / theta) -- points on the unit
+        sphere, second moment along the chord.  theta^2 (1 - theta^2 / 20 + ...) for short arcs (the series below 0.3, where the closed
+        form cancels)."""
+        t = np.asarray(theta, np.float64)
+        t2 = t * t
+        series = t2 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0 * (1.0 - t2 / 72.0)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            closed = 6.0 * (1.0 - np.sin(t) / t)
+        return np.where(t < 0.3, series, closed)
+
+    @staticmethod
+    def arc_angle(q):
+        """the inverse of chord_moment on [0, ARC_MAX], by bisection (numpy): the angle of the great-circle arc whose 12 lambda+ is q"""
+        q = np.asarray(q, np.float64)
+        lo, hi = np.zeros_like(q), np.full_like(q, EventShape.ARC_MAX)
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            below = EventShape.chord_moment(mid) < q
+            lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
+        return 0.5 * (lo + hi)
+
+    @staticmethod
+    def moments(shape_rows, rows):
+        """float64 numpy on the integers: (s0 [n], m [n, 3], C [n, 3, 3], lat [n], lon [n] in radians, lam_plus [n], lam_minus [n],
+        theta [n]: the major axis' angle counter-clockwise from east, in radians) -- the header's decode formula.  Events whose zeroth
+        moment is 0 (pixels on the pole rows only) give NaN moments and zero eigenvalues."""
+        s = np.asarray(shape_rows, np.int64).reshape(-1, len(EVENT_SHAPE_FIELDS)).astype(np.float64)
+        rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
+        s0 = rows[:, 3].astype(np.float64) * float(EVENT_SCALE)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = s[:, 3:6] / s0[:, None]
+            second = np.empty((len(s), 3, 3), np.float64)
+            for (i, j), f in zip(((0, 0), (0, 1), (1, 1), (0, 2), (1, 2), (2, 2)), range(6, 12)):
+                second[:, i, j] = second[:, j, i] = s[:, f] / s0
+            cov = second - m[:, :, None] * m[:, None, :]
+            norm = np.sqrt((m * m).sum(axis=1))
+            c = np.where((norm > 0)[:, None], m / norm[:, None], np.array([1.0, 0.0, 0.0]))
+            lat, lon = np.arcsin(np.clip(c[:, 2], -1.0, 1.0)), np.arctan2(c[:, 1], c[:, 0])
+            zero = np.zeros_like(lat)
+            e = np.stack([-np.sin(lon), np.cos(lon), zero], axis=1)
+            n = np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)], axis=1)
+            cn = np.einsum("kij,kj->ki", cov, n)
+            a, b, d = np.einsum("ki,kij,kj->k", e, cov, e), (e * cn).sum(axis=1), (n * cn).sum(axis=1)
+            rad = np.sqrt(((a - d) / 2) ** 2 + b * b)
+            lp, lm = np.maximum((a + d) / 2 + rad, 0.0), np.maximum((a + d) / 2 - rad, 0.0)
+            theta = 0.5 * np.arctan2(2 * b, a - d)
+        ok = s0 > 0
+        return s0, m, cov, np.where(ok, lat, np.nan), np.where(ok, lon, np.nan), np.where(ok, lp, 0.0), np.where(ok, lm, 0.0), \
+            np.where(ok, theta, np.nan)
+
+    @staticmethod
+    def values(shape_rows, rows, height: int, width: int) -> np.ndarray:
+        """float64 [n, 10] (EVENT_SHAPE_VALUES): decode's numbers for whole arrays at once (what predict.py stores as
+        event_shape_values).  NaN where the zeroth moment is 0 (lat, lon, orientation) or the perimeter is (compactness)."""
+        s = np.asarray(shape_rows, np.int64).reshape(-1, len(EVENT_SHAPE_FIELDS))
+        rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
+        _, _, _, lat, lon, lp, lm, theta = EventShape.moments(s, rows)
+        dlat, dlon = EventShape.steps(height, width)
+        out = np.empty((len(s), len(EVENT_SHAPE_VALUES)), np.float64)
+        length, wid = EARTH_RADIUS_KM * EventShape.arc_angle(12.0 * lp), EARTH_RADIUS_KM * np.sqrt(12.0 * lm)
+        perimeter = EARTH_RADIUS_KM * (dlat * s[:, 1].astype(np.float64) + dlon * s[:, 2].astype(np.float64) / EVENT_SCALE)
+        area = EventFilter.area_km2(rows[:, 3].astype(np.float64), height, width)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[:, 0], out[:, 1] = np.degrees(lat), np.degrees(lon)
+            out[:, 2], out[:, 3] = length, wid
+            out[:, 4] = np.where(lm > 0, np.sqrt(lp / lm), np.inf)
+            out[:, 5] = np.degrees(theta)                     # atan2 lies in (-pi, pi]: half of it in (-90, 90]
+            out[:, 6], out[:, 7] = perimeter, area
+            out[:, 8] = np.where(perimeter > 0, 4.0 * math.pi * area / (perimeter * perimeter), np.nan)
+            out[:, 9] = s[:, 0]
+        return out
+
+    @staticmethod
+    def decode(shape_rows, rows, height: int, width: int):
+        """Shape rows [n, 12] (EVENT_SHAPE_FIELDS) and the events' own rows [n, 10] (EVENT_FIELDS) -> one dict per event with the keys of
+        EVENT_SHAPE_VALUES, R = 6371 km: lat / lon of the spherical centroid in degrees; sqrt(12 lambda+) and sqrt(12 lambda-) are the
+        sides of the uniform strip with the same second moments in chord space (not a skeleton length).  width_km = R sqrt(12 lambda-).
+        length_km = R theta with 6 (1 - sin(theta) / theta) = 12 lambda+: the great-circle arc with that second moment (arc_angle) --
+        R sqrt(12 lambda+) itself is the chord-space figure and falls short of a long thin event by theta^2 / 40, 2.7 % at 6700 km.
+        aspect = sqrt(lambda+ / lambda-), the ratio of the strip's sides and the number the filter compares (inf at width 0);
+        orientation_deg of the major axis, counter-clockwise from east, in (-90, 90]; perimeter_km =
+        R (dlat faces_v + dlon faces_h / 2^20); area_km2 from the catalogue's area; compactness = 4 pi area / perimeter^2;
+        boundary_pixels."""
+        vals = EventShape.values(shape_rows, rows, height, width)
+        out = []
+        for v in vals:
+            d = {k: float(x) for k, x in zip(EVENT_SHAPE_VALUES, v)}
+            d["boundary_pixels"] = int(v[9])
+            out.append(d)
+        return out
+
+
+class EventFilter:
+    """A size and shape filter for the events of a mask, on the device (dc_event_select + dc_mask_select behind an EventCatalog and an
+    EventShape): an event of class k is kept iff it has at least min_pixels[k] pixels, min_area_km2[k] of area, min_length_km[k] of length
+    and min_aspect[k] of aspect (EventShape.decode's numbers; 0: the criterion is off), and the filtered mask keeps the pixels of kept
+    events -- and of events beyond the catalogue's cap, for which nothing was evaluated.  Each threshold is a pair (class 1, class 2).
+    `catalog` is the filter's own catalogue of the RAW mask; whatever consumes the filtered mask (another EventCatalog, a matcher, a
+    tracker, ...) does so unchanged.  Nothing is copied to the host and nothing synchronises."""
+
+    def __init__(self, catalog: EventCatalog, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0)):
+        self.min_pixels, self.min_area_km2 = self._pair(min_pixels, "min_pixels"), self._pair(min_area_km2, "min_area_km2")
+        self.min_length_km, self.min_aspect = self._pair(min_length_km, "min_length_km"), self._pair(min_aspect, "min_aspect")
+        self.catalog = catalog
+        self.shape = EventShape(catalog)
+        dev = catalog._labels.device
+        self.criteria = self.criteria_rows(catalog.H, catalog.W, self.min_pixels, self.min_area_km2, self.min_length_km, self.min_aspect)
+        self._criteria = torch.from_numpy(self.criteria.view(np.int64).copy()).to(dev)
+        self._keep = torch.zeros((catalog.B, catalog.cap), dtype=torch.uint8, device=dev)
+        self._counts = torch.zeros((catalog.B, 2, len(EVENT_FILTER_COUNTS)), dtype=torch.int64, device=dev)
+        self._out = torch.zeros((catalog.B, catalog.H, catalog.W), dtype=torch.uint8, device=dev)
+        self._last_valid = 0
+
+    @staticmethod
+    def _pair(v, name):
+        v = tuple(float(x) for x in (v if isinstance(v, (tuple, list, np.ndarray)) else (v, v)))
+        if len(v) != 2 or any(not (x >= 0) or math.isinf(x) for x in v):
+            raise L.DeepcamHipError(f"EventFilter: {name} takes two finite values >= 0 (class 1, class 2), got {v}")
+        return v
+
+    # -- the thresholds in the kernel's units, and back (the checker and the tests use the same ones)
+    @staticmethod
+    def pixel_area_km2(height: int, width: int) -> float:
+        """km^2 of one pixel on the equator: R^2 dlat dlon"""
+        dlat, dlon = EventShape.steps(height, width)
+        return EARTH_RADIUS_KM * EARTH_RADIUS_KM * dlat * dlon
+
+    @staticmethod
+    def area_units(km2: float, height: int, width: int) -> int:
+        """min_area: the smallest catalogue area (field 3: sum of 2^20 cos lat) that is at least km2"""
+        return int(math.ceil(float(km2) / EventFilter.pixel_area_km2(height, width) * EVENT_SCALE))
+
+    @staticmethod
+    def area_km2(units, height: int, width: int):
+        return units / float(EVENT_SCALE) * EventFilter.pixel_area_km2(height, width)
+
+    @staticmethod
+    def length_units(km: float) -> float:
+        """min_len2 = chord_moment(km / R): length_km >= km  iff  12 lambda+ >= min_len2 (both sides of decode's arc_angle)"""
+        theta = float(km) / EARTH_RADIUS_KM
+        if not 0.0 <= theta <= EventShape.ARC_MAX:
+            raise L.DeepcamHipError(f"EventFilter: a length threshold must lie in [0, {EARTH_RADIUS_KM * EventShape.ARC_MAX:.0f}] km, got {km}")
+        return float(EventShape.chord_moment(theta))
+
+    @staticmethod
+    def length_km(len2: float) -> float:
+        return EARTH_RADIUS_KM * float(EventShape.arc_angle(len2))
+
+    @staticmethod
+    def aspect_units(aspect: float) -> float:
+        """min_aspect2 = aspect^2: decode's aspect >= aspect  iff  lambda+ >= min_aspect2 lambda-"""
+        return float(aspect) ** 2
+
+    @staticmethod
+    def aspect(aspect2: float) -> float:
+        return math.sqrt(aspect2)
+
+    CRITERIA = np.dtype([("min_pixels", np.int64), ("min_area", np.int64), ("min_len2", np.float64), ("min_aspect2", np.float64)])
+
+    @staticmethod
+    def criteria_rows(height: int, width: int, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0)) -> np.ndarray:
+        """the two rows dc_event_select takes (class 1, class 2), a numpy record array of dtype CRITERIA"""
+        out = np.zeros(2, EventFilter.CRITERIA)
+        for k in range(2):
+            out[k] = (int(math.ceil(min_pixels[k])), EventFilter.area_units(min_area_km2[k], height, width),
+                      EventFilter.length_units(min_length_km[k]), EventFilter.aspect_units(min_aspect[k]))
+        return out
+
+    def thresholds(self) -> dict:
+        return {"min_pixels": list(self.min_pixels), "min_area_km2": list(self.min_area_km2), "min_length_km": list(self.min_length_km),
+                "min_aspect": list(self.min_aspect)}
+
+    def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
+        """mask: device uint8 [B, H, W].  Returns the filtered mask [n_valid, H, W], a view of a buffer this object owns (mask_buffer is
+        the whole of it; the next call overwrites it).  Samples from n_valid on are padding: neither read nor written."""
+        cat = self.catalog
+        cat(mask, n_valid=n_valid)
+        nv = cat._last_valid
+        self.shape(nv)
+        st = L.stream_ptr()
+        L.call("dc_event_select", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(self.shape._shape), L.dptr(self._criteria),
+               L.dptr(self._keep), L.dptr(self._counts), st)
+        L.call("dc_mask_select", cat.B, nv, cat.H, cat.W, L.dptr(mask), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, L.dptr(self._keep),
+               L.dptr(self._out), L.dptr(self._counts), st)
+        self._last_valid = nv
+        return self._out[:nv]
+
+    @property
+    def mask_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the whole buffer the filtered masks are written to, padding samples included"""
+        return self._out
+
+    @property
+    def keep(self) -> torch.Tensor:
+        """uint8 [n_valid, cap] of the last call (a view): 1 for a kept event, 0 for a dropped one and for rows without an event"""
+        return self._keep[:self._last_valid]
+
+    def counts(self) -> torch.Tensor:
+        """int64 [n_valid, 2, 4] of the last call (a view): per class EVENT_FILTER_COUNTS (events among the ranks below cap)"""
+        return self._counts[:self._last_valid]
+
+
 TRACK_STORE_FIELDS = ("frame", "rank") + EVENT_FIELDS
 TRACK_FIELDS = ("id", "class", "events", "first_frame", "last_frame", "pixels", "peak", "area")
 

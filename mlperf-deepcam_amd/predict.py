@@ -50,6 +50,16 @@ nn.Climatology.decode turns them into frequencies, means and shares --, with --v
 the files' labels; ``summary.json`` gains ``climatology`` (the groups, their frames, the area-weighted frequency per class and group).
 With --plots ``plots/climatology-<group>-class<k>.png`` shows, for every group that received a frame, the frequency of class k across
 [0, 1] with the region of frequency >= --climatology_contour outlined (with --verify above the same picture of the labels).
+With --event_shape (which implies --events) nn.EventShape adds the geometry of every event, behind the catalogue: every output file also
+carries ``event_shape`` (int64 [n, 12]: boundary pixels, the two face counts and the nine moment sums -- the rows of ``events``, in their
+order), ``event_shape_values`` (float64 [n, 10]: lat, lon, length_km, width_km, aspect, orientation_deg, perimeter_km, area_km2,
+compactness, boundary_pixels) and ``event_shape_value_names`` (uint8: that column order, comma-separated ASCII).
+With --event_filter nn.EventFilter drops, on the device, the events of the classifier's mask that miss the --filter_min_pixels,
+--filter_min_area_km2, --filter_min_length_km or --filter_min_aspect of their class (two values each: class 1, class 2; 0: off).
+``prediction`` stays the classifier's mask, ``prediction_filtered`` is added, and EVERYTHING downstream takes the filtered mask: the
+catalogue behind ``events`` (a second one: the filter's own runs on the raw mask), --verify's prediction side, --event_fields, --tracks,
+--track_fields, --climatology and --plots.  The labels under --verify are not filtered.  ``summary.json`` gains ``event_filter`` (the
+thresholds and per class the events and pixels kept and dropped).
 Single process, single device."""
 from __future__ import annotations
 
@@ -114,6 +124,17 @@ class _TrackFields(argparse.Action):
         namespace.events = True
 
 
+class _EventShape(argparse.Action):
+    """--event_shape: implies --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.event_shape = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -135,6 +156,20 @@ def build_parser():
                     "least this share of it with its class, in (0, 1]")
     AP.add_argument("--event_fields", action=_EventFields, help="per event and file channel the extremes with their positions and the means "
                     "of the raw fields (implies --events): datasets 'event_fields', 'event_field_values', 'event_field_bits'")
+    AP.add_argument("--event_shape", action=_EventShape, help="per event its geometry (implies --events): spherical centroid, length, width, "
+                    "aspect, orientation, perimeter, compactness; datasets 'event_shape', 'event_shape_values', 'event_shape_value_names'")
+    AP.add_argument("--event_filter", action="store_true", help="filter the classifier's mask by event size and shape on the device (the "
+                    "--filter_* thresholds): dataset 'prediction_filtered', 'event_filter' in the summary; --events, --verify's prediction "
+                    "side, --event_fields, --tracks, --track_fields, --climatology and --plots all take the FILTERED mask.  The labels "
+                    "under --verify are NOT filtered")
+    AP.add_argument("--filter_min_pixels", type=int, nargs=2, default=[0, 0], metavar=("TC", "AR"), help="with --event_filter: drop events "
+                    "of fewer pixels (class 1, class 2; 0: off)")
+    AP.add_argument("--filter_min_area_km2", type=float, nargs=2, default=[0.0, 0.0], metavar=("TC", "AR"), help="with --event_filter: drop "
+                    "events of less area")
+    AP.add_argument("--filter_min_length_km", type=float, nargs=2, default=[0.0, 0.0], metavar=("TC", "AR"), help="with --event_filter: drop "
+                    "events shorter than this (an atmospheric river is roughly 2000 km or longer)")
+    AP.add_argument("--filter_min_aspect", type=float, nargs=2, default=[0.0, 0.0], metavar=("TC", "AR"), help="with --event_filter: drop "
+                    "events whose length / width is below this (an atmospheric river is at least twice as long as wide)")
     AP.add_argument("--plots", action="store_true", help="also write <output_dir>/plots/<base>.png: the field with the predicted classes "
                     "outlined (with --verify: above the same field with the labelled ones).  Encoding one two-panel 768 x 1152 frame takes tens "
                     "to hundreds of milliseconds of the writer thread, so with --plot_every 1 the writer bounds the rate, not the device: raise --plot_every")
@@ -300,7 +335,12 @@ def plot_name(base: str) -> str:
 
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
-                 plot_rows: int = 0):
+                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False):
+        # --event_shape: the rows of nn.EventShape (cap rows of 96 bytes per sample)
+        self.shape = torch.empty((B, event_cap, len(dnn.EVENT_SHAPE_FIELDS)), dtype=torch.int64).pin_memory() if event_shape else None
+        # --event_filter: the filtered mask and the filter's counts
+        self.fmask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if event_filter else None
+        self.fcounts = torch.empty((B, 2, len(dnn.EVENT_FILTER_COUNTS)), dtype=torch.int64).pin_memory() if event_filter else None
         # --plots: the RGB bytes of nn.FrameRenderer, per sample the panels stacked
         self.rgb = torch.empty((B, plot_rows, W, 3), dtype=torch.uint8).pin_memory() if plot_rows else None
         # --event_fields: the rows of nn.EventFields (cap * C rows of 48 bytes per sample)
@@ -338,9 +378,11 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if slot.events is not None:
                         total = int(slot.ncomp[j, 0])
                         rows = slot.events[j, :min(total, slot.events.shape[1])].numpy()
-                        frows = None
+                        frows = srows = None
                         if slot.fields is not None:          # the filter of `events`, whichever branch below applies it
                             frows = np.ascontiguousarray(slot.fields[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
+                        if slot.shape is not None:
+                            srows = np.ascontiguousarray(slot.shape[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.pairs is not None:
                             truth = slot.truth[j, :min(int(slot.ntruth[j, 0]), slot.truth.shape[1])].numpy()
                             pairs = dnn.EventMatcher.sort_pairs(slot.pairs[j, :int(slot.npairs[j, 0])].numpy())
@@ -352,6 +394,12 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             H, W = slot.mask.shape[1:]
                             extra = dict(extra or {}, event_fields=frows, event_field_values=dnn.EventFields.values(frows, rows, H, W, field_bits),
                                          event_field_bits=np.asarray(field_bits, np.int32))
+                        if srows is not None:
+                            H, W = slot.mask.shape[1:]
+                            extra = dict(extra or {}, event_shape=srows, event_shape_values=dnn.EventShape.values(srows, rows, H, W),
+                                         event_shape_value_names=np.frombuffer(",".join(dnn.EVENT_SHAPE_VALUES).encode(), np.uint8).copy())
+                    if slot.fmask is not None:
+                        extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     if plot[j]:
                         png.write_png(os.path.join(out_dir, "plots", plot_name(base)), slot.rgb[j].numpy())
@@ -359,6 +407,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if plot[j]:
                         rec["plot"] = plot_name(base)
+                    if slot.fcounts is not None:
+                        rec["event_filter"] = [dict(zip(dnn.EVENT_FILTER_COUNTS, (int(v) for v in row))) for row in slot.fcounts[j].tolist()]
                     if rows is not None:
                         rec["events"] = [int((rows[:, 1] == 1).sum()), int((rows[:, 1] == 2).sum())]
                         rec["events_overflowed"] = total > slot.events.shape[1]
@@ -401,13 +451,23 @@ def main(pargs) -> dict:
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     loader = ddata.InputPipeline(dataset, B, dtype=dtype, device=device, layout=layout, drop_last=False, workers=pargs.max_inter_threads)
     events = bool(pargs.events) or verify or bool(getattr(pargs, "tracks", False))
-    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify,
+    # --event_filter: the filter's own catalogue takes the classifier's mask; everything below takes the filtered one
+    efilter = None
+    if getattr(pargs, "event_filter", False):
+        efilter = dnn.EventFilter(dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device),
+                                  min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
+                                  min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect)
+    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify and efilter is None,
                               event_connectivity=pargs.event_connectivity)
     # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
     matcher = dnn.EventMatcher(B, H, W, connectivity=pargs.event_connectivity, min_pixels=pargs.min_event_pixels,
                                min_cover=pargs.min_event_cover, device=device) if verify else None
     catalog = matcher.a if verify else predictor.catalog
+    if events and catalog is None:                # --event_filter without --verify: a second catalogue, of the filtered mask
+        catalog = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
+    own_catalog = events and not verify and efilter is not None
     event_cap = catalog.cap if events else 0
+    eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
     efields = field_bits = None
     if getattr(pargs, "event_fields", False):
@@ -452,7 +512,7 @@ def main(pargs) -> dict:
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
-                             renderer.P * renderer.Ho if renderer else 0))
+                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -467,10 +527,19 @@ def main(pargs) -> dict:
                 free_q.put(slot)
                 break
             mask = predictor(x, n_valid=nv)
+            dmask = predictor.mask_buffer          # what everything downstream takes
+            if efilter is not None:
+                slot.fmask[:nv].copy_(efilter(predictor.mask_buffer, n_valid=nv), non_blocking=True)
+                slot.fcounts[:nv].copy_(efilter.counts(), non_blocking=True)
+                dmask = efilter.mask_buffer
+            if own_catalog:
+                catalog(dmask, n_valid=nv)
             if verify:
-                matcher(predictor.mask_buffer, y, n_valid=nv)
+                matcher(dmask, y, n_valid=nv)
+            if eshape is not None:
+                slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
             if tracker is not None:
-                tracker(predictor.mask_buffer, n_valid=nv)
+                tracker(dmask, n_valid=nv)
             if efields is not None:
                 efields(loader.raw, n_valid=nv)     # behind the catalogue's launches, on their stream
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
@@ -479,7 +548,7 @@ def main(pargs) -> dict:
             if clim is not None:
                 groups = [dnn.climatology_group(name, clim_by) for name in names] + [-1] * (B - nv)
                 raw = loader.raw if clim.C else None
-                clim(predictor.mask_buffer, raw, groups=groups, n_valid=nv)
+                clim(dmask, raw, groups=groups, n_valid=nv)
                 if clim_truth is not None:
                     clim_truth(y, raw, groups=groups, n_valid=nv)
             slot.mask[:nv].copy_(mask, non_blocking=True)
@@ -498,7 +567,7 @@ def main(pargs) -> dict:
             plot = [renderer is not None and (seen + j) % plot_every == 0 for j in range(nv)]
             seen += nv
             if any(plot):
-                slot.rgb[:nv].copy_(renderer(loader.raw, predictor.mask_buffer, y if verify else None, n_valid=nv), non_blocking=True)
+                slot.rgb[:nv].copy_(renderer(loader.raw, dmask, y if verify else None, n_valid=nv), non_blocking=True)
             slot.done.record(torch.cuda.current_stream())
             work_q.put((slot, names, plot))
     finally:
@@ -519,6 +588,9 @@ def main(pargs) -> dict:
     if events:
         summary["events"] = [sum(r["events"][j] for r in records) for j in range(2)]
         summary["events_overflowed_files"] = sum(1 for r in records if r["events_overflowed"])
+    if efilter is not None:
+        summary["event_filter"] = dict(efilter.thresholds(), classes=[
+            {k: sum(r["event_filter"][j][k] for r in records) for k in dnn.EVENT_FILTER_COUNTS} for j in range(2)])
     if efields is not None:
         summary["event_fields"] = {"channels": efields.C, "scale_bits": [int(v) for v in field_bits],
                                    "nonfinite": sum(r["event_field_counts"][0] for r in records),
