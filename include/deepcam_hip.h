@@ -83,6 +83,8 @@ int dc_reset_options(void);
  *     (colour table, graticule and outlines into the RGB bytes)
  *   climatology (dc_climatology_accumulate, dc_climatology_maps): climatology_accumulate_vec (16-byte loads, four lanes per 16-channel
  *     pixel), climatology_accumulate_scalar (any channel selection, and none), climatology_maps
+ *   storm composites (dc_composite_centers, dc_composite_accumulate): composite_centers, composite_accumulate_vec (16-byte loads, four
+ *     lanes per 16-channel pixel), composite_accumulate_scalar (any channel selection)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -946,6 +948,76 @@ int dc_climatology_accumulate(int B, int H, int W, int G, const void* mask, int 
                               int32_t* count, int64_t* sum, int32_t* n, void* stream);
 int dc_climatology_maps(int G, int H, int W, int C, const int64_t* frames, const int32_t* count, const int64_t* sum, const int32_t* n,
                         const int32_t* bits, int K, const int32_t* products, float t1, float t2, float* out, uint8_t* contour, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Storm-centred composites (nn.StormComposite; predict.py --composites): the fields in STORM coordinates -- a window of S x S grid pixels,
+ * S = 2 R + 1, around every event's centre, summed cell by cell over the events of a group, and the sums per great-circle distance from
+ * the centre.  The centre is a field extreme that dc_component_fields located (a cyclone's pressure minimum).  The accumulators live in
+ * device memory from call to call, owned by the caller, who zeroes them to start.  Everything is an integer sum: the state after a
+ * sequence of frames does not depend on how it was cut into batches, on the order of arrival, or on scheduling.
+ * dc_composite_centers, one thread per catalogue row (b, k), b < n_valid, k < cap:
+ *   table, ncomp  as dc_component_stats leaves them       ftable  int64 [B][cap][Cf][6] as dc_component_fields leaves it, 1 <= Cf <= 32
+ *   center_channel in [0, Cf), stat 0 = the minimum's pixel, 1 = the maximum's
+ *   class_mask    bit 1 is class 1, bit 2 is class 2 (2, 4 or 6)          min_pixels >= 0
+ *   frame_group   int32 [B], device: the group of every frame, G groups    edges  fp32 [NE], device, ascending, 0 <= NE <= 255 (NULL
+ *                 allowed when NE == 0); G * (NE + 1) <= 65536
+ *   centers       int32 [B][cap]: the centre pixel r0 * W + c0 -- the low 32 bits of the min word, or 0xFFFFFFFF minus the low 32 bits
+ *                 of the max word --, -1 where the row is not composited
+ *   egroup        int32 [B][cap]: frame_group[b] * (NE + 1) + bin, -1 where centers is -1.  bin = the number of edges e with centre
+ *                 value >= e, compared as the order-preserving 32-bit keys of dc_component_fields (unsigned integers: exact, and
+ *                 -0.0 < +0.0 as everywhere else)
+ *   counts        int64 [5], NOT zeroed by the call: += composited, no_center, below_min_pixels, other_class, uncatalogued; added with
+ *                 one atomic per workgroup and counter, as dc_mask_select does
+ *   A row k < min(ncomp[b][0], cap) of a frame with frame_group[b] in [0, G) falls into the FIRST category that applies, in this order:
+ *   other_class (its class is not 1 or 2, or its bit of class_mask is clear), below_min_pixels (pixels < min_pixels), no_center (the
+ *   field row is empty: min == -1, or max == 0; a pixel index >= H * W counts here too, so nothing is ever read through it), else
+ *   composited.  uncatalogued += max(ncomp[b][0] - cap, 0) per such frame.  Rows from min(ncomp, cap) on get -1.  Frames with
+ *   frame_group[b] < 0 or >= G get -1 everywhere and count nothing.  Samples from n_valid on are neither read nor written.
+ * dc_composite_accumulate adds the windows of a batch.  1 <= R <= 40, S <= W, GT = G * (NE + 1) <= 65536, 1 <= C <= 32 selected channels.
+ *   events  int64 [GT]             events added to group g
+ *   sum     int64 [GT][S][S][C]    the sum of q per cell and selected channel       n  int32 [GT][S][S][C]  how many values it holds
+ *   inside  int32 [GT][S][S]       events whose own pixels cover the cell (the mean footprint of the storms)
+ *   rsum    int64 [GT][NB][C], rn int64 [GT][NB][C]: the same sums per distance bin
+ *   centers, egroup  as dc_composite_centers leaves them      table (for each event's root), labels int32 [B][H][W] as
+ *           dc_mask_components leaves them
+ *   fields  fp32 [B][H][W][ldc], channel-last, physical units      chan  int32 [C], device, or NULL: as dc_climatology_accumulate
+ *   bits    int32 [C], device (nn.composite_bits)                  negate_mask  bit ch: selected channel ch changes sign in a
+ *           southern event        flip_south 0 or 1
+ *   rbin    uint8 [H][S][R + 1], device (nn.composite_radius_table), or NULL with NB = 0 (rsum and rn are then not touched); 1 <= NB <= 255
+ * For every event with centre (r0, c0) and g = egroup in [0, GT), and every cell (i, j) with di = i - R, dj = j - R:
+ *   The event is SOUTHERN iff flip_south is set and 2 r0 < H - 1 (row 0 is -90 degrees, as nn.event_weight_tables has it; the equator row
+ *   of an odd H is not southern).  The source row is r = r0 - di for a southern event, else r0 + di: di > 0 is poleward in both
+ *   hemispheres, and the reflection turns the southern sense of rotation into the northern one.  The source column is c = (c0 + dj)
+ *   mod W: columns are periodic.  A cell whose row falls outside [0, H) adds nothing anywhere -- no wrap over the poles; n shows the gap.
+ *   events[g] += 1, once per event.  inside[g][i][j] += 1 where labels[b][r][c] == root + 1.
+ *   Per selected channel ch: v = fields[b][r][c][chan[ch]], q = rint(ldexp((double)v, bits[ch])), ties to even.  Only finite v with
+ *   |q| <= 2^28 take part.  Bit ch of negate_mask set and the event southern: q = -q (the meridional wind components, whose sign the
+ *   reflection reverses).  sum[g][i][j][ch] += q, n[g][i][j][ch] += 1.
+ *   With rbin: k = rbin[r0][(r - r0) + R][|dj|], indexed with the TRUE source row whether flipped or not.  k < NB: rsum[g][k][ch] += q,
+ *   rn[g][k][ch] += 1.
+ * An entry of centers outside [0, H * W) or of egroup outside [0, GT) skips its event, and so does a chan entry outside [0, ldc) its
+ * channel, rather than reading or writing out of bounds.  Samples from n_valid on are neither read nor written.
+ * Capacity: a radial word takes at most S^2 < 2^13 values of at most 2^28 per event.  The caller keeps every group below 2^21 events:
+ * then no int64 word (2^13 * 2^28 * 2^21 < 2^63) and no int32 word (n, inside < 2^21) can overflow.
+ * The gather is inverted: a thread owns a cell's channel quad (one channel in the scalar form), walks the batch's composited events --
+ * compacted into worklist chunks in LDS -- with its partial sums in registers and adds them once per chunk and group; the batch's rows
+ * are cut into slices that meet in 64-bit integer atomics; the radial bins are reduced in LDS and leave with one 64-bit atomic per workgroup and
+ * word (straight to global memory where NB * C > 4096).  With chan == NULL, ldc == C, C % 4 == 0 and fields 16-byte aligned the fields
+ * are loaded 16 bytes per lane on consecutive addresses, split only at the seam; every other layout takes scalar loads.
+ * dc_composite_chunk: the events of a worklist chunk (a host function; tests build a frame with more events than that).
+ * Neither device call synchronises.  Both run on the caller's stream, behind the catalogue's and the dc_component_fields call of the
+ * same batch.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_composite_chunk(int* events);
+int dc_composite_centers(int B, int n_valid, int H, int W, int cap, const int64_t* table, const int32_t* ncomp, const int64_t* ftable,
+                         int Cf, int center_channel, int stat, int class_mask, long min_pixels, const int32_t* frame_group, int G,
+                         const float* edges /*may be NULL when NE == 0*/, int NE, int32_t* centers, int32_t* egroup, int64_t* counts,
+                         void* stream);
+int dc_composite_accumulate(int B, int n_valid, int H, int W, int cap, int R, int GT, const int32_t* centers, const int32_t* egroup,
+                            const int64_t* table, const int32_t* labels, const float* fields, int C, int ldc,
+                            const int32_t* chan /*may be NULL*/, const int32_t* bits, int negate_mask, int flip_south,
+                            const uint8_t* rbin /*may be NULL*/, int NB, int64_t* events, int64_t* sum, int32_t* n, int32_t* inside,
+                            int64_t* rsum, int64_t* rn, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

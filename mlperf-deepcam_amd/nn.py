@@ -2246,3 +2246,220 @@ class Climatology:
         scaled = np.ldexp(total, -np.asarray(bits, np.int32).reshape(-1)) if C else total
         out.update(mean=div(scaled, n.astype(np.float64)), share=div(total[:, 1:], total[:, :1]))
         return out
+
+
+# ---------------------------------------------------------------------------------------------- storm-centred composites
+COMPOSITE_COUNTS = ("composited", "no_center", "below_min_pixels", "other_class", "uncatalogued")
+COMPOSITE_MAX_EVENTS = 1 << 21
+COMPOSITE_MAX_RADIUS = 40
+COMPOSITE_KEYS = ("events", "sum", "n", "inside", "rsum", "rn")
+
+
+def composite_bits(minval, maxval) -> np.ndarray:
+    """int32 [C]: the binary scale of dc_composite_accumulate's sums per channel, from the dataset's recorded range.  With m =
+    max(|minval|, |maxval|): 27 - frexp(m)[1], and 0 where m is zero or not finite.  A value inside the range is summed as
+    rint(v * 2^bits) with |q| < 2^27; values up to twice outside the range still fit below the kernel's limit of 2^28."""
+    lo = np.atleast_1d(np.asarray(minval, np.float64))
+    hi = np.atleast_1d(np.asarray(maxval, np.float64))
+    m = np.maximum(np.abs(lo), np.abs(hi))
+    ok = np.isfinite(m) & (m > 0)
+    return np.where(ok, 27 - np.frexp(np.where(ok, m, 1.0))[1], 0).astype(np.int32)
+
+
+def composite_radius_table(height: int, width: int, radius: int, bin_km: float, bins: int) -> np.ndarray:
+    """uint8 [H][S][R + 1], S = 2 R + 1: entry (r0, d + R, a) is the distance bin floor(distance / bin_km) between the pixel centres
+    (r0, c0) and (r0 + d, c0 + a) -- the great-circle distance by the haversine formula in float64, latitudes from linspace(-90, 90, H),
+    a longitude step of 360 / W (the periodic grid of event_shape_tables), Earth radius EARTH_RADIUS_KM.  255 where the bin is >= bins or
+    row r0 + d is off the grid.  bins <= 255."""
+    height, width, radius, bins = int(height), int(width), int(radius), int(bins)
+    if height < 1 or width < 1 or not 1 <= radius <= COMPOSITE_MAX_RADIUS or not 0 <= bins <= 255 or not float(bin_km) > 0:
+        raise L.DeepcamHipError(f"composite_radius_table: height and width must be positive, radius in [1, {COMPOSITE_MAX_RADIUS}], bins in "
+                                f"[0, 255] and bin_km positive, got {height}, {width}, {radius}, {bins}, {bin_km}")
+    lat = np.deg2rad(np.linspace(-90.0, 90.0, height))
+    d = np.arange(-radius, radius + 1)
+    rows = np.arange(height)[:, None] + d[None, :]                              # [H, S]
+    on = (rows >= 0) & (rows < height)
+    lat1 = lat[:, None, None]
+    lat2 = lat[np.clip(rows, 0, height - 1)][:, :, None]
+    dlon = np.deg2rad(360.0 / width * np.arange(radius + 1))[None, None, :]
+    hav = np.sin((lat2 - lat1) / 2.0) ** 2 + np.cos(lat1) * np.cos(lat2) * np.sin(dlon / 2.0) ** 2
+    dist = 2.0 * EARTH_RADIUS_KM * np.arcsin(np.sqrt(np.clip(hav, 0.0, 1.0)))
+    k = np.floor(dist / float(bin_km))
+    return np.where(on[:, :, None] & (k < bins), np.minimum(k, 255), 255).astype(np.uint8)
+
+
+class StormComposite:
+    """The fields in storm coordinates, accumulated on the device (dc_composite_centers, dc_composite_accumulate, csrc/composite.hip):
+    around the centre of every selected event of an EventFields catalogue -- the pixel of the minimum (or maximum) of center_channel, a
+    cyclone's pressure minimum -- a window of S x S grid pixels, S = 2 radius + 1, summed cell by cell over the events of a group, with
+    the events' mean footprint and the sums per great-circle distance bin (bins of bin_km; bins = 0: no radial profile).
+    channels: indices into the ldc channels of a pixel (None: all of them); bits: the binary scale per SELECTED channel (composite_bits;
+    None: EventFields' bits less 12, which is the same number for a channel with a recorded range); classes: the event classes that are
+    composited; groups: the frame groups G (climatology_group); intensity_edges: ascending finite values that cut the centre value into
+    len + 1 bins (an event on an edge goes to the bin above), so that GT = G * (len + 1) composites are kept, index group * (len + 1) + bin;
+    flip_south: southern events are reflected about their centre row, so that "up" is poleward and the rotation is northern; negate:
+    selected-channel POSITIONS whose sign the reflection reverses (the meridional wind components).
+    The object owns events (int64 [GT]), sum (int64 [GT, S, S, C]), n (int32 [GT, S, S, C]), inside (int32 [GT, S, S]), rsum / rn (int64
+    [GT, NB, C]) and counts (int64 [5], COMPOSITE_COUNTS); everything is an integer sum, so the state does not depend on how a sequence was
+    cut into batches or ordered.  A call must follow the catalogue's and the EventFields call of the same batch on the same stream; it
+    launches and does not synchronise; state() and composites() read back."""
+
+    def __init__(self, fields: "EventFields", center_channel: int, center_stat: str = "min", radius: int = 32, channels=None, bits=None,
+                 classes=(1,), min_pixels: int = 0, groups: int = 1, intensity_edges=(), flip_south: bool = True, negate=(),
+                 bin_km: float = 25.0, bins: int = 40):
+        cat = fields.catalog
+        if center_stat not in ("min", "max"):
+            raise L.DeepcamHipError(f"StormComposite: center_stat must be 'min' or 'max', got {center_stat!r}")
+        if not 0 <= int(center_channel) < fields.C:
+            raise L.DeepcamHipError(f"StormComposite: center_channel must lie in [0, {fields.C}), got {center_channel}")
+        radius = int(radius)
+        if not 1 <= radius <= COMPOSITE_MAX_RADIUS or 2 * radius + 1 > cat.W:
+            raise L.DeepcamHipError(f"StormComposite: radius must lie in [1, {COMPOSITE_MAX_RADIUS}] and 2 * radius + 1 may not exceed the "
+                                    f"width {cat.W}, got {radius}")
+        channels = list(range(fields.ldc)) if channels is None else [int(c) for c in channels]
+        C_ = len(channels)
+        if not 1 <= C_ <= 32 or min(channels) < 0 or max(channels) >= fields.ldc:
+            raise L.DeepcamHipError(f"StormComposite: between 1 and 32 channels out of [0, {fields.ldc}), got {channels}")
+        if bits is None:
+            if max(channels) >= fields.C:
+                raise L.DeepcamHipError("StormComposite: bits are needed for channels the EventFields object does not cover")
+            bits = [fields.bits[c] - 12 for c in channels]
+        bits = [int(v) for v in np.asarray(bits).reshape(-1)]
+        if len(bits) != C_:
+            raise L.DeepcamHipError(f"StormComposite: {len(bits)} scale bits for {C_} channels")
+        classes = sorted({int(k) for k in classes})
+        if not classes or any(k not in (1, 2) for k in classes):
+            raise L.DeepcamHipError(f"StormComposite: classes must be a non-empty subset of (1, 2), got {classes}")
+        if int(min_pixels) < 0:
+            raise L.DeepcamHipError(f"StormComposite: min_pixels must not be negative, got {min_pixels}")
+        edges = np.asarray(list(intensity_edges), np.float32).reshape(-1)
+        if len(edges) > 255 or not np.all(np.isfinite(edges)) or np.any(np.diff(edges) < 0):
+            raise L.DeepcamHipError(f"StormComposite: intensity_edges must be at most 255 finite ascending values, got {list(intensity_edges)}")
+        if not 1 <= int(groups) or int(groups) * (len(edges) + 1) > 65536:
+            raise L.DeepcamHipError(f"StormComposite: groups must be positive and groups * (edges + 1) at most 65536, got {groups}")
+        negate = sorted({int(c) for c in negate})
+        if any(not 0 <= c < C_ for c in negate):
+            raise L.DeepcamHipError(f"StormComposite: negate holds positions of selected channels, [0, {C_}), got {negate}")
+        if not 0 <= int(bins) <= 255 or not float(bin_km) > 0:
+            raise L.DeepcamHipError(f"StormComposite: bins must lie in [0, 255] and bin_km be positive, got {bins}, {bin_km}")
+        self.fields, self.catalog = fields, cat
+        self.center_channel, self.center_stat, self.R, self.S = int(center_channel), center_stat, radius, 2 * radius + 1
+        self.channels, self.bits, self.C, self.classes, self.min_pixels = channels, bits, C_, classes, int(min_pixels)
+        self.G, self.edges, self.NE = int(groups), edges, len(edges)
+        self.GT = self.G * (self.NE + 1)
+        self.flip_south, self.negate, self.bin_km, self.NB = bool(flip_south), negate, float(bin_km), int(bins)
+        self.class_mask = sum(1 << k for k in classes)
+        self.negate_mask = sum(1 << c for c in negate)
+        dev = self.device = cat._labels.device
+        S, GT = self.S, self.GT
+        self._events = torch.zeros((GT,), dtype=torch.int64, device=dev)
+        self._sum = torch.zeros((GT, S, S, C_), dtype=torch.int64, device=dev)
+        self._n = torch.zeros((GT, S, S, C_), dtype=torch.int32, device=dev)
+        self._inside = torch.zeros((GT, S, S), dtype=torch.int32, device=dev)
+        self._rsum = torch.zeros((GT, self.NB, C_), dtype=torch.int64, device=dev)
+        self._rn = torch.zeros((GT, self.NB, C_), dtype=torch.int64, device=dev)
+        self._counts = torch.zeros((len(COMPOSITE_COUNTS),), dtype=torch.int64, device=dev)
+        self._centers = torch.full((cat.B, cat.cap), -1, dtype=torch.int32, device=dev)
+        self._egroup = torch.full((cat.B, cat.cap), -1, dtype=torch.int32, device=dev)
+        self._bits = torch.tensor(bits, dtype=torch.int32, device=dev)
+        self._edges = torch.from_numpy(edges).to(dev) if self.NE else None
+        # the identity over all ldc channels travels as a null table: the library then knows it on the host and may take its 16-byte loads
+        self._chan = None if channels == list(range(fields.ldc)) else torch.tensor(channels, dtype=torch.int32, device=dev)
+        self.radius_table = composite_radius_table(cat.H, cat.W, radius, bin_km, bins) if self.NB else None
+        self._rbin = torch.from_numpy(self.radius_table).to(dev) if self.NB else None
+        self._tables = {}                            # group tuple -> device int32 [B]
+        self._last_valid = 0
+
+    def _group_table(self, groups, nv: int) -> tuple:
+        B = self.catalog.B
+        if groups is None or isinstance(groups, (int, np.integer)):
+            table = [0 if groups is None else int(groups)] * B
+        else:
+            table = [int(g) for g in groups]
+            if len(table) != B:
+                raise L.DeepcamHipError(f"StormComposite: {len(table)} groups for a batch of {B}")
+        table = tuple(g if j < nv and g >= 0 else -1 for j, g in enumerate(table))
+        if any(g >= self.G for g in table):
+            raise L.DeepcamHipError(f"StormComposite: group indices must be below {self.G}, got {list(table)}")
+        return table
+
+    def __call__(self, raw_fields: torch.Tensor, groups=None, n_valid: Optional[int] = None) -> "StormComposite":
+        """raw_fields: contiguous device fp32 [B, H, W, ldc], physical units (InputPipeline.raw) -- the tensor the EventFields call of this
+        batch was given; groups: None (every frame to group 0), an int, or B ints, a negative one skipping its frame; n_valid defaults to
+        the EventFields call's, frames from it on are skipped."""
+        cat, ef = self.catalog, self.fields
+        want = (cat.B, cat.H, cat.W, ef.ldc)
+        if raw_fields.dtype != torch.float32 or tuple(raw_fields.shape) != want or not raw_fields.is_cuda or not raw_fields.is_contiguous() \
+                or raw_fields.device != self.device:
+            raise L.DeepcamHipError(f"StormComposite: fields must be a contiguous fp32 tensor {list(want)} on {self.device}, got "
+                                    f"{raw_fields.dtype} {tuple(raw_fields.shape)} on {raw_fields.device}")
+        nv = ef._last_valid if n_valid is None else int(n_valid)
+        if not 0 <= nv <= cat.B:
+            raise L.DeepcamHipError(f"StormComposite: n_valid must lie in [0, {cat.B}], got {n_valid}")
+        table = self._group_table(groups, nv)
+        self._last_valid = nv
+        if nv == 0 or all(g < 0 for g in table):
+            return self
+        dev_table = self._tables.get(table)
+        if dev_table is None:
+            dev_table = self._tables[table] = torch.tensor(table, dtype=torch.int32, device=self.device)
+        st = L.stream_ptr()
+        L.call("dc_composite_centers", cat.B, nv, cat.H, cat.W, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(ef._ftable), ef.C,
+               self.center_channel, 0 if self.center_stat == "min" else 1, self.class_mask, self.min_pixels, L.dptr(dev_table), self.G,
+               L.dptr(self._edges), self.NE, L.dptr(self._centers), L.dptr(self._egroup), L.dptr(self._counts), st)
+        L.call("dc_composite_accumulate", cat.B, nv, cat.H, cat.W, cat.cap, self.R, self.GT, L.dptr(self._centers), L.dptr(self._egroup),
+               L.dptr(cat._table), L.dptr(cat._labels), L.dptr(raw_fields), self.C, ef.ldc, L.dptr(self._chan), L.dptr(self._bits),
+               _c_int(self.negate_mask), int(self.flip_south), L.dptr(self._rbin), self.NB, L.dptr(self._events), L.dptr(self._sum),
+               L.dptr(self._n), L.dptr(self._inside), L.dptr(self._rsum) if self.NB else None, L.dptr(self._rn) if self.NB else None, st)
+        return self
+
+    @property
+    def centers(self) -> torch.Tensor:
+        """int32 [n_valid, cap] of the last call (a view): the centre pixel r0 * W + c0 of every composited event, -1 elsewhere"""
+        return self._centers[:self._last_valid]
+
+    @property
+    def event_groups(self) -> torch.Tensor:
+        """int32 [n_valid, cap] of the last call (a view): group * (edges + 1) + intensity bin of every composited event, -1 elsewhere"""
+        return self._egroup[:self._last_valid]
+
+    def reset(self) -> None:
+        """zeroes the accumulators and the counts (in stream order)"""
+        for t in (self._events, self._sum, self._n, self._inside, self._rsum, self._rn, self._counts):
+            t.zero_()
+
+    def state(self) -> dict:
+        """the raw integers on the host (COMPOSITE_KEYS) and counts (a dict over COMPOSITE_COUNTS).  Raises when a group has reached
+        COMPOSITE_MAX_EVENTS events: from there on the sums are no longer known to fit their words."""
+        out = {"events": self._events.cpu().numpy(), "sum": self._sum.cpu().numpy(), "n": self._n.cpu().numpy(),
+               "inside": self._inside.cpu().numpy(), "rsum": self._rsum.cpu().numpy(), "rn": self._rn.cpu().numpy()}
+        if int(out["events"].max()) >= COMPOSITE_MAX_EVENTS:
+            raise L.DeepcamHipError(f"StormComposite: a group has reached {COMPOSITE_MAX_EVENTS} events, the bound of the integer sums")
+        out["counts"] = dict(zip(COMPOSITE_COUNTS, (int(v) for v in self._counts.cpu().tolist())))
+        return out
+
+    def composites(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(*(s[k] for k in COMPOSITE_KEYS), self.bits, self.bin_km)
+
+    @staticmethod
+    def decode(events, sum, n, inside, rsum, rn, bits, bin_km: float = 25.0) -> dict:
+        """float64 from the raw integers: mean [GT, S, S, C] = sum * 2^-bits / n, NaN where n == 0; footprint [GT, S, S] = inside /
+        events, NaN where events == 0; radial_mean [GT, NB, C] = rsum * 2^-bits / rn, NaN where rn == 0; radius_km [NB], the bin
+        centres (k + 1/2) * bin_km; radius_of_max_km [GT, C], the centre of the bin with the largest finite radial mean -- the smallest
+        such bin on ties --, NaN where no bin has a value."""
+        bits = np.asarray(bits, np.int32).reshape(-1)
+        events = np.asarray(events, np.int64).reshape(-1)
+        total, n = np.asarray(sum, np.int64).astype(np.float64), np.asarray(n, np.int64).astype(np.float64)
+        rsum, rn = np.asarray(rsum, np.int64).astype(np.float64), np.asarray(rn, np.int64).astype(np.float64)
+        div = lambda a, b: np.where(b != 0, a / np.where(b != 0, b, 1), np.nan)  # noqa: E731
+        radial = div(np.ldexp(rsum, -bits), rn)
+        radius = (np.arange(radial.shape[1]) + 0.5) * float(bin_km)
+        rmax = np.full((radial.shape[0], radial.shape[2]), np.nan)
+        if radial.shape[1]:
+            some = np.isfinite(radial).any(axis=1)
+            first = np.argmax(np.where(np.isfinite(radial), radial, -np.inf), axis=1)    # argmax takes the first among equals
+            rmax = np.where(some, radius[first], np.nan)
+        return {"mean": div(np.ldexp(total, -bits), n), "footprint": div(np.asarray(inside, np.int64).astype(np.float64), events[:, None, None].astype(np.float64)),
+                "radial_mean": radial, "radius_km": radius, "radius_of_max_km": rmax}

@@ -60,6 +60,17 @@ With --event_filter nn.EventFilter drops, on the device, the events of the class
 catalogue behind ``events`` (a second one: the filter's own runs on the raw mask), --verify's prediction side, --event_fields, --tracks,
 --track_fields, --climatology and --plots.  The labels under --verify are not filtered.  ``summary.json`` gains ``event_filter`` (the
 thresholds and per class the events and pixels kept and dropped).
+With --composites (which implies --event_fields) nn.StormComposite accumulates, behind every batch and on the device, the fields in storm
+coordinates: around the --composite_center_stat (min or max) pixel of file channel --composite_center_channel of every event of the
+--composite_classes with at least --composite_min_pixels pixels, a window of 2 * --composite_radius + 1 grid pixels a side of the
+--composite_channels (all file channels by default), southern storms reflected so that "up" is poleward (--composite_no_flip: as they
+lie; --composite_negate: the channels whose sign the reflection reverses, the meridional winds), per group (--composite_by) and per bin
+of the centre value between the --composite_intensity_edges, with the sums per distance bin (--composite_bins bins of
+--composite_bin_km).  At the end ``<output_dir>/composites.h5`` holds the raw integers ``events``, ``sum``, ``n``, ``inside``, ``rsum``,
+``rn``, ``counts`` (int64 [5]: composited, no_center, below_min_pixels, other_class, uncatalogued), ``bits``, ``channels``, ``edges``,
+``group_names`` (uint8: comma-separated ASCII) and the decoded ``mean``, ``footprint``, ``radial_mean``, ``radius_km``,
+``radius_of_max_km``; ``summary.json`` gains ``composites``.  The catalogue is the one the other event products use: under --event_filter
+the filtered one.
 Single process, single device."""
 from __future__ import annotations
 
@@ -135,6 +146,18 @@ class _EventShape(argparse.Action):
         namespace.events = True
 
 
+class _Composites(argparse.Action):
+    """--composites: implies --event_fields and --events"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.composites = True
+        namespace.event_fields = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -195,6 +218,30 @@ def build_parser():
     AP.add_argument("--climatology_channels", type=int, nargs="*", default=[], help="with --climatology: the file channels whose sums are "
                     "kept (36 bytes per pixel, group and channel); none by default: occurrence only")
     AP.add_argument("--climatology_contour", type=float, default=0.1, help="with --climatology and --plots: the frequency whose region is outlined")
+    # the --composite_* flags leave no attribute behind unless given (COMPOSITE_DEFAULTS has their defaults): a namespace without
+    # them is the namespace of before
+    AP.add_argument("--composites", action=_Composites, help="accumulate storm-centred composites on the device (implies --event_fields; "
+                    "needs --composite_center_channel): windows of the raw fields around every event's centre and their radial profiles.  "
+                    "Writes <output_dir>/composites.h5; 'composites' in the summary")
+    S = argparse.SUPPRESS
+    AP.add_argument("--composite_center_channel", type=int, default=S, help="with --composites: the file channel whose extreme is an "
+                    "event's centre (sea-level pressure for cyclones)")
+    AP.add_argument("--composite_center_stat", type=str, default=S, choices=["min", "max"], help="with --composites: which extreme (min)")
+    AP.add_argument("--composite_radius", type=int, default=S, help="with --composites: the window reaches this many grid pixels from the "
+                    "centre (32)")
+    AP.add_argument("--composite_channels", type=int, nargs="+", default=S, help="with --composites: the file channels that are composited "
+                    "(all)")
+    AP.add_argument("--composite_negate", type=int, nargs="*", default=S, help="with --composites: file channels (among --composite_channels) "
+                    "whose sign changes in a reflected southern storm: the meridional wind components (none)")
+    AP.add_argument("--composite_classes", type=int, nargs="+", default=S, choices=[1, 2], help="with --composites: the event classes (1)")
+    AP.add_argument("--composite_min_pixels", type=int, default=S, help="with --composites: leave out events of fewer pixels (0)")
+    AP.add_argument("--composite_by", type=str, default=S, choices=list(dnn.CLIMATOLOGY_GROUPS), help="with --composites: one composite "
+                    "for the whole run, per month or per season, from the first YYYY-MM-DD in every file name (all)")
+    AP.add_argument("--composite_intensity_edges", type=float, nargs="*", default=S, help="with --composites: ascending values of the centre "
+                    "channel that cut the events into intensity bins; an event on an edge goes to the bin above (none)")
+    AP.add_argument("--composite_no_flip", action="store_true", default=S, help="with --composites: do not reflect southern storms")
+    AP.add_argument("--composite_bin_km", type=float, default=S, help="with --composites: the width of a distance bin of the radial profile (25)")
+    AP.add_argument("--composite_bins", type=int, default=S, help="with --composites: the number of distance bins; 0: no radial profile (40)")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -220,6 +267,61 @@ def track_fields_summary(rows: dict, height: int, width: int, center_channel=Non
                                       "frame": word & 0xFFFFFFFF, "lat": float(np.linspace(-90.0, 90.0, height)[p // width]),
                                       "lon": float(np.linspace(-180.0, 180.0, width)[p % width])}
     return out
+
+
+COMPOSITE_DEFAULTS = {"composite_center_channel": None, "composite_center_stat": "min", "composite_radius": 32, "composite_channels": None,
+                      "composite_negate": [], "composite_classes": [1], "composite_min_pixels": 0, "composite_by": "all",
+                      "composite_intensity_edges": [], "composite_no_flip": False, "composite_bin_km": 25.0, "composite_bins": 40}
+
+
+def composite_options(pargs, cfile: int, width: int) -> dict:
+    """the keyword arguments of nn.StormComposite from the --composite_* flags (COMPOSITE_DEFAULTS where one was not given), validated
+    against the files' channel count and the width; --composite_negate names FILE channels and is turned into positions among the
+    selected ones"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in COMPOSITE_DEFAULTS.items()})
+    cc = a.composite_center_channel
+    if cc is None:
+        raise ValueError("--composites needs --composite_center_channel")
+    if not 0 <= int(cc) < cfile:
+        raise ValueError(f"--composite_center_channel must lie in [0, {cfile}), got {cc}")
+    channels = list(range(cfile)) if a.composite_channels is None else [int(c) for c in a.composite_channels]
+    if not 1 <= len(channels) <= 32 or any(not 0 <= c < cfile for c in channels) or len(set(channels)) != len(channels):
+        raise ValueError(f"--composite_channels: between 1 and 32 distinct file channels in [0, {cfile}), got {channels}")
+    negate = [int(c) for c in a.composite_negate]
+    if any(c not in channels for c in negate):
+        raise ValueError(f"--composite_negate: every channel must be one of --composite_channels {channels}, got {negate}")
+    radius = int(a.composite_radius)
+    if not 1 <= radius <= dnn.COMPOSITE_MAX_RADIUS or 2 * radius + 1 > width:
+        raise ValueError(f"--composite_radius must lie in [1, {dnn.COMPOSITE_MAX_RADIUS}] with 2 * radius + 1 <= --width, got {radius}")
+    edges = [float(e) for e in a.composite_intensity_edges]
+    if len(edges) > 255 or not all(np.isfinite(edges)) or any(hi < lo for lo, hi in zip(edges, edges[1:])):
+        raise ValueError(f"--composite_intensity_edges: at most 255 finite ascending values, got {edges}")
+    if a.composite_min_pixels < 0:
+        raise ValueError("--composite_min_pixels must not be negative")
+    if not 0 <= a.composite_bins <= 255 or not a.composite_bin_km > 0:
+        raise ValueError("--composite_bins must lie in [0, 255] and --composite_bin_km be positive")
+    return {"center_channel": int(cc), "center_stat": a.composite_center_stat, "radius": radius, "channels": channels,
+            "classes": tuple(sorted(set(a.composite_classes))), "min_pixels": int(a.composite_min_pixels),
+            "groups": len(dnn.CLIMATOLOGY_GROUPS[a.composite_by]), "intensity_edges": tuple(edges),
+            "flip_south": not a.composite_no_flip, "negate": tuple(channels.index(c) for c in negate),
+            "bin_km": float(a.composite_bin_km), "bins": int(a.composite_bins)}
+
+
+def composite_group_names(by: str, edges) -> list:
+    """the names of the GT composites in their order: the group, then ".bin<k>" when there are intensity edges"""
+    names = dnn.CLIMATOLOGY_GROUPS[by]
+    return [g if not len(edges) else f"{g}.bin{k}" for g in names for k in range(len(edges) + 1)]
+
+
+def composite_summary(by: str, comp_kwargs: dict, state: dict, decoded: dict) -> dict:
+    """the `composites` entry of summary.json: the definition, the counters, the events per composite and, per composite and selected
+    channel, the radius of the largest radial mean (None where there is none)"""
+    clean = lambda a: [None if np.isnan(v) else float(v) for v in a]  # noqa: E731
+    return {"by": by, "group_names": composite_group_names(by, comp_kwargs["intensity_edges"]), "center_channel": comp_kwargs["center_channel"],
+            "center_stat": comp_kwargs["center_stat"], "radius": comp_kwargs["radius"], "channels": list(comp_kwargs["channels"]),
+            "classes": list(comp_kwargs["classes"]), "min_pixels": comp_kwargs["min_pixels"], "intensity_edges": list(comp_kwargs["intensity_edges"]),
+            "flip_south": comp_kwargs["flip_south"], "counts": dict(state["counts"]), "events": [int(v) for v in state["events"]],
+            "radius_of_max_km": [clean(row) for row in decoded["radius_of_max_km"]]}
 
 
 def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
@@ -506,6 +608,13 @@ def main(pargs) -> dict:
         make = lambda: dnn.Climatology(B, H, W, channels=clim_channels, bits=clim_bits, ldc=loader.cfile,  # noqa: E731
                                        groups=len(dnn.CLIMATOLOGY_GROUPS[clim_by]), device=device)
         clim, clim_truth = make(), make() if verify else None
+    # --composites: behind every batch, on the catalogue and the field rows of --event_fields
+    comp = None
+    if getattr(pargs, "composites", False):
+        comp_kwargs = composite_options(pargs, loader.cfile, W)
+        comp_by = getattr(pargs, "composite_by", COMPOSITE_DEFAULTS["composite_by"])
+        comp_bits = [int(v) for v in dnn.composite_bits(dataset.minval, dataset.maxval)[comp_kwargs["channels"]]]
+        comp = dnn.StormComposite(efields, bits=comp_bits, **comp_kwargs)
     seen = 0                                       # input files so far, in the order the batches arrive (sorted names)
 
     free_q: "queue.Queue" = queue.Queue()
@@ -545,6 +654,8 @@ def main(pargs) -> dict:
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
             if tfields is not None:
                 tfields()
+            if comp is not None:
+                comp(loader.raw, groups=[dnn.climatology_group(name, comp_by) for name in names] + [-1] * (B - nv), n_valid=nv)
             if clim is not None:
                 groups = [dnn.climatology_group(name, clim_by) for name in names] + [-1] * (B - nv)
                 raw = loader.raw if clim.C else None
@@ -580,6 +691,7 @@ def main(pargs) -> dict:
     track_rows = tracker.rows() if tracker is not None else None
     cycle_rows = tfields.rows(min_frames=pargs.min_track_frames) if tfields is not None else None
     clim_state = clim.state() if clim is not None else None
+    comp_state = comp.state() if comp is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -625,6 +737,14 @@ def main(pargs) -> dict:
             for name, rgb in pictures.items():
                 png.write_png(os.path.join(pargs.output_dir, "plots", name), rgb)
             summary["climatology"]["plots"] = sorted(pictures)
+    if comp is not None:
+        decoded = dnn.StormComposite.decode(*(comp_state[k] for k in dnn.COMPOSITE_KEYS), comp.bits, comp.bin_km)
+        arrays = {k: comp_state[k] for k in dnn.COMPOSITE_KEYS}
+        arrays.update(decoded, counts=np.asarray([comp_state["counts"][k] for k in dnn.COMPOSITE_COUNTS], np.int64),
+                      bits=np.asarray(comp.bits, np.int32), channels=np.asarray(comp.channels, np.int32), edges=comp.edges,
+                      group_names=np.frombuffer(",".join(composite_group_names(comp_by, comp.edges)).encode(), np.uint8))
+        write_datasets(os.path.join(pargs.output_dir, "composites.h5"), arrays)
+        summary["composites"] = composite_summary(comp_by, comp_kwargs, comp_state, decoded)
     with open(os.path.join(pargs.output_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     line = {"samples": len(records), "class_counts": totals, "seconds": round(elapsed, 4),
