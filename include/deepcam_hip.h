@@ -85,6 +85,8 @@ int dc_reset_options(void);
  *     pixel), climatology_accumulate_scalar (any channel selection, and none), climatology_maps
  *   storm composites (dc_composite_centers, dc_composite_accumulate): composite_centers, composite_accumulate_vec (16-byte loads, four
  *     lanes per 16-channel pixel), composite_accumulate_scalar (any channel selection)
+ *   neighbourhood verification (dc_fss_score): fss_rows (the horizontal box sums of four indicator fields, one packed word per pixel),
+ *     fss_cols (the vertical sliding sums, the squared terms and their reduction), fss_total (the two-word running totals)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -1018,6 +1020,47 @@ int dc_composite_accumulate(int B, int n_valid, int H, int W, int cap, int R, in
                             const int32_t* chan /*may be NULL*/, const int32_t* bits, int negate_mask, int flip_south,
                             const uint8_t* rbin /*may be NULL*/, int NB, int64_t* events, int64_t* sum, int32_t* n, int32_t* inside,
                             int64_t* rsum, int64_t* rn, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Neighbourhood verification (nn.FractionsSkill; predict.py --fss): the integer sums behind the Fractions Skill Score (Roberts & Lean
+ * 2008), FSS = 1 - sum (F - O)^2 / (sum F^2 + sum O^2), per frame, class and window, and their running totals over all frames.  The score
+ * asks at which spatial scale a prediction becomes skilful: a cyclone displaced by a few grid points scores 0 per pixel and may miss
+ * its match per object, yet has FSS (n - d) / n at a window of n > d pixels.  Everything is an integer; the quotient is taken on the host.
+ *   pred, truth  [B][H][W] of 1-, 4- or 8-byte integers (pred_bytes, truth_bytes, as dc_climatology_accumulate takes a mask): 1 and 2
+ *                are the classes, every other value (0, 3, 255, -1, 257, ...) is background
+ *   radius       int32 [S], DEVICE memory (a host pointer would not survive a recorded launch list): window s has n_s = 2 radius[s] + 1
+ *                pixels a side
+ *   wrap         1: columns are taken modulo W (longitude is periodic); 0: columns outside [0, W) contribute 0
+ *   row0, row1   the band of rows that is scored
+ * For frame b < n_valid, class k in {1, 2} and window s: F(i, j) = the number of pixels of pred[b] == k in the n_s x n_s window centred on
+ * (i, j), O(i, j) the same of truth[b]; rows outside [0, H) contribute 0 (zero padding at the poles), also when the window's centre lies
+ * inside the band and part of the window outside it -- the band selects the centres, not the pixels counted.
+ *   rows    int64 [B][2][S][3]   rows[b][k - 1][s] = (A, B, C) = (sum (F - O)^2, sum F^2, sum O^2) over row0 <= i < row1 and all j
+ *   pixels  int64 [B][2][2]      pixels[b][k - 1] = (# pred[b] == k, # truth[b] == k) over the same rows
+ * Both are ZEROED by the call and then written; the rows of frames b >= n_valid stay zero and those frames are not read.
+ *   total         int64 [2][S][3][2]  per class, window and term a TWO-WORD running total (lo, hi) of `rows` over all frames since the
+ *                 caller zeroed it: lo += x, hi += carry -- the value is (hi << 64) | lo with lo taken as unsigned.  One word would not
+ *                 do: at a window of 255 pixels a frame of 768 x 1152 can add 2^51.7 to a term, and 2,500 such frames -- less than two
+ *                 years of six-hourly data -- pass 2^63.
+ *   total_pixels  int64 [2][2], frames int64 [1]: the running sums of `pixels` and of n_valid, plain int64.
+ * A single thread per total walks b = 0 .. n_valid - 1 in order, so the state is the same however a sequence is cut into batches.
+ * Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W < 2^31, 1 <= S <= 16, 0 <= row0 < row1 <= H, 0 <= radius[s] <= 127 (n_s <= 255), and with
+ * wrap also n_s <= W, so that a periodic window counts no column twice.  With n <= 255 a window count is at most 65025, a squared term at
+ * most 2^32 and a frame's sum below 2^63: the int64 rows cannot overflow.  The host checks what it can see; a radius outside its bounds is
+ * the caller's error (the table is on the device): that window is skipped, its rows stay zero, nothing is read or written out of bounds.
+ * The box sum is separable: fss_rows reads both masks, builds per row the prefix sums of the four indicator fields (pred 1, pred 2, truth
+ * 1, truth 2) in LDS and stores the four horizontal window counts, each <= 255, as one packed 32-bit word per pixel into the workspace;
+ * fss_cols slides a window of those words down every column, squares, and reduces to six 64-bit integer atomics per workgroup (integer
+ * sums: order does not matter); fss_total adds the batch to the totals.  One horizontal pass writes every window, a slab per window:
+ *   workspace  dc_fss_workspace(B, H, W, S) bytes = B * S * H * W * 4, 4-byte aligned; 0 = arguments out of range.
+ * dc_fss_block: the columns of a strip and the rows of a segment one workgroup covers (a host function; tests derive shapes from it).
+ * dc_fss_score makes no synchronisation and runs on the caller's stream; a failed argument check sets the message and launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_fss_block(int* cols, int* rows);
+size_t dc_fss_workspace(int B, int H, int W, int S);
+int dc_fss_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int S,
+                 const int32_t* radius /*device*/, int wrap, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
+                 int64_t* total_pixels, int64_t* frames, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -2463,3 +2463,139 @@ class StormComposite:
             rmax = np.where(some, radius[first], np.nan)
         return {"mean": div(np.ldexp(total, -bits), n), "footprint": div(np.asarray(inside, np.int64).astype(np.float64), events[:, None, None].astype(np.float64)),
                 "radial_mean": radial, "radius_km": radius, "radius_of_max_km": rmax}
+
+
+# ---------------------------------------------------------------------------------------------- neighbourhood verification
+FSS_WINDOWS = (1, 3, 9, 17, 33, 65, 129)
+FSS_MAX_WINDOW = 255
+FSS_MAX_WINDOWS = 16
+FSS_MAX_BATCH = 4095
+
+
+def _fss(a: int, b: int, c: int):
+    """1 - A / (B + C) from Python ints by true division (correctly rounded), None where B + C == 0"""
+    return None if b + c == 0 else 1.0 - a / (b + c)
+
+
+def fss_from_rows(rows):
+    """The scores of integer rows [..., 3] = (A, B, C) as nested lists of the leading shape: 1 - A / (B + C) as a Python float from the
+    exact integers, None where B + C == 0 (the class is absent from both masks)."""
+    rows = np.asarray(rows)
+    if rows.shape[-1:] != (3,):
+        raise L.DeepcamHipError(f"fss_from_rows: the last axis must hold (A, B, C), got shape {rows.shape}")
+    flat = rows.reshape(-1, 3).tolist()
+    out = np.empty(len(flat), dtype=object)
+    out[:] = [_fss(int(a), int(b), int(c)) for a, b, c in flat]
+    return out.reshape(rows.shape[:-1]).tolist()
+
+
+class FractionsSkill:
+    """Neighbourhood verification on the device (dc_fss_score, csrc/fss.hip): per frame, class (1, 2) and window of n x n GRID PIXELS the
+    integers (A, B, C) = (sum (F - O)^2, sum F^2, sum O^2), F and O the predicted and labelled pixel counts of the class inside the window
+    around every pixel of the rows row_range = (row0, row1) -- columns periodic with wrap, rows beyond the poles empty -- and their running
+    totals over all frames since reset() as two-word integers.  FSS = 1 - A / (B + C) (Roberts & Lean 2008) is decoded on the host from
+    the exact integers; the pooled score of a run is 1 - sum A / (sum B + sum C).  windows: distinct odd sides in [1, 255], at most 16,
+    with wrap also <= width.  No latitude weighting and no kilometres: row_range is the tool for a tropics-only score.
+    Memory: a workspace of batch * S * height * width * 4 bytes, one packed word per pixel and window (dc_fss_workspace) -- 8 x 768 x 1152
+    at the 7 default windows: 198.2 MB --, beside batch * (2 * S * 3 + 4) * 8 bytes of rows and a few hundred bytes of totals.
+    A call launches on the current stream and does not synchronise; state() and result() read back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, windows: Sequence[int] = FSS_WINDOWS, wrap: bool = True, row_range=None,
+                 device=None):
+        if batch < 1 or batch > FSS_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError(f"FractionsSkill: batch must lie in [1, {FSS_MAX_BATCH}], height and width be positive and height * width below 2^31")
+        windows = [int(n) for n in windows]
+        if not 1 <= len(windows) <= FSS_MAX_WINDOWS:
+            raise L.DeepcamHipError(f"FractionsSkill: between 1 and {FSS_MAX_WINDOWS} windows, got {len(windows)}")
+        for n in windows:
+            if n % 2 == 0 or not 1 <= n <= FSS_MAX_WINDOW:
+                raise L.DeepcamHipError(f"FractionsSkill: a window is an odd number of pixels in [1, {FSS_MAX_WINDOW}], got {n}")
+            if wrap and n > width:
+                raise L.DeepcamHipError(f"FractionsSkill: a periodic window must not be wider than the frame ({width}), got {n}")
+        if len(set(windows)) != len(windows):
+            raise L.DeepcamHipError(f"FractionsSkill: the windows must be distinct, got {windows}")
+        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        if not 0 <= row0 < row1 <= height:
+            raise L.DeepcamHipError(f"FractionsSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
+        self.B, self.H, self.W, self.S = batch, height, width, len(windows)
+        self.windows, self.wrap, self.row_range = windows, bool(wrap), (row0, row1)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._radius = torch.tensor([(n - 1) // 2 for n in windows], dtype=torch.int32, device=dev)
+        dev = self.device = self._radius.device
+        self._rows = torch.zeros((batch, 2, self.S, 3), dtype=torch.int64, device=dev)
+        self._pixels = torch.zeros((batch, 2, 2), dtype=torch.int64, device=dev)
+        self._total = torch.zeros((2, self.S, 3, 2), dtype=torch.int64, device=dev)          # (lo, hi)
+        self._total_pixels = torch.zeros((2, 2), dtype=torch.int64, device=dev)
+        self._frames = torch.zeros((1,), dtype=torch.int64, device=dev)
+        size = L.load().dc_fss_workspace(batch, height, width, self.S)
+        if size == 0:
+            raise L.DeepcamHipError("FractionsSkill: dc_fss_workspace refused the shape")
+        self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
+        self._nv = 0
+
+    def _check(self, t, name: str) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
+                or t.device != self.device or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"FractionsSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
+                                    f"on {self.device}, got {got}")
+
+    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "FractionsSkill":
+        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
+        are not read and their rows are zero."""
+        self._check(pred, "pred")
+        self._check(truth, "truth")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"FractionsSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
+        L.call("dc_fss_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
+               self.S, L.dptr(self._radius), int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
+               L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
+        self._nv = nv
+        return self
+
+    def frame_rows(self):
+        """(int64 [n_valid, 2, S, 3], int64 [n_valid, 2, 2]) of the last call: views of the object's device buffers, not synchronised"""
+        return self._rows[:self._nv], self._pixels[:self._nv]
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for t in (self._total, self._total_pixels, self._frames):
+            t.zero_()
+
+    @staticmethod
+    def combine(total_words) -> list:
+        """[2][S][3] Python ints from the int64 words [2, S, 3, 2] = (lo, hi): (hi << 64) | lo with lo taken as unsigned"""
+        words = np.asarray(total_words, np.int64)
+        if words.ndim != 4 or words.shape[0] != 2 or words.shape[2:] != (3, 2):
+            raise L.DeepcamHipError(f"FractionsSkill: the totals are int64 [2, S, 3, 2], got shape {words.shape}")
+        return [[[(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in term] for term in cls] for cls in words.tolist()]
+
+    def state(self) -> dict:
+        """on the host: total [2][S][3] as Python ints, pixels [2][2] ((pred, truth) per class) and frames as ints"""
+        return {"total": self.combine(self._total.cpu().numpy()), "pixels": [[int(v) for v in row] for row in self._total_pixels.cpu().tolist()],
+                "frames": int(self._frames.cpu()[0])}
+
+    def result(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(s["total"], s["pixels"], s["frames"], self.windows, self.row_range[1] - self.row_range[0], self.W)
+
+    @staticmethod
+    def decode(total, pixels, frames, windows, rows: int, width: int) -> dict:
+        """Per class ("class_1", "class_2"), from the exact integers: fss, a list over the windows of the pooled 1 - sum A / (sum B + sum
+        C), None where sum B + sum C == 0; base_rate = labelled pixels / (frames * rows * width), the share of the scored band the class
+        covers; useful = 0.5 + base_rate / 2, the score above which a forecast is taken as skilful at that scale; skilful_window, the
+        smallest window whose fss >= useful, else None.  Without a frame base_rate, useful and skilful_window are None."""
+        windows = [int(n) for n in windows]
+        cells = int(frames) * int(rows) * int(width)
+        out = {}
+        for k in range(2):
+            scores = [_fss(*(int(v) for v in total[k][s])) for s in range(len(windows))]
+            base = int(pixels[k][1]) / cells if cells > 0 else None
+            useful = None if base is None else 0.5 + base / 2
+            good = [n for n, f in zip(windows, scores) if useful is not None and f is not None and f >= useful]
+            out[f"class_{k + 1}"] = {"fss": scores, "base_rate": base, "useful": useful, "skilful_window": min(good) if good else None}
+        return out

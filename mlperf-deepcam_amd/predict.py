@@ -71,6 +71,13 @@ of the centre value between the --composite_intensity_edges, with the sums per d
 ``group_names`` (uint8: comma-separated ASCII) and the decoded ``mean``, ``footprint``, ``radial_mean``, ``radius_km``,
 ``radius_of_max_km``; ``summary.json`` gains ``composites``.  The catalogue is the one the other event products use: under --event_filter
 the filtered one.
+With --fss (which implies --verify) nn.FractionsSkill scores, behind every batch and on the device, the prediction side of --verify (the
+filtered mask under --event_filter) against the unfiltered labels by neighbourhood: per class and window of --fss_windows grid pixels a
+side (odd; columns periodic unless --fss_no_wrap; centres in the rows --fss_rows I0 I1, the whole frame by default) the integers sum (F -
+O)^2, sum F^2, sum O^2 of the window counts F and O.  Every output file also carries ``fss`` (int64 [2, S, 3]) and ``fss_pixels`` (int64
+[2, 2]: predicted and labelled pixels per class in those rows); ``summary.json`` gains ``fss`` (windows, rows, frames and per class the
+pooled Fractions Skill Score 1 - sum A / (sum B + sum C) per window, the labels' base rate, the useful score 0.5 + base_rate / 2, the
+smallest window that reaches it, and the raw totals as integers).
 Single process, single device."""
 from __future__ import annotations
 
@@ -158,6 +165,18 @@ class _Composites(argparse.Action):
         namespace.events = True
 
 
+class _Fss(argparse.Action):
+    """--fss: implies --verify (and with it --events)"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.fss = True
+        namespace.verify = True
+        namespace.events = True
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -242,6 +261,15 @@ def build_parser():
     AP.add_argument("--composite_no_flip", action="store_true", default=S, help="with --composites: do not reflect southern storms")
     AP.add_argument("--composite_bin_km", type=float, default=S, help="with --composites: the width of a distance bin of the radial profile (25)")
     AP.add_argument("--composite_bins", type=int, default=S, help="with --composites: the number of distance bins; 0: no radial profile (40)")
+    # like the --composite_* flags, the --fss* flags leave no attribute behind unless given (FSS_DEFAULTS has their defaults)
+    AP.add_argument("--fss", action=_Fss, help="neighbourhood verification on the device (implies --verify; the files need climate/labels_0): "
+                    "the Fractions Skill Score of --verify's prediction side against the labels per class and window.  Datasets 'fss', "
+                    "'fss_pixels'; 'fss' in the summary")
+    AP.add_argument("--fss_windows", type=int, nargs="+", default=S, help="with --fss: the windows' sides in grid pixels, distinct odd "
+                    "numbers in [1, 255], at most 16 (1 3 9 17 33 65 129)")
+    AP.add_argument("--fss_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --fss: score the window centres in the "
+                    "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
+    AP.add_argument("--fss_no_wrap", action="store_true", default=S, help="with --fss: do not take the columns as periodic")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -322,6 +350,27 @@ def composite_summary(by: str, comp_kwargs: dict, state: dict, decoded: dict) ->
             "classes": list(comp_kwargs["classes"]), "min_pixels": comp_kwargs["min_pixels"], "intensity_edges": list(comp_kwargs["intensity_edges"]),
             "flip_south": comp_kwargs["flip_south"], "counts": dict(state["counts"]), "events": [int(v) for v in state["events"]],
             "radius_of_max_km": [clean(row) for row in decoded["radius_of_max_km"]]}
+
+
+FSS_DEFAULTS = {"fss": False, "fss_windows": list(dnn.FSS_WINDOWS), "fss_rows": None, "fss_no_wrap": False}
+
+
+def fss_options(pargs) -> dict:
+    """the keyword arguments of nn.FractionsSkill from the --fss_* flags (FSS_DEFAULTS where one was not given)"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in FSS_DEFAULTS.items()})
+    return {"windows": tuple(int(n) for n in a.fss_windows), "wrap": not a.fss_no_wrap,
+            "row_range": None if a.fss_rows is None else (int(a.fss_rows[0]), int(a.fss_rows[1]))}
+
+
+def fss_summary(windows, row_range, width: int, state: dict) -> dict:
+    """the `fss` entry of summary.json from nn.FractionsSkill.state(): the windows, the scored rows, the frames and, per class, the
+    decoded result (pooled scores, base rate, useful score, skilful window) with the raw totals [S][3] as integers"""
+    decoded = dnn.FractionsSkill.decode(state["total"], state["pixels"], state["frames"], windows, row_range[1] - row_range[0], width)
+    out = {"windows": [int(n) for n in windows], "rows": [int(row_range[0]), int(row_range[1])], "frames": int(state["frames"])}
+    for k in range(2):
+        out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], total=[[int(v) for v in term] for term in state["total"][k]],
+                                     pixels=[int(v) for v in state["pixels"][k]])
+    return out
 
 
 def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
@@ -437,7 +486,10 @@ def plot_name(base: str) -> str:
 
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
-                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False):
+                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0):
+        # --fss: the rows of nn.FractionsSkill and the pixel counts beside them
+        self.fss = torch.empty((B, 2, fss_windows, 3), dtype=torch.int64).pin_memory() if fss_windows else None
+        self.fss_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if fss_windows else None
         # --event_shape: the rows of nn.EventShape (cap rows of 96 bytes per sample)
         self.shape = torch.empty((B, event_cap, len(dnn.EVENT_SHAPE_FIELDS)), dtype=torch.int64).pin_memory() if event_shape else None
         # --event_filter: the filtered mask and the filter's counts
@@ -502,6 +554,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                                          event_shape_value_names=np.frombuffer(",".join(dnn.EVENT_SHAPE_VALUES).encode(), np.uint8).copy())
                     if slot.fmask is not None:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
+                    if slot.fss is not None:
+                        extra = dict(extra or {}, fss=slot.fss[j].numpy(), fss_pixels=slot.fss_pixels[j].numpy())
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     if plot[j]:
                         png.write_png(os.path.join(out_dir, "plots", plot_name(base)), slot.rgb[j].numpy())
@@ -608,6 +662,8 @@ def main(pargs) -> dict:
         make = lambda: dnn.Climatology(B, H, W, channels=clim_channels, bits=clim_bits, ldc=loader.cfile,  # noqa: E731
                                        groups=len(dnn.CLIMATOLOGY_GROUPS[clim_by]), device=device)
         clim, clim_truth = make(), make() if verify else None
+    # --fss: behind every batch, the prediction side of --verify against the labels
+    fss = dnn.FractionsSkill(B, H, W, device=device, **fss_options(pargs)) if getattr(pargs, "fss", False) else None
     # --composites: behind every batch, on the catalogue and the field rows of --event_fields
     comp = None
     if getattr(pargs, "composites", False):
@@ -621,7 +677,7 @@ def main(pargs) -> dict:
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
-                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None))
+                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -645,6 +701,10 @@ def main(pargs) -> dict:
                 catalog(dmask, n_valid=nv)
             if verify:
                 matcher(dmask, y, n_valid=nv)
+            if fss is not None:
+                frame_rows, frame_pixels = fss(dmask, y, n_valid=nv).frame_rows()
+                slot.fss[:nv].copy_(frame_rows, non_blocking=True)
+                slot.fss_pixels[:nv].copy_(frame_pixels, non_blocking=True)
             if eshape is not None:
                 slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
             if tracker is not None:
@@ -692,6 +752,7 @@ def main(pargs) -> dict:
     cycle_rows = tfields.rows(min_frames=pargs.min_track_frames) if tfields is not None else None
     clim_state = clim.state() if clim is not None else None
     comp_state = comp.state() if comp is not None else None
+    fss_state = fss.state() if fss is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -709,6 +770,8 @@ def main(pargs) -> dict:
                                    "saturated": sum(r["event_field_counts"][1] for r in records)}
     if verify:
         summary["event_verification"] = verification
+    if fss is not None:
+        summary["fss"] = fss_summary(fss.windows, fss.row_range, W, fss_state)
     if track_rows is not None:
         t_state, t_store, t_of, t_tracks = track_rows
         arrays = {"tracks": t_tracks, "track_events": np.concatenate([t_store, t_of.astype(np.int64)[:, None]], axis=1), "track_state": t_state}
