@@ -129,25 +129,42 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
     hoff[it] = (gok && hp < K::HP) ? (unsigned)((((hy - DIL) * W + (hx - DIL)) * a.ldin + (cg0 + g) * 8) * 2) : OOB;
     hedge |= ((hx < DIL ? 1u : 0u) | (hx >= K::HW - DIL ? 2u : 0u)) << (2 * it);
   }
-  // own-pixel tiles (BatchNorm input, addend, second BatchNorm input): pixel (it * 512 + tid) >> 4 of the 8 x 8 tile, never past an edge
-  unsigned yoff[2], aoff[2], y2off[2];
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int pp = (it * P_THREADS + tid) >> 4;
+  // own-pixel tiles (BatchNorm input, addend, second BatchNorm input): pixel (it * 512 + tid) >> 4 of the 8 x 8 tile, never past an edge.  The
+  // second instruction's pixel lies four rows below the first one's: one offset register per tensor, the four rows go into the tile's origin
+  unsigned yoff, aoff, y2off;
+  {
+    const int pp = tid >> 4;
     const int py = pp >> 3, px = pp & 7;
-    yoff[it] = gok && S::Y ? (unsigned)(((py * W + px) * a.st.ldy + (cg0 + g) * 8) * 2) : OOB;
-    aoff[it] = gok && S::A ? (unsigned)(((py * W + px) * a.ldadd + (cg0 + g) * 8) * 2) : OOB;
-    y2off[it] = gok && S::Y2 ? (unsigned)(((py * W + px) * a.ldy2 + (cg0 + g) * 8) * 2) : OOB;
+    yoff = gok && S::Y ? (unsigned)(((py * W + px) * a.st.ldy + (cg0 + g) * 8) * 2) : OOB;
+    aoff = gok && S::A ? (unsigned)(((py * W + px) * a.ldadd + (cg0 + g) * 8) * 2) : OOB;
+    y2off = gok && S::Y2 ? (unsigned)(((py * W + px) * a.ldy2 + (cg0 + g) * 8) * 2) : OOB;
   }
+  constexpr int ROWS2 = P_THREADS / 16 / P_TW;     // rows of the tile one instruction covers
+
+  // tile id -> (tx, ty, n) is divided out ONCE per launch: the DMA side, the transform and the stencil each walk consecutive tiles and step
+  // a position of their own (three decodes per tile, two divisions each, were 150 of the loop's 200 scalar instructions)
+  struct TilePos { int tx, ty, n; };
+  TilePos p0;
+  {
+    p0.tx = t0 % a.ntx;
+    const int r = t0 / a.ntx;
+    p0.ty = r % a.nty;
+    p0.n = r / a.nty;
+  }
+  auto advance = [&](TilePos& p) {
+    if (++p.tx == a.ntx) {
+      p.tx = 0;
+      if (++p.ty == a.nty) { p.ty = 0; ++p.n; }
+    }
+  };
+  TilePos pi = p0, px = p0, pc = p0;   // next tile to request / to transform / to compute
 
   auto issue = [&](int t, int stage) {
 #if defined(__HIP_DEVICE_COMPILE__)     // (the buffer-resource builtins do not exist in the host pass)
     char* sb = smem + stage * S::BYTES;
-    const bool live = t < t1;
-    const int tt = live ? t : t0;
-    const int tx = tt % a.ntx;
-    const int r = tt / a.ntx;
-    const int ty = r % a.nty, n = r / a.nty;
+    const bool live = t < t1;           // (a dummy request names the tensor's first tile)
+    const int tx = live ? pi.tx : 0, ty = live ? pi.ty : 0, n = live ? pi.n : 0;
+    advance(pi);
     const int y0 = ty * P_TH, x0 = tx * P_TW;
     const int live_mask = live ? -1 : 0;                                     // (scalar) a dummy request: a resource of zero bytes, every lane out of range
     const unsigned emask = (x0 == 0 ? 0x55555555u : 0u) | (x0 + P_TW == W ? 0xAAAAAAAAu : 0u);
@@ -167,21 +184,21 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
       const unsigned torg = (unsigned)((y0 * W + x0) * a.st.ldy * 2);
 #pragma unroll
       for (int it = 0; it < 2; ++it)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + K::HALO + (it * P_THREADS + wv * 64) * 16), 16, yoff[it] + torg, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + K::HALO + (it * P_THREADS + wv * 64) * 16), 16, yoff + (torg + (unsigned)(it * ROWS2 * W * a.st.ldy * 2)), 0, 0, 0);
     }
     if constexpr (S::A) {
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.addend + (size_t)n * H * W * a.ldadd), 0, (H * W * a.ldadd * 2) & live_mask, 0x00020000);
       const unsigned torg = (unsigned)((y0 * W + x0) * a.ldadd * 2);
 #pragma unroll
       for (int it = 0; it < 2; ++it)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + S::OFF_A + (it * P_THREADS + wv * 64) * 16), 16, aoff[it] + torg, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + S::OFF_A + (it * P_THREADS + wv * 64) * 16), 16, aoff + (torg + (unsigned)(it * ROWS2 * W * a.ldadd * 2)), 0, 0, 0);
     }
     if constexpr (S::Y2) {
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.y2 + (size_t)n * H * W * a.ldy2), 0, (H * W * a.ldy2 * 2) & live_mask, 0x00020000);
       const unsigned torg = (unsigned)((y0 * W + x0) * a.ldy2 * 2);
 #pragma unroll
       for (int it = 0; it < 2; ++it)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + S::OFF_Y2 + (it * P_THREADS + wv * 64) * 16), 16, y2off[it] + torg, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)(sb + S::OFF_Y2 + (it * P_THREADS + wv * 64) * 16), 16, y2off + (torg + (unsigned)(it * ROWS2 * W * a.ldy2 * 2)), 0, 0, 0);
     }
 #endif
   };
@@ -233,20 +250,11 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(xsc[e]), "+v"(xsh[e]));
   }
-  auto decode = [&](int t, int& n, int& y0, int& x0) {
-    const int tx = t % a.ntx;
-    const int r = t / a.ntx;
-    const int ty = r % a.nty;
-    n = r / a.nty;
-    y0 = ty * P_TH;
-    x0 = tx * P_TW;
-  };
   // v = act(x * scale + shift) in place on a landed halo tile, once per staged element; the zero padding (out of the image) stays zero
-  auto xform_tile = [&](int t, int stg) {
+  auto xform_tile = [&](int stg) {
     char* sb = smem + stg * S::BYTES;
-    int n, y0, x0;
-    decode(t, n, y0, x0);
-    (void)n;
+    const int y0 = px.ty * P_TH, x0 = px.tx * P_TW;
+    advance(px);
 #pragma unroll
       for (int it = 0; it < K::HIT; ++it) {
         if (it == K::HIT - 1 && wv >= K::LASTW) break;
@@ -274,40 +282,80 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
         }
       }
   };
-  auto compute_tile = [&](int t, int stg) {
+  // a thread's stores of a tile: the tile's first pixel as a 64-bit base the whole workgroup shares plus a 32-bit offset of the thread's own
+  // (its strip's first pixel and channel; an image is smaller than 2 GiB), instead of a 64-bit product chain per store
+  const unsigned ooff = (unsigned)(((row * W + xs) * a.ldout + ch0) * 2), ldob = (unsigned)(a.ldout * 2);
+  auto compute_tile = [&](int stg) {
     char* sb = smem + stg * S::BYTES;
-    int n, y0, x0;
-    decode(t, n, y0, x0);
+    const int n = pc.n, y0 = pc.ty * P_TH, x0 = pc.tx * P_TW;
+    advance(pc);
+    char* ob = reinterpret_cast<char*>(a.out + (((size_t)n * H + y0) * W + x0) * a.ldout);
     // ---- one strip: output row `row`, columns xs .. xs+3
     const char* tile = sb + h * 8;
-    const int oy = y0 + row;
+    const char* own = sb + (row * P_TW + xs) * P_ROWB + h * 8;      // the strip's own pixels in the 8 x 8 tiles behind the halo
+    // (the dilation-2 forms that carry both riders have no registers to spare: there y does not cross the stencil in registers at all but is
+    // read from the stage a second time for the sums, and the addend is read where it is added)
+    constexpr bool LEAN = DIL == 2 && STATS && WGRAD;
     float yf[DT_PX][KH];
+    f32x2 yu[(STATS || WGRAD) ? DT_PX : 1][KH / 2];                  // y*ms + mh: the forward activation's argument (weight gradient, ReLU mask)
+    // the masks of the epilogue (STATS: the ReLU of y*ms + mh, or every lane without one; RES: the stored block output x = yf > 0, or every
+    // lane where that BatchNorm has no ReLU), taken here so that neither yu nor yf has to cross the stencil for them
+    wave_mask pos[(STATS || RES) ? DT_PX : 1][KH];
     if constexpr (S::Y) {
 #pragma unroll
-      for (int j = 0; j < DT_PX; ++j)
-        unpack8(*reinterpret_cast<const vec8*>(sb + K::HALO + (row * P_TW + xs + j) * P_ROWB + h * 8), yf[j], bf16());
+      for (int j = 0; j < DT_PX; ++j) {
+        unpack8(*reinterpret_cast<const vec8*>(own + K::HALO + j * P_ROWB), yf[j], bf16());
+        if constexpr (STATS || WGRAD) {
+#pragma unroll
+          for (int e = 0; e < KH; e += 2) yu[j][e >> 1] = fma2(yf[j], bn.ms, bn.mh, e);
+        }
+        if constexpr (STATS && !(LEAN && ADD)) {
+#pragma unroll
+          for (int e = 0; e < KH; ++e) pos[j][e] = mask_gt0(yu[j][e >> 1][e & 1], a.st.relu ? 0ull : ~0ull);
+        }
+        if constexpr (RES) {
+#pragma unroll
+          for (int e = 0; e < KH; ++e) pos[j][e] = mask_gt0(yf[j][e], (MASK || a.relu2) ? 0ull : ~0ull);
+        }
+      }
+    }
+    // the addend and the second BatchNorm's input at the same pixels, requested with the halo's reads (packed: two registers per pixel)
+    vec8 avp[ADD ? DT_PX : 1], y2p[RES ? DT_PX : 1];
+    if constexpr (ADD && !LEAN) {
+#pragma unroll
+      for (int j = 0; j < DT_PX; ++j) avp[j] = *reinterpret_cast<const vec8*>(own + S::OFF_A + j * P_ROWB);
+    }
+    if constexpr (RES) {
+#pragma unroll
+      for (int j = 0; j < DT_PX; ++j) y2p[j] = *reinterpret_cast<const vec8*>(own + S::OFF_Y2 + j * P_ROWB);
     }
     float xh[WGRAD ? DT_PX : 1][KH];
     if constexpr (WGRAD) {
       // the forward input of this layer at the strip's pixels: act(y*ms + mh) rounded to bf16 exactly as the forward kernel staged it
+      f32x2 v[DT_PX][KH / 2];
 #pragma unroll
-      for (int j = 0; j < DT_PX; ++j) {
-        float v[KH];
+      for (int j = 0; j < DT_PX; ++j)
 #pragma unroll
-        for (int e = 0; e < KH; ++e) {
-          const float u = fmaf(yf[j][e], bn.ms[e], bn.mh[e]);
-          v[e] = a.st.relu ? fmaxf(u, 0.f) : u;
-        }
-        vec8 rr;
-        pack8(rr, v, bf16());
-        unpack8(rr, xh[j], bf16());
+        for (int p = 0; p < KH / 2; ++p) v[j][p] = yu[j][p];
+      if (a.st.relu) {
+        asm volatile("");     // (a branch the whole grid takes alike, kept a branch: as a select it is a second instruction per element)
+#pragma unroll
+        for (int j = 0; j < DT_PX; ++j)
+#pragma unroll
+          for (int p = 0; p < KH / 2; ++p) v[j][p] = f32x2{relu_f32(v[j][p][0]), relu_f32(v[j][p][1])};
       }
+#pragma unroll
+      for (int j = 0; j < DT_PX; ++j)
+#pragma unroll
+        for (int p = 0; p < KH / 2; ++p) round2_bf16(v[j][p][0], v[j][p][1], xh[j][2 * p], xh[j][2 * p + 1]);
     }
-    float acc[DT_PX][KH];
+    // both chains on channel pairs (e, e+1), spelled as vectors so that every mode gets v_pk_fma_f32 (left to the compiler's pairing, the
+    // addend forms came out as scalar FMAs): a fused multiply-add on either half, the bits of the scalar chain
+    f32x2 acc2[DT_PX][KH / 2];
 #pragma unroll
     for (int j = 0; j < DT_PX; ++j)
 #pragma unroll
-      for (int e = 0; e < KH; ++e) acc[j][e] = 0.f;
+      for (int p = 0; p < KH / 2; ++p) acc2[j][p] = f32x2{0.f, 0.f};
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
@@ -316,49 +364,79 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
         unpack8(*reinterpret_cast<const vec8*>(tile + ((row + ky * DIL) * K::HW + xs + c) * P_ROWB), f, bf16());
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
-          const int j = c - kx * DIL;
+          const int j = c - kx * DIL, t9 = ky * 3 + kx;
           if (j >= 0 && j < DT_PX) {
 #pragma unroll
-            for (int e = 0; e < KH; ++e) acc[j][e] = fmaf(f[e], wk[ky * 3 + kx][e], acc[j][e]);
+            for (int p = 0; p < KH / 2; ++p) {
+              const f32x2 fv = {f[2 * p], f[2 * p + 1]};
+              acc2[j][p] = __builtin_elementwise_fma(fv, f32x2{wk[t9][2 * p], wk[t9][2 * p + 1]}, acc2[j][p]);
+            }
             if constexpr (WGRAD) {
 #pragma unroll
-              for (int e = 0; e < KH; ++e) dwa[8 - (ky * 3 + kx)][e] = fmaf(f[e], xh[j][e], dwa[8 - (ky * 3 + kx)][e]);
+              for (int e = 0; e < KH; ++e) dwa[8 - t9][e] = fmaf(f[e], xh[j][e], dwa[8 - t9][e]);
             }
           }
         }
       }
     }
+    float acc[DT_PX][KH];
+#pragma unroll
+    for (int j = 0; j < DT_PX; ++j)
+#pragma unroll
+      for (int e = 0; e < KH; ++e) acc[j][e] = acc2[j][e >> 1][e & 1];
+    typedef __attribute__((address_space(3))) const char lds_cchar;
+    lds_cchar* own2 = (lds_cchar*)own;
+    if constexpr (LEAN) asm("" : "+v"(own2));     // (an address of its own: a second read, not the first one's registers kept alive)
 #pragma unroll
     for (int j = 0; j < DT_PX; ++j) {
       if constexpr (ADD) {
         float av[KH];
-        unpack8(*reinterpret_cast<const vec8*>(sb + S::OFF_A + (row * P_TW + xs + j) * P_ROWB + h * 8), av, bf16());
+        if constexpr (LEAN) avp[j] = *reinterpret_cast<const vec8*>(own + S::OFF_A + j * P_ROWB);
+        unpack8(avp[j], av, bf16());
 #pragma unroll
-        for (int e = 0; e < KH; ++e) acc[j][e] += av[e];
+        for (int p = 0; p < KH / 2; ++p) {      // (on the pair: v_pk_add_f32)
+          const f32x2 s2 = acc2[j][p] + f32x2{av[2 * p], av[2 * p + 1]};
+          acc[j][2 * p] = s2[0];
+          acc[j][2 * p + 1] = s2[1];
+        }
       }
       if constexpr (MASK) {
         // the select the sums below make on the rounded value, made on the sum instead (zero rounds to zero: the same bits as masking the
         // packed halves); the store count per wave and tile, which the vmcnt immediates rely on, stays as it is
 #pragma unroll
-        for (int e = 0; e < KH; ++e) acc[j][e] = yf[j][e] > 0.f ? acc[j][e] : 0.f;
+        for (int e = 0; e < KH; ++e) acc[j][e] = masked(pos[j][e], acc[j][e]);
       }
       vec8 v;
       pack8(v, acc[j], bf16());
       // (exactly STORES store instructions per wave per tile: the `cok` mask never empties a wave, every wave holds all 32 half-groups)
-      if (cok) *reinterpret_cast<vec8*>(a.out + (((size_t)n * H + oy) * W + x0 + xs + j) * a.ldout + ch0) = v;
+      if (cok) *reinterpret_cast<vec8*>(ob + (ooff + (unsigned)j * ldob)) = v;
       if constexpr (STATS) {
+        // BnAcc::add on the stored (rounded) values, the mask's y*ms + mh shared with the weight gradient's
+        if constexpr (LEAN) {
+          const unsigned long long y2w = *reinterpret_cast<__attribute__((address_space(3))) const unsigned long long*>(own2 + K::HALO + j * P_ROWB);
+          vec8 yv;
+          yv.w[0] = (uint32_t)y2w;
+          yv.w[1] = (uint32_t)(y2w >> 32);
+          unpack8(yv, yf[j], bf16());
+        }
         float gs[KH];
         unpack8(v, gs, bf16());
-        bn.add(gs, yf[j], a.st.relu);
+#pragma unroll
+        for (int e = 0; e < KH; ++e) {
+          // (LEAN with an addend: the mask from the second read as well -- its thirty-two scalar registers were the last ones missing)
+          const float gm = (LEAN && ADD) ? ((!a.st.relu || fmaf(yf[j][e], bn.ms[e], bn.mh[e]) > 0.f) ? gs[e] : 0.f) : masked(pos[j][e], gs[e]);
+          bn.a[e] += gm;
+          bn.b[e] = fmaf(gm, (yf[j][e] - bn.mu[e]) * bn.is[e], bn.b[e]);
+        }
       }
       if constexpr (RES) {
         // g = the stored dx masked by the stored block output (yf = x here); xhat from the producing BatchNorm's input
         float gs[KH], y2f[KH];
         unpack8(v, gs, bf16());
-        unpack8(*reinterpret_cast<const vec8*>(sb + S::OFF_Y2 + (row * P_TW + xs + j) * P_ROWB + h * 8), y2f, bf16());
+        unpack8(y2p[j], y2f, bf16());
 #pragma unroll
         for (int e = 0; e < KH; ++e) {
-          const float gm = (MASK || !a.relu2 || yf[j][e] > 0.f) ? gs[e] : 0.f;
+          const float gm = MASK ? gs[e] : masked(pos[j][e], gs[e]);
           ra[e] += gm;
           rb[e] = fmaf(gm, (y2f[e] - mu2[e]) * is2[e], rb[e]);
         }
@@ -367,6 +445,7 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
   };
   int stage = 0;
   if constexpr (!XFORM) {
+#pragma nounroll      // (nor peeled: one copy of the tile loop)
     for (int i = 0; i < nt; ++i) {
       // tile i has landed once all but the youngest [stores of the last min(i, NS-1) tiles + DMAs of tiles i+1 .. i+NS-2] are done
       if (wv < K::LASTW) {
@@ -386,7 +465,7 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
         if (ns >= NS) ns -= NS;
         issue(t0 + i + NS - 1, ns);     // into the stage tile i-1 has just left
       }
-      compute_tile(t0 + i, stage);
+      compute_tile(stage);
       if (++stage == NS) stage = 0;
     }
   } else {
@@ -398,7 +477,8 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
     constexpr int D0 = S::DMAS, D1 = S::DMAS - 1;
     if (wv < K::LASTW) wait_vm<(NS - 2) * D0>(); else wait_vm<(NS - 2) * D1>();     // tile 0
     __builtin_amdgcn_s_barrier();
-    xform_tile(t0, 0);
+    xform_tile(0);
+#pragma nounroll
     for (int i = 0; i < nt; ++i) {
       if (wv < K::LASTW) {
         if (i >= NS - 2) wait_vm<(NS - 2) * S::STORES + (NS - 3) * D0>();
@@ -419,9 +499,9 @@ __global__ __launch_bounds__(P_THREADS) void dwp_kernel(const DwpArgs a) {
       if (i + 1 < nt) {
         int s1 = stage + 1;
         if (s1 == NS) s1 = 0;
-        xform_tile(t0 + i + 1, s1);
+        xform_tile(s1);
       }
-      compute_tile(t0 + i, stage);
+      compute_tile(stage);
       if (++stage == NS) stage = 0;
     }
   }

@@ -38,6 +38,47 @@ __device__ inline void pack8(vec8& v, const float (&f)[4], bf16) {
   v.w[1] = pack2_bf16(f[2], f[3]);
 }
 
+// A pair of fp32 values rounded to bf16 and widened again: the values pack8 + unpack8 give, as ONE v_cvt_pk_bf16_f32, one shift and one
+// mask.  (The empty asm keeps the packed word a value of its own: without it the compiler rewrites the round trip per element -- a
+// conversion, a shift and a mask for each half.)
+__device__ inline void round2_bf16(float lo, float hi, float& rlo, float& rhi) {
+  uint32_t w = pack2_bf16(lo, hi);
+  asm("" : "+v"(w));
+  rlo = __uint_as_float(w << 16);
+  rhi = __uint_as_float(w & 0xffff0000u);
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// x * s + t on channels (e, e+1) as one v_pk_fma_f32: a fused multiply-add on either half, the bits of the scalar fmaf
+template <int KH>
+__device__ inline f32x2 fma2(const float (&x)[KH], const float (&s)[KH], const float (&t)[KH], int e) {
+  const f32x2 xv = {x[e], x[e + 1]}, sv = {s[e], s[e + 1]}, tv = {t[e], t[e + 1]};
+  return __builtin_elementwise_fma(xv, sv, tv);
+}
+
+// max(x, 0) as the ONE v_max_f32 that fmaxf is beside the FMA that feeds it (where a branch lies between the two the compiler puts a second,
+// canonicalizing v_max_f32 in front)
+__device__ inline float relu_f32(float x) {
+  float r;
+  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
+// A per-lane condition held as a WAVE MASK in a scalar register pair, taken where its operand is at hand and applied many instructions
+// later: left to the compiler, `x > 0 ? g : 0` is compared where it is used, and x (a vector register per element) stays alive until then.
+typedef unsigned long long wave_mask;
+__device__ inline wave_mask mask_gt0(float x, wave_mask always = 0) {
+  wave_mask m = __builtin_amdgcn_ballot_w64(x > 0.f) | always;
+  asm("" : "+s"(m));
+  return m;
+}
+// m ? g : 0 per lane, one v_cndmask_b32
+__device__ inline float masked(wave_mask m, float g) {
+  float r;
+  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(g), "s"(m));
+  return r;
+}
+
 template <int KH>
 __device__ inline void load_taps(const float* __restrict__ wp, int ch0, int C, bool flip, float (&wk)[9][KH]) {
 #pragma unroll
