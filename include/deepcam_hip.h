@@ -87,6 +87,9 @@ int dc_reset_options(void);
  *     lanes per 16-channel pixel), composite_accumulate_scalar (any channel selection)
  *   neighbourhood verification (dc_fss_score): fss_rows (the horizontal box sums of four indicator fields, one packed word per pixel),
  *     fss_cols (the vertical sliding sums, the squared terms and their reduction), fss_total (the two-word running totals)
+ *   probabilistic verification (dc_prob_score): prob_zero (this call's outputs), then prob_hist_vec (16-byte loads, H * W a multiple of 4)
+ *     or prob_hist (4-byte loads, any H * W): the joint histogram in LDS, the squared errors and the pixel counters; prob_total (the
+ *     running totals)
  *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -1061,6 +1064,46 @@ size_t dc_fss_workspace(int B, int H, int W, int S);
 int dc_fss_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int S,
                  const int32_t* radius /*device*/, int wrap, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
                  int64_t* total_pixels, int64_t* frames, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Probabilistic verification (nn.ProbabilitySkill; predict.py --prob_skill): the integers behind the reliability diagram, the Brier score
+ * with Murphy's (1973) decomposition, and POD / POFD / CSI per probability threshold with ROC and AUC (Mason 1982), per class, from the
+ * classifier's softmax probabilities -- not from the argmax mask that every other verification family scores.  One joint histogram per
+ * class (probability bin x whether the label is that class, with the sum of the probabilities per cell) and one sum of squared errors
+ * answer all three; the host decodes them (nn.ProbabilitySkill.decode).
+ * Per pixel, with its logits l0, l1, l2 and its label (load_label of csrc/pixel_score.h: 1-, 4- or 8-byte integers, the full value compared):
+ *   p_c   = e_c / se in fp32, (e, se) = softmax_terms(l0, l1, l2, first_max(l0, l1, l2).best)
+ *   q_c   = __float2int_rn(p_c * 65536.f), in [0, 65536]; o_c = (label == c)
+ *   bin_c = min(K - 1, (q_c * K) >> 16): a function of the INTEGER q; the forecast "class c at threshold k / K" is bin_c >= k
+ * A pixel whose label is outside [0, 3) is counted in pixels[b][1] and contributes nothing else; otherwise a pixel with a logit that is
+ * not finite is counted in pixels[b][2] and contributes nothing else; every other pixel is scored and counted in pixels[b][0].  From q on
+ * everything is an integer: equal logits give equal state whatever the schedule and however the frames are cut into batches.
+ *   logits_nchw   fp32 [B][3][H][W]; labels [B][H][W] of label_bytes = 1, 4 or 8
+ *   K             bins, 1 .. 256
+ *   hist          int64 [3][2][K][2]  class, outcome, bin, (n, sum q) over THIS call's frames b < n_valid; zeroed by the call
+ *   rows          int64 [B][3]        per sample and class sum (q_c - o_c * 65536)^2, the Brier score's numerator scaled by 2^32
+ *   pixels        int64 [B][3]        (scored, label outside [0, 3), a logit not finite)
+ *                 rows and pixels of the samples < n_valid are zeroed by the call, in stream order, and then written; the samples
+ *                 >= n_valid are neither read nor written, in any buffer.
+ *   total_hist    int64 [3][2][K][2]  += hist
+ *   total_sq      int64 [3][2]        per class a TWO-WORD running total (lo, hi) of rows, dc_fss_score's convention: lo += x,
+ *                 hi += carry, the value (hi << 64) | lo with lo taken as unsigned.  A frame can add 2^30 * 2^32 = 2^62.
+ *   total_pixels  int64 [3], frames int64 [1]: += pixels, += n_valid
+ * Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W <= 2^30, so that total_hist's sum of q holds 2^63 / (2^30 * 2^16) = 2^17 frames of
+ * the largest size and 2^27 of 768 x 1152.  Pointers are aligned to their element size.
+ * prob_hist gives every workgroup dc_prob_block's `pixels` consecutive pixels of one sample and a private histogram in LDS (64-bit cells,
+ * count << 40 | sum q, which cannot wrap within that many pixels); per class a wave whose scored pixels all fall into one cell adds once,
+ * from one lane; the workgroup flushes its non-zero cells by 64-bit global atomics.  Where H * W is a multiple of 4 and the logits are
+ * 16-byte aligned the loads are 16 bytes wide (prob_hist_vec), else 4 (prob_hist).  prob_zero clears this call's outputs in front of it,
+ * prob_total adds the call to the totals behind it: three launches, with n_valid == 0 only the first.
+ * dc_prob_block: the pixels one workgroup takes, and the cap on the workgroups per sample (0: none -- a workgroup takes one chunk and
+ * ends, there is no grid-stride loop).  A host function; tests derive shapes from it.
+ * dc_prob_score makes no synchronisation and runs on the caller's stream; a failed argument check sets the message and launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_prob_block(int* pixels, int* max_groups);
+int dc_prob_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_bytes, int K, int64_t* hist,
+                  int64_t* rows, int64_t* pixels, int64_t* total_hist, int64_t* total_sq, int64_t* total_pixels, int64_t* frames,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

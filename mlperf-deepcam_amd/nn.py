@@ -1886,6 +1886,11 @@ class Predictor:
         """the engine's fp32 NCHW logits of the last call (fp32 engines always; bf16 with store_logits=True), valid samples only"""
         return self.eng.logits[:self._last_valid]
 
+    @property
+    def logits_buffer(self) -> torch.Tensor:
+        """fp32 [B, 3, H, W]: the whole buffer the logits are written to, padding samples included (what ProbabilitySkill takes)"""
+        return self.eng.logits
+
     def close(self) -> None:
         self.eng.close()
         self._mask = self._conf = self._counts = self.catalog = None
@@ -2598,4 +2603,172 @@ class FractionsSkill:
             useful = None if base is None else 0.5 + base / 2
             good = [n for n, f in zip(windows, scores) if useful is not None and f is not None and f >= useful]
             out[f"class_{k + 1}"] = {"fss": scores, "base_rate": base, "useful": useful, "skilful_window": min(good) if good else None}
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- probabilistic verification
+PROB_BINS = 20
+PROB_MAX_BINS = 256
+PROB_MAX_BATCH = 4095
+PROB_MAX_PIXELS = 1 << 30
+PROB_ONE = 65536                                  # q = rint(p * PROB_ONE)
+
+
+def _ratio(a, b):
+    """a / b as a Python float, None where b == 0"""
+    return None if b == 0 else a / b
+
+
+def brier_from_rows(rows, pixels):
+    """The Brier scores of single frames from ProbabilitySkill.frame_rows(): rows [..., 3] = sum (q_c - o_c * 65536)^2 per class, pixels
+    [..., 3] = (scored, bad label, logit not finite); rows / (scored * 2^32) as nested lists of Python floats of rows' shape, None where no
+    pixel was scored."""
+    rows, pixels = np.asarray(rows), np.asarray(pixels)
+    if rows.shape[-1:] != (3,) or pixels.shape != rows.shape:
+        raise L.DeepcamHipError(f"brier_from_rows: rows and pixels must both be [..., 3], got {rows.shape} and {pixels.shape}")
+    n = pixels.reshape(-1, 3)[:, 0].tolist()
+    out = np.empty((len(n), 3), dtype=object)
+    for i, (row, scored) in enumerate(zip(rows.reshape(-1, 3).tolist(), n)):
+        out[i] = [_ratio(int(v), int(scored) << 32) for v in row]
+    return out.reshape(rows.shape).tolist()
+
+
+class ProbabilitySkill:
+    """Probabilistic verification on the device (dc_prob_score, csrc/probskill.hip): from the classifier's fp32 logits and the labels, per
+    class c the joint histogram of (probability bin, label == c) with the sum of the probabilities per cell, and the sum of the squared
+    errors -- one streaming pass --, as integers: q_c = rint(softmax_c * 65536), bin = min(bins - 1, (q_c * bins) >> 16).  Running totals
+    over all frames since reset(); the squared errors as two-word integers.  decode() turns the integers into the reliability diagram,
+    the Brier score with Murphy's (1973) decomposition, ECE / MCE, and POD / POFD / CSI / bias per threshold k / bins with the ROC area
+    (Mason 1982).  Pixels whose label is outside [0, 3) or whose logits are not finite are counted and left out.  No latitude weighting.
+    Memory: (2 * 3 * 2 * bins * 2 + 2 * batch * 3 + 10) * 8 bytes.  A call launches on the current stream and does not synchronise; state()
+    and result() read back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, bins: int = PROB_BINS, device=None):
+        if batch < 1 or batch > PROB_MAX_BATCH or height < 1 or width < 1 or height * width > PROB_MAX_PIXELS:
+            raise L.DeepcamHipError(f"ProbabilitySkill: batch must lie in [1, {PROB_MAX_BATCH}], height and width be positive and height * width at most 2^30")
+        bins = int(bins)
+        if not 1 <= bins <= PROB_MAX_BINS:
+            raise L.DeepcamHipError(f"ProbabilitySkill: bins must lie in [1, {PROB_MAX_BINS}], got {bins}")
+        self.B, self.H, self.W, self.K = batch, height, width, bins
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._hist = torch.zeros((3, 2, bins, 2), dtype=torch.int64, device=dev)
+        dev = self.device = self._hist.device
+        self._rows = torch.zeros((batch, 3), dtype=torch.int64, device=dev)
+        self._pixels = torch.zeros((batch, 3), dtype=torch.int64, device=dev)
+        self._total_hist = torch.zeros((3, 2, bins, 2), dtype=torch.int64, device=dev)
+        self._total_sq = torch.zeros((3, 2), dtype=torch.int64, device=dev)                  # (lo, hi)
+        self._total_pixels = torch.zeros((3,), dtype=torch.int64, device=dev)
+        self._frames = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._nv = 0
+
+    def _check(self, t, name: str, dtypes, shape) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != shape or not t.is_cuda or t.device != self.device \
+                or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"ProbabilitySkill: {name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor "
+                                    f"{list(shape)} on {self.device}, got {got}")
+
+    def __call__(self, logits: torch.Tensor, labels: torch.Tensor, n_valid: Optional[int] = None) -> "ProbabilitySkill":
+        """logits: contiguous device fp32 [B, 3, H, W]; labels: contiguous device uint8, int32 or int64 [B, H, W]; the frames from n_valid
+        on are not read."""
+        self._check(logits, "logits", (torch.float32,), (self.B, 3, self.H, self.W))
+        self._check(labels, "labels", tuple(self._BYTES), (self.B, self.H, self.W))
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"ProbabilitySkill: n_valid must lie in [0, {self.B}], got {n_valid}")
+        L.call("dc_prob_score", self.B, nv, self.H, self.W, L.dptr(logits), L.dptr(labels), self._BYTES[labels.dtype], self.K,
+               L.dptr(self._hist), L.dptr(self._rows), L.dptr(self._pixels), L.dptr(self._total_hist), L.dptr(self._total_sq),
+               L.dptr(self._total_pixels), L.dptr(self._frames), L.stream_ptr())
+        self._nv = nv
+        return self
+
+    def frame_rows(self):
+        """(int64 [n_valid, 3], int64 [n_valid, 3]) of the last call: per frame and class the sum of squared errors, and the pixel
+        counters (scored, bad label, not finite); views of the object's device buffers, not synchronised"""
+        return self._rows[:self._nv], self._pixels[:self._nv]
+
+    def batch_hist(self) -> torch.Tensor:
+        """int64 [3, 2, bins, 2] of the last call: class, outcome, bin, (n, sum q); the object's device buffer, not synchronised"""
+        return self._hist
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for t in (self._total_hist, self._total_sq, self._total_pixels, self._frames):
+            t.zero_()
+
+    @staticmethod
+    def combine(words) -> list:
+        """[3] Python ints from the int64 words [3, 2] = (lo, hi): (hi << 64) | lo with lo taken as unsigned (FractionsSkill's convention)"""
+        words = np.asarray(words, np.int64)
+        if words.shape != (3, 2):
+            raise L.DeepcamHipError(f"ProbabilitySkill: the squared-error totals are int64 [3, 2], got shape {words.shape}")
+        return [(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in words.tolist()]
+
+    def state(self) -> dict:
+        """on the host: hist int64 [3, 2, bins, 2], sq [3] as Python ints, pixels [3] and frames as ints"""
+        return {"hist": self._total_hist.cpu().numpy(), "sq": self.combine(self._total_sq.cpu().numpy()),
+                "pixels": [int(v) for v in self._total_pixels.cpu().tolist()], "frames": int(self._frames.cpu()[0])}
+
+    def result(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(s["hist"], s["sq"], s["pixels"], self.K)
+
+    @staticmethod
+    def decode(hist, sq, pixels, bins: int) -> dict:
+        """Per class ("class_0", "class_1", "class_2"), in float64 from the exact integers hist [3][2][bins][2] = (n, sum q) per (outcome,
+        bin), sq [3] and pixels [3]:
+          n, base_rate (o = labelled share), mean_probability, brier = sq / (n * 2^32), brier_skill = 1 - brier / (o (1 - o)),
+          reliability = sum_k n_k (f_k - o_k)^2 / n, resolution = sum_k n_k (o_k - o)^2 / n, uncertainty = o (1 - o) (Murphy 1973; f_k =
+          sum q / n_k / 65536 the bin's mean forecast, o_k its observed frequency), ece = sum_k n_k |f_k - o_k| / n, mce = max_k |f_k - o_k|,
+          curve {mean_probability, observed_frequency, n} per bin, sharpness n_k / n per bin,
+          pod, pofd, csi, bias at the thresholds k / bins, k = 0 .. bins (the forecast is "bin >= k": k = 0 says yes everywhere, k = bins
+          nowhere), auc by trapezoids over the (pofd, pod) points, best_csi and best_csi_threshold (the smallest among equals).
+        A value is None where its denominator is zero.  "pixels" holds the three counters."""
+        K = int(bins)
+        h = np.asarray(hist, np.int64)
+        if h.shape != (3, 2, K, 2):
+            raise L.DeepcamHipError(f"ProbabilitySkill.decode: hist must be [3, 2, {K}, 2], got {h.shape}")
+        h = h.tolist()
+        out = {"bins": K, "pixels": {"scored": int(pixels[0]), "bad_label": int(pixels[1]), "not_finite": int(pixels[2])}}
+        for c in range(3):
+            n0, n1 = [cell[0] for cell in h[c][0]], [cell[0] for cell in h[c][1]]
+            qk = [a[1] + b[1] for a, b in zip(h[c][0], h[c][1])]
+            nk = [a + b for a, b in zip(n0, n1)]
+            N0, N1 = sum(n0), sum(n1)
+            N = N0 + N1
+            base = _ratio(N1, N)
+            unc = None if base is None else base * (1.0 - base)
+            brier = _ratio(int(sq[c]), N << 32)
+            fk = [_ratio(q, n * PROB_ONE) for q, n in zip(qk, nk)]
+            ok = [_ratio(o, n) for o, n in zip(n1, nk)]
+            full = [k for k in range(K) if nk[k]]
+            rel = res = ece = mce = None
+            if N:
+                rel = sum(nk[k] * (fk[k] - ok[k]) ** 2 for k in full) / N
+                res = sum(nk[k] * (ok[k] - base) ** 2 for k in full) / N
+                ece = sum(nk[k] * abs(fk[k] - ok[k]) for k in full) / N
+                mce = max(abs(fk[k] - ok[k]) for k in full)
+            hits, alarms = [0] * (K + 1), [0] * (K + 1)     # labelled / unlabelled pixels in the bins >= k
+            for k in range(K - 1, -1, -1):
+                hits[k], alarms[k] = hits[k + 1] + n1[k], alarms[k + 1] + n0[k]
+            pod = [_ratio(a, N1) for a in hits]
+            pofd = [_ratio(b, N0) for b in alarms]
+            csi = [_ratio(a, N1 + b) for a, b in zip(hits, alarms)]          # hits / (hits + misses + false alarms)
+            bias = [_ratio(a + b, N1) for a, b in zip(hits, alarms)]
+            auc = None
+            if N0 and N1:
+                auc = sum((pofd[k] - pofd[k + 1]) * (pod[k] + pod[k + 1]) / 2 for k in range(K))
+            best = None
+            for k in range(K + 1):
+                if csi[k] is not None and (best is None or csi[k] > csi[best]):
+                    best = k
+            out[f"class_{c}"] = {
+                "n": N, "base_rate": base, "mean_probability": _ratio(sum(qk), N * PROB_ONE), "brier": brier,
+                "brier_skill": None if brier is None or not unc else 1.0 - brier / unc, "reliability": rel, "resolution": res,
+                "uncertainty": unc, "ece": ece, "mce": mce, "curve": {"mean_probability": fk, "observed_frequency": ok, "n": nk},
+                "sharpness": [_ratio(n, N) for n in nk], "pod": pod, "pofd": pofd, "csi": csi, "bias": bias, "auc": auc,
+                "best_csi": None if best is None else csi[best], "best_csi_threshold": None if best is None else best / K}
         return out

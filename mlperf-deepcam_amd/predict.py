@@ -78,6 +78,14 @@ O)^2, sum F^2, sum O^2 of the window counts F and O.  Every output file also car
 [2, 2]: predicted and labelled pixels per class in those rows); ``summary.json`` gains ``fss`` (windows, rows, frames and per class the
 pooled Fractions Skill Score 1 - sum A / (sum B + sum C) per window, the labels' base rate, the useful score 0.5 + base_rate / 2, the
 smallest window that reaches it, and the raw totals as integers).
+With --prob_skill (which implies --verify) nn.ProbabilitySkill scores, behind every batch and on the device, the classifier's softmax
+probabilities -- the stored fp32 logits, never the mask, so --event_filter does not change them -- against the unfiltered labels: per
+class the joint histogram of (probability bin of --prob_bins bins, label is the class) with the sum of the probabilities per cell, and the
+sum of squared errors, as integers (q = rint(p * 65536)).  Every output file also carries ``brier`` (float64 [3], NaN where no pixel was
+scored) and ``prob_pixels`` (int64 [3]: scored, label outside [0, 3), a logit not finite); ``<output_dir>/prob_skill.h5`` holds the raw
+integers ``hist``, ``sq_words``, ``pixels``, ``frames``, ``bins`` and the decoded curves per class (reliability diagram, sharpness, POD /
+POFD / CSI / bias per threshold, and ``scalars`` named by ``scalar_names``); ``summary.json`` gains ``prob_skill`` (per class brier,
+brier_skill, reliability, resolution, ece, auc, best_csi_threshold, base_rate).
 Single process, single device."""
 from __future__ import annotations
 
@@ -177,6 +185,29 @@ class _Fss(argparse.Action):
         namespace.events = True
 
 
+class _ProbSkill(argparse.Action):
+    """--prob_skill: implies --verify (and with it --events)"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.prob_skill = True
+        namespace.verify = True
+        namespace.events = True
+
+
+def _prob_bins(text: str) -> int:
+    """--prob_bins: an integer in [1, 256]"""
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--prob_bins takes an integer, got {text!r}")
+    if not 1 <= k <= dnn.PROB_MAX_BINS:
+        raise argparse.ArgumentTypeError(f"--prob_bins must lie in [1, {dnn.PROB_MAX_BINS}], got {k}")
+    return k
+
+
 def build_parser():
     AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
@@ -270,6 +301,14 @@ def build_parser():
     AP.add_argument("--fss_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --fss: score the window centres in the "
                     "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     AP.add_argument("--fss_no_wrap", action="store_true", default=S, help="with --fss: do not take the columns as periodic")
+    # likewise the --prob_* flags (PROB_DEFAULTS)
+    AP.add_argument("--prob_skill", action=_ProbSkill, help="probabilistic verification on the device (implies --verify; the files need "
+                    "climate/labels_0): reliability diagram, Brier score with its decomposition, POD / POFD / CSI per probability threshold "
+                    "and ROC area per class, from the classifier's softmax probabilities against the labels.  It always scores the "
+                    "classifier's probabilities: --event_filter does not change them.  Datasets 'brier', 'prob_pixels'; prob_skill.h5; "
+                    "'prob_skill' in the summary")
+    AP.add_argument("--prob_bins", type=_prob_bins, default=S, help="with --prob_skill: the probability bins, 1 .. 256; the thresholds are "
+                    "k / bins (20)")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -371,6 +410,44 @@ def fss_summary(windows, row_range, width: int, state: dict) -> dict:
         out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], total=[[int(v) for v in term] for term in state["total"][k]],
                                      pixels=[int(v) for v in state["pixels"][k]])
     return out
+
+
+PROB_DEFAULTS = {"prob_skill": False, "prob_bins": dnn.PROB_BINS}
+PROB_SUMMARY_KEYS = ("brier", "brier_skill", "reliability", "resolution", "ece", "auc", "best_csi_threshold", "base_rate")
+PROB_SCALARS = ("n", "base_rate", "mean_probability", "brier", "brier_skill", "reliability", "resolution", "uncertainty", "ece", "mce", "auc",
+                "best_csi", "best_csi_threshold")
+
+
+def prob_options(pargs) -> dict:
+    """the keyword arguments of nn.ProbabilitySkill from the --prob_* flags (PROB_DEFAULTS where one was not given)"""
+    return {"bins": int(getattr(pargs, "prob_bins", PROB_DEFAULTS["prob_bins"]))}
+
+
+def prob_summary(bins: int, state: dict) -> dict:
+    """the `prob_skill` entry of summary.json from nn.ProbabilitySkill.state(): bins, frames, the pixel counters and, per class, the
+    scalar scores of decode() named in PROB_SUMMARY_KEYS"""
+    decoded = dnn.ProbabilitySkill.decode(state["hist"], state["sq"], state["pixels"], bins)
+    out = {"bins": int(bins), "frames": int(state["frames"]), "pixels": decoded["pixels"]}
+    for c in range(3):
+        out[f"class_{c}"] = {k: decoded[f"class_{c}"][k] for k in PROB_SUMMARY_KEYS}
+    return out
+
+
+def prob_arrays(bins: int, state: dict) -> dict:
+    """the datasets of prob_skill.h5: the raw integers (the squared errors as (lo, hi) words) and decode()'s curves, None as NaN"""
+    decoded = dnn.ProbabilitySkill.decode(state["hist"], state["sq"], state["pixels"], bins)
+    per_class = [decoded[f"class_{c}"] for c in range(3)]
+    real = lambda rows: np.asarray([[np.nan if v is None else float(v) for v in row] for row in rows], np.float64)  # noqa: E731
+    words = [[(v & 0xFFFFFFFFFFFFFFFF) - ((v & (1 << 63)) << 1), v >> 64] for v in (int(v) for v in state["sq"])]
+    return {"hist": np.asarray(state["hist"], np.int64), "sq_words": np.asarray(words, np.int64),
+            "pixels": np.asarray(state["pixels"], np.int64), "frames": np.asarray([state["frames"]], np.int64),
+            "bins": np.asarray([bins], np.int32),
+            "curve_mean_probability": real(d["curve"]["mean_probability"] for d in per_class),
+            "curve_observed_frequency": real(d["curve"]["observed_frequency"] for d in per_class),
+            "curve_n": np.asarray([d["curve"]["n"] for d in per_class], np.int64), "sharpness": real(d["sharpness"] for d in per_class),
+            "pod": real(d["pod"] for d in per_class), "pofd": real(d["pofd"] for d in per_class), "csi": real(d["csi"] for d in per_class),
+            "bias": real(d["bias"] for d in per_class), "scalars": real([d[k] for k in PROB_SCALARS] for d in per_class),
+            "scalar_names": np.frombuffer(",".join(PROB_SCALARS).encode(), np.uint8).copy()}
 
 
 def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
@@ -486,7 +563,11 @@ def plot_name(base: str) -> str:
 
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
-                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0):
+                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
+                 prob_skill: bool = False):
+        # --prob_skill: the squared-error rows of nn.ProbabilitySkill and the pixel counters beside them
+        self.prob_rows = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
+        self.prob_pixels = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
         # --fss: the rows of nn.FractionsSkill and the pixel counts beside them
         self.fss = torch.empty((B, 2, fss_windows, 3), dtype=torch.int64).pin_memory() if fss_windows else None
         self.fss_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if fss_windows else None
@@ -556,6 +637,10 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
                     if slot.fss is not None:
                         extra = dict(extra or {}, fss=slot.fss[j].numpy(), fss_pixels=slot.fss_pixels[j].numpy())
+                    if slot.prob_rows is not None:
+                        brier = dnn.brier_from_rows(slot.prob_rows[j].numpy(), slot.prob_pixels[j].numpy())
+                        extra = dict(extra or {}, brier=np.asarray([np.nan if v is None else v for v in brier], np.float64),
+                                     prob_pixels=slot.prob_pixels[j].numpy())
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     if plot[j]:
                         png.write_png(os.path.join(out_dir, "plots", plot_name(base)), slot.rgb[j].numpy())
@@ -664,6 +749,11 @@ def main(pargs) -> dict:
         clim, clim_truth = make(), make() if verify else None
     # --fss: behind every batch, the prediction side of --verify against the labels
     fss = dnn.FractionsSkill(B, H, W, device=device, **fss_options(pargs)) if getattr(pargs, "fss", False) else None
+    # --prob_skill: behind every batch, the classifier's stored logits against the labels
+    prob = None
+    if getattr(pargs, "prob_skill", False):
+        prob = dnn.ProbabilitySkill(B, H, W, device=device, **prob_options(pargs))
+        predictor.store_logits = True              # bf16 keeps the logits in registers unless asked
     # --composites: behind every batch, on the catalogue and the field rows of --event_fields
     comp = None
     if getattr(pargs, "composites", False):
@@ -677,7 +767,8 @@ def main(pargs) -> dict:
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
-                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0))
+                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
+                             prob is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -705,6 +796,10 @@ def main(pargs) -> dict:
                 frame_rows, frame_pixels = fss(dmask, y, n_valid=nv).frame_rows()
                 slot.fss[:nv].copy_(frame_rows, non_blocking=True)
                 slot.fss_pixels[:nv].copy_(frame_pixels, non_blocking=True)
+            if prob is not None:
+                prob_rows, prob_pixels = prob(predictor.logits_buffer, y, n_valid=nv).frame_rows()
+                slot.prob_rows[:nv].copy_(prob_rows, non_blocking=True)
+                slot.prob_pixels[:nv].copy_(prob_pixels, non_blocking=True)
             if eshape is not None:
                 slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
             if tracker is not None:
@@ -753,6 +848,7 @@ def main(pargs) -> dict:
     clim_state = clim.state() if clim is not None else None
     comp_state = comp.state() if comp is not None else None
     fss_state = fss.state() if fss is not None else None
+    prob_state = prob.state() if prob is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -772,6 +868,9 @@ def main(pargs) -> dict:
         summary["event_verification"] = verification
     if fss is not None:
         summary["fss"] = fss_summary(fss.windows, fss.row_range, W, fss_state)
+    if prob is not None:
+        write_datasets(os.path.join(pargs.output_dir, "prob_skill.h5"), prob_arrays(prob.K, prob_state))
+        summary["prob_skill"] = prob_summary(prob.K, prob_state)
     if track_rows is not None:
         t_state, t_store, t_of, t_tracks = track_rows
         arrays = {"tracks": t_tracks, "track_events": np.concatenate([t_store, t_of.astype(np.int64)[:, None]], axis=1), "track_state": t_state}
