@@ -90,7 +90,10 @@ int dc_reset_options(void);
  *   probabilistic verification (dc_prob_score): prob_zero (this call's outputs), then prob_hist_vec (16-byte loads, H * W a multiple of 4)
  *     or prob_hist (4-byte loads, any H * W): the joint histogram in LDS, the squared errors and the pixel counters; prob_total (the
  *     running totals)
- *   aux                                     every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
+ *   decision rule (dc_logits_decide, dc_hysteresis_select): decide_q_vec (16-byte loads and 32-bit stores, H * W a multiple of 4) or
+ *     decide_q (4-byte loads, byte stores, any H * W): candidates, seeds and their counters; decide_mark (a seed flags its component's
+ *     root), decide_select (the mask of the flagged components, the kept pixels and the events)
+ *   aux                                  every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
 
@@ -1104,6 +1107,50 @@ int dc_prob_block(int* pixels, int* max_groups);
 int dc_prob_score(int B, int n_valid, int H, int W, const float* logits_nchw, const void* labels, int label_bytes, int K, int64_t* hist,
                   int64_t* rows, int64_t* pixels, int64_t* total_hist, int64_t* total_sq, int64_t* total_pixels, int64_t* frames,
                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The decision rule (nn.DecisionRule; predict.py --decision_low / --decision_high / --decision_from): a mask from the stored logits by
+ * per-class probability thresholds, with hysteresis -- instead of the argmax, which the class weights of the training bias on purpose.
+ * dc_prob_score measures what every threshold would give; this applies one.  Per pixel with its logits l0, l1, l2:
+ *   q_c        dc_prob_score's integer, by the same inline function (csrc/pixel_score.h: prob_q): p_c = e_c / se in fp32 with (e, se) =
+ *              softmax_terms(l, first_max(l).best), q_c = __float2int_rn(p_c * 65536.f), in [0, 65536]
+ *   the rule   four integers in [0, 65537]: low[1], low[2], high[1], high[2] with high[c] >= low[c]; 65537 means "never"
+ *   candidate  class c in {1, 2} QUALIFIES iff q_c >= low[c].  cand is 0 if neither class qualifies, the qualifying class if only one
+ *              does, and the class with the larger q if both do; class 1 wins on equal q
+ *   seed       the pixel is a seed iff cand = c != 0 and q_c >= high[c]; a pixel that lost the conflict is no seed of the class that lost
+ *   non-finite a pixel with any logit that is NaN or an infinity is background, is no seed, and is counted
+ *   out        out[p] = cand[p] iff the connected component of cand that holds p contains at least one seed, else 0; the component is
+ *              dc_mask_components': one class, connectivity 4 or 8, columns periodic with wrap, rows never
+ * With high == low for both classes every candidate is a seed and out == cand: plain thresholding, for which the caller runs no
+ * component pass.  dc_prob_score's forecast "class c at threshold k / K", min(K - 1, (q * K) >> 16) >= k, is q >= ceil(k * 65536 / K) for
+ * k < K and "never" for k = K (nn.decision_q_from_bin): a threshold read off its table reproduces the scored forecast bit for bit.
+ *   logits_nchw  fp32 [B][3][H][W]
+ *   cand, seed   uint8 [B][H][W]: the candidate class; 1 at a seed.  seed may be NULL iff high == low for both classes
+ *   labels       int32 [B][H][W], what dc_mask_components left for cand on the same stream
+ *   flags        uint8 [B][H][W] (dc_decide_workspace bytes), indexed by root (label - 1): zeroed by dc_hysteresis_select in stream order
+ *                for the samples below n_valid, then 1 at the root of every component that holds a seed.  By root, not by rank: there is
+ *                no event cap anywhere in this path
+ *   out_mask     uint8 [B][H][W]; may not alias cand
+ *   counts       int64 [B][12]: words 0-4 for class 1 -- candidate pixels, seed pixels, kept pixels, candidate events, kept events --,
+ *                words 5-9 the same for class 2, word 10 the pixels with a non-finite logit, word 11 the pixels where both classes
+ *                qualified.  dc_logits_decide zeroes the rows of the samples below n_valid and fills the candidate, seed, non-finite and
+ *                conflict words; dc_hysteresis_select adds the kept pixels and, counted at root pixels, the events.  On the
+ *                plain-threshold route the caller copies candidate pixels into kept pixels and the event words stay 0
+ * dc_logits_decide is one streaming pass: a workgroup takes dc_decide_block's `pixels` consecutive pixels of one sample and ends.  Where
+ * H * W is a multiple of 4, the logits are 16-byte aligned and cand and seed 4-byte aligned, the loads are 16 bytes wide and four pixels
+ * leave in one 32-bit store per plane (decide_q_vec), else 4-byte loads and byte stores (decide_q).  The counters go through ballots and
+ * one workgroup reduction; there are no per-pixel atomics.  dc_hysteresis_select makes two launches: decide_mark, in which every seed
+ * pixel stores 1 at its root's flag (all writers of a byte write the same value, so a plain store serves), and decide_select.
+ * Samples from n_valid on are neither read nor written, in any buffer; n_valid == 0 launches nothing; nothing synchronises; a failed
+ * argument check sets the message and launches nothing.  Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W <= 2^30, pointers aligned to
+ * their element size.  dc_decide_block and dc_decide_workspace (0: arguments out of range) are host functions.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_decide_block(int* pixels);
+size_t dc_decide_workspace(int B, int H, int W);
+int dc_logits_decide(int B, int n_valid, int H, int W, const float* logits_nchw, int low1, int low2, int high1, int high2, uint8_t* cand,
+                     uint8_t* seed /*may be NULL iff high == low*/, int64_t* counts /*[B][12]*/, void* stream);
+int dc_hysteresis_select(int B, int n_valid, int H, int W, const uint8_t* cand, const uint8_t* seed, const int32_t* labels, uint8_t* flags,
+                         uint8_t* out_mask, int64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -43,6 +43,21 @@ __device__ inline SoftmaxTerms softmax_terms(float l0, float l1, float l2, float
   return t;
 }
 
+// The quantised probabilities q_c = rint(p_c * 65536) in [0, 65536], p_c = e_c / se in fp32: the ONE chain from logits to q.  What
+// probskill.hip bins and scores and what decide.hip thresholds, so that a threshold read off the former's table reproduces its
+// forecast bit for bit.
+struct ProbQ {
+  int q0, q1, q2;
+};
+__device__ inline ProbQ prob_q(float l0, float l1, float l2) {
+  const FirstMax m = first_max(l0, l1, l2);
+  const SoftmaxTerms s = softmax_terms(l0, l1, l2, m.best);
+  return {__float2int_rn(s.e0 / s.se * 65536.f), __float2int_rn(s.e1 / s.se * 65536.f), __float2int_rn(s.e2 / s.se * 65536.f)};
+}
+// neither NaN nor an infinity, in all three (the exponent bits)
+__device__ inline bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+__device__ inline bool logits_finite(float l0, float l1, float l2) { return finite_bits(l0) && finite_bits(l1) && finite_bits(l2); }
+
 struct ClassWeights {
   float w0, w1, w2;
 };

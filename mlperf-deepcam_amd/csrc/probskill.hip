@@ -47,8 +47,6 @@ __device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
   return v;
 }
 
-__device__ inline bool ps_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
 template <bool VEC>
 __global__ __launch_bounds__(PS_THREADS) void prob_hist_kernel(long HW, const float* __restrict__ logits, const void* __restrict__ labels,
                                                                int lbytes, int K, unsigned long long* __restrict__ hist,
@@ -100,14 +98,11 @@ __global__ __launch_bounds__(PS_THREADS) void prob_hist_kernel(long HW, const fl
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool badl = ok[j] && y[j] < 0;
-      const bool nonf = ok[j] && y[j] >= 0 && !(ps_finite(l[0][j]) && ps_finite(l[1][j]) && ps_finite(l[2][j]));
+      const bool nonf = ok[j] && y[j] >= 0 && !logits_finite(l[0][j], l[1][j], l[2][j]);
       sc[j] = ok[j] && !badl && !nonf;
       px[0] += wave_count(sc[j]), px[1] += wave_count(badl), px[2] += wave_count(nonf);
-      const FirstMax m = first_max(l[0][j], l[1][j], l[2][j]);
-      const SoftmaxTerms s = softmax_terms(l[0][j], l[1][j], l[2][j], m.best);
-      q[0][j] = __float2int_rn(s.e0 / s.se * 65536.f);
-      q[1][j] = __float2int_rn(s.e1 / s.se * 65536.f);
-      q[2][j] = __float2int_rn(s.e2 / s.se * 65536.f);
+      const ProbQ pq = prob_q(l[0][j], l[1][j], l[2][j]);
+      q[0][j] = pq.q0, q[1][j] = pq.q1, q[2][j] = pq.q2;
     }
     const unsigned long long any = __ballot(sc[0] || sc[1] || sc[2] || sc[3]);
     if (any == 0) continue;                         // wave-uniform

@@ -192,6 +192,10 @@ _SIGS = {
     "dc_fss_score": (I, [I, I, I, I, P, I, P, I, I, P, I, I, I, P, P, P, P, P, P, P]),
     "dc_prob_block": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_prob_score": (I, [I, I, I, I, P, P, I, I, P, P, P, P, P, P, P, P]),
+    "dc_decide_block": (I, [C.POINTER(I)]),
+    "dc_decide_workspace": (SZ, [I, I, I]),
+    "dc_logits_decide": (I, [I, I, I, I, P, I, I, I, I, P, P, P, P]),
+    "dc_hysteresis_select": (I, [I, I, I, I, P, P, P, P, P, P, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

@@ -2772,3 +2772,153 @@ class ProbabilitySkill:
                 "sharpness": [_ratio(n, N) for n in nk], "pod": pod, "pofd": pofd, "csi": csi, "bias": bias, "auc": auc,
                 "best_csi": None if best is None else csi[best], "best_csi_threshold": None if best is None else best / K}
         return out
+
+
+# ---------------------------------------------------------------------------------------------- decision rule
+DECISION_NEVER = PROB_ONE + 1                     # a threshold no q reaches
+DECISION_COUNTS = ("class1_candidate_pixels", "class1_seed_pixels", "class1_kept_pixels", "class1_candidate_events", "class1_kept_events",
+                   "class2_candidate_pixels", "class2_seed_pixels", "class2_kept_pixels", "class2_candidate_events", "class2_kept_events",
+                   "nonfinite_pixels", "conflict_pixels")
+
+
+def decision_q(p) -> int:
+    """The threshold on q = rint(softmax * 65536) for the probability p: ceil(p * 65536) clamped to [0, 65537], so that q >= decision_q(p)
+    iff q / 65536 >= p.  p > 1 gives 65537: never."""
+    p = float(p)
+    if math.isnan(p):
+        raise L.DeepcamHipError("decision_q: the probability is NaN")
+    if p > 1.0:
+        return DECISION_NEVER
+    return max(0, int(math.ceil(p * PROB_ONE)))
+
+
+def decision_q_from_bin(k: int, bins: int) -> int:
+    """The threshold on q that reproduces ProbabilitySkill's forecast "class c at threshold k / bins", min(bins - 1, (q * bins) >> 16) >= k:
+    ceil(k * 65536 / bins) for k < bins, 65537 (never) for k == bins."""
+    k, bins = int(k), int(bins)
+    if not 1 <= bins <= PROB_MAX_BINS or not 0 <= k <= bins:
+        raise L.DeepcamHipError(f"decision_q_from_bin: bins must lie in [1, {PROB_MAX_BINS}] and k in [0, bins], got k = {k}, bins = {bins}")
+    return DECISION_NEVER if k == bins else -((-k * PROB_ONE) // bins)
+
+
+class DecisionRule:
+    """A mask from the classifier's fp32 logits by per-class probability thresholds with hysteresis, on the device (dc_logits_decide,
+    dc_mask_components, dc_hysteresis_select; csrc/decide.hip) -- instead of the argmax, which the training's class weights bias on purpose.
+    With q_c = rint(softmax_c * 65536), ProbabilitySkill's integer: class c in (1, 2) qualifies at a pixel iff q_c >= low[c]; the candidate
+    class is the qualifying one, of two the one with the larger q (class 1 on equal q), else 0; a candidate pixel with q_c >= high[c] is a
+    seed; the mask keeps the connected components of the candidates (one class, `connectivity` 4 or 8, periodic columns with `wrap`) that
+    hold a seed.  A pixel with a logit that is not finite is background.  high=None, or high == low: plain thresholding, no component pass.
+    low and high are pairs (class 1, class 2): a float is a probability (decision_q), an int is q itself, in [0, 65537]; 65537 is never.
+    Memory with hysteresis: 4 * B * H * W bytes of planes (candidates, seeds, flags, mask) plus 4 * B * H * W bytes of labels plus the
+    workspace of dc_mask_components; without: one plane of B * H * W bytes.  A call launches on the current stream and does not
+    synchronise; the mask is whatever consumes a mask takes (EventFilter, EventCatalog, EventMatcher, FractionsSkill, ...)."""
+
+    def __init__(self, batch: int, height: int, width: int, low=(0.5, 0.5), high=None, connectivity: int = 8, wrap: bool = True, device=None):
+        if batch < 1 or batch > PROB_MAX_BATCH or height < 1 or width < 1 or height * width > PROB_MAX_PIXELS:
+            raise L.DeepcamHipError(f"DecisionRule: batch must lie in [1, {PROB_MAX_BATCH}], height and width be positive and height * width at most 2^30")
+        if connectivity not in (4, 8):
+            raise L.DeepcamHipError(f"DecisionRule: connectivity must be 4 or 8, got {connectivity}")
+        self.low = self._pair(low, "low")
+        self.high = self.low if high is None else self._pair(high, "high")
+        if any(h < l for l, h in zip(self.low, self.high)):
+            raise L.DeepcamHipError(f"DecisionRule: a high threshold must not be below its low threshold, got low = {self.low}, high = {self.high} (q)")
+        self.hysteresis = self.high != self.low
+        self.B, self.H, self.W, self.connectivity, self.wrap = batch, height, width, connectivity, bool(wrap)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._counts = torch.zeros((batch, len(DECISION_COUNTS)), dtype=torch.int64, device=dev)
+        dev = self.device = self._counts.device
+        plane = lambda: torch.zeros((batch, height, width), dtype=torch.uint8, device=dev)  # noqa: E731
+        self._cand = plane()
+        self._seed = self._flags = self._out = self._labels = self._ws = None
+        if self.hysteresis:
+            self._seed, self._out = plane(), plane()
+            self._flags = torch.zeros(max(L.load().dc_decide_workspace(batch, height, width), 256), dtype=torch.uint8, device=dev)
+            self._labels = torch.zeros((batch, height, width), dtype=torch.int32, device=dev)
+            self._ws = torch.empty(max(L.load().dc_mask_components_workspace(batch, height, width), 256), dtype=torch.uint8, device=dev)
+        self._last_valid = 0
+
+    @staticmethod
+    def _pair(v, name):
+        if not isinstance(v, (tuple, list, np.ndarray)) or len(v) != 2:
+            raise L.DeepcamHipError(f"DecisionRule: {name} takes two values (class 1, class 2), got {v!r}")
+        out = []
+        for x in v:
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+                raise L.DeepcamHipError(f"DecisionRule: {name} takes probabilities (float) or q (int), got {x!r}")
+            q = int(x) if isinstance(x, (int, np.integer)) else decision_q(x)
+            if not 0 <= q <= DECISION_NEVER:
+                raise L.DeepcamHipError(f"DecisionRule: a threshold q must lie in [0, {DECISION_NEVER}], got {name} = {x!r}")
+            out.append(q)
+        return tuple(out)
+
+    @staticmethod
+    def low_from_prob_skill(decoded) -> tuple:
+        """(q class 1, q class 2) from best_csi_threshold: decoded is ProbabilitySkill.decode's dict, or a mapping with the `scalars`,
+        `scalar_names` and `bins` arrays of a prob_skill.h5.  low[c] = decision_q_from_bin(round(best_csi_threshold_c * bins), bins);
+        raises where a class has no threshold (None or NaN)."""
+        if "scalars" in decoded:
+            names = bytes(np.asarray(decoded["scalar_names"], np.uint8)).decode().split(",")
+            col = names.index("best_csi_threshold")
+            bins = int(np.asarray(decoded["bins"]).reshape(-1)[0])
+            best = [float(np.asarray(decoded["scalars"])[c, col]) for c in (1, 2)]
+        else:
+            bins = int(decoded["bins"])
+            best = [decoded[f"class_{c}"]["best_csi_threshold"] for c in (1, 2)]
+        out = []
+        for c, t in zip((1, 2), best):
+            if t is None or math.isnan(t):
+                raise L.DeepcamHipError(f"DecisionRule.from_prob_skill: class {c} has no best_csi_threshold (no pixel scored)")
+            out.append(decision_q_from_bin(int(round(t * bins)), bins))
+        return tuple(out)
+
+    @classmethod
+    def from_prob_skill(cls, decoded, batch: int, height: int, width: int, high=None, connectivity: int = 8, wrap: bool = True,
+                        device=None) -> "DecisionRule":
+        """The rule whose low thresholds are the best-CSI thresholds of a ProbabilitySkill result (low_from_prob_skill), typically of a
+        validation split; as integers q they reproduce the scored forecasts bit for bit."""
+        return cls(batch, height, width, low=cls.low_from_prob_skill(decoded), high=high, connectivity=connectivity, wrap=wrap, device=device)
+
+    def thresholds(self) -> dict:
+        """q and probability (q / 65536) per class (1, 2)"""
+        return {"low_q": list(self.low), "high_q": list(self.high), "low": [q / PROB_ONE for q in self.low],
+                "high": [q / PROB_ONE for q in self.high]}
+
+    def __call__(self, logits: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
+        """logits: contiguous device fp32 [B, 3, H, W] (Predictor.logits_buffer).  Returns the uint8 mask [n_valid, H, W], a view of a buffer
+        this object owns (mask_buffer is the whole of it; the next call overwrites it).  Samples from n_valid on are neither read nor
+        written."""
+        shape = (self.B, 3, self.H, self.W)
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or tuple(logits.shape) != shape or not logits.is_cuda \
+                or logits.device != self.device or not logits.is_contiguous():
+            got = f"{logits.dtype} {tuple(logits.shape)} on {logits.device}" if isinstance(logits, torch.Tensor) else type(logits).__name__
+            raise L.DeepcamHipError(f"DecisionRule: logits must be a contiguous torch.float32 tensor {list(shape)} on {self.device}, got {got}")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"DecisionRule: n_valid must lie in [0, {self.B}], got {n_valid}")
+        st = L.stream_ptr()
+        L.call("dc_logits_decide", self.B, nv, self.H, self.W, L.dptr(logits), self.low[0], self.low[1], self.high[0], self.high[1],
+               L.dptr(self._cand), L.dptr(self._seed) if self.hysteresis else None, L.dptr(self._counts), st)
+        self._last_valid = nv
+        if nv and self.hysteresis:
+            L.call("dc_mask_components", self.B, nv, self.H, self.W, L.dptr(self._cand), self.connectivity, int(self.wrap),
+                   L.dptr(self._labels), L.dptr(self._ws), st)
+            L.call("dc_hysteresis_select", self.B, nv, self.H, self.W, L.dptr(self._cand), L.dptr(self._seed), L.dptr(self._labels),
+                   L.dptr(self._flags), L.dptr(self._out), L.dptr(self._counts), st)
+        elif nv:                                  # plain thresholding: every candidate pixel is kept; no events are counted
+            c = self._counts[:nv]
+            c[:, 2], c[:, 7] = c[:, 0], c[:, 5]
+        return self.mask_buffer[:nv]
+
+    @property
+    def mask_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the whole buffer the masks are written to, padding samples included (plain thresholding: the candidates')"""
+        return self._out if self.hysteresis else self._cand
+
+    @property
+    def candidate_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the candidate classes, padding samples included"""
+        return self._cand
+
+    def counts(self) -> torch.Tensor:
+        """int64 [n_valid, 12] of the last call (a device view, not synchronised): DECISION_COUNTS"""
+        return self._counts[:self._last_valid]

@@ -86,6 +86,14 @@ scored) and ``prob_pixels`` (int64 [3]: scored, label outside [0, 3), a logit no
 integers ``hist``, ``sq_words``, ``pixels``, ``frames``, ``bins`` and the decoded curves per class (reliability diagram, sharpness, POD /
 POFD / CSI / bias per threshold, and ``scalars`` named by ``scalar_names``); ``summary.json`` gains ``prob_skill`` (per class brier,
 brier_skill, reliability, resolution, ece, auc, best_csi_threshold, base_rate).
+With --decision_low TC AR (probabilities of class 1 and class 2), or --decision_from FILE (the prob_skill.h5 of an earlier run, typically
+of the validation split: the best-CSI threshold per class), nn.DecisionRule turns the stored fp32 logits into a second mask on the device:
+class c where its softmax probability reaches the threshold, of two the more probable one -- instead of the argmax, which the training's
+class weights bias on purpose.  --decision_high TC AR adds hysteresis: a connected region above the low threshold (--event_connectivity,
+periodic columns) is kept only if it holds a pixel above the high one.  ``prediction`` stays the argmax mask, every output file gains
+``prediction_decided`` (uint8 [H, W]) and ``decision`` (int64 [12], nn.DECISION_COUNTS), and EVERYTHING downstream takes the decided mask:
+--event_filter (which then filters it), --events, --verify, --fss and the rest; --prob_skill keeps scoring the probabilities.
+``summary.json`` gains ``decision`` (the thresholds as q and as probabilities, the connectivity, the counters' totals).
 Single process, single device."""
 from __future__ import annotations
 
@@ -208,8 +216,18 @@ def _prob_bins(text: str) -> int:
     return k
 
 
+class _Parser(argparse.ArgumentParser):
+    """the checks that span two flags"""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if hasattr(ns, "decision_high") and not (hasattr(ns, "decision_low") or hasattr(ns, "decision_from")):
+            self.error("--decision_high needs --decision_low or --decision_from")
+        return ns
+
+
 def build_parser():
-    AP = argparse.ArgumentParser(description="DeepCAM inference: masks for unlabelled CAM5 files")
+    AP = _Parser(description="DeepCAM inference: masks for unlabelled CAM5 files")
     AP.add_argument("--checkpoint", type=str, required=True, help="a checkpoint written by train.py or by the reference (its 'model' entry), "
                     "or a bare state dict")
     AP.add_argument("--data_dir", type=str, required=True, help="directory with the input .h5 files (climate/data, no labels needed)")
@@ -309,6 +327,16 @@ def build_parser():
                     "'prob_skill' in the summary")
     AP.add_argument("--prob_bins", type=_prob_bins, default=S, help="with --prob_skill: the probability bins, 1 .. 256; the thresholds are "
                     "k / bins (20)")
+    # likewise the --decision_* flags
+    low = AP.add_mutually_exclusive_group()
+    low.add_argument("--decision_low", type=float, nargs=2, default=S, metavar=("TC", "AR"), help="decide the mask by probability thresholds "
+                     "on the device, not by the argmax: class 1 / class 2 where its softmax probability is at least this.  Dataset "
+                     "'prediction_decided' and the counters 'decision'; everything downstream (--event_filter, --events, --verify, --fss, "
+                     "...) takes the decided mask; 'prediction' stays the argmax")
+    low.add_argument("--decision_from", type=str, default=S, metavar="FILE", help="like --decision_low, the thresholds being the best-CSI "
+                     "thresholds of the prob_skill.h5 an earlier --prob_skill run wrote (typically on the validation split)")
+    AP.add_argument("--decision_high", type=float, nargs=2, default=S, metavar=("TC", "AR"), help="with --decision_low or --decision_from: "
+                    "hysteresis -- a connected region above the low threshold is kept only if it holds a pixel at or above this one")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -450,6 +478,41 @@ def prob_arrays(bins: int, state: dict) -> dict:
             "scalar_names": np.frombuffer(",".join(PROB_SCALARS).encode(), np.uint8).copy()}
 
 
+DECISION_FLAGS = ("decision_low", "decision_high", "decision_from")
+
+
+def read_datasets(path: str, names) -> dict:
+    """name -> array of the named datasets of one HDF5 file, through the backend data.CamDataset reads with"""
+    backend, h5 = ddata._h5_backend()
+    with (h5.File(path, "r") if backend == "h5py" else h5.File(path)) as f:
+        return {n: np.asarray(f[n][...] if backend == "h5py" else f.read(n)) for n in names}
+
+
+def decision_options(pargs):
+    """the `low` and `high` of nn.DecisionRule from the --decision_* flags, None where none of them was given: --decision_low's
+    probabilities, or the q thresholds of --decision_from's prob_skill.h5; --decision_high's probabilities or None"""
+    if not any(hasattr(pargs, k) for k in DECISION_FLAGS):
+        return None
+    low, source = getattr(pargs, "decision_low", None), getattr(pargs, "decision_from", None)
+    if (low is None) == (source is None):
+        raise ValueError("give exactly one of --decision_low and --decision_from" if low is not None else
+                         "--decision_high needs --decision_low or --decision_from")
+    if source is not None:
+        low = dnn.DecisionRule.low_from_prob_skill(read_datasets(source, ("scalars", "scalar_names", "bins")))
+    else:
+        low = tuple(float(v) for v in low)
+    high = getattr(pargs, "decision_high", None)
+    return {"low": low, "high": None if high is None else tuple(float(v) for v in high)}
+
+
+def decision_summary(rule, records) -> dict:
+    """the `decision` entry of summary.json: the thresholds as q and as probabilities, whether hysteresis ran, the connectivity, and the
+    counters summed over the files"""
+    totals = [sum(r["decision"][k] for r in records) for k in range(len(dnn.DECISION_COUNTS))]
+    return dict(rule.thresholds(), hysteresis=rule.hysteresis, connectivity=rule.connectivity, wrap=rule.wrap,
+                counts=dict(zip(dnn.DECISION_COUNTS, totals)))
+
+
 def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
     """the `climatology` entry of summary.json: the groups' names and frames and, per class, the area-weighted frequency of every group
     (None for a group without a frame); with --verify the same of the labels"""
@@ -564,7 +627,10 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
-                 prob_skill: bool = False):
+                 prob_skill: bool = False, decision: bool = False):
+        # --decision_*: the decided mask and the rule's counters
+        self.dmask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if decision else None
+        self.dcounts = torch.empty((B, len(dnn.DECISION_COUNTS)), dtype=torch.int64).pin_memory() if decision else None
         # --prob_skill: the squared-error rows of nn.ProbabilitySkill and the pixel counters beside them
         self.prob_rows = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
         self.prob_pixels = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
@@ -633,6 +699,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             H, W = slot.mask.shape[1:]
                             extra = dict(extra or {}, event_shape=srows, event_shape_values=dnn.EventShape.values(srows, rows, H, W),
                                          event_shape_value_names=np.frombuffer(",".join(dnn.EVENT_SHAPE_VALUES).encode(), np.uint8).copy())
+                    if slot.dmask is not None:
+                        extra = dict(extra or {}, prediction_decided=slot.dmask[j].numpy(), decision=slot.dcounts[j].numpy())
                     if slot.fmask is not None:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
                     if slot.fss is not None:
@@ -648,6 +716,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if plot[j]:
                         rec["plot"] = plot_name(base)
+                    if slot.dcounts is not None:
+                        rec["decision"] = [int(v) for v in slot.dcounts[j].tolist()]
                     if slot.fcounts is not None:
                         rec["event_filter"] = [dict(zip(dnn.EVENT_FILTER_COUNTS, (int(v) for v in row))) for row in slot.fcounts[j].tolist()]
                     if rows is not None:
@@ -692,21 +762,27 @@ def main(pargs) -> dict:
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     loader = ddata.InputPipeline(dataset, B, dtype=dtype, device=device, layout=layout, drop_last=False, workers=pargs.max_inter_threads)
     events = bool(pargs.events) or verify or bool(getattr(pargs, "tracks", False))
-    # --event_filter: the filter's own catalogue takes the classifier's mask; everything below takes the filtered one
+    # --decision_*: the rule takes the stored logits; everything below, the filter included, takes the decided mask
+    decision = decision_options(pargs)
+    decide = None
+    if decision is not None:
+        decide = dnn.DecisionRule(B, H, W, connectivity=pargs.event_connectivity, device=device, **decision)
+    # --event_filter: the filter's own catalogue takes the mask as it arrives; everything below takes the filtered one
     efilter = None
     if getattr(pargs, "event_filter", False):
         efilter = dnn.EventFilter(dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device),
                                   min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
                                   min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect)
-    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify and efilter is None,
+    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify and efilter is None and decide is None,
                               event_connectivity=pargs.event_connectivity)
     # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
     matcher = dnn.EventMatcher(B, H, W, connectivity=pargs.event_connectivity, min_pixels=pargs.min_event_pixels,
                                min_cover=pargs.min_event_cover, device=device) if verify else None
     catalog = matcher.a if verify else predictor.catalog
-    if events and catalog is None:                # --event_filter without --verify: a second catalogue, of the filtered mask
+    predictor.store_logits = predictor.store_logits or decide is not None      # bf16 keeps the logits in registers unless asked
+    if events and catalog is None:                # a decided or filtered mask without --verify: a catalogue of its own for it
         catalog = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
-    own_catalog = events and not verify and efilter is not None
+    own_catalog = events and not verify and (efilter is not None or decide is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
@@ -768,7 +844,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
-                             prob is not None))
+                             prob is not None, decide is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -784,8 +860,12 @@ def main(pargs) -> dict:
                 break
             mask = predictor(x, n_valid=nv)
             dmask = predictor.mask_buffer          # what everything downstream takes
+            if decide is not None:
+                slot.dmask[:nv].copy_(decide(predictor.logits_buffer, n_valid=nv), non_blocking=True)
+                slot.dcounts[:nv].copy_(decide.counts(), non_blocking=True)
+                dmask = decide.mask_buffer
             if efilter is not None:
-                slot.fmask[:nv].copy_(efilter(predictor.mask_buffer, n_valid=nv), non_blocking=True)
+                slot.fmask[:nv].copy_(efilter(dmask, n_valid=nv), non_blocking=True)
                 slot.fcounts[:nv].copy_(efilter.counts(), non_blocking=True)
                 dmask = efilter.mask_buffer
             if own_catalog:
@@ -857,6 +937,8 @@ def main(pargs) -> dict:
     if events:
         summary["events"] = [sum(r["events"][j] for r in records) for j in range(2)]
         summary["events_overflowed_files"] = sum(1 for r in records if r["events_overflowed"])
+    if decide is not None:
+        summary["decision"] = decision_summary(decide, records)
     if efilter is not None:
         summary["event_filter"] = dict(efilter.thresholds(), classes=[
             {k: sum(r["event_filter"][j][k] for r in records) for k in dnn.EVENT_FILTER_COUNTS} for j in range(2)])
