@@ -93,6 +93,8 @@ int dc_reset_options(void);
  *   decision rule (dc_logits_decide, dc_hysteresis_select): decide_q_vec (16-byte loads and 32-bit stores, H * W a multiple of 4) or
  *     decide_q (4-byte loads, byte stores, any H * W): candidates, seeds and their counters; decide_mark (a seed flags its component's
  *     root), decide_select (the mask of the flagged components, the kept pixels and the events)
+ *   distance-map verification (dc_distance_score): dist_vert (the row distances of four indicator fields, one packed word per pixel),
+ *     dist_horz (the capped squared distance maps, the ring counters, the sums and the Baddeley term), dist_total (the running totals)
  *   aux                                  every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -1067,6 +1069,61 @@ size_t dc_fss_workspace(int B, int H, int W, int S);
 int dc_fss_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int S,
                  const int32_t* radius /*device*/, int wrap, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
                  int64_t* total_pixels, int64_t* frames, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Distance-map verification (nn.DistanceSkill; predict.py --distance_skill): capped squared Euclidean distance maps of both masks and the
+ * integers behind the distance measures for binary fields -- mean error distance in both directions, (partial) Hausdorff distance,
+ * Baddeley's (1992) Delta, and hit rate / success ratio with a displacement of up to r grid points forgiven.  They answer "how far, in
+ * grid points, is the predicted object from the labelled one", which neither the per-pixel, the per-object nor the neighbourhood scores
+ * do.  Everything is an integer; the quotients and roots are taken on the host (nn.DistanceSkill.decode).
+ *   pred, truth  [B][H][W] of 1-, 4- or 8-byte integers (pred_bytes, truth_bytes): class k in {1, 2} is the full-width value k, every
+ *                other value (0, 3, 255, -1, 257, 2^32 + 1, ...) is background -- dc_fss_score's rule
+ *   metric       d^2((y, x), (y', x')) = (y - y')^2 + dx^2 with dx = min(|x - x'|, W - |x - x'|) under wrap and |x - x'| otherwise.  Rows are
+ *                never periodic.  Distances are GRID PIXELS: no latitude weighting, no kilometres
+ *   R            the cap, 1 <= R <= 127, with wrap also 2 R + 1 <= W.  A map value is the minimum of d^2 over the pixels of a side and
+ *                class where that is <= R^2, and R^2 + 1 ("beyond") otherwise, also where the frame has no such pixel.  The cap makes a
+ *                window of +-R rows and columns exact: a nearest pixel within R lies inside it, and if none lies within R every pixel
+ *                inside it is farther than R too.  Values fit uint16
+ *   maps         uint16 [B][2][2][H][W], side (0 prediction, 1 labels) then class - 1; may be NULL.  0: the pixel itself is of that side
+ *                and class.  Written for ALL rows, whatever the row range
+ *   table        int32 [R^2 + 2], DEVICE memory, built by the host (nn.distance_table): entry v = ring(v) | dq(v) << 8, ring(v) in bits
+ *                0-7 the smallest integer j with j^2 >= v, dq(v) in bits 8-23 = rint(sqrt(v) * 256) in double precision; the last entry
+ *                (v = R^2 + 1, beyond) holds ring R + 1 and dq 0.  A ring above R + 1 in the table counts as R + 1
+ *   directions   per class: 0 "miss", the sources are the labelled pixels and the distance is to the nearest predicted pixel; 1 "false
+ *                alarm", the sources are the predicted pixels and the distance is to the nearest labelled pixel.  A source pixel of a
+ *                side is a pixel whose own map value is 0
+ *   rows         int64 [B][2 classes][2 directions][R + 4]: cells 0 .. R + 1 count the sources per ring(distance) -- ring 0 is |P and T|,
+ *                ring R + 1 the sources beyond the cap --, cell R + 2 is the sum of dq and cell R + 3 the sum of d^2 over the sources
+ *                within the cap
+ *   baddeley     int64 [B][2]: per class the sum over pixels of (w_P - w_T)^2, w = dq(map value) within the cap and 256 R beyond:
+ *                Baddeley's Delta with p = 2 and the cut-off transformation w = min(d, c) at c = R, scaled by 256^2
+ *   row0, row1   only sources and Baddeley pixels in these rows count; targets anywhere in the frame still do
+ * rows and baddeley of the frames below n_valid are zeroed by the call, in stream order, and then written; frames from n_valid on are
+ * neither read nor written, in any buffer, and n_valid == 0 launches nothing.
+ *   total           int64 [2][2][R + 4] += rows over the valid frames.  A frame adds at most H * W * 32512 to a cell, below 2^37 at
+ *                   768 x 1152: a single word lasts 2^26 such frames
+ *   total_baddeley  int64 [2][2]: per class a TWO-WORD total (lo, hi), dc_fss_score's convention: lo += x, hi += carry.  A frame of
+ *                   768 x 1152 can add 2^50
+ *   frames          int64 [1] += n_valid
+ * The sums are integers and every total is added frame by frame by one thread: the state does not depend on the schedule or on how a
+ * sequence is cut into batches.  Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W < 2^31, 0 <= row0 < row1 <= H; pointers aligned to their
+ * element size.
+ * The transform is separable.  dist_vert gives, per pixel and indicator field (pred 1, pred 2, truth 1, truth 2), the rows g <= R + 1 to the
+ * nearest pixel of the field in the same column -- a thread per column of a segment of rows with a halo of R rows above and below, which
+ * the cap makes exact -- as one byte each of a packed 32-bit word; dist_horz stages those words of a strip and a halo of R columns in
+ * LDS, takes min over |dx| <= R of dx^2 + g^2 per field, a tap to the left and one to the right serving all four fields, stops once dx^2
+ * reaches the largest running minimum, and scores the pixel in place (ring counters in an LDS histogram, sums by wave reduction, one
+ * 64-bit atomic per non-zero cell and workgroup); dist_total adds the batch to the totals.
+ *   workspace  dc_distance_workspace(B, H, W, R) bytes = B * H * W * 4, 4-byte aligned; 0 = arguments out of range.
+ * dc_distance_block: the columns of a strip and the rows of a segment one workgroup covers (a host function; tests derive shapes from it).
+ * dc_distance_score makes no synchronisation and runs on the caller's stream; a failed argument check sets the message and launches
+ * nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_distance_block(int* cols, int* rows);
+size_t dc_distance_workspace(int B, int H, int W, int R);
+int dc_distance_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int R,
+                      const int32_t* table /*device*/, int wrap, int row0, int row1, int64_t* rows, int64_t* baddeley, int64_t* total,
+                      int64_t* total_baddeley, int64_t* frames, uint16_t* maps /*may be NULL*/, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Probabilistic verification (nn.ProbabilitySkill; predict.py --prob_skill): the integers behind the reliability diagram, the Brier score

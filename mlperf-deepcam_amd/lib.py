@@ -190,6 +190,9 @@ _SIGS = {
     "dc_fss_block": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_fss_workspace": (SZ, [I, I, I, I]),
     "dc_fss_score": (I, [I, I, I, I, P, I, P, I, I, P, I, I, I, P, P, P, P, P, P, P]),
+    "dc_distance_block": (I, [C.POINTER(I), C.POINTER(I)]),
+    "dc_distance_workspace": (SZ, [I, I, I, I]),
+    "dc_distance_score": (I, [I, I, I, I, P, I, P, I, I, P, I, I, I, P, P, P, P, P, P, P, P]),
     "dc_prob_block": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_prob_score": (I, [I, I, I, I, P, P, I, I, P, P, P, P, P, P, P, P]),
     "dc_decide_block": (I, [C.POINTER(I)]),

@@ -2606,6 +2606,172 @@ class FractionsSkill:
         return out
 
 
+# ---------------------------------------------------------------------------------------------- distance-map verification
+DISTANCE_RADIUS = 64
+DISTANCE_MAX_RADIUS = 127
+DISTANCE_MAX_BATCH = 4095
+DISTANCE_Q = 256                                  # dq = rint(sqrt(d^2) * DISTANCE_Q)
+
+
+def distance_table(radius: int) -> np.ndarray:
+    """int32 [R^2 + 2], the table dc_distance_score reads: entry v = ring(v) | dq(v) << 8 with ring(v) the smallest integer j with j^2 >= v
+    (math.isqrt) and dq(v) = int(rint(sqrt(float64(v)) * 256)); the last entry (v = R^2 + 1, beyond the cap) has ring R + 1 and dq 0."""
+    R = int(radius)
+    if not 1 <= R <= DISTANCE_MAX_RADIUS:
+        raise L.DeepcamHipError(f"distance_table: the radius must lie in [1, {DISTANCE_MAX_RADIUS}], got {radius}")
+    table = np.zeros(R * R + 2, np.int32)
+    for v in range(R * R + 1):
+        ring = math.isqrt(v)
+        ring += ring * ring < v
+        table[v] = ring | int(np.rint(np.sqrt(np.float64(v)) * DISTANCE_Q)) << 8
+    table[R * R + 1] = R + 1
+    return table
+
+
+def _ratio(a, b):
+    return None if b == 0 else a / b
+
+
+class DistanceSkill:
+    """Distance-map verification on the device (dc_distance_score, csrc/distance.hip): per frame, side (prediction, labels) and class (1, 2)
+    the map of the squared Euclidean distance, in GRID PIXELS, to the nearest pixel of that side and class -- columns periodic with wrap,
+    rows never --, capped: R^2 + 1 ("beyond") where nothing lies within `radius` = R.  From the maps, per class and direction (0 "miss": from
+    every labelled pixel to the nearest predicted one; 1 "false alarm": the reverse) the sources per ring of distance, the sums of the
+    distance (in 1/256 pixel) and of its square, and Baddeley's sum of squared map differences, as integers and as running totals over all
+    frames since reset(); decode() turns them into the mean error distances, the (partial) Hausdorff distance, Baddeley's Delta and the hit
+    rate and success ratio with a displacement of up to r pixels forgiven.  1 <= radius <= 127, with wrap also 2 radius + 1 <= width.
+    No latitude weighting and no kilometres: row_range is the tool for a tropics-only score; it selects the sources and the Baddeley
+    pixels, targets anywhere in the frame still count.  The single-word totals last 2^26 frames of 768 x 1152.
+    Memory: a workspace of batch * height * width * 4 bytes (dc_distance_workspace; 28.3 MB at 8 x 768 x 1152), with keep_maps another
+    batch * 4 * height * width * 2 bytes of uint16 maps (56.6 MB), beside batch * (4 * (R + 4) + 2) * 8 bytes of rows and the totals.
+    A call launches on the current stream and does not synchronise; state() and result() read back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, radius: int = DISTANCE_RADIUS, wrap: bool = True, row_range=None,
+                 keep_maps: bool = False, device=None):
+        if batch < 1 or batch > DISTANCE_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError(f"DistanceSkill: batch must lie in [1, {DISTANCE_MAX_BATCH}], height and width be positive and height * width below 2^31")
+        R = int(radius)
+        if not 1 <= R <= DISTANCE_MAX_RADIUS:
+            raise L.DeepcamHipError(f"DistanceSkill: the radius must lie in [1, {DISTANCE_MAX_RADIUS}], got {radius}")
+        if wrap and 2 * R + 1 > width:
+            raise L.DeepcamHipError(f"DistanceSkill: a periodic window of 2 * {R} + 1 columns must not be wider than the frame ({width})")
+        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        if not 0 <= row0 < row1 <= height:
+            raise L.DeepcamHipError(f"DistanceSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
+        self.B, self.H, self.W, self.R = batch, height, width, R
+        self.wrap, self.row_range, self.keep_maps = bool(wrap), (row0, row1), bool(keep_maps)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._table = torch.from_numpy(distance_table(R)).to(dev)
+        dev = self.device = self._table.device
+        self._rows = torch.zeros((batch, 2, 2, R + 4), dtype=torch.int64, device=dev)
+        self._baddeley = torch.zeros((batch, 2), dtype=torch.int64, device=dev)
+        self._total = torch.zeros((2, 2, R + 4), dtype=torch.int64, device=dev)
+        self._total_baddeley = torch.zeros((2, 2), dtype=torch.int64, device=dev)            # (lo, hi)
+        self._frames = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._maps = torch.zeros((batch, 2, 2, height, width), dtype=torch.uint16, device=dev) if keep_maps else None
+        size = L.load().dc_distance_workspace(batch, height, width, R)
+        if size == 0:
+            raise L.DeepcamHipError("DistanceSkill: dc_distance_workspace refused the shape")
+        self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
+        self._nv = 0
+
+    def _check(self, t, name: str) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
+                or t.device != self.device or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"DistanceSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
+                                    f"on {self.device}, got {got}")
+
+    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "DistanceSkill":
+        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
+        are neither read nor written."""
+        self._check(pred, "pred")
+        self._check(truth, "truth")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"DistanceSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
+        L.call("dc_distance_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
+               self.R, L.dptr(self._table), int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._baddeley),
+               L.dptr(self._total), L.dptr(self._total_baddeley), L.dptr(self._frames), L.dptr(self._maps) if self._maps is not None else None,
+               L.dptr(self._ws), L.stream_ptr())
+        self._nv = nv
+        return self
+
+    def frame_rows(self):
+        """(int64 [n_valid, 2, 2, R + 4], int64 [n_valid, 2]) of the last call: views of the object's device buffers, not synchronised"""
+        return self._rows[:self._nv], self._baddeley[:self._nv]
+
+    def maps(self) -> torch.Tensor:
+        """uint16 [n_valid, 2 sides, 2 classes, H, W] of the last call (keep_maps): a view of the object's device buffer, not synchronised"""
+        if self._maps is None:
+            raise L.DeepcamHipError("DistanceSkill: maps() needs keep_maps=True")
+        return self._maps[:self._nv]
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for t in (self._total, self._total_baddeley, self._frames):
+            t.zero_()
+
+    def state(self) -> dict:
+        """on the host, as Python ints: total [2][2][R + 4], baddeley [2] (the two words combined) and frames"""
+        words = self._total_baddeley.cpu().tolist()
+        return {"total": [[[int(v) for v in d] for d in cls] for cls in self._total.cpu().tolist()],
+                "baddeley": [(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in words], "frames": int(self._frames.cpu()[0])}
+
+    def result(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(s["total"], s["baddeley"], s["frames"], self.R, self.H, self.W, self.row_range)
+
+    @staticmethod
+    def decode(total, total_baddeley, frames, radius: int, height: int, width: int, row_range=None) -> dict:
+        """Per class ("class_1", "class_2"), in float64 from the exact integers; distances in grid pixels; None wherever a denominator is 0:
+        pixels {"labelled", "predicted"}; pod_within[r] and success_within[r] for r = 0 .. R, the share of labelled (predicted) pixels with a
+        predicted (labelled) pixel within r -- r = 0 is the per-pixel POD and 1 - FAR; med_miss, med_false_alarm, the mean error distances
+        sum dq / 256 / n over the sources within the cap, and rms_miss, rms_false_alarm; beyond_miss, beyond_false_alarm, the shares of
+        sources beyond the cap; hausdorff, the largest non-empty ring over both directions, None when any source is beyond the cap or there
+        is no source; hausdorff_q90, the larger over the directions that have sources of the smallest ring that, with the rings below it,
+        holds 90 % of the direction's sources, None when that ring is beyond the cap; baddeley, sqrt(total / (frames * pixels of the band))
+        / 256, Baddeley's Delta with p = 2 and cut-off R."""
+        R = int(radius)
+        row0, row1 = (0, int(height)) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        cells = int(frames) * (row1 - row0) * int(width)
+        out = {}
+        for k in range(2):
+            entry, rings, quantiles = {}, [], []
+            for d, (name, curve) in enumerate((("miss", "pod_within"), ("false_alarm", "success_within"))):
+                cell = [int(v) for v in total[k][d]]
+                if len(cell) != R + 4:
+                    raise L.DeepcamHipError(f"DistanceSkill.decode: a row holds R + 4 = {R + 4} cells, got {len(cell)}")
+                n, beyond = sum(cell[:R + 2]), cell[R + 1]
+                within, cum = n - beyond, np.cumsum(np.asarray(cell[:R + 1], np.int64)).tolist()
+                entry[curve] = [_ratio(c, n) for c in cum]
+                entry[f"med_{name}"] = _ratio(cell[R + 2] / DISTANCE_Q, within)
+                entry[f"rms_{name}"] = None if within == 0 else math.sqrt(cell[R + 3] / within)
+                entry[f"beyond_{name}"] = _ratio(beyond, n)
+                rings.append(cell[:R + 2])
+                if n:
+                    quantiles.append(next(j for j, c in enumerate(cum + [n]) if 10 * c >= 9 * n))
+            entry["pixels"] = {"labelled": sum(rings[0]), "predicted": sum(rings[1])}
+            occupied = [j for j in range(R + 2) if rings[0][j] or rings[1][j]]
+            entry["hausdorff"] = occupied[-1] if occupied and occupied[-1] <= R else None
+            entry["hausdorff_q90"] = max(quantiles) if quantiles and max(quantiles) <= R else None
+            entry["baddeley"] = None if cells <= 0 else math.sqrt(int(total_baddeley[k]) / cells) / DISTANCE_Q
+            out[f"class_{k + 1}"] = entry
+        return out
+
+
+def distance_from_rows(rows, baddeley, radius: int, height: int, width: int, row_range=None) -> list:
+    """DistanceSkill.decode of single frames: rows int64 [n, 2, 2, R + 4] and baddeley int64 [n, 2] (what frame_rows() returns, on the
+    host) give a list of n dictionaries, each the decode of that frame alone."""
+    rows, baddeley = np.asarray(rows), np.asarray(baddeley)
+    if rows.ndim != 4 or rows.shape[1:] != (2, 2, int(radius) + 4) or baddeley.shape != (rows.shape[0], 2):
+        raise L.DeepcamHipError(f"distance_from_rows: rows [n, 2, 2, R + 4] and baddeley [n, 2], got shapes {rows.shape} and {baddeley.shape}")
+    return [DistanceSkill.decode(r, b, 1, radius, height, width, row_range) for r, b in zip(rows.tolist(), baddeley.tolist())]
+
+
 # ---------------------------------------------------------------------------------------------- probabilistic verification
 PROB_BINS = 20
 PROB_MAX_BINS = 256

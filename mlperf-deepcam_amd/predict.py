@@ -78,6 +78,13 @@ O)^2, sum F^2, sum O^2 of the window counts F and O.  Every output file also car
 [2, 2]: predicted and labelled pixels per class in those rows); ``summary.json`` gains ``fss`` (windows, rows, frames and per class the
 pooled Fractions Skill Score 1 - sum A / (sum B + sum C) per window, the labels' base rate, the useful score 0.5 + base_rate / 2, the
 smallest window that reaches it, and the raw totals as integers).
+With --distance_skill (which implies --verify) nn.DistanceSkill scores, behind every batch and on the device, the same prediction side
+against the unfiltered labels by distance: capped squared Euclidean distance maps in grid pixels (cap --distance_radius; columns periodic
+unless --distance_no_wrap; sources in the rows --distance_rows I0 I1, the whole frame by default; no latitude weighting) and from them, per
+class and direction (miss, false alarm), the sources per ring of distance with the sums of the distance and of its square, and Baddeley's
+sum.  Every output file also carries ``distance`` (int64 [2, 2, R + 4]) and ``distance_baddeley`` (int64 [2]); ``summary.json`` gains
+``distance_skill`` (radius, wrap, rows, frames and per class the mean error distances, the Hausdorff and partial Hausdorff distance,
+Baddeley's Delta, the hit rate and success ratio within r pixels, and the raw totals as integers).
 With --prob_skill (which implies --verify) nn.ProbabilitySkill scores, behind every batch and on the device, the classifier's softmax
 probabilities -- the stored fp32 logits, never the mask, so --event_filter does not change them -- against the unfiltered labels: per
 class the joint histogram of (probability bin of --prob_bins bins, label is the class) with the sum of the probabilities per cell, and the
@@ -189,6 +196,18 @@ class _Fss(argparse.Action):
 
     def __call__(self, parser, namespace, values, option_string=None):
         namespace.fss = True
+        namespace.verify = True
+        namespace.events = True
+
+
+class _DistanceSkill(argparse.Action):
+    """--distance_skill: implies --verify (and with it --events)"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.distance_skill = True
         namespace.verify = True
         namespace.events = True
 
@@ -319,6 +338,16 @@ def build_parser():
     AP.add_argument("--fss_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --fss: score the window centres in the "
                     "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     AP.add_argument("--fss_no_wrap", action="store_true", default=S, help="with --fss: do not take the columns as periodic")
+    # likewise the --distance_* flags (DISTANCE_DEFAULTS)
+    AP.add_argument("--distance_skill", action=_DistanceSkill, help="distance-map verification on the device (implies --verify; the files "
+                    "need climate/labels_0): mean error distance, Hausdorff distance, Baddeley's Delta and hit rate / success ratio within "
+                    "r grid pixels of --verify's prediction side against the labels, per class.  Datasets 'distance', 'distance_baddeley'; "
+                    "'distance_skill' in the summary")
+    AP.add_argument("--distance_radius", type=int, default=S, help="with --distance_skill: the cap R on the distances in grid pixels, "
+                    "1 .. 127, with periodic columns 2 R + 1 <= --width (64)")
+    AP.add_argument("--distance_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --distance_skill: count the sources "
+                    "in the rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
+    AP.add_argument("--distance_no_wrap", action="store_true", default=S, help="with --distance_skill: do not take the columns as periodic")
     # likewise the --prob_* flags (PROB_DEFAULTS)
     AP.add_argument("--prob_skill", action=_ProbSkill, help="probabilistic verification on the device (implies --verify; the files need "
                     "climate/labels_0): reliability diagram, Brier score with its decomposition, POD / POFD / CSI per probability threshold "
@@ -437,6 +466,27 @@ def fss_summary(windows, row_range, width: int, state: dict) -> dict:
     for k in range(2):
         out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], total=[[int(v) for v in term] for term in state["total"][k]],
                                      pixels=[int(v) for v in state["pixels"][k]])
+    return out
+
+
+DISTANCE_DEFAULTS = {"distance_skill": False, "distance_radius": dnn.DISTANCE_RADIUS, "distance_rows": None, "distance_no_wrap": False}
+
+
+def distance_options(pargs) -> dict:
+    """the keyword arguments of nn.DistanceSkill from the --distance_* flags (DISTANCE_DEFAULTS where one was not given)"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in DISTANCE_DEFAULTS.items()})
+    return {"radius": int(a.distance_radius), "wrap": not a.distance_no_wrap,
+            "row_range": None if a.distance_rows is None else (int(a.distance_rows[0]), int(a.distance_rows[1]))}
+
+
+def distance_summary(radius: int, wrap: bool, row_range, height: int, width: int, state: dict) -> dict:
+    """the `distance_skill` entry of summary.json from nn.DistanceSkill.state(): the cap, the scored rows, the frames and, per class, the
+    decoded result with the raw totals [2][R + 4] and the Baddeley sum as integers"""
+    decoded = dnn.DistanceSkill.decode(state["total"], state["baddeley"], state["frames"], radius, height, width, row_range)
+    out = {"radius": int(radius), "wrap": bool(wrap), "rows": [int(row_range[0]), int(row_range[1])], "frames": int(state["frames"])}
+    for k in range(2):
+        out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], total=[[int(v) for v in d] for d in state["total"][k]],
+                                     total_baddeley=int(state["baddeley"][k]))
     return out
 
 
@@ -627,7 +677,10 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
-                 prob_skill: bool = False, decision: bool = False):
+                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0):
+        # --distance_skill: the rows of nn.DistanceSkill and the Baddeley sums beside them
+        self.distance = torch.empty((B, 2, 2, distance_cells), dtype=torch.int64).pin_memory() if distance_cells else None
+        self.distance_baddeley = torch.empty((B, 2), dtype=torch.int64).pin_memory() if distance_cells else None
         # --decision_*: the decided mask and the rule's counters
         self.dmask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if decision else None
         self.dcounts = torch.empty((B, len(dnn.DECISION_COUNTS)), dtype=torch.int64).pin_memory() if decision else None
@@ -705,6 +758,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
                     if slot.fss is not None:
                         extra = dict(extra or {}, fss=slot.fss[j].numpy(), fss_pixels=slot.fss_pixels[j].numpy())
+                    if slot.distance is not None:
+                        extra = dict(extra or {}, distance=slot.distance[j].numpy(), distance_baddeley=slot.distance_baddeley[j].numpy())
                     if slot.prob_rows is not None:
                         brier = dnn.brier_from_rows(slot.prob_rows[j].numpy(), slot.prob_pixels[j].numpy())
                         extra = dict(extra or {}, brier=np.asarray([np.nan if v is None else v for v in brier], np.float64),
@@ -825,6 +880,8 @@ def main(pargs) -> dict:
         clim, clim_truth = make(), make() if verify else None
     # --fss: behind every batch, the prediction side of --verify against the labels
     fss = dnn.FractionsSkill(B, H, W, device=device, **fss_options(pargs)) if getattr(pargs, "fss", False) else None
+    # --distance_skill: likewise
+    dist = dnn.DistanceSkill(B, H, W, device=device, **distance_options(pargs)) if getattr(pargs, "distance_skill", False) else None
     # --prob_skill: behind every batch, the classifier's stored logits against the labels
     prob = None
     if getattr(pargs, "prob_skill", False):
@@ -844,7 +901,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
-                             prob is not None, decide is not None))
+                             prob is not None, decide is not None, dist.R + 4 if dist else 0))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -876,6 +933,10 @@ def main(pargs) -> dict:
                 frame_rows, frame_pixels = fss(dmask, y, n_valid=nv).frame_rows()
                 slot.fss[:nv].copy_(frame_rows, non_blocking=True)
                 slot.fss_pixels[:nv].copy_(frame_pixels, non_blocking=True)
+            if dist is not None:
+                dist_rows, dist_baddeley = dist(dmask, y, n_valid=nv).frame_rows()
+                slot.distance[:nv].copy_(dist_rows, non_blocking=True)
+                slot.distance_baddeley[:nv].copy_(dist_baddeley, non_blocking=True)
             if prob is not None:
                 prob_rows, prob_pixels = prob(predictor.logits_buffer, y, n_valid=nv).frame_rows()
                 slot.prob_rows[:nv].copy_(prob_rows, non_blocking=True)
@@ -928,6 +989,7 @@ def main(pargs) -> dict:
     clim_state = clim.state() if clim is not None else None
     comp_state = comp.state() if comp is not None else None
     fss_state = fss.state() if fss is not None else None
+    dist_state = dist.state() if dist is not None else None
     prob_state = prob.state() if prob is not None else None
     elapsed = time.perf_counter() - t0
 
@@ -950,6 +1012,8 @@ def main(pargs) -> dict:
         summary["event_verification"] = verification
     if fss is not None:
         summary["fss"] = fss_summary(fss.windows, fss.row_range, W, fss_state)
+    if dist is not None:
+        summary["distance_skill"] = distance_summary(dist.R, dist.wrap, dist.row_range, H, W, dist_state)
     if prob is not None:
         write_datasets(os.path.join(pargs.output_dir, "prob_skill.h5"), prob_arrays(prob.K, prob_state))
         summary["prob_skill"] = prob_summary(prob.K, prob_state)
