@@ -95,6 +95,8 @@ int dc_reset_options(void);
  *     root), decide_select (the mask of the flagged components, the kept pixels and the events)
  *   distance-map verification (dc_distance_score): dist_vert (the row distances of four indicator fields, one packed word per pixel),
  *     dist_horz (the capped squared distance maps, the ring counters, the sums and the Baddeley term), dist_total (the running totals)
+ *   displacement verification (dc_displacement_score): disp_pack (the four bit planes, the predicted pixels per row, the pixel counts),
+ *     disp_corr (the overlap table and `kept`), disp_best (the best shift per frame and class), disp_total (the running totals)
  *   aux                                  every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -1124,6 +1126,56 @@ size_t dc_distance_workspace(int B, int H, int W, int R);
 int dc_distance_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int R,
                       const int32_t* table /*device*/, int wrap, int row0, int row1, int64_t* rows, int64_t* baddeley, int64_t* total,
                       int64_t* total_baddeley, int64_t* frames, uint16_t* maps /*may be NULL*/, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Displacement verification (nn.DisplacementSkill; predict.py --displacement): the overlap of the labelled mask with the predicted mask
+ * moved by every (dy, dx) of a window -- the cross-correlation of two binary fields -- and the shift with the most hits: the rigid-shift
+ * part of Ebert & McBride's (2000) CRA method, the field-deformation family of Gilleland et al. (2009).  It answers "how much of the miss
+ * is the prediction lying two pixels too far north", which the distance measures (no direction), the matched events' centroids (overlapping
+ * objects only) and the FSS (a scale, not a vector) do not.  Everything is an integer; the host decodes (nn.DisplacementSkill.decode).
+ *   pred, truth  [B][H][W] of 1-, 4- or 8-byte integers (pred_bytes, truth_bytes), each side with its own element size: class k in {1, 2}
+ *                is the full-width value k, every other value (0, 3, 255, -1, 257, 2^32 + 1, ...) is background -- dc_fss_score's rule.
+ *                P_k, T_k: the indicator fields of class k
+ *   columns      periodic, always (a regional grid is out of scope); rows are never periodic
+ *   R            the radius of the window, 1 <= R <= 63, with 2 R + 1 <= W
+ *   row0, row1   the band, 0 <= row0 < row1 <= H
+ * The prediction moved by (dy, dx), |dy|, |dx| <= R, is P'_k(y, x) = P_k(y - dy, (x - dx) mod W) where 0 <= y - dy < H and 0 elsewhere:
+ * pixels moved over a pole are lost.
+ *   hits[b][k][dy][dx] = #{(y, x): row0 <= y < row1, T_k(y, x) = 1, P'_k(y, x) = 1}
+ *   kept[b][k][dy]     = #{(y', x): P_k(y', x) = 1, row0 <= y' + dy < row1}, the predicted pixels inside the band after the move; it does
+ *                        not depend on dx
+ *   rows         int64 [B][2][2 R + 1][2 R + 2]: cells 0 .. 2 R of row dy + R are the hits for dx = -R .. R, cell 2 R + 1 is kept
+ *   pixels       int64 [B][2][2]: per class (the predicted pixels of the WHOLE frame, the labelled pixels inside the band)
+ *   best         int64 [B][2][4]: (dy, dx, hits, kept[dy]) of the best shift, the one with the most hits (the maximum of the
+ *                cross-correlation; not the minimum squared error, which rewards pushing a false alarm out of the band or over a pole).
+ *                Ties go to the smaller dy^2 + dx^2, then the smaller dy, then the smaller dx: a table without hits gives (0, 0).  The
+ *                order is the maximum of one 64-bit key, hits << 27 | (8191 - (dy^2 + dx^2)) << 14 | (127 - (dy + R)) << 7 |
+ *                (127 - (dx + R)), which H * W < 2^31 keeps below 2^58
+ * rows, pixels and best of the frames below n_valid are zeroed by the call, in stream order, and then written; frames from n_valid on are
+ * neither read nor written, in any buffer, and n_valid == 0 launches nothing.
+ *   total         int64 [2][2 R + 1][2 R + 2] += rows over the valid frames; single words: a frame adds at most H * W to a cell
+ *   total_pixels  int64 [2][2] += pixels
+ *   frames        int64 [1] += n_valid
+ * The sums are integers and every total is added frame by frame by one thread: the state does not depend on the schedule or on how a
+ * sequence is cut into batches.  Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W < 2^31; masks aligned to their element size, every other
+ * pointer to 8 bytes.
+ * disp_pack turns both masks into bit planes, a wave's ballot of the class test being one word of 64 pixels: label rows of ceil(W / 64)
+ * words, and prediction rows EXTENDED by a periodic halo, bit i = P[(i - R) mod W] for i < W + 2 R, in ceil((W + 2 R) / 64) + 1 words, so
+ * that the 64 bits meeting a label word under any dx are a funnel shift of two neighbouring words; it also counts the predicted pixels
+ * per row and `pixels`.  disp_corr gives a workgroup one (frame, class, dy) and a segment of rows of the band, a lane one dx: the label
+ * word is uniform and skipped when zero, else AND and popcount into a register, one 64-bit atomic per lane at the end; one more lane sums
+ * the row counts into kept.  disp_best takes the maximum of the key, disp_total adds the batch to the totals.
+ *   workspace  dc_displacement_workspace(B, H, W, R) bytes, 8-byte aligned: the bit planes and the row counts, B * 2 * H * ((ceil(W / 64)
+ *              + ceil((W + 2 R) / 64) + 1) * 8 + 4); 0 = arguments out of range.
+ * dc_displacement_block: the pixels of a word and the label rows of a segment one workgroup of disp_corr covers (a host function; tests
+ * derive shapes from it).  dc_displacement_score makes no synchronisation and runs on the caller's stream; a failed argument check sets
+ * the message and launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_displacement_block(int* bits, int* rows);
+size_t dc_displacement_workspace(int B, int H, int W, int R);
+int dc_displacement_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int R,
+                          int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* best, int64_t* total, int64_t* total_pixels,
+                          int64_t* frames, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Probabilistic verification (nn.ProbabilitySkill; predict.py --prob_skill): the integers behind the reliability diagram, the Brier score

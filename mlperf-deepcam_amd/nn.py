@@ -2772,6 +2772,162 @@ def distance_from_rows(rows, baddeley, radius: int, height: int, width: int, row
     return [DistanceSkill.decode(r, b, 1, radius, height, width, row_range) for r, b in zip(rows.tolist(), baddeley.tolist())]
 
 
+# ---------------------------------------------------------------------------------------------- displacement verification
+DISPLACEMENT_RADIUS = 16
+DISPLACEMENT_MAX_RADIUS = 63
+DISPLACEMENT_MAX_BATCH = 4095
+
+
+def displacement_best(table, radius: int):
+    """(dy, dx, hits, kept[dy]) of one class's table [2 R + 1][2 R + 2] in Python ints: the most hits, ties to the smaller dy^2 + dx^2, then
+    the smaller dy, then the smaller dx -- the order of dc_displacement_score's key; a table without hits gives (0, 0)."""
+    R = int(radius)
+    hits, _, dy, dx = max((int(table[dy + R][dx + R]), -(dy * dy + dx * dx), -dy, -dx) for dy in range(-R, R + 1) for dx in range(-R, R + 1))
+    return -dy, -dx, hits, int(table[R - dy][2 * R + 1])
+
+
+class DisplacementSkill:
+    """Displacement verification on the device (dc_displacement_score, csrc/displacement.hip): per frame and class (1, 2) the overlap of the
+    labelled mask with the predicted mask moved by every (dy, dx), |dy|, |dx| <= radius -- columns periodic, always; rows never: pixels
+    moved over a pole are lost --, the predicted pixels each dy keeps inside the band, and the best shift, the one with the most hits: the
+    rigid-shift part of the CRA method.  Integers, per frame and as running totals over all frames since reset(); decode() turns a table
+    into the shift, the scores without and with it and the CRA decomposition of the error into displacement, volume and pattern.
+    1 <= radius <= 63 and 2 radius + 1 <= width.  row_range is the band of LABEL rows scored (a tropics-only score); predicted pixels from
+    anywhere in the frame may move into it.  No latitude weighting, no kilometres, no sub-pixel shifts.
+    Memory: a workspace of bit planes (dc_displacement_workspace; 3.8 MB at 8 x 768 x 1152, R = 16) beside batch * 2 * (2 R + 1) * (2 R + 2)
+    * 8 bytes of rows and the totals.  A call launches on the current stream and does not synchronise; state() and result() read back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, radius: int = DISPLACEMENT_RADIUS, row_range=None, device=None):
+        if batch < 1 or batch > DISPLACEMENT_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError(f"DisplacementSkill: batch must lie in [1, {DISPLACEMENT_MAX_BATCH}], height and width be positive and "
+                                    "height * width below 2^31")
+        R = int(radius)
+        if not 1 <= R <= DISPLACEMENT_MAX_RADIUS:
+            raise L.DeepcamHipError(f"DisplacementSkill: the radius must lie in [1, {DISPLACEMENT_MAX_RADIUS}], got {radius}")
+        if 2 * R + 1 > width:
+            raise L.DeepcamHipError(f"DisplacementSkill: the window of 2 * {R} + 1 columns must not be wider than the frame ({width})")
+        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        if not 0 <= row0 < row1 <= height:
+            raise L.DeepcamHipError(f"DisplacementSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
+        self.B, self.H, self.W, self.R, self.row_range = batch, height, width, R, (row0, row1)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        S = 2 * R + 1
+        self._rows = torch.zeros((batch, 2, S, S + 1), dtype=torch.int64, device=dev)
+        dev = self.device = self._rows.device
+        self._pixels = torch.zeros((batch, 2, 2), dtype=torch.int64, device=dev)
+        self._best = torch.zeros((batch, 2, 4), dtype=torch.int64, device=dev)
+        self._total = torch.zeros((2, S, S + 1), dtype=torch.int64, device=dev)
+        self._total_pixels = torch.zeros((2, 2), dtype=torch.int64, device=dev)
+        self._frames = torch.zeros((1,), dtype=torch.int64, device=dev)
+        size = L.load().dc_displacement_workspace(batch, height, width, R)
+        if size == 0:
+            raise L.DeepcamHipError("DisplacementSkill: dc_displacement_workspace refused the shape")
+        self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
+        self._nv = 0
+
+    def _check(self, t, name: str) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
+                or t.device != self.device or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"DisplacementSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
+                                    f"on {self.device}, got {got}")
+
+    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "DisplacementSkill":
+        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
+        are neither read nor written."""
+        self._check(pred, "pred")
+        self._check(truth, "truth")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"DisplacementSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
+        L.call("dc_displacement_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth),
+               self._BYTES[truth.dtype], self.R, self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
+               L.dptr(self._best), L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
+        self._nv = nv
+        return self
+
+    def frame_rows(self):
+        """(rows int64 [n_valid, 2, 2 R + 1, 2 R + 2], pixels int64 [n_valid, 2, 2], best int64 [n_valid, 2, 4]) of the last call: views of
+        the object's device buffers, not synchronised"""
+        return self._rows[:self._nv], self._pixels[:self._nv], self._best[:self._nv]
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for t in (self._total, self._total_pixels, self._frames):
+            t.zero_()
+
+    def state(self) -> dict:
+        """on the host, as Python ints: total [2][2 R + 1][2 R + 2], pixels [2][2] and frames"""
+        return {"total": [[[int(v) for v in row] for row in cls] for cls in self._total.cpu().tolist()],
+                "pixels": [[int(v) for v in cls] for cls in self._total_pixels.cpu().tolist()], "frames": int(self._frames.cpu()[0])}
+
+    def result(self, surface: bool = False) -> dict:
+        """decode() of the object's state: one common shift for all frames since reset(), the systematic displacement"""
+        s = self.state()
+        return self.decode(s["total"], s["pixels"], s["frames"], self.R, self.H, self.W, self.row_range, surface)
+
+    @staticmethod
+    def decode(total, pixels, frames, radius: int, height: int, width: int, row_range=None, surface: bool = False) -> dict:
+        """Per class ("class_1", "class_2"), in float64 from the exact integers; None wherever a denominator is 0:
+        pixels {"predicted" (whole frame), "labelled" (in the band)}; best, the raw integers [dy, dx, hits, kept[dy]] of the best shift;
+        shift {"rows": dy, "cols": dx, "pixels": sqrt(dy^2 + dx^2), "lat_deg", "lon_deg"} by the steps of linspace(-90, 90, H) and
+        linspace(-180, 180, W) -- row 0 is -90 degrees, a positive dy is poleward-north; at_edge, |dy| = R or |dx| = R: the window was too
+        small; hits_unshifted, hits_shifted; csi, pod, far, each {"unshifted", "shifted"}, from hits, kept[dy] and labelled (CSI = hits /
+        (kept[dy] + labelled - hits)); and the CRA decomposition for binary fields with N = frames * band rows * W: mse_total = (kept[0] +
+        labelled - 2 hits[0][0]) / N, mse_shifted likewise at the best shift, mse_displacement = mse_total - mse_shifted, mse_volume =
+        ((kept[dy] - labelled) / N)^2, mse_pattern = mse_shifted - mse_volume, and share {"displacement", "volume", "pattern"} of
+        mse_total.  surface=True adds csi_surface, float64 [2 R + 1][2 R + 1], the CSI of every shift (NaN where undefined)."""
+        R = int(radius)
+        S = 2 * R + 1
+        row0, row1 = (0, int(height)) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        N = int(frames) * (row1 - row0) * int(width)
+        out = {}
+        for k in range(2):
+            table = [[int(v) for v in row] for row in total[k]]
+            if len(table) != S or any(len(row) != S + 1 for row in table):
+                raise L.DeepcamHipError(f"DisplacementSkill.decode: a table holds [2 R + 1][2 R + 2] = [{S}][{S + 1}] cells")
+            predicted, labelled = int(pixels[k][0]), int(pixels[k][1])
+            dy, dx, hits, kept = displacement_best(table, R)
+            hits0, kept0 = table[R][R], table[R][S]
+            entry = {"pixels": {"predicted": predicted, "labelled": labelled}, "best": [dy, dx, hits, kept],
+                     "shift": {"rows": dy, "cols": dx, "pixels": math.sqrt(dy * dy + dx * dx),
+                               "lat_deg": None if height < 2 else dy * 180.0 / (height - 1),
+                               "lon_deg": None if width < 2 else dx * 360.0 / (width - 1)},
+                     "at_edge": abs(dy) == R or abs(dx) == R, "hits_unshifted": hits0, "hits_shifted": hits}
+            both = ((hits0, kept0), (hits, kept))
+            entry["csi"] = {n: _ratio(h, kp + labelled - h) for n, (h, kp) in zip(("unshifted", "shifted"), both)}
+            entry["pod"] = {n: _ratio(h, labelled) for n, (h, kp) in zip(("unshifted", "shifted"), both)}
+            entry["far"] = {n: _ratio(kp - h, kp) for n, (h, kp) in zip(("unshifted", "shifted"), both)}
+            if N > 0:
+                mse_total, mse_shifted = (kept0 + labelled - 2 * hits0) / N, (kept + labelled - 2 * hits) / N
+                volume = ((kept - labelled) / N) ** 2
+                parts = {"displacement": mse_total - mse_shifted, "volume": volume, "pattern": mse_shifted - volume}
+                entry.update(mse_total=mse_total, mse_shifted=mse_shifted, mse_displacement=parts["displacement"], mse_volume=volume,
+                             mse_pattern=parts["pattern"], share={n: _ratio(v, mse_total) for n, v in parts.items()})
+            else:
+                entry.update(mse_total=None, mse_shifted=None, mse_displacement=None, mse_volume=None, mse_pattern=None,
+                             share={"displacement": None, "volume": None, "pattern": None})
+            if surface:
+                t = np.asarray(table, np.float64)
+                union = t[:, S:] + labelled - t[:, :S]
+                entry["csi_surface"] = np.where(union > 0, t[:, :S] / np.where(union > 0, union, 1.0), np.nan)
+            out[f"class_{k + 1}"] = entry
+        return out
+
+
+def displacement_from_rows(rows, pixels, radius: int, height: int, width: int, row_range=None, surface: bool = False) -> list:
+    """DisplacementSkill.decode of single frames: rows int64 [n, 2, 2 R + 1, 2 R + 2] and pixels int64 [n, 2, 2] (what frame_rows()
+    returns, on the host) give a list of n dictionaries, each the decode of that frame alone."""
+    rows, pixels = np.asarray(rows), np.asarray(pixels)
+    S = 2 * int(radius) + 1
+    if rows.ndim != 4 or rows.shape[1:] != (2, S, S + 1) or pixels.shape != (rows.shape[0], 2, 2):
+        raise L.DeepcamHipError(f"displacement_from_rows: rows [n, 2, 2 R + 1, 2 R + 2] and pixels [n, 2, 2], got shapes {rows.shape} and "
+                                f"{pixels.shape}")
+    return [DisplacementSkill.decode(r, p, 1, radius, height, width, row_range, surface) for r, p in zip(rows.tolist(), pixels.tolist())]
+
+
 # ---------------------------------------------------------------------------------------------- probabilistic verification
 PROB_BINS = 20
 PROB_MAX_BINS = 256

@@ -85,6 +85,13 @@ class and direction (miss, false alarm), the sources per ring of distance with t
 sum.  Every output file also carries ``distance`` (int64 [2, 2, R + 4]) and ``distance_baddeley`` (int64 [2]); ``summary.json`` gains
 ``distance_skill`` (radius, wrap, rows, frames and per class the mean error distances, the Hausdorff and partial Hausdorff distance,
 Baddeley's Delta, the hit rate and success ratio within r pixels, and the raw totals as integers).
+With --displacement (which implies --verify) nn.DisplacementSkill scores, behind every batch and on the device, the same prediction side
+against the unfiltered labels by displacement: per class the overlap with the prediction moved by every (dy, dx) within
+--displacement_radius rows and columns (columns periodic, rows never; label rows --displacement_rows I0 I1, the whole frame by default) and
+the shift with the most hits.  Every output file also carries ``displacement`` (int64 [2, 2 R + 1, 2 R + 2]: the hits per shift, the last
+cell of a row the predicted pixels that dy keeps in the band), ``displacement_pixels`` (int64 [2, 2]) and ``displacement_best`` (int64
+[2, 4]: dy, dx, hits, kept); ``summary.json`` gains ``displacement`` (radius, rows, frames, per class the pooled decode -- one common
+shift for all frames, the scores without and with it, the CRA decomposition -- and the means of the per-frame best shifts).
 With --prob_skill (which implies --verify) nn.ProbabilitySkill scores, behind every batch and on the device, the classifier's softmax
 probabilities -- the stored fp32 logits, never the mask, so --event_filter does not change them -- against the unfiltered labels: per
 class the joint histogram of (probability bin of --prob_bins bins, label is the class) with the sum of the probabilities per cell, and the
@@ -208,6 +215,18 @@ class _DistanceSkill(argparse.Action):
 
     def __call__(self, parser, namespace, values, option_string=None):
         namespace.distance_skill = True
+        namespace.verify = True
+        namespace.events = True
+
+
+class _Displacement(argparse.Action):
+    """--displacement: implies --verify (and with it --events)"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.displacement = True
         namespace.verify = True
         namespace.events = True
 
@@ -348,6 +367,15 @@ def build_parser():
     AP.add_argument("--distance_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --distance_skill: count the sources "
                     "in the rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     AP.add_argument("--distance_no_wrap", action="store_true", default=S, help="with --distance_skill: do not take the columns as periodic")
+    # likewise the --displacement* flags (DISPLACEMENT_DEFAULTS)
+    AP.add_argument("--displacement", action=_Displacement, help="displacement verification on the device (implies --verify; the files "
+                    "need climate/labels_0): the shift of --verify's prediction side that overlaps the labels most, the scores without "
+                    "and with it and the CRA decomposition of the error, per class.  Datasets 'displacement', 'displacement_pixels', "
+                    "'displacement_best'; 'displacement' in the summary")
+    AP.add_argument("--displacement_radius", type=int, default=S, help="with --displacement: the largest shift in rows and in columns, "
+                    "1 .. 63, with 2 R + 1 <= --width (16)")
+    AP.add_argument("--displacement_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --displacement: score the label "
+                    "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     # likewise the --prob_* flags (PROB_DEFAULTS)
     AP.add_argument("--prob_skill", action=_ProbSkill, help="probabilistic verification on the device (implies --verify; the files need "
                     "climate/labels_0): reliability diagram, Brier score with its decomposition, POD / POFD / CSI per probability threshold "
@@ -487,6 +515,33 @@ def distance_summary(radius: int, wrap: bool, row_range, height: int, width: int
     for k in range(2):
         out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], total=[[int(v) for v in d] for d in state["total"][k]],
                                      total_baddeley=int(state["baddeley"][k]))
+    return out
+
+
+DISPLACEMENT_DEFAULTS = {"displacement": False, "displacement_radius": dnn.DISPLACEMENT_RADIUS, "displacement_rows": None}
+
+
+def displacement_options(pargs) -> dict:
+    """the keyword arguments of nn.DisplacementSkill from the --displacement* flags (DISPLACEMENT_DEFAULTS where one was not given)"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in DISPLACEMENT_DEFAULTS.items()})
+    return {"radius": int(a.displacement_radius),
+            "row_range": None if a.displacement_rows is None else (int(a.displacement_rows[0]), int(a.displacement_rows[1]))}
+
+
+def displacement_summary(radius: int, row_range, height: int, width: int, state: dict, frame_best) -> dict:
+    """the `displacement` entry of summary.json from nn.DisplacementSkill.state() and the per-frame best shifts (int64 [n, 2, 4], the
+    files' displacement_best): the radius, the scored rows, the frames and, per class, the pooled decode (its "best" the raw integers of
+    the common shift) with frame_shifts: over the frames that have hits, their number and the mean dy, mean dx and mean length of the
+    per-frame best shifts (None without such a frame)"""
+    decoded = dnn.DisplacementSkill.decode(state["total"], state["pixels"], state["frames"], radius, height, width, row_range)
+    best = np.asarray(frame_best, np.int64).reshape(-1, 2, 4)
+    out = {"radius": int(radius), "rows": [int(row_range[0]), int(row_range[1])], "frames": int(state["frames"])}
+    for k in range(2):
+        shifts = best[best[:, k, 2] > 0, k, :2].astype(np.float64)
+        n = len(shifts)
+        out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], frame_shifts={
+            "frames": n, "mean_rows": float(shifts[:, 0].mean()) if n else None, "mean_cols": float(shifts[:, 1].mean()) if n else None,
+            "mean_pixels": float(np.sqrt((shifts ** 2).sum(axis=1)).mean()) if n else None})
     return out
 
 
@@ -677,7 +732,12 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
-                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0):
+                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0, displacement_window: int = 0):
+        # --displacement: the tables of nn.DisplacementSkill (window = 2 R + 1), the pixel counts and the best shifts beside them
+        S = displacement_window
+        self.displacement = torch.empty((B, 2, S, S + 1), dtype=torch.int64).pin_memory() if S else None
+        self.displacement_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if S else None
+        self.displacement_best = torch.empty((B, 2, 4), dtype=torch.int64).pin_memory() if S else None
         # --distance_skill: the rows of nn.DistanceSkill and the Baddeley sums beside them
         self.distance = torch.empty((B, 2, 2, distance_cells), dtype=torch.int64).pin_memory() if distance_cells else None
         self.distance_baddeley = torch.empty((B, 2), dtype=torch.int64).pin_memory() if distance_cells else None
@@ -760,6 +820,9 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         extra = dict(extra or {}, fss=slot.fss[j].numpy(), fss_pixels=slot.fss_pixels[j].numpy())
                     if slot.distance is not None:
                         extra = dict(extra or {}, distance=slot.distance[j].numpy(), distance_baddeley=slot.distance_baddeley[j].numpy())
+                    if slot.displacement is not None:
+                        extra = dict(extra or {}, displacement=slot.displacement[j].numpy(),
+                                     displacement_pixels=slot.displacement_pixels[j].numpy(), displacement_best=slot.displacement_best[j].numpy())
                     if slot.prob_rows is not None:
                         brier = dnn.brier_from_rows(slot.prob_rows[j].numpy(), slot.prob_pixels[j].numpy())
                         extra = dict(extra or {}, brier=np.asarray([np.nan if v is None else v for v in brier], np.float64),
@@ -771,6 +834,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if plot[j]:
                         rec["plot"] = plot_name(base)
+                    if slot.displacement_best is not None:
+                        rec["displacement_best"] = [[int(v) for v in row] for row in slot.displacement_best[j].tolist()]
                     if slot.dcounts is not None:
                         rec["decision"] = [int(v) for v in slot.dcounts[j].tolist()]
                     if slot.fcounts is not None:
@@ -882,6 +947,8 @@ def main(pargs) -> dict:
     fss = dnn.FractionsSkill(B, H, W, device=device, **fss_options(pargs)) if getattr(pargs, "fss", False) else None
     # --distance_skill: likewise
     dist = dnn.DistanceSkill(B, H, W, device=device, **distance_options(pargs)) if getattr(pargs, "distance_skill", False) else None
+    # --displacement: likewise
+    disp = dnn.DisplacementSkill(B, H, W, device=device, **displacement_options(pargs)) if getattr(pargs, "displacement", False) else None
     # --prob_skill: behind every batch, the classifier's stored logits against the labels
     prob = None
     if getattr(pargs, "prob_skill", False):
@@ -901,7 +968,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
-                             prob is not None, decide is not None, dist.R + 4 if dist else 0))
+                             prob is not None, decide is not None, dist.R + 4 if dist else 0, 2 * disp.R + 1 if disp else 0))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -937,6 +1004,11 @@ def main(pargs) -> dict:
                 dist_rows, dist_baddeley = dist(dmask, y, n_valid=nv).frame_rows()
                 slot.distance[:nv].copy_(dist_rows, non_blocking=True)
                 slot.distance_baddeley[:nv].copy_(dist_baddeley, non_blocking=True)
+            if disp is not None:
+                disp_rows, disp_pixels, disp_best = disp(dmask, y, n_valid=nv).frame_rows()
+                slot.displacement[:nv].copy_(disp_rows, non_blocking=True)
+                slot.displacement_pixels[:nv].copy_(disp_pixels, non_blocking=True)
+                slot.displacement_best[:nv].copy_(disp_best, non_blocking=True)
             if prob is not None:
                 prob_rows, prob_pixels = prob(predictor.logits_buffer, y, n_valid=nv).frame_rows()
                 slot.prob_rows[:nv].copy_(prob_rows, non_blocking=True)
@@ -990,6 +1062,7 @@ def main(pargs) -> dict:
     comp_state = comp.state() if comp is not None else None
     fss_state = fss.state() if fss is not None else None
     dist_state = dist.state() if dist is not None else None
+    disp_state = disp.state() if disp is not None else None
     prob_state = prob.state() if prob is not None else None
     elapsed = time.perf_counter() - t0
 
@@ -1014,6 +1087,8 @@ def main(pargs) -> dict:
         summary["fss"] = fss_summary(fss.windows, fss.row_range, W, fss_state)
     if dist is not None:
         summary["distance_skill"] = distance_summary(dist.R, dist.wrap, dist.row_range, H, W, dist_state)
+    if disp is not None:
+        summary["displacement"] = displacement_summary(disp.R, disp.row_range, H, W, disp_state, [r["displacement_best"] for r in records])
     if prob is not None:
         write_datasets(os.path.join(pargs.output_dir, "prob_skill.h5"), prob_arrays(prob.K, prob_state))
         summary["prob_skill"] = prob_summary(prob.K, prob_state)
