@@ -97,6 +97,8 @@ int dc_reset_options(void);
  *     dist_horz (the capped squared distance maps, the ring counters, the sums and the Baddeley term), dist_total (the running totals)
  *   displacement verification (dc_displacement_score): disp_pack (the four bit planes, the predicted pixels per row, the pixel counts),
  *     disp_corr (the overlap table and `kept`), disp_best (the best shift per frame and class), disp_total (the running totals)
+ *   scale-separation verification (dc_scale_score): scale_sums (the block sums of levels 0 .. 6 per tile, the pixel counts), scale_coarse
+ *     (levels 7 and 8 from the tiles' sums; launched only for L > 6), scale_total (the running totals)
  *   aux                                  every other launch site (one entry per checked site: packing, gathers, finalizes, reductions, ...) */
 int dc_launch_log_begin(void);
 int dc_launch_log_end(char* buf, size_t cap);
@@ -1176,6 +1178,52 @@ size_t dc_displacement_workspace(int B, int H, int W, int R);
 int dc_displacement_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int R,
                           int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* best, int64_t* total, int64_t* total_pixels,
                           int64_t* frames, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scale-separation verification (nn.ScaleSkill; predict.py --scale_skill): the integers behind the intensity-scale skill score of Casati,
+ * Ross & Stephenson (2004) with the energies of Casati (2010), the scale-separation family of Gilleland et al. (2009).  The binary error
+ * field of a class is split by a 2-D Haar transform into components of spatial scale 1, 2, 4, ... grid pixels; the squared error and the
+ * energy of prediction and labels are reported per scale.  It answers "at which scale does the error sit", which the FSS (everything below
+ * the window), the best shift (one vector) and the distance maps (a length without a scale) do not.  Everything is an integer; the host
+ * decodes (nn.ScaleSkill.decode).
+ *   pred, truth  [B][H][W] of 1-, 4- or 8-byte integers (pred_bytes, truth_bytes), each side with its own element size: class k in {1, 2}
+ *                is the full-width value k, every other value is background -- dc_fss_score's rule
+ *   row0, row1   the band, 0 <= row0 < row1 <= H
+ *   L            the levels, 1 <= L <= 8; the tile T = 2^L must divide both row1 - row0 and W (row0 itself may be any row)
+ *   origins      int32 [O] in DEVICE memory (a host pointer would not survive a recorded launch list), 1 <= O <= 8, each 0 <= c < T
+ * For origin c the band is tiled by blocks of side 2^j, j = 0 .. L, on a grid that starts at row row0 and column c; columns are taken
+ * modulo W, so a block may lie across the seam; rows are never periodic.  S_F, S_O: the pixels of a block with pred == k, truth == k.
+ *   rows    int64 [B][2][O][L + 1][3]: per frame, class, origin and level (A, B, C) = (sum (S_F - S_O)^2, sum S_F^2, sum S_O^2) over the
+ *           blocks of that level
+ *   pixels  int64 [B][2][2]: per class (# pred == k, # truth == k) inside the band
+ * rows and pixels of the frames below n_valid are zeroed by the call, in stream order, and then written; frames from n_valid on are
+ * neither read nor written, in any buffer, and n_valid == 0 launches nothing.  An origin outside [0, T) is the caller's error that only
+ * the device can see: it is skipped, its rows stay zero, and nothing is read or written out of bounds.
+ *   total         int64 [2][O][L + 1][3][2] += rows over the valid frames, as two-word integers (lo, hi) in dc_fss_score's convention,
+ *                 lo += x, hi += carry: a frame adds up to H * W * 4^L < 2^47 to a cell, so one word would last 65,536 frames only
+ *   total_pixels  int64 [2][2] += pixels
+ *   frames        int64 [1] += n_valid
+ * At level 0 A is the number of mismatched pixels, B and C equal `pixels`, the triple does not depend on the origin and equals
+ * dc_fss_score's row of window 1 on the same band.  With Q_j any of A, B, C at level j, the Haar component of scale 2^j carries
+ * E_j = (4 Q_j - Q_{j+1}) / 4^(j+1) for j < L (the detail between the block means of side 2^j and 2^(j+1)) and E_L = Q_L / 4^L (the
+ * father component: the tile means); the E_j are non-negative and sum to Q_0.
+ * The sums are integers and every total is added frame by frame by one thread: the state does not depend on the schedule or on how a
+ * sequence is cut into batches.  Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W < 2^31; masks aligned to their element size, origins
+ * and workspace to 4 bytes, every other pointer to 8.
+ * scale_sums gives a workgroup one 64 x 64 tile of one (frame, origin) and a thread one 4 x 4 block, in Morton order, so that levels 0 to
+ * 2 stay in registers, 3 to 5 are lane exchanges and 6 goes through LDS; one 64-bit atomic per non-zero cell.  For L > 6 it leaves each
+ * tile's four sums in the workspace and scale_coarse forms levels 7 and 8 from them (sums up to 2^16 in 32-bit words, squares up to 2^32
+ * in 64 bits).  scale_total adds the batch to the totals.
+ *   workspace  dc_scale_workspace(B, H, W, L, O) bytes, 4-byte aligned: four 32-bit sums per tile, B * O * ceil(H / 64) * ceil(W / 64)
+ *              * 16, whatever L (read and written for L > 6 only); 0 = arguments out of range (T > H or T does not divide W included).
+ * dc_scale_block: the columns and rows of the workgroup tile (a host function; tests derive shapes from it).  dc_scale_score makes no
+ * synchronisation and runs on the caller's stream; a failed argument check sets the message and launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_scale_block(int* cols, int* rows);
+size_t dc_scale_workspace(int B, int H, int W, int L, int O);
+int dc_scale_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int L, int O,
+                   const int32_t* origins /*device*/, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
+                   int64_t* total_pixels, int64_t* frames, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Probabilistic verification (nn.ProbabilitySkill; predict.py --prob_skill): the integers behind the reliability diagram, the Brier score

@@ -196,6 +196,9 @@ _SIGS = {
     "dc_displacement_block": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_displacement_workspace": (SZ, [I, I, I, I]),
     "dc_displacement_score": (I, [I, I, I, I, P, I, P, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "dc_scale_block": (I, [C.POINTER(I), C.POINTER(I)]),
+    "dc_scale_workspace": (SZ, [I, I, I, I, I]),
+    "dc_scale_score": (I, [I, I, I, I, P, I, P, I, I, I, P, I, I, P, P, P, P, P, P, P]),
     "dc_prob_block": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_prob_score": (I, [I, I, I, I, P, P, I, I, P, P, P, P, P, P, P, P]),
     "dc_decide_block": (I, [C.POINTER(I)]),

@@ -19,6 +19,7 @@ import math
 import os
 import re
 from collections import OrderedDict
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -2926,6 +2927,206 @@ def displacement_from_rows(rows, pixels, radius: int, height: int, width: int, r
         raise L.DeepcamHipError(f"displacement_from_rows: rows [n, 2, 2 R + 1, 2 R + 2] and pixels [n, 2, 2], got shapes {rows.shape} and "
                                 f"{pixels.shape}")
     return [DisplacementSkill.decode(r, p, 1, radius, height, width, row_range, surface) for r, p in zip(rows.tolist(), pixels.tolist())]
+
+
+# ---------------------------------------------------------------------------------------------- scale-separation verification
+SCALE_MAX_LEVELS = 8
+SCALE_MAX_ORIGINS = 8
+SCALE_MAX_BATCH = 4095
+SCALE_LISTS = ("mse", "mse_share", "skill", "energy_pred", "energy_truth", "energy_rel_diff")
+
+
+def scale_levels(rows_in_band: int, width: int) -> int:
+    """the largest L <= 8 whose tile T = 2^L divides both the rows of the band and the width (7, T = 128, for 768 x 1152); 0 where one
+    of them is odd, which ScaleSkill refuses"""
+    L_ = 0
+    while L_ < SCALE_MAX_LEVELS and int(rows_in_band) % (2 << L_) == 0 and int(width) % (2 << L_) == 0:
+        L_ += 1
+    return L_
+
+
+def _scale_components(q) -> list:
+    """the Haar components E_0 .. E_L as Fractions from the block sums Q_0 .. Q_L of one term: E_j = (4 Q_j - Q_{j+1}) / 4^(j+1) for
+    j < L, E_L = Q_L / 4^L"""
+    n = len(q) - 1
+    return [Fraction(4 * q[j] - q[j + 1], 4 ** (j + 1)) for j in range(n)] + [Fraction(q[n], 4 ** n)]
+
+
+def _float(v):
+    return None if v is None else float(v)
+
+
+class ScaleSkill:
+    """Scale-separation verification on the device (dc_scale_score, csrc/scale.hip): the integers behind the intensity-scale skill score
+    (Casati, Ross & Stephenson 2004; energies: Casati 2010).  Per frame, class (1, 2), column origin and level j = 0 .. levels the sums
+    (A, B, C) = (sum (S_F - S_O)^2, sum S_F^2, sum S_O^2) over the disjoint blocks of side 2^j GRID PIXELS that tile the rows row_range
+    from (row0, origin) on, S_F and S_O the predicted and labelled pixels of the class in a block -- columns periodic, always; rows never
+    --, and their running totals over all frames since reset() as two-word integers.  decode() turns them, in exact arithmetic, into the
+    squared error and the energies of the 2-D Haar components of scale 1, 2, ..., 2^levels pixels.  The tile T = 2^levels must divide
+    both the rows of the band and the width; levels=None takes scale_levels(), the largest that does.  origins: 1 to 8 column offsets in
+    [0, T) of the dyadic grid, scored in one pass: their spread shows how much a result owes to where the grid falls.  No latitude
+    weighting, no kilometres, tiles instead of the whole domain, and "intensity" is the class, not a threshold ladder.
+    Memory: batch * 2 * O * (levels + 1) * 3 * 8 bytes of rows and a workspace of 16 bytes per 64 x 64 tile and origin
+    (dc_scale_workspace); no per-pixel buffer.  A call launches on the current stream and does not synchronise; state() and result() read
+    back."""
+
+    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+    def __init__(self, batch: int, height: int, width: int, levels: Optional[int] = None, origins: Sequence[int] = (0,), row_range=None,
+                 device=None):
+        if batch < 1 or batch > SCALE_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError(f"ScaleSkill: batch must lie in [1, {SCALE_MAX_BATCH}], height and width be positive and height * width "
+                                    "below 2^31")
+        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        if not 0 <= row0 < row1 <= height:
+            raise L.DeepcamHipError(f"ScaleSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
+        lv = scale_levels(row1 - row0, width) if levels is None else int(levels)
+        if levels is None and lv < 1:
+            raise L.DeepcamHipError(f"ScaleSkill: levels=None needs an even number of rows in the band and an even width, got {row1 - row0} "
+                                    f"and {width}")
+        if not 1 <= lv <= SCALE_MAX_LEVELS:
+            raise L.DeepcamHipError(f"ScaleSkill: levels must lie in [1, {SCALE_MAX_LEVELS}], got {levels}")
+        T = 1 << lv
+        if (row1 - row0) % T or width % T:
+            raise L.DeepcamHipError(f"ScaleSkill: the tile 2^levels = {T} must divide the rows of the band ({row1 - row0}) and the width "
+                                    f"({width})")
+        try:
+            origins = [int(c) for c in origins]
+        except TypeError:
+            raise L.DeepcamHipError(f"ScaleSkill: origins is a sequence of column offsets, got {origins!r}") from None
+        if not 1 <= len(origins) <= SCALE_MAX_ORIGINS:
+            raise L.DeepcamHipError(f"ScaleSkill: between 1 and {SCALE_MAX_ORIGINS} origins, got {len(origins)}")
+        for c in origins:
+            if not 0 <= c < T:
+                raise L.DeepcamHipError(f"ScaleSkill: an origin is a column offset in [0, {T}), got {c}")
+        self.B, self.H, self.W, self.L, self.O = batch, height, width, lv, len(origins)
+        self.origins, self.row_range = origins, (row0, row1)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._origins = torch.tensor(origins, dtype=torch.int32, device=dev)
+        dev = self.device = self._origins.device
+        self._rows = torch.zeros((batch, 2, self.O, lv + 1, 3), dtype=torch.int64, device=dev)
+        self._pixels = torch.zeros((batch, 2, 2), dtype=torch.int64, device=dev)
+        self._total = torch.zeros((2, self.O, lv + 1, 3, 2), dtype=torch.int64, device=dev)          # (lo, hi)
+        self._total_pixels = torch.zeros((2, 2), dtype=torch.int64, device=dev)
+        self._frames = torch.zeros((1,), dtype=torch.int64, device=dev)
+        size = L.load().dc_scale_workspace(batch, height, width, lv, self.O)
+        if size == 0:
+            raise L.DeepcamHipError("ScaleSkill: dc_scale_workspace refused the shape")
+        self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
+        self._nv = 0
+
+    def _check(self, t, name: str) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
+                or t.device != self.device or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"ScaleSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
+                                    f"on {self.device}, got {got}")
+
+    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "ScaleSkill":
+        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
+        are neither read nor written."""
+        self._check(pred, "pred")
+        self._check(truth, "truth")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.DeepcamHipError(f"ScaleSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
+        L.call("dc_scale_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
+               self.L, self.O, L.dptr(self._origins), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
+               L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
+        self._nv = nv
+        return self
+
+    def frame_rows(self):
+        """(rows int64 [n_valid, 2, O, levels + 1, 3], pixels int64 [n_valid, 2, 2]) of the last call: views of the object's device
+        buffers, not synchronised"""
+        return self._rows[:self._nv], self._pixels[:self._nv]
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for t in (self._total, self._total_pixels, self._frames):
+            t.zero_()
+
+    @staticmethod
+    def combine(total_words) -> list:
+        """[2][O][levels + 1][3] Python ints from the int64 words [2, O, levels + 1, 3, 2] = (lo, hi): (hi << 64) | lo, lo unsigned"""
+        words = np.asarray(total_words, np.int64)
+        if words.ndim != 5 or words.shape[0] != 2 or words.shape[3:] != (3, 2):
+            raise L.DeepcamHipError(f"ScaleSkill: the totals are int64 [2, O, levels + 1, 3, 2], got shape {words.shape}")
+        return [[[[(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in level] for level in origin] for origin in cls]
+                for cls in words.tolist()]
+
+    def state(self) -> dict:
+        """on the host: total [2][O][levels + 1][3] as Python ints, pixels [2][2] ((pred, truth) per class) and frames as ints"""
+        return {"total": self.combine(self._total.cpu().numpy()), "pixels": [[int(v) for v in row] for row in self._total_pixels.cpu().tolist()],
+                "frames": int(self._frames.cpu()[0])}
+
+    def result(self) -> dict:
+        """decode() of the object's state"""
+        s = self.state()
+        return self.decode(s["total"], s["pixels"], s["frames"], self.L, self.row_range[1] - self.row_range[0], self.W, self.origins)
+
+    @staticmethod
+    def decode(total, pixels, frames, levels: int, rows_in_band: int, width: int, origins=None) -> dict:
+        """Per class ("class_1", "class_2"), computed in exact arithmetic (Python ints and fractions.Fraction) from total [2][O][levels +
+        1][3] and pixels [2][2]; every reported number is one float() of the exact value, None wherever a denominator is 0.  With N =
+        frames * rows_in_band * width and Q_j one of A, B, C at level j, the Haar component of scale 2^j carries E_j = (4 Q_j - Q_{j+1}) /
+        4^(j+1) for j < levels (the detail between block means of side 2^j and 2^(j+1)) and E_L = Q_L / 4^L (the father component: the
+        TILE means, not the domain mean).  Per origin, lists over j = 0 .. levels: mse = E_j(A) / N, which sum to the per-pixel error
+        rate; mse_share = E_j(A) / A_0; skill = 1 - mse (levels + 1) / mse_random with mse_random = p (1 - o) + o (1 - p), p and o the
+        pooled predicted and labelled rates -- Casati's equipartition of the random error over the levels + 1 components;
+        energy_pred = E_j(B) / N, energy_truth = E_j(C) / N, energy_rel_diff = (pred - truth) / (pred + truth).
+        The entry holds pixels {"predicted", "labelled"}, base_rate = labelled / N, bias = predicted / labelled, mse_random, scales =
+        [1, 2, ..., 2^levels], the six lists as the exact mean over the origins (energy_rel_diff from the mean energies), by_origin (a
+        list of {"origin", the six lists}), origin_spread (max - min of mse[j] over the origins) and skilful_scale: the smallest 2^j from
+        which the mean skill of every component up to levels - 1 is positive, else None."""
+        n = int(levels)
+        N = int(frames) * int(rows_in_band) * int(width)
+        out = {}
+        for k in range(2):
+            table = [[[int(v) for v in level] for level in origin] for origin in total[k]]
+            if not table or any(len(origin) != n + 1 or any(len(level) != 3 for level in origin) for origin in table):
+                raise L.DeepcamHipError(f"ScaleSkill.decode: a class holds [O][levels + 1][3] = [O][{n + 1}][3] cells")
+            O = len(table)
+            names = list(range(O)) if origins is None else [int(c) for c in origins]
+            if len(names) != O:
+                raise L.DeepcamHipError(f"ScaleSkill.decode: {len(names)} origins for a table of {O}")
+            predicted, labelled = int(pixels[k][0]), int(pixels[k][1])
+            rnd = None if N == 0 else Fraction(predicted * (N - labelled) + labelled * (N - predicted), N * N)
+            per = []                                  # per origin: the exact lists
+            for origin in table:
+                ea, eb, ec = (_scale_components([level[i] for level in origin]) for i in range(3))
+                a0 = origin[0][0]
+                per.append({"mse": [None if N == 0 else e / N for e in ea], "mse_share": [None if a0 == 0 else e / a0 for e in ea],
+                            "energy_pred": [None if N == 0 else e / N for e in eb], "energy_truth": [None if N == 0 else e / N for e in ec]})
+            mean = {name: [None if per[0][name][j] is None else sum(p[name][j] for p in per) / O for j in range(n + 1)] for name in per[0]}
+            for entry in per + [mean]:
+                entry["skill"] = [None if not rnd else 1 - m * (n + 1) / rnd for m in entry["mse"]]
+                entry["energy_rel_diff"] = [None if p is None or p + t == 0 else (p - t) / (p + t)
+                                            for p, t in zip(entry["energy_pred"], entry["energy_truth"])]
+            good = None
+            for j in range(n - 1, -1, -1):            # the component n is the father: tile means, not a scale's detail
+                if mean["skill"][j] is None or mean["skill"][j] <= 0:
+                    break
+                good = 1 << j
+            entry = {"pixels": {"predicted": predicted, "labelled": labelled}, "base_rate": None if N == 0 else labelled / N,
+                     "bias": None if labelled == 0 else predicted / labelled, "mse_random": _float(rnd), "scales": [1 << j for j in range(n + 1)]}
+            entry.update({name: [_float(v) for v in mean[name]] for name in SCALE_LISTS})
+            entry["by_origin"] = [dict({"origin": c}, **{name: [_float(v) for v in p[name]] for name in SCALE_LISTS}) for c, p in zip(names, per)]
+            entry["origin_spread"] = [None if N == 0 else float(max(p["mse"][j] for p in per) - min(p["mse"][j] for p in per))
+                                      for j in range(n + 1)]
+            entry["skilful_scale"] = good
+            out[f"class_{k + 1}"] = entry
+        return out
+
+
+def scale_from_rows(rows, pixels, levels: int, rows_in_band: int, width: int, origins=None) -> list:
+    """ScaleSkill.decode of single frames: rows int64 [n, 2, O, levels + 1, 3] and pixels int64 [n, 2, 2] (what frame_rows() returns, on
+    the host) give a list of n dictionaries, each the decode of that frame alone."""
+    rows, pixels = np.asarray(rows), np.asarray(pixels)
+    if rows.ndim != 5 or rows.shape[1] != 2 or rows.shape[3:] != (int(levels) + 1, 3) or pixels.shape != (rows.shape[0], 2, 2):
+        raise L.DeepcamHipError(f"scale_from_rows: rows [n, 2, O, levels + 1, 3] and pixels [n, 2, 2], got shapes {rows.shape} and "
+                                f"{pixels.shape}")
+    return [ScaleSkill.decode(r, p, 1, levels, rows_in_band, width, origins) for r, p in zip(rows.tolist(), pixels.tolist())]
 
 
 # ---------------------------------------------------------------------------------------------- probabilistic verification

@@ -92,6 +92,12 @@ the shift with the most hits.  Every output file also carries ``displacement`` (
 cell of a row the predicted pixels that dy keeps in the band), ``displacement_pixels`` (int64 [2, 2]) and ``displacement_best`` (int64
 [2, 4]: dy, dx, hits, kept); ``summary.json`` gains ``displacement`` (radius, rows, frames, per class the pooled decode -- one common
 shift for all frames, the scores without and with it, the CRA decomposition -- and the means of the per-frame best shifts).
+With --scale_skill (which implies --verify) nn.ScaleSkill scores, behind every batch and on the device, the same prediction side against
+the unfiltered labels by spatial scale: per class, column origin of the dyadic grid (--scale_origins, 0 by default) and level j = 0 ..
+--scale_levels (by default the largest whose tile 2^L divides the scored rows and the width) the sums (A, B, C) over the blocks of side
+2^j grid pixels of the rows --scale_rows I0 I1 (the whole frame by default).  Every output file also carries ``scale`` (int64 [2, O,
+L + 1, 3]) and ``scale_pixels`` (int64 [2, 2]); ``summary.json`` gains ``scale_skill`` (levels, origins, rows, frames and per class the
+pooled decode: squared error, skill and energies per Haar component of scale 1, 2, ..., 2^L pixels).
 With --prob_skill (which implies --verify) nn.ProbabilitySkill scores, behind every batch and on the device, the classifier's softmax
 probabilities -- the stored fp32 logits, never the mask, so --event_filter does not change them -- against the unfiltered labels: per
 class the joint histogram of (probability bin of --prob_bins bins, label is the class) with the sum of the probabilities per cell, and the
@@ -227,6 +233,18 @@ class _Displacement(argparse.Action):
 
     def __call__(self, parser, namespace, values, option_string=None):
         namespace.displacement = True
+        namespace.verify = True
+        namespace.events = True
+
+
+class _ScaleSkill(argparse.Action):
+    """--scale_skill: implies --verify (and with it --events)"""
+
+    def __init__(self, option_strings, dest, **kw):
+        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.scale_skill = True
         namespace.verify = True
         namespace.events = True
 
@@ -376,6 +394,17 @@ def build_parser():
                     "1 .. 63, with 2 R + 1 <= --width (16)")
     AP.add_argument("--displacement_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --displacement: score the label "
                     "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
+    # likewise the --scale_* flags (SCALE_DEFAULTS)
+    AP.add_argument("--scale_skill", action=_ScaleSkill, help="scale-separation verification on the device (implies --verify; the files "
+                    "need climate/labels_0): the squared error of --verify's prediction side and the energies of both sides per 2-D Haar "
+                    "component of scale 1, 2, 4, ... grid pixels, per class (the intensity-scale skill score).  Datasets 'scale', "
+                    "'scale_pixels'; 'scale_skill' in the summary")
+    AP.add_argument("--scale_levels", type=int, default=S, help="with --scale_skill: the levels L, 1 .. 8; the tile 2^L must divide the "
+                    "scored rows and --width (the largest that does)")
+    AP.add_argument("--scale_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --scale_skill: score the rows "
+                    "I0 <= i < I1 only (a latitude band; the whole frame by default)")
+    AP.add_argument("--scale_origins", type=int, nargs="+", default=S, metavar="C", help="with --scale_skill: up to 8 column offsets in "
+                    "[0, 2^L) of the dyadic grid, scored in one pass (0)")
     # likewise the --prob_* flags (PROB_DEFAULTS)
     AP.add_argument("--prob_skill", action=_ProbSkill, help="probabilistic verification on the device (implies --verify; the files need "
                     "climate/labels_0): reliability diagram, Brier score with its decomposition, POD / POFD / CSI per probability threshold "
@@ -542,6 +571,26 @@ def displacement_summary(radius: int, row_range, height: int, width: int, state:
         out[f"class_{k + 1}"] = dict(decoded[f"class_{k + 1}"], frame_shifts={
             "frames": n, "mean_rows": float(shifts[:, 0].mean()) if n else None, "mean_cols": float(shifts[:, 1].mean()) if n else None,
             "mean_pixels": float(np.sqrt((shifts ** 2).sum(axis=1)).mean()) if n else None})
+    return out
+
+
+SCALE_DEFAULTS = {"scale_skill": False, "scale_levels": None, "scale_rows": None, "scale_origins": (0,)}
+
+
+def scale_options(pargs) -> dict:
+    """the keyword arguments of nn.ScaleSkill from the --scale_* flags (SCALE_DEFAULTS where one was not given)"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in SCALE_DEFAULTS.items()})
+    return {"levels": None if a.scale_levels is None else int(a.scale_levels),
+            "row_range": None if a.scale_rows is None else (int(a.scale_rows[0]), int(a.scale_rows[1])),
+            "origins": tuple(int(c) for c in a.scale_origins)}
+
+
+def scale_summary(levels: int, origins, row_range, width: int, state: dict) -> dict:
+    """the `scale_skill` entry of summary.json from nn.ScaleSkill.state(): the levels, the origins, the scored rows, the frames and, per
+    class, the pooled decode"""
+    out = {"levels": int(levels), "origins": [int(c) for c in origins], "rows": [int(row_range[0]), int(row_range[1])],
+           "frames": int(state["frames"])}
+    out.update(dnn.ScaleSkill.decode(state["total"], state["pixels"], state["frames"], levels, row_range[1] - row_range[0], width, origins))
     return out
 
 
@@ -732,7 +781,11 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
-                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0, displacement_window: int = 0):
+                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0, displacement_window: int = 0,
+                 scale_cells=None):
+        # --scale_skill: the rows of nn.ScaleSkill (scale_cells = (O, L + 1)) and the pixel counts beside them
+        self.scale = torch.empty((B, 2, *scale_cells, 3), dtype=torch.int64).pin_memory() if scale_cells else None
+        self.scale_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if scale_cells else None
         # --displacement: the tables of nn.DisplacementSkill (window = 2 R + 1), the pixel counts and the best shifts beside them
         S = displacement_window
         self.displacement = torch.empty((B, 2, S, S + 1), dtype=torch.int64).pin_memory() if S else None
@@ -823,6 +876,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if slot.displacement is not None:
                         extra = dict(extra or {}, displacement=slot.displacement[j].numpy(),
                                      displacement_pixels=slot.displacement_pixels[j].numpy(), displacement_best=slot.displacement_best[j].numpy())
+                    if slot.scale is not None:
+                        extra = dict(extra or {}, scale=slot.scale[j].numpy(), scale_pixels=slot.scale_pixels[j].numpy())
                     if slot.prob_rows is not None:
                         brier = dnn.brier_from_rows(slot.prob_rows[j].numpy(), slot.prob_pixels[j].numpy())
                         extra = dict(extra or {}, brier=np.asarray([np.nan if v is None else v for v in brier], np.float64),
@@ -949,6 +1004,8 @@ def main(pargs) -> dict:
     dist = dnn.DistanceSkill(B, H, W, device=device, **distance_options(pargs)) if getattr(pargs, "distance_skill", False) else None
     # --displacement: likewise
     disp = dnn.DisplacementSkill(B, H, W, device=device, **displacement_options(pargs)) if getattr(pargs, "displacement", False) else None
+    # --scale_skill: likewise
+    scale = dnn.ScaleSkill(B, H, W, device=device, **scale_options(pargs)) if getattr(pargs, "scale_skill", False) else None
     # --prob_skill: behind every batch, the classifier's stored logits against the labels
     prob = None
     if getattr(pargs, "prob_skill", False):
@@ -968,7 +1025,8 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
-                             prob is not None, decide is not None, dist.R + 4 if dist else 0, 2 * disp.R + 1 if disp else 0))
+                             prob is not None, decide is not None, dist.R + 4 if dist else 0, 2 * disp.R + 1 if disp else 0,
+                             (scale.O, scale.L + 1) if scale else None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -1009,6 +1067,10 @@ def main(pargs) -> dict:
                 slot.displacement[:nv].copy_(disp_rows, non_blocking=True)
                 slot.displacement_pixels[:nv].copy_(disp_pixels, non_blocking=True)
                 slot.displacement_best[:nv].copy_(disp_best, non_blocking=True)
+            if scale is not None:
+                scale_rows, scale_pixels = scale(dmask, y, n_valid=nv).frame_rows()
+                slot.scale[:nv].copy_(scale_rows, non_blocking=True)
+                slot.scale_pixels[:nv].copy_(scale_pixels, non_blocking=True)
             if prob is not None:
                 prob_rows, prob_pixels = prob(predictor.logits_buffer, y, n_valid=nv).frame_rows()
                 slot.prob_rows[:nv].copy_(prob_rows, non_blocking=True)
@@ -1063,6 +1125,7 @@ def main(pargs) -> dict:
     fss_state = fss.state() if fss is not None else None
     dist_state = dist.state() if dist is not None else None
     disp_state = disp.state() if disp is not None else None
+    scale_state = scale.state() if scale is not None else None
     prob_state = prob.state() if prob is not None else None
     elapsed = time.perf_counter() - t0
 
@@ -1089,6 +1152,8 @@ def main(pargs) -> dict:
         summary["distance_skill"] = distance_summary(dist.R, dist.wrap, dist.row_range, H, W, dist_state)
     if disp is not None:
         summary["displacement"] = displacement_summary(disp.R, disp.row_range, H, W, disp_state, [r["displacement_best"] for r in records])
+    if scale is not None:
+        summary["scale_skill"] = scale_summary(scale.L, scale.origins, scale.row_range, W, scale_state)
     if prob is not None:
         write_datasets(os.path.join(pargs.output_dir, "prob_skill.h5"), prob_arrays(prob.K, prob_state))
         summary["prob_skill"] = prob_summary(prob.K, prob_state)
