@@ -14,6 +14,7 @@
 //   clim_maps      one thread per (group, pixel, product): an fp64 quotient of the integers, rounded once more to fp32; the thread of a
 //                  pixel's first product also writes the pixel's contour byte.
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -24,12 +25,9 @@ typedef long long cl_ll2 __attribute__((ext_vector_type(2)));
 typedef int cl_i4 __attribute__((ext_vector_type(4)));
 typedef float cl_f4 __attribute__((ext_vector_type(4)));
 
-// classes 1 and 2 of a mask of 1-, 4- or 8-byte integers; every other value is background
+// classes 1 and 2 of a mask element; every other value is background
 __device__ inline int cl_class(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
+  const long long v = mask_value(m, i, bytes);
   return (v == 1 || v == 2) ? (int)v : 0;
 }
 

@@ -21,6 +21,7 @@
 //   disp_total  one thread per cell adds the batch's rows and pixels to the totals, frame by frame; one the frame count.
 // The workspace holds the four bit planes and the row counts.  Four launches per call.
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -29,15 +30,6 @@ static constexpr int DP_SEG = 32;                 // label rows of a workgroup o
 static constexpr int DP_RMAX = 63;                // 2 R + 2 lanes fit two waves; the key holds dy + R and dx + R in 7 bits each
 static constexpr int DP_BMAX = 4095;              // a legal grid.y
 static constexpr int DP_PACK = 256;               // threads of disp_pack: four waves share a row's words
-
-// the class of one mask element: the full-width value 1 or 2, else 0; masks of 1-, 4- or 8-byte integers
-__device__ inline unsigned dp_class(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
-  return v == 1 ? 1u : (v == 2 ? 2u : 0u);
-}
 
 __global__ __launch_bounds__(DP_PACK) void disp_pack_kernel(int H, int W, const void* __restrict__ pred, int pred_bytes,
                                                             const void* __restrict__ truth, int truth_bytes, int R, int row0, int row1,
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(DP_PACK) void disp_pack_kernel(int H, int W, const 
       if (i < W + 2 * R) {
         int x = i - R;                              // in [-R, W + R), where R < W
         x = x < 0 ? x + W : (x >= W ? x - W : x);
-        c = dp_class(pred, row + x, pred_bytes);
+        c = mask_class(pred, row + x, pred_bytes);
       }
       const unsigned long long m1 = __ballot(c == 1u), m2 = __ballot(c == 2u);
       const unsigned long long own = __ballot(i >= R && i < R + W);   // the bits that are the row itself
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(DP_PACK) void disp_pack_kernel(int H, int W, const 
       if (lane == 0) ext[plane * PW + item] = m1, ext[(plane + H) * PW + item] = m2;
     } else {
       const int w = item - PW, j = w * DP_BITS + lane;
-      const unsigned c = j < W ? dp_class(truth, row + j, truth_bytes) : 0u;
+      const unsigned c = j < W ? mask_class(truth, row + j, truth_bytes) : 0u;
       const unsigned long long m1 = __ballot(c == 1u), m2 = __ballot(c == 2u);
       n[2] += (unsigned)__popcll(m1), n[3] += (unsigned)__popcll(m2);
       if (lane == 0) lab[plane * TW + w] = m1, lab[(plane + H) * TW + w] = m2;
@@ -158,18 +150,9 @@ __global__ __launch_bounds__(256) void disp_total_kernel(int n_valid, int R, con
                                                          const long long* __restrict__ pixels, long long* __restrict__ total,
                                                          long long* __restrict__ total_pixels, long long* __restrict__ frames) {
   const int t = blockIdx.x * 256 + threadIdx.x, cells = 2 * (2 * R + 1) * (2 * R + 2);
-  if (t < cells) {
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += rows[(size_t)b * cells + t];
-    total[t] += sum;
-  } else if (t < cells + 4) {
-    const int c = t - cells;
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += pixels[(size_t)b * 4 + c];
-    total_pixels[c] += sum;
-  } else if (t == cells + 4) {
-    frames[0] += n_valid;
-  }
+  if (t < cells) total_add64(total, rows, cells, t, n_valid);
+  else if (t < cells + 4) total_add64(total_pixels, pixels, 4, t - cells, n_valid);
+  else if (t == cells + 4) frames[0] += n_valid;
 }
 
 static bool dp_shape_ok(int B, int H, int W, int R) {
@@ -197,17 +180,10 @@ extern "C" size_t dc_displacement_workspace(int B, int H, int W, int R) {
 extern "C" int dc_displacement_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes,
                                      int R, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* best, int64_t* total,
                                      int64_t* total_pixels, int64_t* frames, void* workspace, void* stream) {
-  DC_REQUIRE(B >= 1 && B <= DP_BMAX && H >= 1 && W >= 1, "dc_displacement_score: B must lie in [1, 4095], H and W must be positive");
-  DC_REQUIRE((long)H * W < 2147483648L, "dc_displacement_score: H * W must be below 2^31");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_displacement_score: n_valid must lie in [0, B]");
-  DC_REQUIRE((pred_bytes == 1 || pred_bytes == 4 || pred_bytes == 8) && (truth_bytes == 1 || truth_bytes == 4 || truth_bytes == 8),
-             "dc_displacement_score: mask_bytes must be 1, 4 or 8 on either side");
+  if (int e = mask_skill_check("dc_displacement_score", B, DP_BMAX, n_valid, H, W, pred, pred_bytes, truth, truth_bytes, row0, row1)) return e;
   DC_REQUIRE(R >= 1 && R <= DP_RMAX, "dc_displacement_score: the radius R must lie in [1, 63]");
   DC_REQUIRE(2 * R + 1 <= W, "dc_displacement_score: the window 2 R + 1 must not be wider than the frame");
-  DC_REQUIRE(row0 >= 0 && row0 < row1 && row1 <= H, "dc_displacement_score: the row range must satisfy 0 <= row0 < row1 <= H");
-  DC_REQUIRE(pred && truth && rows && pixels && best && total && total_pixels && frames && workspace, "dc_displacement_score: null pointer");
-  DC_REQUIRE(((uintptr_t)pred & (pred_bytes - 1)) == 0 && ((uintptr_t)truth & (truth_bytes - 1)) == 0,
-             "dc_displacement_score: a mask is not aligned to its element size");
+  DC_REQUIRE(rows && pixels && best && total && total_pixels && frames && workspace, "dc_displacement_score: null pointer");
   DC_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)pixels & 7) == 0 && ((uintptr_t)best & 7) == 0 &&
                  ((uintptr_t)total & 7) == 0 && ((uintptr_t)total_pixels & 7) == 0 && ((uintptr_t)frames & 7) == 0,
              "dc_displacement_score: workspace, rows, pixels, best or a total not aligned to 8 bytes");

@@ -23,6 +23,7 @@
 //               two-word totals (lo += x, hi += carry), one the frame count.
 // The workspace holds the packed words, B * H * W * 4 bytes.  Three launches per call.
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -32,15 +33,6 @@ static constexpr int DT_HR = 8;                   // rows a workgroup of the hor
 static constexpr int DT_RMAX = 127;               // R + 1 fits a byte, R^2 + 1 sixteen bits
 static constexpr int DT_BMAX = 4095;              // a legal grid.y
 static constexpr int DT_SUMS = 10;                // per workgroup: (sum dq, sum d^2) per class and direction, the Baddeley term per class
-
-// the class bits of one mask element: 1 for the full-width value 1, 2 for 2, else 0; masks of 1-, 4- or 8-byte integers
-__device__ inline unsigned dt_class(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
-  return v == 1 ? 1u : (v == 2 ? 2u : 0u);
-}
 
 // one step of the four running row distances: 0 where the field has a pixel in this row, else one more, saturated at far = R + 1
 __device__ inline void dt_step(unsigned g[4], unsigned bits, unsigned far) {
@@ -65,13 +57,13 @@ __global__ __launch_bounds__(DT_TC) void dist_vert_kernel(int H, int W, const vo
   unsigned g[4] = {far, far, far, far};
   for (int i = i0 - R > 0 ? i0 - R : 0; i < i1; ++i) {           // down: rows since the last pixel at or above
     const size_t px = frame + (size_t)i * W + c;
-    dt_step(g, dt_class(pred, px, pred_bytes) | dt_class(truth, px, truth_bytes) << 2, far);
+    dt_step(g, mask_class(pred, px, pred_bytes) | mask_class(truth, px, truth_bytes) << 2, far);
     if (i >= i0) ws[px] = g[0] | g[1] << 8 | g[2] << 16 | g[3] << 24;
   }
   g[0] = g[1] = g[2] = g[3] = far;
   for (int i = (i1 + R < H ? i1 + R : H) - 1; i >= i0; --i) {    // up: rows to the next pixel at or below; the minimum of both
     const size_t px = frame + (size_t)i * W + c;
-    dt_step(g, dt_class(pred, px, pred_bytes) | dt_class(truth, px, truth_bytes) << 2, far);
+    dt_step(g, mask_class(pred, px, pred_bytes) | mask_class(truth, px, truth_bytes) << 2, far);
     if (i < i1) {
       const uint32_t w = ws[px];
       uint32_t out = 0;
@@ -209,22 +201,9 @@ __global__ __launch_bounds__(256) void dist_total_kernel(int n_valid, int R, con
                                                          const unsigned long long* __restrict__ baddeley, long long* __restrict__ total,
                                                          unsigned long long* __restrict__ total_baddeley, long long* __restrict__ frames) {
   const int t = blockIdx.x * 256 + threadIdx.x, cells = 4 * (R + 4);
-  if (t < cells) {
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += rows[(size_t)b * cells + t];
-    total[t] += sum;
-  } else if (t < cells + 2) {
-    const int k = t - cells;
-    unsigned long long lo = total_baddeley[2 * k], hi = total_baddeley[2 * k + 1];
-    for (int b = 0; b < n_valid; ++b) {
-      const unsigned long long x = baddeley[(size_t)b * 2 + k];
-      lo += x;
-      hi += lo < x;                                 // the carry
-    }
-    total_baddeley[2 * k] = lo, total_baddeley[2 * k + 1] = hi;
-  } else if (t == cells + 2) {
-    frames[0] += n_valid;
-  }
+  if (t < cells) total_add64(total, rows, cells, t, n_valid);
+  else if (t < cells + 2) total_add128(total_baddeley, baddeley, 2, t - cells, n_valid);
+  else if (t == cells + 2) frames[0] += n_valid;
 }
 
 static bool dt_shape_ok(int B, int H, int W, int R) {
@@ -250,19 +229,12 @@ extern "C" size_t dc_distance_workspace(int B, int H, int W, int R) {
 extern "C" int dc_distance_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes,
                                  int R, const int32_t* table, int wrap, int row0, int row1, int64_t* rows, int64_t* baddeley,
                                  int64_t* total, int64_t* total_baddeley, int64_t* frames, uint16_t* maps, void* workspace, void* stream) {
-  DC_REQUIRE(B >= 1 && B <= DT_BMAX && H >= 1 && W >= 1, "dc_distance_score: B must lie in [1, 4095], H and W must be positive");
-  DC_REQUIRE((long)H * W < 2147483648L, "dc_distance_score: H * W must be below 2^31");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_distance_score: n_valid must lie in [0, B]");
-  DC_REQUIRE((pred_bytes == 1 || pred_bytes == 4 || pred_bytes == 8) && (truth_bytes == 1 || truth_bytes == 4 || truth_bytes == 8),
-             "dc_distance_score: mask_bytes must be 1, 4 or 8 on either side");
+  if (int e = mask_skill_check("dc_distance_score", B, DT_BMAX, n_valid, H, W, pred, pred_bytes, truth, truth_bytes, row0, row1)) return e;
   DC_REQUIRE(R >= 1 && R <= DT_RMAX, "dc_distance_score: the radius R must lie in [1, 127]");
   DC_REQUIRE(wrap == 0 || wrap == 1, "dc_distance_score: wrap must be 0 or 1");
   DC_REQUIRE(!wrap || 2 * R + 1 <= W, "dc_distance_score: with wrap the window 2 R + 1 must not be wider than the frame");
-  DC_REQUIRE(row0 >= 0 && row0 < row1 && row1 <= H, "dc_distance_score: the row range must satisfy 0 <= row0 < row1 <= H");
-  DC_REQUIRE(pred && truth && table && rows && baddeley && total && total_baddeley && frames && workspace,
+  DC_REQUIRE(table && rows && baddeley && total && total_baddeley && frames && workspace,
              "dc_distance_score: null pointer");
-  DC_REQUIRE(((uintptr_t)pred & (pred_bytes - 1)) == 0 && ((uintptr_t)truth & (truth_bytes - 1)) == 0,
-             "dc_distance_score: a mask is not aligned to its element size");
   DC_REQUIRE(((uintptr_t)table & 3) == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)maps & 1) == 0 && ((uintptr_t)rows & 7) == 0 &&
                  ((uintptr_t)baddeley & 7) == 0 && ((uintptr_t)total & 7) == 0 && ((uintptr_t)total_baddeley & 7) == 0 &&
                  ((uintptr_t)frames & 7) == 0,

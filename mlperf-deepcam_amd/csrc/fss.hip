@@ -23,6 +23,7 @@
 // reused slab (15 launches at 7 windows, each of them too small a grid to fill the chip): 0.23 ms against 0.64 ms per batch of 8 at
 // 768 x 1152 (profiles/fss.txt).
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -33,15 +34,6 @@ static constexpr int FS_RMAX = 127;               // n = 2 r + 1 <= 255: a row's
 static constexpr int FS_SMAX = 16;
 static constexpr int FS_BMAX = 4095;              // B * S stays a legal grid.y
 static constexpr unsigned FS_LANES = 0x00FF00FFu;
-
-// the two indicator bits of one mask element in 16-bit lanes: (value == 1) | (value == 2) << 16; masks of 1-, 4- or 8-byte integers
-__device__ inline unsigned fs_bits(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
-  return v == 1 ? 1u : (v == 2 ? 0x10000u : 0u);
-}
 
 // the radius of window s, or -1 where the table (device memory: the host never saw it) holds one the call cannot serve
 __device__ inline int fs_radius(const int32_t* __restrict__ radius, int s, int W, int wrap) {
@@ -81,8 +73,8 @@ __global__ __launch_bounds__(FS_TC) void fss_rows_kernel(int B, int H, int W, co
         if (wrap) c = c < 0 ? c + W : (c >= W ? c - W : c);
         if (c >= 0 && c < W) {
           const size_t px = frame + (size_t)i * W + c;
-          vp[j] = fs_bits(pred, px, pred_bytes);
-          vq[j] = fs_bits(truth, px, truth_bytes);
+          vp[j] = mask_bits(pred, px, pred_bytes);
+          vq[j] = mask_bits(truth, px, truth_bytes);
         }
         if (i >= row0 && i < row1 && e >= R && e < R + tcw) cp += vp[j], cq += vq[j];
       }
@@ -181,21 +173,9 @@ __global__ __launch_bounds__(128) void fss_total_kernel(int n_valid, int S, cons
                                                         const long long* __restrict__ pixels, unsigned long long* __restrict__ total,
                                                         long long* __restrict__ total_pixels, long long* __restrict__ frames) {
   const int t = threadIdx.x, words = 2 * S * 3;     // <= 96
-  if (t < words) {
-    unsigned long long lo = total[2 * t], hi = total[2 * t + 1];
-    for (int b = 0; b < n_valid; ++b) {
-      const unsigned long long x = rows[(size_t)b * words + t];
-      lo += x;
-      hi += lo < x;                                 // the carry
-    }
-    total[2 * t] = lo, total[2 * t + 1] = hi;
-  } else if (t < words + 4) {
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += pixels[(size_t)b * 4 + (t - words)];
-    total_pixels[t - words] += sum;
-  } else if (t == words + 4) {
-    frames[0] += n_valid;
-  }
+  if (t < words) total_add128(total, rows, words, t, n_valid);
+  else if (t < words + 4) total_add64(total_pixels, pixels, 4, t - words, n_valid);
+  else if (t == words + 4) frames[0] += n_valid;
 }
 
 }  // namespace dc
@@ -217,17 +197,10 @@ extern "C" size_t dc_fss_workspace(int B, int H, int W, int S) {
 extern "C" int dc_fss_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int S,
                             const int32_t* radius, int wrap, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
                             int64_t* total_pixels, int64_t* frames, void* workspace, void* stream) {
-  DC_REQUIRE(B >= 1 && B <= FS_BMAX && H >= 1 && W >= 1, "dc_fss_score: B must lie in [1, 4095], H and W must be positive");
-  DC_REQUIRE((long)H * W < 2147483648L, "dc_fss_score: H * W must be below 2^31");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_fss_score: n_valid must lie in [0, B]");
-  DC_REQUIRE((pred_bytes == 1 || pred_bytes == 4 || pred_bytes == 8) && (truth_bytes == 1 || truth_bytes == 4 || truth_bytes == 8),
-             "dc_fss_score: mask_bytes must be 1, 4 or 8 on either side");
+  if (int e = mask_skill_check("dc_fss_score", B, FS_BMAX, n_valid, H, W, pred, pred_bytes, truth, truth_bytes, row0, row1)) return e;
   DC_REQUIRE(S >= 1 && S <= FS_SMAX, "dc_fss_score: S must lie in [1, 16]");
   DC_REQUIRE(wrap == 0 || wrap == 1, "dc_fss_score: wrap must be 0 or 1");
-  DC_REQUIRE(row0 >= 0 && row0 < row1 && row1 <= H, "dc_fss_score: the row range must satisfy 0 <= row0 < row1 <= H");
-  DC_REQUIRE(pred && truth && radius && rows && pixels && total && total_pixels && frames && workspace, "dc_fss_score: null pointer");
-  DC_REQUIRE(((uintptr_t)pred & (pred_bytes - 1)) == 0 && ((uintptr_t)truth & (truth_bytes - 1)) == 0,
-             "dc_fss_score: a mask is not aligned to its element size");
+  DC_REQUIRE(radius && rows && pixels && total && total_pixels && frames && workspace, "dc_fss_score: null pointer");
   DC_REQUIRE(((uintptr_t)radius & 3) == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)pixels & 7) == 0 &&
                  ((uintptr_t)total & 7) == 0 && ((uintptr_t)total_pixels & 7) == 0 && ((uintptr_t)frames & 7) == 0,
              "dc_fss_score: radius, workspace, rows, pixels or a total not aligned to its element size");

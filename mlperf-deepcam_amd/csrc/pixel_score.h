@@ -7,6 +7,7 @@
 //              torch.max(outputs,1)[1] (train_hdf5_ddp.py:406,458), utils/utils.py:32-60.
 #pragma once
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -14,10 +15,7 @@ constexpr int NC = 3;   // classes
 
 // labels outside [0, NC) come back as -1 (the full 64-bit value is compared, not its low half)
 __device__ inline int load_label(const void* labels, int bytes, size_t i) {
-  long long v;
-  if (bytes == 8) v = reinterpret_cast<const int64_t*>(labels)[i];
-  else if (bytes == 4) v = reinterpret_cast<const int32_t*>(labels)[i];
-  else v = reinterpret_cast<const uint8_t*>(labels)[i];
+  const long long v = mask_value(labels, i, bytes);
   return (v >= 0 && v < NC) ? (int)v : -1;
 }
 

@@ -181,19 +181,9 @@ __global__ __launch_bounds__(256) void prob_total_kernel(int n_valid, int ncell2
     const long long v = hist[i];
     if (v) total_hist[i] += v;
   } else if (i < ncell2 + NC) {
-    const int c = i - ncell2;
-    unsigned long long lo = total_sq[2 * c], hi = total_sq[2 * c + 1];
-    for (int b = 0; b < n_valid; ++b) {
-      const unsigned long long x = rows[(size_t)b * NC + c];
-      lo += x;
-      hi += lo < x;                                 // the carry
-    }
-    total_sq[2 * c] = lo, total_sq[2 * c + 1] = hi;
+    total_add128(total_sq, rows, NC, i - ncell2, n_valid);
   } else if (i < ncell2 + 2 * NC) {
-    const int k = i - ncell2 - NC;
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += pixels[(size_t)b * NC + k];
-    total_pixels[k] += sum;
+    total_add64(total_pixels, pixels, NC, i - ncell2 - NC, n_valid);
   } else if (i == ncell2 + 2 * NC) {
     frames[0] += n_valid;
   }

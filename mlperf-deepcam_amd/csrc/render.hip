@@ -14,6 +14,7 @@
 //                  contiguous run of 768 bytes; where W % 4 != 0 or `out` is not 4-byte aligned the same code stores single bytes.
 // The field load is strided by ldc floats: with ldc = 16 one dword of every 64-byte segment is used.
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -23,12 +24,9 @@ static constexpr int RP_CW = RP_TW + 2 * (RP_RMAX + 1), RP_CH = RP_TH + 2 * (RP_
 static constexpr int RP_EW = RP_TW + 2 * RP_RMAX, RP_EH = RP_TH + 2 * RP_RMAX;               // edges: 70 x 38
 static constexpr uint8_t RP_ABSENT = 0xff;        // a row outside the image: neither a class nor a neighbour that counts
 
-// classes 1 and 2 of a mask of 1-, 4- or 8-byte integers; every other value is background
+// classes 1 and 2 of a mask element; every other value is background
 __device__ inline uint8_t rp_class(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
+  const long long v = mask_value(m, i, bytes);
   return (v == 1 || v == 2) ? (uint8_t)v : (uint8_t)0;
 }
 

@@ -23,6 +23,7 @@
 // The origins live in device memory, so a table entry outside [0, T) is found here, not on the host: that origin's workgroups leave, its
 // rows stay zero (origin 0's still count the pixels, on the grid of column 0).
 #include "common.h"
+#include "mask_skill.h"
 
 namespace dc {
 
@@ -33,15 +34,6 @@ static constexpr int SC_OMAX = 8;
 static constexpr int SC_BMAX = 4095;              // B * O stays a legal grid.y
 static constexpr int SC_TLEVELS = 7;              // levels 0 .. 6 are formed inside a tile
 static constexpr int SC_TOTAL_THREADS = 512;      // >= 2 * SC_OMAX * (SC_LMAX + 1) * 3 + 5
-
-// the two indicator bits of one mask element: (value == 1) | (value == 2) << 16; masks of 1-, 4- or 8-byte integers (dc_fss_score's rule)
-__device__ inline unsigned sc_bits(const void* m, size_t i, int bytes) {
-  long long v;
-  if (bytes == 1) v = ((const uint8_t*)m)[i];
-  else if (bytes == 4) v = ((const int32_t*)m)[i];
-  else v = ((const long long*)m)[i];
-  return v == 1 ? 1u : (v == 2 ? 0x10000u : 0u);
-}
 
 // bits 0, 2, 4, 6 of t as a 4-bit number: one coordinate of the Morton order
 __device__ inline int sc_even_bits(unsigned t) {
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(SC_THREADS) void scale_sums_kernel(int H, int W, co
       if (r < row1 && u < W) {                      // c < T <= W and u < W: one subtraction wraps the column
         const int col = c + u >= W ? c + u - W : c + u;
         const size_t px = frame + (size_t)r * W + col;
-        const unsigned p = sc_bits(pred, px, pred_bytes), y = sc_bits(truth, px, truth_bytes);
+        const unsigned p = mask_bits(pred, px, pred_bytes), y = mask_bits(truth, px, truth_bytes);
         const unsigned f1 = p & 1u, f2 = p >> 16, o1 = y & 1u, o2 = y >> 16;
         acc[0][0] += f1 ^ o1, acc[0][1] += f1, acc[0][2] += o1;
         acc[0][3] += f2 ^ o2, acc[0][4] += f2, acc[0][5] += o2;
@@ -218,21 +210,9 @@ __global__ __launch_bounds__(SC_TOTAL_THREADS) void scale_total_kernel(int n_val
                                                                        unsigned long long* __restrict__ total,
                                                                        long long* __restrict__ total_pixels, long long* __restrict__ frames) {
   const int t = threadIdx.x;                        // cells = 2 * O * (L + 1) * 3 <= 432
-  if (t < cells) {
-    unsigned long long lo = total[2 * t], hi = total[2 * t + 1];
-    for (int b = 0; b < n_valid; ++b) {
-      const unsigned long long x = rows[(size_t)b * cells + t];
-      lo += x;
-      hi += lo < x;                                 // the carry
-    }
-    total[2 * t] = lo, total[2 * t + 1] = hi;
-  } else if (t < cells + 4) {
-    long long sum = 0;
-    for (int b = 0; b < n_valid; ++b) sum += pixels[(size_t)b * 4 + (t - cells)];
-    total_pixels[t - cells] += sum;
-  } else if (t == cells + 4) {
-    frames[0] += n_valid;
-  }
+  if (t < cells) total_add128(total, rows, cells, t, n_valid);
+  else if (t < cells + 4) total_add64(total_pixels, pixels, 4, t - cells, n_valid);
+  else if (t == cells + 4) frames[0] += n_valid;
 }
 
 }  // namespace dc
@@ -255,19 +235,12 @@ extern "C" size_t dc_scale_workspace(int B, int H, int W, int L, int O) {
 extern "C" int dc_scale_score(int B, int n_valid, int H, int W, const void* pred, int pred_bytes, const void* truth, int truth_bytes, int L,
                               int O, const int32_t* origins, int row0, int row1, int64_t* rows, int64_t* pixels, int64_t* total,
                               int64_t* total_pixels, int64_t* frames, void* workspace, void* stream) {
-  DC_REQUIRE(B >= 1 && B <= SC_BMAX && H >= 1 && W >= 1, "dc_scale_score: B must lie in [1, 4095], H and W must be positive");
-  DC_REQUIRE((long)H * W < 2147483648L, "dc_scale_score: H * W must be below 2^31");
-  DC_REQUIRE(n_valid >= 0 && n_valid <= B, "dc_scale_score: n_valid must lie in [0, B]");
-  DC_REQUIRE((pred_bytes == 1 || pred_bytes == 4 || pred_bytes == 8) && (truth_bytes == 1 || truth_bytes == 4 || truth_bytes == 8),
-             "dc_scale_score: mask_bytes must be 1, 4 or 8 on either side");
+  if (int e = mask_skill_check("dc_scale_score", B, SC_BMAX, n_valid, H, W, pred, pred_bytes, truth, truth_bytes, row0, row1)) return e;
   DC_REQUIRE(L >= 1 && L <= SC_LMAX, "dc_scale_score: the levels L must lie in [1, 8]");
   DC_REQUIRE(O >= 1 && O <= SC_OMAX, "dc_scale_score: the number of origins O must lie in [1, 8]");
-  DC_REQUIRE(row0 >= 0 && row0 < row1 && row1 <= H, "dc_scale_score: the row range must satisfy 0 <= row0 < row1 <= H");
   DC_REQUIRE(((row1 - row0) & ((1 << L) - 1)) == 0 && (W & ((1 << L) - 1)) == 0,
              "dc_scale_score: the tile T = 2^L must divide the rows of the band and W");
-  DC_REQUIRE(pred && truth && origins && rows && pixels && total && total_pixels && frames && workspace, "dc_scale_score: null pointer");
-  DC_REQUIRE(((uintptr_t)pred & (pred_bytes - 1)) == 0 && ((uintptr_t)truth & (truth_bytes - 1)) == 0,
-             "dc_scale_score: a mask is not aligned to its element size");
+  DC_REQUIRE(origins && rows && pixels && total && total_pixels && frames && workspace, "dc_scale_score: null pointer");
   DC_REQUIRE(((uintptr_t)origins & 3) == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)pixels & 7) == 0 &&
                  ((uintptr_t)total & 7) == 0 && ((uintptr_t)total_pixels & 7) == 0 && ((uintptr_t)frames & 7) == 0,
              "dc_scale_score: origins, workspace, rows, pixels or a total not aligned to its element size");

@@ -1970,6 +1970,9 @@ def _c_int(v: int) -> int:
     return v - (1 << 32) if v >= 1 << 31 else v
 
 
+_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}    # the element sizes of a class mask
+
+
 class FrameRenderer:
     """The visualiser's picture on the device (dc_render_frames, csrc/render.hip): per sample `panels` panels stacked, the first with
     mask_a's classes outlined (the prediction), the second with mask_b's (the labels), over channel `channel` of the raw fields drawn
@@ -2020,14 +2023,12 @@ class FrameRenderer:
         self._ws = torch.empty(max(L.load().dc_render_workspace(batch, panels, height, width), 256), dtype=torch.uint8, device=dev)
         self._out = torch.zeros((batch, panels, self.Ho, width, 3), dtype=torch.uint8, device=dev)
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-
     def _mask(self, m: torch.Tensor, name: str) -> int:
-        if m.dtype not in self._BYTES or tuple(m.shape) != (self.B, self.H, self.W) or not m.is_cuda or m.device != self.device \
+        if m.dtype not in _BYTES or tuple(m.shape) != (self.B, self.H, self.W) or not m.is_cuda or m.device != self.device \
                 or not m.is_contiguous():
             raise L.DeepcamHipError(f"FrameRenderer: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
                                     f"on {self.device}, got {m.dtype} {tuple(m.shape)} on {m.device}")
-        return self._BYTES[m.dtype]
+        return _BYTES[m.dtype]
 
     def __call__(self, fields: torch.Tensor, mask_a: torch.Tensor, mask_b: Optional[torch.Tensor] = None,
                  n_valid: Optional[int] = None) -> torch.Tensor:
@@ -2089,8 +2090,6 @@ class Climatology:
     one group: 884736 * 584 = 516.7 MB (12 months: 6.2 GB; without channels 7.1 MB per group).
     A call launches on the current stream and does not synchronise; state() and maps() read back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-
     def __init__(self, batch: int, height: int, width: int, channels: Sequence[int] = (), bits=None, ldc: Optional[int] = None,
                  groups: int = 1, device=None):
         channels = [int(c) for c in channels]
@@ -2141,7 +2140,7 @@ class Climatology:
         """mask: contiguous device uint8, int32 or int64 [B, H, W]; fields: contiguous device fp32 [B, H, W, ldc] in physical units
         (InputPipeline.raw), given exactly when channels were selected; groups: None (every frame to group 0), an int, or B ints, a
         negative one skipping its frame; frames from n_valid on are skipped."""
-        if mask.dtype not in self._BYTES or tuple(mask.shape) != (self.B, self.H, self.W) or not mask.is_cuda or mask.device != self.device \
+        if mask.dtype not in _BYTES or tuple(mask.shape) != (self.B, self.H, self.W) or not mask.is_cuda or mask.device != self.device \
                 or not mask.is_contiguous():
             raise L.DeepcamHipError(f"Climatology: mask must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] on "
                                     f"{self.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
@@ -2165,7 +2164,7 @@ class Climatology:
         dev_table = self._tables.get(table)
         if dev_table is None:
             dev_table = self._tables[table] = torch.tensor(table, dtype=torch.int32, device=self.device)
-        L.call("dc_climatology_accumulate", self.B, self.H, self.W, self.G, L.dptr(mask), self._BYTES[mask.dtype], L.dptr(fields), self.C,
+        L.call("dc_climatology_accumulate", self.B, self.H, self.W, self.G, L.dptr(mask), _BYTES[mask.dtype], L.dptr(fields), self.C,
                max(self.ldc, 1), L.dptr(self._chan), L.dptr(self._bits), L.dptr(dev_table), L.dptr(self._frames), L.dptr(self._count),
                L.dptr(self._sum), L.dptr(self._n), L.stream_ptr())
         self.host_frames = [h + a for h, a in zip(self.host_frames, added)]
@@ -2471,6 +2470,79 @@ class StormComposite:
                 "radial_mean": radial, "radius_km": radius, "radius_of_max_km": rmax}
 
 
+# ---------------------------------------------------------------------------------------------- verification skills: what they share
+def _ratio(a, b):
+    """a / b as a Python float, None where b == 0"""
+    return None if b == 0 else a / b
+
+
+def _two_words(words):
+    """Python ints, nested as the leading axes, from int64 words [..., 2] = (lo, hi): (hi << 64) | lo with lo taken as unsigned"""
+    words = np.asarray(words, np.int64)
+    out = np.empty(words.size // 2, dtype=object)
+    out[:] = [(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in words.reshape(-1, 2).tolist()]
+    return out.reshape(words.shape[:-1]).tolist()
+
+
+def _n_valid(who: str, n_valid: Optional[int], batch: int) -> int:
+    nv = batch if n_valid is None else int(n_valid)
+    if not 0 <= nv <= batch:
+        raise L.DeepcamHipError(f"{who}: n_valid must lie in [0, {batch}], got {n_valid}")
+    return nv
+
+
+class _MaskSkill:
+    """What the skills that score a predicted class mask against a labelled one share (FractionsSkill, DistanceSkill, DisplacementSkill,
+    ScaleSkill): a batch of [B, H, W] frames with fewer than 2^31 pixels each, a band of rows row_range = (row0, row1), the check of
+    the two masks (contiguous device uint8, int32 or int64, each side with its own element size), per-frame buffers of the last call
+    and running totals since reset().  A subclass names the attributes of its per-frame buffers in `_frame` (the order of FRAME_KEYS, the
+    datasets they are stored under) and of its totals in `_totals`, and makes the call in _score()."""
+
+    FRAME_KEYS: tuple = ()
+    _frame: tuple = ()
+    _totals: tuple = ()
+
+    def _geometry(self, batch: int, height: int, width: int, max_batch: int) -> None:
+        if batch < 1 or batch > max_batch or height < 1 or width < 1 or height * width >= 1 << 31:
+            raise L.DeepcamHipError(f"{type(self).__name__}: batch must lie in [1, {max_batch}], height and width be positive and "
+                                    "height * width below 2^31")
+        self.B, self.H, self.W, self._nv = batch, height, width, 0
+
+    def _band(self, row_range) -> tuple:
+        row0, row1 = (0, self.H) if row_range is None else (int(row_range[0]), int(row_range[1]))
+        if not 0 <= row0 < row1 <= self.H:
+            raise L.DeepcamHipError(f"{type(self).__name__}: row_range must satisfy 0 <= row0 < row1 <= {self.H}, got {row_range}")
+        self.row_range = (row0, row1)
+        return row0, row1
+
+    def _check(self, t, name: str) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype not in _BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
+                or t.device != self.device or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise L.DeepcamHipError(f"{type(self).__name__}: {name} must be a contiguous uint8, int32 or int64 tensor "
+                                    f"[{self.B}, {self.H}, {self.W}] on {self.device}, got {got}")
+
+    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None):
+        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
+        are neither read nor written (FractionsSkill: not read, and their rows are zero).  Returns the object."""
+        self._check(pred, "pred")
+        self._check(truth, "truth")
+        nv = _n_valid(type(self).__name__, n_valid, self.B)
+        self._score(nv, L.dptr(pred), _BYTES[pred.dtype], L.dptr(truth), _BYTES[truth.dtype])
+        self._nv = nv
+        return self
+
+    def frame_rows(self) -> tuple:
+        """the per-frame buffers of the last call, in the order of FRAME_KEYS, each cut to [n_valid, ...]: views of the object's device
+        buffers, not synchronised"""
+        return tuple(getattr(self, name)[:self._nv] for name in self._frame)
+
+    def reset(self) -> None:
+        """zeroes the running totals (in stream order)"""
+        for name in self._totals:
+            getattr(self, name).zero_()
+
+
 # ---------------------------------------------------------------------------------------------- neighbourhood verification
 FSS_WINDOWS = (1, 3, 9, 17, 33, 65, 129)
 FSS_MAX_WINDOW = 255
@@ -2495,7 +2567,7 @@ def fss_from_rows(rows):
     return out.reshape(rows.shape[:-1]).tolist()
 
 
-class FractionsSkill:
+class FractionsSkill(_MaskSkill):
     """Neighbourhood verification on the device (dc_fss_score, csrc/fss.hip): per frame, class (1, 2) and window of n x n GRID PIXELS the
     integers (A, B, C) = (sum (F - O)^2, sum F^2, sum O^2), F and O the predicted and labelled pixel counts of the class inside the window
     around every pixel of the rows row_range = (row0, row1) -- columns periodic with wrap, rows beyond the poles empty -- and their running
@@ -2506,12 +2578,12 @@ class FractionsSkill:
     at the 7 default windows: 198.2 MB --, beside batch * (2 * S * 3 + 4) * 8 bytes of rows and a few hundred bytes of totals.
     A call launches on the current stream and does not synchronise; state() and result() read back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+    FRAME_KEYS = ("fss", "fss_pixels")                # frame_rows(): int64 [n_valid, 2, S, 3], int64 [n_valid, 2, 2]
+    _frame, _totals = ("_rows", "_pixels"), ("_total", "_total_pixels", "_frames")
 
     def __init__(self, batch: int, height: int, width: int, windows: Sequence[int] = FSS_WINDOWS, wrap: bool = True, row_range=None,
                  device=None):
-        if batch < 1 or batch > FSS_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
-            raise L.DeepcamHipError(f"FractionsSkill: batch must lie in [1, {FSS_MAX_BATCH}], height and width be positive and height * width below 2^31")
+        self._geometry(batch, height, width, FSS_MAX_BATCH)
         windows = [int(n) for n in windows]
         if not 1 <= len(windows) <= FSS_MAX_WINDOWS:
             raise L.DeepcamHipError(f"FractionsSkill: between 1 and {FSS_MAX_WINDOWS} windows, got {len(windows)}")
@@ -2522,11 +2594,8 @@ class FractionsSkill:
                 raise L.DeepcamHipError(f"FractionsSkill: a periodic window must not be wider than the frame ({width}), got {n}")
         if len(set(windows)) != len(windows):
             raise L.DeepcamHipError(f"FractionsSkill: the windows must be distinct, got {windows}")
-        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
-        if not 0 <= row0 < row1 <= height:
-            raise L.DeepcamHipError(f"FractionsSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
-        self.B, self.H, self.W, self.S = batch, height, width, len(windows)
-        self.windows, self.wrap, self.row_range = windows, bool(wrap), (row0, row1)
+        self._band(row_range)
+        self.S, self.windows, self.wrap = len(windows), windows, bool(wrap)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._radius = torch.tensor([(n - 1) // 2 for n in windows], dtype=torch.int32, device=dev)
         dev = self.device = self._radius.device
@@ -2539,37 +2608,11 @@ class FractionsSkill:
         if size == 0:
             raise L.DeepcamHipError("FractionsSkill: dc_fss_workspace refused the shape")
         self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
-        self._nv = 0
 
-    def _check(self, t, name: str) -> None:
-        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
-                or t.device != self.device or not t.is_contiguous():
-            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise L.DeepcamHipError(f"FractionsSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
-                                    f"on {self.device}, got {got}")
-
-    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "FractionsSkill":
-        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
-        are not read and their rows are zero."""
-        self._check(pred, "pred")
-        self._check(truth, "truth")
-        nv = self.B if n_valid is None else int(n_valid)
-        if not 0 <= nv <= self.B:
-            raise L.DeepcamHipError(f"FractionsSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
-        L.call("dc_fss_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
-               self.S, L.dptr(self._radius), int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
-               L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
-        self._nv = nv
-        return self
-
-    def frame_rows(self):
-        """(int64 [n_valid, 2, S, 3], int64 [n_valid, 2, 2]) of the last call: views of the object's device buffers, not synchronised"""
-        return self._rows[:self._nv], self._pixels[:self._nv]
-
-    def reset(self) -> None:
-        """zeroes the running totals (in stream order)"""
-        for t in (self._total, self._total_pixels, self._frames):
-            t.zero_()
+    def _score(self, nv: int, pred: int, pred_bytes: int, truth: int, truth_bytes: int) -> None:
+        L.call("dc_fss_score", self.B, nv, self.H, self.W, pred, pred_bytes, truth, truth_bytes, self.S, L.dptr(self._radius),
+               int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels), L.dptr(self._total),
+               L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
 
     @staticmethod
     def combine(total_words) -> list:
@@ -2577,7 +2620,7 @@ class FractionsSkill:
         words = np.asarray(total_words, np.int64)
         if words.ndim != 4 or words.shape[0] != 2 or words.shape[2:] != (3, 2):
             raise L.DeepcamHipError(f"FractionsSkill: the totals are int64 [2, S, 3, 2], got shape {words.shape}")
-        return [[[(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in term] for term in cls] for cls in words.tolist()]
+        return _two_words(words)
 
     def state(self) -> dict:
         """on the host: total [2][S][3] as Python ints, pixels [2][2] ((pred, truth) per class) and frames as ints"""
@@ -2629,11 +2672,7 @@ def distance_table(radius: int) -> np.ndarray:
     return table
 
 
-def _ratio(a, b):
-    return None if b == 0 else a / b
-
-
-class DistanceSkill:
+class DistanceSkill(_MaskSkill):
     """Distance-map verification on the device (dc_distance_score, csrc/distance.hip): per frame, side (prediction, labels) and class (1, 2)
     the map of the squared Euclidean distance, in GRID PIXELS, to the nearest pixel of that side and class -- columns periodic with wrap,
     rows never --, capped: R^2 + 1 ("beyond") where nothing lies within `radius` = R.  From the maps, per class and direction (0 "miss": from
@@ -2647,22 +2686,19 @@ class DistanceSkill:
     batch * 4 * height * width * 2 bytes of uint16 maps (56.6 MB), beside batch * (4 * (R + 4) + 2) * 8 bytes of rows and the totals.
     A call launches on the current stream and does not synchronise; state() and result() read back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+    FRAME_KEYS = ("distance", "distance_baddeley")    # frame_rows(): int64 [n_valid, 2, 2, R + 4], int64 [n_valid, 2]
+    _frame, _totals = ("_rows", "_baddeley"), ("_total", "_total_baddeley", "_frames")
 
     def __init__(self, batch: int, height: int, width: int, radius: int = DISTANCE_RADIUS, wrap: bool = True, row_range=None,
                  keep_maps: bool = False, device=None):
-        if batch < 1 or batch > DISTANCE_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
-            raise L.DeepcamHipError(f"DistanceSkill: batch must lie in [1, {DISTANCE_MAX_BATCH}], height and width be positive and height * width below 2^31")
+        self._geometry(batch, height, width, DISTANCE_MAX_BATCH)
         R = int(radius)
         if not 1 <= R <= DISTANCE_MAX_RADIUS:
             raise L.DeepcamHipError(f"DistanceSkill: the radius must lie in [1, {DISTANCE_MAX_RADIUS}], got {radius}")
         if wrap and 2 * R + 1 > width:
             raise L.DeepcamHipError(f"DistanceSkill: a periodic window of 2 * {R} + 1 columns must not be wider than the frame ({width})")
-        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
-        if not 0 <= row0 < row1 <= height:
-            raise L.DeepcamHipError(f"DistanceSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
-        self.B, self.H, self.W, self.R = batch, height, width, R
-        self.wrap, self.row_range, self.keep_maps = bool(wrap), (row0, row1), bool(keep_maps)
+        self._band(row_range)
+        self.R, self.wrap, self.keep_maps = R, bool(wrap), bool(keep_maps)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._table = torch.from_numpy(distance_table(R)).to(dev)
         dev = self.device = self._table.device
@@ -2676,33 +2712,12 @@ class DistanceSkill:
         if size == 0:
             raise L.DeepcamHipError("DistanceSkill: dc_distance_workspace refused the shape")
         self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
-        self._nv = 0
 
-    def _check(self, t, name: str) -> None:
-        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
-                or t.device != self.device or not t.is_contiguous():
-            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise L.DeepcamHipError(f"DistanceSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
-                                    f"on {self.device}, got {got}")
-
-    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "DistanceSkill":
-        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
-        are neither read nor written."""
-        self._check(pred, "pred")
-        self._check(truth, "truth")
-        nv = self.B if n_valid is None else int(n_valid)
-        if not 0 <= nv <= self.B:
-            raise L.DeepcamHipError(f"DistanceSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
-        L.call("dc_distance_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
-               self.R, L.dptr(self._table), int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._baddeley),
-               L.dptr(self._total), L.dptr(self._total_baddeley), L.dptr(self._frames), L.dptr(self._maps) if self._maps is not None else None,
+    def _score(self, nv: int, pred: int, pred_bytes: int, truth: int, truth_bytes: int) -> None:
+        L.call("dc_distance_score", self.B, nv, self.H, self.W, pred, pred_bytes, truth, truth_bytes, self.R, L.dptr(self._table),
+               int(self.wrap), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._baddeley), L.dptr(self._total),
+               L.dptr(self._total_baddeley), L.dptr(self._frames), L.dptr(self._maps) if self._maps is not None else None,
                L.dptr(self._ws), L.stream_ptr())
-        self._nv = nv
-        return self
-
-    def frame_rows(self):
-        """(int64 [n_valid, 2, 2, R + 4], int64 [n_valid, 2]) of the last call: views of the object's device buffers, not synchronised"""
-        return self._rows[:self._nv], self._baddeley[:self._nv]
 
     def maps(self) -> torch.Tensor:
         """uint16 [n_valid, 2 sides, 2 classes, H, W] of the last call (keep_maps): a view of the object's device buffer, not synchronised"""
@@ -2710,16 +2725,10 @@ class DistanceSkill:
             raise L.DeepcamHipError("DistanceSkill: maps() needs keep_maps=True")
         return self._maps[:self._nv]
 
-    def reset(self) -> None:
-        """zeroes the running totals (in stream order)"""
-        for t in (self._total, self._total_baddeley, self._frames):
-            t.zero_()
-
     def state(self) -> dict:
         """on the host, as Python ints: total [2][2][R + 4], baddeley [2] (the two words combined) and frames"""
-        words = self._total_baddeley.cpu().tolist()
         return {"total": [[[int(v) for v in d] for d in cls] for cls in self._total.cpu().tolist()],
-                "baddeley": [(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in words], "frames": int(self._frames.cpu()[0])}
+                "baddeley": _two_words(self._total_baddeley.cpu().numpy()), "frames": int(self._frames.cpu()[0])}
 
     def result(self) -> dict:
         """decode() of the object's state"""
@@ -2787,7 +2796,7 @@ def displacement_best(table, radius: int):
     return -dy, -dx, hits, int(table[R - dy][2 * R + 1])
 
 
-class DisplacementSkill:
+class DisplacementSkill(_MaskSkill):
     """Displacement verification on the device (dc_displacement_score, csrc/displacement.hip): per frame and class (1, 2) the overlap of the
     labelled mask with the predicted mask moved by every (dy, dx), |dy|, |dx| <= radius -- columns periodic, always; rows never: pixels
     moved over a pole are lost --, the predicted pixels each dy keeps inside the band, and the best shift, the one with the most hits: the
@@ -2798,21 +2807,19 @@ class DisplacementSkill:
     Memory: a workspace of bit planes (dc_displacement_workspace; 3.8 MB at 8 x 768 x 1152, R = 16) beside batch * 2 * (2 R + 1) * (2 R + 2)
     * 8 bytes of rows and the totals.  A call launches on the current stream and does not synchronise; state() and result() read back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+    # frame_rows(): rows int64 [n_valid, 2, 2 R + 1, 2 R + 2], pixels int64 [n_valid, 2, 2], best int64 [n_valid, 2, 4]
+    FRAME_KEYS = ("displacement", "displacement_pixels", "displacement_best")
+    _frame, _totals = ("_rows", "_pixels", "_best"), ("_total", "_total_pixels", "_frames")
 
     def __init__(self, batch: int, height: int, width: int, radius: int = DISPLACEMENT_RADIUS, row_range=None, device=None):
-        if batch < 1 or batch > DISPLACEMENT_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
-            raise L.DeepcamHipError(f"DisplacementSkill: batch must lie in [1, {DISPLACEMENT_MAX_BATCH}], height and width be positive and "
-                                    "height * width below 2^31")
+        self._geometry(batch, height, width, DISPLACEMENT_MAX_BATCH)
         R = int(radius)
         if not 1 <= R <= DISPLACEMENT_MAX_RADIUS:
             raise L.DeepcamHipError(f"DisplacementSkill: the radius must lie in [1, {DISPLACEMENT_MAX_RADIUS}], got {radius}")
         if 2 * R + 1 > width:
             raise L.DeepcamHipError(f"DisplacementSkill: the window of 2 * {R} + 1 columns must not be wider than the frame ({width})")
-        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
-        if not 0 <= row0 < row1 <= height:
-            raise L.DeepcamHipError(f"DisplacementSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
-        self.B, self.H, self.W, self.R, self.row_range = batch, height, width, R, (row0, row1)
+        self._band(row_range)
+        self.R = R
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         S = 2 * R + 1
         self._rows = torch.zeros((batch, 2, S, S + 1), dtype=torch.int64, device=dev)
@@ -2826,38 +2833,11 @@ class DisplacementSkill:
         if size == 0:
             raise L.DeepcamHipError("DisplacementSkill: dc_displacement_workspace refused the shape")
         self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
-        self._nv = 0
 
-    def _check(self, t, name: str) -> None:
-        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
-                or t.device != self.device or not t.is_contiguous():
-            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise L.DeepcamHipError(f"DisplacementSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
-                                    f"on {self.device}, got {got}")
-
-    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "DisplacementSkill":
-        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
-        are neither read nor written."""
-        self._check(pred, "pred")
-        self._check(truth, "truth")
-        nv = self.B if n_valid is None else int(n_valid)
-        if not 0 <= nv <= self.B:
-            raise L.DeepcamHipError(f"DisplacementSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
-        L.call("dc_displacement_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth),
-               self._BYTES[truth.dtype], self.R, self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
-               L.dptr(self._best), L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
-        self._nv = nv
-        return self
-
-    def frame_rows(self):
-        """(rows int64 [n_valid, 2, 2 R + 1, 2 R + 2], pixels int64 [n_valid, 2, 2], best int64 [n_valid, 2, 4]) of the last call: views of
-        the object's device buffers, not synchronised"""
-        return self._rows[:self._nv], self._pixels[:self._nv], self._best[:self._nv]
-
-    def reset(self) -> None:
-        """zeroes the running totals (in stream order)"""
-        for t in (self._total, self._total_pixels, self._frames):
-            t.zero_()
+    def _score(self, nv: int, pred: int, pred_bytes: int, truth: int, truth_bytes: int) -> None:
+        L.call("dc_displacement_score", self.B, nv, self.H, self.W, pred, pred_bytes, truth, truth_bytes, self.R, self.row_range[0],
+               self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels), L.dptr(self._best), L.dptr(self._total),
+               L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
 
     def state(self) -> dict:
         """on the host, as Python ints: total [2][2 R + 1][2 R + 2], pixels [2][2] and frames"""
@@ -2956,7 +2936,7 @@ def _float(v):
     return None if v is None else float(v)
 
 
-class ScaleSkill:
+class ScaleSkill(_MaskSkill):
     """Scale-separation verification on the device (dc_scale_score, csrc/scale.hip): the integers behind the intensity-scale skill score
     (Casati, Ross & Stephenson 2004; energies: Casati 2010).  Per frame, class (1, 2), column origin and level j = 0 .. levels the sums
     (A, B, C) = (sum (S_F - S_O)^2, sum S_F^2, sum S_O^2) over the disjoint blocks of side 2^j GRID PIXELS that tile the rows row_range
@@ -2970,16 +2950,13 @@ class ScaleSkill:
     (dc_scale_workspace); no per-pixel buffer.  A call launches on the current stream and does not synchronise; state() and result() read
     back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+    FRAME_KEYS = ("scale", "scale_pixels")            # frame_rows(): int64 [n_valid, 2, O, levels + 1, 3], int64 [n_valid, 2, 2]
+    _frame, _totals = ("_rows", "_pixels"), ("_total", "_total_pixels", "_frames")
 
     def __init__(self, batch: int, height: int, width: int, levels: Optional[int] = None, origins: Sequence[int] = (0,), row_range=None,
                  device=None):
-        if batch < 1 or batch > SCALE_MAX_BATCH or height < 1 or width < 1 or height * width >= 1 << 31:
-            raise L.DeepcamHipError(f"ScaleSkill: batch must lie in [1, {SCALE_MAX_BATCH}], height and width be positive and height * width "
-                                    "below 2^31")
-        row0, row1 = (0, height) if row_range is None else (int(row_range[0]), int(row_range[1]))
-        if not 0 <= row0 < row1 <= height:
-            raise L.DeepcamHipError(f"ScaleSkill: row_range must satisfy 0 <= row0 < row1 <= {height}, got {row_range}")
+        self._geometry(batch, height, width, SCALE_MAX_BATCH)
+        row0, row1 = self._band(row_range)
         lv = scale_levels(row1 - row0, width) if levels is None else int(levels)
         if levels is None and lv < 1:
             raise L.DeepcamHipError(f"ScaleSkill: levels=None needs an even number of rows in the band and an even width, got {row1 - row0} "
@@ -2999,8 +2976,7 @@ class ScaleSkill:
         for c in origins:
             if not 0 <= c < T:
                 raise L.DeepcamHipError(f"ScaleSkill: an origin is a column offset in [0, {T}), got {c}")
-        self.B, self.H, self.W, self.L, self.O = batch, height, width, lv, len(origins)
-        self.origins, self.row_range = origins, (row0, row1)
+        self.L, self.O, self.origins = lv, len(origins), origins
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._origins = torch.tensor(origins, dtype=torch.int32, device=dev)
         dev = self.device = self._origins.device
@@ -3013,38 +2989,11 @@ class ScaleSkill:
         if size == 0:
             raise L.DeepcamHipError("ScaleSkill: dc_scale_workspace refused the shape")
         self._ws = torch.empty(size // 4, dtype=torch.int32, device=dev)
-        self._nv = 0
 
-    def _check(self, t, name: str) -> None:
-        if not isinstance(t, torch.Tensor) or t.dtype not in self._BYTES or tuple(t.shape) != (self.B, self.H, self.W) or not t.is_cuda \
-                or t.device != self.device or not t.is_contiguous():
-            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise L.DeepcamHipError(f"ScaleSkill: {name} must be a contiguous uint8, int32 or int64 tensor [{self.B}, {self.H}, {self.W}] "
-                                    f"on {self.device}, got {got}")
-
-    def __call__(self, pred: torch.Tensor, truth: torch.Tensor, n_valid: Optional[int] = None) -> "ScaleSkill":
-        """pred, truth: contiguous device uint8, int32 or int64 [B, H, W], each side with its own element size; the frames from n_valid on
-        are neither read nor written."""
-        self._check(pred, "pred")
-        self._check(truth, "truth")
-        nv = self.B if n_valid is None else int(n_valid)
-        if not 0 <= nv <= self.B:
-            raise L.DeepcamHipError(f"ScaleSkill: n_valid must lie in [0, {self.B}], got {n_valid}")
-        L.call("dc_scale_score", self.B, nv, self.H, self.W, L.dptr(pred), self._BYTES[pred.dtype], L.dptr(truth), self._BYTES[truth.dtype],
-               self.L, self.O, L.dptr(self._origins), self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels),
-               L.dptr(self._total), L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
-        self._nv = nv
-        return self
-
-    def frame_rows(self):
-        """(rows int64 [n_valid, 2, O, levels + 1, 3], pixels int64 [n_valid, 2, 2]) of the last call: views of the object's device
-        buffers, not synchronised"""
-        return self._rows[:self._nv], self._pixels[:self._nv]
-
-    def reset(self) -> None:
-        """zeroes the running totals (in stream order)"""
-        for t in (self._total, self._total_pixels, self._frames):
-            t.zero_()
+    def _score(self, nv: int, pred: int, pred_bytes: int, truth: int, truth_bytes: int) -> None:
+        L.call("dc_scale_score", self.B, nv, self.H, self.W, pred, pred_bytes, truth, truth_bytes, self.L, self.O, L.dptr(self._origins),
+               self.row_range[0], self.row_range[1], L.dptr(self._rows), L.dptr(self._pixels), L.dptr(self._total),
+               L.dptr(self._total_pixels), L.dptr(self._frames), L.dptr(self._ws), L.stream_ptr())
 
     @staticmethod
     def combine(total_words) -> list:
@@ -3052,8 +3001,7 @@ class ScaleSkill:
         words = np.asarray(total_words, np.int64)
         if words.ndim != 5 or words.shape[0] != 2 or words.shape[3:] != (3, 2):
             raise L.DeepcamHipError(f"ScaleSkill: the totals are int64 [2, O, levels + 1, 3, 2], got shape {words.shape}")
-        return [[[[(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in level] for level in origin] for origin in cls]
-                for cls in words.tolist()]
+        return _two_words(words)
 
     def state(self) -> dict:
         """on the host: total [2][O][levels + 1][3] as Python ints, pixels [2][2] ((pred, truth) per class) and frames as ints"""
@@ -3137,11 +3085,6 @@ PROB_MAX_PIXELS = 1 << 30
 PROB_ONE = 65536                                  # q = rint(p * PROB_ONE)
 
 
-def _ratio(a, b):
-    """a / b as a Python float, None where b == 0"""
-    return None if b == 0 else a / b
-
-
 def brier_from_rows(rows, pixels):
     """The Brier scores of single frames from ProbabilitySkill.frame_rows(): rows [..., 3] = sum (q_c - o_c * 65536)^2 per class, pixels
     [..., 3] = (scored, bad label, logit not finite); rows / (scored * 2^32) as nested lists of Python floats of rows' shape, None where no
@@ -3166,7 +3109,7 @@ class ProbabilitySkill:
     Memory: (2 * 3 * 2 * bins * 2 + 2 * batch * 3 + 10) * 8 bytes.  A call launches on the current stream and does not synchronise; state()
     and result() read back."""
 
-    _BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+    FRAME_KEYS = ("prob", "prob_pixels")              # frame_rows(); the driver stores `brier` (brier_from_rows) in place of the raw rows
 
     def __init__(self, batch: int, height: int, width: int, bins: int = PROB_BINS, device=None):
         if batch < 1 or batch > PROB_MAX_BATCH or height < 1 or width < 1 or height * width > PROB_MAX_PIXELS:
@@ -3197,11 +3140,9 @@ class ProbabilitySkill:
         """logits: contiguous device fp32 [B, 3, H, W]; labels: contiguous device uint8, int32 or int64 [B, H, W]; the frames from n_valid
         on are not read."""
         self._check(logits, "logits", (torch.float32,), (self.B, 3, self.H, self.W))
-        self._check(labels, "labels", tuple(self._BYTES), (self.B, self.H, self.W))
-        nv = self.B if n_valid is None else int(n_valid)
-        if not 0 <= nv <= self.B:
-            raise L.DeepcamHipError(f"ProbabilitySkill: n_valid must lie in [0, {self.B}], got {n_valid}")
-        L.call("dc_prob_score", self.B, nv, self.H, self.W, L.dptr(logits), L.dptr(labels), self._BYTES[labels.dtype], self.K,
+        self._check(labels, "labels", tuple(_BYTES), (self.B, self.H, self.W))
+        nv = _n_valid("ProbabilitySkill", n_valid, self.B)
+        L.call("dc_prob_score", self.B, nv, self.H, self.W, L.dptr(logits), L.dptr(labels), _BYTES[labels.dtype], self.K,
                L.dptr(self._hist), L.dptr(self._rows), L.dptr(self._pixels), L.dptr(self._total_hist), L.dptr(self._total_sq),
                L.dptr(self._total_pixels), L.dptr(self._frames), L.stream_ptr())
         self._nv = nv
@@ -3227,7 +3168,7 @@ class ProbabilitySkill:
         words = np.asarray(words, np.int64)
         if words.shape != (3, 2):
             raise L.DeepcamHipError(f"ProbabilitySkill: the squared-error totals are int64 [3, 2], got shape {words.shape}")
-        return [(int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF) for lo, hi in words.tolist()]
+        return _two_words(words)
 
     def state(self) -> dict:
         """on the host: hist int64 [3, 2, bins, 2], sq [3] as Python ints, pixels [3] and frames as ints"""

@@ -132,133 +132,19 @@ from . import nn as dnn
 from . import png
 
 
-class _Verify(argparse.Action):
-    """--verify: implies --events"""
+def _implies(*flags, default=False):
+    """The Action class of a flag that implies others: given, it sets every attribute named in `flags` -- its own first -- to True.
+    default: False, or argparse.SUPPRESS for a flag that leaves no attribute behind unless given."""
 
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
+    class Implies(argparse.Action):
+        def __init__(self, option_strings, dest, **kw):
+            super().__init__(option_strings, dest, nargs=0, default=default, **kw)
 
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.verify = True
-        namespace.events = True
+        def __call__(self, parser, namespace, values, option_string=None):
+            for name in flags:
+                setattr(namespace, name, True)
 
-
-class _EventFields(argparse.Action):
-    """--event_fields: implies --events"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.event_fields = True
-        namespace.events = True
-
-
-class _Tracks(argparse.Action):
-    """--tracks: implies --events"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.tracks = True
-        namespace.events = True
-
-
-class _TrackFields(argparse.Action):
-    """--track_fields: implies --tracks, --event_fields and --events"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.track_fields = True
-        namespace.tracks = True
-        namespace.event_fields = True
-        namespace.events = True
-
-
-class _EventShape(argparse.Action):
-    """--event_shape: implies --events"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=False, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.event_shape = True
-        namespace.events = True
-
-
-class _Composites(argparse.Action):
-    """--composites: implies --event_fields and --events"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.composites = True
-        namespace.event_fields = True
-        namespace.events = True
-
-
-class _Fss(argparse.Action):
-    """--fss: implies --verify (and with it --events)"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.fss = True
-        namespace.verify = True
-        namespace.events = True
-
-
-class _DistanceSkill(argparse.Action):
-    """--distance_skill: implies --verify (and with it --events)"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.distance_skill = True
-        namespace.verify = True
-        namespace.events = True
-
-
-class _Displacement(argparse.Action):
-    """--displacement: implies --verify (and with it --events)"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.displacement = True
-        namespace.verify = True
-        namespace.events = True
-
-
-class _ScaleSkill(argparse.Action):
-    """--scale_skill: implies --verify (and with it --events)"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.scale_skill = True
-        namespace.verify = True
-        namespace.events = True
-
-
-class _ProbSkill(argparse.Action):
-    """--prob_skill: implies --verify (and with it --events)"""
-
-    def __init__(self, option_strings, dest, **kw):
-        super().__init__(option_strings, dest, nargs=0, default=argparse.SUPPRESS, **kw)
-
-    def __call__(self, parser, namespace, values, option_string=None):
-        namespace.prob_skill = True
-        namespace.verify = True
-        namespace.events = True
+    return Implies
 
 
 def _prob_bins(text: str) -> int:
@@ -297,13 +183,16 @@ def build_parser():
     AP.add_argument("--events", action="store_true", help="also catalogue the connected components of every mask (dataset 'events')")
     AP.add_argument("--min_event_pixels", type=int, default=0, help="with --events: leave out components of fewer pixels")
     AP.add_argument("--event_connectivity", type=int, default=8, choices=[4, 8], help="with --events: pixel connectivity")
-    AP.add_argument("--verify", action=_Verify, help="match the events of every mask to the events of the file's labels (implies --events; "
+    AP.add_argument("--verify", action=_implies("verify", "events"),
+                    help="match the events of every mask to the events of the file's labels (implies --events; "
                     "the files need climate/labels_0): datasets 'truth_events', 'matches', 'event_scores'; 'event_verification' in the summary")
     AP.add_argument("--min_event_cover", type=float, default=0.5, help="with --verify: an event is found when the other mask covers at "
                     "least this share of it with its class, in (0, 1]")
-    AP.add_argument("--event_fields", action=_EventFields, help="per event and file channel the extremes with their positions and the means "
+    AP.add_argument("--event_fields", action=_implies("event_fields", "events"),
+                    help="per event and file channel the extremes with their positions and the means "
                     "of the raw fields (implies --events): datasets 'event_fields', 'event_field_values', 'event_field_bits'")
-    AP.add_argument("--event_shape", action=_EventShape, help="per event its geometry (implies --events): spherical centroid, length, width, "
+    AP.add_argument("--event_shape", action=_implies("event_shape", "events"),
+                    help="per event its geometry (implies --events): spherical centroid, length, width, "
                     "aspect, orientation, perimeter, compactness; datasets 'event_shape', 'event_shape_values', 'event_shape_value_names'")
     AP.add_argument("--event_filter", action="store_true", help="filter the classifier's mask by event size and shape on the device (the "
                     "--filter_* thresholds): dataset 'prediction_filtered', 'event_filter' in the summary; --events, --verify's prediction "
@@ -322,12 +211,14 @@ def build_parser():
                     "to hundreds of milliseconds of the writer thread, so with --plot_every 1 the writer bounds the rate, not the device: raise --plot_every")
     AP.add_argument("--plot_every", type=int, default=1, help="with --plots: draw every N-th input file")
     AP.add_argument("--plot_channel", type=int, default=0, help="with --plots: the file channel that is drawn (0: integrated water vapour)")
-    AP.add_argument("--tracks", action=_Tracks, help="link the events of consecutive files into tracks (implies --events): the files, in the "
+    AP.add_argument("--tracks", action=_implies("tracks", "events"),
+                    help="link the events of consecutive files into tracks (implies --events): the files, in the "
                     "order of their sorted names, are taken as one gap-free time sequence (file index = frame number; date gaps or interleaved "
                     "runs are not detected).  Writes <output_dir>/tracks.h5 ('tracks', 'track_events', 'track_state'); 'tracks' in the summary")
     AP.add_argument("--min_track_frames", type=int, default=1, help="with --tracks: the summary also counts the tracks of at least N frames")
     AP.add_argument("--min_track_pixels", type=int, default=0, help="with --tracks: events of fewer pixels link nothing")
-    AP.add_argument("--track_fields", action=_TrackFields, help="the storm life cycles: per track and frame the merged field rows of its events, "
+    AP.add_argument("--track_fields", action=_implies("track_fields", "tracks", "event_fields", "events"),
+                    help="the storm life cycles: per track and frame the merged field rows of its events, "
                     "per track the lifetime extremes with frame and place (implies --tracks and --event_fields; --min_track_frames selects the "
                     "cycles).  tracks.h5 gains 'track_step_offsets', 'track_steps', 'track_step_fields', 'track_fields', 'track_cycle_counts'; "
                     "'track_fields' in the summary")
@@ -344,7 +235,8 @@ def build_parser():
     AP.add_argument("--climatology_contour", type=float, default=0.1, help="with --climatology and --plots: the frequency whose region is outlined")
     # the --composite_* flags leave no attribute behind unless given (COMPOSITE_DEFAULTS has their defaults): a namespace without
     # them is the namespace of before
-    AP.add_argument("--composites", action=_Composites, help="accumulate storm-centred composites on the device (implies --event_fields; "
+    AP.add_argument("--composites", action=_implies("composites", "event_fields", "events", default=argparse.SUPPRESS),
+                    help="accumulate storm-centred composites on the device (implies --event_fields; "
                     "needs --composite_center_channel): windows of the raw fields around every event's centre and their radial profiles.  "
                     "Writes <output_dir>/composites.h5; 'composites' in the summary")
     S = argparse.SUPPRESS
@@ -367,7 +259,8 @@ def build_parser():
     AP.add_argument("--composite_bin_km", type=float, default=S, help="with --composites: the width of a distance bin of the radial profile (25)")
     AP.add_argument("--composite_bins", type=int, default=S, help="with --composites: the number of distance bins; 0: no radial profile (40)")
     # like the --composite_* flags, the --fss* flags leave no attribute behind unless given (FSS_DEFAULTS has their defaults)
-    AP.add_argument("--fss", action=_Fss, help="neighbourhood verification on the device (implies --verify; the files need climate/labels_0): "
+    AP.add_argument("--fss", action=_implies("fss", "verify", "events", default=argparse.SUPPRESS),
+                    help="neighbourhood verification on the device (implies --verify; the files need climate/labels_0): "
                     "the Fractions Skill Score of --verify's prediction side against the labels per class and window.  Datasets 'fss', "
                     "'fss_pixels'; 'fss' in the summary")
     AP.add_argument("--fss_windows", type=int, nargs="+", default=S, help="with --fss: the windows' sides in grid pixels, distinct odd "
@@ -376,7 +269,8 @@ def build_parser():
                     "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     AP.add_argument("--fss_no_wrap", action="store_true", default=S, help="with --fss: do not take the columns as periodic")
     # likewise the --distance_* flags (DISTANCE_DEFAULTS)
-    AP.add_argument("--distance_skill", action=_DistanceSkill, help="distance-map verification on the device (implies --verify; the files "
+    AP.add_argument("--distance_skill", action=_implies("distance_skill", "verify", "events", default=argparse.SUPPRESS),
+                    help="distance-map verification on the device (implies --verify; the files "
                     "need climate/labels_0): mean error distance, Hausdorff distance, Baddeley's Delta and hit rate / success ratio within "
                     "r grid pixels of --verify's prediction side against the labels, per class.  Datasets 'distance', 'distance_baddeley'; "
                     "'distance_skill' in the summary")
@@ -386,7 +280,8 @@ def build_parser():
                     "in the rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     AP.add_argument("--distance_no_wrap", action="store_true", default=S, help="with --distance_skill: do not take the columns as periodic")
     # likewise the --displacement* flags (DISPLACEMENT_DEFAULTS)
-    AP.add_argument("--displacement", action=_Displacement, help="displacement verification on the device (implies --verify; the files "
+    AP.add_argument("--displacement", action=_implies("displacement", "verify", "events", default=argparse.SUPPRESS),
+                    help="displacement verification on the device (implies --verify; the files "
                     "need climate/labels_0): the shift of --verify's prediction side that overlaps the labels most, the scores without "
                     "and with it and the CRA decomposition of the error, per class.  Datasets 'displacement', 'displacement_pixels', "
                     "'displacement_best'; 'displacement' in the summary")
@@ -395,7 +290,8 @@ def build_parser():
     AP.add_argument("--displacement_rows", type=int, nargs=2, default=S, metavar=("I0", "I1"), help="with --displacement: score the label "
                     "rows I0 <= i < I1 only (a latitude band; the whole frame by default)")
     # likewise the --scale_* flags (SCALE_DEFAULTS)
-    AP.add_argument("--scale_skill", action=_ScaleSkill, help="scale-separation verification on the device (implies --verify; the files "
+    AP.add_argument("--scale_skill", action=_implies("scale_skill", "verify", "events", default=argparse.SUPPRESS),
+                    help="scale-separation verification on the device (implies --verify; the files "
                     "need climate/labels_0): the squared error of --verify's prediction side and the energies of both sides per 2-D Haar "
                     "component of scale 1, 2, 4, ... grid pixels, per class (the intensity-scale skill score).  Datasets 'scale', "
                     "'scale_pixels'; 'scale_skill' in the summary")
@@ -406,7 +302,8 @@ def build_parser():
     AP.add_argument("--scale_origins", type=int, nargs="+", default=S, metavar="C", help="with --scale_skill: up to 8 column offsets in "
                     "[0, 2^L) of the dyadic grid, scored in one pass (0)")
     # likewise the --prob_* flags (PROB_DEFAULTS)
-    AP.add_argument("--prob_skill", action=_ProbSkill, help="probabilistic verification on the device (implies --verify; the files need "
+    AP.add_argument("--prob_skill", action=_implies("prob_skill", "verify", "events", default=argparse.SUPPRESS),
+                    help="probabilistic verification on the device (implies --verify; the files need "
                     "climate/labels_0): reliability diagram, Brier score with its decomposition, POD / POFD / CSI per probability threshold "
                     "and ROC area per class, from the classifier's softmax probabilities against the labels.  It always scores the "
                     "classifier's probabilities: --event_filter does not change them.  Datasets 'brier', 'prob_pixels'; prob_skill.h5; "
@@ -780,29 +677,14 @@ def plot_name(base: str) -> str:
 
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
-                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, fss_windows: int = 0,
-                 prob_skill: bool = False, decision: bool = False, distance_cells: int = 0, displacement_window: int = 0,
-                 scale_cells=None):
-        # --scale_skill: the rows of nn.ScaleSkill (scale_cells = (O, L + 1)) and the pixel counts beside them
-        self.scale = torch.empty((B, 2, *scale_cells, 3), dtype=torch.int64).pin_memory() if scale_cells else None
-        self.scale_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if scale_cells else None
-        # --displacement: the tables of nn.DisplacementSkill (window = 2 R + 1), the pixel counts and the best shifts beside them
-        S = displacement_window
-        self.displacement = torch.empty((B, 2, S, S + 1), dtype=torch.int64).pin_memory() if S else None
-        self.displacement_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if S else None
-        self.displacement_best = torch.empty((B, 2, 4), dtype=torch.int64).pin_memory() if S else None
-        # --distance_skill: the rows of nn.DistanceSkill and the Baddeley sums beside them
-        self.distance = torch.empty((B, 2, 2, distance_cells), dtype=torch.int64).pin_memory() if distance_cells else None
-        self.distance_baddeley = torch.empty((B, 2), dtype=torch.int64).pin_memory() if distance_cells else None
+                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=()):
+        # --fss, --distance_skill, --displacement, --scale_skill, --prob_skill: per skill the buffers of its frame_rows(), under the
+        # names of its FRAME_KEYS and in the skills' order, which is the order of their datasets in a mask file
+        self.frames = {key: torch.empty((B, *t.shape[1:]), dtype=t.dtype).pin_memory()
+                       for skill in frame_skills for key, t in zip(skill.FRAME_KEYS, skill.frame_rows())}
         # --decision_*: the decided mask and the rule's counters
         self.dmask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if decision else None
         self.dcounts = torch.empty((B, len(dnn.DECISION_COUNTS)), dtype=torch.int64).pin_memory() if decision else None
-        # --prob_skill: the squared-error rows of nn.ProbabilitySkill and the pixel counters beside them
-        self.prob_rows = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
-        self.prob_pixels = torch.empty((B, 3), dtype=torch.int64).pin_memory() if prob_skill else None
-        # --fss: the rows of nn.FractionsSkill and the pixel counts beside them
-        self.fss = torch.empty((B, 2, fss_windows, 3), dtype=torch.int64).pin_memory() if fss_windows else None
-        self.fss_pixels = torch.empty((B, 2, 2), dtype=torch.int64).pin_memory() if fss_windows else None
         # --event_shape: the rows of nn.EventShape (cap rows of 96 bytes per sample)
         self.shape = torch.empty((B, event_cap, len(dnn.EVENT_SHAPE_FIELDS)), dtype=torch.int64).pin_memory() if event_shape else None
         # --event_filter: the filtered mask and the filter's counts
@@ -869,19 +751,13 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         extra = dict(extra or {}, prediction_decided=slot.dmask[j].numpy(), decision=slot.dcounts[j].numpy())
                     if slot.fmask is not None:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
-                    if slot.fss is not None:
-                        extra = dict(extra or {}, fss=slot.fss[j].numpy(), fss_pixels=slot.fss_pixels[j].numpy())
-                    if slot.distance is not None:
-                        extra = dict(extra or {}, distance=slot.distance[j].numpy(), distance_baddeley=slot.distance_baddeley[j].numpy())
-                    if slot.displacement is not None:
-                        extra = dict(extra or {}, displacement=slot.displacement[j].numpy(),
-                                     displacement_pixels=slot.displacement_pixels[j].numpy(), displacement_best=slot.displacement_best[j].numpy())
-                    if slot.scale is not None:
-                        extra = dict(extra or {}, scale=slot.scale[j].numpy(), scale_pixels=slot.scale_pixels[j].numpy())
-                    if slot.prob_rows is not None:
-                        brier = dnn.brier_from_rows(slot.prob_rows[j].numpy(), slot.prob_pixels[j].numpy())
-                        extra = dict(extra or {}, brier=np.asarray([np.nan if v is None else v for v in brier], np.float64),
-                                     prob_pixels=slot.prob_pixels[j].numpy())
+                    frames = {key: t[j].numpy() for key, t in slot.frames.items()}
+                    if "prob" in frames:                     # the last skill's two: `brier` is stored in the raw rows' place
+                        prob_rows, prob_pixels = frames.pop("prob"), frames.pop("prob_pixels")
+                        brier = dnn.brier_from_rows(prob_rows, prob_pixels)
+                        frames.update(brier=np.asarray([np.nan if v is None else v for v in brier], np.float64), prob_pixels=prob_pixels)
+                    if frames:
+                        extra = dict(extra or {}, **frames)
                     write_mask_file(os.path.join(out_dir, base), slot.mask[j].numpy(), conf, rows, extra)
                     if plot[j]:
                         png.write_png(os.path.join(out_dir, "plots", plot_name(base)), slot.rgb[j].numpy())
@@ -889,8 +765,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                            "mean_confidence": float(conf.mean(dtype=np.float64)) if conf is not None else None}
                     if plot[j]:
                         rec["plot"] = plot_name(base)
-                    if slot.displacement_best is not None:
-                        rec["displacement_best"] = [[int(v) for v in row] for row in slot.displacement_best[j].tolist()]
+                    if "displacement_best" in frames:
+                        rec["displacement_best"] = [[int(v) for v in row] for row in frames["displacement_best"].tolist()]
                     if slot.dcounts is not None:
                         rec["decision"] = [int(v) for v in slot.dcounts[j].tolist()]
                     if slot.fcounts is not None:
@@ -1011,6 +887,7 @@ def main(pargs) -> dict:
     if getattr(pargs, "prob_skill", False):
         prob = dnn.ProbabilitySkill(B, H, W, device=device, **prob_options(pargs))
         predictor.store_logits = True              # bf16 keeps the logits in registers unless asked
+    frame_skills = [skill for skill in (fss, dist, disp, scale, prob) if skill is not None]
     # --composites: behind every batch, on the catalogue and the field rows of --event_fields
     comp = None
     if getattr(pargs, "composites", False):
@@ -1024,9 +901,8 @@ def main(pargs) -> dict:
     work_q: "queue.Queue" = queue.Queue()
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
-                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, fss.S if fss else 0,
-                             prob is not None, decide is not None, dist.R + 4 if dist else 0, 2 * disp.R + 1 if disp else 0,
-                             (scale.O, scale.L + 1) if scale else None))
+                             renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, decide is not None,
+                             frame_skills))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -1054,27 +930,10 @@ def main(pargs) -> dict:
                 catalog(dmask, n_valid=nv)
             if verify:
                 matcher(dmask, y, n_valid=nv)
-            if fss is not None:
-                frame_rows, frame_pixels = fss(dmask, y, n_valid=nv).frame_rows()
-                slot.fss[:nv].copy_(frame_rows, non_blocking=True)
-                slot.fss_pixels[:nv].copy_(frame_pixels, non_blocking=True)
-            if dist is not None:
-                dist_rows, dist_baddeley = dist(dmask, y, n_valid=nv).frame_rows()
-                slot.distance[:nv].copy_(dist_rows, non_blocking=True)
-                slot.distance_baddeley[:nv].copy_(dist_baddeley, non_blocking=True)
-            if disp is not None:
-                disp_rows, disp_pixels, disp_best = disp(dmask, y, n_valid=nv).frame_rows()
-                slot.displacement[:nv].copy_(disp_rows, non_blocking=True)
-                slot.displacement_pixels[:nv].copy_(disp_pixels, non_blocking=True)
-                slot.displacement_best[:nv].copy_(disp_best, non_blocking=True)
-            if scale is not None:
-                scale_rows, scale_pixels = scale(dmask, y, n_valid=nv).frame_rows()
-                slot.scale[:nv].copy_(scale_rows, non_blocking=True)
-                slot.scale_pixels[:nv].copy_(scale_pixels, non_blocking=True)
-            if prob is not None:
-                prob_rows, prob_pixels = prob(predictor.logits_buffer, y, n_valid=nv).frame_rows()
-                slot.prob_rows[:nv].copy_(prob_rows, non_blocking=True)
-                slot.prob_pixels[:nv].copy_(prob_pixels, non_blocking=True)
+            for skill in frame_skills:             # the mask skills take the mask, the probabilities' skill the stored logits
+                skill(predictor.logits_buffer if skill is prob else dmask, y, n_valid=nv)
+                for key, rows in zip(skill.FRAME_KEYS, skill.frame_rows()):
+                    slot.frames[key][:nv].copy_(rows, non_blocking=True)
             if eshape is not None:
                 slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
             if tracker is not None:

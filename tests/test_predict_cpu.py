@@ -51,6 +51,37 @@ def test_predict_parser_accepts_the_documented_flags():
         predict.build_parser().parse_args(["--data_dir", "d"])                  # no checkpoint, no output directory
 
 
+# flag -> the attributes it sets to True, and whether the flag leaves no attribute behind unless given (argparse.SUPPRESS)
+IMPLYING_FLAGS = {
+    "verify": (("verify", "events"), False),
+    "event_fields": (("event_fields", "events"), False),
+    "tracks": (("tracks", "events"), False),
+    "track_fields": (("track_fields", "tracks", "event_fields", "events"), False),
+    "event_shape": (("event_shape", "events"), False),
+    "composites": (("composites", "event_fields", "events"), True),
+    "fss": (("fss", "verify", "events"), True),
+    "distance_skill": (("distance_skill", "verify", "events"), True),
+    "displacement": (("displacement", "verify", "events"), True),
+    "scale_skill": (("scale_skill", "verify", "events"), True),
+    "prob_skill": (("prob_skill", "verify", "events"), True),
+}
+
+
+@pytest.mark.parametrize("flag", sorted(IMPLYING_FLAGS))
+def test_a_flag_that_implies_others_sets_exactly_those(flag):
+    from mlperf_deepcam_amd import predict
+    required = ["--checkpoint", "m", "--data_dir", "d", "--stats_file", "s", "--output_dir", "o"]
+    plain = vars(predict.build_parser().parse_args(required))
+    given = vars(predict.build_parser().parse_args([*required, "--" + flag]))
+    sets, suppressed = IMPLYING_FLAGS[flag]
+    assert (flag not in plain) if suppressed else (plain[flag] is False)
+    for other, (_, other_suppressed) in IMPLYING_FLAGS.items():                  # the flag brings in no other flag's attribute
+        assert (other in given) == (other in sets or not other_suppressed), other
+    changed = {k for k in given if k not in plain or given[k] != plain[k]}
+    assert changed == set(sets) and all(given[k] is True for k in sets)
+    assert set(plain) - set(given) == set()
+
+
 def _unlabelled_files(tmp_path, n=3, H=16, W=24):
     from mlperf_deepcam_amd import h5lite
     root = str(tmp_path / "unlabelled")

@@ -213,7 +213,26 @@ def test_an_origin_out_of_range_on_the_device_is_skipped(name, band):
         assert not total[:, slot].any() and (total[:, 1 - slot] == np.asarray(state["total"], dtype=object)[:, 1 - slot]).all()
 
 
-# ------------------------------------------------------------------------------------------------------------------ 5. errors
+# ------------------------------------------------------------------------------------------------------------------ 5. the carry
+def test_the_carry_into_the_high_word():
+    ss = dnn.ScaleSkill(2, 8, 8, levels=1, origins=(0,), device=DEV)
+    words = torch.zeros_like(ss._total)                                          # [2, 1, 2, 3, 2] = (lo, hi)
+    words[..., 0] = -1                                                           # every lo = 2^64 - 1, every hi = 0
+    ss._total.copy_(words)
+    truth = np.zeros((2, 8, 8), np.uint8)
+    truth[0, 1:4, 2:5], truth[0, 5:7, 0:3], truth[1, 0:2, 6:8], truth[1, 4:8, 3:4] = 1, 2, 1, 2
+    pred = np.zeros((2, 8, 8), np.uint8)                                         # class 1 moved by a pixel, class 2 never predicted
+    pred[0, 2:5, 3:6], pred[1, 0:2, 5:7] = 1, 1
+    ss(_dev(pred), _dev(truth))
+    own = ss.frame_rows()[0].cpu().numpy().astype(object).sum(axis=0)            # [2, 1, 2, 3] Python ints: the call's own rows
+    assert (own > 0).any() and (own == 0).any()                                  # class 2 has no sum F^2
+    want = (own + ((1 << 64) - 1)).tolist()
+    assert ss.state()["total"] == want
+    raw = ss._total.cpu().numpy()
+    assert np.array_equal(raw[..., 1], (own != 0).astype(np.int64))              # the high words themselves: one carry per non-zero row
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. errors
 def test_errors_raise_and_launch_nothing():
     H, W, n, origins = us.shape("two-tiles")
     ss = _make("two-tiles", "full")
@@ -259,7 +278,7 @@ def test_errors_raise_and_launch_nothing():
     assert _zero_state(ss.state())
 
 
-# ------------------------------------------------------------------------------------------------------------------ 6. driver
+# ------------------------------------------------------------------------------------------------------------------ 7. driver
 def _h5_write(path, datasets):
     from mlperf_deepcam_amd import data as ddata
     backend, h5 = ddata._h5_backend()
