@@ -863,6 +863,13 @@ def event_weight_tables(height: int, width: int):
     return q(np.cos(lat)), q(np.cos(lon)), q(np.sin(lon))
 
 
+def _filled_rows(table: torch.Tensor, fill):
+    """Per valid sample only the filled rows of a device table [B, cap, ...]: a list of numpy arrays table[b, :fill[b]], b < len(fill) (at
+    least one sample).  One copy to the host, cut at the fullest sample's rows."""
+    host = table[:len(fill), :max(max(fill), 1)].cpu().numpy()
+    return [host[b, :fill[b]].copy() for b in range(len(fill))]
+
+
 class EventCatalog:
     """Connected components of class masks on the device (dc_mask_components + dc_component_stats, csrc/components.hip): what a user of a
     tropical-cyclone / atmospheric-river detector works with -- how many events a snapshot holds, where they are and how large.
@@ -928,9 +935,11 @@ class EventCatalog:
         if nv == 0:
             return [], []
         ncomp = self._ncomp[:nv].cpu().numpy()
-        fill = [min(int(t), self.cap) for t in ncomp[:, 0]]
-        host = self._table[:nv, :max(max(fill), 1)].cpu().numpy()
-        return ncomp, [host[b, :fill[b]].copy() for b in range(nv)]
+        return ncomp, _filled_rows(self._table, [min(int(t), self.cap) for t in ncomp[:, 0]])
+
+    def _fill(self, nv: int):
+        """The rows the table holds for each of the first nv samples: min(total, cap) (EventFields and EventShape cut their tables by it)"""
+        return [min(int(t), self.cap) for t in self._ncomp[:nv, 0].cpu().tolist()]
 
     def events(self, min_pixels: int = 0):
         """Per valid sample of the last call a list of dicts (decode), components below min_pixels left out on the host."""
@@ -956,7 +965,7 @@ class EventCatalog:
 
 
 class EventMatcher:
-    """Two event catalogues of the same frames matched on the device (dc_component_overlap + dc_event_scores, csrc/components.hip): which
+    """Two event catalogues of the same frames matched on the device (dc_component_overlap + dc_event_scores, csrc/event_match.hip): which
     event of mask a overlaps which event of mask b and by how many pixels, how much of every event the other mask covers with the same
     class, and from that the detection scores per class -- hits and misses among b's events, false alarms and matched detections among
     a's.  With a = a prediction and b = its labels these are the counts behind POD, FAR and CSI; the same pairs link the events of two
@@ -1038,9 +1047,7 @@ class EventMatcher:
         if nv == 0:
             return [], []
         npairs = self._npairs[:nv].cpu().numpy()
-        fill = [int(n) for n in npairs[:, 0]]
-        host = self._pairs[:nv, :max(max(fill), 1)].cpu().numpy()
-        return [self.sort_pairs(host[s, :fill[s]]) for s in range(nv)], [int(f) for f in npairs[:, 1]]
+        return [self.sort_pairs(p) for p in _filled_rows(self._pairs, [int(n) for n in npairs[:, 0]])], [int(f) for f in npairs[:, 1]]
 
     def cover(self):
         """(cover_a, cover_b) on the host: int64 numpy arrays [n_valid, cap], per component the pixels the other mask covers with its class"""
@@ -1131,7 +1138,7 @@ def event_field_value(keys) -> np.ndarray:
 
 
 class EventFields:
-    """Per-event statistics of the raw input fields on the device (dc_component_fields, csrc/components.hip): for every event of a
+    """Per-event statistics of the raw input fields on the device (dc_component_fields, csrc/event_fields.hip): for every event of a
     catalogue and every channel the minimum and where it sits (a cyclone's pressure minimum is its centre), the maximum and where it sits
     (its strongest wind), the sum and the area-weighted sum (a river's mean water vapour).  The object owns the device scale_bits (int32
     [C], see event_field_bits) and the table (int64 [B, cap, C, 6], EVENT_FIELD_STATS; row k belongs to row k of the catalogue's table).
@@ -1177,9 +1184,7 @@ class EventFields:
         nv = self._last_valid
         if nv == 0:
             return []
-        fill = [min(int(t), self.catalog.cap) for t in self.catalog._ncomp[:nv, 0].cpu().tolist()]
-        host = self._ftable[:nv, :max(max(fill), 1)].cpu().numpy()
-        return [host[b, :fill[b]].copy() for b in range(nv)]
+        return _filled_rows(self._ftable, self.catalog._fill(nv))
 
     def stats(self, min_pixels: int = 0):
         """Per valid sample a list aligned with catalog.events(min_pixels): per event a list over channels of dicts (decode)."""
@@ -1270,7 +1275,7 @@ def event_shape_tables(height: int, width: int):
 
 
 class EventShape:
-    """Geometry per event on the device (dc_component_shape, csrc/components.hip): boundary pixels, perimeter faces, and the first and
+    """Geometry per event on the device (dc_component_shape, csrc/event_shape.hip): boundary pixels, perimeter faces, and the first and
     second moments of the event's pixels as area-weighted unit vectors on the sphere, all exact integer sums (EVENT_SHAPE_FIELDS; the
     header has the definition).  decode turns them into a spherical centroid, the length and width of the uniform strip with the same
     second moments, aspect, orientation, perimeter and compactness.  Built on an existing EventCatalog, as EventFields is; a call must
@@ -1306,9 +1311,7 @@ class EventShape:
         nv = self._last_valid
         if nv == 0:
             return []
-        fill = [min(int(t), self.catalog.cap) for t in self.catalog._ncomp[:nv, 0].cpu().tolist()]
-        host = self._shape[:nv, :max(max(fill), 1)].cpu().numpy()
-        return [host[b, :fill[b]].copy() for b in range(nv)]
+        return _filled_rows(self._shape, self.catalog._fill(nv))
 
     def shapes(self):
         """Per valid sample of the last call a list of dicts (decode), one per row of the catalogue."""
@@ -1531,7 +1534,7 @@ TRACK_FIELDS = ("id", "class", "events", "first_frame", "last_frame", "pixels", 
 
 
 class EventTracker:
-    """Events linked across time steps on the device (dc_track_append, dc_track_link, dc_track_resolve, csrc/components.hip): the frames
+    """Events linked across time steps on the device (dc_track_append, dc_track_link, dc_track_resolve, csrc/tracks.hip): the frames
     given since reset() are one time series, frame numbers 0, 1, 2, ...; two events of consecutive frames are linked when they have the
     same class, share at least one pixel and each has at least max(min_pixels, 1) pixels; a track is a connected component of the events
     under these links (merges and splits stay in one track), its id the smallest event number it holds (include/deepcam_hip.h has the
@@ -1677,7 +1680,7 @@ TRACK_FIELD_STATS = ("min", "min_pixel", "max", "max_pixel")
 
 
 class TrackFields:
-    """Storm life cycles on the device (dc_track_fields_append, dc_track_cycles, csrc/components.hip): the join of an EventTracker (which
+    """Storm life cycles on the device (dc_track_fields_append, dc_track_cycles, csrc/tracks.hip): the join of an EventTracker (which
     events of which frames form one storm) and an EventFields of the same catalogue (every event's extremes and sums of the raw fields).
     Per track and frame -- a STEP -- the field rows of the track's events in that frame merged into one (for a cyclone and sea-level
     pressure the minimum's place is the conventional track position, its value the intensity), per track the lifetime extremes with the

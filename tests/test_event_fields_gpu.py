@@ -1,4 +1,4 @@
-"""Event intensities on the GPU (dc_component_fields of csrc/components.hip, nn.EventFields, predict.py --event_fields) against the loop of
+"""Event intensities on the GPU (dc_component_fields of csrc/event_fields.hip, nn.EventFields, predict.py --event_fields) against the loop of
 tests/util_event_fields.py.  Every result is an integer that does not depend on the order of arrival: every comparison is torch.equal on
 int64 tables, without a tolerance.
 

@@ -1,4 +1,4 @@
-"""Event matching on the GPU (dc_component_overlap / dc_event_scores of csrc/components.hip, nn.EventMatcher, predict.py --verify) against
+"""Event matching on the GPU (dc_component_overlap / dc_event_scores of csrc/event_match.hip, nn.EventMatcher, predict.py --verify) against
 the numpy checker of tests/util_event_match.py.  Everything is integer: every comparison is exact.
 
 Shapes come from the labelling kernel's tile (dc_mask_components_tile), as in test_events_gpu.py: (2 TH + 3, 2 TW + 5) has ragged tiles

@@ -1,4 +1,4 @@
-"""Event shapes and the shape filter on the GPU (csrc/components.hip: dc_component_shape, dc_event_select, dc_mask_select; nn.EventShape,
+"""Event shapes and the shape filter on the GPU (csrc/event_shape.hip: dc_component_shape, dc_event_select, dc_mask_select; nn.EventShape,
 nn.EventFilter; predict.py --event_shape / --event_filter) against the checker of tests/util_event_shape.py.  Integer equality
 throughout: shape rows, keep flags, filtered mask, counts.
 

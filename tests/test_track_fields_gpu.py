@@ -1,4 +1,4 @@
-"""Storm life cycles on the GPU (dc_track_fields_append / dc_track_cycles of csrc/components.hip, nn.TrackFields, predict.py --track_fields)
+"""Storm life cycles on the GPU (dc_track_fields_append / dc_track_cycles of csrc/tracks.hip, nn.TrackFields, predict.py --track_fields)
 against the numpy checker of tests/util_track_fields.py, which test_track_fields_cpu.py holds against a brute force over pixels.  Everything
 is integer: every comparison is np.array_equal.
 
@@ -6,6 +6,7 @@ The frames are those of tests/util_track_fields.py (test_track_fields_cpu.py ass
 that tie across fragments and across frames, tracks the selection filters and more track rows than one workgroup ranks).  A sequence is
 fed as batches whose padding samples are all class 1 with huge field values -- they would join and outbid everything if they were read --
 and every buffer the calls fill is pre-filled with a sentinel, so that rows behind the filled parts are seen to be untouched."""
+import ctypes as C
 import functools
 import json
 import os
@@ -21,6 +22,7 @@ pytestmark = pytest.mark.gpu
 from mlperf_deepcam_amd import lib as L  # noqa: E402
 from mlperf_deepcam_amd import nn as dnn  # noqa: E402
 import util_track_fields as uf  # noqa: E402
+import util_tracks as ut  # noqa: E402
 import util_val  # noqa: E402
 from util_launch import served  # noqa: E402
 
@@ -203,6 +205,25 @@ def test_more_components_than_the_catalogue_holds():
     ref = _reference("random", "wide", 3, 4, cap=5)
     assert ref["state"][3] > 0
     _assert_equal(_run("random", "wide", 3, 4, 3, cap=5), ref)
+
+
+def test_more_chunks_of_tracks_than_one_block_of_the_offsets_pass():
+    """dc_track_cycles ranks the selected track rows in chunks of 256 and ONE workgroup turns the chunks' frame counts into offsets, 256
+    chunks at a time with a carry from block to block (the tracker's resolve does the same with the events).  The checkerboard of
+    util_tracks on test_tracks_gpu.py's "tiles" shape gives 71288 events that are 71288 one-frame tracks, 279 chunks of either."""
+    th, tw = C.c_int(), C.c_int()
+    assert L.load().dc_mask_components_tile(C.byref(th), C.byref(tw)) == 0
+    T, H, W = 8, 2 * th.value + 3, 2 * tw.value + 5
+    masks = ut.checkerboard(T, H, W)
+    fields = np.random.RandomState(77).standard_normal((T, H, W, 1)).astype(np.float32) * 40.0
+    kw = {"cap": 16384, "event_cap": 1 << 17, "step_cap": 1 << 17}
+    ref = uf.reference(masks, fields, 4, False, _tables(H, W), 1, uf.scale_bits(1), min_frames=1, **kw)
+    assert ref["state"].tolist() == [T * H * W, T, 0, 0] and ref["ncycles"].tolist() == [T * H * W, T * H * W, T * H * W, 0]
+    objs = _objects(3, H, W, 1, 1, conn=4, wrap=False, **kw)
+    _feed_all(objs, masks, fields)
+    got = _result(objs, min_frames=1)
+    assert int(objs[1]._state[0].item()) > 65536 and int(objs[1]._ntracks[3].item()) > 65536, "fewer than 257 chunks: no carry"
+    _assert_equal(got, ref)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6. series control

@@ -1,4 +1,4 @@
-"""Event tracks on the GPU (dc_track_append / dc_track_link / dc_track_resolve of csrc/components.hip, nn.EventTracker, predict.py --tracks)
+"""Event tracks on the GPU (dc_track_append / dc_track_link / dc_track_resolve of csrc/tracks.hip, nn.EventTracker, predict.py --tracks)
 against the numpy checker of tests/util_tracks.py.  Everything is integer: every comparison is exact.
 
 Shapes come from the labelling kernel's tile (dc_mask_components_tile), as in test_event_match_gpu.py: (2 TH + 3, 2 TW + 5) has ragged
@@ -78,6 +78,8 @@ def _seq(name, H, W):
     elif name == "random":                               # independent frames: many events, late merges of tracks that were long apart
         rs = np.random.RandomState(zlib.crc32(f"tracks random {H} {W}".encode()))
         m[:] = (rs.rand(T, H, W) < 0.45) * rs.randint(1, 3, (T, H, W))
+    elif name == "checker":                              # every pixel an event of its own that links to nothing (connectivity 4)
+        m[:] = ut.checkerboard(T, H, W)
     else:
         raise KeyError(name)
     m.setflags(write=False)
@@ -250,6 +252,19 @@ def test_more_tracks_than_rows():
     got = _run(_seq("random", H, W), 3, 4, False, track_cap=track_cap)
     _assert_equal(got, ref)
     assert np.array_equal(got["tracks"], full["tracks"][:track_cap]) and got["track_of"].max() == track_cap - 1
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4b. many chunks
+def test_more_chunks_of_events_than_one_block_of_the_offsets_pass():
+    """The resolve ranks roots in chunks of 256 events and ONE workgroup turns the chunks' counts into offsets, 256 chunks at a time with a
+    carry from block to block.  71288 events that are 71288 tracks make 279 chunks: the carry is taken once, and every table is compared."""
+    H, W = SHAPES["tiles"]
+    kw = {"cap": 16384, "event_cap": 1 << 17}
+    ref = _reference("checker", "tiles", 4, False, **kw)
+    assert ref["state"].tolist() == [T * H * W, T, 0, 0] and ref["ntracks"].tolist() == [T * H * W, T * H * W // 2, T * H * W // 2, T * H * W]
+    got = _run(_seq("checker", H, W), 3, 4, False, **kw)
+    assert got["state"][0] > 65536 and got["ntracks"][3] > 65536, "fewer than 257 chunks: the offsets pass never carries"
+    _assert_equal(got, ref)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. cut and reset

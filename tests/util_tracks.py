@@ -15,6 +15,13 @@ import util_events as ue
 STORE, TRACK = 12, 8
 
 
+def checkerboard(T, H, W):
+    """uint8 [T, H, W], mask[t] = 1 + (r + c + t) % 2: under 4-connectivity every pixel is an event, and its class alternates from frame to
+    frame, so nothing links -- T * H * W events and as many tracks, the way to more than 256 chunks of either at a small frame"""
+    t, r, c = np.ogrid[:T, :H, :W]
+    return (1 + (r + c + t) % 2).astype(np.uint8)
+
+
 def track(masks, connectivity, wrap, wy, cx, sx, cap=4096, event_cap=1 << 19, track_cap=None, min_pixels=0, cuts=()):
     """masks uint8 [T, H, W] -> {"state" int64 [4], "store" int64 [n, 12], "track_of" int32 [n], "tracks" int64 [m, 8], "ntracks" int64 [4],
     "first" int64 [T]}.  cuts: frame numbers that are NOT linked to the frame before them (EventTracker.cut())."""
