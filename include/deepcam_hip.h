@@ -93,6 +93,9 @@ int dc_reset_options(void);
  *   decision rule (dc_logits_decide, dc_hysteresis_select): decide_q_vec (16-byte loads and 32-bit stores, H * W a multiple of 4) or
  *     decide_q (4-byte loads, byte stores, any H * W): candidates, seeds and their counters; decide_mark (a seed flags its component's
  *     root), decide_select (the mask of the flagged components, the kept pixels and the events)
+ *   view ensemble (dc_input_view_hwc, dc_ensemble_add, dc_ensemble_pool): view_normalize (the rolled, mirrored and normalised input);
+ *     ensemble_add_vec (16-byte loads and stores: W and roll multiples of 4) or ensemble_add (4-byte accesses, any width and roll): one
+ *     member into the state; ensemble_pool (the pooled logits, the vote counters and their running totals)
  *   distance-map verification (dc_distance_score): dist_vert (the row distances of four indicator fields, one packed word per pixel),
  *     dist_horz (the capped squared distance maps, the ring counters, the sums and the Baddeley term), dist_total (the running totals)
  *   displacement verification (dc_displacement_score): disp_pack (the four bit planes, the predicted pixels per row, the pixel counts),
@@ -1308,6 +1311,60 @@ int dc_logits_decide(int B, int n_valid, int H, int W, const float* logits_nchw,
                      uint8_t* seed /*may be NULL iff high == low*/, int64_t* counts /*[B][12]*/, void* stream);
 int dc_hysteresis_select(int B, int n_valid, int H, int W, const uint8_t* cand, const uint8_t* seed, const int32_t* labels, uint8_t* flags,
                          uint8_t* out_mask, int64_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The view ensemble (nn.ViewEnsemble, nn.view_input; predict.py --ensemble_rolls / --ensemble_flip_lat / --ensemble_negate /
+ * --ensemble_seam_margin): test-time augmentation on the periodic grid.  Every convolution pads the first and the last column with zeros,
+ * while everything behind the classifier takes the columns as periodic; a column roll is an exact symmetry of the data that only the
+ * padding breaks, and a mirrored hemisphere with the meridional winds negated is the second physical view.  The forecasts of several views
+ * are pooled per pixel in q, dc_prob_score's integer, and leave as ONE fp32 NCHW logits tensor: its mask is dc_logits_predict of it, its q
+ * is prob_q of it, its thresholds are dc_logits_decide of it, and no consumer changes.
+ *   view       (roll, flip) with 0 <= roll < W and flip in {0, 1}: view pixel (h, w) shows source pixel
+ *              src(h, w) = (flip ? H - 1 - h : h, (w + roll) mod W)
+ *   input      dc_input_view_hwc: out[n, h, w, j] = scale[j] * (sign[j] * x[n, src(h, w), channels[j]] - shift[j]), converted to the
+ *              activation dtype.  sign[j] is +1 or -1 (NULL: all +1) and is applied in physical units, in front of the normalisation.  The
+ *              expression is dc_input_normalize_hwc's with the source pixel permuted: the identity view with a NULL sign gives that
+ *              call's bits.  NHWC output only
+ *   member m   fp32 NCHW logits in VIEW coordinates, with the view and an optional weight per SOURCE column, wt[W] (uint16, at least 1;
+ *              NULL: 1).  For source pixel p take the three logits at the view pixel that shows p.  If they are not all finite (an
+ *              exponent of all ones) then bad[p] += 1 and nothing else happens at p.  Otherwise, with q = prob_q(l0, l1, l2) (csrc/
+ *              pixel_score.h, the chain of dc_prob_score and dc_logits_decide) and am the first maximum of (l0, l1, l2):
+ *              S_c[p] += wt[col(p)] * q_c, votes_am[p] += 1, and for m == 0 first[p] = am -- 3 where the pixel was not finite
+ *   state      uint32 [B][4][H][W]: the planes S_0, S_1, S_2 and one packed plane: bits 0-5, 6-11, 12-17 the votes of class 0, 1, 2,
+ *              bits 18-23 bad, bits 24-25 first.  Six bits: at most 63 members.  Member 0 STORES its contribution and the others add to
+ *              it, so nothing has to clear the state; one thread owns a pixel, so there are no atomics.  The caller keeps the sum of the
+ *              members' largest weights at or below 65535 (S < 2^32) and adds no 64th member: nn.ViewEnsemble refuses both
+ *   pool       dc_ensemble_pool, for every pixel with bad == 0: top is the first class with the largest S_c, and
+ *              L_c = (float) log((double) max(S_c, 1) / (double) S_top), division and log in fp64, one rounding to fp32.  So L_top is
+ *              0.0f exactly, S_c == S_top gives 0.0f as well, and S_c < S_top gives L_c < 0: the first maximum of L is the integer first
+ *              maximum of (S_0, S_1, S_2), ties included, and prob_q(L)_c stands within 0.75 of 65536 * max(S_c, 1) / sum_k max(S_k, 1).
+ *              A pixel with bad > 0 gets three NaNs, which dc_prob_score and dc_logits_decide count as not finite
+ *   logits_nchw  of dc_ensemble_pool: fp32 [B][3][H][W], the pooled forecast
+ *   rows       int64 [B][208], zeroed by the call for the samples below n_valid, in stream order: word 64 c + k the pixels of the frame
+ *              with exactly k votes for class c; word 192 + 4 i + j the pixels whose first is i and whose pooled class is j (3: not
+ *              finite on either side)
+ *   totals     int64 [208] += rows over the samples below n_valid; frames int64 [1] += n_valid.  Integer sums: the same however the
+ *              frames are cut into batches
+ * All three are streaming passes in dc_logits_decide's layout: a workgroup takes dc_ensemble_block's `pixels` consecutive pixels of one
+ * sample and ends.  view_normalize gives one 16-byte vector of an output pixel to a thread; where all file channels are taken in file
+ * order (channels NULL, Cfile a multiple of 4, x_hwc 16-byte aligned) the loads are 16 bytes wide too -- the roll moves whole pixels and
+ * the flip whole rows, so the alignment never breaks.  dc_ensemble_add: where W and roll are multiples of 4, logits and state 16-byte and
+ * col_weight 8-byte aligned, a thread owns four consecutive source pixels, whose view pixels are consecutive and aligned too
+ * (ensemble_add_vec); else 4-byte accesses (ensemble_add).  dc_ensemble_pool counts through cells in LDS, the pixels of a wave that share
+ * a cell by one lane, and one workgroup reduction with 64-bit atomics per non-zero cell; there are no per-pixel global atomics.
+ * Samples from n_valid on are neither read nor written, in any buffer; n_valid == 0 launches nothing; nothing synchronises; a failed
+ * argument check sets the message and launches nothing.  Bounds: 1 <= B <= 4095, 0 <= n_valid <= B, H * W <= 2^30, 0 <= roll < W,
+ * 0 <= member < 63, 1 <= members <= 63, pointers aligned to their element size (out as dc_input_normalize_hwc's).  dc_input_view_hwc
+ * takes all B samples.  dc_ensemble_block is a host function: the pixels one workgroup takes; tests derive shapes from it.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_ensemble_block(int* pixels);
+int dc_input_view_hwc(int dtype, int B, int H, int W, int Cfile, int C, const int* channels /*NULL: the first C*/,
+                      const float* sign /*NULL: all +1*/, const float* x_hwc, const float* shift, const float* scale, int roll, int flip,
+                      void* out, int ldo, void* stream);
+int dc_ensemble_add(int B, int n_valid, int H, int W, const float* logits_nchw, int roll, int flip,
+                    const uint16_t* col_weight /*NULL: 1*/, int member, uint32_t* state, void* stream);
+int dc_ensemble_pool(int B, int n_valid, int H, int W, int members, const uint32_t* state, float* logits_nchw, int64_t* rows /*[B][208]*/,
+                     int64_t* totals /*[208]*/, int64_t* frames /*[1]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -114,6 +114,17 @@ periodic columns) is kept only if it holds a pixel above the high one.  ``predic
 ``prediction_decided`` (uint8 [H, W]) and ``decision`` (int64 [12], nn.DECISION_COUNTS), and EVERYTHING downstream takes the decided mask:
 --event_filter (which then filters it), --events, --verify, --fss and the rest; --prob_skill keeps scoring the probabilities.
 ``summary.json`` gains ``decision`` (the thresholds as q and as probabilities, the connectivity, the counters' totals).
+With --ensemble_rolls S [S ...] and / or --ensemble_flip_lat, nn.ViewEnsemble pools the forecasts of several views of every batch on the
+device (test-time augmentation): the network pads the first and the last column with zeros while the grid is periodic, so a storm on
+longitude 0 is seen cut in two; a view rolled by S columns sees it whole.  Shift 0 is always member 0, the plain forward pass;
+--ensemble_flip_lat adds the north-south mirrored twin of every member, the file channels of --ensemble_negate (the meridional winds)
+with their sign reversed; --ensemble_seam_margin N fades every member out over the N columns next to its own seam (1: the plain mean).
+Every further view is made from the raw fields by nn.view_input, costs one more forward pass, and is pooled in q.  ``prediction`` stays
+the classifier's mask of the identity view; every output file gains ``prediction_ensemble`` (uint8 [H, W], the first maximum of the
+pooled logits), with --confidence ``confidence_ensemble``, and ``ensemble_rows`` (int64 [208]: the pixels with exactly k votes for class
+c at 64 c + k, the (identity class, pooled class) matrix at 192 + 4 i + j, 3 = not finite).  EVERYTHING downstream takes the pooled mask,
+and --decision_* and --prob_skill take the pooled logits in place of the classifier's.  ``summary.json`` gains ``ensemble`` (the views,
+the margin and nn.ViewEnsemble.decode's result).  The flags need the NHWC input pipeline (a channel count the MFMA stem takes).
 Single process, single device."""
 from __future__ import annotations
 
@@ -165,6 +176,10 @@ class _Parser(argparse.ArgumentParser):
         ns = super().parse_args(args, namespace)
         if hasattr(ns, "decision_high") and not (hasattr(ns, "decision_low") or hasattr(ns, "decision_from")):
             self.error("--decision_high needs --decision_low or --decision_from")
+        if hasattr(ns, "ensemble_negate") and not hasattr(ns, "ensemble_flip_lat"):
+            self.error("--ensemble_negate needs --ensemble_flip_lat")
+        if hasattr(ns, "ensemble_seam_margin") and not (hasattr(ns, "ensemble_rolls") or hasattr(ns, "ensemble_flip_lat")):
+            self.error("--ensemble_seam_margin needs --ensemble_rolls or --ensemble_flip_lat")
         return ns
 
 
@@ -320,6 +335,18 @@ def build_parser():
                      "thresholds of the prob_skill.h5 an earlier --prob_skill run wrote (typically on the validation split)")
     AP.add_argument("--decision_high", type=float, nargs=2, default=S, metavar=("TC", "AR"), help="with --decision_low or --decision_from: "
                     "hysteresis -- a connected region above the low threshold is kept only if it holds a pixel at or above this one")
+    # likewise the --ensemble_* flags (ENSEMBLE_DEFAULTS)
+    AP.add_argument("--ensemble_rolls", type=int, nargs="+", default=S, metavar="S", help="test-time augmentation on the device: also predict "
+                    "on the frame rolled by S columns (periodic longitudes; only the network's zero padding breaks that symmetry) and pool "
+                    "the views' probabilities.  Shift 0 is always member 0, the plain forward pass; every other view costs one more.  "
+                    "Datasets 'prediction_ensemble', 'ensemble_rows'; 'ensemble' in the summary; everything downstream takes the pooled "
+                    "mask, --decision_* and --prob_skill the pooled logits; 'prediction' stays the identity view's mask")
+    AP.add_argument("--ensemble_flip_lat", action="store_true", default=S, help="add the north-south mirrored twin of every ensemble member")
+    AP.add_argument("--ensemble_negate", type=int, nargs="+", default=S, metavar="C", help="with --ensemble_flip_lat: the file channels "
+                    "(among --channels) whose sign reverses in a mirrored view: the meridional wind components (none)")
+    AP.add_argument("--ensemble_seam_margin", type=int, default=S, metavar="N", help="with --ensemble_rolls or --ensemble_flip_lat: a member "
+                    "weighs min(d + 1, N) at a pixel d columns from the nearer edge of its own view, so that near a view's seam the other "
+                    "views decide (1: the plain mean)")
     AP.add_argument("--height", type=int, default=768)
     AP.add_argument("--width", type=int, default=1152)
     AP.add_argument("--max_inter_threads", type=int, default=4, help="Maximum number of concurrent readers")
@@ -564,6 +591,46 @@ def decision_summary(rule, records) -> dict:
                 counts=dict(zip(dnn.DECISION_COUNTS, totals)))
 
 
+ENSEMBLE_DEFAULTS = {"ensemble_rolls": None, "ensemble_flip_lat": False, "ensemble_negate": [], "ensemble_seam_margin": 1}
+
+
+def ensemble_options(pargs, width: int, channels):
+    """From the --ensemble_* flags (ENSEMBLE_DEFAULTS where one was not given), None where neither --ensemble_rolls nor
+    --ensemble_flip_lat was: {"views": the (roll, flip) pairs in member order -- (0, False) first, then the other shifts as given, then
+    the mirrored twin of each --, "margin", "negate": the file channels whose sign a mirrored view reverses}, validated against the width
+    and the selected file channels"""
+    a = argparse.Namespace(**{k: getattr(pargs, k, v) for k, v in ENSEMBLE_DEFAULTS.items()})
+    if a.ensemble_rolls is None and not a.ensemble_flip_lat:
+        if a.ensemble_negate or a.ensemble_seam_margin != 1:
+            raise ValueError("--ensemble_negate and --ensemble_seam_margin need --ensemble_rolls or --ensemble_flip_lat")
+        return None
+    rolls = [0]
+    for s in a.ensemble_rolls or []:
+        s = int(s)
+        if not 0 <= s < width:
+            raise ValueError(f"--ensemble_rolls: a shift must lie in [0, {width}), got {s}")
+        if s not in rolls:
+            rolls.append(s)
+    negate = [int(c) for c in a.ensemble_negate]
+    if negate and not a.ensemble_flip_lat:
+        raise ValueError("--ensemble_negate needs --ensemble_flip_lat")
+    if any(c not in list(channels) for c in negate):
+        raise ValueError(f"--ensemble_negate: every channel must be one of --channels {list(channels)}, got {negate}")
+    margin = int(a.ensemble_seam_margin)
+    views = [(s, False) for s in rolls] + ([(s, True) for s in rolls] if a.ensemble_flip_lat else [])
+    if len(views) > dnn.ENSEMBLE_MAX_MEMBERS or margin < 1 or margin * len(views) > dnn.ENSEMBLE_MAX_WEIGHT_SUM:
+        raise ValueError(f"--ensemble_*: at most {dnn.ENSEMBLE_MAX_MEMBERS} views, and --ensemble_seam_margin at least 1 with margin * views "
+                         f"at most {dnn.ENSEMBLE_MAX_WEIGHT_SUM}, got {len(views)} views and margin {margin}")
+    return {"views": views, "margin": margin, "negate": negate}
+
+
+def ensemble_summary(options: dict, state: dict) -> dict:
+    """the `ensemble` entry of summary.json: the views as [roll, flip] in member order, the margin, the negated channels and
+    nn.ViewEnsemble.decode of the running totals"""
+    return dict(dnn.ViewEnsemble.decode(state["totals"], state["frames"], len(options["views"])),
+                views=[[int(s), bool(f)] for s, f in options["views"]], seam_margin=options["margin"], negate=list(options["negate"]))
+
+
 def climatology_summary(by: str, frames, maps: dict, truth_maps=None, channels=()) -> dict:
     """the `climatology` entry of summary.json: the groups' names and frames and, per class, the area-weighted frequency of every group
     (None for a group without a frame); with --verify the same of the labels"""
@@ -677,7 +744,12 @@ def plot_name(base: str) -> str:
 
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
-                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=()):
+                 plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=(),
+                 ensemble: bool = False):
+        # --ensemble_*: the pooled mask, its confidence and the counters of nn.ViewEnsemble
+        self.emask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if ensemble else None
+        self.econf = torch.empty((B, H, W), dtype=torch.float32).pin_memory() if ensemble and confidence else None
+        self.erows = torch.empty((B, dnn.ENSEMBLE_ROW), dtype=torch.int64).pin_memory() if ensemble else None
         # --fss, --distance_skill, --displacement, --scale_skill, --prob_skill: per skill the buffers of its frame_rows(), under the
         # names of its FRAME_KEYS and in the skills' order, which is the order of their datasets in a mask file
         self.frames = {key: torch.empty((B, *t.shape[1:]), dtype=t.dtype).pin_memory()
@@ -747,6 +819,10 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             H, W = slot.mask.shape[1:]
                             extra = dict(extra or {}, event_shape=srows, event_shape_values=dnn.EventShape.values(srows, rows, H, W),
                                          event_shape_value_names=np.frombuffer(",".join(dnn.EVENT_SHAPE_VALUES).encode(), np.uint8).copy())
+                    if slot.emask is not None:
+                        extra = dict(extra or {}, prediction_ensemble=slot.emask[j].numpy(), ensemble_rows=slot.erows[j].numpy())
+                        if slot.econf is not None:
+                            extra["confidence_ensemble"] = slot.econf[j].numpy()
                     if slot.dmask is not None:
                         extra = dict(extra or {}, prediction_decided=slot.dmask[j].numpy(), decision=slot.dcounts[j].numpy())
                     if slot.fmask is not None:
@@ -824,16 +900,28 @@ def main(pargs) -> dict:
         efilter = dnn.EventFilter(dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device),
                                   min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
                                   min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect)
-    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence, events=events and not verify and efilter is None and decide is None,
+    # --ensemble_*: the views of every batch pooled into one logits tensor, which then stands where the classifier's stood
+    ens_options = ensemble_options(pargs, W, pargs.channels)
+    ens = ens_view = ens_sign = None
+    if ens_options is not None:
+        if layout != "nhwc":
+            raise ValueError("--ensemble_* needs the NHWC input pipeline: a --channels count the MFMA stem takes (a multiple of 8 in bf16, of 4 in fp32)")
+        ens = dnn.ViewEnsemble(B, H, W, device=device)
+        ens_view = torch.empty((B, H, W, len(pargs.channels)), dtype=dtype, device=device)       # every further view, one after the other
+        if ens_options["negate"]:
+            ens_sign = torch.tensor([-1.0 if c in ens_options["negate"] else 1.0 for c in pargs.channels], dtype=torch.float32, device=device)
+        ens_weights = [None if ens_options["margin"] == 1 else dnn.seam_weights(W, s, ens_options["margin"]) for s, _ in ens_options["views"]]
+    predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence,
+                              events=events and not verify and efilter is None and decide is None and ens is None,
                               event_connectivity=pargs.event_connectivity)
     # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
     matcher = dnn.EventMatcher(B, H, W, connectivity=pargs.event_connectivity, min_pixels=pargs.min_event_pixels,
                                min_cover=pargs.min_event_cover, device=device) if verify else None
     catalog = matcher.a if verify else predictor.catalog
-    predictor.store_logits = predictor.store_logits or decide is not None      # bf16 keeps the logits in registers unless asked
-    if events and catalog is None:                # a decided or filtered mask without --verify: a catalogue of its own for it
+    predictor.store_logits = predictor.store_logits or decide is not None or ens is not None   # bf16 keeps the logits in registers unless asked
+    if events and catalog is None:                # a pooled, decided or filtered mask without --verify: a catalogue of its own for it
         catalog = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
-    own_catalog = events and not verify and (efilter is not None or decide is not None)
+    own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
@@ -902,7 +990,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, decide is not None,
-                             frame_skills))
+                             frame_skills, ens is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -918,8 +1006,27 @@ def main(pargs) -> dict:
                 break
             mask = predictor(x, n_valid=nv)
             dmask = predictor.mask_buffer          # what everything downstream takes
+            logits = predictor.logits_buffer       # ... and what --decision_* and --prob_skill take
+            if ens is not None:
+                # the identity view's outputs leave first: the further views run through the same predictor and overwrite its buffers
+                slot.mask[:nv].copy_(mask, non_blocking=True)
+                if slot.conf is not None:
+                    slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
+                slot.counts[:nv].copy_(predictor.class_counts, non_blocking=True)
+                ens.begin()
+                for (shift, flip), weights in zip(ens_options["views"], ens_weights):
+                    if shift or flip:
+                        dnn.view_input(loader.raw, loader.channels, loader.shift, loader.scale, shift, flip, ens_sign if flip else None, ens_view)
+                        predictor(ens_view, n_valid=nv)
+                    ens.add(predictor.logits_buffer, shift, flip, weights, n_valid=nv)
+                logits = ens.pool()
+                dmask, econf, _ = dnn.predict_from_logits(logits, confidence=slot.econf is not None, n_valid=nv)
+                slot.emask[:nv].copy_(dmask[:nv], non_blocking=True)
+                if econf is not None:
+                    slot.econf[:nv].copy_(econf[:nv], non_blocking=True)
+                slot.erows[:nv].copy_(ens.frame_rows(), non_blocking=True)
             if decide is not None:
-                slot.dmask[:nv].copy_(decide(predictor.logits_buffer, n_valid=nv), non_blocking=True)
+                slot.dmask[:nv].copy_(decide(logits, n_valid=nv), non_blocking=True)
                 slot.dcounts[:nv].copy_(decide.counts(), non_blocking=True)
                 dmask = decide.mask_buffer
             if efilter is not None:
@@ -931,7 +1038,7 @@ def main(pargs) -> dict:
             if verify:
                 matcher(dmask, y, n_valid=nv)
             for skill in frame_skills:             # the mask skills take the mask, the probabilities' skill the stored logits
-                skill(predictor.logits_buffer if skill is prob else dmask, y, n_valid=nv)
+                skill(logits if skill is prob else dmask, y, n_valid=nv)
                 for key, rows in zip(skill.FRAME_KEYS, skill.frame_rows()):
                     slot.frames[key][:nv].copy_(rows, non_blocking=True)
             if eshape is not None:
@@ -951,10 +1058,11 @@ def main(pargs) -> dict:
                 clim(dmask, raw, groups=groups, n_valid=nv)
                 if clim_truth is not None:
                     clim_truth(y, raw, groups=groups, n_valid=nv)
-            slot.mask[:nv].copy_(mask, non_blocking=True)
-            if slot.conf is not None:
-                slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
-            slot.counts[:nv].copy_(predictor.class_counts, non_blocking=True)
+            if ens is None:
+                slot.mask[:nv].copy_(mask, non_blocking=True)
+                if slot.conf is not None:
+                    slot.conf[:nv].copy_(predictor.confidence, non_blocking=True)
+                slot.counts[:nv].copy_(predictor.class_counts, non_blocking=True)
             if slot.events is not None:
                 slot.events[:nv].copy_(catalog.table, non_blocking=True)
                 slot.ncomp[:nv].copy_(catalog.counts(), non_blocking=True)
@@ -986,6 +1094,7 @@ def main(pargs) -> dict:
     disp_state = disp.state() if disp is not None else None
     scale_state = scale.state() if scale is not None else None
     prob_state = prob.state() if prob is not None else None
+    ens_state = ens.state() if ens is not None else None
     elapsed = time.perf_counter() - t0
 
     records.sort(key=lambda r: r["file"])
@@ -994,6 +1103,8 @@ def main(pargs) -> dict:
     if events:
         summary["events"] = [sum(r["events"][j] for r in records) for j in range(2)]
         summary["events_overflowed_files"] = sum(1 for r in records if r["events_overflowed"])
+    if ens is not None:
+        summary["ensemble"] = ensemble_summary(ens_options, ens_state)
     if decide is not None:
         summary["decision"] = decision_summary(decide, records)
     if efilter is not None:
