@@ -427,6 +427,10 @@ class ArenaOptimizer:
                 self.param_groups[0][k] = v
         st = sd.get("state", {})
         self.step_count = 0
+        # a parameter without an entry has no state (a step-0 checkpoint has none at all): its moments start from zero, as in torch.optim,
+        # whatever this optimizer held before
+        self.m.zero_()
+        self.v.zero_()
         for i, p in enumerate(lay.params.values()):
             s = st.get(i, st.get(str(i)))
             if s is None:
