@@ -96,6 +96,8 @@ int dc_reset_options(void);
  *   view ensemble (dc_input_view_hwc, dc_ensemble_add, dc_ensemble_pool): view_normalize (the rolled, mirrored and normalised input);
  *     ensemble_add_vec (16-byte loads and stores: W and roll multiples of 4) or ensemble_add (4-byte accesses, any width and roll): one
  *     member into the state; ensemble_pool (the pooled logits, the vote counters and their running totals)
+ *   train-time augmentation (dc_augment_view_hwc): augment_view (a batch normalised with every sample in a view of its own, the label map
+ *     moved with it)
  *   distance-map verification (dc_distance_score): dist_vert (the row distances of four indicator fields, one packed word per pixel),
  *     dist_horz (the capped squared distance maps, the ring counters, the sums and the Baddeley term), dist_total (the running totals)
  *   displacement verification (dc_displacement_score): disp_pack (the four bit planes, the predicted pixels per row, the pixel counts),
@@ -1365,6 +1367,45 @@ int dc_ensemble_add(int B, int n_valid, int H, int W, const float* logits_nchw, 
                     const uint16_t* col_weight /*NULL: 1*/, int member, uint32_t* state, void* stream);
 int dc_ensemble_pool(int B, int n_valid, int H, int W, int members, const uint32_t* state, float* logits_nchw, int64_t* rows /*[B][208]*/,
                      int64_t* totals /*[208]*/, int64_t* frames /*[1]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Train-time augmentation (data.Augment, data.InputPipeline(augment=...); train.py --augment_roll / --augment_flip_lat / --augment_negate /
+ * --augment_seed): the two exact symmetries of the view ensemble above, applied while a training batch is staged, so that the network sees
+ * every sample at a longitude offset of its own and learns that the seam of the zero padding is nowhere in particular.  The reference
+ * shuffles its file list once and never again (data/cam_hdf5_dataset.py:39-41), so every epoch shows the same batches pixel for pixel;
+ * per-epoch views are the variety a long run gets.  ONE launch stages the whole batch: dc_input_view_hwc gives one view to all B samples,
+ * negates unconditionally and has no labels.
+ *   views_host HOST memory, int32 [B][2]: (roll_n, flip_n) of sample n with 0 <= roll_n < W and flip_n in {0, 1}.  View pixel (h, w) of
+ *              sample n shows source pixel src_n(h, w) = (flip_n ? H - 1 - h : h, (w + roll_n) mod W), the view ensemble's definition.
+ *              The table is read and checked BEFORE THE CALL RETURNS and travels, packed into one 32-bit word per sample, in the kernel
+ *              arguments (1 KB at B = 256): the device never indexes by a number the host has not range-checked, a row's word is uniform
+ *              over its workgroup and read by a scalar load, and there is no table in device memory, no extra copy, no pinned buffer.
+ *              The caller may reuse the array as soon as the call has returned.  Because a host pointer is read at call time the call is
+ *              NOT meant for dc_program_* recording (a replay would read whatever the array holds then, or a dead address); the input
+ *              pipeline is not part of the recorded step
+ *   data       out[n, h, w, j] = scale[j] * (s_nj * x[n, src_n(h, w), channels[j]] - shift[j]), converted to the activation dtype, NHWC
+ *              with leading dimension ldo.  s_nj = flip_sign[j] where flip_n is set and flip_sign is not NULL, else +1: only the mirrored
+ *              samples have their meridional winds negated, in physical units, in front of the normalisation
+ *   labels     labels_out[n, h, w] = labels_in[n, src_n(h, w)], int64 [B][H][W] both: the words are moved verbatim and not interpreted, so
+ *              an out-of-range label stays what it was, for the loss kernel to flag.  Both NULL: the data alone.  Never in place
+ *   bits       sample n of `out` is what dc_input_view_hwc writes for that sample alone with (roll_n, flip_n) and sign = flip_n ?
+ *              flip_sign : NULL; a batch of identity views is dc_input_normalize_hwc bit for bit (+-1 * v is exact, whether or not it
+ *              is contracted with the subtraction)
+ * The kernel (augment_view) has view_normalize's decomposition: blockIdx.y walks the B * H rows, a row of the view is a rotated row of the
+ * source, a thread takes one 16-byte vector of one output pixel.  Where all file channels are taken in file order (channels NULL, Cfile a
+ * multiple of 4, x_hwc 16-byte aligned) the loads are 16 bytes wide too -- the roll moves whole pixels and the flip whole rows, so the
+ * alignment never breaks; a channel selection gathers by 4-byte loads.  The workgroups of a row then move its labels by 8-byte words.  One
+ * streaming pass, 64 + 8 bytes in and 32 + 8 bytes out per pixel (bf16, 16 channels); no atomics, no LDS.
+ * Nothing synchronises; a failed argument check sets the message and launches nothing.  Refused: B outside [1, 256]; a view outside the
+ * ranges above; a dtype other than DC_F32 / DC_BF16; a NULL x_hwc, shift, scale, out or views_host; one label pointer without the other;
+ * labels_in == labels_out; a pointer not aligned to its element (out and ldo as dc_input_normalize_hwc's); Cfile < C; B * H >= 2^31 or
+ * H * W > 2^30.
+ * ------------------------------------------------------------------------------------------------ */
+int dc_augment_view_hwc(int dtype, int B, int H, int W, int Cfile, int C, const int* channels /*NULL: the first C*/,
+                        const float* flip_sign /*NULL: all +1*/, const float* x_hwc, const float* shift, const float* scale,
+                        const int32_t* views_host /*[B][2]: roll, flip -- HOST memory*/,
+                        const int64_t* labels_in /*[B][H][W] or NULL*/, int64_t* labels_out /*NULL iff labels_in is*/,
+                        void* out, int ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Image-pool branch helpers (deeplab_xception.py:425,449-450): AdaptiveAvgPool2d((1,1)), the 1x1 ->

@@ -13,6 +13,11 @@ consumes: the training step then contains no layout pass at all.  Reading is dou
 h5py is not available in every image: CamDataset decodes with h5py when it is installed and otherwise through `h5lite`, a ctypes
 binding of the HDF5 C library (contiguous fp32 payloads are pread() straight into the pinned staging buffer, several files in
 parallel).  The tests write small CAM5-shaped files with h5lite and read them back through the whole pipeline.
+
+Train-time augmentation (Augment, InputPipeline(augment=...), to_source): the grid is periodic in longitude while every convolution
+pads the first and the last column with zeros, and the file list is shuffled once, so every epoch shows the same batches.  With an
+Augment every training sample is staged at a longitude offset of its own and / or mirrored north-south with the meridional winds
+negated, the label map moved with it, by ONE kernel (dc_augment_view_hwc) in place of the normalise kernel and the direct label copy.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ import ctypes as C
 import os
 import queue
 import threading
+import zlib
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -198,10 +204,60 @@ class SyntheticHWC:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# train-time augmentation (host logic; the kernel is dc_augment_view_hwc)
+# ---------------------------------------------------------------------------------------------------------------------
+class Augment:
+    """Per-sample views of the training data: roll -- every sample at a longitude offset of its own, an exact symmetry of the periodic
+    grid that only the convolutions' zero padding breaks --, flip_lat -- every other sample (a fair coin) mirrored north-south, the FILE
+    channels of `negate` (the meridional winds) with their sign reversed in physical units.  The view (roll, flip) is nn.ViewEnsemble's:
+    view pixel (h, w) shows source pixel (H - 1 - h if flip else h, (w + roll) mod W).
+
+    draw() is a function of (seed, epoch, basename of the file) and nothing else: a sample's view does not depend on the batch it lands
+    in, on the reader threads, on the rank count or on virtual ranks (virtual rank v draws what real rank v of the larger job draws), a
+    resumed run redraws what the uninterrupted one drew, and switching one kind off does not move the other's draws."""
+
+    def __init__(self, roll: bool = False, flip_lat: bool = False, negate: Sequence[int] = (), seed: int = 0):
+        self.roll, self.flip_lat = bool(roll), bool(flip_lat)
+        self.negate = [int(c) for c in negate]
+        self.seed = int(seed)
+        if not (self.roll or self.flip_lat):
+            raise ValueError("Augment: enable roll, flip_lat or both")
+        if self.negate and not self.flip_lat:
+            raise ValueError("Augment: negate lists the channels a mirrored sample reverses: it needs flip_lat")
+        if self.seed < 0:
+            raise ValueError("Augment: seed must not be negative")
+
+    def draw(self, epoch: int, name: str, W: int) -> Tuple[int, int]:
+        """(roll, flip) of the file `name` in epoch `epoch` on a grid of W columns"""
+        g = np.random.default_rng([self.seed, int(epoch), zlib.crc32(os.path.basename(name).encode())])
+        r = int(g.integers(0, W))
+        f = int(g.integers(0, 2))                     # both always drawn, in this order
+        return (r if self.roll else 0, f if self.flip_lat else 0)
+
+
+def to_source(maps: torch.Tensor, views) -> torch.Tensor:
+    """Integer maps [B, H, W] in VIEW coordinates (the labels an augmented pipeline hands out, a prediction made from its batch) back in
+    SOURCE coordinates, out[n, src_n(h, w)] = maps[n, h, w] with views[n] = (roll_n, flip_n) (InputPipeline.views), so that they can be
+    drawn over InputPipeline.raw.  Host logic on a rare path (one plotted sample): torch.flip / torch.roll per sample on the tensor's own
+    device, CPU tensors included."""
+    views = np.asarray(views)
+    if maps.dim() != 3 or maps.is_floating_point() or views.shape != (maps.shape[0], 2):
+        raise ValueError("to_source: maps must be an integer tensor [B, H, W] and views [B, 2]")
+    out = torch.empty_like(maps)
+    for n, (roll, flip) in enumerate(views.tolist()):
+        m = maps[n].flip(0) if flip else maps[n]
+        out[n] = torch.roll(m, int(roll), dims=1)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # device half
 # ---------------------------------------------------------------------------------------------------------------------
 class _Slot:
-    def __init__(self, B, H, W, cfile, C_, dtype, device, nchw=False, labels=True):
+    def __init__(self, B, H, W, cfile, C_, dtype, device, nchw=False, labels=True, augment=False):
+        # augment: the labels land in a staging map in SOURCE coordinates, and dc_augment_view_hwc moves them into `label` with the data
+        self.label_stage = torch.empty((B, H, W), dtype=torch.int64, device=device) if augment else None
+        self.views = np.zeros((B, 2), np.int32) if augment else None
         self.data_host = torch.empty((B, H, W, cfile), dtype=torch.float32).pin_memory()
         self.label_host = torch.empty((B, H, W), dtype=torch.int64).pin_memory() if labels else None
         self.data_dev = torch.empty((B, H, W, cfile), dtype=torch.float32, device=device)
@@ -224,10 +280,16 @@ class InputPipeline:
 
     Over an unlabelled dataset (CamDataset(labels=False)) there are no label slots and the batches are (x, None, filenames).
     drop_last=False: the last batch may be ragged; its padding repeats the last sample, `filenames` lists the valid samples only and
-    `n_valid` holds the fill count of the batch handed out last."""
+    `n_valid` holds the fill count of the batch handed out last.
+
+    augment: an Augment (NHWC layout and a labelled dataset only).  Every sample is then staged in the view Augment.draw gives its file
+    in the epoch of the pass (set_epoch, else the count of passes started), x and labels alike, by one dc_augment_view_hwc on the copy
+    stream in place of the normalise kernel and the direct label copy; a padding slot of a ragged batch repeats the last sample and takes
+    its view.  `views` holds the (roll, flip) pairs of the batch handed out last; `raw` stays in SOURCE coordinates (to_source brings
+    labels and predictions back to it)."""
 
     def __init__(self, dataset, batch_size: int, dtype=torch.bfloat16, device=None, depth: int = 3, drop_last: bool = True,
-                 workers: int = 4, layout: str = "nhwc"):
+                 workers: int = 4, layout: str = "nhwc", augment: Optional[Augment] = None):
         if not torch.cuda.is_available():
             raise L.DeepcamHipError("InputPipeline needs a HIP device")
         self.ds, self.B, self.dtype = dataset, batch_size, dtype
@@ -243,7 +305,26 @@ class InputPipeline:
             raise ValueError(f"layout must be 'nhwc' or 'nchw', got {layout!r}")
         self.nchw = layout == "nchw"
         self.labels = bool(getattr(dataset, "labels", True))
-        self.slots = [_Slot(batch_size, H, W, cfile, self.C, dtype, self.device, self.nchw, self.labels) for _ in range(max(2, depth))]
+        self.augment = augment
+        self._next_epoch = 0
+        self.flip_sign = None
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise ValueError("augment must be a data.Augment or None")
+            if self.nchw:
+                raise ValueError("layout 'nchw' is not augmented: channel subsets that the MFMA stem does not take train without an Augment")
+            if not self.labels:
+                raise ValueError("an unlabelled dataset is not augmented: the augmentation belongs to training")
+            if not 1 <= batch_size <= 256:
+                raise ValueError(f"an augmented batch holds at most 256 samples (dc_augment_view_hwc), got {batch_size}")
+            stray = sorted(set(augment.negate) - set(dataset.channels))
+            if stray:
+                raise ValueError(f"Augment.negate: every channel must be one of the dataset's channels {list(dataset.channels)}, got {stray}")
+            if augment.negate:                        # +1 / -1 per SELECTED channel, applied to the mirrored samples only
+                self.flip_sign = torch.tensor([-1.0 if c in augment.negate else 1.0 for c in dataset.channels], dtype=torch.float32,
+                                              device=self.device)
+        self.slots = [_Slot(batch_size, H, W, cfile, self.C, dtype, self.device, self.nchw, self.labels, augment is not None)
+                      for _ in range(max(2, depth))]
         self.n_valid = 0
         self.shift = torch.from_numpy(np.asarray(dataset.data_shift, np.float32)).to(self.device)
         self.scale = torch.from_numpy(np.asarray(dataset.data_scale, np.float32)).to(self.device)
@@ -265,6 +346,16 @@ class InputPipeline:
         every file channel, before channel selection and normalisation); None before the first batch.  Valid until the next batch is
         requested, and ordered on the current stream by the same event as the batch itself."""
         return self._prev.data_dev if self._prev is not None else None
+
+    @property
+    def views(self) -> Optional[np.ndarray]:
+        """np.int32 [B, 2]: the (roll, flip) of every slot of the batch handed out last (a copy); None without an Augment and before the
+        first batch."""
+        return self._prev.views.copy() if self.augment is not None and self._prev is not None else None
+
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch of the next pass (Augment.draw's); the passes after it count on from there.  Without it: the count of passes started."""
+        self._next_epoch = int(epoch)
 
     def _reader(self, free_q: "queue.Queue", full_q: "queue.Queue", stop: "threading.Event"):
         from concurrent.futures import ThreadPoolExecutor
@@ -304,6 +395,8 @@ class InputPipeline:
             self._reader_thread.join()
             self._reader_thread = None
         self._prev = None
+        epoch = self._next_epoch                      # of this pass (Augment.draw); the next pass is the next epoch unless set_epoch says otherwise
+        self._next_epoch = epoch + 1
         free_q: "queue.Queue" = queue.Queue()
         full_q: "queue.Queue" = queue.Queue()
         stop = threading.Event()
@@ -324,6 +417,21 @@ class InputPipeline:
                 return False
             if isinstance(item, BaseException):
                 raise item
+            if self.augment is not None:
+                # the views of the slot's samples; a padding slot repeats the last sample and takes its view.  The table is host memory
+                # that the call reads before it returns.
+                for j in range(self.B):
+                    item.views[j] = self.augment.draw(epoch, item.names[min(j, len(item.names) - 1)], self.W)
+                with torch.cuda.stream(self.copy_stream):
+                    item.data_dev.copy_(item.data_host, non_blocking=True)
+                    item.label_stage.copy_(item.label_host, non_blocking=True)
+                    L.call("dc_augment_view_hwc", self.dt, self.B, self.H, self.W, self.cfile, self.C, L.dptr(self.channels),
+                           L.dptr(self.flip_sign), L.dptr(item.data_dev), L.dptr(self.shift), L.dptr(self.scale),
+                           C.c_void_p(item.views.ctypes.data), L.dptr(item.label_stage), L.dptr(item.label), L.dptr(item.x), self.C,
+                           C.c_void_p(self.copy_stream.cuda_stream))
+                    item.ready.record(self.copy_stream)
+                staged.append(item)
+                return True
             with torch.cuda.stream(self.copy_stream):
                 item.data_dev.copy_(item.data_host, non_blocking=True)
                 if self.labels:

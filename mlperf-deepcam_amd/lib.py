@@ -209,6 +209,7 @@ _SIGS = {
     "dc_input_view_hwc": (I, [I, I, I, I, I, I, P, P, P, P, P, I, I, P, I, P]),
     "dc_ensemble_add": (I, [I, I, I, I, P, I, I, P, I, P, P]),
     "dc_ensemble_pool": (I, [I, I, I, I, I, P, P, P, P, P, P]),
+    "dc_augment_view_hwc": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P]),
     "dc_avgpool_fwd": (I, [I, I, I, I, P, I, P, P]),
     "dc_avgpool_bwd_add": (I, [I, I, I, I, P, P, I, P]),
     "dc_broadcast_hw": (I, [I, I, I, I, P, P, I, P]),

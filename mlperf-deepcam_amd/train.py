@@ -12,7 +12,9 @@ h5lite), or over synthetic HWC fields with ``--synthetic_samples N``.
 Extra flags (not in the reference): --wireup_method env|single, --dtype, --synthetic_samples, --synthetic_learnable,
 --height/--width, --max_steps, --validation_batch_size (above 1: nn.ValStep, the validation pass in batches with its three sums kept on
 the device), --virtual_ranks K (process r of R acts as global ranks r*K .. r*K+K-1 of an R*K-rank job: same sample assignment, K
-micro-batches per step with their gradients summed on the device, one optimizer update; nn.TrainStep(virtual_ranks=K)).
+micro-batches per step with their gradients summed on the device, one optimizer update; nn.TrainStep(virtual_ranks=K)),
+--augment_roll / --augment_flip_lat / --augment_negate C [C ...] / --augment_seed N (data.Augment: every training sample at a longitude
+offset of its own and / or mirrored north-south, drawn per epoch and file, staged by one kernel; validation is never augmented).
 """
 from __future__ import annotations
 
@@ -105,8 +107,18 @@ def check_amp_state(state) -> None:
             raise ValueError(f"checkpoint['amp'][{k!r}] is not an apex loss-scaler entry")
 
 
+class _Parser(ap.ArgumentParser):
+    """the check that spans two flags"""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.augment_negate and not ns.augment_flip_lat:
+            self.error("--augment_negate needs --augment_flip_lat")
+        return ns
+
+
 def build_parser():
-    AP = ap.ArgumentParser()
+    AP = _Parser()
     AP.add_argument("--wireup_method", type=str, default="nccl-openmpi",
                     choices=["nccl-openmpi", "nccl-slurm", "nccl-slurm-pmi", "mpi", "env", "single"], help="Specify what is used for wiring up the ranks")
     AP.add_argument("--wandb_certdir", type=str, default="/opt/certs", help="accepted for compatibility; W&B is out of scope")
@@ -152,6 +164,12 @@ def build_parser():
     AP.add_argument("--plots", action="store_true",
                     help="rank 0 writes <output_dir>/plots/training-*.png and validation-*.png at the two visualisation frequencies: the first "
                     "input channel with the predicted classes outlined, above the same field with the labelled ones")
+    AP.add_argument("--augment_roll", action="store_true",
+                    help="training data only: every sample at a longitude offset of its own, drawn per epoch and file (data.Augment)")
+    AP.add_argument("--augment_flip_lat", action="store_true", help="training data only: every other sample mirrored north-south")
+    AP.add_argument("--augment_negate", type=int, nargs="+", default=[], metavar="C",
+                    help="with --augment_flip_lat: the file channels whose sign a mirrored sample reverses (the meridional winds)")
+    AP.add_argument("--augment_seed", type=int, default=0, help="seed of the augmentation's draws")
     return AP
 
 
@@ -213,6 +231,15 @@ def main(pargs):
     logger.log_event(key="opt_learning_rate_warmup_steps", value=pargs.lr_warmup_steps)
     logger.log_event(key="opt_learning_rate_warmup_factor", value=pargs.lr_warmup_factor)
     logger.log_event(key="opt_epsilon", value=pargs.adam_eps)
+    # train-time augmentation (data.Augment): the training loader only, validation is never augmented.  A run without the flags logs
+    # and issues what it always did.
+    augment = None
+    if pargs.augment_negate and not pargs.augment_flip_lat:
+        raise ValueError("--augment_negate needs --augment_flip_lat")
+    if pargs.augment_roll or pargs.augment_flip_lat:
+        augment = ddata.Augment(roll=pargs.augment_roll, flip_lat=pargs.augment_flip_lat, negate=pargs.augment_negate, seed=pargs.augment_seed)
+        logger.log_event(key="data_augmentation", value={"roll": augment.roll, "flip_lat": augment.flip_lat, "negate": augment.negate,
+                                                         "seed": augment.seed})
 
     dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[pargs.dtype] if pargs.dtype else \
         (torch.float32 if pargs.amp_opt_level == "O0" else torch.bfloat16)
@@ -267,7 +294,11 @@ def main(pargs):
     # channel counts the MFMA stem does not take go through the direct stem kernel, which reads the reference's NCHW fp32 batch
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     # (with virtual ranks a batch holds the K micro-batches of one step, rank after rank: data.shard_files_virtual)
-    train_loader = ddata.InputPipeline(train_set, K * B, dtype=dtype, device=device, layout=layout)
+    if augment is not None and layout == "nchw":
+        raise ValueError(f"--augment_roll / --augment_flip_lat need a channel count the MFMA stem takes (a multiple of "
+                         f"{8 if dtype == torch.bfloat16 else 4} for this dtype): --channels selects {len(pargs.channels)}, whose batches go "
+                         "through the NCHW path, which is not augmented")
+    train_loader = ddata.InputPipeline(train_set, K * B, dtype=dtype, device=device, layout=layout, augment=augment)
     VB = pargs.validation_batch_size
     if VB < 1:
         raise ValueError("--validation_batch_size must be at least 1")
@@ -295,6 +326,7 @@ def main(pargs):
 
     while True:
         logger.log_start(key="epoch_start", metadata={"epoch_num": epoch + 1, "step_num": step}, sync=True)
+        train_loader.set_epoch(epoch)                              # the epoch of the augmentation's draws: a resumed run redraws them
         for inputs, label, filename in train_loader:
             train_step(inputs, label)                          # forward, loss, backward (+all-reduce), optimizer.step
             step += 1
@@ -302,7 +334,12 @@ def main(pargs):
                 current_lr = scheduler.get_last_lr()[0]
                 scheduler.step()
             if plotter is not None and tvf > 0 and step % tvf == 0:
-                plotter.plot("training", train_loader.raw, train_step.pred, label, filename)
+                pred_now, label_now = train_step.pred, label
+                if augment is not None:
+                    # the picture stays the raw field with both outlines in Earth coordinates: .raw is in source coordinates
+                    views_now = train_loader.views
+                    pred_now, label_now = ddata.to_source(pred_now, views_now), ddata.to_source(label_now, views_now)
+                plotter.plot("training", train_loader.raw, pred_now, label_now, filename)
             if step % pargs.logging_frequency == 0:
                 loss_now = train_step.loss()
                 # the fused loss kernel turns a label outside [0, 3) into NaN (the reference's CrossEntropyLoss raises on it,
