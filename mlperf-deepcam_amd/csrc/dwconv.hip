@@ -2,7 +2,9 @@
 // One lane owns one 16-byte channel group (8 bf16 / 4 f32 channels) so every global access is a full vector and
 // a wave covers up to 1 KiB of contiguous channels; each thread walks PX output pixels along W with the nine
 // per-channel weights held in registers.  Forward / data-gradient read the weights repacked as [9][C] fp32.
-#include <string.h>
+#include <stdio.h>
+
+#include <initializer_list>
 
 #include "common.h"
 #include "dwtile.h"
@@ -419,42 +421,66 @@ static int dw_pix_per_block(long P) {
   return (int)ppb;
 }
 
+// The one routing decision (dwtile.h): the queries the engine sizes its slabs from and the dispatchers read the same answer.
+DwRoute dw_route(DwDir dir, int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
+  if ((dtype != DC_BF16 && dtype != DC_F32) || C <= 0 || N <= 0 || Hi <= 0 || Wi <= 0) return {DW_NONE, 0};
+  if (stride == 1 && (dil == 1 || dil == 2)) {
+    if (!g_options.dw_tile) return {DW_WIN, 0};
+    // the persistent pipelined kernel serves the data gradients (52.0 -> 41.5 us with BatchNorm sums and weight gradient on the 728-channel
+    // layers at local batch 8); the forward pass stays on the tiled kernel unless option "dw_pipe" = 2 (23.4 vs 24.1 us plain, 34.5 vs
+    // 31.7 us with the BatchNorm applied on load: its in-place transform pass costs eight waves more than it costs three co-resident
+    // workgroups).  It is not given tensors of 2^31 pixels or more: the tiled launcher gets those calls, and refuses them.
+    const bool piped = dir == DW_DGRAD || (dir == DW_FWD && dw_pipe_forward());
+    const int pr = piped && (long)N * Hi * Wi < (1L << 31) ? dw_pipe_rows(dtype, C, dil, N, Hi, Wi) : 0;   // one slab row per workgroup
+    if (pr > 0) return {DW_PIPE, pr};
+    return {DW_TILE, dw_tile_rows(dtype, C, N, Hi, Wi)};
+  }
+  // the stride-2 data-gradient kernel walks its tiles: one row per workgroup
+  if (stride == 2 && dil == 1 && g_options.dw_tile) return {DW_TILE_S2, dw_tile_s2_dgrad_rows(dtype, C, N, Hi, Wi)};
+  return {DW_REG, 0};
+}
+
 }  // namespace dc
 
 using namespace dc;
 
-template <typename T, int MODE>
-static int launch_dw(const void* in, int ldin, const float* w, const void* addend, int ldadd, void* out, int ldout,
-                     int N, int Hin, int Win, int Hout, int Wout, int C, int stride, int dil, hipStream_t st,
-                     const float* pscale = nullptr, const float* pshift = nullptr, int prelu = 0) {
-  const long total = (long)N * Hout * ((Wout + DW_PX - 1) / DW_PX) * (C / Elem<T>::kPerVec);
+// the generic kernel: any stride and dilation
+static int launch_dw(const DwCall& c) {
+  const int Ho = dw_out(c.Hi, c.stride, c.dil), Wo = dw_out(c.Wi, c.stride, c.dil);
+  // forward: x [Hi,Wi] -> y [Ho,Wo]; data gradient: gather from dy [Ho,Wo] into dx [Hi,Wi]
+  const int Hin = c.flip ? Ho : c.Hi, Win = c.flip ? Wo : c.Wi, Hout = c.flip ? c.Hi : Ho, Wout = c.flip ? c.Wi : Wo;
+  const long total = (long)c.N * Hout * ((Wout + DW_PX - 1) / DW_PX) * (c.C / (c.dtype == DC_BF16 ? 8 : 4));
   long blocks = (total + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL((dw_kernel<T, MODE>), dim3((int)blocks), dim3(256), 0, st, (const T*)in, ldin, w,
-                     (const T*)addend, ldadd, (T*)out, ldout, N, Hin, Win, Hout, Wout, C, stride, dil, pscale, pshift, prelu);
-  DC_LAUNCHED(MODE == 0 ? "dw_reg_fwd" : "dw_reg_dgrad");
+#define DW(TT, MODE) hipLaunchKernelGGL((dw_kernel<TT, MODE>), dim3((int)blocks), dim3(256), 0, c.st, (const TT*)c.in, c.ldin, c.wp, (const TT*)c.addend, c.ldadd, (TT*)c.out, c.ldout, c.N, Hin, Win, Hout, Wout, c.C, c.stride, c.dil, c.pscale, c.pshift, c.prelu)
+  if (c.dtype == DC_BF16) { if (c.flip) DW(bf16, 1); else DW(bf16, 0); }
+  else                    { if (c.flip) DW(float, 1); else DW(float, 0); }
+#undef DW
+  DC_LAUNCHED(c.flip ? "dw_reg_dgrad" : "dw_reg_fwd");
   return 0;
 }
 
-static int launch_dw_s1(int dtype, int dil, bool flip, const void* in, int ldin, const float* wp, const void* addend, int ldadd,
-                        void* out, int ldout, int N, int H, int W, int C, hipStream_t st, const float* pscale = nullptr,
-                        const float* pshift = nullptr, int prelu = 0) {
-  if (g_options.dw_tile) return launch_dw_tile(dtype, dil, flip, in, ldin, wp, addend, ldadd, out, ldout, N, H, W, C, st, pscale, pshift, prelu, nullptr);
-  const int kpv = dtype == DC_BF16 ? 8 : 4;
-  const long total = (long)N * H * ((W + DW_PX - 1) / DW_PX) * (C / kpv);
+// the stride-1 register-window kernels (option "dw_tile" = 0)
+static int launch_dw_s1(const DwCall& c) {
+  const long total = (long)c.N * c.Hi * ((c.Wi + DW_PX - 1) / DW_PX) * (c.C / (c.dtype == DC_BF16 ? 8 : 4));
   DC_REQUIRE(total < (1L << 31), "dc_dwconv: tensor too large for the stride-1 fast path");
   dim3 grid((unsigned)((total + 255) / 256));
-#define DW_S1(TT, D, F) hipLaunchKernelGGL((dw_s1_kernel<TT, D, F>), grid, dim3(256), 0, st, (const TT*)in, ldin, wp, (const TT*)addend, ldadd, (TT*)out, ldout, N, H, W, C, pscale, pshift, prelu)
-  if (dtype == DC_BF16) {
-    if (dil == 1) { if (flip) DW_S1(bf16, 1, true); else DW_S1(bf16, 1, false); }
-    else          { if (flip) DW_S1(bf16, 2, true); else DW_S1(bf16, 2, false); }
-  } else {
-    if (dil == 1) { if (flip) DW_S1(float, 1, true); else DW_S1(float, 1, false); }
-    else          { if (flip) DW_S1(float, 2, true); else DW_S1(float, 2, false); }
-  }
+#define DW_S1(TT, D, F) hipLaunchKernelGGL((dw_s1_kernel<TT, D, F>), grid, dim3(256), 0, c.st, (const TT*)c.in, c.ldin, c.wp, (const TT*)c.addend, c.ldadd, (TT*)c.out, c.ldout, c.N, c.Hi, c.Wi, c.C, c.pscale, c.pshift, c.prelu)
+  DW_S1_CASES(c, DW_S1)
 #undef DW_S1
-  DC_LAUNCHED(flip ? "dw_win_dgrad" : "dw_win_fwd");
+  DC_LAUNCHED(c.flip ? "dw_win_dgrad" : "dw_win_fwd");
   return 0;
+}
+
+static int dw_dispatch(const DwCall& c) {
+  switch (dw_route(c.flip ? DW_DGRAD : DW_FWD, c.dtype, c.C, c.stride, c.dil, c.N, c.Hi, c.Wi).family) {
+    case DW_PIPE: return launch_dw_pipe(c);
+    case DW_TILE: return launch_dw_tile(c);
+    case DW_TILE_S2: return launch_dw_tile_s2(c);
+    case DW_WIN: return launch_dw_s1(c);
+    case DW_REG: return launch_dw(c);
+    default: return dc_fail("dc_dwconv: shape not served", __FILE__, __LINE__);
+  }
 }
 
 static int dw_check(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
@@ -462,6 +488,46 @@ static int dw_check(int dtype, int C, int stride, int dil, int N, int Hi, int Wi
   DC_REQUIRE(stride == 1 || stride == 2, "dc_dwconv: stride must be 1 or 2");
   DC_REQUIRE(dil >= 1 && C > 0 && N > 0 && Hi > 0 && Wi > 0, "dc_dwconv: bad shape");
   return 0;
+}
+
+// The argument check of the forward and data-gradient entry points: the shape; the views of in ("x" / "dy") and out ("y" / "dx"), of the
+// rider's tensor c.bs.y under the name the entry point gives it (null: the call has none), of the residual BatchNorm's input and of an
+// addend that is there; then the entry point's own requirements in order, each with its refusal.  `name`: the entry point in view errors.
+struct DwReq { bool ok; const char* msg; };
+static int dw_check_call(const char* name, const DwCall& c, const char* rider, std::initializer_list<DwReq> reqs) {
+  const auto view = [&](const void* p, int ld, const char* what) {
+    char full[96];
+    snprintf(full, sizeof(full), "%s %s", name, what);
+    return dc_check_view(p, ld, c.C, c.dtype, full);
+  };
+  int e = dw_check(c.dtype, c.C, c.stride, c.dil, c.N, c.Hi, c.Wi);
+  if (!e) e = view(c.in, c.ldin, c.flip ? "dy" : "x");
+  if (!e) e = view(c.out, c.ldout, c.flip ? "dx" : "y");
+  if (!e && rider != nullptr) e = view(c.bs.y, c.bs.ldy, rider);
+  if (!e && c.res.on()) e = view(c.res.y, c.res.ldy, "ybn");
+  if (!e && c.addend != nullptr) e = view(c.addend, c.ldadd, "addend");
+  for (const DwReq& r : reqs)
+    if (!e && !r.ok) e = dc_fail(r.msg, __FILE__, __LINE__);
+  return e;
+}
+
+// a call's shape, in the order every entry point of the C ABI lists it, its direction and its stream
+static DwCall dw_call(bool flip, int dtype, int C, int stride, int dil, int N, int Hi, int Wi, void* stream) {
+  DwCall c;
+  c.flip = flip; c.dtype = dtype; c.C = C; c.stride = stride; c.dil = dil; c.N = N; c.Hi = Hi; c.Wi = Wi; c.st = (hipStream_t)stream;
+  return c;
+}
+
+// The riders of a data gradient.  bn_rider: the sums of the BatchNorm in front of the layer (input ybn; a SUM ROW when sum_row) and, with
+// wslab, this layer's weight-gradient rows, its forward input being act(ybn*mscale + mshift).  wgrad_rider: the weight-gradient rows alone,
+// the forward input being the stored x, or act(x*pscale + pshift) of it.  (DwBnStats in member order: y, ldy, mean, invstd, mscale, mshift, relu,
+// slab, rows, wslab)
+static DwBnStats bn_rider(const void* ybn, int ldybn, const float* mean, const float* invstd, const float* mscale, const float* mshift, int relu,
+                          float* slab, float* wslab = nullptr, bool sum_row = false) {
+  return {ybn, ldybn, mean, invstd, mscale, mshift, relu ? 1 : 0, slab, sum_row ? SUM_ROW : 0, wslab};
+}
+static DwBnStats wgrad_rider(const void* x, int ldx, const float* pscale, const float* pshift, int prelu, float* wslab) {
+  return {x, ldx, nullptr, nullptr, pscale, pshift, (pscale != nullptr && prelu) ? 1 : 0, nullptr, 0, wslab};
 }
 
 extern "C" int dc_dwconv_pack_weights(int C, const float* master, float* packed, void* stream) {
@@ -475,139 +541,103 @@ extern "C" int dc_dwconv_pack_weights(int C, const float* master, float* packed,
 extern "C" int dc_dwconv_fwd(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* x, int ldx,
                              const float* w, void* y, int ldy, const float* pscale, const float* pshift, int prelu,
                              void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(x, ldx, C, dtype, "dc_dwconv_fwd x")) return e;
-  if (int e = dc_check_view(y, ldy, C, dtype, "dc_dwconv_fwd y")) return e;
-  DC_REQUIRE(w != nullptr, "dc_dwconv_fwd: null weights");
-  const int Ho = dw_out(Hi, stride, dil), Wo = dw_out(Wi, stride, dil);
-  hipStream_t st = (hipStream_t)stream;
-  DC_REQUIRE((pscale == nullptr) == (pshift == nullptr), "dc_dwconv_fwd: pscale and pshift go together");
-  if (stride == 1 && (dil == 1 || dil == 2)) return launch_dw_s1(dtype, dil, false, x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, C, st, pscale, pshift, prelu);
-  if (stride == 2 && dil == 1 && g_options.dw_tile)
-    return launch_dw_tile_s2(dtype, 0, N, Hi, Wi, C, x, ldx, w, nullptr, 0, y, ldy, nullptr, nullptr, st, pscale, pshift, prelu);
-  return dtype == DC_BF16 ? launch_dw<bf16, 0>(x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, Ho, Wo, C, stride, dil, st, pscale, pshift, prelu)
-                          : launch_dw<float, 0>(x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, Ho, Wo, C, stride, dil, st, pscale, pshift, prelu);
+  DwCall c = dw_call(false, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = x; c.ldin = ldx; c.wp = w; c.out = y; c.ldout = ldy; c.pscale = pscale; c.pshift = pshift; c.prelu = prelu;
+  if (int e = dw_check_call("dc_dwconv_fwd", c, nullptr, {{w != nullptr, "dc_dwconv_fwd: null weights"},
+                            {(pscale == nullptr) == (pshift == nullptr), "dc_dwconv_fwd: pscale and pshift go together"}})) return e;
+  return dw_dispatch(c);
 }
 
 // dc_dwconv_fwd reading through a BatchNorm(+ReLU) whose finalize it runs itself: the producer left a SHORT slab of partial sums
 // (rows <= dc_bn_bwd_apply_fin_max_rows()), every workgroup sums it for its own channels while its halo tile travels (same order, same bits as
 // dc_bn_finalize), the workgroups of pixel tile 0 store scale / shift / save_mean / save_invstd and the running statistics.
 extern "C" int dc_dwconv_fwd_fin_ok(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  return g_options.dw_tile && !dw_pipe_forward() && stride == 1 && (dil == 1 || dil == 2) && (dtype == DC_BF16 || dtype == DC_F32) &&
-         C % (dtype == DC_BF16 ? 8 : 4) == 0;
+  return !dw_pipe_forward() && dw_route(DW_FWD, dtype, C, stride, dil, N, Hi, Wi).family == DW_TILE && C % (dtype == DC_BF16 ? 8 : 4) == 0;
 }
 extern "C" int dc_dwconv_fwd_fin(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* x, int ldx, const float* w,
                                  void* y, int ldy, int prelu, long count, const float* slab, int rows, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
                                  float* scale, float* shift, float* save_mean, float* save_invstd, void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(x, ldx, C, dtype, "dc_dwconv_fwd_fin x")) return e;
-  if (int e = dc_check_view(y, ldy, C, dtype, "dc_dwconv_fwd_fin y")) return e;
-  DC_REQUIRE(w && slab && gamma && beta && scale && shift && (rows > 0 || rows == SUM_ROW), "dc_dwconv_fwd_fin: null argument");
-  DC_REQUIRE(((uintptr_t)slab & 15) == 0, "dc_dwconv_fwd_fin: the slab is read with 16-byte loads (16-byte aligned)");
-  DC_REQUIRE(dc_dwconv_fwd_fin_ok(dtype, C, stride, dil, N, Hi, Wi), "dc_dwconv_fwd_fin: shape not served (dc_dwconv_fwd_fin_ok)");
-  if (count <= 1) return dc_fail("Expected more than 1 value per channel when training", __FILE__, __LINE__);
+  DwCall c = dw_call(false, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = x; c.ldin = ldx; c.wp = w; c.out = y; c.ldout = ldy; c.prelu = prelu;
+  if (int e = dw_check_call("dc_dwconv_fwd_fin", c, nullptr,
+                            {{w && slab && gamma && beta && scale && shift && (rows > 0 || rows == SUM_ROW), "dc_dwconv_fwd_fin: null argument"},
+                             {((uintptr_t)slab & 15) == 0, "dc_dwconv_fwd_fin: the slab is read with 16-byte loads (16-byte aligned)"},
+                             {dc_dwconv_fwd_fin_ok(dtype, C, stride, dil, N, Hi, Wi) != 0, "dc_dwconv_fwd_fin: shape not served (dc_dwconv_fwd_fin_ok)"},
+                             {count > 1, "Expected more than 1 value per channel when training"}})) return e;
   const BnFinArgs a = bn_fin_args(C, count, slab, rows, 0, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
                                   shift, save_mean, save_invstd);
-  return launch_dw_tile(dtype, dil, false, x, ldx, w, nullptr, 0, y, ldy, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, prelu, nullptr, &a);
+  c.fin = &a;
+  return dw_dispatch(c);
 }
 
 extern "C" int dc_dwconv_dgrad(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                const float* w, const void* addend, int ldadd, void* dx, int lddx, void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad dx")) return e;
-  if (addend != nullptr)
-    if (int e = dc_check_view(addend, ldadd, C, dtype, "dc_dwconv_dgrad addend")) return e;
-  DC_REQUIRE(w != nullptr, "dc_dwconv_dgrad: null weights");
-  const int Ho = dw_out(Hi, stride, dil), Wo = dw_out(Wi, stride, dil);
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1 && (dil == 1 || dil == 2)) return launch_dw_s1(dtype, dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, st);
-  if (stride == 2 && dil == 1 && g_options.dw_tile)
-    return launch_dw_tile_s2(dtype, 1, N, Hi, Wi, C, dy, lddy, w, addend, ldadd, dx, lddx, nullptr, nullptr, st);
-  // gather from dy [Ho,Wo] into dx [Hi,Wi]
-  return dtype == DC_BF16 ? launch_dw<bf16, 1>(dy, lddy, w, addend, ldadd, dx, lddx, N, Ho, Wo, Hi, Wi, C, stride, dil, st)
-                          : launch_dw<float, 1>(dy, lddy, w, addend, ldadd, dx, lddx, N, Ho, Wo, Hi, Wi, C, stride, dil, st);
+  DwCall c = dw_call(true, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = dy; c.ldin = lddy; c.wp = w; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldout = lddx;
+  if (int e = dw_check_call("dc_dwconv_dgrad", c, nullptr, {{w != nullptr, "dc_dwconv_dgrad: null weights"}})) return e;
+  return dw_dispatch(c);
 }
 
+// slab rows of the BatchNorm sums that ride along with the data gradient; 0: the register kernels serve the shape, they take no riders
 extern "C" int dc_dwconv_dgrad_bnstats_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_options.dw_tile || (dtype != DC_BF16 && dtype != DC_F32) || C <= 0 || N <= 0) return 0;
-  if (stride == 1 && (dil == 1 || dil == 2)) {
-    const int pr = dw_pipe_rows(dtype, C, dil, N, Hi, Wi);    // persistent kernel (dwpipe.hip): one slab row per workgroup
-    return pr > 0 ? pr : dw_tile_rows(dtype, C, N, Hi, Wi);
-  }
-  if (stride == 2 && dil == 1) return dw_tile_s2_dgrad_rows(dtype, C, N, Hi, Wi);
-  return 0;
+  return dw_route(DW_DGRAD, dtype, C, stride, dil, N, Hi, Wi).rows;
 }
 
 extern "C" int dc_dwconv_dgrad_bnstats(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                        const float* w, void* dx, int lddx, const void* ybn, int ldybn, const float* save_mean,
                                        const float* save_invstd, const float* mscale, const float* mshift, int relu, float* slab,
                                        void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad_bnstats dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad_bnstats dx")) return e;
-  if (int e = dc_check_view(ybn, ldybn, C, dtype, "dc_dwconv_dgrad_bnstats y")) return e;
-  DC_REQUIRE(w && save_mean && save_invstd && slab, "dc_dwconv_dgrad_bnstats: null argument");
-  DC_REQUIRE(!relu || (mscale && mshift), "dc_dwconv_dgrad_bnstats: the ReLU mask needs the forward scale / shift vectors");
-  DC_REQUIRE(dc_dwconv_dgrad_bnstats_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_bnstats: shape not served by the tiled kernels");
-  DwBnStats bs;
-  bs.y = ybn; bs.ldy = ldybn; bs.mean = save_mean; bs.invstd = save_invstd; bs.mscale = mscale; bs.mshift = mshift; bs.relu = relu ? 1 : 0;
-  bs.slab = slab; bs.rows = 0; bs.wslab = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) return launch_dw_tile(dtype, dil, true, dy, lddy, w, nullptr, 0, dx, lddx, N, Hi, Wi, C, st, nullptr, nullptr, 0, &bs);
-  return launch_dw_tile_s2(dtype, 1, N, Hi, Wi, C, dy, lddy, w, nullptr, 0, dx, lddx, nullptr, nullptr, st, nullptr, nullptr, 0, &bs);
+  DwCall c = dw_call(true, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = dy; c.ldin = lddy; c.wp = w; c.out = dx; c.ldout = lddx;
+  c.bs = bn_rider(ybn, ldybn, save_mean, save_invstd, mscale, mshift, relu, slab);
+  if (int e = dw_check_call("dc_dwconv_dgrad_bnstats", c, "y", {{w && save_mean && save_invstd && slab, "dc_dwconv_dgrad_bnstats: null argument"},
+                             {!relu || (mscale && mshift), "dc_dwconv_dgrad_bnstats: the ReLU mask needs the forward scale / shift vectors"},
+                             {dc_dwconv_dgrad_bnstats_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_bnstats: shape not served by the tiled kernels"}})) return e;
+  return dw_dispatch(c);
 }
 
-// The same with THIS depthwise layer's weight gradient taken from the same dy window (stride 1, tiled path, at most DWT_MAX_ROWS pixel
-// tiles): wslab receives dc_dwconv_dgrad_wgrad_rows rows of [9][C] partial sums; dc_dwconv_wgrad_reduce adds them into grad_w.  The
+// The same with THIS depthwise layer's weight gradient taken from the same dy window (tiled and pipelined kernels, at most DWT_MAX_ROWS
+// rows): wslab receives dc_dwconv_dgrad_wgrad_rows rows of [9][C] partial sums; dc_dwconv_wgrad_reduce adds them into grad_w.  The
 // layer's forward input is act(ybn*mscale + mshift) (the never-stored BatchNorm output), so nothing is read that the data gradient
 // with statistics does not read already.
 extern "C" int dc_dwconv_dgrad_wgrad_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_options.dw_tile) return 0;
-  if (stride == 2 && dil == 1) {          // the stride-2 data-gradient kernel walks its tiles: one row per workgroup
-    const int rows = dc_dwconv_dgrad_bnstats_rows(dtype, C, stride, dil, N, Hi, Wi);
-    return rows > 0 && rows <= DWT_MAX_ROWS ? rows : 0;
-  }
-  if (stride != 1 || (dil != 1 && dil != 2)) return 0;
-  if (dc_dwconv_dgrad_bnstats_rows(dtype, C, stride, dil, N, Hi, Wi) <= 0) return 0;
-  const int pr = dw_pipe_rows(dtype, C, dil, N, Hi, Wi);
-  if (pr > 0) return pr;
-  const int rows = dw_tile_rows(dtype, C, N, Hi, Wi);
-  return rows <= DWT_MAX_ROWS ? rows : 0;
+  const int rows = dw_route(DW_DGRAD, dtype, C, stride, dil, N, Hi, Wi).rows;
+  return rows > 0 && rows <= DWT_MAX_ROWS ? rows : 0;
 }
 
 // 1: the data gradients that take BatchNorm sums (dc_dwconv_dgrad_bnstats_wgrad_sum, dc_dwconv_dgrad_wgrad_bnres_sum) serve this shape: the
 // persistent pipelined kernel (dwpipe.hip), whose workgroups add their sums to ONE fp64 row (bn_fin.h: SUM_ROW)
 extern "C" int dc_dwconv_dgrad_sum_row_ok(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (!g_options.dw_tile || stride != 1 || (dil != 1 && dil != 2) || C <= 0 || N <= 0 || (long)N * Hi * Wi >= (1L << 31)) return 0;
-  return dw_pipe_rows(dtype, C, dil, N, Hi, Wi) > 0 && dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0 ? 1 : 0;
+  return dw_route(DW_DGRAD, dtype, C, stride, dil, N, Hi, Wi).family == DW_PIPE;
 }
 
-static int dgrad_bnstats_wgrad_impl(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
-                                    const float* w, void* dx, int lddx, const void* ybn, int ldybn, const float* save_mean,
-                                    const float* save_invstd, const float* mscale, const float* mshift, int relu, float* slab,
-                                    float* wslab, void* stream, bool sum_row) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad dx")) return e;
-  if (int e = dc_check_view(ybn, ldybn, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad y")) return e;
-  DC_REQUIRE(w && save_mean && save_invstd && slab && wslab && mscale && mshift, "dc_dwconv_dgrad_bnstats_wgrad: null argument");
-  DC_REQUIRE(dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_bnstats_wgrad: shape not served");
-  DC_REQUIRE(!sum_row || (dc_dwconv_dgrad_sum_row_ok(dtype, C, stride, dil, N, Hi, Wi) && ((uintptr_t)slab & 7) == 0),
-             "dc_dwconv_dgrad_bnstats_wgrad_sum: shape not served (dc_dwconv_dgrad_sum_row_ok), or the sum row is not double[2][C]");
-  DwBnStats bs;
-  bs.y = ybn; bs.ldy = ldybn; bs.mean = save_mean; bs.invstd = save_invstd; bs.mscale = mscale; bs.mshift = mshift; bs.relu = relu ? 1 : 0;
-  bs.slab = slab; bs.rows = sum_row ? SUM_ROW : 0; bs.wslab = wslab;
-  if (stride == 2) return launch_dw_tile_s2(dtype, 1, N, Hi, Wi, C, dy, lddy, w, nullptr, 0, dx, lddx, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0, &bs);
-  return launch_dw_tile(dtype, dil, true, dy, lddy, w, nullptr, 0, dx, lddx, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, 0, &bs);
+// the three forms of dc_dwconv_dgrad_bnstats_wgrad: plain, with a sum row (which names the plain form in what both check), onto an addend
+enum BnwForm { BNW_PLAIN, BNW_SUM, BNW_ADD };
+static int dgrad_bnstats_wgrad_impl(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy, const float* w,
+                                    const void* addend, int ldadd, void* dx, int lddx, const void* ybn, int ldybn, const float* save_mean,
+                                    const float* save_invstd, const float* mscale, const float* mshift, int relu, float* slab, float* wslab,
+                                    void* stream, BnwForm form) {
+  const bool sum_row = form == BNW_SUM, add = form == BNW_ADD;
+  DwCall c = dw_call(true, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = dy; c.ldin = lddy; c.wp = w; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldout = lddx;
+  c.bs = bn_rider(ybn, ldybn, save_mean, save_invstd, mscale, mshift, relu, slab, wslab, sum_row);
+  if (int e = dw_check_call(add ? "dc_dwconv_dgrad_bnstats_wgrad_add" : "dc_dwconv_dgrad_bnstats_wgrad", c, "y",
+                            {{!add || stride == 1, "dc_dwconv_dgrad_bnstats_wgrad_add: stride 1"},
+                             {w && save_mean && save_invstd && slab && wslab && mscale && mshift,
+                              add ? "dc_dwconv_dgrad_bnstats_wgrad_add: null argument" : "dc_dwconv_dgrad_bnstats_wgrad: null argument"},
+                             {dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0,
+                              add ? "dc_dwconv_dgrad_bnstats_wgrad_add: shape not served" : "dc_dwconv_dgrad_bnstats_wgrad: shape not served"},
+                             {!sum_row || (dc_dwconv_dgrad_sum_row_ok(dtype, C, stride, dil, N, Hi, Wi) && ((uintptr_t)slab & 7) == 0),
+                              "dc_dwconv_dgrad_bnstats_wgrad_sum: shape not served (dc_dwconv_dgrad_sum_row_ok), or the sum row is not double[2][C]"}})) return e;
+  return dw_dispatch(c);
 }
 extern "C" int dc_dwconv_dgrad_bnstats_wgrad(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                              const float* w, void* dx, int lddx, const void* ybn, int ldybn, const float* save_mean,
                                              const float* save_invstd, const float* mscale, const float* mshift, int relu, float* slab,
                                              float* wslab, void* stream) {
-  return dgrad_bnstats_wgrad_impl(dtype, C, stride, dil, N, Hi, Wi, dy, lddy, w, dx, lddx, ybn, ldybn, save_mean, save_invstd, mscale, mshift, relu, slab,
-                                  wslab, stream, false);
+  return dgrad_bnstats_wgrad_impl(dtype, C, stride, dil, N, Hi, Wi, dy, lddy, w, nullptr, 0, dx, lddx, ybn, ldybn, save_mean, save_invstd, mscale, mshift,
+                                  relu, slab, wslab, stream, BNW_PLAIN);
 }
 // ... with the two BatchNorm sums added to a SUM ROW: `slab` is double[2][C] (sum g, sum g*xhat), zeroed by the caller; dc_bn_bwd_finalize and
 // dc_bn_bwd_apply_fin take it with rows = -1
@@ -615,11 +645,10 @@ extern "C" int dc_dwconv_dgrad_bnstats_wgrad_sum(int dtype, int C, int stride, i
                                                  const float* w, void* dx, int lddx, const void* ybn, int ldybn, const float* save_mean,
                                                  const float* save_invstd, const float* mscale, const float* mshift, int relu, float* slab,
                                                  float* wslab, void* stream) {
-  return dgrad_bnstats_wgrad_impl(dtype, C, stride, dil, N, Hi, Wi, dy, lddy, w, dx, lddx, ybn, ldybn, save_mean, save_invstd, mscale, mshift, relu, slab,
-                                  wslab, stream, true);
+  return dgrad_bnstats_wgrad_impl(dtype, C, stride, dil, N, Hi, Wi, dy, lddy, w, nullptr, 0, dx, lddx, ybn, ldybn, save_mean, save_invstd, mscale, mshift,
+                                  relu, slab, wslab, stream, BNW_SUM);
 }
-
-// dc_dwconv_dgrad_bnstats_wgrad when this layer is not the only reader of the BatchNorm's output: the data gradient is added onto what the
+// ... when this layer is not the only reader of the BatchNorm's output: the data gradient is added onto what the
 // other readers left in `addend` (may alias dx) and the sums are those of the COMPLETE gradient -- the caller makes this layer the last
 // writer (block 1's first depthwise layer behind the shortcut conv: the BatchNorm in front of both is bn2, whose 226 MB output gradient and
 // input a separate dc_bn_bwd_reduce pass would read once more).  Stride 1.
@@ -627,19 +656,8 @@ extern "C" int dc_dwconv_dgrad_bnstats_wgrad_add(int dtype, int C, int stride, i
                                                  const float* w, const void* addend, int ldadd, void* dx, int lddx, const void* ybn, int ldybn,
                                                  const float* save_mean, const float* save_invstd, const float* mscale, const float* mshift, int relu,
                                                  float* slab, float* wslab, void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  DC_REQUIRE(stride == 1, "dc_dwconv_dgrad_bnstats_wgrad_add: stride 1");
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad_add dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad_add dx")) return e;
-  if (int e = dc_check_view(ybn, ldybn, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad_add y")) return e;
-  if (addend != nullptr)
-    if (int e = dc_check_view(addend, ldadd, C, dtype, "dc_dwconv_dgrad_bnstats_wgrad_add addend")) return e;
-  DC_REQUIRE(w && save_mean && save_invstd && slab && wslab && mscale && mshift, "dc_dwconv_dgrad_bnstats_wgrad_add: null argument");
-  DC_REQUIRE(dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_bnstats_wgrad_add: shape not served");
-  DwBnStats bs;
-  bs.y = ybn; bs.ldy = ldybn; bs.mean = save_mean; bs.invstd = save_invstd; bs.mscale = mscale; bs.mshift = mshift; bs.relu = relu ? 1 : 0;
-  bs.slab = slab; bs.rows = 0; bs.wslab = wslab;
-  return launch_dw_tile(dtype, dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, 0, &bs);
+  return dgrad_bnstats_wgrad_impl(dtype, C, stride, dil, N, Hi, Wi, dy, lddy, w, addend, ldadd, dx, lddx, ybn, ldybn, save_mean, save_invstd, mscale, mshift,
+                                  relu, slab, wslab, stream, BNW_ADD);
 }
 
 // Data gradient (optionally accumulated onto `addend`) plus this layer's weight-gradient rows when the layer's forward input is a
@@ -648,30 +666,23 @@ extern "C" int dc_dwconv_dgrad_bnstats_wgrad_add(int dtype, int C, int stride, i
 extern "C" int dc_dwconv_dgrad_wgrad(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                      const float* w, const void* addend, int ldadd, void* dx, int lddx, const void* x, int ldx,
                                      const float* pscale, const float* pshift, int prelu, float* wslab, void* stream) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad_wgrad dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad_wgrad dx")) return e;
-  if (int e = dc_check_view(x, ldx, C, dtype, "dc_dwconv_dgrad_wgrad x")) return e;
-  if (addend != nullptr)
-    if (int e = dc_check_view(addend, ldadd, C, dtype, "dc_dwconv_dgrad_wgrad addend")) return e;
-  DC_REQUIRE(w && wslab && (pscale == nullptr) == (pshift == nullptr), "dc_dwconv_dgrad_wgrad: bad argument");
-  DC_REQUIRE(dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_wgrad: shape not served");
-  DwBnStats bs;
-  bs.y = x; bs.ldy = ldx; bs.mean = bs.invstd = nullptr; bs.mscale = pscale; bs.mshift = pshift; bs.relu = (pscale != nullptr && prelu) ? 1 : 0;
-  bs.slab = nullptr; bs.rows = 0; bs.wslab = wslab;
-  if (stride == 2) return launch_dw_tile_s2(dtype, 1, N, Hi, Wi, C, dy, lddy, w, addend, ldadd, dx, lddx, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0, &bs);
-  return launch_dw_tile(dtype, dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, 0, &bs);
+  DwCall c = dw_call(true, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = dy; c.ldin = lddy; c.wp = w; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldout = lddx;
+  c.bs = wgrad_rider(x, ldx, pscale, pshift, prelu, wslab);
+  if (int e = dw_check_call("dc_dwconv_dgrad_wgrad", c, "x", {{w && wslab && (pscale == nullptr) == (pshift == nullptr), "dc_dwconv_dgrad_wgrad: bad argument"},
+                             {dc_dwconv_dgrad_wgrad_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_wgrad: shape not served"}})) return e;
+  return dw_dispatch(c);
 }
 
 // dc_dwconv_dgrad_wgrad on a layer whose stored input x is a BatchNorm output with a residual, relu(bn(ybn) + r) -- the first separable conv
 // of an Xception block reading the previous block's output -- and whose data gradient is the LAST contribution to d(x): the kernel also
 // takes that BatchNorm's backward sums (g = dx masked by x > 0 when relu; slab[2][rows][C]), so dc_bn_bwd_reduce's pass over dx, ybn and x
-// disappears.  Served by the persistent kernel only (rows = 0: use dc_dwconv_dgrad_wgrad + dc_bn_bwd_reduce).
+// disappears.  Served by the persistent kernel only, at dilation 1 (rows = 0: use dc_dwconv_dgrad_wgrad + dc_bn_bwd_reduce).
 // relu = 2 (where dc_dwconv_dgrad_wgrad_bnres_masked says 1): dx is stored masked by x > 0 as well, i.e. as the g that BatchNorm's apply pass
 // and the shortcut need -- dc_bn_bwd_apply then runs with relu = 0, reads no `out` and writes no `g_out`.
 extern "C" int dc_dwconv_dgrad_wgrad_bnres_rows(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
-  if (stride != 1 || dil != 1 || !g_options.dw_tile) return 0;
-  return dw_pipe_rows(dtype, C, dil, N, Hi, Wi);
+  const DwRoute r = dw_route(DW_DGRAD, dtype, C, stride, dil, N, Hi, Wi);
+  return r.family == DW_PIPE && dil == 1 ? r.rows : 0;
 }
 extern "C" int dc_dwconv_dgrad_wgrad_bnres_masked(int dtype, int C, int stride, int dil, int N, int Hi, int Wi) {
   return g_options.dw_res_masked && dc_dwconv_dgrad_wgrad_bnres_rows(dtype, C, stride, dil, N, Hi, Wi) > 0 ? 1 : 0;
@@ -681,25 +692,16 @@ static int dgrad_wgrad_bnres_impl(int dtype, int C, int stride, int dil, int N, 
                                   const float* w, const void* addend, int ldadd, void* dx, int lddx, const void* x, int ldx,
                                   float* wslab, const void* ybn, int ldybn, const float* save_mean, const float* save_invstd,
                                   int relu, float* slab, void* stream, bool sum_row) {
-  if (int e = dw_check(dtype, C, stride, dil, N, Hi, Wi)) return e;
-  if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_dgrad_wgrad_bnres dy")) return e;
-  if (int e = dc_check_view(dx, lddx, C, dtype, "dc_dwconv_dgrad_wgrad_bnres dx")) return e;
-  if (int e = dc_check_view(x, ldx, C, dtype, "dc_dwconv_dgrad_wgrad_bnres x")) return e;
-  if (int e = dc_check_view(ybn, ldybn, C, dtype, "dc_dwconv_dgrad_wgrad_bnres ybn")) return e;
-  if (addend != nullptr)
-    if (int e = dc_check_view(addend, ldadd, C, dtype, "dc_dwconv_dgrad_wgrad_bnres addend")) return e;
-  DC_REQUIRE(w && wslab && save_mean && save_invstd && slab, "dc_dwconv_dgrad_wgrad_bnres: null argument");
-  DC_REQUIRE(dc_dwconv_dgrad_wgrad_bnres_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_wgrad_bnres: shape not served");
-  DC_REQUIRE(relu >= 0 && relu <= 2, "dc_dwconv_dgrad_wgrad_bnres: relu is 0, 1 (mask the sums) or 2 (mask the sums and the stored dx)");
-  DC_REQUIRE(relu != 2 || dc_dwconv_dgrad_wgrad_bnres_masked(dtype, C, stride, dil, N, Hi, Wi),
-             "dc_dwconv_dgrad_wgrad_bnres: relu = 2 is switched off (option dw_res_masked)");
-  DwBnStats bs;
-  bs.y = x; bs.ldy = ldx; bs.mean = bs.invstd = nullptr; bs.mscale = nullptr; bs.mshift = nullptr; bs.relu = 0;
-  bs.slab = nullptr; bs.rows = 0; bs.wslab = wslab;
-  DwResStats rs;
-  DC_REQUIRE(!sum_row || ((uintptr_t)slab & 7) == 0, "dc_dwconv_dgrad_wgrad_bnres_sum: a sum row is double[2][C]");
-  rs.y = ybn; rs.ldy = ldybn; rs.mean = save_mean; rs.invstd = save_invstd; rs.relu = relu; rs.slab = slab; rs.sum_row = sum_row ? 1 : 0;
-  return launch_dw_pipe(dil, true, dy, lddy, w, addend, ldadd, dx, lddx, N, Hi, Wi, C, (hipStream_t)stream, nullptr, nullptr, 0, &bs, &rs);
+  DwCall c = dw_call(true, dtype, C, stride, dil, N, Hi, Wi, stream);
+  c.in = dy; c.ldin = lddy; c.wp = w; c.addend = addend; c.ldadd = ldadd; c.out = dx; c.ldout = lddx;
+  c.bs = wgrad_rider(x, ldx, nullptr, nullptr, 0, wslab);
+  c.res.y = ybn; c.res.ldy = ldybn; c.res.mean = save_mean; c.res.invstd = save_invstd; c.res.relu = relu; c.res.slab = slab; c.res.sum_row = sum_row ? 1 : 0;
+  if (int e = dw_check_call("dc_dwconv_dgrad_wgrad_bnres", c, "x", {{w && wslab && save_mean && save_invstd && slab, "dc_dwconv_dgrad_wgrad_bnres: null argument"},
+                             {dc_dwconv_dgrad_wgrad_bnres_rows(dtype, C, stride, dil, N, Hi, Wi) > 0, "dc_dwconv_dgrad_wgrad_bnres: shape not served"},
+                             {relu >= 0 && relu <= 2, "dc_dwconv_dgrad_wgrad_bnres: relu is 0, 1 (mask the sums) or 2 (mask the sums and the stored dx)"},
+                             {relu != 2 || dc_dwconv_dgrad_wgrad_bnres_masked(dtype, C, stride, dil, N, Hi, Wi), "dc_dwconv_dgrad_wgrad_bnres: relu = 2 is switched off (option dw_res_masked)"},
+                             {!sum_row || ((uintptr_t)slab & 7) == 0, "dc_dwconv_dgrad_wgrad_bnres_sum: a sum row is double[2][C]"}})) return e;
+  return dw_dispatch(c);
 }
 extern "C" int dc_dwconv_dgrad_wgrad_bnres(int dtype, int C, int stride, int dil, int N, int Hi, int Wi, const void* dy, int lddy,
                                            const float* w, const void* addend, int ldadd, void* dx, int lddx, const void* x, int ldx,
@@ -748,48 +750,46 @@ extern "C" int dc_dwconv_wgrad(int dtype, int C, int stride, int dil, int N, int
   if (int e = dc_check_view(x, ldx, C, dtype, "dc_dwconv_wgrad x")) return e;
   if (int e = dc_check_view(dy, lddy, C, dtype, "dc_dwconv_wgrad dy")) return e;
   DC_REQUIRE(workspace != nullptr && grad_w != nullptr, "dc_dwconv_wgrad: null argument");
-  const int Ho = dw_out(Hi, stride, dil), Wo = dw_out(Wi, stride, dil);
-  const long P = (long)N * Ho * Wo;
-  const int ppb = dw_pix_per_block(P);
-  const int rows = (int)((P + ppb - 1) / ppb);
-  hipStream_t st = (hipStream_t)stream;
+  DwWgradCall c;
+  c.dtype = dtype; c.stride = stride; c.dil = dil; c.N = N; c.C = C; c.Hi = Hi; c.Wi = Wi; c.st = (hipStream_t)stream;
+  c.x = x; c.ldx = ldx; c.dy = dy; c.lddy = lddy; c.slab = (float*)workspace; c.grad_w = grad_w; c.pscale = pscale; c.pshift = pshift; c.prelu = prelu;
+  const DwFamily family = dw_route(DW_WGRAD, dtype, C, stride, dil, N, Hi, Wi).family;
+  if (family == DW_TILE) return launch_dw_tile_wgrad(c);
+  if (family == DW_TILE_S2) return launch_dw_tile_s2_wgrad(c);
+  // the register kernels: the stride-1 window form (option "dw_tile" = 0), or the generic one for any stride and dilation
   const int kpv = dtype == DC_BF16 ? 8 : 4;
   const int cgw = dw_pick_cgw(C / kpv);
-  if (stride == 1 && (dil == 1 || dil == 2) && g_options.dw_tile)
-    return launch_dw_tile_wgrad(dtype, dil, x, ldx, dy, lddy, (float*)workspace, grad_w, N, Hi, Wi, C, st, pscale, pshift, prelu);
-  if (stride == 2 && dil == 1 && g_options.dw_tile) {
-    int trows = 0;
-    if (int e = launch_dw_tile_s2(dtype, 2, N, Hi, Wi, C, x, ldx, nullptr, dy, lddy, nullptr, 0, (float*)workspace, &trows, st, pscale, pshift, prelu)) return e;
-    return dw_tile_reduce((const float*)workspace, grad_w, trows, C, st);
-  }
-  if (stride == 1 && (dil == 1 || dil == 2)) {
+  int rows;
+  if (family == DW_WIN) {
     const int nstrips = N * Hi * ((Wi + DW_PX - 1) / DW_PX);
     const int nsl = 256 / cgw;
     int spb = cdiv(nstrips, 256);
     if (spb < 2 * nsl) spb = 2 * nsl;
     spb = cdiv(spb, nsl) * nsl;
-    const int frows = cdiv(nstrips, spb);
-    dim3 fgrid(cdiv(C / kpv, cgw), frows);
+    rows = cdiv(nstrips, spb);
+    dim3 fgrid(cdiv(C / kpv, cgw), rows);
     const size_t lds = (size_t)256 * 9 * sizeof(float);
-#define DW_WS1(TT, D) hipLaunchKernelGGL((dw_s1_wgrad_kernel<TT, D>), fgrid, dim3(256), lds, st, (const TT*)x, ldx, (const TT*)dy, lddy, (float*)workspace, N, Hi, Wi, C, spb, cgw, pscale, pshift, prelu)
+#define DW_WS1(TT, D) hipLaunchKernelGGL((dw_s1_wgrad_kernel<TT, D>), fgrid, dim3(256), lds, c.st, (const TT*)c.x, c.ldx, (const TT*)c.dy, c.lddy, c.slab, N, Hi, Wi, C, spb, cgw, c.pscale, c.pshift, c.prelu)
     if (dtype == DC_BF16) { if (dil == 1) DW_WS1(bf16, 1); else DW_WS1(bf16, 2); }
     else                  { if (dil == 1) DW_WS1(float, 1); else DW_WS1(float, 2); }
 #undef DW_WS1
     DC_LAUNCHED("dw_win_wgrad");
-    hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv(9 * C, 8)), dim3(256), 0, st, (const float*)workspace, grad_w, frows, C);
-    DC_LAUNCHED("dw_reg_reduce");
-    return 0;
-  }
-  dim3 grid(cdiv(C / kpv, cgw), rows);
-#define DW_WG(TT, W) hipLaunchKernelGGL((dw_wgrad_kernel<TT, W>), grid, dim3(256), 0, st, (const TT*)x, ldx, (const TT*)dy, lddy, (float*)workspace, N, Hi, Wi, Ho, Wo, C, stride, dil, ppb, pscale, pshift, prelu)
-  if (dtype == DC_BF16) {
-    if (cgw == 64) DW_WG(bf16, 64); else if (cgw == 32) DW_WG(bf16, 32); else if (cgw == 16) DW_WG(bf16, 16); else DW_WG(bf16, 8);
   } else {
-    if (cgw == 64) DW_WG(float, 64); else if (cgw == 32) DW_WG(float, 32); else if (cgw == 16) DW_WG(float, 16); else DW_WG(float, 8);
-  }
+    const int Ho = dw_out(Hi, stride, dil), Wo = dw_out(Wi, stride, dil);
+    const long P = (long)N * Ho * Wo;
+    const int ppb = dw_pix_per_block(P);
+    rows = (int)((P + ppb - 1) / ppb);
+    dim3 grid(cdiv(C / kpv, cgw), rows);
+#define DW_WG(TT, W) hipLaunchKernelGGL((dw_wgrad_kernel<TT, W>), grid, dim3(256), 0, c.st, (const TT*)c.x, c.ldx, (const TT*)c.dy, c.lddy, c.slab, N, Hi, Wi, Ho, Wo, C, stride, dil, ppb, c.pscale, c.pshift, c.prelu)
+    if (dtype == DC_BF16) {
+      if (cgw == 64) DW_WG(bf16, 64); else if (cgw == 32) DW_WG(bf16, 32); else if (cgw == 16) DW_WG(bf16, 16); else DW_WG(bf16, 8);
+    } else {
+      if (cgw == 64) DW_WG(float, 64); else if (cgw == 32) DW_WG(float, 32); else if (cgw == 16) DW_WG(float, 16); else DW_WG(float, 8);
+    }
 #undef DW_WG
-  DC_LAUNCHED("dw_reg_wgrad");
-  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv(9 * C, 8)), dim3(256), 0, st, (const float*)workspace, grad_w, rows, C);
+    DC_LAUNCHED("dw_reg_wgrad");
+  }
+  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv(9 * C, 8)), dim3(256), 0, c.st, (const float*)c.slab, grad_w, rows, C);
   DC_LAUNCHED("dw_reg_reduce");
   return 0;
 }

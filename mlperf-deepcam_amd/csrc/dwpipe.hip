@@ -606,41 +606,34 @@ int dw_pipe_rows(int dtype, int C, int dil, int N, int H, int W) {
   return (int)wc;
 }
 
-int launch_dw_pipe(int dil, bool flip, const void* in, int ldin, const float* wp, const void* addend, int ldadd, void* out, int ldout, int N,
-                   int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu, const DwBnStats* bnstats,
-                   const DwResStats* res) {
-  const int wc = dw_pipe_rows(DC_BF16, C, dil, N, H, W);
-  DC_REQUIRE(wc > 0, "launch_dw_pipe: shape not served");
+int launch_dw_pipe(const DwCall& c) {
+  const int H = c.Hi, W = c.Wi, C = c.C, dil = c.dil;
+  const bool flip = c.flip;
+  const DwResStats& res = c.res;
+  const int wc = dw_pipe_rows(c.dtype, C, dil, c.N, H, W);
+  DC_REQUIRE(wc > 0 && c.stride == 1, "launch_dw_pipe: shape not served");
   DwpArgs a;
-  a.in = (const bf16*)in; a.ldin = ldin; a.wp = wp; a.addend = (const bf16*)addend; a.ldadd = ldadd; a.out = (bf16*)out; a.ldout = ldout;
+  a.in = (const bf16*)c.in; a.ldin = c.ldin; a.wp = c.wp; a.addend = (const bf16*)c.addend; a.ldadd = c.ldadd; a.out = (bf16*)c.out; a.ldout = c.ldout;
   a.H = H; a.W = W; a.C = C;
-  a.ncb = cdiv(C / 8, P_CG); a.ntx = W / P_TW; a.nty = H / P_TH; a.ptiles = N * a.ntx * a.nty;
-  a.pscale = pscale; a.pshift = pshift; a.prelu = prelu;
-  if (bnstats != nullptr) a.st = *bnstats;
-  else { a.st.slab = nullptr; a.st.y = nullptr; a.st.ldy = 0; a.st.mean = a.st.invstd = a.st.mscale = a.st.mshift = nullptr; a.st.relu = 0; a.st.rows = 0; a.st.wslab = nullptr; }
-  a.sum_row = bnstats != nullptr && bnstats->rows == SUM_ROW && bnstats->slab != nullptr;
-  a.sum_row2 = res != nullptr && res->sum_row;
+  a.ncb = cdiv(C / 8, P_CG); a.ntx = W / P_TW; a.nty = H / P_TH; a.ptiles = c.N * a.ntx * a.nty;
+  a.pscale = c.pscale; a.pshift = c.pshift; a.prelu = c.prelu;
+  a.st = c.bs;
+  a.sum_row = c.bs.rows == SUM_ROW && c.bs.slab != nullptr;
+  a.sum_row2 = res.on() && res.sum_row;
   a.st.rows = wc;
-  a.y2 = nullptr; a.ldy2 = 0; a.mean2 = a.invstd2 = nullptr; a.relu2 = 0; a.slab2 = nullptr;
-  if (res != nullptr) {
-    a.y2 = (const bf16*)res->y; a.ldy2 = res->ldy; a.mean2 = res->mean; a.invstd2 = res->invstd; a.relu2 = res->relu; a.slab2 = res->slab;
-  }
+  a.y2 = (const bf16*)res.y; a.ldy2 = res.ldy; a.mean2 = res.mean; a.invstd2 = res.invstd; a.relu2 = res.relu; a.slab2 = res.slab;   // (off: nulls)
   const int grid = a.ncb * wc;
-  const bool stats = flip && a.st.slab != nullptr, wg = flip && a.st.wslab != nullptr, add = flip && addend != nullptr;
-  const bool xf = !flip && pscale != nullptr;
+  const bool stats = flip && a.st.slab != nullptr, wg = flip && a.st.wslab != nullptr, add = flip && c.addend != nullptr;
+  const bool xf = !flip && c.pscale != nullptr;
   DC_REQUIRE(!(stats || wg) || a.st.y != nullptr, "launch_dw_pipe: the sums need the BatchNorm input");
-  if (res != nullptr) {
+#define DWP(D, M) return launch1<D, M>(a, grid, c.st)
+  if (res.on()) {
     DC_REQUIRE(wg && !stats && a.y2 && a.mean2 && a.invstd2 && a.slab2, "launch_dw_pipe: the residual BatchNorm's sums ride on the weight-gradient form");
     DC_REQUIRE(dil == 1, "launch_dw_pipe: the residual form is built for dilation 1 (with dilation 2 its ring would hold a single stage)");
-    if (res->relu == 2) {
-      if (add) return launch1<1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES | PM_MASK>(a, grid, st);
-      return launch1<1, PM_FLIP | PM_WGRAD | PM_RES | PM_MASK>(a, grid, st);
-    }
-    if (add) return launch1<1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES>(a, grid, st);
-    return launch1<1, PM_FLIP | PM_WGRAD | PM_RES>(a, grid, st);
+    if (res.relu == 2) { if (add) DWP(1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES | PM_MASK); else DWP(1, PM_FLIP | PM_WGRAD | PM_RES | PM_MASK); }
+    if (add) DWP(1, PM_FLIP | PM_WGRAD | PM_ADD | PM_RES); else DWP(1, PM_FLIP | PM_WGRAD | PM_RES);
   }
-#define DWP(D, M) return launch1<D, M>(a, grid, st)
-#define DWP_MODES(D)                                                                                      \
+#define DWP_MODES(D)                                                                                     \
   if (!flip) { if (xf) DWP(D, PM_XFORM); else DWP(D, 0); }                                               \
   if (stats && wg) { if (add) DWP(D, PM_FLIP | PM_STATS | PM_WGRAD | PM_ADD); else DWP(D, PM_FLIP | PM_STATS | PM_WGRAD); } \
   if (stats) { if (add) DWP(D, PM_FLIP | PM_STATS | PM_ADD); else DWP(D, PM_FLIP | PM_STATS); }         \

@@ -473,116 +473,72 @@ size_t dw_tile_wgrad_workspace(int C, int N, int H, int W) {
   return best;
 }
 
+// one instantiation of dwt_kernel over the tile grid
+template <typename T, auto KERNEL, int LDS>
+static void launch_dwt(const DwCall& c, const TileGrid& t, const DwBnStats& bs, const BnFinArgs& fin) {
+  DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+  hipLaunchKernelGGL(KERNEL, dim3(t.ntiles * t.ncgb), dim3(256), LDS, c.st, (const T*)c.in, c.ldin, c.wp, (const T*)c.addend, c.ldadd,
+                     (T*)c.out, c.ldout, c.Hi, c.Wi, c.C, t.ncgb, t.ntx, t.nty, c.pscale, c.pshift, c.prelu, bs, fin);
+}
+
 template <typename T, int DIL, bool FLIP, int CG>
-static void launch_fwd1(const TileGrid& t, const void* in, int ldin, const float* wp, const void* addend, int ldadd, void* out,
-                        int ldout, int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu, const DwBnStats& bs, const BnFinArgs& fin) {
+static void launch_fwd1(const DwCall& c, const TileGrid& t, const DwBnStats& bs, const BnFinArgs& fin) {
+  constexpr int LDS = TileCfg<DIL, CG>::LDS_BYTES;
   if constexpr (FLIP) {
     if (bs.wslab != nullptr) {          // data gradient + BatchNorm sums + this layer's weight-gradient rows
       constexpr int FOLD = TileCfg<DIL, CG>::NSL * 9 * CG * Elem<T>::kPerVec * (int)sizeof(float);
-      constexpr int LDSW = TileCfg<DIL, CG>::LDS_BYTES > FOLD ? TileCfg<DIL, CG>::LDS_BYTES : FOLD;
-      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt_kernel<T, DIL, true, CG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDSW));
-      hipLaunchKernelGGL((dwt_kernel<T, DIL, true, CG, true>), dim3(t.ntiles * t.ncgb), dim3(256), LDSW, st, (const T*)in, ldin, wp,
-                         (const T*)addend, ldadd, (T*)out, ldout, H, W, C, t.ncgb, t.ntx, t.nty, pscale, pshift, prelu, bs, fin);
-      return;
+      return launch_dwt<T, &dwt_kernel<T, DIL, true, CG, true>, (LDS > FOLD ? LDS : FOLD)>(c, t, bs, fin);
     }
-  }
-  constexpr int LDS = TileCfg<DIL, CG>::LDS_BYTES;
-  if constexpr (!FLIP) {
-    if (fin.slab != nullptr && fin.rows == SUM_ROW) {
-      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt_kernel<T, DIL, false, CG, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      hipLaunchKernelGGL((dwt_kernel<T, DIL, false, CG, false, 2>), dim3(t.ntiles * t.ncgb), dim3(256), LDS, st, (const T*)in, ldin, wp,
-                         (const T*)addend, ldadd, (T*)out, ldout, H, W, C, t.ncgb, t.ntx, t.nty, pscale, pshift, prelu, bs, fin);
-      return;
-    }
-    if (fin.slab != nullptr) {
-      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt_kernel<T, DIL, false, CG, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      hipLaunchKernelGGL((dwt_kernel<T, DIL, false, CG, false, 1>), dim3(t.ntiles * t.ncgb), dim3(256), LDS, st, (const T*)in, ldin, wp,
-                         (const T*)addend, ldadd, (T*)out, ldout, H, W, C, t.ncgb, t.ntx, t.nty, pscale, pshift, prelu, bs, fin);
-      return;
-    }
-  }
-  DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt_kernel<T, DIL, FLIP, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-  hipLaunchKernelGGL((dwt_kernel<T, DIL, FLIP, CG>), dim3(t.ntiles * t.ncgb), dim3(256), LDS, st, (const T*)in, ldin, wp,
-                     (const T*)addend, ldadd, (T*)out, ldout, H, W, C, t.ncgb, t.ntx, t.nty, pscale, pshift, prelu, bs, fin);
-}
-
-template <typename T, int DIL, bool FLIP>
-static void launch_fwd2(const TileGrid& t, const void* in, int ldin, const float* wp, const void* addend, int ldadd, void* out,
-                        int ldout, int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu, const DwBnStats& bs, const BnFinArgs& fin) {
-  if (t.cg == 32) launch_fwd1<T, DIL, FLIP, 32>(t, in, ldin, wp, addend, ldadd, out, ldout, H, W, C, st, pscale, pshift, prelu, bs, fin);
-  else if (t.cg == 16) launch_fwd1<T, DIL, FLIP, 16>(t, in, ldin, wp, addend, ldadd, out, ldout, H, W, C, st, pscale, pshift, prelu, bs, fin);
-  else launch_fwd1<T, DIL, FLIP, 8>(t, in, ldin, wp, addend, ldadd, out, ldout, H, W, C, st, pscale, pshift, prelu, bs, fin);
-}
-
-int launch_dw_tile(int dtype, int dil, bool flip, const void* in, int ldin, const float* wp, const void* addend, int ldadd,
-                   void* out, int ldout, int N, int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu,
-                   const DwBnStats* bnstats, const BnFinArgs* finp) {
-  const int kpv = dtype == DC_BF16 ? 8 : 4;
-  BnFinArgs fin;
-  if (finp != nullptr) fin = *finp; else fin.slab = nullptr;
-  DC_REQUIRE(finp == nullptr || (!flip && !dw_pipe_forward() && finp->rows <= FIN_RL && finp->parts == 0),
-             "dc_dwconv_fwd_fin: a forward pass on the tiled kernel over a slab of at most dc_bn_bwd_apply_fin_max_rows() rows");
-  // the persistent pipelined kernel serves the data gradients (52.0 -> 41.5 us with BatchNorm sums and weight gradient on the 728-channel
-  // layers at local batch 8); the forward pass stays here unless option "dw_pipe" = 2 (23.4 vs 24.1 us plain, 34.5 vs 31.7 us with the
-  // BatchNorm applied on load: its in-place transform pass costs eight waves more than it costs three co-resident workgroups)
-  if ((flip || dw_pipe_forward()) && (long)N * H * W < (1L << 31) && dw_pipe_rows(dtype, C, dil, N, H, W) > 0)
-    return launch_dw_pipe(dil, flip, in, ldin, wp, addend, ldadd, out, ldout, N, H, W, C, st, pscale, pshift, prelu, bnstats);
-  DC_REQUIRE(bnstats == nullptr || bnstats->rows != SUM_ROW, "dc_dwconv_dgrad_*_sum: a sum row is served by the pipelined kernel only (dc_dwconv_dgrad_sum_row_ok)");
-  const TileGrid t = tile_grid(C / kpv, N, H, W);
-  DC_REQUIRE((long)t.ntiles * t.ncgb < (1L << 31) && (long)N * H * W < (1L << 31), "dc_dwconv: tensor too large for the tiled path");
-  DwBnStats bs;
-  if (bnstats != nullptr) bs = *bnstats; else { bs.slab = nullptr; bs.y = nullptr; bs.ldy = 0; bs.mean = bs.invstd = bs.mscale = bs.mshift = nullptr; bs.relu = 0; bs.rows = 0; bs.wslab = nullptr; }
-  if (bs.slab != nullptr) bs.rows = t.ntiles;
-#define DWT(TT, D, F) launch_fwd2<TT, D, F>(t, in, ldin, wp, addend, ldadd, out, ldout, H, W, C, st, pscale, pshift, prelu, bs, fin)
-  if (dtype == DC_BF16) {
-    if (dil == 1) { if (flip) DWT(bf16, 1, true); else DWT(bf16, 1, false); }
-    else          { if (flip) DWT(bf16, 2, true); else DWT(bf16, 2, false); }
   } else {
-    if (dil == 1) { if (flip) DWT(float, 1, true); else DWT(float, 1, false); }
-    else          { if (flip) DWT(float, 2, true); else DWT(float, 2, false); }
+    if (fin.slab != nullptr && fin.rows == SUM_ROW) return launch_dwt<T, &dwt_kernel<T, DIL, false, CG, false, 2>, LDS>(c, t, bs, fin);
+    if (fin.slab != nullptr) return launch_dwt<T, &dwt_kernel<T, DIL, false, CG, false, 1>, LDS>(c, t, bs, fin);
   }
+  launch_dwt<T, &dwt_kernel<T, DIL, FLIP, CG>, LDS>(c, t, bs, fin);
+}
+
+// FN<..., CG> ARGS for the channel-group width of the tile grid t
+#define DWT_CG(FN, ARGS, ...) \
+  do { if (t.cg == 32) FN<__VA_ARGS__, 32> ARGS; else if (t.cg == 16) FN<__VA_ARGS__, 16> ARGS; else FN<__VA_ARGS__, 8> ARGS; } while (0)
+
+int launch_dw_tile(const DwCall& c) {
+  BnFinArgs fin;
+  if (c.fin != nullptr) fin = *c.fin; else fin.slab = nullptr;
+  DC_REQUIRE(c.fin == nullptr || (!c.flip && !dw_pipe_forward() && c.fin->rows <= FIN_RL && c.fin->parts == 0),
+             "dc_dwconv_fwd_fin: a forward pass on the tiled kernel over a slab of at most dc_bn_bwd_apply_fin_max_rows() rows");
+  DC_REQUIRE(c.bs.rows != SUM_ROW, "dc_dwconv_dgrad_*_sum: a sum row is served by the pipelined kernel only (dc_dwconv_dgrad_sum_row_ok)");
+  const TileGrid t = tile_grid(c.C / (c.dtype == DC_BF16 ? 8 : 4), c.N, c.Hi, c.Wi);
+  DC_REQUIRE((long)t.ntiles * t.ncgb < (1L << 31) && (long)c.N * c.Hi * c.Wi < (1L << 31), "dc_dwconv: tensor too large for the tiled path");
+  DwBnStats bs = c.bs;
+  if (bs.slab != nullptr) bs.rows = t.ntiles;
+#define DWT(TT, D, F) DWT_CG(launch_fwd1, (c, t, bs, fin), TT, D, F)
+  DW_S1_CASES(c, DWT)
 #undef DWT
-  DC_LAUNCHED(flip ? "dw_tile_dgrad" : "dw_tile_fwd");
+  DC_LAUNCHED(c.flip ? "dw_tile_dgrad" : "dw_tile_fwd");
   return 0;
 }
 
 template <typename T, int DIL, int CG>
-static void launch_wg1(const TileGrid& t, int tpb, int rows, const void* x, int ldx, const void* dy, int lddy, float* slab, int H,
-                       int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu) {
+static void launch_wg1(const DwWgradCall& c, const TileGrid& t, int tpb, int rows) {
   constexpr int FOLD = TileCfg<DIL, CG>::NSL * 9 * CG * Elem<T>::kPerVec * (int)sizeof(float);   // red[strip lane][9][channels]
   constexpr int LDS = TileCfg<DIL, CG>::LDS_BYTES > FOLD ? TileCfg<DIL, CG>::LDS_BYTES : FOLD;
   DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt_wgrad_kernel<T, DIL, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-  hipLaunchKernelGGL((dwt_wgrad_kernel<T, DIL, CG>), dim3(rows * t.ncgb), dim3(256), LDS, st, (const T*)x, ldx, (const T*)dy, lddy,
-                     slab, H, W, C, t.ncgb, t.ntx, t.nty, t.ntiles, tpb, pscale, pshift, prelu);
+  hipLaunchKernelGGL((dwt_wgrad_kernel<T, DIL, CG>), dim3(rows * t.ncgb), dim3(256), LDS, c.st, (const T*)c.x, c.ldx, (const T*)c.dy, c.lddy,
+                     c.slab, c.Hi, c.Wi, c.C, t.ncgb, t.ntx, t.nty, t.ntiles, tpb, c.pscale, c.pshift, c.prelu);
 }
 
-template <typename T, int DIL>
-static void launch_wg2(const TileGrid& t, int tpb, int rows, const void* x, int ldx, const void* dy, int lddy, float* slab, int H,
-                       int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu) {
-  if (t.cg == 32) launch_wg1<T, DIL, 32>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-  else if (t.cg == 16) launch_wg1<T, DIL, 16>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-  else launch_wg1<T, DIL, 8>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-}
-
-int launch_dw_tile_wgrad(int dtype, int dil, const void* x, int ldx, const void* dy, int lddy, float* slab, float* grad_w, int N,
-                         int H, int W, int C, hipStream_t st, const float* pscale, const float* pshift, int prelu) {
-  const int kpv = dtype == DC_BF16 ? 8 : 4;
-  const TileGrid t = tile_grid(C / kpv, N, H, W);
+int launch_dw_tile_wgrad(const DwWgradCall& c) {
+  const TileGrid t = tile_grid(c.C / (c.dtype == DC_BF16 ? 8 : 4), c.N, c.Hi, c.Wi);
   const int tpb = wgrad_tpb(t);
   const int rows = cdiv(t.ntiles, tpb);
   DC_REQUIRE(rows <= DWT_MAX_ROWS, "dc_dwconv_wgrad: tiles-per-workgroup override needs more slab rows than the workspace holds");
-  DC_REQUIRE((long)N * H * W < (1L << 31), "dc_dwconv_wgrad: tensor too large for the tiled path");
-  if (dtype == DC_BF16) {
-    if (dil == 1) launch_wg2<bf16, 1>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-    else launch_wg2<bf16, 2>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-  } else {
-    if (dil == 1) launch_wg2<float, 1>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-    else launch_wg2<float, 2>(t, tpb, rows, x, ldx, dy, lddy, slab, H, W, C, st, pscale, pshift, prelu);
-  }
+  DC_REQUIRE((long)c.N * c.Hi * c.Wi < (1L << 31), "dc_dwconv_wgrad: tensor too large for the tiled path");
+#define DWT_WG(TT, D) DWT_CG(launch_wg1, (c, t, tpb, rows), TT, D)
+  if (c.dtype == DC_BF16) { if (c.dil == 1) DWT_WG(bf16, 1); else DWT_WG(bf16, 2); }
+  else                    { if (c.dil == 1) DWT_WG(float, 1); else DWT_WG(float, 2); }
+#undef DWT_WG
+#undef DWT_CG
   DC_LAUNCHED("dw_tile_wgrad");
-  hipLaunchKernelGGL(dwt_reduce_kernel, dim3(cdiv(9 * C, 16)), dim3(256), 0, st, (const float*)slab, grad_w, rows, C);
-  DC_LAUNCHED("dw_tile_reduce");
-  return 0;
+  return dw_tile_reduce(c.slab, c.grad_w, rows, c.C, c.st);
 }
 
 }  // namespace dc

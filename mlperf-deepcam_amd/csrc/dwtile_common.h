@@ -98,20 +98,21 @@ __device__ inline void load_taps(const float* __restrict__ wp, int ch0, int C, b
 // Fused consumer of a data-gradient kernel: the BatchNorm whose (never stored) output fed this depthwise conv needs
 // sum(g) and sum(g * xhat) per channel, g = dx masked by the ReLU (recomputed from the BatchNorm input y).  The kernel that
 // produces dx takes the two sums on the way out: one slab row per pixel tile, [2][rows][C].
+// A kernel argument: the members keep their order and size.  Default-constructed, everything is off.
 struct DwBnStats {
-  const void* y;        // BatchNorm input (raw conv output), same shape as dx
-  int ldy;
-  const float* mean;
-  const float* invstd;
-  const float* mscale;  // forward scale / shift: the mask is (y*mscale + mshift > 0)
-  const float* mshift;
-  int relu;
-  float* slab;          // null: statistics off
-  int rows;
+  const void* y = nullptr;        // BatchNorm input (raw conv output), same shape as dx
+  int ldy = 0;
+  const float* mean = nullptr;
+  const float* invstd = nullptr;
+  const float* mscale = nullptr;  // forward scale / shift: the mask is (y*mscale + mshift > 0)
+  const float* mshift = nullptr;
+  int relu = 0;
+  float* slab = nullptr;          // null: statistics off
+  int rows = 0;
   // stride-1 tiled kernel only: the depthwise WEIGHT gradient rides along too (dW[t] = sum_q xhat[q] * dy[q - t]: the dy window is the
   // one the data gradient reads, xhat = act(y*mscale + mshift) is recomputed from the y this epilogue loads anyway), one row of
   // [9][C] partial sums per pixel tile into wslab; null: off
-  float* wslab;
+  float* wslab = nullptr;
 };
 
 template <int KH>

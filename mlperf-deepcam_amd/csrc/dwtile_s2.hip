@@ -418,76 +418,89 @@ static int s2_dgrad_plan(int kpv, int C, int N, int Hi, int Wi, int* tpb_out) {
   return cdiv(ntiles, tpb);
 }
 
+// the launchers of one dtype and channel-group width
 template <typename T, int CG>
-static void launch3(int mode, S2Args a, int N, const void* p0, int ld0, const float* wp, const void* p1, int ld1, void* out, int ldout,
-                    float* slab, int* rows_out, hipStream_t st, DwBnStats bs) {
-  constexpr int TW = 8 * (32 / CG);
-  constexpr int LDS_F = lds_bytes(9, 2 * TW + 1, CG);          // forward / wgrad halo
-  constexpr int LDS_D0 = lds_bytes(5, TW / 2 + 1, CG);         // dgrad dy tile
-  constexpr int FOLD2 = (128 / CG) * 2 * CG * Elem<T>::kPerVec * (int)sizeof(float);   // fused BN statistics fold
-  constexpr int LDS_D = LDS_D0 > FOLD2 ? LDS_D0 : FOLD2;
-  constexpr int FOLD = (128 / CG) * 9 * CG * Elem<T>::kPerVec * (int)sizeof(float);
-  a.ntx = cdiv(mode == 1 ? a.Wi : a.Wo, TW);
-  a.nty = cdiv(mode == 1 ? a.Hi : a.Ho, mode == 1 ? 8 : 4);
-  a.ncgb = cdiv(a.C / Elem<T>::kPerVec, CG);
-  const int ntiles = N * a.ntx * a.nty;
-  if (mode == 0) {
-    DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_fwd_kernel<T, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F));
-    hipLaunchKernelGGL((dws2_fwd_kernel<T, CG>), dim3(ntiles * a.ncgb), dim3(256), LDS_F, st, (const T*)p0, ld0, wp, (T*)out, ldout, a);
-  } else if (mode == 1) {
-    int tpb = 1;
-    const int rows = s2_dgrad_plan(Elem<T>::kPerVec, a.C, N, a.Hi, a.Wi, &tpb);
-    bs.rows = rows;
-    if (rows_out) *rows_out = rows;
-    if (bs.wslab != nullptr) {
-      constexpr int LDS_DW = LDS_D > FOLD ? LDS_D : FOLD;
-      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_dgrad_kernel<T, CG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DW));
-      hipLaunchKernelGGL((dws2_dgrad_kernel<T, CG, true>), dim3(rows * a.ncgb), dim3(256), LDS_DW, st, (const T*)p0, ld0, wp, (const T*)p1, ld1, (T*)out, ldout, a, bs, ntiles, tpb);
-    } else {
-      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_dgrad_kernel<T, CG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_D));
-      hipLaunchKernelGGL((dws2_dgrad_kernel<T, CG, false>), dim3(rows * a.ncgb), dim3(256), LDS_D, st, (const T*)p0, ld0, wp, (const T*)p1, ld1, (T*)out, ldout, a, bs, ntiles, tpb);
+struct S2 {
+  static constexpr int TW = 8 * (32 / CG);
+  static constexpr int LDS_F = lds_bytes(9, 2 * TW + 1, CG);          // forward / wgrad halo
+  static constexpr int LDS_D0 = lds_bytes(5, TW / 2 + 1, CG);         // dgrad dy tile
+  static constexpr int FOLD2 = (128 / CG) * 2 * CG * Elem<T>::kPerVec * (int)sizeof(float);   // fused BN statistics fold
+  static constexpr int LDS_D = LDS_D0 > FOLD2 ? LDS_D0 : FOLD2;
+  static constexpr int FOLD = (128 / CG) * 9 * CG * Elem<T>::kPerVec * (int)sizeof(float);
+  // the kernels' shape arguments; their grid is 8 x TW tiles over dx (data gradient) or 4 x TW tiles over the output (forward, weight gradient)
+  static S2Args args(int C, int Hi, int Wi, bool dgrad, const float* pscale, const float* pshift, int prelu) {
+    S2Args a;
+    a.pscale = pscale; a.pshift = pshift; a.prelu = prelu;
+    a.Hi = Hi; a.Wi = Wi; a.Ho = (Hi - 1) / 2 + 1; a.Wo = (Wi - 1) / 2 + 1; a.C = C;
+    a.ncgb = cdiv(C / Elem<T>::kPerVec, CG); a.ntx = cdiv(dgrad ? Wi : a.Wo, TW); a.nty = dgrad ? cdiv(Hi, 8) : cdiv(a.Ho, 4);
+    return a;
+  }
+  template <bool WG, int LDS>
+  static void dgrad(const DwCall& c, const S2Args& a, const DwBnStats& bs, int ntiles, int tpb) {
+    DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_dgrad_kernel<T, CG, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    hipLaunchKernelGGL((dws2_dgrad_kernel<T, CG, WG>), dim3(bs.rows * a.ncgb), dim3(256), LDS, c.st, (const T*)c.in, c.ldin, c.wp, (const T*)c.addend,
+                       c.ldadd, (T*)c.out, c.ldout, a, bs, ntiles, tpb);
+  }
+
+  static int call(const DwCall& c) {
+    const S2Args a = args(c.C, c.Hi, c.Wi, c.flip, c.flip ? nullptr : c.pscale, c.pshift, c.prelu);
+    const int ntiles = c.N * a.ntx * a.nty;
+    if (!c.flip) {
+      DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_fwd_kernel<T, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F));
+      hipLaunchKernelGGL((dws2_fwd_kernel<T, CG>), dim3(ntiles * a.ncgb), dim3(256), LDS_F, c.st, (const T*)c.in, c.ldin, c.wp, (T*)c.out, c.ldout, a);
+      return 0;
     }
-  } else {
+    int tpb = 1;
+    DwBnStats bs = c.bs;
+    bs.rows = s2_dgrad_plan(Elem<T>::kPerVec, a.C, c.N, a.Hi, a.Wi, &tpb);
+    if (bs.wslab != nullptr) dgrad<true, (LDS_D > FOLD ? LDS_D : FOLD)>(c, a, bs, ntiles, tpb);
+    else dgrad<false, LDS_D>(c, a, bs, ntiles, tpb);
+    return 0;
+  }
+
+  // weight-gradient partial rows into c.slab; returns their number
+  static int wgrad(const DwWgradCall& c) {
     constexpr int LDS_W = LDS_F > FOLD ? LDS_F : FOLD;
+    const S2Args a = args(c.C, c.Hi, c.Wi, false, c.pscale, c.pshift, c.prelu);
+    const int ntiles = c.N * a.ntx * a.nty;
     DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dws2_wgrad_kernel<T, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W));
     long tpb = ((long)ntiles * a.ncgb + 256) / 512;      // ~512 workgroups, as the stride-1 planner
     if (tpb < 1) tpb = 1;
     while (cdiv(ntiles, tpb) > DWT_MAX_ROWS) ++tpb;
     const int rows = cdiv(ntiles, tpb);
-    *rows_out = rows;
-    hipLaunchKernelGGL((dws2_wgrad_kernel<T, CG>), dim3(rows * a.ncgb), dim3(256), LDS_W, st, (const T*)p0, ld0, (const T*)p1, ld1, slab, a, ntiles, (int)tpb);
+    hipLaunchKernelGGL((dws2_wgrad_kernel<T, CG>), dim3(rows * a.ncgb), dim3(256), LDS_W, c.st, (const T*)c.x, c.ldx, (const T*)c.dy, c.lddy, c.slab, a,
+                       ntiles, (int)tpb);
+    return rows;
   }
-}
+};
 
+// the two launchers of a call's dtype and channel count (one table, so that a pair's kernels are instantiated together, as they always were)
+struct S2Launch { int (*call)(const DwCall&); int (*wgrad)(const DwWgradCall&); };
 template <typename T>
-static void launch2(int mode, const S2Args& a, int N, const void* p0, int ld0, const float* wp, const void* p1, int ld1, void* out,
-                    int ldout, float* slab, int* rows_out, hipStream_t st, const DwBnStats& bs) {
-  const int cg = pick_cg(a.C / Elem<T>::kPerVec);
-  if (cg == 32) launch3<T, 32>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, rows_out, st, bs);
-  else if (cg == 16) launch3<T, 16>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, rows_out, st, bs);
-  else launch3<T, 8>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, rows_out, st, bs);
+static S2Launch s2_launch_cg(int C) {
+  const int cg = pick_cg(C / Elem<T>::kPerVec);
+  if (cg == 32) return {S2<T, 32>::call, S2<T, 32>::wgrad};
+  if (cg == 16) return {S2<T, 16>::call, S2<T, 16>::wgrad};
+  return {S2<T, 8>::call, S2<T, 8>::wgrad};
 }
+static S2Launch s2_launch(int dtype, int C) { return dtype == DC_BF16 ? s2_launch_cg<bf16>(C) : s2_launch_cg<float>(C); }
 
 }  // namespace
 
-// mode 0: forward (p0 = x -> out = y); mode 1: data gradient (p0 = dy, p1 = addend or null -> out = dx);
-// mode 2: weight gradient partial rows (p0 = x, p1 = dy -> slab, *rows_out rows; reduce with dw_tile_reduce)
-int launch_dw_tile_s2(int dtype, int mode, int N, int Hi, int Wi, int C, const void* p0, int ld0, const float* wp, const void* p1, int ld1,
-                      void* out, int ldout, float* slab, int* rows_out, hipStream_t st, const float* pscale, const float* pshift, int prelu,
-                      const DwBnStats* bnstats) {
-  DwBnStats bs;
-  if (bnstats != nullptr && mode == 1) bs = *bnstats; else { bs.slab = nullptr; bs.y = nullptr; bs.ldy = 0; bs.mean = bs.invstd = bs.mscale = bs.mshift = nullptr; bs.relu = 0; bs.rows = 0; bs.wslab = nullptr; }
-  S2Args a;
-  a.pscale = mode == 1 ? nullptr : pscale; a.pshift = pshift; a.prelu = prelu;
-  a.Hi = Hi; a.Wi = Wi; a.Ho = (Hi - 1) / 2 + 1; a.Wo = (Wi - 1) / 2 + 1; a.C = C;
-  a.ncgb = a.ntx = a.nty = 0;
-  DC_REQUIRE((long)N * Hi * Wi < (1L << 31), "dc_dwconv: tensor too large for the tiled stride-2 path");
-  int rows = 0;
-  if (dtype == DC_BF16) launch2<bf16>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, &rows, st, bs);
-  else launch2<float>(mode, a, N, p0, ld0, wp, p1, ld1, out, ldout, slab, &rows, st, bs);
-  if (rows_out) *rows_out = rows;
-  DC_LAUNCHED(mode == 0 ? "dw_tile_s2_fwd" : mode == 1 ? "dw_tile_s2_dgrad" : "dw_tile_s2_wgrad");
+// forward (c.in = x -> c.out = y) or, with c.flip, data gradient (c.in = dy [Ho,Wo], c.addend or null -> c.out = dx [Hi,Wi])
+int launch_dw_tile_s2(const DwCall& c) {
+  DC_REQUIRE((long)c.N * c.Hi * c.Wi < (1L << 31), "dc_dwconv: tensor too large for the tiled stride-2 path");
+  s2_launch(c.dtype, c.C).call(c);
+  DC_LAUNCHED(c.flip ? "dw_tile_s2_dgrad" : "dw_tile_s2_fwd");
   return 0;
+}
+
+// weight gradient: partial rows into c.slab, reduced into c.grad_w
+int launch_dw_tile_s2_wgrad(const DwWgradCall& c) {
+  DC_REQUIRE((long)c.N * c.Hi * c.Wi < (1L << 31), "dc_dwconv: tensor too large for the tiled stride-2 path");
+  const int rows = s2_launch(c.dtype, c.C).wgrad(c);
+  DC_LAUNCHED("dw_tile_s2_wgrad");
+  return dw_tile_reduce(c.slab, c.grad_w, rows, c.C, c.st);
 }
 
 // workgroups per channel block of the stride-2 data-gradient kernel = slab rows of the sums that ride along (statistics, weight-gradient rows)

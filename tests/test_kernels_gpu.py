@@ -1078,13 +1078,14 @@ DW_CASES = [("s1", 728, 1, 1, 2, 12, 10), ("s2", 128, 2, 1, 2, 16, 12), ("d2", 1
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", DW_CASES, ids=[c[0] for c in DW_CASES])
 def test_depthwise(case, dtype, expect=None):
-    """expect: call -> the launches that serve it (the tests that force a kernel pass it).  Pinned here for the default planner: the pipe*
-    cases (extents multiples of 8, at least 64 channels) run their bf16 data gradients on dwpipe.hip and their fp32 ones on the tiled kernel."""
+    """expect: call -> the launches that serve it; the tests that force a kernel override entries.  Pinned here for the default planner: the
+    stride-2 layers run on dwtile_s2.hip, the stride-1 ones on dwtile.hip, except that the pipe* cases (extents multiples of 8, at least 64
+    channels) run their bf16 data gradients on dwpipe.hip."""
     cname, Cc, stride, dil, N, H, W = case
-    expect = dict(expect or {})
-    if cname.startswith("pipe"):
-        dg = "dwpipe_dgrad" if dtype == torch.bfloat16 else "dw_tile_dgrad"
-        expect.update(dgrad=dg, dgrad_add=dg, dgrad_wgrad=[dg, "dw_tile_reduce"])
+    fam = "dw_tile_s2" if stride == 2 else "dw_tile"
+    dg = "dwpipe_dgrad" if stride == 1 and cname.startswith("pipe") and dtype == torch.bfloat16 else f"{fam}_dgrad"
+    expect = dict(dict(fwd=f"{fam}_fwd", dgrad=dg, dgrad_add=dg, wgrad=[f"{fam}_wgrad", "dw_tile_reduce"], dgrad_wgrad=[dg, "dw_tile_reduce"]),
+                  **(expect or {}))
 
     def check(call, names):
         if call in expect:
@@ -1146,6 +1147,58 @@ def test_depthwise(case, dtype, expect=None):
         assert torch.equal(from_nhwc(gxv2), from_nhwc(gxv))
         assert_close(gw2.cpu(), gw_ref, dtype, f32=2e-4, bf16=2e-3)
         np.testing.assert_allclose(gw2.cpu().numpy(), gw.cpu().numpy(), rtol=2e-5, atol=2e-5 * float(gw.abs().max()))
+
+
+DW_GENERIC_CASES = [("d3", 32, 1, 3, 1, 9, 11), ("s2d2", 32, 2, 2, 1, 9, 11)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", DW_GENERIC_CASES, ids=[c[0] for c in DW_GENERIC_CASES])
+def test_depthwise_generic_kernel(case, dtype):
+    """The dilations and strides no tiled kernel serves run on the generic register kernels (dw_reg_*): test_depthwise's checks against
+    autograd, without the fused data + weight gradient (dc_dwconv_dgrad_wgrad_rows is 0 here)."""
+    cname, Cc, stride, dil, N, H, W = case
+    dt = L.dtype_code(dtype)
+    assert L.load().dc_dwconv_dgrad_wgrad_rows(dt, Cc, stride, dil, N, H, W) == 0
+    x = q(rnd(N, Cc, H, W, seed=1), dtype)
+    w = rnd(Cc, 1, 3, 3, seed=2, scale=1 / 3)
+    xr = x.clone().requires_grad_(True)
+    wr = w.clone().requires_grad_(True)
+    yref = F.conv2d(F.pad(xr, (dil, dil, dil, dil)), wr, None, stride, 0, dil, groups=Cc)
+    Ho, Wo = yref.shape[2:]
+    gy = q(rnd(*yref.shape, seed=3), dtype)
+    gx_ref, gw_ref = torch.autograd.grad(yref, (xr, wr), gy)
+    wm = w.to(dev())
+    wd = torch.empty(9 * Cc, device=dev())
+    L.call("dc_dwconv_pack_weights", Cc, vptr(wm), vptr(wd), S())
+    _, xv = to_nhwc(x, dtype, ld=Cc + 8)
+    _, yv = empty_nhwc(N, Ho, Wo, Cc, dtype)
+    with served("fwd") as names:
+        L.call("dc_dwconv_fwd", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(wd), vptr(yv), Cc, None, None, 0, S())
+    assert_served(names, "dw_reg_fwd", f"{cname} fwd")
+    torch.cuda.synchronize()
+    assert_close(from_nhwc(yv), yref.detach(), dtype, bf16=1e-2)
+    _, gyv = to_nhwc(gy, dtype)
+    add = q(rnd(N, Cc, H, W, seed=4), dtype)
+    _, addv = to_nhwc(add, dtype)
+    _, gxv = empty_nhwc(N, H, W, Cc, dtype)
+    with served("dgrad") as names:
+        L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), None, 0, vptr(gxv), Cc, S())
+    assert_served(names, "dw_reg_dgrad", f"{cname} dgrad")
+    torch.cuda.synchronize()
+    assert_close(from_nhwc(gxv), gx_ref, dtype, bf16=1e-2)
+    with served("dgrad_add") as names:
+        L.call("dc_dwconv_dgrad", dt, Cc, stride, dil, N, H, W, vptr(gyv), Cc, vptr(wd), vptr(addv), Cc, vptr(gxv), Cc, S())
+    assert_served(names, "dw_reg_dgrad", f"{cname} dgrad_add")
+    torch.cuda.synchronize()
+    assert_close(from_nhwc(gxv), gx_ref + add, dtype, bf16=1e-2)
+    ws = torch.empty(L.load().dc_dwconv_wgrad_workspace(Cc, N, H, W, stride), dtype=torch.uint8, device=dev())
+    gw = torch.full((Cc, 1, 3, 3), float("nan"), device=dev())
+    with served("wgrad") as names:
+        L.call("dc_dwconv_wgrad", dt, Cc, stride, dil, N, H, W, vptr(xv), Cc + 8, vptr(gyv), Cc, vptr(ws), vptr(gw), None, None, 0, S())
+    assert_served(names, ["dw_reg_wgrad", "dw_reg_reduce"], f"{cname} wgrad")
+    torch.cuda.synchronize()
+    assert_close(gw.cpu(), gw_ref, dtype, f32=2e-4, bf16=2e-3)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
