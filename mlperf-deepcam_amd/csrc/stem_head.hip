@@ -1225,10 +1225,10 @@ static int head_bwd_impl(int dtype, int N, int Cin, int Hi, int Wi, const void* 
     DC_REQUIRE(bn_mean && bn_invstd && (!bn_relu || (bn_mscale && bn_mshift)), "dc_head_bwd: missing BatchNorm vectors");
     HeadDgradBst b{(const bf16*)bn_y, bn_ldy, bn_mean, bn_invstd, bn_mscale, bn_mshift, bn_relu, bn_slab, chunks, nullptr, nullptr, nullptr, 0.f, nullptr};
     if (wg_rides) {
-      // one slab row (32 x 256 floats) per workgroup in the product image's space of the workspace (unused by the fused forward): at most
-      // chunks / 2 rows of 32 KiB fit its M x 128 bytes
-      int g2 = chunks / 2 < 512 ? chunks / 2 : 512;        // (252 registers: two workgroups per CU, one round)
-      if (g2 < 1) g2 = 1;
+      // one slab row (32 x 256 floats) per workgroup in the product image's space of the workspace (unused by the fused forward): P / 256
+      // rows of 32 KiB fit its P x 128 bytes (P >= 256 here).  Not chunks / 2: with an even number of chunks and a ragged last one that is
+      // one row more, and the row lands on the first pixels of the gathered image behind it, which dc_head_bwd_bnin_apply still reads
+      const int g2 = P / 256 < 512 ? (int)(P / 256) : 512;        // (252 registers: two workgroups per CU, one round)
       b.wslab = ws.P;
       static_assert(HEAD_NP == 32, "product image");
       DC_ONCE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_dgrad_kernel<HD_SUMS_WG>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * TRI_QUAD));

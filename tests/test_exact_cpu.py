@@ -1,6 +1,7 @@
-"""The exact-data kernel tests (test_exact_gpu.py) before any kernel is involved:
+"""The exact-data kernel tests (test_exact_gpu.py, test_exact_ends_gpu.py) before any kernel is involved:
 
-  - the preconditions of util_exact.py hold for every case the GPU file launches, so a failure there is the kernel's;
+  - the preconditions of util_exact.py hold for every case the GPU files launch, so a failure there is the kernel's; the extents of the
+    stem and the head reach the plans, blocks and caps they are there for;
   - the exact comparison rejects the mistakes hand-written tile kernels make (lost pixels in the statistics or the weight gradient, a lost
     8-channel vector of one tap, a pixel taken from its neighbour), and the statistics check of test_conv_fwd_dgrad_wgrad (rtol = 2e-3 on
     Gaussian data) accepts the first of them at the benchmark's pixel count: the gap the exact tests close;
@@ -56,6 +57,81 @@ def test_preconditions_hold_at_the_ends_of_the_network():
     U.need_exact(x.mean((2, 3)), torch.float32, "avgpool")            # 1 / 128: exact
     U.need_exact(x.sum((0, 2, 3)), torch.float32, "colsum", bound=4 * N * H * W)
     U.need_exact(x + 128 * U.ints((N, Cc, 1, 1), 2).double() / (H * W), torch.bfloat16, "avgpool_bwd_add")
+
+
+@pytest.mark.parametrize("name,shape,budget", [pytest.param(*c, id=c[0]) for c in U.STEM_ENDS])
+def test_preconditions_hold_for_the_stem_extents(name, shape, budget):
+    """test_exact_ends_gpu.py's stem cases: exact, and the data reach what the case is there for: most outputs non-zero, and where a side
+    is odd the ky = 2 / kx = 2 taps of the last output row / column lie on padding while the row / column in front of it is data."""
+    N, Cin, H, W = shape
+    c = U.stem_case(shape, budget)
+    b = U.stem_preconditions(c, name)
+    print(name, b)
+    assert b["gx"] <= 128 and b["nonzero_y"] > 0.5
+    Ho, Wo, P = U.stem_out(shape)
+    assert tuple(c.y.shape) == (N, 32, Ho, Wo)
+    if H % 2:
+        assert 2 * (Ho - 1) - 1 + 2 == H and bool(c.x[:, :, H - 1].abs().sum() > 0)
+    if W % 2:
+        assert 2 * (Wo - 1) - 1 + 2 == W and bool(c.x[:, :, :, W - 1].abs().sum() > 0)
+    assert bool((c.gw.abs().sum((0, 2, 3)) > 0).all()) and bool((c.gx.abs().sum((0, 2, 3)) > 0).all())     # every input channel takes part
+
+
+def test_stem_extents_reach_every_weight_gradient_plan():
+    """stem_wgrad_plan mirrors stem_ppb (the GPU test compares it with dc_stem_wgrad_workspace): among the extents there are one workspace
+    row, several rows with a ragged last one, full rows only, a last batch below 64 pixels, and two batches per row."""
+    plans = {name: U.stem_wgrad_plan(U.stem_out(shape)[2]) for name, shape, _ in U.STEM_ENDS}
+    assert plans["one_row_1x7"] == (64, 1, 4) and plans["two_columns_9x2"] == (64, 1, 15)
+    assert plans["odd_31x33"] == (64, 5, 16) and plans["p240"] == (64, 4, 48) and plans["w259"] == (64, 7, 6) and plans["w258"] == (64, 7, 3)
+    assert plans["p512"] == (64, 8, 64)
+    assert plans["ppb128_513x513"] == (128, 517, 1)
+    blocks = {name: (U.stem_out(shape)[2] + 255) // 256 for name, shape, _ in U.STEM_ENDS}       # dc_stem_stat_rows
+    assert blocks["odd_31x33"] == 2 and blocks["p512"] == 2 and blocks["p240"] == 1 and blocks["ppb128_513x513"] == 259
+    cins = sorted({shape[1] for _, shape, _ in U.STEM_ENDS})
+    assert cins == [1, 3, 5, 8, 10, 12, 16]
+    assert {(c + 3) // 4 * 4 for c in cins} == {4, 8, 12, 16}          # every CP instantiation of the data gradient, padded and not
+
+
+@pytest.mark.parametrize("name,shape", [pytest.param(*c, id=c[0]) for c in U.HEAD_ENDS])
+def test_preconditions_hold_for_the_head_extents(name, shape):
+    """test_exact_ends_gpu.py's head cases: the plain head and the head on an unstored BatchNorm output are exact, the riders' sums too;
+    the integer logits tie (the first-index tie-break is exercised) and every class is predicted."""
+    N, Cin, H, W = shape
+    e = U.head_ends_case(shape)
+    b = U.head_ends_preconditions(e, name)
+    assert b["y"] <= U.HEAD_LOGIT_BOUND and b["gx"] <= 27
+    P = N * H * W
+    assert (P >= 256) == (name != "p255")
+    for s in [e.score] + [p.score for p in e.bn]:
+        assert len(torch.unique(s.pred)) == 3
+        assert int(s.counts.sum(0)[:6].sum()) == 4 * P and torch.equal(s.classes.sum(1), torch.full((N,), 4 * H * W))
+    top = e.c.y.sort(1).values
+    assert int((top[:, 2] == top[:, 1]).sum()) > 0                        # ties for the maximum
+    for relu in (0, 1):
+        s0, s1 = U.bn_bwd_sums(e.c.gx, e.rin, relu, name)
+        assert bool(s1.abs().max() > 0)
+
+
+def test_head_matrix_reference_equals_autograd():
+    """head_matrix_case (how the reference of HEAD_BIG is built: unfold, one matrix product per pixel, float32) against float64
+    conv_transpose2d + autograd on the same data, at a small extent with ragged everything."""
+    shape = (2, 256, 5, 7)
+    N, Cin, H, W = shape
+    m = U.head_matrix_case(shape)
+    nchw = lambda t: t.reshape(N, H, W, Cin).permute(0, 3, 1, 2).double()  # noqa: E731
+    a, w, gl = nchw(m.a).requires_grad_(True), m.w.double().requires_grad_(True), m.gl.double()
+    gx, gw = torch.autograd.grad(F.conv_transpose2d(a, w, None, 2, 1, 1), (a, w), gl)
+    assert torch.equal(nchw(m.dx), gx) and torch.equal(m.gw.double(), gw)
+    r = types.SimpleNamespace(y=nchw(m.y), mean=m.mean.double(), invstd=m.invstd.double(), mscale=m.scale.double(), mshift=m.shift.double())
+    s0, s1 = U.bn_bwd_sums(gx, r, 1, "matrix")
+    assert torch.equal(m.s0, s0) and torch.equal(m.s1, s1)
+
+
+def test_head_big_case_binds_both_grid_caps():
+    """Shape arithmetic only (the reference itself is built in the GPU test, and checked there by head_matrix_case's own conditions)."""
+    N, Cin, H, W = U.HEAD_BIG
+    chunks = (N * H * W + 127) // 128
+    assert chunks > 2048 and chunks // 2 > 512 and N * H * W * 4 * 3 < 2 ** 31
 
 
 def test_preconditions_hold_for_the_batchnorm_backward_riders():

@@ -17,7 +17,10 @@ Covered: dense convolutions under the default planner (CONV_CASES, fp32 and bf16
 weight gradient); the forced variants igemm256 = 2, pw384 = 2 .. 5, pw224 = 2 / 3 (dc_conv_fwd_kn / dc_conv_dgrad_kn, compact slab),
 igemm256p, thin_tile, dc_conv_fwd_dilated_group; the weight-gradient families (GROUP_CASES, WG384_CASES, TCONV384_CASES, FOLD_CASES);
 depthwise (DW_CASES, PIPE_CASES with dw_pipe 0 / 1 / 2); dc_bn_stats, dc_colsum, dc_sum_hw, dc_avgpool_fwd / dc_avgpool_bwd_add; stem and
-head.  dc_dwconv_fwd has no statistics slab in its C ABI, so "forward with slab" is the forward alone for the depthwise layers.
+head at the one shape test_kernels_gpu.py gives each (20 x 28 and 6 x 9: less than one block, tile or chunk of their kernels; odd, ragged and
+multi-tile extents, thinner stems, the loss / score / prediction epilogues, the head on an unstored BatchNorm output and the extent at which
+the head's grid caps bind are in test_exact_ends_gpu.py).  dc_dwconv_fwd has no statistics slab in its C ABI, so "forward with slab" is
+the forward alone for the depthwise layers.
 
 Second tier, built because reading the kernels shows every operation exact on this data (integer mean, power-of-two invstd and scale,
 integer shift; the epilogues are gm = mask ? g : 0, a += gm, b = fma(gm, (y - mean) * invstd, b): igemm.hip, igemm256.hip, BnAcc::add in
@@ -28,7 +31,8 @@ dwtile_common.h, dwpipe.hip, head_dgrad_kernel in stem_head.hip; a sum row is fp
   - dc_dwconv_dgrad_wgrad_bnres (relu 0, 1, and 2 where dc_dwconv_dgrad_wgrad_bnres_masked serves) with and without an addend on the
     dilation-1 PIPE_CASES, the stored input built as relu(bn(ybn) + residual); dc_dwconv_dgrad_wgrad_bnres_sum and
     dc_dwconv_dgrad_bnstats_wgrad_sum on the shapes test_kernels_gpu.py and test_dw_masked_gradient_gpu.py give them;
-  - dc_head_bwd_bnstats at the shape of test_head, on the streaming and on the tiled data-gradient kernel;
+  - dc_head_bwd_bnstats at the shape of test_head, on the streaming and on the tiled data-gradient kernel (at more than one chunk, and
+    dc_head_bwd_bnin with the weight gradient riding on the statistics pass: test_exact_ends_gpu.py);
   - dc_sepconv_fwd on SEPFWD_CASES, with generators of its own (util_exact.sep_case): at 65 536 pixels and more the sums of squares pass
     2^24 with the budget and the prologue range of the other cases.
 
@@ -37,7 +41,10 @@ Left out:
     the pointwise tables: they run at the workload's full extent (27 648 pixels of 728 channels);
   - dc_pw_bn_bwd: it applies the BatchNorm backward, its coefficients carry inv_count = 1.0f / count (pwbwd.hip), and the pixel counts of
     its cases (2 x 192 x 192, 257 x 257, ...) are no powers of two: a rounded reciprocal;
-  - BatchNorm finalize / apply (1 / sqrt), the loss and every softmax consumer, the optimizers, and the workload's full extents.
+  - dc_head_bwd_bnin_apply, for the same reason (1 / count; the head's extents are no powers of two either);
+  - BatchNorm finalize / apply (1 / sqrt), the loss and every softmax consumer (test_exact_ends_gpu.py holds the head's fused loss, score
+    and prediction to the float64 logits' classes and counts exactly, and to the project's tolerances in loss, gradient and confidence),
+    the optimizers, and the workload's full extents.
 
 The tests that override options restore them in `finally` (dc_reset_options where a case brings its own list of overrides)."""
 import ctypes as C

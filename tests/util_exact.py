@@ -1,4 +1,4 @@
-"""Exactly representable test data for the kernel tests (test_exact_cpu.py, test_exact_gpu.py): generators, float64 references and the
+"""Exactly representable test data for the kernel tests (test_exact_cpu.py, test_exact_gpu.py, test_exact_ends_gpu.py): generators, float64 references and the
 preconditions under which a correct kernel must reproduce the reference BIT FOR BIT.
 
 On small-integer data every product, every partial sum in any order or split, and every stored value of a convolution is exactly
@@ -356,16 +356,18 @@ POOL = (2, 2048, 8, 16)         # N, C, H, W
 HEAD_LOGIT_BOUND = 1024
 
 
-@functools.lru_cache(maxsize=1)
-def stem_case():
-    N, Cin, H, W = STEM
-    return conv_case((3, 2, 1, 1, 0, Cin, 32, N, H, W))
+@functools.lru_cache(maxsize=4)
+def stem_case(shape=STEM, budget=BUDGET):
+    """Conv2d(Cin -> 32, k 3, s 2, p 1) at shape = (N, Cin, H, W); budget: the expected number of non-zero weights per output is
+    budget * Cin / 32 (fan = 9 * 32)."""
+    N, Cin, H, W = shape
+    return conv_case((3, 2, 1, 1, 0, Cin, 32, N, H, W), budget=budget)
 
 
-@functools.lru_cache(maxsize=1)
-def head_case():
+@functools.lru_cache(maxsize=8)
+def head_case(shape=HEAD):
     """ConvTranspose2d(256 -> 3, k 3, s 2, p 1, op 1) with dense +-1 weights (budget = fan): logits are fp32 sums of at most 4 * 256 terms."""
-    N, Cin, H, W = HEAD
+    N, Cin, H, W = shape
     c = conv_case((3, 2, 1, 1, 1, Cin, 3, N, H, W), budget=10 ** 9)
     if c.bound["y"] > HEAD_LOGIT_BOUND:
         raise NotExact(f"head: |logit| can reach {c.bound['y']:.0f} > {HEAD_LOGIT_BOUND}")
@@ -378,6 +380,161 @@ def head_preconditions(c):
     _need(b["y"] <= HEAD_LOGIT_BOUND and b["gw"] < F32_EXACT, "head sums too large", "head")
     _need(b["gx"] <= BF16_EXACT and bf16_holds(c.gx) and bf16_holds(c.x) and bf16_holds(c.w) and f32_holds(c.gw), "head stores", "head")
     return b
+
+
+# ------------------------------------------------------------------------------------------------------------------ the ends, off their one shape
+# test_exact_ends_gpu.py: the stem and the head at the extents where their kernels take another path.  Ho = (H - 1) / 2 + 1 and Wo likewise,
+# P = N * Ho * Wo output pixels.  The weight-gradient kernel gives a workgroup (= a workspace row) ppb pixels in 64-pixel batches
+# (stem_wgrad_plan below mirrors stem_ppb of stem_head.hip): ppb = 64 up to 65 536 pixels, so only the last extent has two batches per row.
+STEM_THICK = 96     # budget of the small extents: a third of the weights non-zero (the default 24 leaves a one-channel layer 0.75 weights per output)
+STEM_ENDS = [
+    # name, (N, Cin, H, W), budget            what it exercises                                                      weight-gradient rows
+    ("odd_31x33", (1, 16, 31, 33), STEM_THICK),      # both sides odd; P = 272: the second 256-pixel block holds 16 lanes    5, the last ragged: a 16-pixel batch
+    ("odd_h_21x28", (2, 16, 21, 28), STEM_THICK),    # odd H only; P = 308                                                   5, the last ragged: a 52-pixel batch
+    ("odd_w_20x27", (2, 16, 20, 27), STEM_THICK),    # odd W only; P = 280                                                   5, the last ragged: a 24-pixel batch
+    ("p512", (2, 16, 32, 32), STEM_THICK),           # two full blocks, no ragged lane                                       8 full rows
+    ("p240", (1, 16, 32, 30), STEM_THICK),           # a single partial block                                                4, the last ragged: a 48-pixel batch
+    ("w259", (1, 16, 5, 259), STEM_THICK),           # odd W above 256: three pair chunks per row, the last of two pairs     7, the last ragged: a 6-pixel batch
+    ("w258", (1, 16, 5, 258), STEM_THICK),           # even W above 256: three pair chunks per row, the last of one pair     7, the last ragged: a 3-pixel batch
+    ("one_row_1x7", (1, 16, 1, 7), STEM_THICK),      # one input row, Ho = 1; P = 4                                          ONE row, a 4-pixel batch
+    ("two_columns_9x2", (3, 16, 9, 2), STEM_THICK),  # two input columns, Wo = 1; P = 15                                     ONE row, a 15-pixel batch
+    # added for the weight gradient: P = 66 049 > 65 536, so ppb = 128: 517 rows of two 64-pixel batches, the last row one pixel; five pair
+    # chunks per row in the data gradient.  Ranges narrowed: the default budget (a twelfth of the weights non-zero), or the bound on the
+    # sums of squares of that many pixels passes 2^24
+    ("ppb128_513x513", (1, 16, 513, 513), BUDGET),
+]
+STEM_ENDS += [(f"cin{cin}_{h}x{w}", (n, cin, h, w), STEM_THICK) for (n, h, w) in ((1, 31, 33), (2, 20, 28)) for cin in (1, 3, 5, 8, 10, 12)]
+
+
+def stem_out(shape):
+    N, Cin, H, W = shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return Ho, Wo, N * Ho * Wo
+
+
+def stem_wgrad_plan(P):
+    """(pixels per workspace row, rows, pixels of the last 64-pixel batch of the last row) of dc_stem_wgrad."""
+    ppb = ((P + 1023) // 1024 + 63) // 64 * 64
+    rows = (P + ppb - 1) // ppb
+    last = P - (rows - 1) * ppb
+    return ppb, rows, (last - 1) % 64 + 1
+
+
+def stem_preconditions(c, name="stem"):
+    """preconditions() without the accumulate and bias modes the stem does not have: y and gx are stored once."""
+    b = c.bound
+    for key in ("y", "gx", "gw", "sum_y", "sum_yy"):
+        _need(b[key] < F32_EXACT, f"fp32 partial sums of {key} reach {b[key]:.0f} >= 2^24", name)
+    _need(b["y"] <= BF16_EXACT, f"|y| can reach {b['y']:.0f} > 256 (bf16 store)", name)
+    for t in (c.x, c.w, c.gy, c.y):
+        _need(bf16_holds(t), "an operand or a stored result is not a bf16 number", name)
+    _need(f32_holds(c.gw) and f32_holds(c.gx), "a gradient is not an fp32 number", name)      # dx leaves as NCHW fp32 in both modes
+    return b
+
+
+HEAD_ENDS = [
+    # name, (N, Cin, H, W)                            what it exercises
+    ("chunks22_tiles5x3", (2, 256, 20, 70)),        # 2800 pixels: 21 full 128-pixel chunks and one of 112; 5 x 3 tiles with ragged columns
+    ("two_strips", (1, 256, 9, 229)),               # eight tile columns: two strips of HF_TILES = 6; a ragged tile row
+    ("one_tile_p256", (1, 256, 8, 32)),             # exactly one tile, P = 256: the first extent at which the weight gradient rides
+    ("p255", (1, 256, 5, 51)),                      # P = 255: the last extent at which it does not
+    ("three_samples", (3, 256, 7, 37)),             # three samples, nothing aligned
+]
+# both grid caps of head_bwd_impl bind: 266 240 pixels = 2080 chunks > 2048 workgroups, and 1040 > 512 weight-gradient slab rows.  bf16 only.
+# Its reference (head_big_case) took 1.5 s on the CPU this was written on (float32 products of small integers and halves, every partial sum exact)
+HEAD_BIG = (1, 256, 520, 512)
+
+
+def head_weights(seed=2):
+    return signs((256, 3, 3, 3), seed, fan=1)
+
+
+def head_score(logits, labels):
+    """What the loss, score and prediction epilogues leave for float64 logits [N][3][H][W]: the first-maximum class, the nine confusion counts
+    and the three class counts per sample, the per-sample sums of the weighted cross-entropy, the gradient of its mean, and the
+    probability of the predicted class (oracle.loss_metric throughout)."""
+    import numpy as np
+    from oracle import loss_metric as olm
+    cw = olm.class_weights(-0.125)
+    N = logits.shape[0]
+    pred = torch.from_numpy(olm.argmax_first(logits))
+    counts = torch.tensor(np.stack([np.concatenate(olm.confusion_counts(pred[n].numpy(), labels[n].numpy())) for n in range(N)]))
+    classes = torch.stack([(pred == k).sum((1, 2)) for k in range(3)], 1)
+    return types.SimpleNamespace(pred=pred, counts=counts, classes=classes, loss=olm.weighted_ce_map(logits, labels, cw).sum((1, 2)),
+                                 mean_loss=float(olm.fp_loss(logits, labels, cw)), grad=olm.fp_loss_grad(logits, labels, cw),
+                                 conf=torch.softmax(logits, 1).amax(1), cw=cw)
+
+
+@functools.lru_cache(maxsize=8)
+def head_ends_case(shape):
+    """Everything test_exact_ends_gpu.py compares the head with at one extent, float64 and computed once: head_case (logits, dx, gw on
+    x, w, dlogits = gy); labels and head_score of the logits; bn[relu]: the head on a = act(x * scale + shift), x taken as the raw output
+    in front of a BatchNorm with bn_prologue coefficients (halves up to 5: logits and weight gradient stay exact; dx does not depend on
+    the input); rider: independent bn_rider data for dc_head_bwd_bnstats; rin: the rider of the unstored form (the BatchNorm input is x,
+    the mask coefficients are scale / shift)."""
+    N, Cin, H, W = shape
+    c = head_case(shape)
+    labels = torch.randint(0, 3, (N, 2 * H, 2 * W), generator=_gen(7))
+    scale, shift = (t.double() for t in bn_prologue(Cin, 6))
+    mean, invstd = bn_moments(Cin, 8)
+    e = types.SimpleNamespace(c=c, labels=labels, scale=scale, shift=shift, score=head_score(c.y, labels), rider=bn_rider(shape), bn=[],
+                              rin=types.SimpleNamespace(y=c.x, mean=mean.double(), invstd=invstd.double(), mscale=scale, mshift=shift))
+    op = lambda a, b: conv_ref(a, b, None, 3, 2, 1, 1, True)  # noqa: E731
+    for relu in (0, 1):
+        a = c.x * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        if relu:
+            a = a.clamp_min(0)
+        y, gx, gw = _fwd_and_grads(op, a, c.w, c.gy)
+        ya, _, gwa = _fwd_and_grads(op, a.abs(), c.w.abs(), c.gy.abs())
+        e.bn.append(types.SimpleNamespace(a=a, y=y, gx=gx, gw=gw, bound=dict(y=_maxabs(ya), gw=_maxabs(gwa)), score=head_score(y, labels)))
+    return e
+
+
+def head_ends_preconditions(e, name="head"):
+    """head_preconditions, and for the unstored form: the activation a bf16 number, logits and weight gradient (halves) exact in fp32, the
+    data gradient the one of the plain head; every BatchNorm-backward sum exact (bn_bwd_sums raises otherwise)."""
+    b = head_preconditions(e.c)
+    for relu, p in enumerate(e.bn):
+        _need(bf16_holds(p.a) and f32_holds(p.y) and f32_holds(p.gw), "the activation, a logit or the weight gradient is not exact", name)
+        _need(2 * p.bound["y"] < F32_EXACT and 2 * p.bound["gw"] < F32_EXACT, "fp32 partial sums (halves) reach 2^24", name)
+        _need(torch.equal(p.gx, e.c.gx), "the data gradient depends on the input", name)
+        bn_bwd_sums(e.c.gx, e.rider, relu, name)
+        bn_bwd_sums(e.c.gx, e.rin, relu, name)
+    return b
+
+
+def head_big_case():
+    """The head's backward at HEAD_BIG as a 27 x 256 matrix product per pixel, pixel-major ([P][256], the kernels' layout), in float32: the
+    operands are integers and halves, every product and every partial sum of any order is exact, so float32 IS the float64 result here
+    (test_exact_cpu.py checks the construction against head_case at a small extent).  y: the BatchNorm input; a = relu(y * scale + shift):
+    the head's input; dlogits in {-1, 0, 1}; dP: the gathered gradient image (unfold); dx = dP . W, gw = a^T . dP; s0, s1: the float64
+    BatchNorm-backward sums, relu = 1.  Not cached: 1.5 GB."""
+    return head_matrix_case(HEAD_BIG)
+
+
+def head_matrix_case(shape, seeds=(1, 2, 3)):
+    N, Cin, H, W = shape
+    P = N * H * W
+    y = ints((P, Cin), seeds[0])
+    scale, shift = bn_prologue(Cin, 6)
+    mean, invstd = bn_moments(Cin, 8)
+    a = (y * scale + shift).clamp_min(0)
+    w = head_weights(seeds[1])
+    gl = ints((N, 3, 2 * H, 2 * W), seeds[2])
+    dP = F.unfold(gl, 3, 1, 1, 2).permute(0, 2, 1).reshape(P, 27).contiguous()       # [pixel][co * 9 + ky * 3 + kx], zero outside the image
+    wm = w.reshape(Cin, 27)
+    dx = dP @ wm.t()
+    gw = (a.t() @ dP).reshape(Cin, 3, 3, 3)
+    gw_bound = float((a.t() @ dP.abs()).max())
+    xhat = (y - mean) * invstd
+    gm = dx * (a > 0)
+    s0, s1 = gm.double().sum(0), (gm * xhat).double().sum(0)
+    _need(bf16_holds(a) and bf16_holds(dx) and _maxabs(dx) <= BF16_EXACT and bf16_holds(xhat), "big head: a bf16 operand or store is not exact", "head_big")
+    _need(2 * gw_bound < F32_EXACT, "big head: the weight gradient's partial sums (halves) reach 2^24", "head_big")
+    # a slab row adds the 128 pixels of one chunk in fp32; the rows are added in float64 by the test
+    _need(2 * 128 * _maxabs(dx) * _maxabs(xhat) < F32_EXACT, "big head: a chunk's BatchNorm-backward sums reach 2^24", "head_big")
+    return types.SimpleNamespace(shape=shape, y=y, a=a, scale=scale, shift=shift, mean=mean, invstd=invstd, w=w, gl=gl, dP=dP, dx=dx, gw=gw,
+                                 s0=s0, s1=s1, gw_bound=gw_bound)
 
 
 # ------------------------------------------------------------------------------------------------------------------ comparison
