@@ -79,6 +79,7 @@ int dc_reset_options(void);
  *   event shapes and the shape filter (dc_component_shape, dc_event_select, dc_mask_select): cc_shape (every launch of the three calls)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
+ *   track verification (dc_track_match_append, dc_track_match_resolve): cc_track_match (every launch of both calls)
  *   frame renderer (dc_render_frames): render_paint (the outlines of both classes, one byte per source pixel and panel), render_gather
  *     (colour table, graticule and outlines into the RGB bytes)
  *   climatology (dc_climatology_accumulate, dc_climatology_maps): climatology_accumulate_vec (16-byte loads, four lanes per 16-channel
@@ -875,6 +876,63 @@ int dc_track_cycles(int event_cap, int track_cap, int step_cap, int C, int min_f
                     const int64_t* store, const int32_t* track_of, const int64_t* tracks, const int64_t* ntracks, const int64_t* fstore,
                     int64_t* offsets, int64_t* steps, int64_t* step_fields, int64_t* track_fields, int64_t* ncycles, void* workspace,
                     void* stream);
+
+/* Track verification (nn.TrackMatcher; predict.py --verify_tracks): predicted against labelled storm tracks -- how many labelled storms
+ * were found over most of their life, how many predicted ones exist nowhere in the labels, how early or late genesis and decay are.  The
+ * join of three things the device already holds: the pair table of dc_component_overlap per frame, the event numbers of dc_track_append
+ * and the track rows of dc_track_resolve.  Integer arithmetic; equal inputs give equal results however the frames are cut into batches.
+ *   Side a and side b are the two catalogues of ONE overlap call (a: the prediction, b: the labels), each with a tracker of its own; both
+ *   trackers are given the same frames in the same calls, so their frame numbers agree.
+ *   An OVERLAP is a row (rank a, rank b, shared) of frame j's pair table whose two events are stored -- rank below min(ncomp all, cap) of
+ *   its catalogue, event number first_x[j] + rank below event_cap_x -- and have the same class 1 or 2 (column 3 of the trackers' stores;
+ *   the pair table lists pairs of any classes).  It is filed as a LINK (event number a, event number b, shared pixels).
+ *   links     int64 [link_cap][3], kept across calls; the order of the rows is unspecified.  When the store is full, which links are
+ *             dropped is unspecified; every stored row is a true overlap with its full count.
+ *   state     int64 [4], device, kept across calls (zero it to start a series): links stored = min(all, link_cap), links not stored
+ *             because the store was full, frames filed, frames whose pair table had its overflow flag set or whose catalogue (either
+ *             side) was truncated
+ * dc_track_match_append files a batch in ONE launch, behind dc_component_overlap and both dc_track_append calls of that batch on the same
+ * stream: pairs / npairs ([B][pair_cap][3], [B][2]) as the overlap call left them, ncomp_x, first_x and store_x as the catalogues and the
+ * trackers left them.  Samples from n_valid on are not read.
+ * dc_track_match_resolve is called when results are read, after dc_track_resolve of BOTH trackers on the same stream; it reads what those
+ * calls left (track_of_x, tracks_x, ntracks_x; store_a for the frame of a link), changes nothing an append depends on and may run at any
+ * point of a series.  It zeroes what it fills.  A link belongs to the TRACK PAIR (row a, row b) = (track_of_a[event a],
+ * track_of_b[event b]); links with a track_of of -1 on either side are counted and take part in nothing.
+ *   tpairs    int64 [pair_cap][8], zeroed by the call: row a, row b, class, overlaps (links of the pair), common frames (DISTINCT frames
+ *             with at least one link of the pair; merges and splits put several links of one pair into one frame), shared pixels (summed
+ *             over the links), first common frame, last common frame.  The order of the rows is unspecified (sort on the host).
+ *   cover_x   int64 [track_cap_x][2], zeroed by the call (rows without a track stay zero): matched frames = the DISTINCT frames of the
+ *             track in which at least one of its events has a link to any track of the other side with a row; shared pixels = the sum
+ *             over its links.  Accumulated by the link pass itself: exact also when the pair table overflows.
+ *   A track is SCORED when it has a row, its class is 1 or 2 and frames = last - first + 1 >= max(min_frames, 1).  It is MATCHED when
+ *   matched >= 1 and matched * 1024 >= cover_q * frames: the event rule of dc_event_scores with frames in place of pixels.  Coverage, not
+ *   a pairwise overlap ratio, decides: a labelled storm predicted as two tracks with a missed frame in between is still found.
+ *   scores    int64 [2][4], per class 1, 2: hits (scored b tracks that are matched), misses (... that are not), false alarms (scored a
+ *             tracks that are not matched), matched detections (scored a tracks that are)
+ *   counts    int64 [4]: track-pair rows stored, the pair overflow flag, links skipped for a missing track row, 0 (spare).  With at most
+ *             pair_cap distinct track pairs all are stored and the flag is 0, whatever the scheduling (a pair is given up only after the
+ *             whole table was probed).  Otherwise the flag is 1, pair_cap rows are stored (which ones is unspecified) and each of them
+ *             is a distinct true pair with its full counts; state, cover_x, scores and counts[2] stay exact.  When links were dropped
+ *             (state[1] > 0) the results are those of the stored links.
+ *   workspace dc_track_match_workspace(...) bytes (a host function; 0 for arguments out of range), 256-byte aligned; holds nothing
+ *             between calls: the pair table (the power of two >= max(16, 2 * pair_cap) slots of 48 bytes), the (pair, frame) table
+ *             (the power of two >= max(16, 2 * link_cap) words: it cannot fill), one byte per (track, frame) step of each side (at most
+ *             event_cap_x: the frames of a track form an interval, each holding an event of it), pair_cap ticket words and the step
+ *             offsets (8 bytes per track row and side).  The call clears what it needs cleared.
+ * Every result is independent of scheduling except the row order of links and tpairs.  1 <= link_cap <= 2^26, 1 <= pair_cap <= 2^24,
+ * min_frames >= 0, 1 <= cover_q <= 1024, cap_x in [1, 2^22], event_cap_x and track_cap_x as dc_track_resolve takes them.  The grids are
+ * sized from the capacities; the kernels read the live counts on the device.  No call synchronises or reads anything on the host.
+ * Nothing is staged in LDS (there is no dc_track_match_lds_slots): the link pass works on the device tables directly. */
+size_t dc_track_match_workspace(int event_cap_a, int event_cap_b, int track_cap_a, int track_cap_b, int link_cap, int pair_cap);
+int dc_track_match_append(int B, int n_valid, int cap_a, int cap_b, int pair_cap, const int64_t* pairs, const int32_t* npairs,
+                          const int32_t* ncomp_a, const int64_t* first_a, int event_cap_a, const int64_t* store_a, const int32_t* ncomp_b,
+                          const int64_t* first_b, int event_cap_b, const int64_t* store_b, int link_cap, int64_t* links, int64_t* state,
+                          void* stream);
+int dc_track_match_resolve(int event_cap_a, int event_cap_b, int track_cap_a, int track_cap_b, int link_cap, int pair_cap, int min_frames,
+                           int cover_q, const int64_t* state, const int64_t* links, const int64_t* store_a, const int32_t* track_of_a,
+                           const int64_t* tracks_a, const int64_t* ntracks_a, const int32_t* track_of_b, const int64_t* tracks_b,
+                           const int64_t* ntracks_b, int64_t* tpairs, int64_t* cover_a, int64_t* cover_b, int64_t* scores, int64_t* counts,
+                           void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frame renderer (nn.FrameRenderer; predict.py --plots, train.py --plots): the picture the reference's visualiser draws on the host

@@ -70,3 +70,9 @@ def check_tensor(who: str, name: str, t, dtypes, shape, device, kind: Optional[s
         got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
         raise L.DeepcamHipError(f"{who}: {name} must be a contiguous {kind or ' / '.join(str(d) for d in dtypes)} tensor "
                                 f"{list(shape)} on {device}, got {got}")
+
+
+def check_range(who: str, name: str, v: int, lo: int, hi: int) -> None:
+    """Raises unless the integer v lies in [lo, hi]."""
+    if not lo <= v <= hi:
+        raise L.DeepcamHipError(f"{who}: {name} must lie in [{lo}, {hi}], got {v}")

@@ -1,4 +1,4 @@
-// What the event kernels share (components.hip, event_shape.hip, event_match.hip, event_fields.hip, tracks.hip): the tile and the entry
+// What the event kernels share (components.hip, event_shape.hip, event_match.hip, event_fields.hip, tracks.hip, track_match.hip): the tile and the entry
 // checks, the union-find forest, the per-workgroup slot table, the rank lookup, the row walk, the block scan and the count / offsets
 // compaction.  Everything is inline: a kernel compiles these as it would compile a copy of its own.
 #pragma once
@@ -10,6 +10,9 @@ static constexpr int CC_TH = 32, CC_TW = 64;      // the tile: 2048 pixels, 8 pe
 static constexpr int CC_FIELDS = 10;              // words of a catalogue row
 static constexpr int FS_STATS = 6, FS_MAX_C = 32; // words of a field row (min, max, sum, wsum, nonfinite, saturated); channels at most
 static constexpr unsigned long long FS_NONE = ~0ull;   // the empty minimum of a field row
+// the tracker's tables (tracks.hip fills them, track_match.hip reads them)
+static constexpr int TK_STORE = 12, TK_TRACK = 8;  // store row: frame, rank, the catalogue's CC_FIELDS; track row: id, class, events, first, last, pixels, peak, area
+static constexpr int TK_CHUNK = 256;               // events per workgroup of the root count and rank passes
 
 __device__ inline int cc_class(uint8_t m) { return (m == 1 || m == 2) ? (int)m : 0; }
 
@@ -100,6 +103,14 @@ __device__ inline int slot_claim(K* s_key, int start, K key) {
     s = (s + 1) & (SLOTS - 1);
   }
   return hit;
+}
+
+// the 32 hashed bits of a 64-bit key of an open-addressing table in device memory (event_match.hip, track_match.hip)
+__device__ inline unsigned key_hash(unsigned long long k) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  return (unsigned)k;
 }
 
 // ---- rank lookup ---------------------------------------------------------------------------------------------------------------------

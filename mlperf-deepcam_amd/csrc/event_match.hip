@@ -30,13 +30,6 @@ static inline long ov_slots(int pair_cap) {       // a power of two, at least tw
   return s;
 }
 
-__device__ inline unsigned ov_hash(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  return (unsigned)k;
-}
-
 struct OvSample {                                 // one sample's slices
   const int *rank_a, *rank_b;
   unsigned long long *cover_a, *cover_b, *slots;  // slots: [nslots][2] = key (0: empty, else ((rank a << 32) | rank b) + 1), pixels
@@ -57,7 +50,7 @@ __device__ inline void ov_emit(const OvSample& S, int root_a, int root_b, int sa
   }
   if (!in_a || !in_b) return;
   const unsigned long long key = (((unsigned long long)ra << 32) | (unsigned)rb) + 1ull;
-  unsigned h = ov_hash(key) & S.slot_mask;
+  unsigned h = key_hash(key) & S.slot_mask;
   for (unsigned t = 0; t <= S.slot_mask; ++t) {
     unsigned long long* s = S.slots + 2 * (size_t)h;
     unsigned long long k = __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(256) void ov_pixel_kernel(int H, int W, const uint8
       const unsigned long long k = j < 8 ? key[j] : OV_EMPTY;   // the row's end closes the run
       if (k != cur) {
         if (cur != OV_EMPTY) {
-          const int hit = slot_claim<OV_SLOTS, OV_PROBES>(s_key, (int)(ov_hash(cur) >> (32 - slot_log2(OV_SLOTS))), cur);
+          const int hit = slot_claim<OV_SLOTS, OV_PROBES>(s_key, (int)(key_hash(cur) >> (32 - slot_log2(OV_SLOTS))), cur);
           if (hit >= 0) atomicAdd(&s_cnt[hit], n);
           else ov_emit(S, (int)((cur >> 31) & 0x7fffffffull), (int)(cur & 0x7fffffffull), (int)(cur >> 62), n);
         }

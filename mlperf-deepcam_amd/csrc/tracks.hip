@@ -26,8 +26,6 @@
 
 namespace dc {
 
-static constexpr int TK_STORE = 12, TK_TRACK = 8;  // store row: frame, rank, the catalogue's CC_FIELDS; track row: id, class, events, first, last, pixels, peak, area
-static constexpr int TK_CHUNK = 256;               // events per workgroup of the root count and rank passes
 static constexpr unsigned long long TK_NONE = ~0ull;
 static_assert(TK_STORE == CC_FIELDS + 2, "tk_fill_kernel: a store row is (frame, rank) and a catalogue row");
 

@@ -1,6 +1,6 @@
 """The events of class masks, on the device: the catalogue of connected components (EventCatalog), two catalogues matched (EventMatcher),
 per-event statistics of the input fields (EventFields), shapes and a shape filter (EventShape, EventFilter), events linked across time
-steps (EventTracker) and the tracks' life cycles (TrackFields)."""
+steps (EventTracker), the tracks' life cycles (TrackFields) and two sides' tracks matched (TrackMatcher)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from ._args import check_tensor, device_of
+from ._args import _ratio, check_range, check_tensor, device_of
 
 EVENT_FIELDS = ("root", "class", "pixels", "area", "sum_row", "sum_cx", "sum_sx", "row_min", "row_max", "seam")
 EVENT_SCALE = 1 << 20
@@ -183,6 +183,12 @@ class EventMatcher:
                L.dptr(self.acc), st)
         self._last_valid = nv
         return self
+
+    @property
+    def mask_b(self) -> Optional[torch.Tensor]:
+        """uint8 [B, H, W]: side b's mask of the last call as the catalogue took it -- the converted bytes of a label tensor (read-only;
+        what an EventTracker on `.b` is called with).  None before the first call."""
+        return self._mask_b
 
     @property
     def pair_table(self) -> torch.Tensor:
@@ -734,6 +740,7 @@ class EventTracker:
         self._c_first = torch.zeros(1, dtype=torch.int64, device=dev)
         self._carry = False
         self._frames = 0                           # frames given since reset(), counted on the host: the next call's frame0
+        self._last_valid = 0                       # the valid frames of the last call (TrackMatcher compares the two sides)
 
     def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventTracker":
         """mask: the device uint8 [B, H, W] the catalogue was just called with.  n_valid defaults to the catalogue's and must equal it."""
@@ -758,6 +765,7 @@ class EventTracker:
             L.call("dc_memcpy_async", L.dptr(dst), src, dst.numel() * dst.element_size(), st)
         self._carry = True
         self._frames += nv
+        self._last_valid = nv
         return self
 
     def cut(self) -> None:
@@ -981,3 +989,207 @@ class TrackFields:
                         "peak_pixels": peak >> 32, "peak_frame": 0xFFFFFFFF - (peak & 0xFFFFFFFF),
                         "area_fraction_sum": area / whole if whole > 0 else 0.0, "fields": life, "series": series})
         return out
+
+
+TRACK_PAIR_FIELDS = ("row_a", "row_b", "class", "overlaps", "common_frames", "shared_pixels", "first_common_frame", "last_common_frame")
+TRACK_COVER_FIELDS = ("matched_frames", "shared_pixels")
+
+
+def great_circle_km(lat_a: float, lon_a: float, lat_b: float, lon_b: float) -> float:
+    """the great-circle distance of two points given in degrees, in km on the sphere of EARTH_RADIUS_KM (haversine, float64)"""
+    pa, pb = math.radians(lat_a), math.radians(lat_b)
+    h = math.sin((pb - pa) / 2) ** 2 + math.cos(pa) * math.cos(pb) * math.sin(math.radians(lon_b - lon_a) / 2) ** 2
+    return 2.0 * EARTH_RADIUS_KM * math.asin(min(1.0, math.sqrt(h)))
+
+
+class TrackMatcher:
+    """Predicted against labelled storm tracks on the device (dc_track_match_append, dc_track_match_resolve, csrc/track_match.hip): the
+    join of an EventMatcher (side a: the prediction, side b: the labels) and one EventTracker on each of its two catalogues.  Every
+    overlap of two stored events of the same class is filed as a link (event a, event b, shared pixels); at resolve time the links are
+    grouped by (track row a, track row b) -- overlaps, DISTINCT common frames, shared pixels, first and last common frame per pair --
+    and every track gets its matched frames (the distinct frames in which one of its events overlaps any track of the other side) and
+    its shared pixels.  A track is SCORED when it has a row and at least max(min_frames, 1) frames; it is MATCHED when matched >= 1 and
+    matched * 1024 >= round(min_cover * 1024) * frames.  Coverage, not pairwise overlap, decides: a labelled storm predicted as two tracks
+    with a missed frame in between is still found, and the pairs show the fragmentation (include/deepcam_hip.h has the definitions).
+    The object owns the link store (int64 [link_cap, 3]: 24 bytes per link), the four counters, the outputs (pairs int64 [pair_cap, 8],
+    TRACK_PAIR_FIELDS; cover int64 [track_cap, 2] per side, TRACK_COVER_FIELDS; scores int64 [2, 4]; counts int64 [4]) and the resolve's
+    workspace.  A call follows the matcher's call and both trackers' calls of the same batch on the same stream; it launches once and
+    neither synchronises nor reads anything back.  rows() / pairs() / result() resolve and read back only the filled parts."""
+
+    SCORE_FIELDS = EventMatcher.SCORE_FIELDS
+
+    def __init__(self, matcher: EventMatcher, tracker_a: "EventTracker", tracker_b: "EventTracker", link_cap: int = 1 << 20,
+                 pair_cap: int = 1 << 16, min_frames: int = 1, min_cover: float = 0.5):
+        link_cap, pair_cap, min_frames = int(link_cap), int(pair_cap), int(min_frames)
+        check_range("TrackMatcher", "link_cap", link_cap, 1, 1 << 26)
+        check_range("TrackMatcher", "pair_cap", pair_cap, 1, 1 << 24)
+        check_range("TrackMatcher", "min_frames", min_frames, 0, (1 << 31) - 1)
+        if not 0.0 < float(min_cover) <= 1.0:
+            raise L.DeepcamHipError(f"TrackMatcher: min_cover must lie in (0, 1], got {min_cover}")
+        if not isinstance(matcher, EventMatcher) or not isinstance(tracker_a, EventTracker) or not isinstance(tracker_b, EventTracker):
+            raise L.DeepcamHipError("TrackMatcher: needs an EventMatcher and two EventTrackers")
+        if tracker_a.catalog is not matcher.a or tracker_b.catalog is not matcher.b:
+            raise L.DeepcamHipError("TrackMatcher: tracker_a must be built on matcher.a and tracker_b on matcher.b")
+        self.matcher, self.tracker_a, self.tracker_b = matcher, tracker_a, tracker_b
+        self.link_cap, self.pair_cap, self.min_frames = link_cap, pair_cap, min_frames
+        self.cover_q = min(max(int(round(float(min_cover) * 1024)), 1), 1024)
+        dev = tracker_a._store.device
+        i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)  # noqa: E731
+        self._state = i64(4)
+        self._links = torch.empty((link_cap, 3), dtype=torch.int64, device=dev)
+        self._tpairs = i64(pair_cap, len(TRACK_PAIR_FIELDS))
+        self._cover_a = i64(tracker_a.track_cap, len(TRACK_COVER_FIELDS))
+        self._cover_b = i64(tracker_b.track_cap, len(TRACK_COVER_FIELDS))
+        self._scores = i64(2, 4)
+        self._counts = i64(4)
+        nbytes = L.load().dc_track_match_workspace(tracker_a.event_cap, tracker_b.event_cap, tracker_a.track_cap, tracker_b.track_cap, link_cap,
+                                                   pair_cap)
+        if nbytes == 0:
+            raise L.DeepcamHipError("TrackMatcher: a capacity is out of range")
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._frames = 0                           # frames filed since reset(), counted on the host
+
+    def __call__(self) -> "TrackMatcher":
+        """Files the overlaps of the batch the matcher and both trackers were just called with (all three, on this stream, before this)."""
+        m, ta, tb = self.matcher, self.tracker_a, self.tracker_b
+        nv = m._last_valid
+        if nv < 1 or ta._last_valid != nv or tb._last_valid != nv:
+            raise L.DeepcamHipError(f"TrackMatcher: call the matcher and both trackers on the same batch first, with the same n_valid (the "
+                                    f"matcher's last call had {nv}, the trackers' {ta._last_valid} and {tb._last_valid})")
+        if ta._frames != tb._frames or ta._frames != self._frames + nv:
+            raise L.DeepcamHipError(f"TrackMatcher: both trackers must have seen the frames filed so far and this batch ({self._frames} + {nv}); "
+                                    f"they have seen {ta._frames} and {tb._frames}")
+        L.call("dc_track_match_append", m.B, nv, m.a.cap, m.b.cap, m.pair_cap, L.dptr(m._pairs), L.dptr(m._npairs), L.dptr(m.a._ncomp),
+               L.dptr(ta._first), ta.event_cap, L.dptr(ta._store), L.dptr(m.b._ncomp), L.dptr(tb._first), tb.event_cap, L.dptr(tb._store),
+               self.link_cap, L.dptr(self._links), L.dptr(self._state), L.stream_ptr())
+        self._frames += nv
+        return self
+
+    def reset(self) -> None:
+        """Forget every link.  The caller resets the two trackers."""
+        L.call("dc_memset_async", L.dptr(self._state), 0, 32, L.stream_ptr())
+        self._frames = 0
+
+    def state(self) -> dict:
+        """the four counters (one device-to-host read)"""
+        s = [int(v) for v in self._state.cpu().tolist()]
+        return {"links": s[0], "links_dropped": s[1], "frames": s[2], "frames_truncated": s[3]}
+
+    def resolve(self) -> "TrackMatcher":
+        """dc_track_resolve of both trackers, then dc_track_match_resolve, on the current stream, for the frames filed so far.  Does not
+        synchronise; may be called in the middle of a series."""
+        ta, tb = self.tracker_a.resolve(), self.tracker_b.resolve()
+        L.call("dc_track_match_resolve", ta.event_cap, tb.event_cap, ta.track_cap, tb.track_cap, self.link_cap, self.pair_cap, self.min_frames,
+               self.cover_q, L.dptr(self._state), L.dptr(self._links), L.dptr(ta._store), L.dptr(ta._track_of), L.dptr(ta._tracks),
+               L.dptr(ta._ntracks), L.dptr(tb._track_of), L.dptr(tb._tracks), L.dptr(tb._ntracks), L.dptr(self._tpairs), L.dptr(self._cover_a),
+               L.dptr(self._cover_b), L.dptr(self._scores), L.dptr(self._counts), L.dptr(self._ws), L.stream_ptr())
+        return self
+
+    @staticmethod
+    def sort_pairs(rows) -> np.ndarray:
+        """the stored rows [n, 8] ordered by (row a, row b)"""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, len(TRACK_PAIR_FIELDS))
+        return np.ascontiguousarray(rows[np.lexsort((rows[:, 1], rows[:, 0]))])
+
+    def rows(self) -> dict:
+        """resolve(), then the counters and only the filled parts as numpy arrays: "state" int64 [4], "counts" int64 [4] (pair rows stored,
+        the pair overflow flag, links skipped for a missing track row, 0), "scores" int64 [2, 4], "pairs" int64 [n, 8] sorted by (row a,
+        row b), "cover_a" int64 [ma, 2], "cover_b" int64 [mb, 2], "tracks_a" int64 [ma, 8], "tracks_b" int64 [mb, 8] (TRACK_FIELDS), with
+        ma / mb the stored track rows of the two trackers."""
+        self.resolve()
+        ta, tb = self.tracker_a, self.tracker_b
+        counts = self._counts.cpu().numpy()
+        ma, mb = int(ta._ntracks[3].item()), int(tb._ntracks[3].item())
+        return {"state": self._state.cpu().numpy(), "counts": counts, "scores": self._scores.cpu().numpy(),
+                "pairs": self.sort_pairs(self._tpairs[:int(counts[0])].cpu().numpy()), "cover_a": self._cover_a[:ma].cpu().numpy(),
+                "cover_b": self._cover_b[:mb].cpu().numpy(), "tracks_a": ta._tracks[:ma].cpu().numpy(), "tracks_b": tb._tracks[:mb].cpu().numpy()}
+
+    def pairs(self) -> np.ndarray:
+        """the track-pair rows int64 [n, 8] (TRACK_PAIR_FIELDS) sorted by (row a, row b)"""
+        return self.rows()["pairs"]
+
+    def cover(self):
+        """(cover_a [ma, 2], cover_b [mb, 2]) (TRACK_COVER_FIELDS) of the stored track rows"""
+        r = self.rows()
+        return r["cover_a"], r["cover_b"]
+
+    def scores(self) -> np.ndarray:
+        """int64 [2, 4]: per class 1, 2 the SCORE_FIELDS of tracks"""
+        return self.rows()["scores"]
+
+    @staticmethod
+    def decode(pairs, tracks_a, tracks_b, min_frames: int = 1):
+        """Track-pair rows [n, 8] (TRACK_PAIR_FIELDS) and the two sides' tracks as EventTracker.decode gives them with min_frames = 1 (one
+        dict per track row, in row order) -> one dict per pair whose two tracks have at least min_frames frames, in the rows' order: row_a,
+        row_b, id_a, id_b, class, overlaps, common_frames, shared_pixels, first_common_frame, last_common_frame, frames_a, frames_b,
+        genesis_error = first_frame_a - first_frame_b (positive: the prediction is late), lysis_error = last_frame_a - last_frame_b,
+        duration_error = frames_a - frames_b, and mean_separation_km: the great-circle distance (float64, R = 6371 km) between the two
+        paths' joint centroids, averaged over the frames from the first to the last common frame -- both tracks live in every one of
+        them; a frame in between without an overlap counts with its distance.  Needs no GPU."""
+        out = []
+        for ra, rb, cls, links, common, shared, f0, f1 in np.asarray(pairs, np.int64).reshape(-1, len(TRACK_PAIR_FIELDS)).tolist():
+            a, b = tracks_a[ra], tracks_b[rb]
+            if min(a["frames"], b["frames"]) < max(int(min_frames), 1):
+                continue
+            pa = {p["frame"]: p for p in a["path"]}
+            pb = {p["frame"]: p for p in b["path"]}
+            dist = [great_circle_km(pa[f]["lat"], pa[f]["lon"], pb[f]["lat"], pb[f]["lon"]) for f in range(f0, f1 + 1) if f in pa and f in pb]
+            out.append({"row_a": ra, "row_b": rb, "id_a": a["id"], "id_b": b["id"], "class": cls, "overlaps": links, "common_frames": common,
+                        "shared_pixels": shared, "first_common_frame": f0, "last_common_frame": f1, "frames_a": a["frames"],
+                        "frames_b": b["frames"], "genesis_error": a["first_frame"] - b["first_frame"],
+                        "lysis_error": a["last_frame"] - b["last_frame"], "duration_error": a["frames"] - b["frames"],
+                        "mean_separation_km": _ratio(math.fsum(dist), len(dist))})
+        return out
+
+    def _decoded_tracks(self):
+        cat = self.tracker_a.catalog
+        return [EventTracker.decode(*t.rows()[1:], cat.H, cat.W) for t in (self.tracker_a, self.tracker_b)]
+
+    def matches(self, min_frames: Optional[int] = None):
+        """The joined track pairs of the frames filed so far (decode); min_frames defaults to the matcher's."""
+        mf = self.min_frames if min_frames is None else int(min_frames)
+        return self.decode(self.pairs(), *self._decoded_tracks(), min_frames=mf)
+
+    @staticmethod
+    def is_matched(matched: int, frames: int, cover_q: int) -> bool:
+        return matched >= 1 and matched * 1024 >= cover_q * frames
+
+    @staticmethod
+    def summarize(rows: dict, matches, min_frames: int, cover_q: int) -> dict:
+        """rows() and decode(rows["pairs"], ..., min_frames=1) -> the summary: the counters ("frames", "links", "links_dropped",
+        "frames_truncated", "pairs", "pairs_overflowed", "links_without_track", "truncated": any of the four non-zero -- counts may be
+        short), "min_frames", "min_cover" (cover_q / 1024) and per class "class_1", "class_2": the SCORE_FIELDS of tracks with
+        EventMatcher.rates (pod, far, csi), and over the matched scored b tracks that have a stored pair -- each with its BEST partner: most
+        common frames, then most shared pixels, then smallest row a -- "partnered" (their number), "mean_abs_genesis_error",
+        "mean_abs_lysis_error", "mean_separation_km" and "mean_partners" (the pairs per such b track: 1 means no fragmentation).  None where
+        a denominator is zero.  Needs no GPU."""
+        state, counts = [int(v) for v in rows["state"]], [int(v) for v in rows["counts"]]
+        scores = np.asarray(rows["scores"], np.int64).reshape(2, 4)
+        out = {"frames": state[2], "links": state[0], "links_dropped": state[1], "frames_truncated": state[3], "pairs": counts[0],
+               "pairs_overflowed": counts[1] != 0, "links_without_track": counts[2],
+               "truncated": bool(state[1] or state[3] or counts[1] or counts[2]), "min_frames": int(min_frames), "min_cover": cover_q / 1024}
+        by_b: dict = {}
+        for m in matches:
+            by_b.setdefault(m["row_b"], []).append(m)
+        need = max(int(min_frames), 1)
+        for k in (1, 2):
+            h, mi, fa, md = (int(v) for v in scores[k - 1])
+            best, partners = [], 0
+            for t, (row, cov) in enumerate(zip(np.asarray(rows["tracks_b"], np.int64).tolist(), np.asarray(rows["cover_b"], np.int64).tolist())):
+                frames = row[4] - row[3] + 1
+                if row[1] != k or frames < need or not TrackMatcher.is_matched(cov[0], frames, cover_q) or t not in by_b:
+                    continue
+                partners += len(by_b[t])
+                best.append(min(by_b[t], key=lambda m: (-m["common_frames"], -m["shared_pixels"], m["row_a"])))
+            sep = [m["mean_separation_km"] for m in best if m["mean_separation_km"] is not None]
+            out[f"class_{k}"] = {"hits": h, "misses": mi, "false_alarms": fa, "matched": md, **EventMatcher.rates(h, mi, fa, md),
+                                 "partnered": len(best),
+                                 "mean_abs_genesis_error": _ratio(sum(abs(m["genesis_error"]) for m in best), len(best)),
+                                 "mean_abs_lysis_error": _ratio(sum(abs(m["lysis_error"]) for m in best), len(best)),
+                                 "mean_separation_km": _ratio(math.fsum(sep), len(sep)), "mean_partners": _ratio(partners, len(best))}
+        return out
+
+    def result(self) -> dict:
+        """summarize() of the frames filed so far"""
+        rows = self.rows()
+        return self.summarize(rows, self.decode(rows["pairs"], *self._decoded_tracks(), min_frames=1), self.min_frames, self.cover_q)

@@ -178,6 +178,9 @@ _SIGS = {
     "dc_track_cycles_workspace": (SZ, [I, I]),
     "dc_track_fields_append": (I, [I, I, I, P, P, P, I, I, P, P]),
     "dc_track_cycles": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "dc_track_match_workspace": (SZ, [I, I, I, I, I, I]),
+    "dc_track_match_append": (I, [I, I, I, I, I, P, P, P, P, I, P, P, P, I, P, I, P, P, P]),
+    "dc_track_match_resolve": (I, [I, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "dc_render_tile": (I, [C.POINTER(I), C.POINTER(I)]),
     "dc_render_workspace": (SZ, [I, I, I, I]),
     "dc_render_frames": (I, [I, I, I, I, P, I, I, F, F, P, I, P, I, P, I, P, I, I, P, P, I, I, I, I, I, P, P, P]),

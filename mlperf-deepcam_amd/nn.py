@@ -30,9 +30,10 @@ from .engine import Engine
 # the re-exports: every name is defined once, in its topic module
 from ._args import _BYTES, _c_int, _float, _n_valid, _ratio, _two_words  # noqa: F401
 from .events import (EARTH_RADIUS_KM, EVENT_FIELD_STATS, EVENT_FIELDS, EVENT_FILTER_COUNTS, EVENT_SCALE, EVENT_SHAPE_FIELDS,  # noqa: F401
-                     EVENT_SHAPE_VALUES, TRACK_FIELD_STATS, TRACK_FIELDS, TRACK_STEP_FIELDS, TRACK_STORE_FIELDS, EventCatalog, EventFields,
-                     EventFilter, EventMatcher, EventShape, EventTracker, TrackFields, _filled_rows, event_field_bits, event_field_key,
-                     event_field_value, event_shape_tables, event_weight_tables)
+                     EVENT_SHAPE_VALUES, TRACK_COVER_FIELDS, TRACK_FIELD_STATS, TRACK_FIELDS, TRACK_PAIR_FIELDS, TRACK_STEP_FIELDS,
+                     TRACK_STORE_FIELDS, EventCatalog, EventFields, EventFilter, EventMatcher, EventShape, EventTracker, TrackFields,
+                     TrackMatcher, _filled_rows, event_field_bits, event_field_key, event_field_value, event_shape_tables,
+                     event_weight_tables, great_circle_km)
 from .render import _RAMP, RENDER_BACKGROUND, RENDER_COLOURS, FrameRenderer, gall_rows, graticule, plate_rows, render_palette  # noqa: F401
 from .climate import (_DATE, _SEASON_OF_MONTH, CLIMATOLOGY_GROUPS, CLIMATOLOGY_MAX_FRAMES, CLIMATOLOGY_PRODUCTS,  # noqa: F401
                       CLIMATOLOGY_ROWS, COMPOSITE_COUNTS, COMPOSITE_KEYS, COMPOSITE_MAX_EVENTS, COMPOSITE_MAX_RADIUS, Climatology,

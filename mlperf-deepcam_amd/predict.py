@@ -32,6 +32,15 @@ not detected from the names).  At the end of the run ``<output_dir>/tracks.h5`` 
 frame, last frame, pixels, peak, area), ``track_events`` (int64 [m, 13]: frame, rank, the ten columns of ``events``, the row of
 ``tracks`` or -1 -- with --min_event_pixels 0, (frame, rank) is row `rank` of the ``events`` and ``event_fields`` of file `frame`) and
 ``track_state`` (int64 [4]: events stored, frames, events dropped, frames with a truncated catalogue); ``summary.json`` gains ``tracks``.
+With --verify_tracks (which implies --verify and --tracks) a second nn.EventTracker runs on the labels' events and nn.TrackMatcher files,
+behind every batch and on the device, every overlap of a predicted and a labelled event under the two events' tracks.  ``tracks.h5``
+additionally holds ``truth_tracks``, ``truth_track_events``, ``truth_track_state`` (the labels' side of the three datasets above),
+``track_pairs`` (int64 [p, 8]: row of ``tracks``, row of ``truth_tracks``, class, overlaps, distinct common frames, shared pixels, first
+and last common frame), ``track_cover`` and ``truth_track_cover`` (int64 [n, 2] per side: matched frames, shared pixels),
+``track_scores`` (int64 [2, 4]: per class hits, misses, false alarms, matched detections of tracks) and ``track_match_state`` (int64
+[4]: links stored, links dropped, frames filed, frames truncated); ``summary.json`` gains ``track_verification`` (the counters, POD,
+FAR and CSI of tracks per class, the mean
+genesis and lysis errors and the mean separation of the paths over each found storm's best partner, the partners per found storm).
 With --track_fields (which implies --tracks and --event_fields) nn.TrackFields files the field rows of every batch next to the tracker's
 store and joins the two on the device at the end of the run -- the storm life cycles: ``tracks.h5`` additionally holds
 ``track_step_offsets`` (int64 [n]: per row of ``tracks`` the first of its step rows, -1 not selected by --min_track_frames, -2 beyond the
@@ -237,6 +246,14 @@ def build_parser():
                     "per track the lifetime extremes with frame and place (implies --tracks and --event_fields; --min_track_frames selects the "
                     "cycles).  tracks.h5 gains 'track_step_offsets', 'track_steps', 'track_step_fields', 'track_fields', 'track_cycle_counts'; "
                     "'track_fields' in the summary")
+    AP.add_argument("--verify_tracks", action=_implies("verify_tracks", "verify", "tracks", "events", default=argparse.SUPPRESS),
+                    help="match the predicted tracks to the tracks of the files' labels on the device (implies --verify and --tracks): a "
+                    "second tracker runs on the labels' events, and every overlap of a predicted and a labelled event is filed under the "
+                    "two events' tracks.  tracks.h5 gains 'truth_tracks', 'truth_track_events', 'truth_track_state', 'track_pairs', "
+                    "'track_cover', 'truth_track_cover', 'track_scores', 'track_match_state'; 'track_verification' in the summary "
+                    "(--min_track_frames: the tracks that are scored)")
+    AP.add_argument("--min_track_cover", type=float, default=argparse.SUPPRESS, help="with --verify_tracks: a track is found when tracks of the "
+                    "other side overlap it in at least this share of its frames, in (0, 1] (default 0.5)")
     AP.add_argument("--track_center_channel", type=int, default=None, help="with --track_fields: the file channel whose minimum is a track's "
                     "centre (sea-level pressure for cyclones); the summary names the deepest minimum over the class-1 tracks")
     AP.add_argument("--climatology", action="store_true", help="accumulate the maps over time on the device: how often every pixel is class 1 / "
@@ -932,6 +949,11 @@ def main(pargs) -> dict:
 
     # --tracks: behind the catalogue of every batch; the batches arrive in the order of the sorted names, one frame per file
     tracker = dnn.EventTracker(catalog, min_pixels=pargs.min_track_pixels) if getattr(pargs, "tracks", False) else None
+    # --verify_tracks: a second tracker on the labels' catalogue (the matcher's side b), and the join of the two behind every batch
+    truth_tracker = tmatch = None
+    if getattr(pargs, "verify_tracks", False):
+        truth_tracker = dnn.EventTracker(matcher.b, min_pixels=pargs.min_track_pixels)
+        tmatch = dnn.TrackMatcher(matcher, tracker, truth_tracker, min_frames=pargs.min_track_frames, min_cover=getattr(pargs, "min_track_cover", 0.5))
     # --track_fields: the field rows of every batch filed next to the tracker's store, joined with the tracks at the end of the run
     tfields = center = None
     if getattr(pargs, "track_fields", False):
@@ -1045,6 +1067,9 @@ def main(pargs) -> dict:
                 slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
             if tracker is not None:
                 tracker(dmask, n_valid=nv)
+            if tmatch is not None:
+                truth_tracker(matcher.mask_b, n_valid=nv)
+                tmatch()
             if efields is not None:
                 efields(loader.raw, n_valid=nv)     # behind the catalogue's launches, on their stream
                 slot.fields[:nv].copy_(efields.table, non_blocking=True)
@@ -1086,6 +1111,8 @@ def main(pargs) -> dict:
         raise errors[0]
     verification = matcher.result() if verify else None
     track_rows = tracker.rows() if tracker is not None else None
+    truth_track_rows = truth_tracker.rows() if truth_tracker is not None else None
+    match_rows = tmatch.rows() if tmatch is not None else None
     cycle_rows = tfields.rows(min_frames=pargs.min_track_frames) if tfields is not None else None
     clim_state = clim.state() if clim is not None else None
     comp_state = comp.state() if comp is not None else None
@@ -1134,6 +1161,15 @@ def main(pargs) -> dict:
             arrays.update({"track_step_offsets": cycle_rows["offsets"], "track_steps": cycle_rows["steps"],
                            "track_step_fields": cycle_rows["step_fields"], "track_fields": cycle_rows["track_fields"],
                            "track_cycle_counts": cycle_rows["counts"]})
+        if match_rows is not None:
+            b_state, b_store, b_of, b_tracks = truth_track_rows
+            arrays.update({"truth_tracks": b_tracks, "truth_track_events": np.concatenate([b_store, b_of.astype(np.int64)[:, None]], axis=1),
+                           "truth_track_state": b_state, "track_pairs": match_rows["pairs"], "track_cover": match_rows["cover_a"],
+                           "truth_track_cover": match_rows["cover_b"], "track_scores": match_rows["scores"],
+                           "track_match_state": match_rows["state"]})
+            track_dicts = [dnn.EventTracker.decode(st, of, tr, H, W) for st, of, tr in ((t_store, t_of, t_tracks), (b_store, b_of, b_tracks))]
+            summary["track_verification"] = dnn.TrackMatcher.summarize(
+                match_rows, dnn.TrackMatcher.decode(match_rows["pairs"], *track_dicts, min_frames=1), tmatch.min_frames, tmatch.cover_q)
         write_datasets(os.path.join(pargs.output_dir, "tracks.h5"), arrays)
         summary["tracks"] = track_summary(t_state, t_tracks, pargs.min_track_frames)
         if cycle_rows is not None:
