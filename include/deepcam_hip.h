@@ -77,6 +77,8 @@ int dc_reset_options(void);
  *   event matching (dc_component_overlap, dc_event_scores): cc_overlap (every launch of both calls)
  *   event intensities (dc_component_fields): cc_fields (the init and the pixel pass)
  *   event shapes and the shape filter (dc_component_shape, dc_event_select, dc_mask_select): cc_shape (every launch of the three calls)
+ *   event skeletons (dc_mask_thin, dc_skeleton_stats): skel_thin (one workgroup per class and frame, the bit plane thinned in LDS),
+ *     skel_stats (both launches of the statistics call: the rows zeroed, the pixel pass)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   track verification (dc_track_match_append, dc_track_match_resolve): cc_track_match (every launch of both calls)
@@ -778,6 +780,53 @@ int dc_event_select(int B, int n_valid, int cap, const int64_t* table, const int
                     uint8_t* keep, int64_t* counts, void* stream);
 int dc_mask_select(int B, int n_valid, int H, int W, const uint8_t* mask, const int32_t* labels, const int32_t* rank_map, int cap,
                    const uint8_t* keep, uint8_t* out_mask, int64_t* counts, void* stream);
+
+/* Event skeletons and axis lengths (nn.EventAxis; predict.py --event_axis): how long an event is ALONG ITS OWN COURSE, where that course
+ * runs and whether it forks -- what the moment-equivalent strip of dc_component_shape cannot say of a river that curves around a ridge.
+ *
+ * dc_mask_thin.  For each valid sample and each class k in {1, 2} the foreground is mask == k (mask: [B][H][W] of 1-, 4- or 8-byte
+ * integers, mask_bytes, as dc_wce_score takes labels).  The foreground is thinned with Guo and Hall's two-subiteration parallel algorithm
+ * (1989, A1), applied synchronously:
+ *   Neighbours of P are numbered clockwise from north: P2 (r-1, c), P3 (r-1, c+1), P4 (r, c+1), P5 (r+1, c+1), P6 (r+1, c), P7 (r+1, c-1),
+ *   P8 (r, c-1), P9 (r-1, c-1).  Rows outside the frame are background.  Columns are periodic when `wrap` is set, and background otherwise.
+ *     C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *     N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8)
+ *     N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9)
+ *     N  = min(N1, N2)
+ *   A foreground pixel is deleted in a sub-pass iff C == 1, 2 <= N <= 3 and m == 0.
+ *     Sub-pass A: m = (P6 | P7 | !P9) & P8.        Sub-pass B: m = (P2 | P3 | !P5) & P4.
+ *   Every pixel of a sub-pass is judged against the plane as it stood when the sub-pass began.  One pass is A then B.  Stop after the
+ *   first pass in which neither sub-pass deleted anything, or after max_iters passes (at least 1).
+ *   iters     int32 [B][2][2]: iters[j][k-1] holds the passes run, counting the final empty one, and 1 or 0 for converged
+ *   skeleton  uint8 [B][H][W]: k on the surviving pixels of class k and 0 elsewhere, for the valid samples; may not overlap mask
+ * A 2 x 2 square thins to one pixel and a single pixel survives (Zhang and Suen's rule erases the square).  One workgroup per class and
+ * frame keeps the whole bit plane in dc_thin_lds_bytes(H, W) bytes of LDS: H * ceil(W / 64) * 8 for the plane plus 64 of fixed scratch
+ * (110 656 at 768 x 1152); dc_thin_lds_bytes is 0 where that exceeds the 160 KiB of a CU (host only), and dc_mask_thin refuses such a
+ * grid with a message.  Samples from n_valid on are not touched.  Does not synchronise.
+ *
+ * dc_skeleton_stats, one pass over the skeleton and the catalogue's label map:
+ *   skeleton    as dc_mask_thin leaves it, of the mask the catalogue was built from
+ *   labels, ws, cap   the label map and the workspace (its first segment: the rank map) as dc_mask_components and dc_component_stats leave
+ *               them; wrap: the catalogue's flag
+ *   link_table  int32 [H][3], metres (nn.axis_link_table): row i holds the length of an E-W link on row i, of an N-S link, and of a
+ *               diagonal link between rows i and i + 1
+ *   rows        int64 [B][cap][7], zeroed by the call for the samples below n_valid; row k belongs to the event of rank k, events of rank
+ *               >= cap have no row.  Two skeleton pixels are NEIGHBOURS iff they are 8-adjacent (columns periodic under wrap, rows never)
+ *               and carry the same label word -- under a 4-connected catalogue diagonal neighbours can belong to different events.
+ *     0  skeleton_pixels   the event's skeleton pixels
+ *     1  endpoints         skeleton pixels with exactly one neighbour
+ *     2  junctions         skeleton pixels whose ring P2 .. P9 of neighbours has three or more 0 -> 1 transitions
+ *     3  links_ew, 4 links_ns, 5 links_diag   links counted once, from the pixel towards E, S, SE and SW.  A diagonal link counts only when
+ *                          neither of the two pixels 4-adjacent to both of its ends is a neighbour (otherwise every corner of the
+ *                          skeleton would be measured as a triangle)
+ *     6  length_m          the sum over the counted links of link_table[row][type], row the upper end's
+ * Samples from n_valid on are neither read nor written.  Does not synchronise; reads what dc_mask_components, dc_component_stats and
+ * dc_mask_thin left on the same stream. */
+size_t dc_thin_lds_bytes(int H, int W);
+int dc_mask_thin(int B, int n_valid, int H, int W, const void* mask, int mask_bytes, int wrap, int max_iters, uint8_t* skeleton,
+                 int32_t* iters, void* stream);
+int dc_skeleton_stats(int B, int n_valid, int H, int W, const uint8_t* skeleton, const int32_t* labels, const void* ws, int cap, int wrap,
+                      const int32_t* link_table, int64_t* rows, void* stream);
 
 /* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
  * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in

@@ -1,6 +1,7 @@
 """The events of class masks, on the device: the catalogue of connected components (EventCatalog), two catalogues matched (EventMatcher),
-per-event statistics of the input fields (EventFields), shapes and a shape filter (EventShape, EventFilter), events linked across time
-steps (EventTracker), the tracks' life cycles (TrackFields) and two sides' tracks matched (TrackMatcher)."""
+per-event statistics of the input fields (EventFields), shapes and a shape filter (EventShape, EventFilter), skeletons and
+axis lengths (EventAxis), events linked across time steps (EventTracker), the tracks' life cycles (TrackFields) and two sides' tracks
+matched (TrackMatcher)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -1000,6 +1001,112 @@ def great_circle_km(lat_a: float, lon_a: float, lat_b: float, lon_b: float) -> f
     pa, pb = math.radians(lat_a), math.radians(lat_b)
     h = math.sin((pb - pa) / 2) ** 2 + math.cos(pa) * math.cos(pb) * math.sin(math.radians(lon_b - lon_a) / 2) ** 2
     return 2.0 * EARTH_RADIUS_KM * math.asin(min(1.0, math.sqrt(h)))
+
+
+EVENT_AXIS_FIELDS = ("skeleton_pixels", "endpoints", "junctions", "links_ew", "links_ns", "links_diag", "length_m")
+EVENT_AXIS_VALUES = ("skeleton_pixels", "endpoints", "junctions", "branches", "axis_km", "closed")
+
+
+def axis_link_table(height: int, width: int) -> np.ndarray:
+    """int32 [H, 3], metres, rint of float64: per row i the length of an E-W link on row i (R cos(lat_i) dlon), of an N-S link (R dlat)
+    and of a diagonal link between rows i and i + 1 (the great-circle distance between (lat_i, 0) and (lat_{i+1}, dlon); the last row's
+    is 0).  The latitudes of event_weight_tables, the steps of EventShape.steps, the sphere of great_circle_km."""
+    lat = np.linspace(-90.0, 90.0, height)
+    dlat, dlon = EventShape.steps(height, width)
+    out = np.zeros((height, 3), np.float64)
+    out[:, 0] = EARTH_RADIUS_KM * np.cos(np.deg2rad(lat)) * dlon
+    out[:, 1] = EARTH_RADIUS_KM * dlat
+    out[:-1, 2] = [great_circle_km(lat[i], 0.0, lat[i + 1], math.degrees(dlon)) for i in range(height - 1)]
+    return np.rint(out * 1000.0).astype(np.int32)
+
+
+class EventAxis:
+    """Skeletons and axis lengths per event on the device (dc_mask_thin + dc_skeleton_stats, csrc/skeleton.hip): the class planes of a
+    mask thinned to one-pixel-wide skeletons with Guo and Hall's parallel rule (the header has it word for word), and per event of the
+    catalogue the skeleton's pixels, endpoints, junctions, links and length in metres (EVENT_AXIS_FIELDS) -- how long a river is along
+    its own course, which EventShape's moment-equivalent strip cannot say.  Built on an existing EventCatalog, as EventShape is; a call
+    must follow the catalogue's call FOR THE SAME MASK on the same stream, launches twice and does not synchronise.  One workgroup thins
+    one class plane of one frame inside the LDS of a CU, so the plane must fit there (768 x 1152 does; the constructor raises where
+    not).  max_iters bounds the passes (default max(H, W): a layer goes from every side in each pass); iterations() tells which frames
+    hit it.  The object owns the link table, the skeleton (uint8 [B, H, W]), the pass counts (int32 [B, 2, 2]) and the rows (int64
+    [B, cap, 7]; row k belongs to row k of the catalogue's table)."""
+
+    def __init__(self, catalog: EventCatalog, max_iters: Optional[int] = None):
+        if L.load().dc_thin_lds_bytes(catalog.H, catalog.W) == 0:
+            raise L.DeepcamHipError(f"EventAxis: the bit plane of {catalog.H} x {catalog.W} does not fit the LDS of one CU")
+        self.max_iters = max(catalog.H, catalog.W) if max_iters is None else int(max_iters)
+        if self.max_iters < 1:
+            raise L.DeepcamHipError(f"EventAxis: max_iters must be at least 1, got {max_iters}")
+        self.catalog = catalog
+        dev = catalog._labels.device
+        self.link_table = axis_link_table(catalog.H, catalog.W)
+        self._link = torch.from_numpy(self.link_table).to(dev)
+        self._skel = torch.zeros((catalog.B, catalog.H, catalog.W), dtype=torch.uint8, device=dev)
+        self._iters = torch.zeros((catalog.B, 2, 2), dtype=torch.int32, device=dev)
+        self._rows = torch.zeros((catalog.B, catalog.cap, len(EVENT_AXIS_FIELDS)), dtype=torch.int64, device=dev)
+        self._last_valid = 0
+
+    def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventAxis":
+        """mask: the contiguous device tensor [B, H, W] the catalogue was called with (uint8; int32 and int64 are read as they are).
+        n_valid defaults to the catalogue's."""
+        cat = self.catalog
+        check_tensor("EventAxis", "mask", mask, (torch.uint8, torch.int32, torch.int64), (cat.B, cat.H, cat.W), cat._labels.device,
+                     "uint8, int32 or int64")
+        nv = cat._last_valid if n_valid is None else int(n_valid)
+        st = L.stream_ptr()
+        L.call("dc_mask_thin", cat.B, nv, cat.H, cat.W, L.dptr(mask), mask.element_size(), int(cat.wrap), self.max_iters, L.dptr(self._skel),
+               L.dptr(self._iters), st)
+        L.call("dc_skeleton_stats", cat.B, nv, cat.H, cat.W, L.dptr(self._skel), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, int(cat.wrap),
+               L.dptr(self._link), L.dptr(self._rows), st)
+        self._last_valid = nv
+        return self
+
+    @property
+    def skeleton_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the whole buffer the skeletons are written to, padding samples included (k on a skeleton pixel of class k)"""
+        return self._skel
+
+    @property
+    def table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, 7] of the last call (a view): zero from min(count, cap) on"""
+        return self._rows[:self._last_valid]
+
+    def iterations(self) -> np.ndarray:
+        """int32 numpy [n_valid, 2, 2]: per sample and class the passes run (the final empty one counted) and 1 / 0 for converged"""
+        return self._iters[:self._last_valid].cpu().numpy()
+
+    def rows(self):
+        """On the host, per valid sample only the filled rows: int64 numpy arrays [min(total, cap), 7] (the catalogue's counts decide)"""
+        nv = self._last_valid
+        if nv == 0:
+            return []
+        return _filled_rows(self._rows, self.catalog._fill(nv))
+
+    def axes(self):
+        """Per valid sample of the last call a list of dicts (decode), one per row of the catalogue."""
+        _, rows = self.catalog.rows()
+        return [self.decode(a, r, self.catalog.H, self.catalog.W) for a, r in zip(self.rows(), rows)]
+
+    @staticmethod
+    def values(axis_rows) -> np.ndarray:
+        """float64 [n, 6] (EVENT_AXIS_VALUES): decode's numbers for whole arrays at once (what predict.py stores as event_axis_values)"""
+        a = np.asarray(axis_rows, np.int64).reshape(-1, len(EVENT_AXIS_FIELDS))
+        out = np.empty((len(a), len(EVENT_AXIS_VALUES)), np.float64)
+        out[:, 0], out[:, 1], out[:, 2] = a[:, 0], a[:, 1], a[:, 2]
+        out[:, 3] = np.maximum(a[:, 1] - 2, 0)
+        out[:, 4] = a[:, 6] / 1000.0
+        out[:, 5] = (a[:, 1] == 0) & (a[:, 0] > 1)
+        return out
+
+    @staticmethod
+    def decode(axis_rows, rows, height: int, width: int):
+        """Axis rows [n, 7] (EVENT_AXIS_FIELDS) and the events' own rows [n, 10] (EVENT_FIELDS) -> one dict per event: class,
+        skeleton_pixels, endpoints, junctions, branches = max(endpoints - 2, 0), axis_km = length_m / 1000, closed = (endpoints == 0 and
+        skeleton_pixels > 1).  axis_km is the TOTAL length of the skeleton with its branches (the links of axis_link_table(height, width)
+        summed), not the longest path through it: a spur adds its length."""
+        rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
+        return [{"class": int(r[1]), "skeleton_pixels": int(v[0]), "endpoints": int(v[1]), "junctions": int(v[2]), "branches": int(v[3]),
+                 "axis_km": float(v[4]), "closed": bool(v[5])} for v, r in zip(EventAxis.values(axis_rows), rows)]
 
 
 class TrackMatcher:

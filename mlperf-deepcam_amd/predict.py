@@ -63,6 +63,13 @@ With --event_shape (which implies --events) nn.EventShape adds the geometry of e
 carries ``event_shape`` (int64 [n, 12]: boundary pixels, the two face counts and the nine moment sums -- the rows of ``events``, in their
 order), ``event_shape_values`` (float64 [n, 10]: lat, lon, length_km, width_km, aspect, orientation_deg, perimeter_km, area_km2,
 compactness, boundary_pixels) and ``event_shape_value_names`` (uint8: that column order, comma-separated ASCII).
+
+With --event_axis (which implies --events) nn.EventAxis thins the mask the catalogue takes -- the decided, filtered or pooled one where
+those flags are on -- to skeletons and measures them per event: every output file also carries ``prediction_axis`` (uint8 [H, W]: k on a
+skeleton pixel of class k), ``event_axis`` (int64 [n, 7]: skeleton pixels, endpoints, junctions, the three link counts and the length in
+metres -- the rows of ``events``, in their order) and ``event_axis_values`` (float64 [n, 6]: skeleton_pixels, endpoints, junctions,
+branches, axis_km, closed); summary.json gains ``event_axis``: per class the events, the mean and the maximum axis_km, and the frames
+whose thinning stopped at max_iters.  axis_km is the skeleton's total length with its branches, not its longest path.
 With --event_filter nn.EventFilter drops, on the device, the events of the classifier's mask that miss the --filter_min_pixels,
 --filter_min_area_km2, --filter_min_length_km or --filter_min_aspect of their class (two values each: class 1, class 2; 0: off).
 ``prediction`` stays the classifier's mask, ``prediction_filtered`` is added, and EVERYTHING downstream takes the filtered mask: the
@@ -218,6 +225,9 @@ def build_parser():
     AP.add_argument("--event_shape", action=_implies("event_shape", "events"),
                     help="per event its geometry (implies --events): spherical centroid, length, width, "
                     "aspect, orientation, perimeter, compactness; datasets 'event_shape', 'event_shape_values', 'event_shape_value_names'")
+    AP.add_argument("--event_axis", action=_implies("event_axis", "events", default=argparse.SUPPRESS),
+                    help="per event its skeleton and the length along it (implies --events): datasets 'prediction_axis', 'event_axis', "
+                    "'event_axis_values'; 'event_axis' in the summary")
     AP.add_argument("--event_filter", action="store_true", help="filter the classifier's mask by event size and shape on the device (the "
                     "--filter_* thresholds): dataset 'prediction_filtered', 'event_filter' in the summary; --events, --verify's prediction "
                     "side, --event_fields, --tracks, --track_fields, --climatology and --plots all take the FILTERED mask.  The labels "
@@ -762,7 +772,11 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=(),
-                 ensemble: bool = False):
+                 ensemble: bool = False, event_axis: bool = False):
+        # --event_axis: the skeleton, the pass counts and the rows of nn.EventAxis (cap rows of 56 bytes per sample)
+        self.askel = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if event_axis else None
+        self.aiters = torch.empty((B, 2, 2), dtype=torch.int32).pin_memory() if event_axis else None
+        self.axis = torch.empty((B, event_cap, len(dnn.EVENT_AXIS_FIELDS)), dtype=torch.int64).pin_memory() if event_axis else None
         # --ensemble_*: the pooled mask, its confidence and the counters of nn.ViewEnsemble
         self.emask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if ensemble else None
         self.econf = torch.empty((B, H, W), dtype=torch.float32).pin_memory() if ensemble and confidence else None
@@ -816,7 +830,9 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if slot.events is not None:
                         total = int(slot.ncomp[j, 0])
                         rows = slot.events[j, :min(total, slot.events.shape[1])].numpy()
-                        frows = srows = None
+                        frows = srows = arows = None
+                        if slot.axis is not None:
+                            arows = np.ascontiguousarray(slot.axis[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.fields is not None:          # the filter of `events`, whichever branch below applies it
                             frows = np.ascontiguousarray(slot.fields[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.shape is not None:
@@ -836,6 +852,9 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             H, W = slot.mask.shape[1:]
                             extra = dict(extra or {}, event_shape=srows, event_shape_values=dnn.EventShape.values(srows, rows, H, W),
                                          event_shape_value_names=np.frombuffer(",".join(dnn.EVENT_SHAPE_VALUES).encode(), np.uint8).copy())
+                        if arows is not None:
+                            extra = dict(extra or {}, prediction_axis=slot.askel[j].numpy(), event_axis=arows,
+                                         event_axis_values=dnn.EventAxis.values(arows))
                     if slot.emask is not None:
                         extra = dict(extra or {}, prediction_ensemble=slot.emask[j].numpy(), ensemble_rows=slot.erows[j].numpy())
                         if slot.econf is not None:
@@ -867,6 +886,10 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if rows is not None:
                         rec["events"] = [int((rows[:, 1] == 1).sum()), int((rows[:, 1] == 2).sum())]
                         rec["events_overflowed"] = total > slot.events.shape[1]
+                    if extra is not None and "event_axis" in extra:      # per class: events, sum and maximum of axis_km; any plane stopped
+                        km = [extra["event_axis"][rows[:, 1] == k, 6] / 1000.0 for k in (1, 2)]
+                        rec["event_axis"] = {"classes": [[len(v), float(v.sum()), float(v.max()) if len(v) else 0.0] for v in km],
+                                             "stopped": bool((slot.aiters[j, :, 1] == 0).any())}
                     if extra is not None and "event_fields" in extra:
                         rec["event_field_counts"] = [int(extra["event_fields"][..., 4].sum()), int(extra["event_fields"][..., 5].sum())]
                     if extra is not None and "event_scores" in extra:
@@ -941,6 +964,7 @@ def main(pargs) -> dict:
     own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
+    eaxis = dnn.EventAxis(catalog) if getattr(pargs, "event_axis", False) else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
     efields = field_bits = None
     if getattr(pargs, "event_fields", False):
@@ -1012,7 +1036,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, decide is not None,
-                             frame_skills, ens is not None))
+                             frame_skills, ens is not None, eaxis is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -1065,6 +1089,11 @@ def main(pargs) -> dict:
                     slot.frames[key][:nv].copy_(rows, non_blocking=True)
             if eshape is not None:
                 slot.shape[:nv].copy_(eshape(nv).table, non_blocking=True)
+            if eaxis is not None:                  # behind the catalogue's launches, on the mask it took
+                eaxis(dmask, n_valid=nv)
+                slot.askel[:nv].copy_(eaxis.skeleton_buffer[:nv], non_blocking=True)
+                slot.aiters[:nv].copy_(eaxis._iters[:nv], non_blocking=True)
+                slot.axis[:nv].copy_(eaxis.table, non_blocking=True)
             if tracker is not None:
                 tracker(dmask, n_valid=nv)
             if tmatch is not None:
@@ -1137,6 +1166,12 @@ def main(pargs) -> dict:
     if efilter is not None:
         summary["event_filter"] = dict(efilter.thresholds(), classes=[
             {k: sum(r["event_filter"][j][k] for r in records) for k in dnn.EVENT_FILTER_COUNTS} for j in range(2)])
+    if eaxis is not None:
+        per = [[r["event_axis"]["classes"][k] for r in records] for k in range(2)]
+        count = [sum(c[0] for c in cl) for cl in per]
+        summary["event_axis"] = {"events": count, "mean_axis_km": [sum(c[1] for c in cl) / n if n else None for cl, n in zip(per, count)],
+                                 "max_axis_km": [max((c[2] for c in cl), default=0.0) for cl in per], "max_iters": eaxis.max_iters,
+                                 "frames_at_max_iters": sum(1 for r in records if r["event_axis"]["stopped"])}
     if efields is not None:
         summary["event_fields"] = {"channels": efields.C, "scale_bits": [int(v) for v in field_bits],
                                    "nonfinite": sum(r["event_field_counts"][0] for r in records),
