@@ -79,6 +79,7 @@ int dc_reset_options(void);
  *   event shapes and the shape filter (dc_component_shape, dc_event_select, dc_mask_select): cc_shape (every launch of the three calls)
  *   event skeletons (dc_mask_thin, dc_skeleton_stats): skel_thin (one workgroup per class and frame, the bit plane thinned in LDS),
  *     skel_stats (both launches of the statistics call: the rows zeroed, the pixel pass)
+ *   spur pruning and the axis criterion (dc_skeleton_prune, dc_event_select_axis): skel_prune (the launch of either call)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   track verification (dc_track_match_append, dc_track_match_resolve): cc_track_match (every launch of both calls)
@@ -827,6 +828,56 @@ int dc_mask_thin(int B, int n_valid, int H, int W, const void* mask, int mask_by
                  int32_t* iters, void* stream);
 int dc_skeleton_stats(int B, int n_valid, int H, int W, const uint8_t* skeleton, const int32_t* labels, const void* ws, int cap, int wrap,
                       const int32_t* link_table, int64_t* rows, void* stream);
+
+/* Spur pruning of skeletons (nn.EventAxis(prune=N); predict.py --event_axis_prune N).  Guo and Hall's thinning leaves a short spur at
+ * every bump of an outline, and each spur adds its length to the skeleton's: dc_skeleton_prune removes the branches of at most `spur`
+ * pixels and leaves everything else as it was.
+ *   skeleton  uint8 [B][H][W], as dc_mask_thin leaves it: k on the pixels of class k in {1, 2}, 0 elsewhere.  The call is correct for any
+ *             such map, not only for true skeletons.
+ *   Each class plane is handled on its own.  Neighbours are the set bits of that plane, numbered P2 .. P9 as in the thinning text above.
+ *   Rows outside the frame are background.  Columns are periodic under `wrap`, and background otherwise.
+ *   pruned    uint8 [B][H][W], same coding as the input.  It may not overlap skeleton.
+ *   removed   int32 [B][2]: the pixels of class k in the input that are absent from pruned.
+ *   spur      1 <= spur <= 1024; anything else is refused.
+ * A grid whose plane exceeds the LDS is refused, exactly as dc_mask_thin refuses it (dc_thin_lds_bytes).
+ *
+ * Endpoint.  E(S) is the set of pixels of S whose ring P2..P9 has either:
+ *   - exactly one set neighbour, or
+ *   - exactly two set neighbours that are consecutive in the cyclic order P2, P3, ..., P9, P2.  Such a pair is 4-adjacent to each other:
+ *     the tip of a staircase.
+ * Isolated pixels are not endpoints.
+ *
+ * Backward and forward.  The backward neighbours are P8, P9, P2, P3.  The forward ones are P4, P5, P6, P7.  If Q is a forward neighbour
+ * of P, then P is a backward neighbour of Q.
+ *
+ * Shrink.  Repeat the following `spur` times, stopping early when a round deletes nothing.  S is the plane as the round found it.
+ *   - A = pixels of E(S) that have a backward neighbour in S.  Then S' = S \ A.
+ *   - Bc = E(S) \ A.  Both E and A are judged on S, not on S'.
+ *   - B = pixels of Bc that still have at least one neighbour in S'.  Then S'' = S' \ B.
+ * (Every end loses exactly one pixel per round, whichever way it points, and no 8-connected component of the input ever loses all its
+ * pixels: a two-pixel line keeps one pixel, a closed ring keeps everything.)
+ * Call the result X1, and let D = input \ X1.
+ *
+ * Regrow.
+ *   - Seeds G0 are E(X1) together with the isolated pixels of X1.
+ *   - Repeat `spur` times, stopping early when nothing is added: G <- G u (dilate8(G) n D).
+ *   - The result is X1 u G.
+ * A branch of at most `spur` pixels hanging off a pixel that stays a non-endpoint is gone.  A longer branch, and both ends of the main
+ * course, come back in full.  A removed spur that touches the regrown chain within `spur` pixels of an end can grow back in part: a known
+ * property of the method (Gonzalez and Woods, Digital Image Processing, "pruning").
+ * Samples from n_valid on are neither read nor written.  Does not synchronise.
+ *
+ * dc_event_select_axis, the axis criterion of the event filter (nn.EventFilter(min_axis_km=, axis=); predict.py --filter_min_axis_km).  It
+ * runs behind dc_event_select and in front of dc_mask_select, on the keep bytes and the counts the former left:
+ *   axis_rows  int64 [B][cap][7], the rows of dc_skeleton_stats for the same catalogue (table, ncomp, cap as dc_event_select takes them)
+ *   min_axis_m_1, min_axis_m_2   metres, for class 1 and class 2; 0: off; negative values are refused
+ * An event of class k with a row, whose keep is 1 and whose axis_rows[..][6] (length_m) is below min_axis_m_k: its keep becomes 0, and
+ * counts moves one event of class k from kept to dropped.  Integer arithmetic only; the result is independent of scheduling.
+ * dc_mask_select is unchanged and then counts the pixels as it does without this call.  Does not synchronise. */
+int dc_skeleton_prune(int B, int n_valid, int H, int W, const uint8_t* skeleton, int wrap, int spur, uint8_t* pruned, int32_t* removed,
+                      void* stream);
+int dc_event_select_axis(int B, int n_valid, int cap, const int64_t* table, const int32_t* ncomp, const int64_t* axis_rows,
+                         long long min_axis_m_1, long long min_axis_m_2, uint8_t* keep, int64_t* counts, void* stream);
 
 /* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
  * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in

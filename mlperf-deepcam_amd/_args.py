@@ -76,3 +76,9 @@ def check_range(who: str, name: str, v: int, lo: int, hi: int) -> None:
     """Raises unless the integer v lies in [lo, hi]."""
     if not lo <= v <= hi:
         raise L.DeepcamHipError(f"{who}: {name} must lie in [{lo}, {hi}], got {v}")
+
+
+def check_axis(who: str, name: str, wanted: bool, axis, catalog) -> None:
+    """Raises where a criterion on the skeleton's length is set (wanted) without an EventAxis built on `catalog` to measure it."""
+    if wanted and (axis is None or getattr(axis, "catalog", None) is not catalog):
+        raise L.DeepcamHipError(f"{who}: a non-zero {name} needs axis=, an EventAxis on the filter's own catalogue")

@@ -33,35 +33,9 @@
 //              the workgroup's slot table (slot_claim), a full table sends it to its global row, filled slots are flushed at the end.
 //              event_shape.hip's staging, lane layout and row stride (SH_STRIDE has the bank argument), with this kernel's seven terms.
 // 64-bit integer atomics only; no workgroup waits for another.
-#include "event_common.h"
-#include "mask_skill.h"
+#include "skeleton_bits.h"
 
 namespace dc {
-
-static constexpr int TH_THREADS = 1024, TH_WAVES = TH_THREADS / 64;
-static constexpr int TH_WPT = 20;                 // words a thread owns at most
-static constexpr int TH_SCRATCH = 64;             // bytes behind the plane: the two "anything deleted" flags and "not empty"
-static constexpr int TH_LDS_MAX = 160 * 1024;     // a gfx950 CU
-static_assert((size_t)TH_THREADS * TH_WPT * 8 + TH_SCRATCH >= TH_LDS_MAX, "th_thin: the threads' words cover every plane the LDS holds");
-
-typedef unsigned long long u64;
-
-static inline size_t th_lds_bytes(int H, int W) {
-  if (H < 1 || W < 1) return 0;
-  const size_t bytes = (size_t)H * ((size_t)(W + 63) / 64) * 8 + TH_SCRATCH;
-  return bytes <= (size_t)TH_LDS_MAX ? bytes : 0;
-}
-
-// the plane of the western / eastern neighbours of a word's 64 pixels: a funnel shift with the word to the left / right.  `in` is the bit
-// that enters: for an inner word the neighbouring word's bit 63 / bit 0; at the seam the row's other end under wrap, 0 without.
-__device__ inline u64 th_west(u64 x, u64 left, bool first, int lastbit, int wrap) {
-  const u64 in = first ? (wrap ? (left >> lastbit) & 1ull : 0ull) : left >> 63;      // first: `left` is the row's last word
-  return (x << 1) | in;
-}
-__device__ inline u64 th_east(u64 x, u64 right, bool last, int lastbit, int wrap) {
-  const u64 in = last ? (wrap ? (right & 1ull) << lastbit : 0ull) : right << 63;     // last: `right` is the row's first word
-  return (x >> 1) | in;
-}
 
 // n >= 2 and n == 4 of n = a + b + c + d, bit-sliced: a full adder on (a, b, c), a half adder on its sum and d
 __device__ inline void th_sum4(u64 a, u64 b, u64 c, u64 d, u64* ge2, u64* eq4) {
@@ -74,16 +48,9 @@ __device__ inline void th_sum4(u64 a, u64 b, u64 c, u64 d, u64* ge2, u64* eq4) {
 // the pixels of word i (value c, not zero) that sub-pass SUB (0: A, 1: B) deletes
 template <int SUB>
 __device__ inline u64 th_delete(const u64* P, int i, u64 c, int H, int TW, int lastbit, int wrap) {
-  const int r = i / TW, cw = i - r * TW;
-  const bool first = cw == 0, last = cw == TW - 1;
-  const int il = first ? i + TW - 1 : i - 1, ir = last ? i - cw : i + 1;
-  const u64 ml = P[il], mr = P[ir];
-  u64 u = 0, ul = 0, ur = 0, d = 0, dl = 0, dr = 0;
-  if (r > 0) u = P[i - TW], ul = P[il - TW], ur = P[ir - TW];          // rows outside the frame are background
-  if (r < H - 1) d = P[i + TW], dl = P[il + TW], dr = P[ir + TW];
-  const u64 p2 = u, p3 = th_east(u, ur, last, lastbit, wrap), p4 = th_east(c, mr, last, lastbit, wrap);
-  const u64 p5 = th_east(d, dr, last, lastbit, wrap), p6 = d, p7 = th_west(d, dl, first, lastbit, wrap);
-  const u64 p8 = th_west(c, ml, first, lastbit, wrap), p9 = th_west(u, ul, first, lastbit, wrap);
+  u64 p[8];
+  th_ring(P, i, c, H, TW, lastbit, wrap, p);
+  const u64 p2 = p[0], p3 = p[1], p4 = p[2], p5 = p[3], p6 = p[4], p7 = p[5], p8 = p[6], p9 = p[7];
   // C == 1: exactly one of the four terms -- odd parity, and no pair (three terms hold one of the two pairs)
   const u64 t1 = ~p2 & (p3 | p4), t2 = ~p4 & (p5 | p6), t3 = ~p6 & (p7 | p8), t4 = ~p8 & (p9 | p2);
   const u64 c1 = (t1 ^ t2 ^ t3 ^ t4) & ~((t1 & t2) | (t3 & t4));
@@ -125,15 +92,6 @@ __device__ inline bool th_subpass(u64* P, volatile unsigned* flag, int n, int H,
   if (__ballot(any != 0) && (threadIdx.x & 63) == 0) flag[SUB] = 1u;
   __syncthreads();
   return flag[SUB] != 0u;
-}
-
-// the class (0, 1, 2) of lane `lane`'s pixel of word `item`; TH_NONE where the word or the column lies outside the plane
-static constexpr unsigned TH_NONE = 3u;
-static constexpr int TH_BATCH = 4;
-__device__ inline unsigned th_class(const void* __restrict__ mask, int mask_bytes, size_t base, int item, int n, int TW, int W, int lane) {
-  if (item >= n) return TH_NONE;
-  const int r = item / TW, col = (item - r * TW) * 64 + lane;
-  return col < W ? mask_class(mask, base + (size_t)r * W + col, mask_bytes) : TH_NONE;
 }
 
 __global__ __launch_bounds__(TH_THREADS) void th_thin_kernel(int H, int W, const void* __restrict__ mask, int mask_bytes, int wrap,

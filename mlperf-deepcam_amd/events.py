@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from ._args import _ratio, check_range, check_tensor, device_of
+from ._args import _ratio, check_axis, check_range, check_tensor, device_of
 
 EVENT_FIELDS = ("root", "class", "pixels", "area", "sum_row", "sum_cx", "sum_sx", "row_min", "row_max", "seam")
 EVENT_SCALE = 1 << 20
@@ -591,17 +591,29 @@ class EventFilter:
     EventShape): an event of class k is kept iff it has at least min_pixels[k] pixels, min_area_km2[k] of area, min_length_km[k] of length
     and min_aspect[k] of aspect (EventShape.decode's numbers; 0: the criterion is off), and the filtered mask keeps the pixels of kept
     events -- and of events beyond the catalogue's cap, for which nothing was evaluated.  Each threshold is a pair (class 1, class 2).
+    min_axis_km is the criterion on the length ALONG the event's skeleton (EventAxis.decode's axis_km; pruned where the axis prunes): it
+    needs `axis`, an EventAxis on the same catalogue, which the filter then calls on the raw mask behind the catalogue, and
+    dc_event_select_axis between the two launches below.  Without it the filter launches exactly what it launches without the argument.
     `catalog` is the filter's own catalogue of the RAW mask; whatever consumes the filtered mask (another EventCatalog, a matcher, a
     tracker, ...) does so unchanged.  Nothing is copied to the host and nothing synchronises."""
 
-    def __init__(self, catalog: EventCatalog, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0)):
+    def __init__(self, catalog: EventCatalog, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0),
+                 min_axis_km=(0, 0), axis: Optional["EventAxis"] = None):
         self.min_pixels, self.min_area_km2 = self._pair(min_pixels, "min_pixels"), self._pair(min_area_km2, "min_area_km2")
         self.min_length_km, self.min_aspect = self._pair(min_length_km, "min_length_km"), self._pair(min_aspect, "min_aspect")
+        self.min_axis_km = self._pair(min_axis_km, "min_axis_km")
+        self.min_axis_m = tuple(self.axis_units(v) for v in self.min_axis_km)
+        check_axis("EventFilter", "min_axis_km", any(self.min_axis_m), axis, catalog)
+        self.axis = axis if any(self.min_axis_m) else None
         self.catalog = catalog
         self.shape = EventShape(catalog)
         dev = catalog._labels.device
-        self.criteria = self.criteria_rows(catalog.H, catalog.W, self.min_pixels, self.min_area_km2, self.min_length_km, self.min_aspect)
-        self._criteria = torch.from_numpy(self.criteria.view(np.int64).copy()).to(dev)
+        self.criteria = self.criteria_rows(catalog.H, catalog.W, self.min_pixels, self.min_area_km2, self.min_length_km, self.min_aspect,
+                                           self.min_axis_km if self.axis is not None else None)
+        words = np.zeros(2, self.CRITERIA)        # dc_event_select's four words per class; min_axis_m travels as an argument
+        for name in self.CRITERIA.names:
+            words[name] = self.criteria[name]
+        self._criteria = torch.from_numpy(words.view(np.int64).copy()).to(dev)
         self._keep = torch.zeros((catalog.B, catalog.cap), dtype=torch.uint8, device=dev)
         self._counts = torch.zeros((catalog.B, 2, len(EVENT_FILTER_COUNTS)), dtype=torch.int64, device=dev)
         self._out = torch.zeros((catalog.B, catalog.H, catalog.W), dtype=torch.uint8, device=dev)
@@ -651,20 +663,36 @@ class EventFilter:
     def aspect(aspect2: float) -> float:
         return math.sqrt(aspect2)
 
+    @staticmethod
+    def axis_units(km: float) -> int:
+        """min_axis_m: the smallest length_m (whole metres) that is at least km"""
+        return int(math.ceil(float(km) * 1000.0))
+
+    @staticmethod
+    def axis_km(metres: int) -> float:
+        return metres / 1000.0
+
     CRITERIA = np.dtype([("min_pixels", np.int64), ("min_area", np.int64), ("min_len2", np.float64), ("min_aspect2", np.float64)])
 
     @staticmethod
-    def criteria_rows(height: int, width: int, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0)) -> np.ndarray:
-        """the two rows dc_event_select takes (class 1, class 2), a numpy record array of dtype CRITERIA"""
-        out = np.zeros(2, EventFilter.CRITERIA)
+    def criteria_rows(height: int, width: int, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0),
+                      min_axis_km=None) -> np.ndarray:
+        """the two rows dc_event_select takes (class 1, class 2), a numpy record array of dtype CRITERIA; with min_axis_km a record array of
+        CRITERIA's fields and min_axis_m, the two words dc_event_select_axis takes (dc_event_select takes the rows without it)"""
+        dtype = EventFilter.CRITERIA if min_axis_km is None else np.dtype(EventFilter.CRITERIA.descr + [("min_axis_m", np.int64)])
+        out = np.zeros(2, dtype)
         for k in range(2):
-            out[k] = (int(math.ceil(min_pixels[k])), EventFilter.area_units(min_area_km2[k], height, width),
-                      EventFilter.length_units(min_length_km[k]), EventFilter.aspect_units(min_aspect[k]))
+            row = (int(math.ceil(min_pixels[k])), EventFilter.area_units(min_area_km2[k], height, width),
+                   EventFilter.length_units(min_length_km[k]), EventFilter.aspect_units(min_aspect[k]))
+            out[k] = row if min_axis_km is None else row + (EventFilter.axis_units(min_axis_km[k]),)
         return out
 
     def thresholds(self) -> dict:
-        return {"min_pixels": list(self.min_pixels), "min_area_km2": list(self.min_area_km2), "min_length_km": list(self.min_length_km),
-                "min_aspect": list(self.min_aspect)}
+        out = {"min_pixels": list(self.min_pixels), "min_area_km2": list(self.min_area_km2), "min_length_km": list(self.min_length_km),
+               "min_aspect": list(self.min_aspect)}
+        if self.axis is not None:
+            out["min_axis_km"] = list(self.min_axis_km)
+        return out
 
     def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
         """mask: device uint8 [B, H, W].  Returns the filtered mask [n_valid, H, W], a view of a buffer this object owns (mask_buffer is
@@ -673,9 +701,14 @@ class EventFilter:
         cat(mask, n_valid=n_valid)
         nv = cat._last_valid
         self.shape(nv)
+        if self.axis is not None:
+            self.axis(mask, n_valid=nv)
         st = L.stream_ptr()
         L.call("dc_event_select", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(self.shape._shape), L.dptr(self._criteria),
                L.dptr(self._keep), L.dptr(self._counts), st)
+        if self.axis is not None:
+            L.call("dc_event_select_axis", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(self.axis._rows),
+                   self.min_axis_m[0], self.min_axis_m[1], L.dptr(self._keep), L.dptr(self._counts), st)
         L.call("dc_mask_select", cat.B, nv, cat.H, cat.W, L.dptr(mask), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, L.dptr(self._keep),
                L.dptr(self._out), L.dptr(self._counts), st)
         self._last_valid = nv
@@ -1029,9 +1062,15 @@ class EventAxis:
     one class plane of one frame inside the LDS of a CU, so the plane must fit there (768 x 1152 does; the constructor raises where
     not).  max_iters bounds the passes (default max(H, W): a layer goes from every side in each pass); iterations() tells which frames
     hit it.  The object owns the link table, the skeleton (uint8 [B, H, W]), the pass counts (int32 [B, 2, 2]) and the rows (int64
-    [B, cap, 7]; row k belongs to row k of the catalogue's table)."""
+    [B, cap, 7]; row k belongs to row k of the catalogue's table).
+    prune = N > 0 (at most 1024) removes the skeleton's spurs of at most N pixels before it is measured (dc_skeleton_prune; the header
+    has the rule: N rounds that take one pixel off every end, then N rounds of regrowth from the ends that are left, so a longer branch
+    and both ends of the main course come back in full; a removed spur that touches the regrown chain within N pixels of an end can grow
+    back in part).  A call then launches dc_mask_thin, dc_skeleton_stats on the thinned map (raw_table), dc_skeleton_prune, and
+    dc_skeleton_stats on the pruned map: table, rows() and skeleton_buffer describe the PRUNED skeleton, raw_table, raw_rows() and
+    raw_skeleton_buffer the thinned one, removed() counts the pixels taken.  With prune = 0 nothing of this exists or runs."""
 
-    def __init__(self, catalog: EventCatalog, max_iters: Optional[int] = None):
+    def __init__(self, catalog: EventCatalog, max_iters: Optional[int] = None, prune: int = 0):
         if L.load().dc_thin_lds_bytes(catalog.H, catalog.W) == 0:
             raise L.DeepcamHipError(f"EventAxis: the bit plane of {catalog.H} x {catalog.W} does not fit the LDS of one CU")
         self.max_iters = max(catalog.H, catalog.W) if max_iters is None else int(max_iters)
@@ -1045,6 +1084,11 @@ class EventAxis:
         self._iters = torch.zeros((catalog.B, 2, 2), dtype=torch.int32, device=dev)
         self._rows = torch.zeros((catalog.B, catalog.cap, len(EVENT_AXIS_FIELDS)), dtype=torch.int64, device=dev)
         self._last_valid = 0
+        self.prune = int(prune)
+        check_range("EventAxis", "prune", self.prune, 0, 1024)
+        if self.prune:
+            self._raw_skel, self._raw_rows = torch.zeros_like(self._skel), torch.zeros_like(self._rows)
+            self._removed = torch.zeros((catalog.B, 2), dtype=torch.int32, device=dev)
 
     def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventAxis":
         """mask: the contiguous device tensor [B, H, W] the catalogue was called with (uint8; int32 and int64 are read as they are).
@@ -1054,10 +1098,18 @@ class EventAxis:
                      "uint8, int32 or int64")
         nv = cat._last_valid if n_valid is None else int(n_valid)
         st = L.stream_ptr()
-        L.call("dc_mask_thin", cat.B, nv, cat.H, cat.W, L.dptr(mask), mask.element_size(), int(cat.wrap), self.max_iters, L.dptr(self._skel),
+        def stats(skel, rows):
+            L.call("dc_skeleton_stats", cat.B, nv, cat.H, cat.W, L.dptr(skel), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, int(cat.wrap),
+                   L.dptr(self._link), L.dptr(rows), st)
+
+        thinned = self._raw_skel if self.prune else self._skel
+        L.call("dc_mask_thin", cat.B, nv, cat.H, cat.W, L.dptr(mask), mask.element_size(), int(cat.wrap), self.max_iters, L.dptr(thinned),
                L.dptr(self._iters), st)
-        L.call("dc_skeleton_stats", cat.B, nv, cat.H, cat.W, L.dptr(self._skel), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, int(cat.wrap),
-               L.dptr(self._link), L.dptr(self._rows), st)
+        if self.prune:
+            stats(thinned, self._raw_rows)
+            L.call("dc_skeleton_prune", cat.B, nv, cat.H, cat.W, L.dptr(thinned), int(cat.wrap), self.prune, L.dptr(self._skel),
+                   L.dptr(self._removed), st)
+        stats(self._skel, self._rows)
         self._last_valid = nv
         return self
 
@@ -1070,6 +1122,32 @@ class EventAxis:
     def table(self) -> torch.Tensor:
         """int64 [n_valid, cap, 7] of the last call (a view): zero from min(count, cap) on"""
         return self._rows[:self._last_valid]
+
+    def _pruning(self, what: str) -> None:
+        if not self.prune:
+            raise L.DeepcamHipError(f"EventAxis: {what} exists only with prune > 0")
+
+    @property
+    def raw_skeleton_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W], with prune > 0: the thinned skeletons before pruning (skeleton_buffer holds the pruned ones)"""
+        self._pruning("raw_skeleton_buffer")
+        return self._raw_skel
+
+    @property
+    def raw_table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, 7], with prune > 0: the rows of the thinned skeletons before pruning (a view)"""
+        self._pruning("raw_table")
+        return self._raw_rows[:self._last_valid]
+
+    def raw_rows(self):
+        """rows() of the thinned skeletons before pruning"""
+        self._pruning("raw_rows")
+        return _filled_rows(self._raw_rows, self.catalog._fill(self._last_valid)) if self._last_valid else []
+
+    def removed(self) -> np.ndarray:
+        """int32 numpy [n_valid, 2], with prune > 0: per sample and class the skeleton pixels that pruning took"""
+        self._pruning("removed")
+        return self._removed[:self._last_valid].cpu().numpy()
 
     def iterations(self) -> np.ndarray:
         """int32 numpy [n_valid, 2, 2]: per sample and class the passes run (the final empty one counted) and 1 / 0 for converged"""
@@ -1085,7 +1163,8 @@ class EventAxis:
     def axes(self):
         """Per valid sample of the last call a list of dicts (decode), one per row of the catalogue."""
         _, rows = self.catalog.rows()
-        return [self.decode(a, r, self.catalog.H, self.catalog.W) for a, r in zip(self.rows(), rows)]
+        raw = self.raw_rows() if self.prune else [None] * len(rows)
+        return [self.decode(a, r, self.catalog.H, self.catalog.W, w) for a, r, w in zip(self.rows(), rows, raw)]
 
     @staticmethod
     def values(axis_rows) -> np.ndarray:
@@ -1099,14 +1178,19 @@ class EventAxis:
         return out
 
     @staticmethod
-    def decode(axis_rows, rows, height: int, width: int):
+    def decode(axis_rows, rows, height: int, width: int, raw_axis_rows=None):
         """Axis rows [n, 7] (EVENT_AXIS_FIELDS) and the events' own rows [n, 10] (EVENT_FIELDS) -> one dict per event: class,
         skeleton_pixels, endpoints, junctions, branches = max(endpoints - 2, 0), axis_km = length_m / 1000, closed = (endpoints == 0 and
         skeleton_pixels > 1).  axis_km is the TOTAL length of the skeleton with its branches (the links of axis_link_table(height, width)
-        summed), not the longest path through it: a spur adds its length."""
+        summed), not the longest path through it: a spur adds its length -- unless the rows are those of a pruned skeleton.  With
+        raw_axis_rows, the rows of the thinned skeleton before pruning, every dict gains axis_km_unpruned and spur_km, their difference."""
         rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
-        return [{"class": int(r[1]), "skeleton_pixels": int(v[0]), "endpoints": int(v[1]), "junctions": int(v[2]), "branches": int(v[3]),
-                 "axis_km": float(v[4]), "closed": bool(v[5])} for v, r in zip(EventAxis.values(axis_rows), rows)]
+        out = [{"class": int(r[1]), "skeleton_pixels": int(v[0]), "endpoints": int(v[1]), "junctions": int(v[2]), "branches": int(v[3]),
+                "axis_km": float(v[4]), "closed": bool(v[5])} for v, r in zip(EventAxis.values(axis_rows), rows)]
+        if raw_axis_rows is not None:
+            for d, w in zip(out, EventAxis.values(raw_axis_rows)):
+                d["axis_km_unpruned"], d["spur_km"] = float(w[4]), float(w[4]) - d["axis_km"]
+        return out
 
 
 class TrackMatcher:

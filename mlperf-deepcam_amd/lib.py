@@ -174,6 +174,8 @@ _SIGS = {
     "dc_thin_lds_bytes": (SZ, [I, I]),
     "dc_mask_thin": (I, [I, I, I, I, P, I, I, I, P, P, P]),
     "dc_skeleton_stats": (I, [I, I, I, I, P, P, P, I, I, P, P, P]),
+    "dc_skeleton_prune": (I, [I, I, I, I, P, I, I, P, P, P]),
+    "dc_event_select_axis": (I, [I, I, I, P, P, P, L, L, P, P, P]),
     "dc_track_workspace": (SZ, [I]),
     "dc_track_append": (I, [I, I, I, P, P, L, I, P, P, P, P, P]),
     "dc_track_link": (I, [I, I, I, P, P, P, P, P, P, P, P, I, I, L, P, P, P]),

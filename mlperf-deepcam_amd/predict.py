@@ -70,6 +70,10 @@ skeleton pixel of class k), ``event_axis`` (int64 [n, 7]: skeleton pixels, endpo
 metres -- the rows of ``events``, in their order) and ``event_axis_values`` (float64 [n, 6]: skeleton_pixels, endpoints, junctions,
 branches, axis_km, closed); summary.json gains ``event_axis``: per class the events, the mean and the maximum axis_km, and the frames
 whose thinning stopped at max_iters.  axis_km is the skeleton's total length with its branches, not its longest path.
+--event_axis_prune N removes the skeleton's spurs of at most N pixels first (nn.EventAxis(prune=N)): ``prediction_axis`` and the rows are
+then those of the PRUNED skeleton, and the summary's ``event_axis`` gains ``prune`` and ``removed_pixels`` (per class).
+--filter_min_axis_km TC AR (with --event_filter; implies --event_axis) adds the length along the skeleton, pruned as --event_axis_prune
+says, to the filter's criteria: the filter measures the events of the UNFILTERED mask with an axis of its own before it selects.
 With --event_filter nn.EventFilter drops, on the device, the events of the classifier's mask that miss the --filter_min_pixels,
 --filter_min_area_km2, --filter_min_length_km or --filter_min_aspect of their class (two values each: class 1, class 2; 0: off).
 ``prediction`` stays the classifier's mask, ``prediction_filtered`` is added, and EVERYTHING downstream takes the filtered mask: the
@@ -228,6 +232,10 @@ def build_parser():
     AP.add_argument("--event_axis", action=_implies("event_axis", "events", default=argparse.SUPPRESS),
                     help="per event its skeleton and the length along it (implies --events): datasets 'prediction_axis', 'event_axis', "
                     "'event_axis_values'; 'event_axis' in the summary")
+    AP.add_argument("--event_axis_prune", type=int, default=argparse.SUPPRESS, metavar="N", help="with --event_axis: remove the skeleton's "
+                    "spurs of at most N pixels before it is measured (1 .. 1024); 'prune' and 'removed_pixels' in the summary's 'event_axis'")
+    AP.add_argument("--filter_min_axis_km", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("TC", "AR"), help="with --event_filter "
+                    "(implies --event_axis): drop events whose skeleton is shorter than this, measured on the unfiltered mask")
     AP.add_argument("--event_filter", action="store_true", help="filter the classifier's mask by event size and shape on the device (the "
                     "--filter_* thresholds): dataset 'prediction_filtered', 'event_filter' in the summary; --events, --verify's prediction "
                     "side, --event_fields, --tracks, --track_fields, --climatology and --plots all take the FILTERED mask.  The labels "
@@ -928,6 +936,10 @@ def main(pargs) -> dict:
     net.eval()
     layout = "nhwc" if net.engine.x0 is not None else "nchw"
     loader = ddata.InputPipeline(dataset, B, dtype=dtype, device=device, layout=layout, drop_last=False, workers=pargs.max_inter_threads)
+    axis_prune = int(getattr(pargs, "event_axis_prune", 0))
+    filter_min_axis = [float(v) for v in getattr(pargs, "filter_min_axis_km", (0.0, 0.0))]
+    if any(filter_min_axis):                      # implies --event_axis, which implies --events
+        pargs.event_axis = pargs.events = True
     events = bool(pargs.events) or verify or bool(getattr(pargs, "tracks", False))
     # --decision_*: the rule takes the stored logits; everything below, the filter included, takes the decided mask
     decision = decision_options(pargs)
@@ -937,9 +949,10 @@ def main(pargs) -> dict:
     # --event_filter: the filter's own catalogue takes the mask as it arrives; everything below takes the filtered one
     efilter = None
     if getattr(pargs, "event_filter", False):
-        efilter = dnn.EventFilter(dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device),
-                                  min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
-                                  min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect)
+        fcat = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
+        efilter = dnn.EventFilter(fcat, min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
+                                  min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect, min_axis_km=filter_min_axis,
+                                  axis=dnn.EventAxis(fcat, prune=axis_prune) if any(filter_min_axis) else None)
     # --ensemble_*: the views of every batch pooled into one logits tensor, which then stands where the classifier's stood
     ens_options = ensemble_options(pargs, W, pargs.channels)
     ens = ens_view = ens_sign = None
@@ -964,7 +977,8 @@ def main(pargs) -> dict:
     own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
-    eaxis = dnn.EventAxis(catalog) if getattr(pargs, "event_axis", False) else None
+    eaxis = dnn.EventAxis(catalog, prune=axis_prune) if getattr(pargs, "event_axis", False) else None
+    axis_removed = torch.zeros(2, dtype=torch.int64, device=device) if eaxis is not None and axis_prune else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
     efields = field_bits = None
     if getattr(pargs, "event_fields", False):
@@ -1094,6 +1108,8 @@ def main(pargs) -> dict:
                 slot.askel[:nv].copy_(eaxis.skeleton_buffer[:nv], non_blocking=True)
                 slot.aiters[:nv].copy_(eaxis._iters[:nv], non_blocking=True)
                 slot.axis[:nv].copy_(eaxis.table, non_blocking=True)
+                if axis_removed is not None:
+                    axis_removed += eaxis._removed[:nv].sum(dim=0)
             if tracker is not None:
                 tracker(dmask, n_valid=nv)
             if tmatch is not None:
@@ -1172,6 +1188,8 @@ def main(pargs) -> dict:
         summary["event_axis"] = {"events": count, "mean_axis_km": [sum(c[1] for c in cl) / n if n else None for cl, n in zip(per, count)],
                                  "max_axis_km": [max((c[2] for c in cl), default=0.0) for cl in per], "max_iters": eaxis.max_iters,
                                  "frames_at_max_iters": sum(1 for r in records if r["event_axis"]["stopped"])}
+        if axis_removed is not None:
+            summary["event_axis"].update(prune=axis_prune, removed_pixels=[int(v) for v in axis_removed.tolist()])
     if efields is not None:
         summary["event_fields"] = {"channels": efields.C, "scale_bits": [int(v) for v in field_bits],
                                    "nonfinite": sum(r["event_field_counts"][0] for r in records),

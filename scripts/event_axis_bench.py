@@ -5,6 +5,10 @@
   dc_skeleton_stats    (the rows: pixels, endpoints, junctions, links, length)
   dc_component_shape   (the yardstick: the parent commit has it, and it reads the same label map)
   torch thinning       (the same rule with torch.roll and Boolean operators on the same GPU, both classes, the passes dc_mask_thin ran)
+  dc_skeleton_prune    (nn.EventAxis(prune=N): spurs of at most N = 8, 16, 32 pixels removed from the thinned map, one workgroup per class
+                        and frame; dc_mask_thin above, unchanged code, is its yardstick), the pixels it removes, and what it does to the
+                        events' mean axis_km and their branches
+  dc_event_select_axis (the filter's axis criterion on the catalogue's rows)
 
 on the masks of scripts/events_bench.py: 8 blobs per sample (about 97 % background), 40 blobs per sample and 45 % uniform-random
 foreground; the background share of each is printed.  Every call
@@ -101,6 +105,29 @@ def main():
               f"{t['torch thinning'] / t['dc_mask_thin']:.1f}")
         if t["dc_mask_thin"] > fwd:
             print("    dc_mask_thin takes LONGER than the batch's forward pass: the passes are serial and only 16 of the CUs work")
+        # spur pruning of the thinned map `ref`, and the statistics of the pruned map
+        pruned, removed = torch.empty_like(ref), torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        keep = torch.ones((B, cat.cap), dtype=torch.uint8, device=dev)
+        counts = torch.zeros((B, 2, 4), dtype=torch.int64, device=dev)
+        stats_pruned = lambda: L.call("dc_skeleton_stats", B, B, H, W, L.dptr(pruned), L.dptr(cat._labels), L.dptr(cat._ws),  # noqa: E731
+                                      cat.cap, int(cat.wrap), L.dptr(axis._link), L.dptr(axis._rows), st)
+        stats()
+        torch.cuda.synchronize()
+        before = [dnn.EventAxis.values(r) for r in axis.rows()]
+        for spur in (8, 16, 32):
+            prune = lambda: L.call("dc_skeleton_prune", B, B, H, W, L.dptr(ref), int(cat.wrap), spur, L.dptr(pruned), L.dptr(removed), st)  # noqa: E731
+            tp = med(prune)
+            stats_pruned()
+            torch.cuda.synchronize()
+            after = [dnn.EventAxis.values(r) for r in axis.rows()]
+            km = [float(np.concatenate([v[:, 4] for v in side]).mean()) for side in (before, after)]
+            br = [int(np.concatenate([v[:, 3] for v in side]).sum()) for side in (before, after)]
+            print(f"    dc_skeleton_prune spur {spur:2d} {tp:8.3f} ms/batch = {100 * tp / t['dc_mask_thin']:6.1f} % of dc_mask_thin, "
+                  f"{1000 * tp / (2 * spur):.1f} us per round if all {2 * spur} rounds ran; removed {int(removed.sum())} of "
+                  f"{int((ref != 0).sum())} skeleton pixels; mean axis_km {km[0]:.1f} -> {km[1]:.1f}, branches {br[0]} -> {br[1]}")
+        sel = lambda: L.call("dc_event_select_axis", B, B, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(axis._rows), 0,  # noqa: E731
+                             2000000, L.dptr(keep), L.dptr(counts), st)
+        print(f"    dc_skeleton_stats (pruned map, spur 32) {med(stats_pruned):8.3f} ms/batch; dc_event_select_axis {med(sel):8.3f} ms/batch")
 
 
 if __name__ == "__main__":
