@@ -80,6 +80,7 @@ int dc_reset_options(void);
  *   event skeletons (dc_mask_thin, dc_skeleton_stats): skel_thin (one workgroup per class and frame, the bit plane thinned in LDS),
  *     skel_stats (both launches of the statistics call: the rows zeroed, the pixel pass)
  *   spur pruning and the axis criterion (dc_skeleton_prune, dc_event_select_axis): skel_prune (the launch of either call)
+ *   main course (dc_skeleton_course): skel_course (both launches: the rows zeroed, one workgroup per class and frame for the three sweeps)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   track verification (dc_track_match_append, dc_track_match_resolve): cc_track_match (every launch of both calls)
@@ -878,6 +879,60 @@ int dc_skeleton_prune(int B, int n_valid, int H, int W, const uint8_t* skeleton,
                       void* stream);
 int dc_event_select_axis(int B, int n_valid, int cap, const int64_t* table, const int32_t* ncomp, const int64_t* axis_rows,
                          long long min_axis_m_1, long long min_axis_m_2, uint8_t* keep, int64_t* counts, void* stream);
+
+/* The main course of an event (nn.EventAxis(course=True); predict.py --event_course): the longest path through its skeleton.  length_m of
+ * dc_skeleton_stats is the TOTAL length of the skeleton with all its branches, so a river with one long tributary is measured as the sum
+ * of both arms; dc_skeleton_course measures the main course alone and reports where it starts and ends.
+ *
+ * Graph.
+ *   - Nodes are the skeleton pixels of class k whose label has an event row of rank < `cap`.  This is the node set of dc_skeleton_stats.
+ *   - Edges are exactly the links dc_skeleton_stats counts.  They join 8-adjacent skeleton pixels with the same label word, with columns
+ *     periodic under `wrap` and rows never.
+ *   - A diagonal is an edge only when neither of the two pixels 4-adjacent to both of its ends is a neighbour.
+ *   - Edge weights are int32 metres from nn.axis_link_table:
+ *       link_table[i][0] for an E-W link on row i.
+ *       link_table[i][1] for an N-S link between rows i and i + 1.
+ *       link_table[i][2] for a diagonal between rows i and i + 1.
+ *   - d_x(p) is the length of the shortest path from x to p in this graph.  It is well defined with or without cycles.
+ *
+ * Main course of an event is found by a double sweep with a third sweep to mark the path:
+ *   1. s is the event's node with the smallest pixel index r * W + c.
+ *   2. a is the node maximising d_s.  Ties go to the smallest pixel index.  start_ecc_m = d_s(a).
+ *   3. b is the node maximising d_a, with the same tie rule.  course_m = d_a(b).
+ *   4. A node p lies on the course iff d_a(p) + d_b(p) == course_m.  That is, p is on some shortest a-b path.  course_pixels counts
+ *      these nodes.
+ * (A node that the source of a sweep does not reach takes no part in that sweep's maximum and lies on no course.  The nodes of an event
+ * of the catalogue the skeleton was thinned from are always connected.)
+ *
+ * Properties.
+ *   - On a tree, course_m is the weighted diameter, which is the longest path exactly.
+ *   - On a graph with cycles it is a lower bound of the geodesic diameter: a closed ring measures about half its circumference.
+ *   - An isolated pixel has s = a = b, course_m = 0 and course_pixels = 1.
+ *
+ *   skeleton, labels, ws, cap, wrap, link_table   as dc_skeleton_stats takes them.  The call is correct for any map of 0 / 1 / 2, not
+ *             only for true skeletons.  Link lengths are not negative, and min(dc_course_node_cap(), H * W) * max(link_table) must stay
+ *             below 2^32 - 1: a simple path bounds every distance, and distances are uint32 (nn.EventAxis refuses a grid that breaks
+ *             this; the table lives on the device, so the call cannot look).
+ *   rows      int64 [B][cap][7], zeroed by the call for the samples below n_valid; row k belongs to the event of rank k:
+ *               0 nodes   1 start   2 start_ecc_m   3 end_a   4 end_b   5 course_pixels   6 course_m
+ *             Pixel indices are r * W + c.  course_m sits in column 6, where dc_skeleton_stats keeps length_m: dc_event_select_axis
+ *             reads either table.
+ *   course    uint8 [B][H][W]: k on the course pixels of class k and 0 elsewhere, for the valid samples.  The call writes every byte
+ *             itself, once: the workgroup of class 2 owns the bytes where skeleton holds 2, the workgroup of class 1 every other byte
+ *             (its own pixels, the background, and anything that is neither 0, 1 nor 2).
+ *   status    int32 [B][2][3]: per (frame, class) its nodes, the relaxation rounds run summed over the three sweeps, and 1 if the node
+ *             cap was exceeded.  The rounds lie in [3, 3 * nodes] (0 without nodes); their number depends on how the hardware
+ *             interleaves the waves, nothing else does.
+ *   node_ws   B * H * W uint16 node ids of workspace.  It need not be zeroed.
+ * One workgroup per (frame, class) keeps a compact list of at most dc_course_node_cap() nodes (8192; host only) in LDS.  A (frame,
+ * class) with more nodes is not measured: its status flag is 1, the rows of its events hold `nodes` and course_m = -1 with the other
+ * columns 0, and its course bytes are 0.  The other class of the same frame is computed normally.  H * 12 + 106 560 bytes of LDS must
+ * fit the 160 KiB of a CU; a taller grid is refused, as are null, misaligned or overlapping buffers and a wrap outside {0, 1}.
+ * Integer arithmetic only: equal inputs give equal rows and course bytes whatever the scheduling and however the frames were cut into
+ * batches.  Samples from n_valid on are neither read nor written.  Does not synchronise. */
+int dc_course_node_cap(void);
+int dc_skeleton_course(int B, int n_valid, int H, int W, const uint8_t* skeleton, const int32_t* labels, const void* ws, int cap, int wrap,
+                       const int32_t* link_table, int64_t* rows, uint8_t* course, int32_t* status, void* node_ws, void* stream);
 
 /* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
  * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in

@@ -1,6 +1,6 @@
 """The events of class masks, on the device: the catalogue of connected components (EventCatalog), two catalogues matched (EventMatcher),
 per-event statistics of the input fields (EventFields), shapes and a shape filter (EventShape, EventFilter), skeletons and
-axis lengths (EventAxis), events linked across time steps (EventTracker), the tracks' life cycles (TrackFields) and two sides' tracks
+axis lengths and main courses (EventAxis), events linked across time steps (EventTracker), the tracks' life cycles (TrackFields) and two sides' tracks
 matched (TrackMatcher)."""
 from __future__ import annotations
 
@@ -594,17 +594,25 @@ class EventFilter:
     min_axis_km is the criterion on the length ALONG the event's skeleton (EventAxis.decode's axis_km; pruned where the axis prunes): it
     needs `axis`, an EventAxis on the same catalogue, which the filter then calls on the raw mask behind the catalogue, and
     dc_event_select_axis between the two launches below.  Without it the filter launches exactly what it launches without the argument.
+    axis_measure = "course" puts the criterion on the MAIN COURSE instead (EventAxis.decode's course_km, the longest path through the
+    skeleton; the axis must have been built with course=True): a forked, short object no longer passes as a long one.  Events of a class
+    plane with too many skeleton pixels to be measured carry course_m = -1, so any positive criterion drops them.
     `catalog` is the filter's own catalogue of the RAW mask; whatever consumes the filtered mask (another EventCatalog, a matcher, a
     tracker, ...) does so unchanged.  Nothing is copied to the host and nothing synchronises."""
 
     def __init__(self, catalog: EventCatalog, min_pixels=(0, 0), min_area_km2=(0, 0), min_length_km=(0, 0), min_aspect=(0, 0),
-                 min_axis_km=(0, 0), axis: Optional["EventAxis"] = None):
+                 min_axis_km=(0, 0), axis: Optional["EventAxis"] = None, axis_measure: str = "total"):
         self.min_pixels, self.min_area_km2 = self._pair(min_pixels, "min_pixels"), self._pair(min_area_km2, "min_area_km2")
         self.min_length_km, self.min_aspect = self._pair(min_length_km, "min_length_km"), self._pair(min_aspect, "min_aspect")
         self.min_axis_km = self._pair(min_axis_km, "min_axis_km")
         self.min_axis_m = tuple(self.axis_units(v) for v in self.min_axis_km)
         check_axis("EventFilter", "min_axis_km", any(self.min_axis_m), axis, catalog)
         self.axis = axis if any(self.min_axis_m) else None
+        if axis_measure not in ("total", "course"):
+            raise L.DeepcamHipError(f'EventFilter: axis_measure must be "total" or "course", got {axis_measure!r}')
+        if axis_measure == "course" and self.axis is not None and not self.axis.course:
+            raise L.DeepcamHipError('EventFilter: axis_measure="course" needs an axis built with course=True')
+        self.axis_measure = axis_measure
         self.catalog = catalog
         self.shape = EventShape(catalog)
         dev = catalog._labels.device
@@ -692,6 +700,8 @@ class EventFilter:
                "min_aspect": list(self.min_aspect)}
         if self.axis is not None:
             out["min_axis_km"] = list(self.min_axis_km)
+            if self.axis_measure != "total":
+                out["axis_measure"] = self.axis_measure
         return out
 
     def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> torch.Tensor:
@@ -707,7 +717,8 @@ class EventFilter:
         L.call("dc_event_select", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(self.shape._shape), L.dptr(self._criteria),
                L.dptr(self._keep), L.dptr(self._counts), st)
         if self.axis is not None:
-            L.call("dc_event_select_axis", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(self.axis._rows),
+            L.call("dc_event_select_axis", cat.B, nv, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp),
+                   L.dptr(self.axis._course_rows if self.axis_measure == "course" else self.axis._rows),
                    self.min_axis_m[0], self.min_axis_m[1], L.dptr(self._keep), L.dptr(self._counts), st)
         L.call("dc_mask_select", cat.B, nv, cat.H, cat.W, L.dptr(mask), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap, L.dptr(self._keep),
                L.dptr(self._out), L.dptr(self._counts), st)
@@ -1038,6 +1049,8 @@ def great_circle_km(lat_a: float, lon_a: float, lat_b: float, lon_b: float) -> f
 
 EVENT_AXIS_FIELDS = ("skeleton_pixels", "endpoints", "junctions", "links_ew", "links_ns", "links_diag", "length_m")
 EVENT_AXIS_VALUES = ("skeleton_pixels", "endpoints", "junctions", "branches", "axis_km", "closed")
+EVENT_COURSE_FIELDS = ("nodes", "start", "start_ecc_m", "end_a", "end_b", "course_pixels", "course_m")
+EVENT_COURSE_VALUES = ("course_km", "course_pixels", "course_share", "sinuosity")
 
 
 def axis_link_table(height: int, width: int) -> np.ndarray:
@@ -1068,9 +1081,16 @@ class EventAxis:
     and both ends of the main course come back in full; a removed spur that touches the regrown chain within N pixels of an end can grow
     back in part).  A call then launches dc_mask_thin, dc_skeleton_stats on the thinned map (raw_table), dc_skeleton_prune, and
     dc_skeleton_stats on the pruned map: table, rows() and skeleton_buffer describe the PRUNED skeleton, raw_table, raw_rows() and
-    raw_skeleton_buffer the thinned one, removed() counts the pixels taken.  With prune = 0 nothing of this exists or runs."""
+    raw_skeleton_buffer the thinned one, removed() counts the pixels taken.  With prune = 0 nothing of this exists or runs.
+    course = True measures the MAIN COURSE of every event, the longest path through its skeleton (dc_skeleton_course behind the last
+    dc_skeleton_stats, on the pruned skeleton where the axis prunes; the header has the definition: a double sweep over the link graph,
+    exact where the skeleton is a tree, a lower bound -- about half the circumference of a closed ring -- where it has cycles).
+    course_table and course_rows() hold EVENT_COURSE_FIELDS per event, course_buffer the course pixels (uint8 [B, H, W]),
+    course_status() per (frame, class) the nodes, the relaxation rounds and 1 where the class plane has more than
+    dc_course_node_cap() = 8192 skeleton pixels: such a plane is not measured and its events carry course_m = -1.  Without
+    course = True nothing of this exists or runs."""
 
-    def __init__(self, catalog: EventCatalog, max_iters: Optional[int] = None, prune: int = 0):
+    def __init__(self, catalog: EventCatalog, max_iters: Optional[int] = None, prune: int = 0, course: bool = False):
         if L.load().dc_thin_lds_bytes(catalog.H, catalog.W) == 0:
             raise L.DeepcamHipError(f"EventAxis: the bit plane of {catalog.H} x {catalog.W} does not fit the LDS of one CU")
         self.max_iters = max(catalog.H, catalog.W) if max_iters is None else int(max_iters)
@@ -1089,6 +1109,16 @@ class EventAxis:
         if self.prune:
             self._raw_skel, self._raw_rows = torch.zeros_like(self._skel), torch.zeros_like(self._rows)
             self._removed = torch.zeros((catalog.B, 2), dtype=torch.int32, device=dev)
+        self.course = bool(course)
+        if self.course:
+            reach = min(L.load().dc_course_node_cap(), catalog.H * catalog.W) * int(self.link_table.max())
+            if reach >= 2 ** 32 - 1:
+                raise L.DeepcamHipError(f"EventAxis: course distances are uint32 metres, and {reach} m along the longest possible path of "
+                                        f"{catalog.H} x {catalog.W} does not fit")
+            self._course_rows = torch.zeros((catalog.B, catalog.cap, len(EVENT_COURSE_FIELDS)), dtype=torch.int64, device=dev)
+            self._course = torch.zeros_like(self._skel)
+            self._course_status = torch.zeros((catalog.B, 2, 3), dtype=torch.int32, device=dev)
+            self._node_ws = torch.empty((catalog.B, catalog.H, catalog.W), dtype=torch.int16, device=dev)
 
     def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "EventAxis":
         """mask: the contiguous device tensor [B, H, W] the catalogue was called with (uint8; int32 and int64 are read as they are).
@@ -1110,6 +1140,10 @@ class EventAxis:
             L.call("dc_skeleton_prune", cat.B, nv, cat.H, cat.W, L.dptr(thinned), int(cat.wrap), self.prune, L.dptr(self._skel),
                    L.dptr(self._removed), st)
         stats(self._skel, self._rows)
+        if self.course:
+            L.call("dc_skeleton_course", cat.B, nv, cat.H, cat.W, L.dptr(self._skel), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap,
+                   int(cat.wrap), L.dptr(self._link), L.dptr(self._course_rows), L.dptr(self._course), L.dptr(self._course_status),
+                   L.dptr(self._node_ws), st)
         self._last_valid = nv
         return self
 
@@ -1149,6 +1183,33 @@ class EventAxis:
         self._pruning("removed")
         return self._removed[:self._last_valid].cpu().numpy()
 
+    def _coursing(self, what: str) -> None:
+        if not self.course:
+            raise L.DeepcamHipError(f"EventAxis: {what} exists only with course=True")
+
+    @property
+    def course_table(self) -> torch.Tensor:
+        """int64 [n_valid, cap, 7], with course=True: EVENT_COURSE_FIELDS per event of the last call (a view); pixel indices are r * W + c"""
+        self._coursing("course_table")
+        return self._course_rows[:self._last_valid]
+
+    @property
+    def course_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W], with course=True: the whole buffer the courses are written to (k on a course pixel of class k)"""
+        self._coursing("course_buffer")
+        return self._course
+
+    def course_rows(self):
+        """rows() of the course table"""
+        self._coursing("course_rows")
+        return _filled_rows(self._course_rows, self.catalog._fill(self._last_valid)) if self._last_valid else []
+
+    def course_status(self) -> np.ndarray:
+        """int32 numpy [n_valid, 2, 3], with course=True: per sample and class the nodes, the relaxation rounds of the three sweeps together
+        and 1 where the plane has more nodes than dc_course_node_cap() and was not measured, else 0"""
+        self._coursing("course_status")
+        return self._course_status[:self._last_valid].cpu().numpy()
+
     def iterations(self) -> np.ndarray:
         """int32 numpy [n_valid, 2, 2]: per sample and class the passes run (the final empty one counted) and 1 / 0 for converged"""
         return self._iters[:self._last_valid].cpu().numpy()
@@ -1164,7 +1225,8 @@ class EventAxis:
         """Per valid sample of the last call a list of dicts (decode), one per row of the catalogue."""
         _, rows = self.catalog.rows()
         raw = self.raw_rows() if self.prune else [None] * len(rows)
-        return [self.decode(a, r, self.catalog.H, self.catalog.W, w) for a, r, w in zip(self.rows(), rows, raw)]
+        course = self.course_rows() if self.course else [None] * len(rows)
+        return [self.decode(a, r, self.catalog.H, self.catalog.W, w, c) for a, r, w, c in zip(self.rows(), rows, raw, course)]
 
     @staticmethod
     def values(axis_rows) -> np.ndarray:
@@ -1178,18 +1240,40 @@ class EventAxis:
         return out
 
     @staticmethod
-    def decode(axis_rows, rows, height: int, width: int, raw_axis_rows=None):
+    def course_values(course_rows, axis_rows, height: int, width: int) -> np.ndarray:
+        """float64 [n, 4] (EVENT_COURSE_VALUES): decode's course numbers for whole arrays at once, NaN where decode gives None (what
+        predict.py stores as event_course_values)"""
+        events = np.zeros((len(course_rows), len(EVENT_FIELDS)), np.int64)
+        dicts = EventAxis.decode(axis_rows, events, height, width, course_rows=course_rows)
+        return np.array([[np.nan if d[k] is None else d[k] for k in EVENT_COURSE_VALUES] for d in dicts], np.float64).reshape(-1, 4)
+
+    @staticmethod
+    def decode(axis_rows, rows, height: int, width: int, raw_axis_rows=None, course_rows=None):
         """Axis rows [n, 7] (EVENT_AXIS_FIELDS) and the events' own rows [n, 10] (EVENT_FIELDS) -> one dict per event: class,
         skeleton_pixels, endpoints, junctions, branches = max(endpoints - 2, 0), axis_km = length_m / 1000, closed = (endpoints == 0 and
         skeleton_pixels > 1).  axis_km is the TOTAL length of the skeleton with its branches (the links of axis_link_table(height, width)
-        summed), not the longest path through it: a spur adds its length -- unless the rows are those of a pruned skeleton.  With
-        raw_axis_rows, the rows of the thinned skeleton before pruning, every dict gains axis_km_unpruned and spur_km, their difference."""
+        summed), not the longest path through it (course_km below is): a spur adds its length -- unless the rows are those of a pruned skeleton.  With
+        raw_axis_rows, the rows of the thinned skeleton before pruning, every dict gains axis_km_unpruned and spur_km, their difference.
+        With course_rows [n, 7] (EVENT_COURSE_FIELDS) it gains the main course: course_km = course_m / 1000 (None where course_m < 0: the
+        class plane had too many nodes to be measured), course_ends, the (lat, lon) of end_a and end_b in degrees, course_pixels,
+        course_share = course_km / axis_km (None where either is missing or zero) and sinuosity = course_km over the great-circle
+        distance of the ends (None where they coincide)."""
         rows = np.asarray(rows, np.int64).reshape(-1, len(EVENT_FIELDS))
         out = [{"class": int(r[1]), "skeleton_pixels": int(v[0]), "endpoints": int(v[1]), "junctions": int(v[2]), "branches": int(v[3]),
                 "axis_km": float(v[4]), "closed": bool(v[5])} for v, r in zip(EventAxis.values(axis_rows), rows)]
         if raw_axis_rows is not None:
             for d, w in zip(out, EventAxis.values(raw_axis_rows)):
                 d["axis_km_unpruned"], d["spur_km"] = float(w[4]), float(w[4]) - d["axis_km"]
+        if course_rows is not None:
+            lat, lon = np.linspace(-90.0, 90.0, height), np.linspace(-180.0, 180.0, width)
+            for d, c in zip(out, np.asarray(course_rows, np.int64).reshape(-1, len(EVENT_COURSE_FIELDS)).tolist()):
+                measured = c[6] >= 0
+                ends = tuple((float(lat[p // width]), float(lon[p % width])) for p in (c[3], c[4]))
+                km = c[6] / 1000.0 if measured else None
+                gap = great_circle_km(*ends[0], *ends[1])
+                d["course_km"], d["course_ends"], d["course_pixels"] = km, ends, int(c[5])
+                d["course_share"] = _ratio(km, d["axis_km"]) if measured else None
+                d["sinuosity"] = _ratio(km, gap) if measured and c[3] != c[4] else None
         return out
 
 

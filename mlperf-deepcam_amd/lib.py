@@ -176,6 +176,8 @@ _SIGS = {
     "dc_skeleton_stats": (I, [I, I, I, I, P, P, P, I, I, P, P, P]),
     "dc_skeleton_prune": (I, [I, I, I, I, P, I, I, P, P, P]),
     "dc_event_select_axis": (I, [I, I, I, P, P, P, L, L, P, P, P]),
+    "dc_course_node_cap": (I, []),
+    "dc_skeleton_course": (I, [I, I, I, I, P, P, P, I, I, P, P, P, P, P, P]),
     "dc_track_workspace": (SZ, [I]),
     "dc_track_append": (I, [I, I, I, P, P, L, I, P, P, P, P, P]),
     "dc_track_link": (I, [I, I, I, P, P, P, P, P, P, P, P, I, I, L, P, P, P]),

@@ -29,7 +29,7 @@ from . import ops as _ops
 from .engine import Engine
 # the re-exports: every name is defined once, in its topic module
 from ._args import _BYTES, _c_int, _float, _n_valid, _ratio, _two_words  # noqa: F401
-from .events import (EARTH_RADIUS_KM, EVENT_AXIS_FIELDS, EVENT_AXIS_VALUES, EVENT_FIELD_STATS, EVENT_FIELDS,  # noqa: F401
+from .events import (EARTH_RADIUS_KM, EVENT_AXIS_FIELDS, EVENT_AXIS_VALUES, EVENT_COURSE_FIELDS, EVENT_COURSE_VALUES, EVENT_FIELD_STATS, EVENT_FIELDS,  # noqa: F401
                      EVENT_FILTER_COUNTS, EVENT_SCALE, EVENT_SHAPE_FIELDS, EVENT_SHAPE_VALUES, TRACK_COVER_FIELDS, TRACK_FIELD_STATS, TRACK_FIELDS, TRACK_PAIR_FIELDS, TRACK_STEP_FIELDS,
                      TRACK_STORE_FIELDS, EventAxis, EventCatalog, EventFields, EventFilter, EventMatcher, EventShape, EventTracker, TrackFields,
                      TrackMatcher, _filled_rows, axis_link_table, event_field_bits, event_field_key, event_field_value, event_shape_tables,

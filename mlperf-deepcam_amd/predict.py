@@ -72,6 +72,13 @@ branches, axis_km, closed); summary.json gains ``event_axis``: per class the eve
 whose thinning stopped at max_iters.  axis_km is the skeleton's total length with its branches, not its longest path.
 --event_axis_prune N removes the skeleton's spurs of at most N pixels first (nn.EventAxis(prune=N)): ``prediction_axis`` and the rows are
 then those of the PRUNED skeleton, and the summary's ``event_axis`` gains ``prune`` and ``removed_pixels`` (per class).
+--event_course (implies --event_axis) measures the main course of every event, the longest path through its skeleton
+(nn.EventAxis(course=True), on the pruned skeleton with --event_axis_prune): every output file gains ``prediction_course`` (uint8 [H, W]: k
+on a course pixel of class k), ``event_course`` (int64 [n, 7]: nodes, start, start_ecc_m, end_a, end_b, course_pixels, course_m; pixel
+indices are row * W + column) and ``event_course_values`` (float64 [n, 4]: course_km, course_pixels, course_share, sinuosity; NaN where
+undefined); summary.json gains ``event_course``: per class the measured events and their mean course_km, and the frames in which a class
+plane had more skeleton pixels than the kernel's node list holds (their events carry course_m = -1).
+--filter_axis_measure course puts --filter_min_axis_km on the main course instead of the skeleton's total length.
 --filter_min_axis_km TC AR (with --event_filter; implies --event_axis) adds the length along the skeleton, pruned as --event_axis_prune
 says, to the filter's criteria: the filter measures the events of the UNFILTERED mask with an axis of its own before it selects.
 With --event_filter nn.EventFilter drops, on the device, the events of the classifier's mask that miss the --filter_min_pixels,
@@ -232,6 +239,11 @@ def build_parser():
     AP.add_argument("--event_axis", action=_implies("event_axis", "events", default=argparse.SUPPRESS),
                     help="per event its skeleton and the length along it (implies --events): datasets 'prediction_axis', 'event_axis', "
                     "'event_axis_values'; 'event_axis' in the summary")
+    AP.add_argument("--event_course", action=_implies("event_course", "event_axis", "events", default=argparse.SUPPRESS),
+                    help="per event its main course, the longest path through the skeleton (implies --event_axis): datasets "
+                    "'prediction_course', 'event_course', 'event_course_values'; 'event_course' in the summary")
+    AP.add_argument("--filter_axis_measure", choices=("total", "course"), default=argparse.SUPPRESS, help="with --filter_min_axis_km: the "
+                    "skeleton's total length (default) or its main course")
     AP.add_argument("--event_axis_prune", type=int, default=argparse.SUPPRESS, metavar="N", help="with --event_axis: remove the skeleton's "
                     "spurs of at most N pixels before it is measured (1 .. 1024); 'prune' and 'removed_pixels' in the summary's 'event_axis'")
     AP.add_argument("--filter_min_axis_km", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("TC", "AR"), help="with --event_filter "
@@ -780,7 +792,11 @@ def plot_name(base: str) -> str:
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=(),
-                 ensemble: bool = False, event_axis: bool = False):
+                 ensemble: bool = False, event_axis: bool = False, event_course: bool = False):
+        # --event_course: the course pixels, the rows and the status of nn.EventAxis(course=True)
+        self.acourse = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if event_course else None
+        self.crows = torch.empty((B, event_cap, len(dnn.EVENT_COURSE_FIELDS)), dtype=torch.int64).pin_memory() if event_course else None
+        self.cstatus = torch.empty((B, 2, 3), dtype=torch.int32).pin_memory() if event_course else None
         # --event_axis: the skeleton, the pass counts and the rows of nn.EventAxis (cap rows of 56 bytes per sample)
         self.askel = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if event_axis else None
         self.aiters = torch.empty((B, 2, 2), dtype=torch.int32).pin_memory() if event_axis else None
@@ -838,7 +854,9 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                     if slot.events is not None:
                         total = int(slot.ncomp[j, 0])
                         rows = slot.events[j, :min(total, slot.events.shape[1])].numpy()
-                        frows = srows = arows = None
+                        frows = srows = arows = crows = None
+                        if slot.crows is not None:
+                            crows = np.ascontiguousarray(slot.crows[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.axis is not None:
                             arows = np.ascontiguousarray(slot.axis[j, :len(rows)].numpy()[rows[:, 2] >= min_event_pixels])
                         if slot.fields is not None:          # the filter of `events`, whichever branch below applies it
@@ -863,6 +881,10 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         if arows is not None:
                             extra = dict(extra or {}, prediction_axis=slot.askel[j].numpy(), event_axis=arows,
                                          event_axis_values=dnn.EventAxis.values(arows))
+                        if crows is not None:
+                            H, W = slot.mask.shape[1:]
+                            extra = dict(extra, prediction_course=slot.acourse[j].numpy(), event_course=crows,
+                                         event_course_values=dnn.EventAxis.course_values(crows, arows, H, W))
                     if slot.emask is not None:
                         extra = dict(extra or {}, prediction_ensemble=slot.emask[j].numpy(), ensemble_rows=slot.erows[j].numpy())
                         if slot.econf is not None:
@@ -898,6 +920,10 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         km = [extra["event_axis"][rows[:, 1] == k, 6] / 1000.0 for k in (1, 2)]
                         rec["event_axis"] = {"classes": [[len(v), float(v.sum()), float(v.max()) if len(v) else 0.0] for v in km],
                                              "stopped": bool((slot.aiters[j, :, 1] == 0).any())}
+                    if extra is not None and "event_course" in extra:    # per class: measured events, sum of course_km; a plane over the cap
+                        km = [extra["event_course"][rows[:, 1] == k, 6] / 1000.0 for k in (1, 2)]
+                        rec["event_course"] = {"classes": [[int((v >= 0).sum()), float(v[v >= 0].sum())] for v in km],
+                                               "overflowed": bool(slot.cstatus[j, :, 2].any())}
                     if extra is not None and "event_fields" in extra:
                         rec["event_field_counts"] = [int(extra["event_fields"][..., 4].sum()), int(extra["event_fields"][..., 5].sum())]
                     if extra is not None and "event_scores" in extra:
@@ -940,6 +966,8 @@ def main(pargs) -> dict:
     filter_min_axis = [float(v) for v in getattr(pargs, "filter_min_axis_km", (0.0, 0.0))]
     if any(filter_min_axis):                      # implies --event_axis, which implies --events
         pargs.event_axis = pargs.events = True
+    axis_course = bool(getattr(pargs, "event_course", False))
+    filter_measure = getattr(pargs, "filter_axis_measure", "total")
     events = bool(pargs.events) or verify or bool(getattr(pargs, "tracks", False))
     # --decision_*: the rule takes the stored logits; everything below, the filter included, takes the decided mask
     decision = decision_options(pargs)
@@ -952,7 +980,8 @@ def main(pargs) -> dict:
         fcat = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
         efilter = dnn.EventFilter(fcat, min_pixels=pargs.filter_min_pixels, min_area_km2=pargs.filter_min_area_km2,
                                   min_length_km=pargs.filter_min_length_km, min_aspect=pargs.filter_min_aspect, min_axis_km=filter_min_axis,
-                                  axis=dnn.EventAxis(fcat, prune=axis_prune) if any(filter_min_axis) else None)
+                                  axis=dnn.EventAxis(fcat, prune=axis_prune, course=filter_measure == "course") if any(filter_min_axis) else None,
+                                  axis_measure=filter_measure)
     # --ensemble_*: the views of every batch pooled into one logits tensor, which then stands where the classifier's stood
     ens_options = ensemble_options(pargs, W, pargs.channels)
     ens = ens_view = ens_sign = None
@@ -977,7 +1006,7 @@ def main(pargs) -> dict:
     own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
-    eaxis = dnn.EventAxis(catalog, prune=axis_prune) if getattr(pargs, "event_axis", False) else None
+    eaxis = dnn.EventAxis(catalog, prune=axis_prune, course=axis_course) if getattr(pargs, "event_axis", False) else None
     axis_removed = torch.zeros(2, dtype=torch.int64, device=device) if eaxis is not None and axis_prune else None
     # --event_fields: every file channel, in physical units, as the input pipeline holds the batch on the device before normalisation
     efields = field_bits = None
@@ -1050,7 +1079,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, decide is not None,
-                             frame_skills, ens is not None, eaxis is not None))
+                             frame_skills, ens is not None, eaxis is not None, eaxis is not None and axis_course))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -1110,6 +1139,10 @@ def main(pargs) -> dict:
                 slot.axis[:nv].copy_(eaxis.table, non_blocking=True)
                 if axis_removed is not None:
                     axis_removed += eaxis._removed[:nv].sum(dim=0)
+                if axis_course:
+                    slot.acourse[:nv].copy_(eaxis.course_buffer[:nv], non_blocking=True)
+                    slot.crows[:nv].copy_(eaxis.course_table, non_blocking=True)
+                    slot.cstatus[:nv].copy_(eaxis._course_status[:nv], non_blocking=True)
             if tracker is not None:
                 tracker(dmask, n_valid=nv)
             if tmatch is not None:
@@ -1190,6 +1223,11 @@ def main(pargs) -> dict:
                                  "frames_at_max_iters": sum(1 for r in records if r["event_axis"]["stopped"])}
         if axis_removed is not None:
             summary["event_axis"].update(prune=axis_prune, removed_pixels=[int(v) for v in axis_removed.tolist()])
+    if eaxis is not None and axis_course:
+        per = [[r["event_course"]["classes"][k] for r in records] for k in range(2)]
+        count = [sum(c[0] for c in cl) for cl in per]
+        summary["event_course"] = {"events": count, "mean_course_km": [sum(c[1] for c in cl) / n if n else None for cl, n in zip(per, count)],
+                                   "frames_over_node_cap": sum(1 for r in records if r["event_course"]["overflowed"])}
     if efields is not None:
         summary["event_fields"] = {"channels": efields.C, "scale_bits": [int(v) for v in field_bits],
                                    "nonfinite": sum(r["event_field_counts"][0] for r in records),

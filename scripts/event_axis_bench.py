@@ -9,6 +9,9 @@
                         and frame; dc_mask_thin above, unchanged code, is its yardstick), the pixels it removes, and what it does to the
                         events' mean axis_km and their branches
   dc_event_select_axis (the filter's axis criterion on the catalogue's rows)
+  dc_skeleton_course   (nn.EventAxis(course=True): the main course of every event on the thinned map, one workgroup per class and frame;
+                        dc_mask_thin is its yardstick too), the nodes per frame, the relaxation rounds per sweep, the class planes over the
+                        node cap, and the events' mean course_km beside their mean axis_km
 
 on the masks of scripts/events_bench.py: 8 blobs per sample (about 97 % background), 40 blobs per sample and 45 % uniform-random
 foreground; the background share of each is printed.  Every call
@@ -128,6 +131,23 @@ def main():
         sel = lambda: L.call("dc_event_select_axis", B, B, cat.cap, L.dptr(cat._table), L.dptr(cat._ncomp), L.dptr(axis._rows), 0,  # noqa: E731
                              2000000, L.dptr(keep), L.dptr(counts), st)
         print(f"    dc_skeleton_stats (pruned map, spur 32) {med(stats_pruned):8.3f} ms/batch; dc_event_select_axis {med(sel):8.3f} ms/batch")
+        # the main course on the thinned map `ref`
+        co = dnn.EventAxis(cat, course=True)
+        course = lambda: L.call("dc_skeleton_course", B, B, H, W, L.dptr(ref), L.dptr(cat._labels), L.dptr(cat._ws), cat.cap,  # noqa: E731
+                                int(cat.wrap), L.dptr(co._link), L.dptr(co._course_rows), L.dptr(co._course), L.dptr(co._course_status),
+                                L.dptr(co._node_ws), st)
+        tc = med(course)
+        torch.cuda.synchronize()
+        status = co._course_status.cpu().numpy()
+        swept = status[:, :, 2] == 0
+        rows = np.concatenate([r for r in dnn._filled_rows(co._course_rows, cat._fill(B))])
+        has = rows[:, 6] > 0
+        km, axis_km = rows[has, 6] / 1000.0, np.concatenate([v[:, 4] for v in before])[has]
+        print(f"    dc_skeleton_course {tc:8.3f} ms/batch = {100 * tc / t['dc_mask_thin']:6.1f} % of dc_mask_thin; nodes per frame (both "
+              f"classes) {status[:, :, 0].sum(axis=1).tolist()}; class planes over the node cap {int((~swept).sum())} of {2 * B}; rounds "
+              f"per sweep, mean over the swept planes {float(status[:, :, 1][swept].mean()) / 3 if swept.any() else 0:.0f}, largest "
+              f"{int(status[:, :, 1][swept].max()) // 3 if swept.any() else 0}; events with a course {len(km)}, mean course_km "
+              f"{float(km.mean()) if len(km) else 0:.1f} of their mean axis_km {float(axis_km.mean()) if len(km) else 0:.1f}")
 
 
 if __name__ == "__main__":
