@@ -81,6 +81,8 @@ int dc_reset_options(void);
  *     skel_stats (both launches of the statistics call: the rows zeroed, the pixel pass)
  *   spur pruning and the axis criterion (dc_skeleton_prune, dc_event_select_axis): skel_prune (the launch of either call)
  *   main course (dc_skeleton_course): skel_course (both launches: the rows zeroed, one workgroup per class and frame for the three sweeps)
+ *   mask morphology (dc_mask_morph): morph_planes (one workgroup per class and frame runs the class's program on the bit plane in LDS),
+ *     morph_compose (the output mask and the counters, one streaming pass)
  *   event tracks (dc_track_append, dc_track_link, dc_track_resolve): cc_tracks (every launch of the three calls)
  *   storm life cycles (dc_track_fields_append, dc_track_cycles): cc_track_fields (every launch of both calls)
  *   track verification (dc_track_match_append, dc_track_match_resolve): cc_track_match (every launch of both calls)
@@ -933,6 +935,62 @@ int dc_event_select_axis(int B, int n_valid, int cap, const int64_t* table, cons
 int dc_course_node_cap(void);
 int dc_skeleton_course(int B, int n_valid, int H, int W, const uint8_t* skeleton, const int32_t* labels, const void* ws, int cap, int wrap,
                        const int32_t* link_table, int64_t* rows, uint8_t* course, int32_t* status, void* node_ws, void* stream);
+
+/* Mask morphology (nn.MaskMorphology; predict.py --morph_close / --morph_fill / --morph_open): the operators that change the SHAPE of an
+ * event before it is catalogued, thinned, filtered or tracked -- close a gap, fill a hole, open a neck, drop a speck.
+ *
+ * For each valid sample and each class k in {1, 2}, the plane is X = (mask == k) (mask: [B][H][W] of 1-, 4- or 8-byte integers,
+ * mask_bytes, as dc_mask_thin takes it).  Each plane runs its own program of at most 8 steps, independently of the other class.
+ * Columns are periodic under `wrap`.
+ *
+ * DILATE r (1 <= r <= 31).  This is r elementary steps, numbered j = 1..r.
+ *   - Odd j: X <- X u N4-shifts(X).
+ *   - Even j: X <- X u N8-shifts(X).  Together these approximate a disc by an octagon.
+ *   - Rows outside the frame are background.  Without `wrap`, columns outside the frame are background too.
+ * ERODE r (1 <= r <= 31).  This is the dual of DILATE, with the same j order: X <- X n (all shifts of X).
+ *   - Rows outside the frame count as FOREGROUND.  Without `wrap`, columns outside the frame count as foreground too.
+ *   - With this padding a closing (DILATE r, ERODE r) never removes a pixel.
+ *   - With this padding an opening (ERODE r, DILATE r) never adds a pixel.
+ * FILL.  Let C = ~X inside the frame.
+ *   - The marker is the pixels of C on row 0 and on row H - 1.  Without `wrap`, it also includes the pixels of C on column 0 and
+ *     column W - 1.
+ *   - R is everything of C that is 4-connected to the marker inside C.
+ *   - X <- X u (C \ R).  A hole is background that cannot reach a pole without crossing the event.
+ * RECONSTRUCT.  X <- everything of the ORIGINAL plane (mask == k) that is 8-connected, inside that plane, to X n original.
+ *   - ERODE r followed by RECONSTRUCT is the opening by reconstruction.  It drops events that are nowhere wider than the octagon and
+ *     leaves every other event bit for bit.
+ * An empty program is the identity.
+ *
+ * Program word.  A program travels as one 64-bit word per class.  Step i is byte i, with op << 5 | r:
+ *   op 0  end           (the byte is zero, and so is every byte after it)
+ *   op 1  DILATE        r in 1..31
+ *   op 2  ERODE         r in 1..31
+ *   op 3  FILL          r = 0
+ *   op 4  RECONSTRUCT   r = 0
+ * The call refuses, with a message: bytes after an end byte that are not zero, an r outside its range, op 5 to 7.
+ *
+ * Composition.  One output mask uint8 [B][H][W] is written.  It may not overlap the input.  c is the input value of the pixel; X1' and
+ * X2' are the final planes.
+ *   - c >= 3: copied verbatim (of a 4- or 8-byte mask the values 3 .. 255; any other value counts as background).
+ *   - c == k and Xk' holds the pixel: the output is k.
+ *   - Otherwise the output is 1 if X1' holds the pixel, else 2 if X2' holds it, else 0.
+ *       A kept cyclone inside a river's filled hole stays a cyclone.
+ *       A background pixel that both planes claim goes to class 1.
+ *
+ *   counts     int64 [B][2][4], zeroed by the call for the samples below n_valid: per frame and class pixels_in, pixels_out, added (the
+ *              output is k and the input was not k) and removed (the input was k and the output is not k)
+ *   rounds     int32 [B][2][8]: the propagation rounds each FILL or RECONSTRUCT step ran (the last, empty one counted), 0 for other
+ *              steps.  The relaxation is chaotic: its result does not depend on scheduling, the NUMBER of rounds it took may.
+ *   converged  int32 [B][2]: 1 or 0 for "every propagation converged" (a propagation is cut off after H * W rounds, which no real flood
+ *              needs: every round but the last adds a pixel)
+ *   planes     workspace, 8-byte aligned, B * 2 * H * ceil(W / 64) * 8 bytes: the final planes as words, uint64 [B][2][H][ceil(W / 64)]
+ * One workgroup per class and frame keeps the bit plane in the LDS of one CU: a grid whose plane does not fit is refused, exactly as
+ * dc_mask_thin refuses it (dc_thin_lds_bytes).  The radii are grid pixels, not kilometres; the structuring element is an octagon, not a
+ * disc.  Samples from n_valid on are neither read nor written.  The call does not synchronise.  Masks, counts and `converged` are
+ * integers and do not depend on scheduling. */
+int dc_mask_morph(int B, int n_valid, int H, int W, const void* mask, int mask_bytes, int wrap, unsigned long long program_1,
+                  unsigned long long program_2, uint8_t* out_mask, int64_t* counts, int32_t* rounds, int32_t* converged, void* planes,
+                  void* stream);
 
 /* Event tracks (nn.EventTracker; predict.py --tracks): the events of a TIME SERIES of frames linked into tracks on the device -- how long
  * a cyclone or a river lived, where it went, when it peaked.  The catalogue above treats a frame in isolation; here the state lives in

@@ -1468,3 +1468,121 @@ class TrackMatcher:
         """summarize() of the frames filed so far"""
         rows = self.rows()
         return self.summarize(rows, self.decode(rows["pairs"], *self._decoded_tracks(), min_frames=1), self.min_frames, self.cover_q)
+
+
+MORPH_COUNTS = ("pixels_in", "pixels_out", "added", "removed")
+MORPH_OPS = {"dilate": 1, "erode": 2, "fill": 3, "reconstruct": 4}
+MORPH_STEPS = 8
+
+
+def morph_program(steps) -> int:
+    """The 64-bit program word dc_mask_morph takes for one class: step i is byte i, op << 5 | r (include/deepcam_hip.h).  A step is
+    ("dilate", r), ("erode", r), ("fill",) or ("reconstruct",); a step may also be given as its (op, r) numbers.  Refuses what the C call
+    refuses, with its wording."""
+    steps = list(steps)
+    if len(steps) > MORPH_STEPS:
+        raise L.DeepcamHipError(f"morph program: {len(steps)} steps, a program holds at most {MORPH_STEPS}")
+    word = 0
+    for i, step in enumerate(steps):
+        step = (step,) if isinstance(step, str) else tuple(step)
+        if not step or (isinstance(step[0], str) and step[0] not in MORPH_OPS):
+            raise L.DeepcamHipError(f"morph program: step {i}: {step!r} is not one of {sorted(MORPH_OPS)}")
+        op = MORPH_OPS[step[0]] if isinstance(step[0], str) else int(step[0])
+        r = int(step[1]) if len(step) > 1 else 0
+        if not 1 <= op <= 4:
+            raise L.DeepcamHipError(f"morph program: step {i}: op {op} is not defined (1 DILATE, 2 ERODE, 3 FILL, 4 RECONSTRUCT)")
+        if op <= 2 and not 1 <= r <= 31:
+            raise L.DeepcamHipError(f"morph program: step {i}: a radius must lie in [1, 31], got {r}")
+        if op >= 3 and r != 0:
+            raise L.DeepcamHipError(f"morph program: step {i}: FILL and RECONSTRUCT take r = 0, got {r}")
+        word |= (op << 5 | r) << (8 * i)
+    return word
+
+
+def morph_steps(word: int):
+    """morph_program's inverse: the steps of a well-formed program word"""
+    names = {v: k for k, v in MORPH_OPS.items()}
+    out = []
+    for i in range(MORPH_STEPS):
+        code = (int(word) >> (8 * i)) & 0xFF
+        if code == 0:
+            break
+        out.append((names[code >> 5], code & 31) if code >> 5 <= 2 else (names[code >> 5],))
+    return out
+
+
+class MaskMorphology:
+    """Morphological cleaning of class masks on the device (dc_mask_morph, csrc/morph.hip): each class plane runs a program of at most
+    eight steps -- ("dilate", r), ("erode", r), ("fill",), ("reconstruct",); include/deepcam_hip.h has every operator word for word --
+    and one output mask is composed from the two final planes.  closing(r) joins pieces that a gap of at most 2 r pixels separates,
+    ("fill",) fills the holes (background that cannot reach a polar row without crossing the event), opening(r) removes what is nowhere
+    wider than the octagon of radius r, necks included, and opening_by_reconstruction(r) removes the same events whole and leaves every
+    other event bit for bit.  `steps` is one sequence for both classes or a pair (class 1's, class 2's).  Radii are grid pixels, not
+    kilometres: at 768 x 1152 a pixel is 26 km tall and up to 35 km wide, and the octagon approximates a disc on the grid, not on the
+    sphere.  One workgroup runs one class plane of one frame inside the LDS of a CU, so the plane must fit there (768 x 1152 does; the
+    constructor raises where not).  The object owns the output mask (uint8 [B, H, W]), the counts (int64 [B, 2, 4], MORPH_COUNTS), the
+    rounds (int32 [B, 2, 8]), the convergence flags (int32 [B, 2]) and the word planes.  A call launches twice on the current stream and
+    does not synchronise; whatever consumes a mask (EventCatalog, EventAxis, EventFilter, ...) takes mask_buffer unchanged."""
+
+    def __init__(self, batch: int, height: int, width: int, steps, wrap: bool = True, device=None):
+        if batch < 1 or height < 1 or width < 1:
+            raise L.DeepcamHipError("MaskMorphology: batch, height and width must be positive")
+        if L.load().dc_thin_lds_bytes(height, width) == 0:
+            raise L.DeepcamHipError(f"MaskMorphology: the bit plane of {height} x {width} does not fit the LDS of one CU")
+        steps = list(steps)
+        pair = len(steps) == 2 and all(isinstance(s, (list, tuple)) and (len(s) == 0 or isinstance(s[0], (list, tuple))) for s in steps)
+        self.steps = tuple(tuple(tuple(x) for x in s) for s in (steps if pair else (steps, steps)))
+        self.programs = tuple(morph_program(s) for s in self.steps)
+        self.B, self.H, self.W, self.wrap = batch, height, width, bool(wrap)
+        dev = device_of(device)
+        self._dev = dev
+        self._out = torch.zeros((batch, height, width), dtype=torch.uint8, device=dev)
+        self._counts = torch.zeros((batch, 2, len(MORPH_COUNTS)), dtype=torch.int64, device=dev)
+        self._rounds = torch.zeros((batch, 2, MORPH_STEPS), dtype=torch.int32, device=dev)
+        self._converged = torch.zeros((batch, 2), dtype=torch.int32, device=dev)
+        self._planes = torch.zeros((batch, 2, height, (width + 63) // 64), dtype=torch.int64, device=dev)
+        self._last_valid = 0
+
+    @staticmethod
+    def closing(r: int):
+        return [("dilate", int(r)), ("erode", int(r))]
+
+    @staticmethod
+    def opening(r: int):
+        return [("erode", int(r)), ("dilate", int(r))]
+
+    @staticmethod
+    def opening_by_reconstruction(r: int):
+        return [("erode", int(r)), ("reconstruct",)]
+
+    def __call__(self, mask: torch.Tensor, n_valid: Optional[int] = None) -> "MaskMorphology":
+        """mask: a contiguous device tensor [B, H, W], uint8, int32 or int64.  Samples from n_valid on are padding: neither read nor
+        written."""
+        check_tensor("MaskMorphology", "mask", mask, (torch.uint8, torch.int32, torch.int64), (self.B, self.H, self.W), self._dev,
+                     "uint8, int32 or int64")
+        nv = self.B if n_valid is None else int(n_valid)
+        signed = lambda w: w - (1 << 64) if w >= 1 << 63 else w  # noqa: E731  (the word travels as a signed 64-bit argument)
+        L.call("dc_mask_morph", self.B, nv, self.H, self.W, L.dptr(mask), mask.element_size(), int(self.wrap), signed(self.programs[0]),
+               signed(self.programs[1]), L.dptr(self._out), L.dptr(self._counts), L.dptr(self._rounds), L.dptr(self._converged),
+               L.dptr(self._planes), L.stream_ptr())
+        self._last_valid = nv
+        return self
+
+    @property
+    def mask_buffer(self) -> torch.Tensor:
+        """uint8 [B, H, W]: the whole buffer the cleaned masks are written to, padding samples included"""
+        return self._out
+
+    def counts(self):
+        """Per valid sample of the last call a list of two dicts (class 1, class 2) with the keys MORPH_COUNTS"""
+        host = self._counts[:self._last_valid].cpu().tolist()
+        return [[dict(zip(MORPH_COUNTS, row)) for row in frame] for frame in host]
+
+    def rounds(self) -> np.ndarray:
+        """int32 numpy [n_valid, 2, 8]: per sample, class and step the propagation rounds a FILL or RECONSTRUCT ran (the last, empty one
+        counted; a diagnostic: the number may vary from run to run, the result does not), 0 for other steps"""
+        return self._rounds[:self._last_valid].cpu().numpy()
+
+    def converged(self) -> np.ndarray:
+        """int32 numpy [n_valid, 2]: 1 where every propagation of the class's program converged"""
+        return self._converged[:self._last_valid].cpu().numpy()

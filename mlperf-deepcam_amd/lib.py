@@ -178,6 +178,7 @@ _SIGS = {
     "dc_event_select_axis": (I, [I, I, I, P, P, P, L, L, P, P, P]),
     "dc_course_node_cap": (I, []),
     "dc_skeleton_course": (I, [I, I, I, I, P, P, P, I, I, P, P, P, P, P, P]),
+    "dc_mask_morph": (I, [I, I, I, I, P, I, I, L, L, P, P, P, P, P, P]),
     "dc_track_workspace": (SZ, [I]),
     "dc_track_append": (I, [I, I, I, P, P, L, I, P, P, P, P, P]),
     "dc_track_link": (I, [I, I, I, P, P, P, P, P, P, P, P, I, I, L, P, P, P]),

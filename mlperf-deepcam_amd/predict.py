@@ -81,6 +81,11 @@ plane had more skeleton pixels than the kernel's node list holds (their events c
 --filter_axis_measure course puts --filter_min_axis_km on the main course instead of the skeleton's total length.
 --filter_min_axis_km TC AR (with --event_filter; implies --event_axis) adds the length along the skeleton, pruned as --event_axis_prune
 says, to the filter's criteria: the filter measures the events of the UNFILTERED mask with an axis of its own before it selects.
+With --morph_close TC AR, --morph_fill and --morph_open TC AR (radii in grid pixels, 0: not for this class; --morph_open_reconstruct makes
+the opening one by reconstruction) nn.MaskMorphology closes, fills and opens the class planes of the mask on the device, in that order,
+and everything downstream -- --event_filter first -- takes the cleaned mask.  ``prediction`` stays the classifier's mask; every output
+file gains ``prediction_morph`` (uint8 [H, W]) and ``morph_counts`` (int64 [2, 4], nn.MORPH_COUNTS), ``summary.json`` gains
+``morphology``.  The labels under --verify are not touched.  Without these flags nothing of it is built or launched.
 With --event_filter nn.EventFilter drops, on the device, the events of the classifier's mask that miss the --filter_min_pixels,
 --filter_min_area_km2, --filter_min_length_km or --filter_min_aspect of their class (two values each: class 1, class 2; 0: off).
 ``prediction`` stays the classifier's mask, ``prediction_filtered`` is added, and EVERYTHING downstream takes the filtered mask: the
@@ -248,6 +253,16 @@ def build_parser():
                     "spurs of at most N pixels before it is measured (1 .. 1024); 'prune' and 'removed_pixels' in the summary's 'event_axis'")
     AP.add_argument("--filter_min_axis_km", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("TC", "AR"), help="with --event_filter "
                     "(implies --event_axis): drop events whose skeleton is shorter than this, measured on the unfiltered mask")
+    AP.add_argument("--morph_close", type=int, nargs=2, default=argparse.SUPPRESS, metavar=("TC", "AR"), help="close the class planes of the "
+                    "mask by an octagon of this radius in grid pixels (0: not for this class) on the device, nn.MaskMorphology: gaps of up to "
+                    "2 r pixels join.  Any --morph_* flag: datasets 'prediction_morph' and 'morph_counts', 'morphology' in the summary; the "
+                    "steps run in the order close, fill, open, and --event_filter and everything behind it take the cleaned mask")
+    AP.add_argument("--morph_fill", action="store_true", default=argparse.SUPPRESS, help="fill the holes of both classes: background that "
+                    "cannot reach a polar row without crossing the event")
+    AP.add_argument("--morph_open", type=int, nargs=2, default=argparse.SUPPRESS, metavar=("TC", "AR"), help="open the class planes by an "
+                    "octagon of this radius (0: not for this class): what is nowhere wider goes, necks included")
+    AP.add_argument("--morph_open_reconstruct", action="store_true", default=argparse.SUPPRESS, help="with --morph_open: the opening by "
+                    "reconstruction, which drops the same events whole and leaves every other event bit for bit")
     AP.add_argument("--event_filter", action="store_true", help="filter the classifier's mask by event size and shape on the device (the "
                     "--filter_* thresholds): dataset 'prediction_filtered', 'event_filter' in the summary; --events, --verify's prediction "
                     "side, --event_fields, --tracks, --track_fields, --climatology and --plots all take the FILTERED mask.  The labels "
@@ -789,10 +804,24 @@ def plot_name(base: str) -> str:
     return (base[:-3] if base.endswith(".h5") else base) + ".png"
 
 
+def morphology_options(pargs):
+    """None without a --morph_* flag, else the two step lists (class 1, class 2) of nn.MaskMorphology: close, fill, open"""
+    close, opened = getattr(pargs, "morph_close", (0, 0)), getattr(pargs, "morph_open", (0, 0))
+    fill, rec = bool(getattr(pargs, "morph_fill", False)), bool(getattr(pargs, "morph_open_reconstruct", False))
+    if not (any(close) or any(opened) or fill):
+        return None
+    MM = dnn.MaskMorphology
+    return tuple((MM.closing(c) if c else []) + ([("fill",)] if fill else []) +
+                 ((MM.opening_by_reconstruction(o) if rec else MM.opening(o)) if o else []) for c, o in zip(close, opened))
+
+
 class _HostSlot:
     def __init__(self, B: int, H: int, W: int, confidence: bool, event_cap: int = 0, pair_cap: int = 0, field_channels: int = 0,
                  plot_rows: int = 0, event_shape: bool = False, event_filter: bool = False, decision: bool = False, frame_skills=(),
-                 ensemble: bool = False, event_axis: bool = False, event_course: bool = False):
+                 ensemble: bool = False, event_axis: bool = False, event_course: bool = False, morphology: bool = False):
+        # --morph_*: the cleaned mask and the counts of nn.MaskMorphology
+        self.mmask = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if morphology else None
+        self.mcounts = torch.empty((B, 2, len(dnn.MORPH_COUNTS)), dtype=torch.int64).pin_memory() if morphology else None
         # --event_course: the course pixels, the rows and the status of nn.EventAxis(course=True)
         self.acourse = torch.empty((B, H, W), dtype=torch.uint8).pin_memory() if event_course else None
         self.crows = torch.empty((B, event_cap, len(dnn.EVENT_COURSE_FIELDS)), dtype=torch.int64).pin_memory() if event_course else None
@@ -891,6 +920,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                             extra["confidence_ensemble"] = slot.econf[j].numpy()
                     if slot.dmask is not None:
                         extra = dict(extra or {}, prediction_decided=slot.dmask[j].numpy(), decision=slot.dcounts[j].numpy())
+                    if slot.mmask is not None:
+                        extra = dict(extra or {}, prediction_morph=slot.mmask[j].numpy(), morph_counts=slot.mcounts[j].numpy())
                     if slot.fmask is not None:
                         extra = dict(extra or {}, prediction_filtered=slot.fmask[j].numpy())
                     frames = {key: t[j].numpy() for key, t in slot.frames.items()}
@@ -911,6 +942,8 @@ def _writer(work_q: "queue.Queue", free_q: "queue.Queue", out_dir: str, records:
                         rec["displacement_best"] = [[int(v) for v in row] for row in frames["displacement_best"].tolist()]
                     if slot.dcounts is not None:
                         rec["decision"] = [int(v) for v in slot.dcounts[j].tolist()]
+                    if slot.mcounts is not None:
+                        rec["morphology"] = [dict(zip(dnn.MORPH_COUNTS, (int(v) for v in row))) for row in slot.mcounts[j].tolist()]
                     if slot.fcounts is not None:
                         rec["event_filter"] = [dict(zip(dnn.EVENT_FILTER_COUNTS, (int(v) for v in row))) for row in slot.fcounts[j].tolist()]
                     if rows is not None:
@@ -974,6 +1007,9 @@ def main(pargs) -> dict:
     decide = None
     if decision is not None:
         decide = dnn.DecisionRule(B, H, W, connectivity=pargs.event_connectivity, device=device, **decision)
+    # --morph_*: the class planes closed, filled and opened; everything below, the filter included, takes the cleaned mask
+    morph_steps = morphology_options(pargs)
+    morph = dnn.MaskMorphology(B, H, W, morph_steps, device=device) if morph_steps is not None else None
     # --event_filter: the filter's own catalogue takes the mask as it arrives; everything below takes the filtered one
     efilter = None
     if getattr(pargs, "event_filter", False):
@@ -994,7 +1030,7 @@ def main(pargs) -> dict:
             ens_sign = torch.tensor([-1.0 if c in ens_options["negate"] else 1.0 for c in pargs.channels], dtype=torch.float32, device=device)
         ens_weights = [None if ens_options["margin"] == 1 else dnn.seam_weights(W, s, ens_options["margin"]) for s, _ in ens_options["views"]]
     predictor = dnn.Predictor(net, B, H, W, confidence=pargs.confidence,
-                              events=events and not verify and efilter is None and decide is None and ens is None,
+                              events=events and not verify and efilter is None and decide is None and ens is None and morph is None,
                               event_connectivity=pargs.event_connectivity)
     # --verify: the matcher's catalogue of the masks (its side a) is the source of `events`, so that no mask is catalogued twice
     matcher = dnn.EventMatcher(B, H, W, connectivity=pargs.event_connectivity, min_pixels=pargs.min_event_pixels,
@@ -1003,7 +1039,7 @@ def main(pargs) -> dict:
     predictor.store_logits = predictor.store_logits or decide is not None or ens is not None   # bf16 keeps the logits in registers unless asked
     if events and catalog is None:                # a pooled, decided or filtered mask without --verify: a catalogue of its own for it
         catalog = dnn.EventCatalog(B, H, W, connectivity=pargs.event_connectivity, device=device)
-    own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None)
+    own_catalog = events and not verify and (efilter is not None or decide is not None or ens is not None or morph is not None)
     event_cap = catalog.cap if events else 0
     eshape = dnn.EventShape(catalog) if getattr(pargs, "event_shape", False) else None
     eaxis = dnn.EventAxis(catalog, prune=axis_prune, course=axis_course) if getattr(pargs, "event_axis", False) else None
@@ -1079,7 +1115,7 @@ def main(pargs) -> dict:
     for _ in range(2):
         free_q.put(_HostSlot(B, H, W, pargs.confidence, event_cap, matcher.pair_cap if verify else 0, efields.C if efields else 0,
                              renderer.P * renderer.Ho if renderer else 0, eshape is not None, efilter is not None, decide is not None,
-                             frame_skills, ens is not None, eaxis is not None, eaxis is not None and axis_course))
+                             frame_skills, ens is not None, eaxis is not None, eaxis is not None and axis_course, morph is not None))
     records: list = []
     errors: list = []
     writer = threading.Thread(target=_writer, args=(work_q, free_q, pargs.output_dir, records, errors, pargs.min_event_pixels, field_bits),
@@ -1118,6 +1154,10 @@ def main(pargs) -> dict:
                 slot.dmask[:nv].copy_(decide(logits, n_valid=nv), non_blocking=True)
                 slot.dcounts[:nv].copy_(decide.counts(), non_blocking=True)
                 dmask = decide.mask_buffer
+            if morph is not None:
+                slot.mmask[:nv].copy_(morph(dmask, n_valid=nv).mask_buffer[:nv], non_blocking=True)
+                slot.mcounts[:nv].copy_(morph._counts[:nv], non_blocking=True)
+                dmask = morph.mask_buffer
             if efilter is not None:
                 slot.fmask[:nv].copy_(efilter(dmask, n_valid=nv), non_blocking=True)
                 slot.fcounts[:nv].copy_(efilter.counts(), non_blocking=True)
@@ -1212,6 +1252,9 @@ def main(pargs) -> dict:
         summary["ensemble"] = ensemble_summary(ens_options, ens_state)
     if decide is not None:
         summary["decision"] = decision_summary(decide, records)
+    if morph is not None:
+        summary["morphology"] = {"steps": [[list(step) for step in steps] for steps in morph.steps], "classes": [
+            {k: sum(r["morphology"][j][k] for r in records) for k in dnn.MORPH_COUNTS} for j in range(2)]}
     if efilter is not None:
         summary["event_filter"] = dict(efilter.thresholds(), classes=[
             {k: sum(r["event_filter"][j][k] for r in records) for k in dnn.EVENT_FILTER_COUNTS} for j in range(2)])
